@@ -39,6 +39,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -124,6 +125,35 @@ def cpu_baseline(c, flags_names, budget_s=12.0, p_cap=None):
         "encoded_loop_note": f"scalar loop on the encoded integer columns (ora_eval_encoded), {threads} threads, {P_e} pods",
         "host_cores": os.cpu_count(),
     }
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+DUMP_MAX_ROWS = 4096
+DUMP_SEED = 0x5EED0D
+
+
+def capture_outputs(torch, dev, bindings, mask, row0, n_nodes):
+    """--dump-outputs: what the last timed step handed its caller, copied to the host.  bindings: every pod's int32 binding (float64,
+    exact); feasible: a fixed, seeded sample of this rank's mask rows unpacked to 0/1 per node (float32, [rows, n_nodes]); feasible_rows:
+    the pod index of each sampled row (float64).  The sample depends only on the shape, so equal arguments give equal files."""
+    from kube_scheduler_rs_reference_amd import unpack_mask
+    out = {"bindings": bindings.cpu().numpy().astype(np.float64)}
+    if mask is not None and mask.shape[0] > 0 and n_nodes > 0:
+        n_loc = int(mask.shape[0])
+        left = DUMP_BUDGET_BYTES - out["bindings"].nbytes
+        k = max(1, min(n_loc, DUMP_MAX_ROWS, left // (4 * n_nodes + 8)))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_loc, size=k, replace=False))
+        words = mask[torch.from_numpy(rows).to(dev)].cpu().numpy().view(np.uint64)
+        out["feasible"] = unpack_mask(words, n_nodes).astype(np.float32)
+        out["feasible_rows"] = (rows + row0).astype(np.float64)
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def end_to_end(torch, L, Evaluator, dev, c, flag_names, pick, objects=True, reps=24):
@@ -433,7 +463,12 @@ def main():
                          "alternate: whole steps (ONE launch when the pick rides) + their all-gather on stream (slot mod 2)")
     ap.add_argument("--two-stream", action="store_true",
                     help="with --depth >= 2: mask kernels on one HIP stream, pick kernels (+ all-gather) on another (ksched_pipe)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the LAST timed step computed as DIR/<name>.npy: bindings.npy (float64, every pod), feasible.npy "
+                         "(float32 0/1, a fixed seeded sample of mask rows x nodes) and feasible_rows.npy (their pod indices); under 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started plainly (`python bench.py --gpus 8 ...`): become the launcher -- one process per GPU under torch.distributed.run on
@@ -761,6 +796,11 @@ def main():
         mt = torch.tensor([more], dtype=torch.int64, device=cdev)
         dist.all_reduce(mt, op=dist.ReduceOp.MAX)
         more = int(mt.item())
+    if args.dump_outputs:
+        # dumps are compared run against run: the untimed steps are rounded up to whole cycles of the input batches (and of the pipe's
+        # slots and the snapshot refreshes), so the last timed step sees the same batch and snapshot however long the clock ramp took
+        cycle = math.lcm(loop.n_inputs, depth * gather_every, 64 * args.refresh_every if args.refresh_every > 0 else 1)
+        more += -(args.warmup + 16 + more) % cycle
     if more:
         burst(more)
     ramp_steps = 16 + more
@@ -777,6 +817,10 @@ def main():
     elapsed = max_over_ranks(t_done - t0)
     region_split = {"launch_loop_us": (t_issued - t0) * 1e6, "closing_wait_us": (t_done - t_issued) * 1e6}
     bindings = (last.wait() if pipelined else last).clone()
+    dumped, dumped_batch = None, int(loop.last_batch)
+    if args.dump_outputs and rank == 0:  # (before the later regions overwrite the rotating buffers)
+        dumped = capture_outputs(torch, dev, bindings[:P_total] if bindings.numel() >= P_total else bindings,
+                                 None if args.no_mask else loop.masks[loop.last_mask], lo, N)
     # ---- self-check ("the driver-run bench asserts nothing"): what the LAST TIMED STEP wrote -- this rank's bindings, all of
     # them, and --parity-rows of its mask rows word for word -- against the oracle's scalar loop on the encoded columns (test
     # infrastructure, used here as the checker only; it never runs inside a timed region).  A mismatch is in the JSON line AND the exit code.
@@ -1116,6 +1160,8 @@ def main():
                          "mask_kernel_evals_per_s": (hi - lo) * N / avg_kernel_s if avg_kernel_s > 0 else 0.0},
         }
         out["parity_check"] = parity
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "input_batch": dumped_batch, "shapes": write_outputs(args.dump_outputs, dumped)}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(c, flag_names, p_cap=P_total)
         else:
