@@ -10,6 +10,8 @@
  *   ---------------------------------------------------  ------------------------------------------
  *   node_store snapshot + per-evaluation LIST            ksched_set_nodes   (columns of `available`)
  *     src/main.rs:56, src/predicates.rs:21-38            ksched_update_nodes (sparse rows, from watch events)
+ *   successful POST (src/main.rs:94-103) changes the     ksched_apply_bindings_device (the batch's bindings, on the device)
+ *     next evaluation's LIST; SubAssign src/util.rs:31-36
  *   can_pod_fit            src/predicates.rs:20-43       KSCHED_FIT   bit of ksched_eval*
  *   does_node_selector_match  src/predicates.rs:45-61    KSCHED_SEL   bit of ksched_eval*
  *   check_node_validity    src/predicates.rs:63-77       feasible = fit AND sel (+ fit mask for the reason)
@@ -50,7 +52,7 @@
 extern "C" {
 #endif
 
-#define KSCHED_ABI_VERSION 6u
+#define KSCHED_ABI_VERSION 7u
 
 /* at most this many label-key columns per batch */
 #define KSCHED_MAX_KEYS 32u
@@ -208,6 +210,43 @@ int ksched_set_nodes(ksched_ctx *ctx, uint32_t n, const int64_t *avail_cpu_milli
  */
 int ksched_update_nodes(ksched_ctx *ctx, uint32_t count, const uint32_t *node_index, const int64_t *avail_cpu_milli,
                         const int64_t *avail_mem_bytes);
+
+/* Apply a batch's bindings to the snapshot on the device: the step "bind -> shrink `available`" of the scheduler loop
+ * evaluate -> bind -> apply -> evaluate, without a host round trip (every successful POST, src/main.rs:94-103, changes what the
+ * next LIST of can_pod_fit sees, src/predicates.rs:27-38).  Device pointers, all of them [p]:
+ *   bindings      : node index per pod (what ksched_eval_device wrote; -1 = no node)
+ *   req_cpu_milli, req_mem_bytes : the pods' requests, as given to the evaluation
+ *   ok            : nonzero = the POST landed; NULL = every POST landed
+ *   status_out    : per-pod KSCHED_APPLY_* status, or NULL
+ * A pod is ELIGIBLE when 0 <= bindings[i] < ksched_num_nodes and (ok == NULL or ok[i] != 0).  For every node the new `available`
+ * is old - (sum of req) over the eligible ACCEPTED pods bound to it (old + sum with KSCHED_APPLY_RELEASE), per resource: SubAssign,
+ * src/util.rs:31-36.  Without KSCHED_APPLY_FIRST_PER_NODE every eligible pod is accepted; with it, per node only the lowest eligible
+ * pod index (one round of the no-over-commit rule of reconcile_batch_sequential); the others are DEFERRED and not applied.
+ * The sums are exact and independent of order; when either resource's result leaves int64 NEITHER resource of that node changes
+ * and every pod accepted onto it reports KSCHED_APPLY_OVERFLOW.  Same inputs, same bits, on every run.
+ * Status precedence: UNBOUND (binding < 0), BAD_NODE (binding >= n), NOT_OK, DEFERRED, then APPLIED or OVERFLOW.
+ * Ordering: everything is enqueued behind what `hip_stream` (a hipStream_t; NULL = default stream) already holds -- e.g. the evaluation
+ * that wrote `bindings` -- and the host does not wait.  Evaluations already enqueued on any stream this ctx knows read the snapshot as
+ * it was, evaluations enqueued afterwards (on any stream) and work enqueued on `hip_stream` afterwards (reading status_out) see the
+ * change; the change rides `hip_stream` itself when that is the one caller stream the ctx knows (KSCHED_OPT_SNAPSHOT_STREAM).
+ * The input arrays must stay unchanged until that point of `hip_stream`.  The fit part of the bitmap index is rebuilt for the touched
+ * 1024-node tiles only; the best-fit order is marked stale (the next KSCHED_PICK_BESTFIT request rebuilds it).
+ * Errors: KSCHED_E_STATE before ksched_set_nodes; KSCHED_E_INVAL for NULL required pointers or unknown flags; p == 0 is a no-op.
+ * If a HIP call fails midway the snapshot is invalidated (KSCHED_E_STATE until the next ksched_set_nodes). */
+#define KSCHED_APPLY_FIRST_PER_NODE 0x01u /* per node accept only the lowest pod index among the eligible pods */
+#define KSCHED_APPLY_RELEASE 0x02u        /* add the requests back instead of subtracting (pods deleted / unbound) */
+#define KSCHED_APPLY_APPLIED 0
+#define KSCHED_APPLY_UNBOUND 1   /* binding < 0: nothing to apply (no node found) */
+#define KSCHED_APPLY_NOT_OK 2    /* ok[p] == 0: the POST did not land (src/main.rs:103-108) */
+#define KSCHED_APPLY_DEFERRED 3  /* FIRST_PER_NODE: a lower pod index took this node in this call */
+#define KSCHED_APPLY_OVERFLOW 4  /* the node's new value would leave int64: node left unchanged */
+#define KSCHED_APPLY_BAD_NODE 5  /* binding >= ksched_num_nodes */
+int ksched_apply_bindings_device(ksched_ctx *ctx, uint32_t p, const int32_t *bindings, const int64_t *req_cpu_milli,
+                                 const int64_t *req_mem_bytes, const uint8_t *ok /* [p] or NULL = all landed */,
+                                 uint32_t flags, int32_t *status_out /* [p] or NULL */, void *hip_stream);
+/* Host-synchronous read-back of the device's current `available` columns for nodes [first, first + count), ordered behind every
+ * snapshot change enqueued so far (set, update, apply).  KSCHED_E_INVAL when the range exceeds ksched_num_nodes. */
+int ksched_read_nodes(ksched_ctx *ctx, uint32_t first, uint32_t count, int64_t *out_cpu_milli, int64_t *out_mem_bytes);
 
 /* The ctx remembers every stream a *_device evaluation was enqueued on (that is how snapshot changes are ordered against
  * them without a device-wide wait).  A caller that DESTROYS such a stream while the ctx lives must say so first; streams that

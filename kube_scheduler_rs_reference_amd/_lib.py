@@ -14,7 +14,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KSCHED_LIB") or os.path.join(_PKG_DIR, "libksched_hip.so")
 
 # --- constants mirrored from include/ksched.h --------------------------------------------------
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_KEYS = 32
 MAX_ATTEMPTS = 64
 SEL_NEVER = 0xFFFFFFFF
@@ -35,6 +35,15 @@ TAINT = 0x04
 PICK_SAMPLED = 0x08
 PICK_BESTFIT = 0x10
 WANT_FIT_MASK = 0x20
+
+APPLY_FIRST_PER_NODE = 0x01
+APPLY_RELEASE = 0x02
+APPLY_APPLIED = 0
+APPLY_UNBOUND = 1
+APPLY_NOT_OK = 2
+APPLY_DEFERRED = 3
+APPLY_OVERFLOW = 4
+APPLY_BAD_NODE = 5
 
 REASON_OK = 0
 REASON_NOT_ENOUGH_RESOURCES = 1
@@ -88,6 +97,8 @@ SYMBOLS = {
     "ksched_set_option": (C.c_int, [_vp, C.c_int, C.c_int64]),
     "ksched_set_nodes": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "ksched_update_nodes": (C.c_int, [_vp, _u32, _vp, _vp, _vp]),
+    "ksched_apply_bindings_device": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "ksched_read_nodes": (C.c_int, [_vp, _u32, _u32, _vp, _vp]),
     "ksched_forget_stream": (C.c_int, [_vp, _vp]),
     "ksched_num_nodes": (_u32, [_vp]),
     "ksched_num_keys": (_u32, [_vp]),

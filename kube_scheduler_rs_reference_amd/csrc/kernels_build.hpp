@@ -15,11 +15,14 @@
 //                         rows  = {n : lr[n] >= c}, c = 0..128: one wave ballot per (row, word)
 //   k_build_tile_named  grid tiles x 1024: valid row, taint subset rows (ballots), label (key, value) rows (LDS atomic OR)
 //   k_patch_nodes       ksched_update_nodes: scatter the new `available` values into the columns
+//   k_apply_*           ksched_apply_bindings_device: claim (first pod per node), accumulate (exact split sums per node),
+//                       commit (new values, overflow check, per dirty tile) and status; k_build_tile_fit then re-indexes the dirty tiles
 //   k_bf_*              best-fit order and its row bitmaps (built lazily, on the first PICK_BESTFIT after a change)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/ksched.h"
 #include "kernels_direct.hpp"
 #include "tile_index.hpp"
 
@@ -29,6 +32,7 @@ struct BuildFitArgs {
     const int64_t *ncpu, *nmem;  // node columns [n]
     uint64_t *tables, *aux;      // IndexedSnapshot::d_tables, d_aux
     const uint32_t *tile_list;   // tiles to (re)build, or nullptr = tile blockIdx.x
+    const uint32_t *dirty;       // [tiles + 1] or nullptr: with tile_list == nullptr, tile t is rebuilt only when dirty[t] == dirty[tiles]
     uint32_t n, rows, row_cpu;   // layout: rows per tile, first fit row of cpu (memory's follow kFitRows later)
 };
 
@@ -79,6 +83,7 @@ __global__ __launch_bounds__(1024) void k_build_tile_fit(const BuildFitArgs a) {
     __shared__ uint64_t s_wave[16];
     __shared__ uint64_t s_rows[kFitRows * kTileWords];
     const uint32_t tile = a.tile_list ? a.tile_list[blockIdx.x] : blockIdx.x;
+    if (a.dirty && a.dirty[tile] != a.dirty[gridDim.x]) return;  // (the whole block: before any barrier) a clean tile of an apply
     const uint32_t res = blockIdx.y;
     const int64_t *col = res == 0 ? a.ncpu : a.nmem;
     const uint32_t base = tile * kTileNodes;
@@ -277,6 +282,119 @@ __global__ __launch_bounds__(256) void k_patch_nodes(const PatchArgs a) {
     a.nmem[node] = m;
     a.nrec[(size_t)kNodeRecWords * node] = c;
     a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+}
+
+// ---- ksched_apply_bindings_device -----------------------------------------------------------------------------------------
+// available[node] -= (or +=) the sum of the requests of the eligible accepted pods bound to it, exactly.  Each request is split
+// into a signed high half h = req >> 32 and an unsigned low half l = req & 0xFFFFFFFF (req = h * 2^32 + l); the halves of both
+// resources are summed per node with 64-bit integer atomics (order-independent, so the sums are the same bits on every run).  With
+// fewer than 2^32 pods neither sum can wrap: |sum h| < 2^31 * 2^32 = 2^63 and sum l < 2^32 * 2^32 = 2^64.  The commit pass forms
+// old -/+ (sum h * 2^32 + sum l) in 128 bits and keeps the node unchanged when either resource leaves int64.
+//
+// Scratch (ksched_ctx, per node / per tile), all of it back in its idle state when a call's last pass has run:
+//   acc[4 * node]  : sum h cpu, sum l cpu, sum h mem, sum l mem -- idle 0; the commit pass zeroes what it read
+//   claim[node]    : lowest eligible pod index (FIRST_PER_NODE) -- idle 0xFFFFFFFF; the commit pass resets it
+//   ovf[node]      : 1 when the node's new values left int64 -- written by every commit of the node's tile, read only for nodes of that call
+//   dirty[tiles+1] : dirty[t] == dirty[tiles] (the call's generation) <=> tile t holds a node an accepted pod is bound to; never cleared
+constexpr uint32_t kApplyUnclaimed = 0xFFFFFFFFu;
+struct ApplyArgs {
+    const int32_t *bindings;
+    const int64_t *req_cpu, *req_mem;
+    const uint8_t *ok;    // [p] or nullptr = every POST landed
+    int32_t *status;      // [p] or nullptr
+    uint64_t *acc;        // [n][4]
+    uint32_t *claim;      // [n]
+    uint8_t *ovf;         // [n]
+    uint32_t *dirty;      // [tiles + 1]
+    int64_t *ncpu, *nmem, *nrec;
+    uint32_t p, n, tiles, gen;
+    uint32_t first_per_node, release;
+};
+
+__device__ __forceinline__ bool apply_eligible(const ApplyArgs &a, uint32_t i, int32_t b) {
+    return b >= 0 && (uint32_t)b < a.n && (!a.ok || a.ok[i] != 0);
+}
+
+// claim pass (FIRST_PER_NODE): per node the lowest eligible pod index
+__global__ __launch_bounds__(256) void k_apply_claim(const ApplyArgs a) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.p; i += gridDim.x * blockDim.x) {
+        const int32_t b = a.bindings[i];
+        if (apply_eligible(a, i, b)) atomicMin(a.claim + b, i);
+    }
+}
+
+__device__ __forceinline__ void acc_add(uint64_t *p, uint64_t v) {
+    if (v) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (a zero half adds nothing: no atomic)
+}
+
+// accumulate pass: the accepted pods' split requests into acc, their tiles marked dirty; every status but APPLIED / OVERFLOW is final here
+__global__ __launch_bounds__(256) void k_apply_accumulate(const ApplyArgs a) {
+    const uint32_t t0 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t0 == 0) a.dirty[a.tiles] = a.gen;
+    for (uint32_t i = t0; i < a.p; i += gridDim.x * blockDim.x) {
+        const int32_t b = a.bindings[i];
+        int32_t st;
+        if (b < 0) {
+            st = KSCHED_APPLY_UNBOUND;
+        } else if ((uint32_t)b >= a.n) {
+            st = KSCHED_APPLY_BAD_NODE;
+        } else if (a.ok && a.ok[i] == 0) {
+            st = KSCHED_APPLY_NOT_OK;
+        } else if (a.first_per_node && a.claim[b] != i) {
+            st = KSCHED_APPLY_DEFERRED;
+        } else {
+            st = KSCHED_APPLY_APPLIED;
+            const uint64_t c = (uint64_t)a.req_cpu[i], m = (uint64_t)a.req_mem[i];
+            uint64_t *q = a.acc + 4u * (size_t)b;
+            acc_add(q + 0, (uint64_t)((int64_t)c >> 32));
+            acc_add(q + 1, c & 0xFFFFFFFFull);
+            acc_add(q + 2, (uint64_t)((int64_t)m >> 32));
+            acc_add(q + 3, m & 0xFFFFFFFFull);
+            const uint32_t tile = (uint32_t)b / kTileNodes;
+            if (a.dirty[tile] != a.gen) a.dirty[tile] = a.gen;  // (plain store: every writer stores the same word)
+        }
+        if (a.status) a.status[i] = st;
+    }
+}
+
+// old -/+ (h * 2^32 + l) in 128 bits; false when the result leaves int64
+__device__ __forceinline__ bool apply_exact(int64_t old, uint64_t h, uint64_t l, bool release, int64_t *out) {
+    const __int128 s = (__int128)(int64_t)h * ((__int128)1 << 32) + (__int128)l;
+    const __int128 r = release ? (__int128)old + s : (__int128)old - s;
+    if (r < (__int128)INT64_MIN || r > (__int128)INT64_MAX) return false;
+    *out = (int64_t)r;
+    return true;
+}
+
+// commit pass: a block per tile, a thread per node; clean tiles exit at once
+__global__ __launch_bounds__(1024) void k_apply_commit(const ApplyArgs a) {
+    const uint32_t tile = blockIdx.x;
+    if (a.dirty[tile] != a.dirty[a.tiles]) return;
+    const uint32_t node = tile * kTileNodes + threadIdx.x;
+    if (node >= a.n) return;
+    uint64_t *q = a.acc + 4u * (size_t)node;
+    const uint64_t hc = q[0], lc = q[1], hm = q[2], lm = q[3];
+    if (a.first_per_node) a.claim[node] = kApplyUnclaimed;
+    if ((hc | lc | hm | lm) == 0ull) {  // nothing bound here (or requests of zero): unchanged
+        a.ovf[node] = 0;
+        return;
+    }
+    q[0] = q[1] = q[2] = q[3] = 0ull;
+    int64_t c, m;
+    const bool fits = apply_exact(a.ncpu[node], hc, lc, a.release, &c) && apply_exact(a.nmem[node], hm, lm, a.release, &m);
+    a.ovf[node] = fits ? 0 : 1;
+    if (!fits) return;
+    a.ncpu[node] = c;
+    a.nmem[node] = m;
+    a.nrec[(size_t)kNodeRecWords * node] = c;
+    a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+}
+
+// status pass: an accepted pod whose node overflowed reports OVERFLOW
+__global__ __launch_bounds__(256) void k_apply_status(const ApplyArgs a) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.p; i += gridDim.x * blockDim.x) {
+        if (a.status[i] == KSCHED_APPLY_APPLIED && a.ovf[a.bindings[i]]) a.status[i] = KSCHED_APPLY_OVERFLOW;
+    }
 }
 
 // node records (kernels_direct.hpp "Node records"): one 64-byte line per node for the candidate-testing picks

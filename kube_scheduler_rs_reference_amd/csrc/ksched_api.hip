@@ -88,6 +88,14 @@ struct ksched_ctx {
     DevBuf<int64_t> srt_k0[2], srt_k1[2];  // ping-pong sets of the best-fit orders' merge sort (kernels_build.hpp)
     DevBuf<uint32_t> srt_idx[2];
     IndexedSnapshot idx;  // per-tile bitmap index (tile_index.hpp), built on the device (kernels_build.hpp)
+    // ksched_apply_bindings_device (kernels_build.hpp "ksched_apply_bindings_device"): per-node scratch, idle between calls
+    DevBuf<uint64_t> apply_acc;   // [apply_n][4] split sums, idle 0
+    DevBuf<uint32_t> apply_claim; // [apply_n] lowest eligible pod index, idle 0xFFFFFFFF
+    DevBuf<uint8_t> apply_ovf;    // [apply_n]
+    DevBuf<uint32_t> apply_dirty; // [tiles of apply_n + 1] dirty-tile generations, initially 0
+    uint32_t apply_n = 0;         // nodes the scratch holds in its idle state (0 = not yet, or a failed call left it unknown)
+    uint32_t apply_gen = 0;       // generation of the latest call
+    hipEvent_t ev_apply = nullptr;  // the caller's stream, when the change rides another one
     std::string index_reason;  // why the snapshot has no bitmap index (the fused kernel is then not applicable)
     // host -> device staging for the snapshot calls: pinned, so the copies are asynchronous on the ctx's stream
     uint8_t *h_stage = nullptr;
@@ -373,7 +381,7 @@ int stage_reserve(ksched_ctx *c, size_t bytes, uint8_t **out) {
 // ---- index and best-fit build (kernels_build.hpp) --------------------------------------------------------------------
 
 // (re)build the fit part of the listed tiles (or of every tile: tiles == nullptr) on the ctx's stream
-int launch_build_fit(ksched_ctx *c, const uint32_t *d_tile_list, uint32_t count) {
+int launch_build_fit(ksched_ctx *c, const uint32_t *d_tile_list, uint32_t count, const uint32_t *d_dirty = nullptr) {
     const IndexedLayout &l = c->idx.lay;
     BuildFitArgs a{};
     a.ncpu = c->ncpu.ptr;
@@ -381,6 +389,7 @@ int launch_build_fit(ksched_ctx *c, const uint32_t *d_tile_list, uint32_t count)
     a.tables = c->idx.d_tables;
     a.aux = c->idx.d_aux;
     a.tile_list = d_tile_list;
+    a.dirty = d_tile_list ? nullptr : d_dirty;  // (every tile's block is launched; the clean ones exit at once)
     a.n = l.n;
     a.rows = l.rows;
     a.row_cpu = l.row_cpu;
@@ -1133,6 +1142,8 @@ void ksched_destroy(ksched_ctx *c) try {
         if (c->ev_build) (void)hipEventDestroy(c->ev_build);
         if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
         if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
+        if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
+        c->apply_acc.release(); c->apply_claim.release(); c->apply_ovf.release(); c->apply_dirty.release();
         indexed_release(c->idx);
         {  // masks the caller never handed back (ksched_mask_alloc)
             MaskRegistry &reg = mask_registry();
@@ -1419,6 +1430,111 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
     }
     c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
     if (int rc = snapshot_end(c)) return fail(rc);
+    return KSCHED_OK;
+} KSCHED_ABI_CATCH(c)
+
+int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
+                                 const uint8_t *ok, uint32_t flags, int32_t *status_out, void *hip_stream) try {
+    if (!c) return KSCHED_E_INVAL;
+    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE)) return KSCHED_E_INVAL;
+    if (p > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    if (p == 0) return KSCHED_OK;
+    DeviceGuard g(c->device);
+    if (!g.ok) return KSCHED_E_HIP;
+    fault_point(c);  // (nothing has changed yet)
+    const hipStream_t hs = (hipStream_t)hip_stream;
+    const uint32_t n = c->n, tiles = (n + kTileNodes - 1) / kTileNodes;
+    // evaluations already enqueued read the snapshot as it was (snapshot_begin); the change also waits for what `hs` holds (the
+    // evaluation that wrote `bindings`, typically) and `hs` waits for the change (the caller reads status_out there)
+    if (int rc = snapshot_begin(c)) return rc;
+    const hipStream_t s = c->change_stream;
+    auto fail = [&](int rc) {
+        c->have_nodes = false;  // columns, index and scratch may be half-updated: refuse evaluations until the next ksched_set_nodes
+        c->apply_n = 0;
+        return rc;
+    };
+    if (s != hs) {
+        if (!c->ev_apply && hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming) != hipSuccess) return fail(KSCHED_E_HIP);
+        if (hipEventRecord(c->ev_apply, hs) != hipSuccess || hipStreamWaitEvent(s, c->ev_apply, 0) != hipSuccess) return fail(KSCHED_E_HIP);
+    }
+    if (n > c->apply_n) {  // (re)allocate the scratch and put it in its idle state, once per snapshot size
+        c->apply_n = 0;
+        const uint32_t cap = std::max<uint32_t>(n, 1024u), cap_tiles = (cap + kTileNodes - 1) / kTileNodes;
+        if (c->apply_acc.reserve((size_t)cap * 4) != hipSuccess || c->apply_claim.reserve(cap) != hipSuccess ||
+            c->apply_ovf.reserve(cap) != hipSuccess || c->apply_dirty.reserve(cap_tiles + 1u) != hipSuccess)
+            return fail(KSCHED_E_NOMEM);
+        if (hipMemsetAsync(c->apply_acc.ptr, 0, (size_t)cap * 32, s) != hipSuccess ||
+            hipMemsetAsync(c->apply_claim.ptr, 0xFF, (size_t)cap * 4, s) != hipSuccess ||
+            hipMemsetAsync(c->apply_dirty.ptr, 0, (size_t)(cap_tiles + 1u) * 4, s) != hipSuccess)
+            return fail(KSCHED_E_HIP);
+        c->apply_n = cap;
+        c->apply_gen = 0;
+    }
+    if (++c->apply_gen == 0) c->apply_gen = 1;  // (0 is the initial value of every tile's entry)
+    ApplyArgs a{};
+    a.bindings = bindings;
+    a.req_cpu = req_cpu;
+    a.req_mem = req_mem;
+    a.ok = ok;
+    a.status = status_out;
+    a.acc = c->apply_acc.ptr;
+    a.claim = c->apply_claim.ptr;
+    a.ovf = c->apply_ovf.ptr;
+    a.dirty = c->apply_dirty.ptr;
+    a.ncpu = c->ncpu.ptr;
+    a.nmem = c->nmem.ptr;
+    a.nrec = c->nrec.ptr;
+    a.p = p;
+    a.n = n;
+    a.tiles = tiles;
+    a.gen = c->apply_gen;
+    a.first_per_node = (flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
+    a.release = (flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
+    const dim3 pod_grid(std::min<uint32_t>((p + 255u) / 256u, 2048u));
+    if (a.first_per_node) {
+        hipLaunchKernelGGL(k_apply_claim, pod_grid, dim3(256), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
+    }
+    hipLaunchKernelGGL(k_apply_accumulate, pod_grid, dim3(256), 0, s, a);
+    if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
+    if (tiles > 0) {
+        hipLaunchKernelGGL(k_apply_commit, dim3(tiles), dim3(kTileNodes), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
+        if (c->idx.built) {
+            // only the dirty tiles are re-indexed: every tile's block reads its generation and the clean ones exit
+            if (int rc = launch_build_fit(c, nullptr, 0, c->apply_dirty.ptr)) return fail(rc);
+        }
+        if (status_out) {
+            hipLaunchKernelGGL(k_apply_status, pod_grid, dim3(256), 0, s, a);
+            if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
+        }
+    }
+    c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
+    if (int rc = snapshot_end(c)) return fail(rc);
+    if (s != hs) {  // the caller's stream is behind the change by the event; it has then met this generation
+        if (hipStreamWaitEvent(hs, c->ev_build, 0) != hipSuccess) return fail(KSCHED_E_HIP);
+        if (hs == c->stream) c->own_gen = c->build_gen;
+        for (auto &u : c->user_streams)
+            if (u.s == hs) u.gen = c->build_gen;
+    }
+    return KSCHED_OK;
+} KSCHED_ABI_CATCH(c)
+
+int ksched_read_nodes(ksched_ctx *c, uint32_t first, uint32_t count, int64_t *out_cpu, int64_t *out_mem) try {
+    if (!c) return KSCHED_E_INVAL;
+    if (count > 0 && (!out_cpu || !out_mem)) return KSCHED_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    if ((uint64_t)first + count > c->n) return KSCHED_E_INVAL;
+    if (count == 0) return KSCHED_OK;
+    DeviceGuard g(c->device);
+    if (!g.ok) return KSCHED_E_HIP;
+    fault_point(c);
+    HIPCHK(c, hipEventSynchronize(c->ev_build));  // the latest snapshot change, whichever stream carried it
+    HIPCHK(c, hipMemcpy(out_cpu, c->ncpu.ptr + first, (size_t)count * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out_mem, c->nmem.ptr + first, (size_t)count * 8, hipMemcpyDeviceToHost));
     return KSCHED_OK;
 } KSCHED_ABI_CATCH(c)
 

@@ -173,6 +173,42 @@ class Evaluator:
             raise ValueError("node_index, avail_cpu_milli, avail_mem_bytes must be 1-D of one length")
         self._check(self._lib.ksched_update_nodes(self._h, idx.shape[0], _ptr(idx), _ptr(cpu), _ptr(mem)), "ksched_update_nodes")
 
+    def apply_bindings_device(self, bindings, req_cpu_milli, req_mem_bytes, ok=None, flags: int = 0, status_out=None, stream=None):
+        """Apply a batch's bindings to the snapshot on the device (ksched_apply_bindings_device): `available` of every node shrinks by the
+        requests of the eligible pods bound to it (grows with APPLY_RELEASE).  torch CUDA tensors on this evaluator's device, all [p]:
+        bindings int32, requests int64, ok uint8/bool or None (= every POST landed), status_out int32 or None.  Enqueued on `stream`
+        (default: torch's current stream) behind whatever wrote `bindings` there; the host does not wait."""
+        import torch
+        p = int(bindings.shape[0]) if bindings.dim() == 1 else -1
+
+        def dp(t, dtypes, name):
+            if t is None:
+                return None
+            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.dtype not in dtypes:
+                raise ValueError(f"{name}: expected a contiguous {dtypes} CUDA tensor on cuda:{self.device}")
+            if tuple(t.shape) != (p,):
+                raise ValueError(f"{name}: expected shape ({p},), got {tuple(t.shape)}")
+            return C.c_void_p(t.data_ptr())
+        if p < 0:
+            raise ValueError("bindings must be a 1-D int32 tensor")
+        args = (dp(bindings, (torch.int32,), "bindings"), dp(req_cpu_milli, (torch.int64,), "req_cpu_milli"),
+                dp(req_mem_bytes, (torch.int64,), "req_mem_bytes"), dp(ok, (torch.uint8, torch.bool), "ok"))
+        st = dp(status_out, (torch.int32,), "status_out")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rc = self._lib.ksched_apply_bindings_device(self._h, p, *args, int(flags), st, C.c_void_p(stream.cuda_stream))
+        self._check(rc, "ksched_apply_bindings_device")
+
+    def read_nodes(self, first: int = 0, count: Optional[int] = None):
+        """(cpu, mem) int64 numpy arrays: the device's current `available` columns for nodes [first, first + count), after every
+        snapshot change enqueued so far (ksched_read_nodes; waits for them)."""
+        if count is None:
+            count = max(self.n - int(first), 0)
+        cpu = np.empty((int(count),), dtype=np.int64)
+        mem = np.empty((int(count),), dtype=np.int64)
+        self._check(self._lib.ksched_read_nodes(self._h, int(first), int(count), _ptr(cpu), _ptr(mem)), "ksched_read_nodes")
+        return cpu, mem
+
     # -- evaluation, host buffers ------------------------------------------------------------------
     def eval(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, samples=None, flags: int = L.FIT,
              want_mask: bool = True, out: "EvalResult | None" = None) -> EvalResult:

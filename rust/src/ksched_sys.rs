@@ -17,7 +17,7 @@ pub struct ksched_comm {
     _private: [u8; 0],
 }
 
-pub const KSCHED_ABI_VERSION: u32 = 6;
+pub const KSCHED_ABI_VERSION: u32 = 7;
 pub const KSCHED_MAX_KEYS: u32 = 32;
 pub const KSCHED_MAX_ATTEMPTS: u32 = 64;
 pub const KSCHED_SEL_NEVER: u32 = 0xFFFF_FFFF;
@@ -38,6 +38,15 @@ pub const KSCHED_TAINT: u32 = 0x04;
 pub const KSCHED_PICK_SAMPLED: u32 = 0x08;
 pub const KSCHED_PICK_BESTFIT: u32 = 0x10;
 pub const KSCHED_WANT_FIT_MASK: u32 = 0x20;
+
+pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
+pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
+pub const KSCHED_APPLY_APPLIED: c_int = 0; // ksched_apply_bindings_device per-pod status
+pub const KSCHED_APPLY_UNBOUND: c_int = 1;
+pub const KSCHED_APPLY_NOT_OK: c_int = 2;
+pub const KSCHED_APPLY_DEFERRED: c_int = 3;
+pub const KSCHED_APPLY_OVERFLOW: c_int = 4;
+pub const KSCHED_APPLY_BAD_NODE: c_int = 5;
 
 pub const KSCHED_REASON_OK: c_int = 0;
 pub const KSCHED_REASON_NOT_ENOUGH_RESOURCES: c_int = 1; // InvalidNodeReason::NotEnoughResources   (src/predicates.rs:16)
@@ -82,6 +91,11 @@ extern "C" {
     pub fn ksched_update_nodes(
         ctx: *mut ksched_ctx, count: u32, node_index: *const u32, avail_cpu_milli: *const i64, avail_mem_bytes: *const i64,
     ) -> c_int;
+    pub fn ksched_apply_bindings_device(
+        ctx: *mut ksched_ctx, p: u32, bindings: *const i32, req_cpu_milli: *const i64, req_mem_bytes: *const i64, ok: *const u8,
+        flags: u32, status_out: *mut i32, hip_stream: *mut c_void,
+    ) -> c_int;
+    pub fn ksched_read_nodes(ctx: *mut ksched_ctx, first: u32, count: u32, out_cpu_milli: *mut i64, out_mem_bytes: *mut i64) -> c_int;
     pub fn ksched_forget_stream(ctx: *mut ksched_ctx, hip_stream: *mut c_void) -> c_int;
     pub fn ksched_num_nodes(ctx: *const ksched_ctx) -> u32;
     pub fn ksched_num_keys(ctx: *const ksched_ctx) -> u32;
@@ -178,6 +192,8 @@ pub fn symbol_table() -> Vec<(&'static str, usize)> {
         ("ksched_set_option", ksched_set_option as usize),
         ("ksched_set_nodes", ksched_set_nodes as usize),
         ("ksched_update_nodes", ksched_update_nodes as usize),
+        ("ksched_apply_bindings_device", ksched_apply_bindings_device as usize),
+        ("ksched_read_nodes", ksched_read_nodes as usize),
         ("ksched_forget_stream", ksched_forget_stream as usize),
         ("ksched_num_nodes", ksched_num_nodes as usize),
         ("ksched_num_keys", ksched_num_keys as usize),
@@ -243,6 +259,14 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_PICK_SAMPLED", KSCHED_PICK_SAMPLED as i64),
         ("KSCHED_PICK_BESTFIT", KSCHED_PICK_BESTFIT as i64),
         ("KSCHED_WANT_FIT_MASK", KSCHED_WANT_FIT_MASK as i64),
+        ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
+        ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
+        ("KSCHED_APPLY_APPLIED", KSCHED_APPLY_APPLIED as i64),
+        ("KSCHED_APPLY_UNBOUND", KSCHED_APPLY_UNBOUND as i64),
+        ("KSCHED_APPLY_NOT_OK", KSCHED_APPLY_NOT_OK as i64),
+        ("KSCHED_APPLY_DEFERRED", KSCHED_APPLY_DEFERRED as i64),
+        ("KSCHED_APPLY_OVERFLOW", KSCHED_APPLY_OVERFLOW as i64),
+        ("KSCHED_APPLY_BAD_NODE", KSCHED_APPLY_BAD_NODE as i64),
         ("KSCHED_REASON_OK", KSCHED_REASON_OK as i64),
         ("KSCHED_REASON_NOT_ENOUGH_RESOURCES", KSCHED_REASON_NOT_ENOUGH_RESOURCES as i64),
         ("KSCHED_REASON_NODE_SELECTOR_MISMATCH", KSCHED_REASON_NODE_SELECTOR_MISMATCH as i64),
