@@ -482,6 +482,39 @@ int ksched_allgather_bindings_local(ksched_comm *const *comms, int n, const int3
 /* text of the calling thread's last RCCL failure (empty string if none) */
 const char *ksched_comm_last_error(void);
 
+/* Keep the replicated snapshots in step: apply a row-sharded batch's bindings on every rank (ksched_apply_bindings_device over the
+ * whole batch, with each rank holding only its own rows).  Added in ABI 7 without a version change: detect them by symbol.
+ *   per-process form : every rank of `comm` calls ksched_apply_bindings_sharded with its ctx (comm was created for it)
+ *   one-process form : ksched_apply_bindings_sharded_local(ctxs, comms, n, ...): ctxs[i] and comms[i] belong to one device
+ *                      (ksched_comm_create_local); the per-rank arguments are arrays [n]; ok, status_out, hip_streams may be NULL
+ *                      (and entries of ok / status_out NULL), hip_streams NULL = every rank's default stream.
+ * Rank r passes `count` pods, rows [row_lo, row_lo + count) of the batch: bindings, requests, ok and status_out as in
+ * ksched_apply_bindings_device, device pointers on its device.  bindings may be the rank's part of ksched_gather_buffer or its
+ * ksched_eval_device output; padding entries of -1 are UNBOUND.  Pod i of rank r is global pod row_lo + i (the "lowest pod index"
+ * of KSCHED_APPLY_FIRST_PER_NODE); row_lo + count must not exceed 0xFFFFFFFF and the ranks' rows must not overlap.
+ * After the call every rank's snapshot -- `available`, node records, bitmap index (ksched_index_checksum) -- is what ONE ctx gets
+ * from ksched_apply_bindings_device over the concatenation of all ranks' rows, and rank r's status_out is that call's status of its
+ * rows.  Flags, statuses, the exactness and the overflow rule are those of ksched_apply_bindings_device.  Every rank's snapshot must
+ * hold the same nodes (the one-process form checks the count).
+ * Unlike ksched_apply_bindings_device's p == 0 no-op, a rank with count == 0 STILL JOINS: it takes part in the collectives and applies
+ * the other ranks' pods.  Each rank exchanges its per-node claims (FIRST_PER_NODE only, 4 B per node) and its per-node partial sums
+ * (32 B per node) with one all-gather each, enqueued on the stream that carries its change.
+ * Ordering: that of ksched_apply_bindings_device, per rank (behind what `hip_stream` holds, ahead of what is enqueued after; the host
+ * does not wait).
+ * Errors: KSCHED_E_INVAL for NULL handles or required pointers, a ctx and comm on different devices, unknown flags, an aborted comm,
+ * a clique that is not complete (one-process form: every rank once), snapshots of different node counts (one-process form);
+ * KSCHED_E_STATE when a ctx has no snapshot.  A failed collective returns KSCHED_E_RCCL (ksched_comm_last_error): the clique is
+ * aborted as in ksched_allgather_bindings_local, and every ctx that entered the call loses its snapshot (KSCHED_E_STATE until its
+ * next ksched_set_nodes), since the replicas may no longer agree.  A rank of the per-process form that fails before its collectives
+ * leaves its peers waiting in them, as any RCCL rank that drops out does. */
+int ksched_apply_bindings_sharded(ksched_ctx *ctx, ksched_comm *comm, uint32_t count, uint32_t row_lo, const int32_t *bindings,
+                                  const int64_t *req_cpu_milli, const int64_t *req_mem_bytes, const uint8_t *ok /* [count] or NULL */,
+                                  uint32_t flags, int32_t *status_out /* [count] or NULL */, void *hip_stream);
+int ksched_apply_bindings_sharded_local(ksched_ctx *const *ctxs, ksched_comm *const *comms, int n, const uint32_t *count,
+                                        const uint32_t *row_lo, const int32_t *const *bindings, const int64_t *const *req_cpu_milli,
+                                        const int64_t *const *req_mem_bytes, const uint8_t *const *ok /* NULL or [n], entries may be NULL */,
+                                        uint32_t flags, int32_t *const *status_out /* NULL or [n] */, void *const *hip_streams);
+
 /* ---- measurement --------------------------------------------------------------------------
  * With KSCHED_OPT_TIMING = 1 every ksched_eval* brackets its mask kernel with hipEvents on the
  * launch stream.  ksched_kernel_time_ms synchronises those events and returns the accumulated

@@ -131,6 +131,8 @@ SYMBOLS = {
     "ksched_comm_size": (C.c_int, [_vp]),
     "ksched_allgather_bindings": (C.c_int, [_vp, _vp, _vp, _u32, _vp]),
     "ksched_allgather_bindings_local": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, _vp]),
+    "ksched_apply_bindings_sharded": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "ksched_apply_bindings_sharded_local": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "ksched_comm_last_error": (C.c_char_p, []),
     "ksched_kernel_time_ms": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "ksched_kernel_time_samples": (C.c_int, [_vp, _vp, _u32]),

@@ -17,6 +17,9 @@
 //   k_patch_nodes       ksched_update_nodes: scatter the new `available` values into the columns
 //   k_apply_*           ksched_apply_bindings_device: claim (first pod per node), accumulate (exact split sums per node),
 //                       commit (new values, overflow check, per dirty tile) and status; k_build_tile_fit then re-indexes the dirty tiles
+//   k_apply_claim_merge, k_apply_commit_gathered
+//                       ksched_apply_bindings_sharded*: the same passes over one rank's rows, with the per-node claims and partial sums
+//                       of every rank all-gathered and merged before the commit (ksched_api.hip "multi-GPU")
 //   k_bf_*              best-fit order and its row bitmaps (built lazily, on the first PICK_BESTFIT after a change)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -309,6 +312,10 @@ struct ApplyArgs {
     int64_t *ncpu, *nmem, *nrec;
     uint32_t p, n, tiles, gen;
     uint32_t first_per_node, release;
+    uint32_t row_lo;   // global index of pod 0 (the rank's first row of a sharded apply; 0 otherwise): the claim compares global indexes
+    uint32_t sharded;  // 1: the accumulate pass marks no tiles, k_apply_commit_gathered decides them from every rank's sums
+    const uint64_t *gathered;  // sharded: [nranks][n][4] every rank's acc, or [nranks][n] uint32 claims for k_apply_claim_merge
+    uint32_t nranks, rank;
 };
 
 __device__ __forceinline__ bool apply_eligible(const ApplyArgs &a, uint32_t i, int32_t b) {
@@ -319,7 +326,7 @@ __device__ __forceinline__ bool apply_eligible(const ApplyArgs &a, uint32_t i, i
 __global__ __launch_bounds__(256) void k_apply_claim(const ApplyArgs a) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.p; i += gridDim.x * blockDim.x) {
         const int32_t b = a.bindings[i];
-        if (apply_eligible(a, i, b)) atomicMin(a.claim + b, i);
+        if (apply_eligible(a, i, b)) atomicMin(a.claim + b, a.row_lo + i);
     }
 }
 
@@ -330,7 +337,7 @@ __device__ __forceinline__ void acc_add(uint64_t *p, uint64_t v) {
 // accumulate pass: the accepted pods' split requests into acc, their tiles marked dirty; every status but APPLIED / OVERFLOW is final here
 __global__ __launch_bounds__(256) void k_apply_accumulate(const ApplyArgs a) {
     const uint32_t t0 = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t0 == 0) a.dirty[a.tiles] = a.gen;
+    if (t0 == 0 && !a.sharded) a.dirty[a.tiles] = a.gen;
     for (uint32_t i = t0; i < a.p; i += gridDim.x * blockDim.x) {
         const int32_t b = a.bindings[i];
         int32_t st;
@@ -340,7 +347,7 @@ __global__ __launch_bounds__(256) void k_apply_accumulate(const ApplyArgs a) {
             st = KSCHED_APPLY_BAD_NODE;
         } else if (a.ok && a.ok[i] == 0) {
             st = KSCHED_APPLY_NOT_OK;
-        } else if (a.first_per_node && a.claim[b] != i) {
+        } else if (a.first_per_node && a.claim[b] != a.row_lo + i) {
             st = KSCHED_APPLY_DEFERRED;
         } else {
             st = KSCHED_APPLY_APPLIED;
@@ -351,7 +358,7 @@ __global__ __launch_bounds__(256) void k_apply_accumulate(const ApplyArgs a) {
             acc_add(q + 2, (uint64_t)((int64_t)m >> 32));
             acc_add(q + 3, m & 0xFFFFFFFFull);
             const uint32_t tile = (uint32_t)b / kTileNodes;
-            if (a.dirty[tile] != a.gen) a.dirty[tile] = a.gen;  // (plain store: every writer stores the same word)
+            if (!a.sharded && a.dirty[tile] != a.gen) a.dirty[tile] = a.gen;  // (plain store: every writer stores the same word)
         }
         if (a.status) a.status[i] = st;
     }
@@ -388,6 +395,62 @@ __global__ __launch_bounds__(1024) void k_apply_commit(const ApplyArgs a) {
     a.nmem[node] = m;
     a.nrec[(size_t)kNodeRecWords * node] = c;
     a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+}
+
+// ---- ksched_apply_bindings_sharded*: the per-node scratch of every rank, all-gathered --------------------------------------------
+// Rank r passes its own rows only.  The claim pass above writes the lowest GLOBAL pod index per node into claim; the claims of all
+// ranks are all-gathered and their minimum is the claim of the concatenated batch.  The accumulate pass then sums the rank's accepted
+// pods into acc; every rank's acc is all-gathered and the commit below adds the nranks partial sums per node.  The halves are integers
+// summed modulo 2^64 with the true values in range (fewer than 2^32 pods in all), so any order of the additions gives the bits one ctx's
+// atomics give over the whole batch.  Every rank merges the same gathered data, so the dirty-tile decision is the same on every rank.
+
+// per node the minimum of the ranks' claims (a grid-stride loop over nodes; the gathered table is [nranks][n] uint32)
+__global__ __launch_bounds__(256) void k_apply_claim_merge(const ApplyArgs a) {
+    const uint32_t *g = reinterpret_cast<const uint32_t *>(a.gathered);
+    for (uint32_t node = blockIdx.x * blockDim.x + threadIdx.x; node < a.n; node += gridDim.x * blockDim.x) {
+        uint32_t m = kApplyUnclaimed;
+        for (uint32_t r = 0; r < a.nranks; ++r) m = min(m, g[(size_t)r * a.n + node]);
+        if (m != a.claim[node]) a.claim[node] = m;
+    }
+}
+
+// commit pass of a sharded apply: a block per tile, a thread per node; every tile runs (the merged sums decide which ones change).  It
+// also returns the rank's scratch to its idle state: acc zeroed where this rank wrote, claim reset.
+__global__ __launch_bounds__(1024) void k_apply_commit_gathered(const ApplyArgs a) {
+    const uint32_t tile = blockIdx.x;
+    const uint32_t node = tile * kTileNodes + threadIdx.x;
+    if (tile == 0 && threadIdx.x == 0) a.dirty[a.tiles] = a.gen;
+    bool changed = false;
+    if (node < a.n) {
+        uint64_t hc = 0, lc = 0, hm = 0, lm = 0;
+        for (uint32_t r = 0; r < a.nranks; ++r) {
+            const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(a.gathered + 4u * ((size_t)r * a.n + node));
+            const ulonglong2 c = q[0], m = q[1];
+            hc += c.x;
+            lc += c.y;
+            hm += m.x;
+            lm += m.y;
+            if (r == a.rank && (c.x | c.y | m.x | m.y) != 0ull) {  // this rank's own part: its acc goes back to zero
+                uint64_t *mine = a.acc + 4u * (size_t)node;
+                mine[0] = mine[1] = mine[2] = mine[3] = 0ull;
+            }
+        }
+        if (a.first_per_node && a.claim[node] != kApplyUnclaimed) a.claim[node] = kApplyUnclaimed;
+        bool fits = true;
+        if ((hc | lc | hm | lm) != 0ull) {
+            int64_t c, m;
+            fits = apply_exact(a.ncpu[node], hc, lc, a.release, &c) && apply_exact(a.nmem[node], hm, lm, a.release, &m);
+            if (fits) {
+                a.ncpu[node] = c;
+                a.nmem[node] = m;
+                a.nrec[(size_t)kNodeRecWords * node] = c;
+                a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+                changed = true;
+            }
+        }
+        a.ovf[node] = fits ? 0 : 1;
+    }
+    if (__syncthreads_or(changed) && threadIdx.x == 0) a.dirty[tile] = a.gen;
 }
 
 // status pass: an accepted pod whose node overflowed reports OVERFLOW

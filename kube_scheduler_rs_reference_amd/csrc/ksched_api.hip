@@ -93,6 +93,7 @@ struct ksched_ctx {
     DevBuf<uint32_t> apply_claim; // [apply_n] lowest eligible pod index, idle 0xFFFFFFFF
     DevBuf<uint8_t> apply_ovf;    // [apply_n]
     DevBuf<uint32_t> apply_dirty; // [tiles of apply_n + 1] dirty-tile generations, initially 0
+    DevBuf<uint64_t> apply_gath;  // ksched_apply_bindings_sharded*: every rank's acc [nranks][n][4] (or claims [nranks][n] uint32)
     uint32_t apply_n = 0;         // nodes the scratch holds in its idle state (0 = not yet, or a failed call left it unknown)
     uint32_t apply_gen = 0;       // generation of the latest call
     hipEvent_t ev_apply = nullptr;  // the caller's stream, when the change rides another one
@@ -1143,7 +1144,7 @@ void ksched_destroy(ksched_ctx *c) try {
         if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
         if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
         if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
-        c->apply_acc.release(); c->apply_claim.release(); c->apply_ovf.release(); c->apply_dirty.release();
+        c->apply_acc.release(); c->apply_claim.release(); c->apply_ovf.release(); c->apply_dirty.release(); c->apply_gath.release();
         indexed_release(c->idx);
         {  // masks the caller never handed back (ksched_mask_alloc)
             MaskRegistry &reg = mask_registry();
@@ -1433,6 +1434,33 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
     return KSCHED_OK;
 } KSCHED_ABI_CATCH(c)
 
+}  // extern "C"
+
+namespace {
+// the apply scratch of ksched_apply_bindings_device / _sharded*, in its idle state for the ctx's node count, and the next generation;
+// the (re)allocation and its memsets run once per snapshot size, on `s`
+int apply_scratch_ready(ksched_ctx *c, hipStream_t s) {
+    const uint32_t n = c->n;
+    if (n > c->apply_n) {
+        c->apply_n = 0;
+        const uint32_t cap = std::max<uint32_t>(n, 1024u), cap_tiles = (cap + kTileNodes - 1) / kTileNodes;
+        if (c->apply_acc.reserve((size_t)cap * 4) != hipSuccess || c->apply_claim.reserve(cap) != hipSuccess ||
+            c->apply_ovf.reserve(cap) != hipSuccess || c->apply_dirty.reserve(cap_tiles + 1u) != hipSuccess)
+            return KSCHED_E_NOMEM;
+        if (hipMemsetAsync(c->apply_acc.ptr, 0, (size_t)cap * 32, s) != hipSuccess ||
+            hipMemsetAsync(c->apply_claim.ptr, 0xFF, (size_t)cap * 4, s) != hipSuccess ||
+            hipMemsetAsync(c->apply_dirty.ptr, 0, (size_t)(cap_tiles + 1u) * 4, s) != hipSuccess)
+            return KSCHED_E_HIP;
+        c->apply_n = cap;
+        c->apply_gen = 0;
+    }
+    if (++c->apply_gen == 0) c->apply_gen = 1;  // (0 is the initial value of every tile's entry)
+    return KSCHED_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
                                  const uint8_t *ok, uint32_t flags, int32_t *status_out, void *hip_stream) try {
     if (!c) return KSCHED_E_INVAL;
@@ -1459,20 +1487,7 @@ int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindi
         if (!c->ev_apply && hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming) != hipSuccess) return fail(KSCHED_E_HIP);
         if (hipEventRecord(c->ev_apply, hs) != hipSuccess || hipStreamWaitEvent(s, c->ev_apply, 0) != hipSuccess) return fail(KSCHED_E_HIP);
     }
-    if (n > c->apply_n) {  // (re)allocate the scratch and put it in its idle state, once per snapshot size
-        c->apply_n = 0;
-        const uint32_t cap = std::max<uint32_t>(n, 1024u), cap_tiles = (cap + kTileNodes - 1) / kTileNodes;
-        if (c->apply_acc.reserve((size_t)cap * 4) != hipSuccess || c->apply_claim.reserve(cap) != hipSuccess ||
-            c->apply_ovf.reserve(cap) != hipSuccess || c->apply_dirty.reserve(cap_tiles + 1u) != hipSuccess)
-            return fail(KSCHED_E_NOMEM);
-        if (hipMemsetAsync(c->apply_acc.ptr, 0, (size_t)cap * 32, s) != hipSuccess ||
-            hipMemsetAsync(c->apply_claim.ptr, 0xFF, (size_t)cap * 4, s) != hipSuccess ||
-            hipMemsetAsync(c->apply_dirty.ptr, 0, (size_t)(cap_tiles + 1u) * 4, s) != hipSuccess)
-            return fail(KSCHED_E_HIP);
-        c->apply_n = cap;
-        c->apply_gen = 0;
-    }
-    if (++c->apply_gen == 0) c->apply_gen = 1;  // (0 is the initial value of every tile's entry)
+    if (int rc = apply_scratch_ready(c, s)) return fail(rc);
     ApplyArgs a{};
     a.bindings = bindings;
     a.req_cpu = req_cpu;
@@ -2229,6 +2244,45 @@ int comm_caught(int code, const char *what) noexcept {
 }  // namespace
 
 const char *ksched_comm_last_error(void) { return g_comm_error.c_str(); }
+}  // extern "C"
+
+namespace {
+// One all-gather over comms[0..n) in ncclGroupStart/End (send[i], recv[i], streams[i] belong to comms[i]; streams == nullptr: default
+// streams).  If any call or the group's end fails the collective is at best half issued: ranks that did enqueue it would wait for the
+// others for ever, and whoever then synchronises their stream hangs with them.  The whole clique is given up -- ncclCommAbort takes its
+// outstanding work down -- and the handles are left empty: every later call with them fails with KSCHED_E_INVAL, ksched_comm_destroy
+// still frees them.
+int group_allgather(ksched_comm *const *comms, int n, const void *const *send, void *const *recv, size_t count, ncclDataType_t type,
+                    void *const *streams, const char *what) {
+    RcclApi &api = rccl_api();
+    if (!api.ok) return comm_unavailable();
+    // one process drives every device: the per-device calls of one collective must be fused in a group
+    ncclResult_t r = api.GroupStart();
+    if (r != ncclSuccess) return comm_fail("ncclGroupStart", r);
+    ncclResult_t first = ncclSuccess;
+    for (int i = 0; i < n; ++i) {
+        DeviceGuard g(comms[i]->device);
+        r = api.AllGather(send[i], recv[i], count, type, comms[i]->comm, streams ? (hipStream_t)streams[i] : nullptr);
+        if (r != ncclSuccess && first == ncclSuccess) first = r;
+    }
+    r = api.GroupEnd();
+    if (first != ncclSuccess || r != ncclSuccess) {
+        for (int i = 0; i < n; ++i) {
+            DeviceGuard g(comms[i]->device);
+            if (api.CommAbort) (void)api.CommAbort(comms[i]->comm);
+            else (void)api.CommDestroy(comms[i]->comm);
+            comms[i]->comm = nullptr;
+        }
+        const int rc = first != ncclSuccess ? comm_fail(what, first) : comm_fail("ncclGroupEnd", r);
+        g_comm_error += " -- the communicator clique has been aborted; create a new one";
+        return rc;
+    }
+    return KSCHED_OK;
+}
+}  // namespace
+
+extern "C" {
+
 
 int ksched_comm_unique_id(uint8_t *id) try {
     if (!id) return KSCHED_E_INVAL;
@@ -2329,33 +2383,238 @@ int ksched_allgather_bindings_local(ksched_comm *const *comms, int n, const int3
     for (int i = 0; i < n; ++i)
         if (!comms[i] || !comms[i]->comm || (count_per_rank > 0 && (!local[i] || !gathered[i]))) return KSCHED_E_INVAL;
     if (count_per_rank == 0) return KSCHED_OK;
-    RcclApi &api = rccl_api();
-    if (!api.ok) return comm_unavailable();
-    // one process drives every device: the per-device calls of one collective must be fused in a group
-    ncclResult_t r = api.GroupStart();
-    if (r != ncclSuccess) return comm_fail("ncclGroupStart", r);
-    ncclResult_t first = ncclSuccess;
-    for (int i = 0; i < n; ++i) {
-        DeviceGuard g(comms[i]->device);
-        r = api.AllGather(local[i], gathered[i], count_per_rank, ncclInt32, comms[i]->comm, hip_streams ? (hipStream_t)hip_streams[i] : nullptr);
-        if (r != ncclSuccess && first == ncclSuccess) first = r;
+    std::vector<const void *> send(local, local + n);
+    std::vector<void *> recv(gathered, gathered + n);
+    return group_allgather(comms, n, send.data(), recv.data(), count_per_rank, ncclInt32, hip_streams, "ncclAllGather");
+} KSCHED_ABI_CATCH_COMM
+
+}  // extern "C"
+
+// ---- multi-GPU: a sharded batch's bindings applied to every replica (kernels_build.hpp "ksched_apply_bindings_sharded*") ----------
+// Per rank: claim (FIRST_PER_NODE) -> all-gather of claim[n] -> per-node minimum -> accumulate of the rank's rows -> all-gather of
+// acc[n][4] -> commit of the merged sums -> re-index of the dirty tiles -> status of the rank's rows.  Everything of one rank rides
+// its ctx's change stream; the all-gathers are enqueued there too.  The one-process form runs each phase for every rank before the
+// collective that joins them, so the per-device calls of a collective are issued together in one group.
+namespace {
+
+struct ShardedApply {
+    ksched_ctx *c = nullptr;
+    ksched_comm *q = nullptr;
+    hipStream_t hs = nullptr;  // the caller's stream
+    ApplyArgs a{};
+    uint32_t count = 0;
+    bool entered = false;      // snapshot_begin ran: a failure from here on invalidates the snapshot
+};
+
+// a failure of any rank after some rank's snapshot has started to change leaves the replicas possibly different: every ctx that
+// entered the call refuses evaluations until its next ksched_set_nodes
+struct ShardedInvalidate {
+    std::vector<ShardedApply> &v;
+    bool done = false;
+    ~ShardedInvalidate() {
+        if (done) return;
+        for (ShardedApply &x : v)
+            if (x.entered) {
+                x.c->have_nodes = false;
+                x.c->apply_n = 0;
+            }
     }
-    r = api.GroupEnd();
-    if (first != ncclSuccess || r != ncclSuccess) {
-        // The collective is at best half issued: ranks that did enqueue it would wait for the others for ever, and whoever then
-        // synchronises their stream hangs with them.  Give the whole clique up -- ncclCommAbort takes its outstanding work down --
-        // and leave the handles empty: every later call with them fails with KSCHED_E_INVAL, ksched_comm_destroy still frees them.
-        for (int i = 0; i < n; ++i) {
-            DeviceGuard g(comms[i]->device);
-            if (api.CommAbort) (void)api.CommAbort(comms[i]->comm);
-            else (void)api.CommDestroy(comms[i]->comm);
-            comms[i]->comm = nullptr;
-        }
-        const int rc = first != ncclSuccess ? comm_fail("ncclAllGather", first) : comm_fail("ncclGroupEnd", r);
-        g_comm_error += " -- the communicator clique has been aborted; create a new one";
-        return rc;
+};
+
+dim3 pod_grid(uint32_t p) { return dim3(std::min<uint32_t>((p + 255u) / 256u, 2048u)); }
+
+// argument checks of one rank that need no lock and no device
+int sharded_check(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu,
+                  const int64_t *req_mem, uint32_t flags) {
+    if (!c || !q || !q->comm) return KSCHED_E_INVAL;
+    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE)) return KSCHED_E_INVAL;
+    if (count > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
+    if ((uint64_t)row_lo + count > (uint64_t)kApplyUnclaimed) return KSCHED_E_INVAL;  // global pod indexes stay below the idle claim
+    if (q->device != c->device) return KSCHED_E_INVAL;
+    return KSCHED_OK;
+}
+
+// phase 1 (the ctx's mutex held, its device current): order the change, ready the scratch, claim the rank's rows
+int sharded_begin(ShardedApply &x, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
+                  const uint8_t *ok, uint32_t flags, int32_t *status_out) {
+    ksched_ctx *c = x.c;
+    fault_point(c);  // (nothing has changed yet)
+    if (int rc = snapshot_begin(c)) return rc;
+    x.entered = true;
+    const hipStream_t s = c->change_stream;
+    if (s != x.hs) {
+        if (!c->ev_apply) HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_apply, x.hs));
+        HIPCHK(c, hipStreamWaitEvent(s, c->ev_apply, 0));
+    }
+    if (int rc = apply_scratch_ready(c, s)) return rc;
+    const uint32_t n = c->n;
+    if (c->apply_gath.reserve((size_t)x.q->nranks * n * 4) != hipSuccess) return KSCHED_E_NOMEM;
+    ApplyArgs &a = x.a;
+    a.bindings = bindings;
+    a.req_cpu = req_cpu;
+    a.req_mem = req_mem;
+    a.ok = ok;
+    a.status = status_out;
+    a.acc = c->apply_acc.ptr;
+    a.claim = c->apply_claim.ptr;
+    a.ovf = c->apply_ovf.ptr;
+    a.dirty = c->apply_dirty.ptr;
+    a.ncpu = c->ncpu.ptr;
+    a.nmem = c->nmem.ptr;
+    a.nrec = c->nrec.ptr;
+    a.p = x.count;
+    a.n = n;
+    a.tiles = (n + kTileNodes - 1) / kTileNodes;
+    a.gen = c->apply_gen;
+    a.first_per_node = (flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
+    a.release = (flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
+    a.row_lo = row_lo;
+    a.sharded = 1;
+    a.gathered = c->apply_gath.ptr;
+    a.nranks = (uint32_t)x.q->nranks;
+    a.rank = (uint32_t)x.q->rank;
+    if (a.first_per_node && x.count > 0 && n > 0) {
+        hipLaunchKernelGGL(k_apply_claim, pod_grid(x.count), dim3(256), 0, s, a);
+        HIPCHK(c, hipGetLastError());
     }
     return KSCHED_OK;
+}
+
+// phase 2 (FIRST_PER_NODE, after the claims' all-gather): the batch's claim per node; then the rank's accumulate pass
+int sharded_accumulate(ShardedApply &x) {
+    ksched_ctx *c = x.c;
+    const hipStream_t s = c->change_stream;
+    if (x.a.first_per_node && x.a.n > 0) {
+        hipLaunchKernelGGL(k_apply_claim_merge, dim3(std::min<uint32_t>((x.a.n + 255u) / 256u, 1024u)), dim3(256), 0, s, x.a);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (x.count > 0) {
+        hipLaunchKernelGGL(k_apply_accumulate, pod_grid(x.count), dim3(256), 0, s, x.a);
+        HIPCHK(c, hipGetLastError());
+    }
+    return KSCHED_OK;
+}
+
+// phase 3 (after the partial sums' all-gather): commit, re-index, status; the caller's stream waits for the change
+int sharded_finish(ShardedApply &x) {
+    ksched_ctx *c = x.c;
+    const hipStream_t s = c->change_stream;
+    if (x.a.tiles > 0) {
+        hipLaunchKernelGGL(k_apply_commit_gathered, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
+        HIPCHK(c, hipGetLastError());
+        if (c->idx.built)
+            if (int rc = launch_build_fit(c, nullptr, 0, c->apply_dirty.ptr)) return rc;
+    }
+    if (x.a.status && x.count > 0) {  // (every status but OVERFLOW is final after the accumulate pass)
+        hipLaunchKernelGGL(k_apply_status, pod_grid(x.count), dim3(256), 0, s, x.a);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->bf_dirty = true;
+    if (int rc = snapshot_end(c)) return rc;
+    if (s != x.hs) {
+        HIPCHK(c, hipStreamWaitEvent(x.hs, c->ev_build, 0));
+        if (x.hs == c->stream) c->own_gen = c->build_gen;
+        for (auto &u : c->user_streams)
+            if (u.s == x.hs) u.gen = c->build_gen;
+    }
+    return KSCHED_OK;
+}
+
+// the whole call over the ranks in `v` (their mutexes held): the phases of every rank between the collectives
+int sharded_run(std::vector<ShardedApply> &v, const uint32_t *row_lo, const int32_t *const *bindings, const int64_t *const *req_cpu,
+                const int64_t *const *req_mem, const uint8_t *const *ok, uint32_t flags, int32_t *const *status_out) {
+    const int k = (int)v.size();
+    for (int i = 0; i < k; ++i) {
+        DeviceGuard g(v[i].c->device);
+        if (!g.ok) return KSCHED_E_HIP;
+        if (int rc = sharded_begin(v[i], row_lo[i], bindings[i], req_cpu[i], req_mem[i], ok ? ok[i] : nullptr, flags,
+                                   status_out ? status_out[i] : nullptr))
+            return rc;
+    }
+    const uint32_t n = v[0].a.n;
+    std::vector<ksched_comm *> comms(k);
+    std::vector<const void *> send(k);
+    std::vector<void *> recv(k), streams(k);
+    for (int i = 0; i < k; ++i) {
+        comms[i] = v[i].q;
+        recv[i] = v[i].c->apply_gath.ptr;
+        streams[i] = v[i].c->change_stream;
+    }
+    if ((flags & KSCHED_APPLY_FIRST_PER_NODE) && n > 0) {
+        for (int i = 0; i < k; ++i) send[i] = v[i].c->apply_claim.ptr;
+        if (int rc = group_allgather(comms.data(), k, send.data(), recv.data(), n, ncclUint32, streams.data(), "ncclAllGather (claims)")) return rc;
+    }
+    for (int i = 0; i < k; ++i) {
+        DeviceGuard g(v[i].c->device);
+        if (!g.ok) return KSCHED_E_HIP;
+        if (int rc = sharded_accumulate(v[i])) return rc;
+    }
+    if (n > 0) {  // the split sums as 32-bit words: 8 per node
+        for (int i = 0; i < k; ++i) send[i] = v[i].c->apply_acc.ptr;
+        if (int rc = group_allgather(comms.data(), k, send.data(), recv.data(), (size_t)n * 8, ncclUint32, streams.data(), "ncclAllGather (sums)")) return rc;
+    }
+    for (int i = 0; i < k; ++i) {
+        DeviceGuard g(v[i].c->device);
+        if (!g.ok) return KSCHED_E_HIP;
+        if (int rc = sharded_finish(v[i])) return rc;
+    }
+    return KSCHED_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ksched_apply_bindings_sharded(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo, const int32_t *bindings,
+                                  const int64_t *req_cpu, const int64_t *req_mem, const uint8_t *ok, uint32_t flags, int32_t *status_out,
+                                  void *hip_stream) try {
+    if (int rc = sharded_check(c, q, count, row_lo, bindings, req_cpu, req_mem, flags)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    std::vector<ShardedApply> v(1);
+    v[0].c = c;
+    v[0].q = q;
+    v[0].hs = (hipStream_t)hip_stream;
+    v[0].count = count;
+    ShardedInvalidate inv{v};
+    const int rc = sharded_run(v, &row_lo, &bindings, &req_cpu, &req_mem, ok ? &ok : nullptr, flags, status_out ? &status_out : nullptr);
+    inv.done = rc == KSCHED_OK;
+    return rc;
+} KSCHED_ABI_CATCH_COMM
+
+int ksched_apply_bindings_sharded_local(ksched_ctx *const *ctxs, ksched_comm *const *comms, int n, const uint32_t *count,
+                                        const uint32_t *row_lo, const int32_t *const *bindings, const int64_t *const *req_cpu,
+                                        const int64_t *const *req_mem, const uint8_t *const *ok, uint32_t flags,
+                                        int32_t *const *status_out, void *const *hip_streams) try {
+    if (!ctxs || !comms || n <= 0 || n > 64 || !count || !row_lo || !bindings || !req_cpu || !req_mem) return KSCHED_E_INVAL;
+    for (int i = 0; i < n; ++i) {
+        if (int rc = sharded_check(ctxs[i], comms[i], count[i], row_lo[i], bindings[i], req_cpu[i], req_mem[i], flags)) return rc;
+        if (comms[i]->nranks != n) return KSCHED_E_INVAL;  // (the collective needs every rank of the clique, each once)
+        for (int j = 0; j < i; ++j)
+            if (ctxs[j] == ctxs[i] || comms[j] == comms[i] || comms[j]->rank == comms[i]->rank) return KSCHED_E_INVAL;
+    }
+    // every ctx's mutex, in address order (two calls over the same ctxs in different orders cannot deadlock)
+    std::vector<ksched_ctx *> order(ctxs, ctxs + n);
+    std::sort(order.begin(), order.end(), std::less<ksched_ctx *>());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    locks.reserve((size_t)n);
+    for (ksched_ctx *c : order) locks.emplace_back(c->mu);
+    for (int i = 0; i < n; ++i)
+        if (!ctxs[i]->have_nodes) return KSCHED_E_STATE;
+    for (int i = 1; i < n; ++i)
+        if (ctxs[i]->n != ctxs[0]->n) return KSCHED_E_INVAL;  // replicas of one snapshot
+    std::vector<ShardedApply> v((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        v[i].c = ctxs[i];
+        v[i].q = comms[i];
+        v[i].hs = hip_streams ? (hipStream_t)hip_streams[i] : nullptr;
+        v[i].count = count[i];
+    }
+    ShardedInvalidate inv{v};
+    const int rc = sharded_run(v, row_lo, bindings, req_cpu, req_mem, ok, flags, status_out);
+    inv.done = rc == KSCHED_OK;
+    return rc;
 } KSCHED_ABI_CATCH_COMM
 
 int ksched_index_checksum(ksched_ctx *c, uint64_t *out) try {

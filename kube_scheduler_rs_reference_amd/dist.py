@@ -122,10 +122,141 @@ class AbiComm:
                 check(rc, "ksched_allgather_bindings")
         return call
 
+    def apply_bindings(self, bindings: torch.Tensor, req_cpu: torch.Tensor, req_mem: torch.Tensor, row_lo: int, ok=None,
+                       flags: int = 0, status_out=None, stream=None) -> None:
+        """Apply this rank's rows [row_lo, row_lo + len(bindings)) of a sharded batch to every replica (ksched_apply_bindings_sharded):
+        every rank calls it, an empty shard included, and afterwards every rank's snapshot is what one ctx's
+        ksched_apply_bindings_device over the whole batch gives.  Tensors as in Evaluator.apply_bindings_device, on this rank's device;
+        enqueued on `stream` (default: current), the host does not wait."""
+        import ctypes as C
+        args = _apply_args(self._ev, bindings, req_cpu, req_mem, ok, status_out)
+        stream = stream or torch.cuda.current_stream(self._ev.device)
+        self._check(self._lib.ksched_apply_bindings_sharded(self._ev._h, self._h, args[0], int(row_lo), *args[1:5], int(flags), args[5],
+                                                            C.c_void_p(stream.cuda_stream)), "ksched_apply_bindings_sharded")
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.ksched_comm_destroy(self._h)
             self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _apply_args(ev, bindings, req_cpu, req_mem, ok, status_out):
+    """(count, bindings, req_cpu, req_mem, ok, status_out) of one rank, checked, as ctypes values (pointers may be NULL when count is 0)."""
+    import ctypes as C
+    if bindings.dim() != 1:
+        raise ValueError("bindings must be a 1-D int32 tensor")
+    p = int(bindings.shape[0])
+
+    def dp(t, dtypes, name):
+        if t is None:
+            return None
+        if not t.is_cuda or t.device.index != ev.device or not t.is_contiguous() or t.dtype not in dtypes:
+            raise ValueError(f"{name}: expected a contiguous {dtypes} CUDA tensor on cuda:{ev.device}")
+        if tuple(t.shape) != (p,):
+            raise ValueError(f"{name}: expected shape ({p},), got {tuple(t.shape)}")
+        return t.data_ptr() or None
+    return (p, dp(bindings, (torch.int32,), "bindings"), dp(req_cpu, (torch.int64,), "req_cpu"), dp(req_mem, (torch.int64,), "req_mem"),
+            dp(ok, (torch.uint8, torch.bool), "ok"), dp(status_out, (torch.int32,), "status_out"))
+
+
+class LocalClique:
+    """n `Evaluator`s of ONE process as the ranks of one RCCL clique (ksched_comm_create_local): the one-process driver's exchange.
+    Evaluator i is rank i.  allgather_bindings() wraps ksched_allgather_bindings_local, apply_bindings() wraps
+    ksched_apply_bindings_sharded_local.  Every non-OK code raises KschedError (KSCHED_E_RCCL with ksched_comm_last_error's text);
+    after a failed collective the clique is aborted and a new one has to be created."""
+
+    def __init__(self, evaluators):
+        import ctypes as C
+        from . import _lib as L
+        self._evs = list(evaluators)
+        if not self._evs:
+            raise ValueError("a clique needs at least one evaluator")
+        self._lib = self._evs[0]._lib
+        self.n = len(self._evs)
+        ctxs = (C.c_void_p * self.n)(*[e._h for e in self._evs])
+        self._comms = (C.c_void_p * self.n)()
+        rc = self._lib.ksched_comm_create_local(C.cast(ctxs, C.c_void_p), self.n, C.cast(self._comms, C.c_void_p))
+        if rc != 0:
+            raise L.KschedError(rc, "ksched_comm_create_local", self._lib.ksched_comm_last_error().decode())
+        self._ctxs = ctxs
+
+    def _check(self, rc: int, where: str):
+        if rc != 0:
+            from . import _lib as L
+            raise L.KschedError(rc, where, self._lib.ksched_comm_last_error().decode())
+
+    def _streams(self, streams):
+        import ctypes as C
+        if streams is None:
+            streams = [torch.cuda.current_stream(e.device) for e in self._evs]
+        if len(streams) != self.n:
+            raise ValueError(f"expected {self.n} streams")
+        return (C.c_void_p * self.n)(*[s.cuda_stream for s in streams])
+
+    def _live(self):
+        if self._comms is None:
+            raise RuntimeError("the clique is closed")
+
+    def allgather_bindings(self, gathered, local, streams=None) -> None:
+        """gathered[i][r * len(local[i]) + j] = local[r][j] for every rank i (int32 CUDA tensors of evaluator i's device, one count),
+        enqueued on streams[i] (default: each device's current stream)."""
+        import ctypes as C
+        self._live()
+        if len(local) != self.n or len(gathered) != self.n:
+            raise ValueError(f"expected {self.n} local and {self.n} gathered tensors")
+        count = int(local[0].numel())
+        for i in range(self.n):
+            for t in (local[i], gathered[i]):
+                if t.dtype != torch.int32 or not t.is_cuda or t.device.index != self._evs[i].device or not t.is_contiguous():
+                    raise ValueError(f"rank {i}: bindings must be contiguous int32 CUDA tensors on cuda:{self._evs[i].device}")
+            if local[i].numel() != count or gathered[i].numel() != count * self.n:
+                raise ValueError(f"rank {i}: every rank passes {count} bindings and receives {count * self.n}")
+        lp = (C.c_void_p * self.n)(*[t.data_ptr() for t in local])
+        gp = (C.c_void_p * self.n)(*[t.data_ptr() for t in gathered])
+        self._check(self._lib.ksched_allgather_bindings_local(C.cast(self._comms, C.c_void_p), self.n, C.cast(lp, C.c_void_p),
+                                                              C.cast(gp, C.c_void_p), count, C.cast(self._streams(streams), C.c_void_p)),
+                    "ksched_allgather_bindings_local")
+
+    def apply_bindings(self, bindings, req_cpu, req_mem, row_lo, ok=None, flags: int = 0, status_out=None, streams=None) -> None:
+        """Rank i's rows [row_lo[i], row_lo[i] + len(bindings[i])) of a sharded batch, applied to every replica
+        (ksched_apply_bindings_sharded_local).  Per-rank lists of tensors as in AbiComm.apply_bindings; ok / status_out may be None
+        or lists with None entries."""
+        import ctypes as C
+        self._live()
+        n = self.n
+        ok = ok if ok is not None else [None] * n
+        status_out = status_out if status_out is not None else [None] * n
+        if not all(len(x) == n for x in (bindings, req_cpu, req_mem, row_lo, ok, status_out)):
+            raise ValueError(f"expected per-rank lists of {n}")
+        args = [_apply_args(self._evs[i], bindings[i], req_cpu[i], req_mem[i], ok[i], status_out[i]) for i in range(n)]
+        arr = lambda k: (C.c_void_p * n)(*[a[k] for a in args])  # noqa: E731
+        counts = (C.c_uint32 * n)(*[a[0] for a in args])
+        lows = (C.c_uint32 * n)(*[int(r) for r in row_lo])
+        keep = [arr(k) for k in range(1, 6)]
+        vp = lambda x: C.cast(x, C.c_void_p)  # noqa: E731
+        self._check(self._lib.ksched_apply_bindings_sharded_local(vp(self._ctxs), vp(self._comms), n, vp(counts), vp(lows), vp(keep[0]),
+                                                                  vp(keep[1]), vp(keep[2]), vp(keep[3]), int(flags), vp(keep[4]),
+                                                                  vp(self._streams(streams))),
+                    "ksched_apply_bindings_sharded_local")
+
+    def close(self):
+        if getattr(self, "_comms", None) is not None:
+            for h in self._comms:
+                if h:
+                    self._lib.ksched_comm_destroy(h)
+            self._comms = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):  # pragma: no cover
         try:

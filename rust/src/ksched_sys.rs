@@ -168,6 +168,15 @@ extern "C" {
         comms: *const *mut ksched_comm, n: c_int, local: *const *const i32, gathered: *const *mut i32, count_per_rank: u32,
         hip_streams: *const *mut c_void,
     ) -> c_int;
+    pub fn ksched_apply_bindings_sharded(
+        ctx: *mut ksched_ctx, comm: *mut ksched_comm, count: u32, row_lo: u32, bindings: *const i32, req_cpu_milli: *const i64,
+        req_mem_bytes: *const i64, ok: *const u8, flags: u32, status_out: *mut i32, hip_stream: *mut c_void,
+    ) -> c_int;
+    pub fn ksched_apply_bindings_sharded_local(
+        ctxs: *const *mut ksched_ctx, comms: *const *mut ksched_comm, n: c_int, count: *const u32, row_lo: *const u32,
+        bindings: *const *const i32, req_cpu_milli: *const *const i64, req_mem_bytes: *const *const i64, ok: *const *const u8,
+        flags: u32, status_out: *const *mut i32, hip_streams: *const *mut c_void,
+    ) -> c_int;
     pub fn ksched_comm_last_error() -> *const c_char;
     // ---- measurement / diagnostics
     pub fn ksched_kernel_time_ms(ctx: *mut ksched_ctx, total_ms: *mut f64, launches: *mut u64) -> c_int;
@@ -227,6 +236,8 @@ pub fn symbol_table() -> Vec<(&'static str, usize)> {
         ("ksched_comm_size", ksched_comm_size as usize),
         ("ksched_allgather_bindings", ksched_allgather_bindings as usize),
         ("ksched_allgather_bindings_local", ksched_allgather_bindings_local as usize),
+        ("ksched_apply_bindings_sharded", ksched_apply_bindings_sharded as usize),
+        ("ksched_apply_bindings_sharded_local", ksched_apply_bindings_sharded_local as usize),
         ("ksched_comm_last_error", ksched_comm_last_error as usize),
         ("ksched_kernel_time_ms", ksched_kernel_time_ms as usize),
         ("ksched_kernel_time_samples", ksched_kernel_time_samples as usize),
