@@ -512,3 +512,59 @@ def kq061_fit_matrix(pods: Sequence[dict], nodes: Sequence[dict], all_pods: Sequ
             except ReferencePanic:
                 out.append(None)
     return out
+
+
+# ---- ksched_apply_bindings_device, restated with exact integers -----------------------------------
+# include/ksched.h KSCHED_APPLY_*: the per-pod statuses, and the two flags.
+APPLY_FIRST_PER_NODE, APPLY_RELEASE = 0x01, 0x02
+APPLY_APPLIED, APPLY_UNBOUND, APPLY_NOT_OK, APPLY_DEFERRED, APPLY_OVERFLOW, APPLY_BAD_NODE = 0, 1, 2, 3, 4, 5
+_I64_MIN, _I64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def apply_bindings_exact(cpu, mem, bindings, req_cpu, req_mem, ok=None, flags: int = 0):
+    """-> (new cpu, new mem, status) as int64 / int64 / int32 numpy arrays: the rule the header states for ksched_apply_bindings_device
+    (SubAssign, src/util.rs:31-36, over the eligible accepted pods), in Python integers -- no numpy arithmetic, so no sum can wrap.
+
+    A pod is eligible when 0 <= binding < n and ok (when given) is nonzero.  Without APPLY_FIRST_PER_NODE every eligible pod is
+    accepted; with it, per node only the lowest eligible pod index (the others report DEFERRED).  Per node the accepted pods' requests
+    are summed, and old - sum (old + sum with APPLY_RELEASE) replaces `available` when both resources stay inside int64; otherwise the
+    node keeps both old values and its accepted pods report OVERFLOW."""
+    import numpy as np
+    cpu, mem = [int(x) for x in cpu], [int(x) for x in mem]
+    b_, rc, rm = np.asarray(bindings).tolist(), np.asarray(req_cpu).tolist(), np.asarray(req_mem).tolist()
+    okl = None if ok is None else np.asarray(ok).tolist()
+    n, p = len(cpu), len(b_)
+    eligible = [0 <= b_[i] < n and (okl is None or okl[i] != 0) for i in range(p)]
+    first = {}
+    if flags & APPLY_FIRST_PER_NODE:
+        for i in range(p):
+            if eligible[i] and b_[i] not in first:
+                first[b_[i]] = i
+    status, sums = [0] * p, {}
+    for i in range(p):
+        b = b_[i]
+        if b < 0:
+            status[i] = APPLY_UNBOUND
+        elif b >= n:
+            status[i] = APPLY_BAD_NODE
+        elif not eligible[i]:
+            status[i] = APPLY_NOT_OK
+        elif first and first[b] != i:
+            status[i] = APPLY_DEFERRED
+        else:
+            status[i] = APPLY_APPLIED
+            s = sums.setdefault(b, [0, 0])
+            s[0] += rc[i]
+            s[1] += rm[i]
+    sign = 1 if flags & APPLY_RELEASE else -1
+    ovf = set()
+    for node, (sc, sm) in sums.items():
+        nc, nm = cpu[node] + sign * sc, mem[node] + sign * sm
+        if _I64_MIN <= nc <= _I64_MAX and _I64_MIN <= nm <= _I64_MAX:
+            cpu[node], mem[node] = nc, nm
+        else:
+            ovf.add(node)
+    for i in range(p):
+        if status[i] == APPLY_APPLIED and b_[i] in ovf:
+            status[i] = APPLY_OVERFLOW
+    return np.array(cpu, dtype=np.int64), np.array(mem, dtype=np.int64), np.array(status, dtype=np.int32)

@@ -1,0 +1,343 @@
+"""Child process of tests/test_gpu_apply_paths.py (and, for its `check_matrix`, of tests/apply_sharded_worker.py "paths"): every evaluation
+path after ksched_apply_bindings_device on one ctx.
+
+    python -m tests.apply_paths_worker <case> '<json spec>'
+
+An apply writes `available` in three places -- the columns, the node records (read by the "select" pick, the riding pick in its waves
+form, ksched_explain and the list-key best fit) and the dirty tiles of the bitmap index -- so after each apply every path that reads any
+of them is run and compared with the oracle (capi.eval_encoded, and for ksched_explain the reason rebuilt from single-predicate oracle
+masks) on the columns the exact-integer restatement (oracle_ref.apply_bindings_exact) gives.  Every mask word, fit-mask word, binding and
+reason is compared.  A case prints "ok <case>" as its last line when all its checks passed.
+"""
+from __future__ import annotations
+
+import json
+import sys
+
+import numpy as np
+import torch
+
+from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth
+from oracle import capi
+from oracle.oracle_ref import apply_bindings_exact
+from tests.test_gpu_apply_bindings import random_bindings
+
+DEV = torch.device("cuda:0")
+FPN, REL = _lib.APPLY_FIRST_PER_NODE, _lib.APPLY_RELEASE
+KINDS = ("taints", "many-keys", "list-key", "unindexed")
+
+
+def t(a, dt):
+    return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(DEV)
+
+
+def _id_column(rng, N, P, offset, p_constrain=0.3):
+    """a label column of distinct ids offset + 1 .. offset + N (one per node: hostname-like) and the pods' selector row for it: 0 (none),
+    a node's id, an id no node carries, or SEL_NEVER.  The offset keeps the key's largest id high at every N, which is what turns it into
+    a list key (or, three of them, leaves the snapshot unindexed)"""
+    col = (rng.permutation(N) + 1 + offset).astype(np.uint32)
+    r = rng.random(P)
+    sel = np.zeros(P, np.uint32)
+    named = r < p_constrain
+    sel[named] = col[rng.integers(0, N, int(named.sum()))]
+    sel[(r >= p_constrain) & (r < p_constrain + 0.03)] = offset + N + 1 + rng.integers(0, 5)
+    sel[rng.random(P) < 0.01] = SEL_NEVER
+    return col, sel
+
+
+def snapshot(kind, N, P, seed):
+    """-> dict: node columns, pod columns, the predicate sets to evaluate with, whether the snapshot has a bitmap index"""
+    rng = np.random.default_rng(seed)
+    if kind == "taints":  # <= 8 keys, 16 taints
+        c = synth.make_cluster(P, N, n_keys=8, n_taints=16, seed=seed)
+        lab, sel, tnt, tol = c.node_labels, c.pod_sel, c.node_taints, c.pod_tol
+        preds = [FIT | SEL | TAINT, FIT | SEL]
+    elif kind == "many-keys":  # 10 keys: no tile-test pick
+        c = synth.make_cluster(P, N, n_keys=10, seed=seed)
+        lab, sel, tnt, tol = c.node_labels, c.pod_sel, None, None
+        preds = [FIT | SEL]
+    elif kind == "list-key":  # 8 keys + a hostname-style key kept as per-tile sorted lists
+        c = synth.make_cluster(P, N, n_keys=8, seed=seed)
+        col, srow = _id_column(rng, N, P, 3000)
+        lab, sel = np.concatenate([c.node_labels, col[None]]), np.concatenate([c.pod_sel, srow[None]])
+        tnt, tol = None, None
+        preds = [FIT | SEL]
+    elif kind == "unindexed":  # three high-cardinality keys: indexed_plan refuses the snapshot
+        c = synth.make_cluster(P, N, n_keys=4, seed=seed)
+        cols = [_id_column(rng, N, P, off, 0.1) for off in (2000, 2500, 3000)]
+        lab = np.concatenate([c.node_labels] + [x[0][None] for x in cols])
+        sel = np.concatenate([c.pod_sel] + [x[1][None] for x in cols])
+        tnt, tol = None, None
+        preds = [FIT | SEL]
+    else:
+        raise ValueError(kind)
+    return dict(kind=kind, N=N, P=P, cpu=c.avail_cpu.copy(), mem=c.avail_mem.copy(), lab=np.ascontiguousarray(lab), tnt=tnt,
+                rc=c.req_cpu, rm=c.req_mem, sel=np.ascontiguousarray(sel), tol=tol, preds=preds, indexed=kind != "unindexed",
+                smp5=rng.integers(0, N + 2, (P, 5)).astype(np.uint32), smp3=rng.integers(0, N, (P, 3)).astype(np.uint32))
+
+
+def set_nodes(ev, S, cpu, mem):
+    ev.set_nodes(cpu, mem, S["lab"], S["tnt"])
+
+
+def _bits(mask, pp, pn):
+    return ((mask[pp, pn >> 6] >> (pn & 63).astype(np.uint64)) & np.uint64(1)).astype(bool)
+
+
+def want_reasons(S, cpu, mem, preds, pp, pn):
+    """ksched_explain's rule, as tools/fuzz_parity.py states it: the first predicate of (fit, selector, taints) whose single-predicate
+    oracle mask rejects the pair"""
+    def ok(f):
+        if not preds & f:
+            return np.ones(pp.shape, bool)
+        m = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"], S["rc"], S["rm"], S["sel"], S["tol"], None, f)[0]
+        return _bits(m, pp, pn)
+    ok_f, ok_s, ok_t = ok(FIT), ok(SEL), ok(TAINT)
+    return np.where(~ok_f, _lib.REASON_NOT_ENOUGH_RESOURCES, np.where(~ok_s, _lib.REASON_NODE_SELECTOR_MISMATCH,
+                    np.where(~ok_t, _lib.REASON_TAINT_NOT_TOLERATED, _lib.REASON_OK))).astype(np.int32)
+
+
+def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False):
+    """every evaluation path of `ev` (whose snapshot should hold cpu / mem) against the oracle; the names of the picks that ran go into
+    `seen`.  reduced: the kernels and options at their defaults, plus the direct kernel, the waves-form pick, bindings-only "select",
+    best fit, ksched_pick and ksched_explain.  -> the device bindings of a sampled pick (a real evaluation's bindings for the next apply)"""
+    P, N = S["P"], S["N"]
+    rc, rm, sel = S["rc"], S["rm"], S["sel"]
+    out_b = None
+    for preds in S["preds"]:
+        tnt = S["tnt"] if preds & TAINT else None
+        tol = S["tol"] if preds & TAINT else None
+        w = f"{what} preds={preds:#x}"
+        feas, fit, bind_s = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, S["smp5"], preds | PICK_SAMPLED | WANT_FIT_MASK)
+        bind_b = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, None, preds | PICK_BESTFIT, want_mask=False)[2]
+        bind_3 = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, S["smp3"], preds | PICK_SAMPLED, want_mask=False)[2]
+
+        def run(flags, smp=None, want_mask=True, expect_b=None, label=""):
+            r = ev.eval(rc, rm, sel, tol, smp, flags, want_mask=want_mask)
+            if want_mask:
+                assert np.array_equal(r.feasible, feas), f"{w} {label}: mask (kernel {ev.last_kernel}, pick {ev.last_pick})"
+            if flags & WANT_FIT_MASK:
+                assert np.array_equal(r.fit, fit), f"{w} {label}: fit mask"
+            if expect_b is not None:
+                assert np.array_equal(r.binding, expect_b), f"{w} {label}: bindings (kernel {ev.last_kernel}, pick {ev.last_pick})"
+            seen.add(ev.last_pick)
+
+        kernels = ("auto", "direct") if reduced else ("fused", "direct", "auto")
+        for kernel in kernels:
+            ev.set_kernel(kernel)
+            if kernel == "fused" and not S["indexed"]:
+                try:
+                    ev.eval(rc, rm, sel, tol, None, preds)
+                    raise AssertionError(f"{w}: the fused kernel ran on a snapshot without an index")
+                except KschedError as e:
+                    assert e.code == _lib.E_UNSUPPORTED, f"{w}: {e}"
+                continue
+            k = f"kernel={kernel}"
+            run(preds | WANT_FIT_MASK, label=f"{k} no pick")
+            for fp in ((1, 2) if reduced else (0, 1, 2, 3)):
+                ev.set_option(_lib.OPT_FUSED_PICK, fp)
+                try:
+                    run(preds | PICK_SAMPLED, S["smp5"], expect_b=bind_s, label=f"{k} sampled fused_pick={fp}")
+                except KschedError as e:  # 3 = tile tests or E_UNSUPPORTED (taints, more than eight keys, ...)
+                    assert fp == 3 and e.code == _lib.E_UNSUPPORTED, f"{w} {k} fused_pick={fp}: {e}"
+                    seen.add("tile-unsupported")
+                if fp == 2:  # three draws: never the tile-test form
+                    run(preds | PICK_SAMPLED, S["smp3"], expect_b=bind_3, label=f"{k} sampled, 3 draws")
+            ev.set_option(_lib.OPT_FUSED_PICK, 1)
+            for stages in ((0,) if reduced else (0, 1, 2)):
+                ev.set_option(_lib.OPT_BESTFIT_STAGES, stages)
+                run(preds | PICK_BESTFIT, expect_b=bind_b, label=f"{k} best fit stages={stages}")
+            ev.set_option(_lib.OPT_BESTFIT_STAGES, 0)
+        ev.set_kernel("auto")
+        # bindings only: the sampled pick is its own launch ("select"), best fit reads no mask
+        run(preds | PICK_SAMPLED, S["smp5"], want_mask=False, expect_b=bind_s, label="sampled, bindings only")
+        run(preds | PICK_BESTFIT, want_mask=False, expect_b=bind_b, label="best fit, bindings only")
+        if not reduced:  # the mask-reading picks
+            ev.set_option(_lib.OPT_PICK_FROM_MASK, 1)
+            run(preds | PICK_SAMPLED, S["smp5"], expect_b=bind_s, label="sampled from the mask")
+            run(preds | PICK_BESTFIT, expect_b=bind_b, label="best fit from the mask")
+            ev.set_option(_lib.OPT_PICK_FROM_MASK, 0)
+        # device buffers, with and without a mask
+        rc_t, rm_t, sel_t = t(rc, np.int64), t(rm, np.int64), t(sel, np.int32)
+        tol_t = t(tol, np.int64) if tol is not None else None
+        smp_t = t(S["smp5"], np.int32)
+        m = torch.empty((P, ev.W), dtype=torch.int64, device=DEV)
+        bs, bs0, bb = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(3))
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smp_t, preds | PICK_SAMPLED, out_feasible=m, out_binding=bs)
+        seen.add(ev.last_pick)
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smp_t, preds | PICK_SAMPLED, out_binding=bs0)
+        assert ev.last_pick == "select", f"{w}: a bindings-only sampled pick ran as {ev.last_pick}"
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, None, preds | PICK_BESTFIT, out_binding=bb)
+        seen.add(ev.last_pick)
+        torch.cuda.synchronize()
+        assert np.array_equal(m.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask"
+        for got, want, lbl in ((bs, bind_s, "sampled"), (bs0, bind_s, "sampled, bindings only"), (bb, bind_b, "best fit")):
+            assert np.array_equal(got.cpu().numpy(), want), f"{w}: eval_device {lbl} bindings"
+        if out_b is None:
+            out_b = bs.cpu().numpy()
+        # the pick alone from the oracle's host mask (ksched_pick)
+        assert np.array_equal(ev.pick(feas, PICK_SAMPLED, samples=S["smp5"]), bind_s), f"{w}: ksched_pick sampled"
+        assert np.array_equal(ev.pick(feas, PICK_BESTFIT | (preds & FIT), req_mem_bytes=rm if preds & FIT else None), bind_b), \
+            f"{w}: ksched_pick best fit"
+        # per-pair reasons
+        n_pairs = 4000
+        pp, pn = rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
+        got_r = ev.explain(rc, rm, sel, tol, pp, pn, preds)
+        want_r = want_reasons(S, cpu, mem, preds, pp.astype(np.int64), pn.astype(np.int64))
+        assert np.array_equal(got_r, want_r), f"{w}: ksched_explain ({int((got_r != want_r).sum())} of {n_pairs} pairs differ)"
+    ev.set_kernel("auto")
+    return out_b
+
+
+def apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, what):
+    """one apply on `ev` against the restatement: columns, statuses, the index (== a fresh ksched_set_nodes on `ref`; (0, 0) unindexed)"""
+    P = len(b)
+    st = torch.full((P,), -7, dtype=torch.int32, device=DEV)
+    ev.apply_bindings_device(t(b, np.int32), t(S["rc"][:P], np.int64), t(S["rm"][:P], np.int64), None if ok is None else t(ok, np.uint8),
+                             flags, st)
+    torch.cuda.synchronize()
+    ncpu, nmem, want = apply_bindings_exact(cpu, mem, b, S["rc"][:P], S["rm"][:P], ok, flags)
+    assert np.array_equal(st.cpu().numpy(), want), f"{what}: statuses"
+    got = ev.read_nodes()
+    assert np.array_equal(got[0], ncpu) and np.array_equal(got[1], nmem), f"{what}: columns"
+    set_nodes(ref, S, ncpu, nmem)
+    ck = ev.index_checksum()
+    assert ck == ref.index_checksum(), f"{what}: index checksum"
+    if not S["indexed"]:
+        assert ck == (0, 0), f"{what}: an unindexed snapshot has an index checksum {ck}"
+    return ncpu, nmem, want
+
+
+# (bindings, flags, ok) of the apply of round r at node-count index i: FORMS[(i + r) % 6] -- every form on real and random bindings
+FORMS = [("real", 0, False), ("random", FPN, True), ("real", REL, True), ("random", 0, False), ("real", FPN, False), ("random", FPN | REL, True)]
+
+
+def case_single(spec):
+    """per node count: the matrix, then rounds of [apply (the previous evaluation's bindings or random ones) -> the matrix]"""
+    kind, rounds = spec["kind"], spec.get("rounds", 2)
+    seen = set()
+    ev, ref = Evaluator(0), Evaluator(0)
+    for i, N in enumerate(spec["nodes"]):
+        P = spec["pods"] if N <= 5000 else spec["pods_big"]
+        S = snapshot(kind, N, P, 0xAB00 + 17 * N + KINDS.index(kind))
+        cpu, mem = S["cpu"], S["mem"]
+        set_nodes(ev, S, cpu, mem)
+        if S["indexed"]:
+            assert ev.index_checksum() != (0, 0), f"{kind} N={N}: no index"
+        else:
+            assert ev.index_checksum() == (0, 0), f"{kind} N={N}: the snapshot was indexed"
+        rng = np.random.default_rng(N)
+        bind = check_matrix(ev, S, cpu, mem, seen, f"{kind} N={N} before any apply", rng)
+        applied = 0
+        for r in range(rounds):
+            src, flags, use_ok = FORMS[(i + r) % len(FORMS)]
+            if src == "random":
+                b, ok = random_bindings(rng, N, P)
+            else:  # ok: 0 for a fifth of the pods, any of 1 .. 255 (all of them "landed") for the others
+                b, ok = bind, np.where(rng.random(P) < 0.2, 0, rng.integers(1, 256, P)).astype(np.uint8)
+            what = f"{kind} N={N} round {r} ({src} bindings, flags={flags}, ok={use_ok})"
+            cpu, mem, st = apply_and_check(ev, ref, S, cpu, mem, b, ok if use_ok else None, flags, what)
+            applied += int((st == _lib.APPLY_APPLIED).sum())
+            bind = check_matrix(ev, S, cpu, mem, seen, what, rng)
+        assert applied > 0, f"{kind} N={N}: no pod was applied"
+    want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask"},
+            "many-keys": {"select", "fused", "bestfit-rows", "from-mask"},
+            "list-key": {"select", "bestfit-rows", "from-mask"},
+            "unindexed": {"select", "from-mask"}}[kind]
+    assert want <= seen, f"{kind}: picks reached {sorted(seen)}, missing {sorted(want - seen)}"
+    print(f"{kind}: picks reached {sorted(seen)}")
+    ev.close()
+    ref.close()
+
+
+def case_sizes(spec):
+    """one ctx through snapshots of 50 000 -> 300 -> 4097 -> 1 -> 60 000 nodes (the last one past the apply scratch's size): after each
+    ksched_set_nodes an apply, an update of nodes in the tiles it touched and a second apply, enqueued with no host wait in between;
+    then the columns, the statuses, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused evaluation
+    with the sampled pick in its waves form"""
+    ev, ref = Evaluator(0), Evaluator(0)
+    seen = set()
+    for step, N in enumerate(spec["nodes"]):
+        P = 3000
+        S = snapshot("taints", N, P, 0xC0 + step)
+        cpu, mem = S["cpu"], S["mem"]
+        set_nodes(ev, S, cpu, mem)
+        rng = np.random.default_rng(step)
+        b1, ok1 = random_bindings(rng, N, P)
+        b2, ok2 = random_bindings(rng, N, P)
+        touched = np.unique(b1[(b1 >= 0) & (b1 < N)])
+        idx = rng.choice(touched, min(len(touched), 50), replace=False).astype(np.uint32) if len(touched) else np.zeros(0, np.uint32)
+        ucpu, umem = rng.integers(-1000, 64_000, idx.size).astype(np.int64), rng.integers(0, 1 << 40, idx.size).astype(np.int64)
+        f1, f2 = (FPN, 0) if step % 2 == 0 else (0, FPN | REL)
+        st1, st2 = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        rc_t, rm_t = t(S["rc"], np.int64), t(S["rm"], np.int64)
+        ev.apply_bindings_device(t(b1, np.int32), rc_t, rm_t, t(ok1, np.uint8), f1, st1)
+        if idx.size:
+            ev.update_nodes(idx, ucpu, umem)
+        ev.apply_bindings_device(t(b2, np.int32), rc_t, rm_t, None, f2, st2)
+        torch.cuda.synchronize()
+        what = f"step {step} N={N}"
+        cpu, mem, w1 = apply_bindings_exact(cpu, mem, b1, S["rc"], S["rm"], ok1, f1)
+        cpu[idx], mem[idx] = ucpu, umem
+        cpu, mem, w2 = apply_bindings_exact(cpu, mem, b2, S["rc"], S["rm"], None, f2)
+        assert np.array_equal(st1.cpu().numpy(), w1) and np.array_equal(st2.cpu().numpy(), w2), f"{what}: statuses"
+        assert (w1 == _lib.APPLY_APPLIED).any() and (w2 == _lib.APPLY_APPLIED).any(), what
+        got = ev.read_nodes()
+        assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem), f"{what}: columns"
+        set_nodes(ref, S, cpu, mem)
+        assert ev.index_checksum() == ref.index_checksum(), f"{what}: index checksum"
+        preds = FIT | SEL | TAINT
+        feas, _, bind = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"], S["rc"], S["rm"], S["sel"], S["tol"], S["smp5"], preds | PICK_SAMPLED)
+        for kernel, fp in (("direct", 1), ("fused", 2)):
+            ev.set_kernel(kernel)
+            ev.set_option(_lib.OPT_FUSED_PICK, fp)
+            r = ev.eval(S["rc"], S["rm"], S["sel"], S["tol"], S["smp5"], preds | PICK_SAMPLED)
+            seen.add(ev.last_pick)
+            assert np.array_equal(r.feasible, feas), f"{what}: {kernel} mask"
+            assert np.array_equal(r.binding, bind), f"{what}: {kernel} bindings (pick {ev.last_pick})"
+        ev.set_kernel("auto")
+        ev.set_option(_lib.OPT_FUSED_PICK, 1)
+    assert {"select", "fused"} <= seen, seen
+    ev.close()
+    ref.close()
+
+
+def large_batch(rng, N, P, far):
+    """P pods onto N nodes: most onto a few nodes, nodes [0, 64) only from pod `far` on (their first eligible pod lies past it)"""
+    b = rng.integers(64, N, P).astype(np.int32)
+    hot = rng.random(P) < 0.5
+    b[hot] = rng.integers(64, 80, int(hot.sum()))
+    late = np.nonzero(rng.random(P - far) < 0.01)[0] + far
+    b[late] = rng.integers(0, 64, late.size)
+    b[rng.random(P) < 0.05] = -1
+    ok = (rng.random(P) > 0.1).astype(np.uint8)
+    return b, ok
+
+
+def case_large(spec):
+    """one apply of P >= 600 000 pods (more than one stride of the pod kernels' grid, 2048 x 256 threads) for every flag set"""
+    N, P = 5000, spec["pods"]
+    far = 2048 * 256 + 1000
+    S = snapshot("taints", N, P, 0x1A)
+    ev, ref = Evaluator(0), Evaluator(0)
+    cpu, mem = S["cpu"], S["mem"]
+    set_nodes(ev, S, cpu, mem)
+    rng = np.random.default_rng(6)
+    for flags in (0, FPN, REL, FPN | REL):
+        b, ok = large_batch(rng, N, P, far)
+        cpu, mem, want = apply_and_check(ev, ref, S, cpu, mem, b, ok if flags != REL else None, flags, f"P={P} flags={flags}")
+        assert (want[far:] == _lib.APPLY_APPLIED).sum() >= 64, flags
+        if flags & FPN:
+            for node in range(64):
+                elig = np.nonzero((b == node) & ((ok != 0) if flags != REL else True))[0]
+                assert len(elig) and elig[0] >= far and want[elig[0]] == _lib.APPLY_APPLIED, (flags, node)
+    ev.close()
+    ref.close()
+
+
+CASES = {"single": case_single, "sizes": case_sizes, "large": case_large}
+
+if __name__ == "__main__":
+    name = sys.argv[1]
+    CASES[name](json.loads(sys.argv[2]) if len(sys.argv) > 2 else {})
+    print(f"ok {name}")

@@ -368,8 +368,72 @@ def case_rank(spec):
     dist.destroy_process_group()
 
 
+def case_paths(spec):
+    """after each sharded apply every replica runs the reduced evaluation matrix of tests/apply_paths_worker.py against the oracle on the
+    restated columns: the "select" pick, the riding pick in its waves form, ksched_explain, the direct kernel and (list key) best fit from
+    the key's lists -- the paths that read the node records the gathered commit writes"""
+    from tests.apply_paths_worker import check_matrix, snapshot
+    n = spec["n"]
+    seen = set()
+    k = 0
+    for kind in ("taints", "list-key"):
+        for N in spec["nodes"]:
+            P = 1500 if N <= 5000 else 600
+            S = snapshot(kind, N, P, 0x5B + N)
+            R = Ranks(n, dict(avail_cpu_milli=S["cpu"], avail_mem_bytes=S["mem"], label_val_ids=S["lab"], taints=S["tnt"]))
+            cpu, mem = S["cpu"], S["mem"]
+            rng = np.random.default_rng(N + n)
+            bind = check_matrix(R.evs[0], S, cpu, mem, seen, f"{kind} N={N} before any apply", rng, reduced=True)
+            for r in range(2):
+                k += 1
+                flags, use_ok = (0, FPN, REL, FPN | REL)[k % 4], k % 3 != 0
+                b, ok = random_bindings(rng, N, P) if r else (bind, (rng.random(P) > 0.2).astype(np.uint8))
+                bounds = cuts(rng, P, n, "ragged")
+                what = f"n={n} {kind} N={N} round {r} flags={flags} ok={use_ok}"
+                st, want = R.apply(bounds, b, ok, S["rc"], S["rm"], flags, use_ok)
+                got = R.check_equal(what)
+                cpu, mem, exp = restate(cpu, mem, b, S["rc"], S["rm"], ok if use_ok else None, flags)
+                assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem) and np.array_equal(exp, want), f"{what}: exact rule"
+                for q in range(n):
+                    assert np.array_equal(st[q], want[bounds[q]:bounds[q + 1]]), f"{what}: rank {q} status"
+                assert (want == _lib.APPLY_APPLIED).any(), f"{what}: nothing applied"
+                for q, e in enumerate(R.evs):
+                    bq = check_matrix(e, S, cpu, mem, seen, f"{what} rank {q}", rng, reduced=True)
+                    if q == 0:
+                        bind = bq
+            R.close()
+    assert {"select", "fused", "bestfit-rows"} <= seen, f"picks reached {sorted(seen)}"
+    print(f"{k} sharded applies, picks reached {sorted(seen)}")
+
+
+def case_large(spec):
+    """two ranks whose shards are each longer than one stride of the pod kernels' grid (2048 x 256 threads)"""
+    n, N = 2, 5000
+    half = 2048 * 256 + 20_000
+    P = 2 * half + 123
+    c = synth.make_cluster(700, N, n_keys=8, n_taints=16, seed=0x1B)
+    R = Ranks(n, c.node_columns())
+    cpu, mem = c.avail_cpu, c.avail_mem
+    rng = np.random.default_rng(2)
+    for flags in (0, FPN, FPN | REL):
+        b, ok, rc, rm = batch(900 + flags, N, P, False)
+        b[(b >= 0) & (b < 16)] = 16  # nodes 0 .. 7 are named by rank 0's last rows only, nodes 8 .. 15 by rank 1's last rows only
+        b[half - 4000:half] = rng.integers(0, 8, 4000)
+        b[P - 4000:] = rng.integers(8, 16, 4000)
+        bounds = [0, half + int(rng.integers(-100, 100)), P]
+        st, want = R.apply(bounds, b, ok, rc, rm, flags)
+        what = f"P={P} flags={flags}"
+        got = R.check_equal(what)
+        cpu, mem, exp = restate(cpu, mem, b, rc, rm, ok, flags)
+        assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem) and np.array_equal(exp, want), f"{what}: exact rule"
+        for q in range(n):
+            assert np.array_equal(st[q], want[bounds[q]:bounds[q + 1]]), f"{what}: rank {q} status"
+        assert (want[2048 * 256:bounds[1]] == _lib.APPLY_APPLIED).any() and (want[bounds[1] + 2048 * 256:] == _lib.APPLY_APPLIED).any(), what
+    R.close()
+
+
 CASES = {"equal": case_equal, "scratch": case_scratch, "chain": case_chain, "failure": case_failure, "errors": case_errors,
-         "rank": case_rank}
+         "rank": case_rank, "paths": case_paths, "large": case_large}
 
 if __name__ == "__main__":
     name = sys.argv[1]

@@ -1,8 +1,9 @@
 """ksched_apply_bindings_device / ksched_read_nodes (ABI 7) on the MI355X.
 
-Every expected column and status comes from `restate` below -- a plain restatement with exact Python integers of the rule the header
-states (SubAssign, src/util.rs:31-36, over the eligible accepted pods) -- and every expected mask and binding from the oracle
-(capi.eval_encoded) on those columns.  The index after an apply is compared with a fresh ksched_set_nodes of the expected columns.
+Every expected column and status comes from `restate` (oracle/oracle_ref.py apply_bindings_exact) -- a plain restatement with exact
+Python integers of the rule the header states (SubAssign, src/util.rs:31-36, over the eligible accepted pods) -- and every expected mask
+and binding from the oracle (capi.eval_encoded) on those columns.  The index after an apply is compared with a fresh ksched_set_nodes of
+the expected columns.
 """
 import numpy as np
 import pytest
@@ -10,6 +11,7 @@ import torch
 
 from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, SEL, TAINT, Evaluator, KschedError, _lib, synth
 from oracle import capi
+from oracle.oracle_ref import apply_bindings_exact as restate  # (tests/apply_sharded_worker.py imports it from here too)
 
 pytestmark = pytest.mark.gpu
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
@@ -18,48 +20,6 @@ DEV = torch.device("cuda:0")
 
 def t(a, dt):
     return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(DEV)
-
-
-def restate(cpu, mem, bindings, req_cpu, req_mem, ok=None, flags=0):
-    """-> (new cpu, new mem, status): the header's rule, exact integers, no numpy arithmetic"""
-    cpu, mem = [int(x) for x in cpu], [int(x) for x in mem]
-    b_, rc, rm = np.asarray(bindings).tolist(), np.asarray(req_cpu).tolist(), np.asarray(req_mem).tolist()
-    okl = None if ok is None else np.asarray(ok).tolist()
-    n, p = len(cpu), len(b_)
-    eligible = [0 <= b_[i] < n and (okl is None or okl[i] != 0) for i in range(p)]
-    first = {}
-    if flags & _lib.APPLY_FIRST_PER_NODE:
-        for i in range(p):
-            if eligible[i] and b_[i] not in first:
-                first[b_[i]] = i
-    status, sums = [0] * p, {}
-    for i in range(p):
-        b = b_[i]
-        if b < 0:
-            status[i] = _lib.APPLY_UNBOUND
-        elif b >= n:
-            status[i] = _lib.APPLY_BAD_NODE
-        elif not eligible[i]:
-            status[i] = _lib.APPLY_NOT_OK
-        elif first and first[b] != i:
-            status[i] = _lib.APPLY_DEFERRED
-        else:
-            status[i] = _lib.APPLY_APPLIED
-            s = sums.setdefault(b, [0, 0])
-            s[0] += rc[i]
-            s[1] += rm[i]
-    sign = 1 if flags & _lib.APPLY_RELEASE else -1
-    ovf = set()
-    for node, (sc, sm) in sums.items():
-        nc, nm = cpu[node] + sign * sc, mem[node] + sign * sm
-        if I64_MIN <= nc <= I64_MAX and I64_MIN <= nm <= I64_MAX:
-            cpu[node], mem[node] = nc, nm
-        else:
-            ovf.add(node)
-    for i in range(p):
-        if status[i] == _lib.APPLY_APPLIED and b_[i] in ovf:
-            status[i] = _lib.APPLY_OVERFLOW
-    return np.array(cpu, dtype=np.int64), np.array(mem, dtype=np.int64), np.array(status, dtype=np.int32)
 
 
 @pytest.fixture(scope="module")

@@ -1,0 +1,46 @@
+"""Every evaluation path after ksched_apply_bindings_device on one ctx, against the oracle on the columns the exact-integer restatement
+gives (tests/apply_paths_worker.py; one child process per case).
+
+The apply writes `available` into the columns, the node records and the dirty tiles of the bitmap index.  After each apply these run:
+the fused, direct and auto kernels; no pick, the sampled pick in every form (its own launch "select", riding as waves "fused" or as tile
+tests "fused-tile", from the mask) and best fit (bitmap rows in one or two stages, the list-key lists, from the mask); ksched_eval and
+ksched_eval_device with and without a mask; ksched_pick from the oracle's host mask; ksched_explain on 4000 random pairs.  Snapshots: up to
+eight keys with taints, ten keys, a list key, and one that indexed_plan refuses (no index: every evaluation reads columns and records).
+"""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NODES = [1, 63, 1025, 4097, 50_000]
+
+
+def run(case, spec, timeout=300):
+    r = subprocess.run([sys.executable, "-m", "tests.apply_paths_worker", case, json.dumps(spec)], cwd=ROOT, capture_output=True, text=True,
+                       timeout=timeout)
+    print(r.stdout[-4000:])
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-6000:]
+    assert r.stdout.rstrip().endswith(f"ok {case}")
+    return r.stdout
+
+
+@pytest.mark.parametrize("kind", ["taints", "many-keys", "list-key", "unindexed"])
+def test_every_path_after_an_apply(built, kind):
+    """per node count: the matrix, then three rounds of [apply -> the matrix]; the applies rotate over plain, FIRST_PER_NODE, RELEASE and
+    both, with and without ok, on the previous evaluation's device bindings and on random ones"""
+    run("single", {"kind": kind, "nodes": NODES, "pods": 2000, "pods_big": 600, "rounds": 3})
+
+
+def test_snapshot_sizes_and_updates_between_applies_on_one_ctx(built):
+    """50 000 -> 300 -> 4097 -> 1 -> 60 000 nodes on one ctx: the apply scratch is kept while the snapshot shrinks and regrows, then
+    reallocated; updates of the applied tiles between two applies, no host wait"""
+    run("sizes", {"nodes": [50_000, 300, 4097, 1, 60_000]})
+
+
+def test_a_batch_longer_than_one_stride_of_the_pod_kernels(built):
+    """600 000 pods (the pod passes launch at most 2048 x 256 threads): some nodes' first eligible pod lies past pod 524 288"""
+    run("large", {"pods": 600_000}, timeout=600)

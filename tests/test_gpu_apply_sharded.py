@@ -57,6 +57,17 @@ def test_chain_bestfit_at_c5_shard(built):
     run("chain", {"n": 2, "mode": "bestfit"}, timeout=900)
 
 
+@pytest.mark.parametrize("n", [1, 2, 3])
+def test_every_replica_evaluates_right_after_a_sharded_apply(built, n):
+    """the select pick, the waves-form riding pick, ksched_explain, the direct kernel and list-key best fit on every replica, against the
+    oracle; n = 1 over the real RCCL"""
+    run("paths", {"n": n, "nodes": [63, 4097, 50_000]}, hooks=n > 1, timeout=900)
+
+
+def test_shards_longer_than_one_stride_of_the_pod_kernels(built):
+    run("large", {}, timeout=600)
+
+
 def test_scratch_is_idle_after_either_apply(built):
     run("scratch", {"n": 3})
 

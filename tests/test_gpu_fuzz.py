@@ -1,6 +1,7 @@
 """A short run of the randomised differential test (tools/fuzz_parity.py): random shapes, key counts / cardinalities (rows, list
-keys, more than eight keys), taints, predicate subsets, both picks, snapshot updates between evaluations, both kernels -- every
-mask word and binding against the oracle.  (A 240 s run of the same tool: 1217 cases, 0 failures.)"""
+keys, more than eight keys), taints, predicate subsets, both picks, snapshot updates and on-device applies of the previous
+evaluation's bindings between evaluations, both kernels -- every mask word and binding against the oracle.  (A 240 s run of the same
+tool: 1217 cases, 0 failures.)"""
 import os
 import subprocess
 import sys
@@ -15,6 +16,7 @@ def test_fuzz_parity_short(built):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_parity.py"), "12", "20260923"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert "0 failures" in r.stdout
+    assert "'apply': " in r.stdout, "no case applied an evaluation's bindings on the device"
 
 
 def test_fuzz_parity_short_with_the_multi_device_sequence(built):
@@ -29,3 +31,4 @@ def test_fuzz_parity_short_with_the_multi_device_sequence(built):
     print(r.stdout[-1500:])
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "gathered-over-" in r.stdout and " 0 failures" in r.stdout
+    assert "'apply': " in r.stdout and "'sharded-apply-over-" in r.stdout, "no case applied bindings on the device, or none over replicas"

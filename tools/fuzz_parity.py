@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Randomised differential test of the HIP path against the oracle (GPU box): random shapes, key counts and cardinalities (incl.
 list keys and > 8 keys), taints, predicate subsets, both picks, snapshot updates between evaluations, both kernels, per-pair reasons (ksched_explain),
+on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
+ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts),
 the two halves of ksched_eval over 1 .. 5 row shards (ksched_shard_bounds / ksched_eval_begin / ksched_eval_end) and -- with the test hooks on
 (KSCHED_TEST_HOOKS=1 KSCHED_RCCL_LIB=tests/cpp/libfake_rccl.so) -- the whole multi-device sequence over 2 .. 4 evaluators on the one GPU:
 ksched_comm_create_local, ksched_eval_begin on every replica, ksched_gather_buffer, ksched_allgather_bindings_local, ksched_eval_end(gathered_0).
@@ -10,6 +12,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from kube_scheduler_rs_reference_amd import Evaluator, _lib as L
 from oracle import capi
+# the exact-integer apply rule (oracle_ref.apply_bindings_exact) under the name the GPU tests import it by: through that name the tool
+# also runs with an oracle/ that predates the shared restatement
+from tests.test_gpu_apply_bindings import restate as apply_bindings_exact
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -21,6 +26,77 @@ if HOOKS and not hasattr(L.load(), "ksched_test_hooks_linked"):  # the stand-in 
     print("fuzz: KSCHED_TEST_HOOKS is set but the loaded library is the shipped one (no hooks): the n > 1 multi-device cases are left out; set KSCHED_LIB=tests/cpp/hooks/libksched_hip.so", flush=True)
     HOOKS = False
 replicas, cliques = [], {}
+
+
+def clique(n_sh):
+    """the first n_sh replicas and their comms (ksched_comm_create_local), made on first use"""
+    import ctypes as C
+    while len(replicas) < n_sh:
+        replicas.append(Evaluator(0))
+    reps = replicas[:n_sh]
+    if n_sh not in cliques:
+        ctxs = (C.c_void_p * n_sh)(*[e._h for e in reps])
+        comms = (C.c_void_p * n_sh)()
+        rcode = ev._lib.ksched_comm_create_local(ctxs, n_sh, comms)
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_comm_create_local", ev._lib.ksched_comm_last_error().decode())
+        cliques[n_sh] = comms
+    return reps, cliques[n_sh]
+
+
+def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm):
+    """apply `bindings` (the previous evaluation's) on the device -- random flags, ok, now and then RELEASE; with the hooks, now and then
+    also as a sharded apply over replicas with ragged cuts, every replica then equal to `ev` -- and advance cpu / mem (in place) by the
+    exact-integer restatement.  -> the number of failures"""
+    import ctypes as C
+    import torch
+    P, N = bindings.shape[0], cpu.shape[0]
+    okv = np.where(r.random(P) < 0.15, 0, r.integers(1, 256, P)).astype(np.uint8) if r.random() < 0.5 else None
+    af = int(r.choice([0, L.APPLY_FIRST_PER_NODE])) | (L.APPLY_RELEASE if r.random() < 0.2 else 0)
+    ncpu, nmem, want_st = apply_bindings_exact(cpu, mem, bindings, rc, rm, okv, af)
+    dev = torch.device("cuda:0")
+    bt, rct, rmt = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (bindings, rc, rm))
+    okt = None if okv is None else torch.from_numpy(okv).to(dev)
+    bad = 0
+    if HOOKS and r.random() < 0.5:
+        n_sh = int(r.choice([2, 3, 4]))
+        reps, comms = clique(n_sh)
+        for e in reps:
+            e.set_nodes(cpu, mem, lab, taints)
+        cut = [0] + sorted(int(x) for x in r.integers(0, P + 1, n_sh - 1)) + [P]
+        sts = [torch.full((cut[q + 1] - cut[q],), -7, dtype=torch.int32, device=dev) for q in range(n_sh)]
+        ptrs = lambda xs: (C.c_void_p * n_sh)(*xs)  # noqa: E731
+        part = lambda x, q, w: None if x is None or cut[q + 1] == cut[q] else x.data_ptr() + w * cut[q]  # noqa: E731
+        rcode = ev._lib.ksched_apply_bindings_sharded_local(
+            C.cast(ptrs([e._h for e in reps]), C.c_void_p), C.cast(comms, C.c_void_p), n_sh,
+            C.cast((C.c_uint32 * n_sh)(*[cut[q + 1] - cut[q] for q in range(n_sh)]), C.c_void_p), C.cast((C.c_uint32 * n_sh)(*cut[:n_sh]), C.c_void_p),
+            C.cast(ptrs([part(bt, q, 4) for q in range(n_sh)]), C.c_void_p), C.cast(ptrs([part(rct, q, 8) for q in range(n_sh)]), C.c_void_p),
+            C.cast(ptrs([part(rmt, q, 8) for q in range(n_sh)]), C.c_void_p), C.cast(ptrs([part(okt, q, 1) for q in range(n_sh)]), C.c_void_p) if okt is not None else None,
+            af, C.cast(ptrs([s_.data_ptr() if s_.numel() else None for s_ in sts]), C.c_void_p), None)
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_apply_bindings_sharded_local", ev._lib.ksched_comm_last_error().decode())
+        torch.cuda.synchronize()
+        st_sh = np.concatenate([s_.cpu().numpy() for s_ in sts])
+        cols = [e.read_nodes() for e in reps]
+        if not (np.array_equal(st_sh, want_st) and all(np.array_equal(c_[0], ncpu) and np.array_equal(c_[1], nmem) for c_ in cols)):
+            bad += 1
+            print(f"FAIL sharded apply case seed {cs}: N={N} P={P} flags={af} ok={okv is not None} cuts={cut}", flush=True)
+        picks[f"sharded-apply-over-{n_sh}"] = picks.get(f"sharded-apply-over-{n_sh}", 0) + 1
+    else:
+        reps = []
+    st = torch.full((P,), -7, dtype=torch.int32, device=dev)
+    ev.apply_bindings_device(bt, rct, rmt, okt, af, st)
+    torch.cuda.synchronize()
+    got = ev.read_nodes()
+    if not (np.array_equal(st.cpu().numpy(), want_st) and np.array_equal(got[0], ncpu) and np.array_equal(got[1], nmem)):
+        bad += 1
+        print(f"FAIL apply case seed {cs}: N={N} P={P} flags={af} ok={okv is not None}", flush=True)
+    if reps and any(e.index_checksum() != ev.index_checksum() for e in reps):
+        bad += 1
+        print(f"FAIL sharded apply index case seed {cs}: N={N} P={P} flags={af} replicas={len(reps)}", flush=True)
+    picks["apply"] = picks.get("apply", 0) + 1
+    cpu[:], mem[:] = ncpu, nmem
+    return bad
 t_end = time.time() + budget
 cases = fails = 0
 picks = {}
@@ -66,8 +142,11 @@ while time.time() < t_end:
         ev.set_option(L.OPT_ROUND_ORDER, int(r.choice([0, 0, 1, 2])))  # which wave takes which round: same results
         ev.set_option(L.OPT_FUSED_PICK, int(r.choice([0, 1, 1, 2])))  # 3 (tile tests or E_UNSUPPORTED) below, where it applies
         ev.set_nodes(cpu, mem, lab, taints)
-        for step in range(int(r.choice([1, 1, 3]))):
-            if step:  # a snapshot update between evaluations
+        last_b = None
+        for step in range(int(r.choice([1, 2, 3]))):
+            if step and last_b is not None and r.random() < 0.6:  # the previous evaluation's bindings applied on the device
+                fails += apply_step(r, cs, cpu, mem, lab, taints, last_b, rc, rm)
+            elif step:  # a snapshot update between evaluations
                 idx = r.integers(0, N, int(r.choice([1, 5, 40, N]))).astype(np.uint32)
                 nc, nm = r.integers(-scale, 64 * scale, idx.size).astype(np.int64), r.integers(-scale, 64 * scale, idx.size).astype(np.int64)
                 ev.update_nodes(idx, nc, nm)
@@ -83,6 +162,8 @@ while time.time() < t_end:
                     fails += 1
                     print(f"FAIL case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} flags={flags:#x} kernel={kernel}/{ev.last_kernel} pick={ev.last_pick} step={step}", flush=True)
                 picks[ev.last_pick] = picks.get(ev.last_pick, 0) + 1
+                if pick:
+                    last_b = got.binding.copy()
             if pick == L.PICK_SAMPLED and K <= 8 and not (preds & L.TAINT):  # the tile-test form of the riding pick, forced
                 ev.set_kernel("fused")
                 ev.set_option(L.OPT_FUSED_PICK, 3)
@@ -156,18 +237,8 @@ while time.time() < t_end:
         if HOOKS and pick and r.random() < 0.35:
             import ctypes as C
             n_sh = int(r.choice([2, 3, 4]))
-            while len(replicas) < n_sh:
-                replicas.append(Evaluator(0))
-            reps = replicas[:n_sh]
+            reps, comms = clique(n_sh)
             lib = ev._lib
-            if n_sh not in cliques:
-                ctxs = (C.c_void_p * n_sh)(*[e._h for e in reps])
-                comms = (C.c_void_p * n_sh)()
-                rcode = lib.ksched_comm_create_local(ctxs, n_sh, comms)
-                if rcode != 0:
-                    raise L.KschedError(rcode, "ksched_comm_create_local", lib.ksched_comm_last_error().decode())
-                cliques[n_sh] = comms
-            comms = cliques[n_sh]
             for e in reps:  # the snapshot is replicated (the current values: the updates above are in cpu / mem)
                 e.set_option(L.OPT_BESTFIT_STAGES, int(r.choice([0, 1, 2])))
                 e.set_nodes(cpu, mem, lab, taints)
