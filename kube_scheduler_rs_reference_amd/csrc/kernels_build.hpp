@@ -15,11 +15,11 @@
 //                         rows  = {n : lr[n] >= c}, c = 0..128: one wave ballot per (row, word)
 //   k_build_tile_named  grid tiles x 1024: valid row, taint subset rows (ballots), label (key, value) rows (LDS atomic OR)
 //   k_patch_nodes       ksched_update_nodes: scatter the new `available` values into the columns
-//   k_apply_*           ksched_apply_bindings_device: claim (first pod per node), accumulate (exact split sums per node),
-//                       commit (new values, overflow check, per dirty tile) and status; k_build_tile_fit then re-indexes the dirty tiles
-//   k_apply_claim_merge, k_apply_commit_gathered
-//                       ksched_apply_bindings_sharded*: the same passes over one rank's rows, with the per-node claims and partial sums
-//                       of every rank all-gathered and merged before the commit (ksched_api.hip "multi-GPU")
+//   k_apply_*           ksched_apply_bindings_device / _sharded*, one pipeline over one rank's rows: claim (first pod per node),
+//                       accumulate (exact split sums per node), commit (new values, overflow check, per dirty tile) and status;
+//                       k_build_tile_fit then re-indexes the dirty tiles.  With a communicator only, the claims and the partial sums of
+//                       every rank are all-gathered between the passes: k_apply_claim_merge takes the per-node minimum claim and
+//                       k_apply_commit_gathered commits the merged sums in place of k_apply_commit (ksched_api.hip "applying")
 //   k_bf_*              best-fit order and its row bitmaps (built lazily, on the first PICK_BESTFIT after a change)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -287,7 +287,10 @@ __global__ __launch_bounds__(256) void k_patch_nodes(const PatchArgs a) {
     a.nrec[(size_t)kNodeRecWords * node + 1] = m;
 }
 
-// ---- ksched_apply_bindings_device -----------------------------------------------------------------------------------------
+// ---- ksched_apply_bindings_device / _sharded* ------------------------------------------------------------------------------
+// One pipeline per rank over that rank's rows (the whole batch of a single-ctx call): claim (FIRST_PER_NODE), accumulate, commit,
+// then status.  Only with a communicator: the claims and the sums are all-gathered between the passes (section below), and
+// k_apply_commit_gathered commits the merged sums in place of k_apply_commit.
 // available[node] -= (or +=) the sum of the requests of the eligible accepted pods bound to it, exactly.  Each request is split
 // into a signed high half h = req >> 32 and an unsigned low half l = req & 0xFFFFFFFF (req = h * 2^32 + l); the halves of both
 // resources are summed per node with 64-bit integer atomics (order-independent, so the sums are the same bits on every run).  With
@@ -295,10 +298,11 @@ __global__ __launch_bounds__(256) void k_patch_nodes(const PatchArgs a) {
 // old -/+ (sum h * 2^32 + sum l) in 128 bits and keeps the node unchanged when either resource leaves int64.
 //
 // Scratch (ksched_ctx, per node / per tile), all of it back in its idle state when a call's last pass has run:
-//   acc[4 * node]  : sum h cpu, sum l cpu, sum h mem, sum l mem -- idle 0; the commit pass zeroes what it read
+//   acc[4 * node]  : sum h cpu, sum l cpu, sum h mem, sum l mem -- idle 0; the commit pass zeroes what this rank wrote
 //   claim[node]    : lowest eligible pod index (FIRST_PER_NODE) -- idle 0xFFFFFFFF; the commit pass resets it
 //   ovf[node]      : 1 when the node's new values left int64 -- written by every commit of the node's tile, read only for nodes of that call
-//   dirty[tiles+1] : dirty[t] == dirty[tiles] (the call's generation) <=> tile t holds a node an accepted pod is bound to; never cleared
+//   dirty[tiles+1] : dirty[t] == dirty[tiles] (the call's generation) <=> tile t holds a node an accepted pod is bound to (marked by the
+//                    accumulate pass), or with a communicator a node that changed (marked by k_apply_commit_gathered); never cleared
 constexpr uint32_t kApplyUnclaimed = 0xFFFFFFFFu;
 struct ApplyArgs {
     const int32_t *bindings;
@@ -373,6 +377,26 @@ __device__ __forceinline__ bool apply_exact(int64_t old, uint64_t h, uint64_t l,
     return true;
 }
 
+// the commit of one node: its summed halves applied to both resources, ovf set, the columns and node record words 0 and 1 (the words
+// k_patch_nodes writes) stored when both fit; true when the node changed.  Sums of zero (nothing bound here, or requests of zero)
+// leave it unchanged.
+__device__ __forceinline__ bool apply_node(const ApplyArgs &a, uint32_t node, uint64_t hc, uint64_t lc, uint64_t hm, uint64_t lm) {
+    bool changed = false, fits = true;
+    if ((hc | lc | hm | lm) != 0ull) {
+        int64_t c, m;
+        fits = apply_exact(a.ncpu[node], hc, lc, a.release, &c) && apply_exact(a.nmem[node], hm, lm, a.release, &m);
+        if (fits) {
+            a.ncpu[node] = c;
+            a.nmem[node] = m;
+            a.nrec[(size_t)kNodeRecWords * node] = c;
+            a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+            changed = true;
+        }
+    }
+    a.ovf[node] = fits ? 0 : 1;
+    return changed;
+}
+
 // commit pass: a block per tile, a thread per node; clean tiles exit at once
 __global__ __launch_bounds__(1024) void k_apply_commit(const ApplyArgs a) {
     const uint32_t tile = blockIdx.x;
@@ -382,19 +406,8 @@ __global__ __launch_bounds__(1024) void k_apply_commit(const ApplyArgs a) {
     uint64_t *q = a.acc + 4u * (size_t)node;
     const uint64_t hc = q[0], lc = q[1], hm = q[2], lm = q[3];
     if (a.first_per_node) a.claim[node] = kApplyUnclaimed;
-    if ((hc | lc | hm | lm) == 0ull) {  // nothing bound here (or requests of zero): unchanged
-        a.ovf[node] = 0;
-        return;
-    }
-    q[0] = q[1] = q[2] = q[3] = 0ull;
-    int64_t c, m;
-    const bool fits = apply_exact(a.ncpu[node], hc, lc, a.release, &c) && apply_exact(a.nmem[node], hm, lm, a.release, &m);
-    a.ovf[node] = fits ? 0 : 1;
-    if (!fits) return;
-    a.ncpu[node] = c;
-    a.nmem[node] = m;
-    a.nrec[(size_t)kNodeRecWords * node] = c;
-    a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+    if ((hc | lc | hm | lm) != 0ull) q[0] = q[1] = q[2] = q[3] = 0ull;
+    apply_node(a, node, hc, lc, hm, lm);
 }
 
 // ---- ksched_apply_bindings_sharded*: the per-node scratch of every rank, all-gathered --------------------------------------------
@@ -436,19 +449,7 @@ __global__ __launch_bounds__(1024) void k_apply_commit_gathered(const ApplyArgs 
             }
         }
         if (a.first_per_node && a.claim[node] != kApplyUnclaimed) a.claim[node] = kApplyUnclaimed;
-        bool fits = true;
-        if ((hc | lc | hm | lm) != 0ull) {
-            int64_t c, m;
-            fits = apply_exact(a.ncpu[node], hc, lc, a.release, &c) && apply_exact(a.nmem[node], hm, lm, a.release, &m);
-            if (fits) {
-                a.ncpu[node] = c;
-                a.nmem[node] = m;
-                a.nrec[(size_t)kNodeRecWords * node] = c;
-                a.nrec[(size_t)kNodeRecWords * node + 1] = m;
-                changed = true;
-            }
-        }
-        a.ovf[node] = fits ? 0 : 1;
+        changed = apply_node(a, node, hc, lc, hm, lm);
     }
     if (__syncthreads_or(changed) && threadIdx.x == 0) a.dirty[tile] = a.gen;
 }

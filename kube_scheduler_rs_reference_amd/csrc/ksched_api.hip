@@ -364,6 +364,19 @@ int snapshot_end(ksched_ctx *c) {
     return KSCHED_OK;
 }
 
+// A snapshot change that can stop halfway, by an error return or a throw: once snapshot_begin has succeeded (`c` set), the ctx refuses
+// evaluations until its next ksched_set_nodes unless the change is marked done -- columns, index and apply scratch may disagree.
+struct SnapshotChange {
+    ksched_ctx *c = nullptr;
+    bool done = false;
+    ~SnapshotChange() {
+        if (c && !done) {
+            c->have_nodes = false;
+            c->apply_n = 0;
+        }
+    }
+};
+
 // pinned staging: returns a host pointer to `bytes` bytes whose previous use (an async copy) has completed
 int stage_reserve(ksched_ctx *c, size_t bytes, uint8_t **out) {
     if (c->h_stage) HIPCHK(c, hipEventSynchronize(c->ev_stage));
@@ -1376,11 +1389,8 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
     tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
     // evaluations already enqueued read the snapshot as it was (events, no host wait)
     if (int rc = snapshot_begin(c)) return rc;
+    SnapshotChange chg{c};
     hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
-    auto fail = [&](int rc) {
-        c->have_nodes = false;  // columns, index and best-fit order may now disagree: refuse evaluations until the next ksched_set_nodes
-        return rc;
-    };
     PatchArgs pa{};
     pa.ncpu = c->ncpu.ptr;
     pa.nmem = c->nmem.ptr;
@@ -1398,7 +1408,7 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
     } else {
         const size_t b_idx = ((size_t)m * 4 + 7) & ~(size_t)7, b_val = (size_t)m * 8, b_tiles = tiles.size() * 4;
         uint8_t *h = nullptr;
-        if (int rc = stage_reserve(c, b_idx + 2 * b_val + b_tiles, &h)) return fail(rc);
+        if (int rc = stage_reserve(c, b_idx + 2 * b_val + b_tiles, &h)) return rc;
         uint32_t *hi = reinterpret_cast<uint32_t *>(h);
         int64_t *hc = reinterpret_cast<int64_t *>(h + b_idx), *hm = hc + m;
         for (uint32_t j = 0; j < m; ++j) {
@@ -1407,133 +1417,30 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
             hm[j] = mem[keep[j]];
         }
         memcpy(h + b_idx + 2 * b_val, tiles.data(), b_tiles);
-        if (c->d_stage.reserve(b_idx + 2 * b_val + b_tiles) != hipSuccess) return fail(KSCHED_E_NOMEM);
-        if (hipMemcpyAsync(c->d_stage.ptr, h, b_idx + 2 * b_val + b_tiles, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipEventRecord(c->ev_stage, s) != hipSuccess)
-            return fail(KSCHED_E_HIP);
+        HIPCHK(c, c->d_stage.reserve(b_idx + 2 * b_val + b_tiles));
+        HIPCHK(c, hipMemcpyAsync(c->d_stage.ptr, h, b_idx + 2 * b_val + b_tiles, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipEventRecord(c->ev_stage, s));
         pa.idx = reinterpret_cast<const uint32_t *>(c->d_stage.ptr);
         pa.cpu = reinterpret_cast<const int64_t *>(c->d_stage.ptr + b_idx);
         pa.mem = pa.cpu + m;
         d_tiles = reinterpret_cast<const uint32_t *>(c->d_stage.ptr + b_idx + 2 * b_val);
     }
     if (want_tiles && !d_tiles) {  // small update: the tile list rides in the patch kernel's arguments
-        if (c->d_stage.reserve(kPatchInline * 4) != hipSuccess) return fail(KSCHED_E_NOMEM);
+        HIPCHK(c, c->d_stage.reserve(kPatchInline * 4));
         pa.tile_out = reinterpret_cast<uint32_t *>(c->d_stage.ptr);
         pa.ntiles = (uint32_t)tiles.size();
         for (size_t j = 0; j < tiles.size(); ++j) pa.tiles_in[j] = tiles[j];
         d_tiles = pa.tile_out;
     }
     hipLaunchKernelGGL(k_patch_nodes, dim3((m + 255u) / 256u), dim3(256), 0, s, pa);
-    if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
+    HIPCHK(c, hipGetLastError());
     if (want_tiles) {
         // only the touched 1024-node tiles are re-indexed (fit rows, search trees, cnt tables); label and taint rows are untouched
-        if (int rc = launch_build_fit(c, d_tiles, (uint32_t)tiles.size())) return fail(rc);
+        if (int rc = launch_build_fit(c, d_tiles, (uint32_t)tiles.size())) return rc;
     }
     c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
-    if (int rc = snapshot_end(c)) return fail(rc);
-    return KSCHED_OK;
-} KSCHED_ABI_CATCH(c)
-
-}  // extern "C"
-
-namespace {
-// the apply scratch of ksched_apply_bindings_device / _sharded*, in its idle state for the ctx's node count, and the next generation;
-// the (re)allocation and its memsets run once per snapshot size, on `s`
-int apply_scratch_ready(ksched_ctx *c, hipStream_t s) {
-    const uint32_t n = c->n;
-    if (n > c->apply_n) {
-        c->apply_n = 0;
-        const uint32_t cap = std::max<uint32_t>(n, 1024u), cap_tiles = (cap + kTileNodes - 1) / kTileNodes;
-        if (c->apply_acc.reserve((size_t)cap * 4) != hipSuccess || c->apply_claim.reserve(cap) != hipSuccess ||
-            c->apply_ovf.reserve(cap) != hipSuccess || c->apply_dirty.reserve(cap_tiles + 1u) != hipSuccess)
-            return KSCHED_E_NOMEM;
-        if (hipMemsetAsync(c->apply_acc.ptr, 0, (size_t)cap * 32, s) != hipSuccess ||
-            hipMemsetAsync(c->apply_claim.ptr, 0xFF, (size_t)cap * 4, s) != hipSuccess ||
-            hipMemsetAsync(c->apply_dirty.ptr, 0, (size_t)(cap_tiles + 1u) * 4, s) != hipSuccess)
-            return KSCHED_E_HIP;
-        c->apply_n = cap;
-        c->apply_gen = 0;
-    }
-    if (++c->apply_gen == 0) c->apply_gen = 1;  // (0 is the initial value of every tile's entry)
-    return KSCHED_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
-                                 const uint8_t *ok, uint32_t flags, int32_t *status_out, void *hip_stream) try {
-    if (!c) return KSCHED_E_INVAL;
-    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE)) return KSCHED_E_INVAL;
-    if (p > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (!c->have_nodes) return KSCHED_E_STATE;
-    if (p == 0) return KSCHED_OK;
-    DeviceGuard g(c->device);
-    if (!g.ok) return KSCHED_E_HIP;
-    fault_point(c);  // (nothing has changed yet)
-    const hipStream_t hs = (hipStream_t)hip_stream;
-    const uint32_t n = c->n, tiles = (n + kTileNodes - 1) / kTileNodes;
-    // evaluations already enqueued read the snapshot as it was (snapshot_begin); the change also waits for what `hs` holds (the
-    // evaluation that wrote `bindings`, typically) and `hs` waits for the change (the caller reads status_out there)
-    if (int rc = snapshot_begin(c)) return rc;
-    const hipStream_t s = c->change_stream;
-    auto fail = [&](int rc) {
-        c->have_nodes = false;  // columns, index and scratch may be half-updated: refuse evaluations until the next ksched_set_nodes
-        c->apply_n = 0;
-        return rc;
-    };
-    if (s != hs) {
-        if (!c->ev_apply && hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming) != hipSuccess) return fail(KSCHED_E_HIP);
-        if (hipEventRecord(c->ev_apply, hs) != hipSuccess || hipStreamWaitEvent(s, c->ev_apply, 0) != hipSuccess) return fail(KSCHED_E_HIP);
-    }
-    if (int rc = apply_scratch_ready(c, s)) return fail(rc);
-    ApplyArgs a{};
-    a.bindings = bindings;
-    a.req_cpu = req_cpu;
-    a.req_mem = req_mem;
-    a.ok = ok;
-    a.status = status_out;
-    a.acc = c->apply_acc.ptr;
-    a.claim = c->apply_claim.ptr;
-    a.ovf = c->apply_ovf.ptr;
-    a.dirty = c->apply_dirty.ptr;
-    a.ncpu = c->ncpu.ptr;
-    a.nmem = c->nmem.ptr;
-    a.nrec = c->nrec.ptr;
-    a.p = p;
-    a.n = n;
-    a.tiles = tiles;
-    a.gen = c->apply_gen;
-    a.first_per_node = (flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
-    a.release = (flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
-    const dim3 pod_grid(std::min<uint32_t>((p + 255u) / 256u, 2048u));
-    if (a.first_per_node) {
-        hipLaunchKernelGGL(k_apply_claim, pod_grid, dim3(256), 0, s, a);
-        if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
-    }
-    hipLaunchKernelGGL(k_apply_accumulate, pod_grid, dim3(256), 0, s, a);
-    if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
-    if (tiles > 0) {
-        hipLaunchKernelGGL(k_apply_commit, dim3(tiles), dim3(kTileNodes), 0, s, a);
-        if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
-        if (c->idx.built) {
-            // only the dirty tiles are re-indexed: every tile's block reads its generation and the clean ones exit
-            if (int rc = launch_build_fit(c, nullptr, 0, c->apply_dirty.ptr)) return fail(rc);
-        }
-        if (status_out) {
-            hipLaunchKernelGGL(k_apply_status, pod_grid, dim3(256), 0, s, a);
-            if (hipGetLastError() != hipSuccess) return fail(KSCHED_E_HIP);
-        }
-    }
-    c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
-    if (int rc = snapshot_end(c)) return fail(rc);
-    if (s != hs) {  // the caller's stream is behind the change by the event; it has then met this generation
-        if (hipStreamWaitEvent(hs, c->ev_build, 0) != hipSuccess) return fail(KSCHED_E_HIP);
-        if (hs == c->stream) c->own_gen = c->build_gen;
-        for (auto &u : c->user_streams)
-            if (u.s == hs) u.gen = c->build_gen;
-    }
+    if (int rc = snapshot_end(c)) return rc;
+    chg.done = true;
     return KSCHED_OK;
 } KSCHED_ABI_CATCH(c)
 
@@ -2390,40 +2297,47 @@ int ksched_allgather_bindings_local(ksched_comm *const *comms, int n, const int3
 
 }  // extern "C"
 
-// ---- multi-GPU: a sharded batch's bindings applied to every replica (kernels_build.hpp "ksched_apply_bindings_sharded*") ----------
-// Per rank: claim (FIRST_PER_NODE) -> all-gather of claim[n] -> per-node minimum -> accumulate of the rank's rows -> all-gather of
-// acc[n][4] -> commit of the merged sums -> re-index of the dirty tiles -> status of the rank's rows.  Everything of one rank rides
-// its ctx's change stream; the all-gathers are enqueued there too.  The one-process form runs each phase for every rank before the
-// collective that joins them, so the per-device calls of a collective are issued together in one group.
+// ---- applying a batch's bindings (kernels_build.hpp "ksched_apply_bindings_device") ------------------------------------------------
+// One ApplyCall per rank: claim (FIRST_PER_NODE) -> accumulate of the rank's rows -> commit -> re-index of the dirty tiles -> status of
+// the rank's rows.  The single-ctx call is one rank without a communicator.  With one, each rank passes its own rows of a row-sharded
+// batch, the claims and the partial sums are all-gathered between the phases, and the commit merges them.  Everything of one rank rides
+// its ctx's change stream; the all-gathers are enqueued there too.  The runner takes each phase through every rank before the
+// collective that joins them, so the one-process form issues the per-device calls of a collective together in one group.
 namespace {
 
-struct ShardedApply {
+struct ApplyCall {
     ksched_ctx *c = nullptr;
-    ksched_comm *q = nullptr;
+    ksched_comm *q = nullptr;  // nullptr: the single-ctx call (no collectives)
     hipStream_t hs = nullptr;  // the caller's stream
+    uint32_t count = 0;        // the rank's rows
     ApplyArgs a{};
-    uint32_t count = 0;
-    bool entered = false;      // snapshot_begin ran: a failure from here on invalidates the snapshot
-};
-
-// a failure of any rank after some rank's snapshot has started to change leaves the replicas possibly different: every ctx that
-// entered the call refuses evaluations until its next ksched_set_nodes
-struct ShardedInvalidate {
-    std::vector<ShardedApply> &v;
-    bool done = false;
-    ~ShardedInvalidate() {
-        if (done) return;
-        for (ShardedApply &x : v)
-            if (x.entered) {
-                x.c->have_nodes = false;
-                x.c->apply_n = 0;
-            }
-    }
+    SnapshotChange chg;        // marked done when every rank's change has finished
 };
 
 dim3 pod_grid(uint32_t p) { return dim3(std::min<uint32_t>((p + 255u) / 256u, 2048u)); }
 
-// argument checks of one rank that need no lock and no device
+// the apply scratch in its idle state for the ctx's node count, and the next generation; the (re)allocation and its memsets run once per
+// snapshot size, on `s`
+int apply_scratch_ready(ksched_ctx *c, hipStream_t s) {
+    const uint32_t n = c->n;
+    if (c->apply_n == 0 || n > c->apply_n) {  // (an empty snapshot needs the scratch too: the accumulate pass writes dirty[0])
+        c->apply_n = 0;
+        const uint32_t cap = std::max<uint32_t>(n, 1024u), cap_tiles = (cap + kTileNodes - 1) / kTileNodes;
+        HIPCHK(c, c->apply_acc.reserve((size_t)cap * 4));
+        HIPCHK(c, c->apply_claim.reserve(cap));
+        HIPCHK(c, c->apply_ovf.reserve(cap));
+        HIPCHK(c, c->apply_dirty.reserve(cap_tiles + 1u));
+        HIPCHK(c, hipMemsetAsync(c->apply_acc.ptr, 0, (size_t)cap * 32, s));
+        HIPCHK(c, hipMemsetAsync(c->apply_claim.ptr, 0xFF, (size_t)cap * 4, s));
+        HIPCHK(c, hipMemsetAsync(c->apply_dirty.ptr, 0, (size_t)(cap_tiles + 1u) * 4, s));
+        c->apply_n = cap;
+        c->apply_gen = 0;
+    }
+    if (++c->apply_gen == 0) c->apply_gen = 1;  // (0 is the initial value of every tile's entry)
+    return KSCHED_OK;
+}
+
+// argument checks of one rank of a sharded call that need no lock and no device
 int sharded_check(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu,
                   const int64_t *req_mem, uint32_t flags) {
     if (!c || !q || !q->comm) return KSCHED_E_INVAL;
@@ -2434,13 +2348,15 @@ int sharded_check(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo
     return KSCHED_OK;
 }
 
-// phase 1 (the ctx's mutex held, its device current): order the change, ready the scratch, claim the rank's rows
-int sharded_begin(ShardedApply &x, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
-                  const uint8_t *ok, uint32_t flags, int32_t *status_out) {
+// phase 1 (the ctx's mutex held, its device current): order the change, ready the scratch, claim the rank's rows.  Evaluations already
+// enqueued read the snapshot as it was (snapshot_begin); the change also waits for what the caller's stream holds (the evaluation that
+// wrote `bindings`, typically).
+int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
+                const uint8_t *ok, uint32_t flags, int32_t *status_out) {
     ksched_ctx *c = x.c;
     fault_point(c);  // (nothing has changed yet)
     if (int rc = snapshot_begin(c)) return rc;
-    x.entered = true;
+    x.chg.c = c;
     const hipStream_t s = c->change_stream;
     if (s != x.hs) {
         if (!c->ev_apply) HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
@@ -2449,7 +2365,7 @@ int sharded_begin(ShardedApply &x, uint32_t row_lo, const int32_t *bindings, con
     }
     if (int rc = apply_scratch_ready(c, s)) return rc;
     const uint32_t n = c->n;
-    if (c->apply_gath.reserve((size_t)x.q->nranks * n * 4) != hipSuccess) return KSCHED_E_NOMEM;
+    if (x.q) HIPCHK(c, c->apply_gath.reserve((size_t)x.q->nranks * n * 4));
     ApplyArgs &a = x.a;
     a.bindings = bindings;
     a.req_cpu = req_cpu;
@@ -2469,48 +2385,55 @@ int sharded_begin(ShardedApply &x, uint32_t row_lo, const int32_t *bindings, con
     a.gen = c->apply_gen;
     a.first_per_node = (flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
     a.release = (flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
-    a.row_lo = row_lo;
-    a.sharded = 1;
-    a.gathered = c->apply_gath.ptr;
-    a.nranks = (uint32_t)x.q->nranks;
-    a.rank = (uint32_t)x.q->rank;
-    if (a.first_per_node && x.count > 0 && n > 0) {
-        hipLaunchKernelGGL(k_apply_claim, pod_grid(x.count), dim3(256), 0, s, a);
+    if (x.q) {
+        a.row_lo = row_lo;
+        a.sharded = 1;
+        a.gathered = c->apply_gath.ptr;
+        a.nranks = (uint32_t)x.q->nranks;
+        a.rank = (uint32_t)x.q->rank;
+    }
+    if (a.first_per_node && a.p > 0 && n > 0) {
+        hipLaunchKernelGGL(k_apply_claim, pod_grid(a.p), dim3(256), 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
     return KSCHED_OK;
 }
 
-// phase 2 (FIRST_PER_NODE, after the claims' all-gather): the batch's claim per node; then the rank's accumulate pass
-int sharded_accumulate(ShardedApply &x) {
+// phase 2: with a communicator and FIRST_PER_NODE (after the claims' all-gather), the batch's claim per node; then the rank's
+// accumulate pass
+int apply_accumulate(ApplyCall &x) {
     ksched_ctx *c = x.c;
     const hipStream_t s = c->change_stream;
-    if (x.a.first_per_node && x.a.n > 0) {
+    if (x.q && x.a.first_per_node && x.a.n > 0) {
         hipLaunchKernelGGL(k_apply_claim_merge, dim3(std::min<uint32_t>((x.a.n + 255u) / 256u, 1024u)), dim3(256), 0, s, x.a);
         HIPCHK(c, hipGetLastError());
     }
-    if (x.count > 0) {
-        hipLaunchKernelGGL(k_apply_accumulate, pod_grid(x.count), dim3(256), 0, s, x.a);
+    if (x.a.p > 0) {
+        hipLaunchKernelGGL(k_apply_accumulate, pod_grid(x.a.p), dim3(256), 0, s, x.a);
         HIPCHK(c, hipGetLastError());
     }
     return KSCHED_OK;
 }
 
-// phase 3 (after the partial sums' all-gather): commit, re-index, status; the caller's stream waits for the change
-int sharded_finish(ShardedApply &x) {
+// phase 3 (with a communicator, after the partial sums' all-gather): commit, re-index, status; the caller's stream waits for the change
+// (the caller reads status_out there) and has then met this generation
+int apply_finish(ApplyCall &x) {
     ksched_ctx *c = x.c;
     const hipStream_t s = c->change_stream;
     if (x.a.tiles > 0) {
-        hipLaunchKernelGGL(k_apply_commit_gathered, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
+        if (x.q) hipLaunchKernelGGL(k_apply_commit_gathered, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
+        else hipLaunchKernelGGL(k_apply_commit, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
         HIPCHK(c, hipGetLastError());
-        if (c->idx.built)
+        if (c->idx.built) {
+            // only the dirty tiles are re-indexed: every tile's block reads its generation and the clean ones exit
             if (int rc = launch_build_fit(c, nullptr, 0, c->apply_dirty.ptr)) return rc;
+        }
+        if (x.a.status && x.a.p > 0) {  // (every status but OVERFLOW is final after the accumulate pass; with no node, all of them)
+            hipLaunchKernelGGL(k_apply_status, pod_grid(x.a.p), dim3(256), 0, s, x.a);
+            HIPCHK(c, hipGetLastError());
+        }
     }
-    if (x.a.status && x.count > 0) {  // (every status but OVERFLOW is final after the accumulate pass)
-        hipLaunchKernelGGL(k_apply_status, pod_grid(x.count), dim3(256), 0, s, x.a);
-        HIPCHK(c, hipGetLastError());
-    }
-    c->bf_dirty = true;
+    c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
     if (int rc = snapshot_end(c)) return rc;
     if (s != x.hs) {
         HIPCHK(c, hipStreamWaitEvent(x.hs, c->ev_build, 0));
@@ -2521,44 +2444,48 @@ int sharded_finish(ShardedApply &x) {
     return KSCHED_OK;
 }
 
-// the whole call over the ranks in `v` (their mutexes held): the phases of every rank between the collectives
-int sharded_run(std::vector<ShardedApply> &v, const uint32_t *row_lo, const int32_t *const *bindings, const int64_t *const *req_cpu,
-                const int64_t *const *req_mem, const uint8_t *const *ok, uint32_t flags, int32_t *const *status_out) {
-    const int k = (int)v.size();
-    for (int i = 0; i < k; ++i) {
-        DeviceGuard g(v[i].c->device);
-        if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = sharded_begin(v[i], row_lo[i], bindings[i], req_cpu[i], req_mem[i], ok ? ok[i] : nullptr, flags,
-                                   status_out ? status_out[i] : nullptr))
-            return rc;
-    }
-    const uint32_t n = v[0].a.n;
+// one grouped all-gather, on the ranks' change streams, of every rank's claims (or sums) into its apply_gath
+int apply_allgather(ApplyCall *v, int k, bool claims, size_t count, const char *what) {
     std::vector<ksched_comm *> comms(k);
     std::vector<const void *> send(k);
     std::vector<void *> recv(k), streams(k);
     for (int i = 0; i < k; ++i) {
         comms[i] = v[i].q;
+        send[i] = claims ? (const void *)v[i].c->apply_claim.ptr : (const void *)v[i].c->apply_acc.ptr;
         recv[i] = v[i].c->apply_gath.ptr;
         streams[i] = v[i].c->change_stream;
     }
-    if ((flags & KSCHED_APPLY_FIRST_PER_NODE) && n > 0) {
-        for (int i = 0; i < k; ++i) send[i] = v[i].c->apply_claim.ptr;
-        if (int rc = group_allgather(comms.data(), k, send.data(), recv.data(), n, ncclUint32, streams.data(), "ncclAllGather (claims)")) return rc;
-    }
+    return group_allgather(comms.data(), k, send.data(), recv.data(), count, ncclUint32, streams.data(), what);
+}
+
+// the whole call over the k ranks of `v` (their mutexes held): the phases of every rank, and between them the collectives when the
+// ranks have a communicator.  Any failure leaves every ctx that entered the call invalidated (ApplyCall::chg).
+int apply_run(ApplyCall *v, int k, const uint32_t *row_lo, const int32_t *const *bindings, const int64_t *const *req_cpu,
+              const int64_t *const *req_mem, const uint8_t *const *ok, uint32_t flags, int32_t *const *status_out) {
     for (int i = 0; i < k; ++i) {
         DeviceGuard g(v[i].c->device);
         if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = sharded_accumulate(v[i])) return rc;
+        if (int rc = apply_begin(v[i], row_lo[i], bindings[i], req_cpu[i], req_mem[i], ok ? ok[i] : nullptr, flags,
+                                 status_out ? status_out[i] : nullptr))
+            return rc;
     }
-    if (n > 0) {  // the split sums as 32-bit words: 8 per node
-        for (int i = 0; i < k; ++i) send[i] = v[i].c->apply_acc.ptr;
-        if (int rc = group_allgather(comms.data(), k, send.data(), recv.data(), (size_t)n * 8, ncclUint32, streams.data(), "ncclAllGather (sums)")) return rc;
-    }
+    const uint32_t n = v[0].a.n;
+    const bool comm = v[0].q != nullptr;
+    if (comm && (flags & KSCHED_APPLY_FIRST_PER_NODE) && n > 0)
+        if (int rc = apply_allgather(v, k, true, n, "ncclAllGather (claims)")) return rc;
     for (int i = 0; i < k; ++i) {
         DeviceGuard g(v[i].c->device);
         if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = sharded_finish(v[i])) return rc;
+        if (int rc = apply_accumulate(v[i])) return rc;
     }
+    if (comm && n > 0)  // the split sums as 32-bit words: 8 per node
+        if (int rc = apply_allgather(v, k, false, (size_t)n * 8, "ncclAllGather (sums)")) return rc;
+    for (int i = 0; i < k; ++i) {
+        DeviceGuard g(v[i].c->device);
+        if (!g.ok) return KSCHED_E_HIP;
+        if (int rc = apply_finish(v[i])) return rc;
+    }
+    for (int i = 0; i < k; ++i) v[i].chg.done = true;
     return KSCHED_OK;
 }
 
@@ -2566,21 +2493,34 @@ int sharded_run(std::vector<ShardedApply> &v, const uint32_t *row_lo, const int3
 
 extern "C" {
 
+int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
+                                 const uint8_t *ok, uint32_t flags, int32_t *status_out, void *hip_stream) try {
+    if (!c) return KSCHED_E_INVAL;
+    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE)) return KSCHED_E_INVAL;
+    if (p > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    if (p == 0) return KSCHED_OK;
+    const uint32_t row_lo = 0;
+    ApplyCall x;
+    x.c = c;
+    x.hs = (hipStream_t)hip_stream;
+    x.count = p;
+    return apply_run(&x, 1, &row_lo, &bindings, &req_cpu, &req_mem, &ok, flags, &status_out);
+} KSCHED_ABI_CATCH(c)
+
 int ksched_apply_bindings_sharded(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo, const int32_t *bindings,
                                   const int64_t *req_cpu, const int64_t *req_mem, const uint8_t *ok, uint32_t flags, int32_t *status_out,
                                   void *hip_stream) try {
     if (int rc = sharded_check(c, q, count, row_lo, bindings, req_cpu, req_mem, flags)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    std::vector<ShardedApply> v(1);
-    v[0].c = c;
-    v[0].q = q;
-    v[0].hs = (hipStream_t)hip_stream;
-    v[0].count = count;
-    ShardedInvalidate inv{v};
-    const int rc = sharded_run(v, &row_lo, &bindings, &req_cpu, &req_mem, ok ? &ok : nullptr, flags, status_out ? &status_out : nullptr);
-    inv.done = rc == KSCHED_OK;
-    return rc;
+    ApplyCall x;
+    x.c = c;
+    x.q = q;
+    x.hs = (hipStream_t)hip_stream;
+    x.count = count;
+    return apply_run(&x, 1, &row_lo, &bindings, &req_cpu, &req_mem, &ok, flags, &status_out);
 } KSCHED_ABI_CATCH_COMM
 
 int ksched_apply_bindings_sharded_local(ksched_ctx *const *ctxs, ksched_comm *const *comms, int n, const uint32_t *count,
@@ -2604,17 +2544,14 @@ int ksched_apply_bindings_sharded_local(ksched_ctx *const *ctxs, ksched_comm *co
         if (!ctxs[i]->have_nodes) return KSCHED_E_STATE;
     for (int i = 1; i < n; ++i)
         if (ctxs[i]->n != ctxs[0]->n) return KSCHED_E_INVAL;  // replicas of one snapshot
-    std::vector<ShardedApply> v((size_t)n);
+    std::vector<ApplyCall> v((size_t)n);  // (destroyed before the locks are released)
     for (int i = 0; i < n; ++i) {
         v[i].c = ctxs[i];
         v[i].q = comms[i];
         v[i].hs = hip_streams ? (hipStream_t)hip_streams[i] : nullptr;
         v[i].count = count[i];
     }
-    ShardedInvalidate inv{v};
-    const int rc = sharded_run(v, row_lo, bindings, req_cpu, req_mem, ok, flags, status_out);
-    inv.done = rc == KSCHED_OK;
-    return rc;
+    return apply_run(v.data(), n, row_lo, bindings, req_cpu, req_mem, ok, flags, status_out);
 } KSCHED_ABI_CATCH_COMM
 
 int ksched_index_checksum(ksched_ctx *c, uint64_t *out) try {

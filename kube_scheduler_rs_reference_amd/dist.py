@@ -30,6 +30,8 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .evaluator import _apply_args
+
 
 class _EventWork:
     """`.wait()` orders the current stream after a recorded event (the stream-ordered equivalent of a torch Work)."""
@@ -144,25 +146,6 @@ class AbiComm:
             self.close()
         except Exception:
             pass
-
-
-def _apply_args(ev, bindings, req_cpu, req_mem, ok, status_out):
-    """(count, bindings, req_cpu, req_mem, ok, status_out) of one rank, checked, as ctypes values (pointers may be NULL when count is 0)."""
-    import ctypes as C
-    if bindings.dim() != 1:
-        raise ValueError("bindings must be a 1-D int32 tensor")
-    p = int(bindings.shape[0])
-
-    def dp(t, dtypes, name):
-        if t is None:
-            return None
-        if not t.is_cuda or t.device.index != ev.device or not t.is_contiguous() or t.dtype not in dtypes:
-            raise ValueError(f"{name}: expected a contiguous {dtypes} CUDA tensor on cuda:{ev.device}")
-        if tuple(t.shape) != (p,):
-            raise ValueError(f"{name}: expected shape ({p},), got {tuple(t.shape)}")
-        return t.data_ptr() or None
-    return (p, dp(bindings, (torch.int32,), "bindings"), dp(req_cpu, (torch.int64,), "req_cpu"), dp(req_mem, (torch.int64,), "req_mem"),
-            dp(ok, (torch.uint8, torch.bool), "ok"), dp(status_out, (torch.int32,), "status_out"))
 
 
 class LocalClique:

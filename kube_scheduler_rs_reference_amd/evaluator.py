@@ -41,6 +41,27 @@ def _attempts(samples, flags: int, p: int) -> int:
     return int(samples.shape[1])
 
 
+def _apply_args(ev, bindings, req_cpu, req_mem, ok, status_out):
+    """(count, bindings, req_cpu, req_mem, ok, status_out) of one apply on `ev`'s device (one rank's rows of a sharded one), checked: all
+    [count] contiguous CUDA tensors, bindings int32, requests int64, ok uint8/bool, status_out int32.  Pointers as ints, None for an absent
+    tensor (and may be None when count is 0)."""
+    import torch
+    if bindings.dim() != 1:
+        raise ValueError("bindings must be a 1-D int32 tensor")
+    p = int(bindings.shape[0])
+
+    def dp(t, dtypes, name):
+        if t is None:
+            return None
+        if not t.is_cuda or t.device.index != ev.device or not t.is_contiguous() or t.dtype not in dtypes:
+            raise ValueError(f"{name}: expected a contiguous {dtypes} CUDA tensor on cuda:{ev.device}")
+        if tuple(t.shape) != (p,):
+            raise ValueError(f"{name}: expected shape ({p},), got {tuple(t.shape)}")
+        return t.data_ptr() or None
+    return (p, dp(bindings, (torch.int32,), "bindings"), dp(req_cpu, (torch.int64,), "req_cpu"), dp(req_mem, (torch.int64,), "req_mem"),
+            dp(ok, (torch.uint8, torch.bool), "ok"), dp(status_out, (torch.int32,), "status_out"))
+
+
 @dataclass
 class EvalResult:
     feasible: Optional[np.ndarray] = None  # [P, W] uint64
@@ -179,24 +200,10 @@ class Evaluator:
         bindings int32, requests int64, ok uint8/bool or None (= every POST landed), status_out int32 or None.  Enqueued on `stream`
         (default: torch's current stream) behind whatever wrote `bindings` there; the host does not wait."""
         import torch
-        p = int(bindings.shape[0]) if bindings.dim() == 1 else -1
-
-        def dp(t, dtypes, name):
-            if t is None:
-                return None
-            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.dtype not in dtypes:
-                raise ValueError(f"{name}: expected a contiguous {dtypes} CUDA tensor on cuda:{self.device}")
-            if tuple(t.shape) != (p,):
-                raise ValueError(f"{name}: expected shape ({p},), got {tuple(t.shape)}")
-            return C.c_void_p(t.data_ptr())
-        if p < 0:
-            raise ValueError("bindings must be a 1-D int32 tensor")
-        args = (dp(bindings, (torch.int32,), "bindings"), dp(req_cpu_milli, (torch.int64,), "req_cpu_milli"),
-                dp(req_mem_bytes, (torch.int64,), "req_mem_bytes"), dp(ok, (torch.uint8, torch.bool), "ok"))
-        st = dp(status_out, (torch.int32,), "status_out")
+        p, *ptrs = _apply_args(self, bindings, req_cpu_milli, req_mem_bytes, ok, status_out)
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        rc = self._lib.ksched_apply_bindings_device(self._h, p, *args, int(flags), st, C.c_void_p(stream.cuda_stream))
+        rc = self._lib.ksched_apply_bindings_device(self._h, p, *ptrs[:4], int(flags), ptrs[4], C.c_void_p(stream.cuda_stream))
         self._check(rc, "ksched_apply_bindings_device")
 
     def read_nodes(self, first: int = 0, count: Optional[int] = None):

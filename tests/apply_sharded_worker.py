@@ -432,8 +432,34 @@ def case_large(spec):
     R.close()
 
 
+def case_empty(spec):
+    """an apply to a snapshot of no nodes with status_out, through the clique and on one ctx: the statuses are the exact rule's (all of them
+    final after the accumulate pass), and every ctx evaluates right after"""
+    n, P = spec["n"], 700
+    none = np.zeros(0, np.int64)
+    R = Ranks(n, {"avail_cpu_milli": none, "avail_mem_bytes": none})
+    rng = np.random.default_rng(17)
+    for k, flags in enumerate((0, FPN, REL, FPN | REL)):
+        b = rng.integers(-3, 4, P).astype(np.int32)  # unbound, or past the (absent) last node
+        ok = (rng.random(P) > 0.3).astype(np.uint8)
+        rc, rm = rng.integers(0, 1 << 40, P), rng.integers(-(1 << 40), 1 << 40, P)
+        use_ok, bounds = k % 2 == 0, cuts(rng, P, n, ("ragged", "empty")[k // 2])
+        st, want = R.apply(bounds, b, ok, rc, rm, flags, use_ok)
+        what = f"n={n} N=0 flags={flags} ok={use_ok}"
+        R.check_equal(what)
+        exp = restate(none, none, b, rc, rm, ok if use_ok else None, flags)
+        assert np.array_equal(exp[2], want), f"{what}: exact rule"
+        for r in range(n):
+            assert np.array_equal(st[r], want[bounds[r]:bounds[r + 1]]), f"{what}: rank {r} status"
+    z = np.zeros(5, np.int64)
+    for e in R.evs + [R.ref]:
+        res = e.eval(z, z, samples=np.zeros((5, 5), np.uint32), flags=FIT | PICK_SAMPLED)
+        assert res.feasible.shape == (5, 0) and (res.binding == -1).all(), "evaluation after the apply"
+    R.close()
+
+
 CASES = {"equal": case_equal, "scratch": case_scratch, "chain": case_chain, "failure": case_failure, "errors": case_errors,
-         "rank": case_rank, "paths": case_paths, "large": case_large}
+         "rank": case_rank, "paths": case_paths, "large": case_large, "empty": case_empty}
 
 if __name__ == "__main__":
     name = sys.argv[1]

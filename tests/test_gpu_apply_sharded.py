@@ -68,6 +68,10 @@ def test_shards_longer_than_one_stride_of_the_pod_kernels(built):
     run("large", {}, timeout=600)
 
 
+def test_apply_to_an_empty_snapshot(built):
+    run("empty", {"n": 2})
+
+
 def test_scratch_is_idle_after_either_apply(built):
     run("scratch", {"n": 3})
 
