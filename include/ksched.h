@@ -10,6 +10,8 @@
  *   ---------------------------------------------------  ------------------------------------------
  *   node_store snapshot + per-evaluation LIST            ksched_set_nodes   (columns of `available`)
  *     src/main.rs:56, src/predicates.rs:21-38            ksched_update_nodes (sparse rows, from watch events)
+ *   node reflector (src/main.rs:134-139): a node's      ksched_update_node_labels (sparse rows, from node watch events)
+ *     labels / taints, src/predicates.rs:28-31, 49-50
  *   successful POST (src/main.rs:94-103) changes the     ksched_apply_bindings_device (the batch's bindings, on the device)
  *     next evaluation's LIST; SubAssign src/util.rs:31-36
  *   can_pod_fit            src/predicates.rs:20-43       KSCHED_FIT   bit of ksched_eval*
@@ -199,7 +201,8 @@ int ksched_set_nodes(ksched_ctx *ctx, uint32_t n, const int64_t *avail_cpu_milli
  * bound to or removed from them (src/predicates.rs:36-38 subtracts every pod the LIST returns; here the caller
  * keeps that sum current from watch events instead of re-LISTing).  node_index[i] is a canonical node index
  * (< ksched_num_nodes); the two value arrays hold the node's NEW available cpu / memory.  Labels and taints are
- * not touched (use ksched_set_nodes when the node set or its labels change).  A node listed twice takes its last values.
+ * not touched (use ksched_update_node_labels when a node's labels or taints change, ksched_set_nodes when the node set
+ * changes).  A node listed twice takes its last values.
  * Cost: the new values are scattered into the columns and the fit part (rows, search trees, cnt tables) of the touched
  * 1024-node tiles is rebuilt by one kernel; updates of up to 16 nodes travel in kernel arguments (no copy).  The best-fit
  * order is only marked stale: the next KSCHED_PICK_BESTFIT request rebuilds it.  The host does not wait: evaluations already
@@ -210,6 +213,29 @@ int ksched_set_nodes(ksched_ctx *ctx, uint32_t n, const int64_t *avail_cpu_milli
  */
 int ksched_update_nodes(ksched_ctx *ctx, uint32_t count, const uint32_t *node_index, const int64_t *avail_cpu_milli,
                         const int64_t *avail_mem_bytes);
+
+/* The node-watch twin of ksched_update_nodes: the labels (and optionally the taints) of `count` nodes changed -- a node was relabelled
+ * or tainted (the reference's node reflector, src/main.rs:134-139, makes every such change visible to the next pick:
+ * src/predicates.rs:28-31, 49-50).  Host pointers, copied before return; the call does not wait for the device.
+ *   node_index    : [count] canonical node indexes (< ksched_num_nodes)
+ *   label_val_ids : [n_keys][count] with n_keys = ksched_num_keys: ALL of a listed node's label ids are replaced (column k of the
+ *                   update starts count entries after column k - 1's, the [k][n] convention of ksched_set_nodes); NULL when n_keys == 0
+ *   taints        : [count] the nodes' new taint bits, or NULL = taints unchanged.  Allowed on a snapshot set without taints: every
+ *                   other node then has taint bits 0.
+ * `available` is not touched (that is ksched_update_nodes).  A node listed twice takes its last row; count == 0 is a no-op.
+ * Afterwards every evaluation entry point gives the same bits as after a ksched_set_nodes with the updated columns.
+ * Cost: while every new id is at most its key's largest id when the bitmap index's layout was planned, and every new taint bit falls
+ * in its planned taint groups, only the named rows and list-key slots of the touched 1024-node tiles are rebuilt (the index is then
+ * bit-identical to a fresh build that plans the same layout: ksched_index_checksum); otherwise the layout is planned again for the
+ * union of the old and the new maxima and bits, and the whole index is rebuilt from the columns on the device (a layout outside the
+ * fused kernel's limits leaves the snapshot to the direct kernel, as ksched_set_nodes does).  The best-fit ORDER does not change
+ * (it reads `available` only): the next KSCHED_PICK_BESTFIT request rebuilds its row bitmaps alone, without sorting.
+ * Ordering as ksched_update_nodes (KSCHED_OPT_SNAPSHOT_STREAM): evaluations already enqueued read the old labels, later ones the new.
+ * Errors: KSCHED_E_STATE before ksched_set_nodes; KSCHED_E_INVAL, with nothing changed, for an index >= ksched_num_nodes, an id equal
+ * to KSCHED_SEL_NEVER, or label_val_ids == NULL while n_keys > 0.  If a HIP call fails midway the snapshot is invalidated
+ * (KSCHED_E_STATE until the next ksched_set_nodes).  Added in ABI 7 after its first release: detect it by its symbol. */
+int ksched_update_node_labels(ksched_ctx *ctx, uint32_t count, const uint32_t *node_index, const uint32_t *label_val_ids,
+                              const uint64_t *taints);
 
 /* Apply a batch's bindings to the snapshot on the device: the step "bind -> shrink `available`" of the scheduler loop
  * evaluate -> bind -> apply -> evaluate, without a host round trip (every successful POST, src/main.rs:94-103, changes what the

@@ -97,6 +97,7 @@ SYMBOLS = {
     "ksched_set_option": (C.c_int, [_vp, C.c_int, C.c_int64]),
     "ksched_set_nodes": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "ksched_update_nodes": (C.c_int, [_vp, _u32, _vp, _vp, _vp]),
+    "ksched_update_node_labels": (C.c_int, [_vp, _u32, _vp, _vp, _vp]),
     "ksched_apply_bindings_device": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "ksched_read_nodes": (C.c_int, [_vp, _u32, _u32, _vp, _vp]),
     "ksched_forget_stream": (C.c_int, [_vp, _vp]),

@@ -13,8 +13,10 @@
 //                         cnt[r]= per-sub-tile counts of nodes with pos < r, one byte each = exclusive prefix sum over positions
 //                         lr    = rank of the node inside its 128-node sub-tile = its sub-tile's byte of that prefix
 //                         rows  = {n : lr[n] >= c}, c = 0..128: one wave ballot per (row, word)
-//   k_build_tile_named  grid tiles x 1024: valid row, taint subset rows (ballots), label (key, value) rows (LDS atomic OR)
+//   k_build_tile_named  grid (tiles | listed tiles) x 1024: valid row, taint subset rows (ballots), label (key, value) rows (LDS atomic OR)
+//   k_build_tile_list   grid (tiles | listed tiles, list keys) x 1024: the list keys' sorted slots
 //   k_patch_nodes       ksched_update_nodes: scatter the new `available` values into the columns
+//   k_patch_labels      ksched_update_node_labels: scatter the new label ids / taints into the columns and the node records
 //   k_apply_*           ksched_apply_bindings_device / _sharded*, one pipeline over one rank's rows: claim (first pod per node),
 //                       accumulate (exact split sums per node), commit (new values, overflow check, per dirty tile) and status;
 //                       k_build_tile_fit then re-indexes the dirty tiles.  With a communicator only, the claims and the partial sums of
@@ -185,8 +187,9 @@ __global__ __launch_bounds__(1024) void k_build_tile_fit(const BuildFitArgs a) {
 
 // List keys (tile_index.hpp): per (tile, list key) the tile's slots ascending by (value id, node); padding carries id 0 (absent).
 struct BuildListArgs {
-    const uint32_t *nlab;  // [nkeys][n]
-    uint8_t *lists;        // IndexedSnapshot::d_list
+    const uint32_t *nlab;       // [nkeys][n]
+    uint8_t *lists;             // IndexedSnapshot::d_list
+    const uint32_t *tile_list;  // tiles to (re)build, or nullptr = tile blockIdx.x
     uint32_t n, nlist;
     uint32_t list_col[kMaxListKeys];
 };
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(1024) void k_build_tile_list(const BuildListArgs a)
     kernarg_warm<sizeof(BuildListArgs)>();
     __shared__ uint32_t s_key[kTileNodes];
     __shared__ uint16_t s_idx[kTileNodes];
-    const uint32_t tile = blockIdx.x, j = blockIdx.y, i = threadIdx.x;
+    const uint32_t tile = a.tile_list ? a.tile_list[blockIdx.x] : blockIdx.x, j = blockIdx.y, i = threadIdx.x;
     const uint32_t base = tile * kTileNodes;
     const uint32_t m = min((uint32_t)kTileNodes, a.n - base);
     uint32_t kv = (i < m) ? a.nlab[(size_t)a.list_col[j] * a.n + base + i] : 0u;
@@ -210,6 +213,7 @@ struct BuildNamedArgs {
     const uint64_t *ntaint;    // [n] or nullptr
     uint64_t *tables;
     const uint32_t *lab_meta;  // lab_base[32] (kLabList = the key has no rows), lab_max[32]
+    const uint32_t *tile_list; // tiles to (re)build, or nullptr = tile blockIdx.x
     uint32_t n, rows, nkeys, ngroups, row_valid, row_taint, named_rows;  // named_rows = row_cpu: rows [0, named_rows) are built here
 };
 
@@ -218,7 +222,7 @@ struct BuildNamedArgs {
 __global__ __launch_bounds__(1024) void k_build_tile_named(const BuildNamedArgs a) {
     kernarg_warm<sizeof(BuildNamedArgs)>();
     extern __shared__ __attribute__((aligned(16))) uint64_t s_named[];
-    const uint32_t tile = blockIdx.x;
+    const uint32_t tile = a.tile_list ? a.tile_list[blockIdx.x] : blockIdx.x;
     const uint32_t base = tile * kTileNodes;
     const uint32_t m = min((uint32_t)kTileNodes, a.n - base);
     const uint32_t i = threadIdx.x, lane = i & 63u, wave = i >> 6;
@@ -285,6 +289,42 @@ __global__ __launch_bounds__(256) void k_patch_nodes(const PatchArgs a) {
     a.nmem[node] = m;
     a.nrec[(size_t)kNodeRecWords * node] = c;
     a.nrec[(size_t)kNodeRecWords * node + 1] = m;
+}
+
+// ---- ksched_update_node_labels --------------------------------------------------------------------------------------------
+// Thread = one updated node (the host kept one row per node: the last one it was given).  Scatters the node's label ids of every
+// key into nlab ([k][n]) and, with taints, its taint bits into ntaint; rewrites the record words k_build_nrec derives from them
+// (2 = taints, 4..7 = the first eight keys' ids, packed).  The named rows and list slots of the touched tiles are rebuilt after it.
+struct PatchLabelsArgs {
+    uint32_t *nlab;         // [nkeys][n]
+    uint64_t *ntaint;       // [n]; nullptr = taints unchanged
+    int64_t *nrec;          // [n][kNodeRecWords]
+    const uint32_t *idx;    // [count] node indexes, distinct
+    const uint32_t *lab;    // [nkeys][count] the nodes' new ids
+    const uint64_t *taints; // [count]; nullptr = taints unchanged
+    uint32_t count, n, nkeys;
+};
+__global__ __launch_bounds__(256) void k_patch_labels(const PatchLabelsArgs a) {
+    kernarg_warm<sizeof(PatchLabelsArgs)>();
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.count) return;
+    const uint32_t node = a.idx[t];
+    uint32_t l[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) l[k] = 0u;
+    for (uint32_t k = 0; k < a.nkeys; ++k) {
+        const uint32_t id = a.lab[(size_t)k * a.count + t];
+        a.nlab[(size_t)k * a.n + node] = id;
+        if (k < 8u) l[k] = id;
+    }
+    int64_t *r = a.nrec + (size_t)kNodeRecWords * node;
+    if (a.taints) {
+        const uint64_t tb = a.taints[t];
+        a.ntaint[node] = tb;
+        r[2] = (int64_t)tb;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) r[4 + k] = (int64_t)(((uint64_t)l[2 * k + 1] << 32) | l[2 * k]);
 }
 
 // ---- ksched_apply_bindings_device / _sharded* ------------------------------------------------------------------------------

@@ -82,12 +82,18 @@ struct ksched_ctx {
     DevBuf<uint64_t> bf_rows;        // [rows][Wbf] bitmaps over best-fit positions (k_pick_bestfit_rows); built with the tile index
     bool bf_rows_built = false;
     uint32_t bf_row_cpu0 = 0, bf_q = 1, bf_W = 0;
-    // the best-fit structures are built lazily, by the first PICK_BESTFIT request after the snapshot changed
+    // the best-fit structures are built lazily, by the first PICK_BESTFIT request after the snapshot changed: bf_dirty = the order
+    // (and with it everything) is stale, bf_rows_dirty = only the row bitmaps are (labels or taints changed, `available` did not)
     bool bf_dirty = true;
+    bool bf_rows_dirty = false;
     DevBuf<uint32_t> by_cpu, cpurank;
     DevBuf<int64_t> srt_k0[2], srt_k1[2];  // ping-pong sets of the best-fit orders' merge sort (kernels_build.hpp)
     DevBuf<uint32_t> srt_idx[2];
     IndexedSnapshot idx;  // per-tile bitmap index (tile_index.hpp), built on the device (kernels_build.hpp)
+    // what the index layout was planned for (index_plan), indexed or not: per key the largest id, and every taint bit; a label
+    // update whose ids and bits stay within them keeps the layout
+    uint32_t plan_lab_max[KSCHED_MAX_KEYS] = {};
+    uint64_t plan_taints = 0;
     // ksched_apply_bindings_device (kernels_build.hpp "ksched_apply_bindings_device"): per-node scratch, idle between calls
     DevBuf<uint64_t> apply_acc;   // [apply_n][4] split sums, idle 0
     DevBuf<uint32_t> apply_claim; // [apply_n] lowest eligible pod index, idle 0xFFFFFFFF
@@ -412,27 +418,31 @@ int launch_build_fit(ksched_ctx *c, const uint32_t *d_tile_list, uint32_t count,
     return KSCHED_OK;
 }
 
-int launch_build_lists(ksched_ctx *c) {
+// (re)build the list keys' slots of the listed tiles (or of every tile: d_tile_list == nullptr) on the change stream
+int launch_build_lists(ksched_ctx *c, const uint32_t *d_tile_list = nullptr, uint32_t count = 0) {
     const IndexedLayout &l = c->idx.lay;
     if (l.nlist == 0) return KSCHED_OK;
     BuildListArgs a{};
     a.nlab = c->nlab.ptr;
     a.lists = c->idx.d_list;
+    a.tile_list = d_tile_list;
     a.n = l.n;
     a.nlist = l.nlist;
     for (uint32_t j = 0; j < l.nlist; ++j) a.list_col[j] = l.list_col[j];
-    hipLaunchKernelGGL(k_build_tile_list, dim3(l.tiles, l.nlist), dim3(1024), 0, c->change_stream, a);
+    hipLaunchKernelGGL(k_build_tile_list, dim3(d_tile_list ? count : l.tiles, l.nlist), dim3(1024), 0, c->change_stream, a);
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
 
-int launch_build_named(ksched_ctx *c) {
+// (re)build the named rows (valid, taint, label) of the listed tiles (or of every tile: d_tile_list == nullptr)
+int launch_build_named(ksched_ctx *c, const uint32_t *d_tile_list = nullptr, uint32_t count = 0) {
     const IndexedLayout &l = c->idx.lay;
     BuildNamedArgs a{};
     a.nlab = c->nlab.ptr;
     a.ntaint = c->have_taints ? c->ntaint.ptr : nullptr;
     a.tables = c->idx.d_tables;
     a.lab_meta = c->idx.d_lab_meta;
+    a.tile_list = d_tile_list;
     a.n = l.n;
     a.rows = l.rows;
     a.nkeys = l.nkeys;
@@ -442,7 +452,7 @@ int launch_build_named(ksched_ctx *c) {
     a.named_rows = l.row_cpu;
     const uint32_t lds = l.row_cpu * 128u;
     HIPCHK(c, hipFuncSetAttribute((const void *)k_build_tile_named, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_build_tile_named, dim3(l.tiles), dim3(1024), lds, c->change_stream, a);
+    hipLaunchKernelGGL(k_build_tile_named, dim3(d_tile_list ? count : l.tiles), dim3(1024), lds, c->change_stream, a);
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
@@ -452,11 +462,13 @@ int launch_build_named(ksched_ctx *c) {
 // bitmap index -- the named rows once more over best-fit positions plus the 257 cpu threshold rows (k_pick_bestfit_rows).
 // Two device merge sorts (kernels_build.hpp: k_sort_runs + k_merge_pass) and two kernels, on the ctx's stream; called lazily by the first PICK_BESTFIT request
 // after the snapshot changed (ksched_set_nodes / ksched_update_nodes only mark it dirty).
+int build_bestfit_rows(ksched_ctx *c);
 int build_bestfit(ksched_ctx *c) {
     const uint32_t n = c->n;
     c->bf_rows_built = false;
     if (n == 0) {
         c->bf_dirty = false;
+        c->bf_rows_dirty = false;
         return KSCHED_OK;
     }
     hipStream_t s = c->change_stream;
@@ -560,7 +572,18 @@ int build_bestfit(ksched_ctx *c) {
             HIPCHK(c, hipGetLastError());
         }
     }
-    if (c->idx.built) {  // (list keys have no rows: pods that constrain one are picked from the key's sorted lists, k_pick_bestfit_listed)
+    if (int rc = build_bestfit_rows(c)) return rc;
+    c->bf_dirty = false;
+    return KSCHED_OK;
+}
+
+// The row bitmaps in best-fit order alone, over the current order: what a label / taint change (ksched_update_node_labels) makes
+// stale -- it cannot move the order, which reads `available` only.
+int build_bestfit_rows(ksched_ctx *c) {
+    const uint32_t n = c->n;
+    hipStream_t s = c->change_stream;
+    c->bf_rows_built = false;
+    if (c->idx.built && n > 0) {  // (list keys have no rows: pods that constrain one are picked from the key's sorted lists, k_pick_bestfit_listed)
         const IndexedLayout &l = c->idx.lay;
         const uint32_t Wbf = ((n + 63u) / 64u + 7u) & ~7u, named = l.row_cpu;  // (rows padded to whole 64-byte lines: k_pick_bestfit_lanes reads aligned blocks of 8 words)
         const uint32_t levels = 256u, q = (n + levels - 1u) / levels;
@@ -590,7 +613,7 @@ int build_bestfit(ksched_ctx *c) {
         c->bf_q = q;
         c->bf_rows_built = true;
     }
-    c->bf_dirty = false;
+    c->bf_rows_dirty = false;
     return KSCHED_OK;
 }
 
@@ -599,11 +622,65 @@ inline bool bf_rows_expected(const ksched_ctx *c) { return c->idx.built && c->n 
 
 // a PICK_BESTFIT request is about to be enqueued: make sure the structures match the snapshot
 int ensure_bestfit(ksched_ctx *c) {
-    if (!c->bf_dirty) return KSCHED_OK;
+    if (!c->bf_dirty && !c->bf_rows_dirty) return KSCHED_OK;
     int rc = snapshot_begin(c);  // picks already enqueued read the previous order
     if (rc) return rc;
-    if ((rc = build_bestfit(c))) return rc;
+    if ((rc = c->bf_dirty ? build_bestfit(c) : build_bestfit_rows(c))) return rc;  // (rows only: no sort)
     return snapshot_end(c);
+}
+
+// ---- the bitmap index's layout: plan -> reserve -> build ----------------------------------------------------------------
+// One decision for ksched_set_nodes and for a label update that leaves the planned layout (ksched_update_node_labels): the layout
+// (indexed_plan: lab_max, row vs list keys, taint groups) is planned on the host, its buffers reserved and its meta words copied,
+// then the index is built from the node columns.
+struct IndexPlan {
+    IndexedLayout l{};
+    const char *why = "";
+    bool indexed = false;
+    uint32_t meta[72] = {};
+};
+constexpr size_t kPlanMetaBytes = sizeof(IndexPlan::meta);
+
+// the layout for these per-key maxima and taint bits; they become the ctx's plan inputs
+void index_plan(ksched_ctx *c, uint32_t n, uint32_t n_keys, const uint32_t *lab_max, uint64_t all_taints, IndexPlan &p) {
+    p.indexed = indexed_plan(p.l, n, n_keys, lab_max, all_taints, &p.why);
+    if (p.indexed) indexed_meta(p.l, p.meta);
+    for (uint32_t k = 0; k < KSCHED_MAX_KEYS; ++k) c->plan_lab_max[k] = k < n_keys ? lab_max[k] : 0u;
+    c->plan_taints = all_taints;
+}
+
+// the index's buffers, and the copy of its meta words out of `h_meta` (kPlanMetaBytes of the pinned staging block) on the change stream
+int index_reserve(ksched_ctx *c, const IndexPlan &p, uint8_t *h_meta) {
+    c->idx.built = false;
+    if (!p.indexed) return KSCHED_OK;
+    hipError_t e = indexed_reserve(c->idx, p.l);
+    if (e != hipSuccess) return fail_hip(c, e, "indexed_reserve");
+    memcpy(h_meta, p.meta, kPlanMetaBytes);
+    HIPCHK(c, hipMemcpyAsync(c->idx.d_lab_meta, h_meta, kPlanMetaBytes, hipMemcpyHostToDevice, c->change_stream));
+    return KSCHED_OK;
+}
+
+// the whole index, by the kernels of kernels_build.hpp from the columns resident on the device -- or, with KSCHED_OPT_INDEX_BUILD = 1
+// and the caller's host columns at hand (`host`: ksched_set_nodes), by the host spec; without an index, the reason the fused kernel
+// is not applicable
+int index_build(ksched_ctx *c, const IndexPlan &p, bool host, const int64_t *cpu, const int64_t *mem, const uint32_t *lab,
+                const uint64_t *taints) {
+    if (!p.indexed) {
+        c->index_reason = p.why;
+        return KSCHED_OK;
+    }
+    c->idx.lay = p.l;
+    if (host && c->opt_index_build == 1) {
+        hipError_t e = indexed_build_host(c->idx, p.l, cpu, mem, lab, taints, c->change_stream);
+        if (e != hipSuccess) return fail_hip(c, e, "indexed_build_host");
+    } else {
+        if (int rc = launch_build_named(c)) return rc;
+        if (int rc = launch_build_lists(c)) return rc;
+        if (int rc = launch_build_fit(c, nullptr, 0)) return rc;
+    }
+    c->idx.built = true;
+    c->index_reason.clear();
+    return KSCHED_OK;
 }
 
 // ---- mask kernel dispatch ---------------------------------------------------------------------
@@ -1306,14 +1383,11 @@ int ksched_set_nodes(ksched_ctx *c, uint32_t n, const int64_t *cpu, const int64_
     HIPCHK(c, c->cpu_sorted.reserve((size_t)n + 8));
     hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
     // the per-tile bitmap index: layout on the host (it fixes kernel arguments and LDS sizes), contents on the device
-    IndexedLayout l{};
-    const char *why = "";
-    const bool indexed = indexed_plan(l, n, n_keys, lab_max, all_taints, &why);
-    uint32_t meta[72] = {};
-    if (indexed) indexed_meta(l, meta);
+    IndexPlan plan;
+    index_plan(c, n, n_keys, lab_max, all_taints, plan);
     // the caller's arrays (and the index's meta words) -> pinned staging -> asynchronous copies on the chosen stream; nothing is
     // copied from pageable or stack memory, so the call never waits for work already queued on that stream
-    const size_t b_col = (size_t)n * 8, b_lab = (size_t)n * n_keys * 4, b_taint = taints ? b_col : 0, b_meta = indexed ? sizeof meta : 0;
+    const size_t b_col = (size_t)n * 8, b_lab = (size_t)n * n_keys * 4, b_taint = taints ? b_col : 0, b_meta = plan.indexed ? kPlanMetaBytes : 0;
     const size_t o_meta = 2 * b_col + b_lab + b_taint;
     uint8_t *h = nullptr;
     if (n > 0 || b_meta) {
@@ -1329,35 +1403,119 @@ int ksched_set_nodes(ksched_ctx *c, uint32_t n, const int64_t *cpu, const int64_
         if (b_lab) HIPCHK(c, hipMemcpyAsync(c->nlab.ptr, h + 2 * b_col, b_lab, hipMemcpyHostToDevice, s));
         if (b_taint) HIPCHK(c, hipMemcpyAsync(c->ntaint.ptr, h + 2 * b_col + b_lab, b_taint, hipMemcpyHostToDevice, s));
     }
-    if (indexed) {
-        hipError_t e = indexed_reserve(c->idx, l);
-        if (e != hipSuccess) return fail_hip(c, e, "indexed_reserve");
-        memcpy(h + o_meta, meta, b_meta);
-        HIPCHK(c, hipMemcpyAsync(c->idx.d_lab_meta, h + o_meta, b_meta, hipMemcpyHostToDevice, s));
-    }
+    if (int rc = index_reserve(c, plan, h + o_meta)) return rc;
     if (h) HIPCHK(c, hipEventRecord(c->ev_stage, s));  // the last copy out of the staging block
     if (n > 0) {
         hipLaunchKernelGGL(k_build_nrec, dim3((n + 255u) / 256u), dim3(256), 0, s, (const int64_t *)c->ncpu.ptr, (const int64_t *)c->nmem.ptr,
                            taints ? (const uint64_t *)c->ntaint.ptr : nullptr, (const uint32_t *)c->nlab.ptr, n_keys, c->nrec.ptr, n);
         HIPCHK(c, hipGetLastError());
     }
-    if (indexed) {
-        c->idx.lay = l;
-        if (c->opt_index_build == 1) {
-            hipError_t e = indexed_build_host(c->idx, l, cpu, mem, lab, taints, s);
-            if (e != hipSuccess) return fail_hip(c, e, "indexed_build_host");
-        } else {
-            if (int rc = launch_build_named(c)) return rc;
-            if (int rc = launch_build_lists(c)) return rc;
-            if (int rc = launch_build_fit(c, nullptr, 0)) return rc;
-        }
-        c->idx.built = true;
-        c->index_reason.clear();
-    } else {
-        c->index_reason = why;
-    }
+    if (int rc = index_build(c, plan, true, cpu, mem, lab, taints)) return rc;
     if (int rc = snapshot_end(c)) return rc;
     c->have_nodes = true;
+    return KSCHED_OK;
+} KSCHED_ABI_CATCH(c)
+
+int ksched_update_node_labels(ksched_ctx *c, uint32_t count, const uint32_t *node_index, const uint32_t *lab, const uint64_t *taints) try {
+    if (!c) return KSCHED_E_INVAL;
+    if (count > 0 && !node_index) return KSCHED_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    const uint32_t n = c->n, nkeys = c->nkeys;
+    if (count > 0 && nkeys > 0 && !lab) return KSCHED_E_INVAL;
+    for (uint32_t i = 0; i < count; ++i)
+        if (node_index[i] >= n) return KSCHED_E_INVAL;
+    for (size_t i = 0; i < (size_t)nkeys * count; ++i)
+        if (lab[i] == KSCHED_SEL_NEVER) return KSCHED_E_INVAL;
+    if (count == 0) return KSCHED_OK;
+    DeviceGuard g(c->device);
+    if (!g.ok) return KSCHED_E_HIP;
+    fault_point(c);  // (nothing has changed yet)
+    // a node listed twice takes its last row: keep the last occurrence of every index (the patch kernel's threads are unordered)
+    std::vector<uint32_t> keep;
+    {
+        std::vector<uint32_t> order(count);
+        std::iota(order.begin(), order.end(), 0u);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return node_index[a] < node_index[b]; });
+        for (uint32_t i = 0; i < count; ++i)
+            if (i + 1 == count || node_index[order[i + 1]] != node_index[order[i]]) keep.push_back(order[i]);
+    }
+    const uint32_t m = (uint32_t)keep.size();
+    std::vector<uint32_t> tiles;
+    for (uint32_t i : keep) tiles.push_back(node_index[i] / kTileNodes);  // ascending already
+    tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
+    // Does the planned layout still hold?  Every new id at most its key's planned maximum, every new taint bit inside the planned taint
+    // groups.  Otherwise re-plan with the union of the old and the new maxima and bits, and rebuild the whole index.
+    uint32_t lab_max[KSCHED_MAX_KEYS];
+    for (uint32_t k = 0; k < KSCHED_MAX_KEYS; ++k) lab_max[k] = c->plan_lab_max[k];
+    uint64_t all_taints = c->plan_taints;
+    bool holds = c->idx.built;
+    for (uint32_t k = 0; k < nkeys; ++k)
+        for (uint32_t i : keep) {
+            const uint32_t id = lab[(size_t)k * count + i];
+            if (id > lab_max[k]) {
+                lab_max[k] = id;
+                holds = false;
+            }
+        }
+    if (taints) {
+        for (uint32_t i : keep) all_taints |= taints[i];
+        const uint32_t groups = c->idx.built ? c->idx.lay.ngroups : 0u;
+        const uint64_t covered = groups >= 16u ? ~0ull : (1ull << (4u * groups)) - 1ull;
+        if (all_taints & ~covered) holds = false;
+    }
+    if (int rc = snapshot_begin(c)) return rc;  // evaluations already enqueued read the snapshot as it was (events, no host wait)
+    SnapshotChange chg{c};
+    hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
+    IndexPlan plan;
+    if (holds) c->plan_taints = all_taints;  // (same groups)
+    else index_plan(c, n, nkeys, lab_max, all_taints, plan);
+    // the kept rows -> pinned staging -> one copy: [taints u64 m][node u32 m][ids u32 nkeys x m][tiles u32]; the meta words (re-plan) after it
+    const size_t b_taint = taints ? (size_t)m * 8 : 0, b_idx = (size_t)m * 4, b_lab = (size_t)nkeys * m * 4, b_tiles = tiles.size() * 4;
+    const size_t b_dev = b_taint + b_idx + b_lab + b_tiles, b_meta = plan.indexed ? kPlanMetaBytes : 0;
+    uint8_t *h = nullptr;
+    if (int rc = stage_reserve(c, b_dev + b_meta, &h)) return rc;
+    uint64_t *ht = reinterpret_cast<uint64_t *>(h);
+    uint32_t *hi = reinterpret_cast<uint32_t *>(h + b_taint), *hl = hi + m, *hs = hl + (size_t)nkeys * m;
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t i = keep[j];
+        hi[j] = node_index[i];
+        if (taints) ht[j] = taints[i];
+        for (uint32_t k = 0; k < nkeys; ++k) hl[(size_t)k * m + j] = lab[(size_t)k * count + i];
+    }
+    memcpy(hs, tiles.data(), b_tiles);
+    HIPCHK(c, c->d_stage.reserve(b_dev));
+    HIPCHK(c, hipMemcpyAsync(c->d_stage.ptr, h, b_dev, hipMemcpyHostToDevice, s));
+    if (!holds)
+        if (int rc = index_reserve(c, plan, h + b_dev)) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_stage, s));
+    if (taints && !c->have_taints) {  // taints on a snapshot set without them: every other node has none
+        HIPCHK(c, hipMemsetAsync(c->ntaint.ptr, 0, (size_t)n * 8, s));
+        c->have_taints = true;
+    }
+    PatchLabelsArgs pa{};
+    pa.nlab = c->nlab.ptr;
+    pa.ntaint = taints ? c->ntaint.ptr : nullptr;
+    pa.nrec = c->nrec.ptr;
+    pa.taints = taints ? reinterpret_cast<const uint64_t *>(c->d_stage.ptr) : nullptr;
+    pa.idx = reinterpret_cast<const uint32_t *>(c->d_stage.ptr + b_taint);
+    pa.lab = pa.idx + m;
+    pa.count = m;
+    pa.n = n;
+    pa.nkeys = nkeys;
+    hipLaunchKernelGGL(k_patch_labels, dim3((m + 255u) / 256u), dim3(256), 0, s, pa);
+    HIPCHK(c, hipGetLastError());
+    if (holds) {
+        // only the touched 1024-node tiles are re-indexed: their named rows and list slots (the fit part reads `available` only)
+        const uint32_t *d_tiles = pa.lab + (size_t)nkeys * m;
+        if (int rc = launch_build_named(c, d_tiles, (uint32_t)tiles.size())) return rc;
+        if (int rc = launch_build_lists(c, d_tiles, (uint32_t)tiles.size())) return rc;
+    } else {
+        if (int rc = index_build(c, plan, false, nullptr, nullptr, nullptr, nullptr)) return rc;
+    }
+    c->bf_rows_dirty = true;  // the best-fit ORDER reads `available` only: the next PICK_BESTFIT request rebuilds the rows alone
+    if (int rc = snapshot_end(c)) return rc;
+    chg.done = true;
     return KSCHED_OK;
 } KSCHED_ABI_CATCH(c)
 

@@ -194,6 +194,22 @@ class Evaluator:
             raise ValueError("node_index, avail_cpu_milli, avail_mem_bytes must be 1-D of one length")
         self._check(self._lib.ksched_update_nodes(self._h, idx.shape[0], _ptr(idx), _ptr(cpu), _ptr(mem)), "ksched_update_nodes")
 
+    def update_node_labels(self, node_index, label_val_ids=None, taints=None):
+        """New label ids of every key ([n_keys][count]) and, with `taints` ([count]), new taint bits for the listed canonical node
+        indices (ksched_update_node_labels); `available` is not touched."""
+        idx = _np(node_index, np.uint32, "node_index")
+        if idx.ndim != 1:
+            raise ValueError("node_index must be 1-D")
+        count = idx.shape[0]
+        lab = _np(label_val_ids, np.uint32, "label_val_ids")
+        if lab is not None and (lab.ndim != 2 or lab.shape != (self.n_keys, count)):
+            raise ValueError(f"label_val_ids must be [{self.n_keys}][{count}]")
+        tnt = _np(taints, np.uint64, "taints")
+        if tnt is not None and tnt.shape != (count,):
+            raise ValueError("taints shape")
+        rc = self._lib.ksched_update_node_labels(self._h, count, _ptr(idx), _ptr(lab) if lab is not None and lab.size else None, _ptr(tnt))
+        self._check(rc, "ksched_update_node_labels")
+
     def apply_bindings_device(self, bindings, req_cpu_milli, req_mem_bytes, ok=None, flags: int = 0, status_out=None, stream=None):
         """Apply a batch's bindings to the snapshot on the device (ksched_apply_bindings_device): `available` of every node shrinks by the
         requests of the eligible pods bound to it (grows with APPLY_RELEASE).  torch CUDA tensors on this evaluator's device, all [p]:

@@ -101,7 +101,7 @@ void Snapshot::rebuild(const std::vector<corev1::Node> &nodes, PodLister *client
     for (uint32_t i = 0; i < n; ++i) canonical_of_store[order[i]] = i;
     NodeColumns c;
     CountedTable counted;
-    std::vector<__int128> cpu_nanos(n, 0), mem_nanos(n, 0);
+    std::vector<__int128> cpu_nanos(n, 0), mem_nanos(n, 0), alloc_cpu(n, 0), alloc_mem(n, 0);
     c.n = n;
     c.names.resize(n);
     c.avail_cpu_milli.resize(n);
@@ -128,6 +128,8 @@ void Snapshot::rebuild(const std::vector<corev1::Node> &nodes, PodLister *client
                 throw EncodeError("node " + c.names[i] + ": invalid node spec: " + e.what());
             }
         }
+        alloc_cpu[i] = avail.cpu.nanos();
+        alloc_mem[i] = avail.memory.nanos();
         // src/predicates.rs:34-38: every pod the LIST returns is subtracted, any phase
         if (with_resources && client) {
             ++client->list_calls;
@@ -176,6 +178,8 @@ void Snapshot::rebuild(const std::vector<corev1::Node> &nodes, PodLister *client
     cols_ = std::move(c);
     avail_cpu_nanos_ = std::move(cpu_nanos);
     avail_mem_nanos_ = std::move(mem_nanos);
+    alloc_cpu_nanos_ = std::move(alloc_cpu);
+    alloc_mem_nanos_ = std::move(alloc_mem);
     cpu_unit_ = cpu_unit;
     mem_unit_ = mem_unit;
     counted_ = std::move(counted);
@@ -696,6 +700,297 @@ PodColumns Snapshot::encode_pods(const std::vector<const corev1::Pod *> &pods, c
                                [&](size_t lo, size_t hi, uint32_t) { encode_range((uint32_t)lo, (uint32_t)hi); });
     clock.lap("requests + selector ids (threads)");
     return pc;
+}
+
+// ---- node watch events (observe_nodes) ------------------------------------------------------------------------------------------
+namespace {
+// what the predicates read of one node: allocatable (src/predicates.rs:27-32), labels (:45-61), the counted taints (extension E2)
+struct NodeRead {
+    __int128 alloc_cpu = 0, alloc_mem = 0;
+    bool has_labels = false;
+    corev1::StringMap labels;
+    std::vector<TaintId> taints;
+};
+NodeRead read_node(const corev1::Node &node, const std::string &name) {
+    NodeRead r;
+    if (node.status && node.status->allocatable) {  // (as rebuild: a node without allocatable offers nothing)
+        const auto &al = *node.status->allocatable;
+        auto cpu = al.find("cpu"), mem = al.find("memory");
+        if (cpu == al.end() || mem == al.end())
+            throw EncodeError("node " + name + ": allocatable lacks cpu or memory (reference panics, src/predicates.rs:29-31)");
+        try {
+            r.alloc_cpu = ParsedQuantity::try_from(cpu->second).nanos();
+            r.alloc_mem = ParsedQuantity::try_from(mem->second).nanos();
+        } catch (const QuantityError &e) {
+            throw EncodeError("node " + name + ": invalid node spec: " + e.what());
+        }
+    }
+    if (node.metadata.labels) {
+        r.labels = *node.metadata.labels;
+        r.has_labels = true;
+    }
+    if (node.spec && node.spec->taints)
+        for (const auto &t : *node.spec->taints)
+            if (t.effect == "NoSchedule" || t.effect == "NoExecute") r.taints.emplace_back(t.key, t.value.value_or(""), t.effect);
+    return r;
+}
+}  // namespace
+
+size_t Snapshot::observe_nodes(const std::vector<std::pair<NodeEvent, const corev1::Node *>> &events, PodLister *client) {
+    const uint32_t n = cols_.n;
+    bool structural = false;  // a node joins or leaves: the canonical order changes
+    for (const auto &[kind, node] : events) {
+        const int idx = index_of(corev1::name_any(node->metadata));
+        if ((kind == NodeEvent::Applied && idx < 0) || (kind == NodeEvent::Deleted && idx >= 0)) structural = true;
+    }
+    // ---- the nodes of this snapshot only: a diff, applied as row updates --------------------------------------------------------
+    if (!structural) {
+        std::map<uint32_t, NodeRead> now;  // canonical index -> the node as it is now (events taken in order)
+        size_t changed = 0;
+        auto taints_of = [&](uint32_t i) -> const std::vector<TaintId> & { auto it = now.find(i); return it == now.end() ? node_taints_raw_[i] : it->second.taints; };
+        for (const auto &[kind, node] : events) {
+            if (kind != NodeEvent::Applied) continue;  // (a Deleted event names no node of the snapshot here)
+            const std::string name = corev1::name_any(node->metadata);
+            const uint32_t i = (uint32_t)index_of(name);
+            NodeRead r = read_node(*node, name);
+            auto it = now.find(i);
+            const bool same_res = it != now.end() ? (r.alloc_cpu == it->second.alloc_cpu && r.alloc_mem == it->second.alloc_mem)
+                                                   : (r.alloc_cpu == alloc_cpu_nanos_[i] && r.alloc_mem == alloc_mem_nanos_[i]);
+            const bool same_lab = it != now.end() ? (r.has_labels == it->second.has_labels && r.labels == it->second.labels)
+                                                   : (r.has_labels == node_has_labels_[i] && r.labels == node_labels_[i]);
+            const bool same_taints = !taints_enabled_ || r.taints == taints_of(i);
+            if (!(same_res && same_lab && same_taints)) ++changed;
+            if (it != now.end()) it->second = std::move(r);
+            else if (!(same_res && same_lab && r.taints == node_taints_raw_[i])) now.emplace(i, std::move(r));
+        }
+        if (now.empty()) return changed;
+        // everything the change needs, computed before anything is committed
+        std::vector<uint32_t> res_nodes, lab_nodes;
+        std::vector<std::pair<__int128, __int128>> res_fresh;
+        std::map<TaintId, uint32_t> ids = taint_ids_;
+        std::vector<std::map<std::string, uint32_t>> fresh_values(cols_.n_keys);  // values new to a column -> their ids
+        std::map<uint32_t, std::vector<uint32_t>> lab_rows;                         // node -> its new ids of every column
+        std::map<uint32_t, uint64_t> taint_rows;
+        for (const auto &[i, r] : now) {
+            if (r.alloc_cpu != alloc_cpu_nanos_[i] || r.alloc_mem != alloc_mem_nanos_[i]) {
+                res_nodes.push_back(i);
+                res_fresh.emplace_back(avail_cpu_nanos_[i] + (r.alloc_cpu - alloc_cpu_nanos_[i]), avail_mem_nanos_[i] + (r.alloc_mem - alloc_mem_nanos_[i]));
+            }
+            bool dev = false;
+            std::vector<uint32_t> row(cols_.n_keys, 0u);
+            for (uint32_t k = 0; k < cols_.n_keys; ++k) {
+                auto v = r.labels.find(cols_.keys[k]);
+                if (v != r.labels.end()) {
+                    auto known = value_ids_[k].find(v->second);
+                    if (known != value_ids_[k].end()) {
+                        row[k] = known->second;
+                    } else {
+                        auto [f, _] = fresh_values[k].emplace(v->second, (uint32_t)(value_ids_[k].size() + fresh_values[k].size() + 1u));
+                        row[k] = f->second;
+                    }
+                }
+                dev = dev || row[k] != cols_.label_val_ids[(size_t)k * n + i];
+            }
+            uint64_t bits = 0;
+            if (taints_enabled_) {
+                for (const TaintId &t : r.taints) {
+                    auto it = ids.find(t);
+                    if (it == ids.end()) {
+                        if (ids.size() >= 64) throw EncodeError("taint extension: more than 64 distinct NoSchedule/NoExecute taints in one snapshot");
+                        it = ids.emplace(t, (uint32_t)ids.size()).first;
+                    }
+                    bits |= 1ull << it->second;
+                }
+                dev = dev || bits != cols_.taints[i];
+            }
+            if (dev) {
+                lab_nodes.push_back(i);
+                lab_rows[i] = std::move(row);
+                taint_rows[i] = bits;
+            }
+        }
+        auto commit = [&] {
+            for (uint32_t k = 0; k < cols_.n_keys; ++k) value_ids_[k].insert(fresh_values[k].begin(), fresh_values[k].end());
+            if (taints_enabled_) taint_ids_ = ids;
+            for (auto &[i, r] : now) {
+                alloc_cpu_nanos_[i] = r.alloc_cpu;
+                alloc_mem_nanos_[i] = r.alloc_mem;
+                node_labels_[i] = std::move(r.labels);
+                node_has_labels_[i] = r.has_labels;
+                node_taints_raw_[i] = std::move(r.taints);
+            }
+            for (const auto &[i, row] : lab_rows) {
+                for (uint32_t k = 0; k < cols_.n_keys; ++k) cols_.label_val_ids[(size_t)k * n + i] = row[k];
+                if (taints_enabled_) cols_.taints[i] = taint_rows[i];
+            }
+            any_counted_taint_ = std::any_of(node_taints_raw_.begin(), node_taints_raw_.end(), [](const std::vector<TaintId> &t) { return !t.empty(); });
+        };
+        if (!res_nodes.empty()) store_available(res_nodes, res_fresh, commit);  // (validates, commits, pushes the rows)
+        else commit();
+        if (!lab_nodes.empty()) push_labels(lab_nodes);
+        else if (changed && res_nodes.empty()) ++generation_;  // (a label no column holds yet: nothing on the device, but the snapshot moved)
+        return changed;
+    }
+    // ---- a node joins or leaves: re-encode from the nodes and the counted pods (Rust's Snapshot::build_from_counted) ---------------
+    struct Rec {
+        NodeRead r;
+        __int128 avail_cpu = 0, avail_mem = 0;
+        int old = -1;  // canonical index in the snapshot as it is, -1 = joins now
+    };
+    std::map<std::string, Rec> recs;  // the nodes as they will be, in canonical order (ascending name, as rebuild sorts)
+    for (uint32_t i = 0; i < n; ++i) {
+        Rec x;
+        x.r.alloc_cpu = alloc_cpu_nanos_[i];
+        x.r.alloc_mem = alloc_mem_nanos_[i];
+        x.r.has_labels = node_has_labels_[i];
+        x.r.labels = node_labels_[i];
+        x.r.taints = node_taints_raw_[i];
+        x.avail_cpu = avail_cpu_nanos_[i];
+        x.avail_mem = avail_mem_nanos_[i];
+        x.old = (int)i;
+        recs.emplace(cols_.names[i], std::move(x));
+    }
+    std::vector<std::string> store(n);  // the node store's order, kept as the reflector's writer keeps it
+    for (uint32_t i = 0; i < n; ++i) store[store_of_canonical_[i]] = cols_.names[i];
+    size_t changed = 0;
+    for (const auto &[kind, node] : events) {
+        const std::string name = corev1::name_any(node->metadata);
+        auto it = recs.find(name);
+        if (kind == NodeEvent::Deleted) {
+            if (it == recs.end()) continue;
+            recs.erase(it);
+            store.erase(std::find(store.begin(), store.end(), name));
+            ++changed;
+            continue;
+        }
+        NodeRead r = read_node(*node, name);
+        if (it == recs.end()) {
+            Rec x;
+            x.r = std::move(r);
+            recs.emplace(name, std::move(x));
+            store.push_back(name);
+            ++changed;
+            continue;
+        }
+        Rec &x = it->second;
+        if (!(r.alloc_cpu == x.r.alloc_cpu && r.alloc_mem == x.r.alloc_mem && r.has_labels == x.r.has_labels && r.labels == x.r.labels &&
+              (!taints_enabled_ || r.taints == x.r.taints)))
+            ++changed;
+        x.avail_cpu += r.alloc_cpu - x.r.alloc_cpu;  // (a joining node's `available` is computed from its LIST below)
+        x.avail_mem += r.alloc_mem - x.r.alloc_mem;
+        x.r = std::move(r);
+    }
+    const uint32_t m = (uint32_t)recs.size();
+    std::vector<int> new_of_old(n, -1);
+    NodeColumns c;
+    c.n = m;
+    c.names.reserve(m);
+    c.avail_cpu_milli.resize(m);
+    c.avail_mem_bytes.resize(m);
+    c.taints.assign(m, 0);
+    std::vector<__int128> cpu_nanos(m), mem_nanos(m), alloc_cpu(m), alloc_mem(m);
+    std::vector<corev1::StringMap> labels(m);
+    std::vector<bool> has_labels(m, false);
+    std::vector<std::vector<TaintId>> taints_raw(m);
+    CountedTable counted;
+    bool any_taint = false;
+    {
+        uint32_t j = 0;
+        for (auto &[name, x] : recs) {
+            c.names.push_back(name);
+            if (x.old >= 0) {
+                new_of_old[(size_t)x.old] = (int)j;
+            } else {  // joins: only its pods are LISTed
+                x.avail_cpu = x.r.alloc_cpu;
+                x.avail_mem = x.r.alloc_mem;
+                if (client) {
+                    ++client->list_calls;
+                    for (const auto &p : client->list_pods_on_node(name)) {
+                        try {
+                            const PodResources pr = total_pod_resources(p);
+                            x.avail_cpu -= pr.cpu.nanos();
+                            x.avail_mem -= pr.memory.nanos();
+                            counted[full_name(p.metadata)] = Counted{j, pr.cpu.nanos(), pr.memory.nanos()};
+                        } catch (const QuantityError &e) {
+                            throw EncodeError("pod " + full_name(p.metadata) + ": invalid pod spec: " + e.what());
+                        }
+                    }
+                }
+            }
+            cpu_nanos[j] = x.avail_cpu;
+            mem_nanos[j] = x.avail_mem;
+            alloc_cpu[j] = x.r.alloc_cpu;
+            alloc_mem[j] = x.r.alloc_mem;
+            has_labels[j] = x.r.has_labels;
+            labels[j] = x.r.labels;
+            taints_raw[j] = x.r.taints;
+            any_taint = any_taint || !x.r.taints.empty();
+            ++j;
+        }
+    }
+    for (const auto &sh : counted_.shard)  // the counted pods of the nodes that stay, remapped; those of deleted nodes are dropped
+        for (const auto &[key, ct] : sh) {
+            const int j = new_of_old[ct.node];
+            if (j >= 0 && counted.shard[CountedTable::shard_of(CountedTable::hash_of(key))].count(key) == 0)
+                counted[key] = Counted{(uint32_t)j, ct.cpu_nanos, ct.mem_nanos};
+        }
+    const __int128 cpu_unit = choose_unit(cpu_nanos, kCpuUnits), mem_unit = choose_unit(mem_nanos, kMemUnits);
+    if (!cpu_unit || !mem_unit) throw EncodeError("observe_nodes: the nodes' available values do not fit int64 in one common unit");
+    for (uint32_t j = 0; j < m; ++j) {
+        c.avail_cpu_milli[j] = (int64_t)(cpu_nanos[j] / cpu_unit);
+        c.avail_mem_bytes[j] = (int64_t)(mem_nanos[j] / mem_unit);
+    }
+    std::map<TaintId, uint32_t> ids;
+    if (taints_enabled_) intern_taints_into(taints_raw, ids, c.taints);  // (throws before anything is committed)
+    std::vector<uint32_t> canonical_of_store(m), store_of_canonical(m);
+    for (uint32_t s = 0; s < m; ++s) {
+        const uint32_t j = (uint32_t)std::distance(c.names.begin(), std::lower_bound(c.names.begin(), c.names.end(), store[s]));
+        canonical_of_store[s] = j;
+        store_of_canonical[j] = s;
+    }
+    // ---- commit ----
+    c.keys = cols_.keys;
+    cols_ = std::move(c);
+    avail_cpu_nanos_ = std::move(cpu_nanos);
+    avail_mem_nanos_ = std::move(mem_nanos);
+    alloc_cpu_nanos_ = std::move(alloc_cpu);
+    alloc_mem_nanos_ = std::move(alloc_mem);
+    cpu_unit_ = cpu_unit;
+    mem_unit_ = mem_unit;
+    counted_ = std::move(counted);
+    store_of_canonical_ = std::move(store_of_canonical);
+    canonical_of_store_ = std::move(canonical_of_store);
+    node_labels_ = std::move(labels);
+    node_has_labels_ = std::move(has_labels);
+    node_taints_raw_ = std::move(taints_raw);
+    any_counted_taint_ = any_taint;
+    if (taints_enabled_) taint_ids_ = std::move(ids);
+    encode_labels();
+    upload();
+    return changed;
+}
+
+// the label ids (every column) and taint bits of `nodes` -> one ksched_update_node_labels per device (replicated, like upload())
+void Snapshot::push_labels(const std::vector<uint32_t> &nodes) {
+    ++generation_;
+    if (!dev_) return;  // encode-only snapshot
+    if (device_stale_) {  // the device missed an earlier change: the whole snapshot goes up
+        upload();
+        return;
+    }
+    device_stale_ = true;  // until every device has the rows (see push_rows)
+    const uint32_t m = (uint32_t)nodes.size(), K = cols_.n_keys, n = cols_.n;
+    std::vector<uint32_t> lab((size_t)K * m);
+    std::vector<uint64_t> taints(m);
+    for (uint32_t j = 0; j < m; ++j) {
+        for (uint32_t k = 0; k < K; ++k) lab[(size_t)k * m + j] = cols_.label_val_ids[(size_t)k * n + nodes[j]];
+        taints[j] = cols_.taints[nodes[j]];
+    }
+    const bool with_taints = taints_enabled_ && !taint_ids_.empty();  // (allowed on a device snapshot set without taints)
+    for (const auto &d : devs_)
+        d->check(ksched_update_node_labels(d->handle(), m, nodes.data(), K ? lab.data() : nullptr, with_taints ? taints.data() : nullptr),
+                 "ksched_update_node_labels");
+    device_stale_ = false;
 }
 
 }  // namespace ksched_host

@@ -135,6 +135,24 @@ public:
     size_t observe_bound(const std::vector<Bound> &bound);
     size_t counted_pods() const { return counted_.size(); }
 
+    // The node-watch twin of observe_pods: keep the snapshot current from node events instead of a rebuild (one LIST per node).
+    // `client` LISTs the pods of nodes that join.  Events are taken in order; for each node the last one counts.
+    //   Applied, a node of this snapshot : diffed against what the snapshot holds for it.  Allocatable: `available` moves by new - old,
+    //                                      exactly (ksched_update_nodes).  Labels / taints (taints only with enable_taints(); new ones take
+    //                                      the next free bit, raw taints are always recorded): ksched_update_node_labels on every device.
+    //                                      Nothing the predicates read changed (a heartbeat, a status-only update): no device call and
+    //                                      generation() unchanged.
+    //   Applied, an unknown node (Added) / Deleted, a node of this snapshot : the canonical order changes: the columns are re-encoded from
+    //                                      the nodes and the counted pods (their node indexes remapped), only the added nodes' pods are
+    //                                      LISTed (client->list_calls grows by the number of added nodes), one ksched_set_nodes per device.
+    //   Deleted, an unknown node         : nothing.
+    // The store <-> canonical maps follow the reflector's writer (Context::observe_nodes): replaced in place, appended, erased.
+    // Returns how many events changed what the predicates read.  Strong guarantee: on EncodeError (allocatable without cpu / memory or
+    // unparsable -- where the reference panics, src/predicates.rs:29-31 --, a LISTed pod that cannot be encoded, more than 64 distinct
+    // taints with the extension on, `available` outside the exact integer domain) nothing has changed.
+    using NodeEvent = ksched_host::NodeEvent;
+    size_t observe_nodes(const std::vector<std::pair<NodeEvent, const corev1::Node *>> &events, PodLister *client);
+
     // Make sure every label key in `keys` (the selector keys of ONE batch) has a column; re-uploads the label columns when the
     // column set changes.  Columns are a per-batch working set, not a lifetime dictionary: when adding the batch's keys would
     // exceed KSCHED_MAX_KEYS, the columns no pod of this batch uses are evicted.  Throws EncodeError only when one batch alone
@@ -203,6 +221,8 @@ private:
     static void intern_taints_into(const std::vector<std::vector<TaintId>> &raw, std::map<TaintId, uint32_t> &ids, std::vector<uint64_t> &column);
     uint64_t generation_ = 0;
     std::vector<__int128> avail_cpu_nanos_, avail_mem_nanos_;  // canonical order: the exact values behind the two resource columns
+    std::vector<__int128> alloc_cpu_nanos_, alloc_mem_nanos_;  // canonical order: the nodes' exact allocatable (observe_nodes diffs it)
+    void push_labels(const std::vector<uint32_t> &nodes);      // label ids / taints of these nodes -> ksched_update_node_labels
     __int128 cpu_unit_ = 1000000, mem_unit_ = 1000000000;      // nano-units per column unit (see cpu_unit_nanos())
     // new exact `available` values of some nodes -> columns (+ a new unit when one of them needs it) -> device.  Validates before it
     // changes anything (strong guarantee); `commit` runs between validation and the device call (the callers' own bookkeeping).

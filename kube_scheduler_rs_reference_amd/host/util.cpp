@@ -1,5 +1,6 @@
 #include "util.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -63,6 +64,22 @@ void Context::refresh_snapshot() {
         snapshot = (devs.size() > 1 || sharded) ? std::make_shared<Snapshot>(devs, sharded) : std::make_shared<Snapshot>(devs[0]);
     }
     snapshot->rebuild(node_store, client.get());
+}
+
+size_t Context::observe_nodes(const std::vector<std::pair<NodeEvent, const corev1::Node *>> &events) {
+    const size_t changed = snapshot ? snapshot->observe_nodes(events, client.get()) : 0;  // (throws before anything changes)
+    for (const auto &[kind, node] : events) {
+        const std::string name = corev1::name_any(node->metadata);
+        auto it = std::find_if(node_store.begin(), node_store.end(), [&](const corev1::Node &x) { return corev1::name_any(x.metadata) == name; });
+        if (kind == NodeEvent::Deleted) {
+            if (it != node_store.end()) node_store.erase(it);
+        } else if (it != node_store.end()) {
+            *it = *node;
+        } else {
+            node_store.push_back(*node);
+        }
+    }
+    return changed;
 }
 
 }  // namespace ksched_host

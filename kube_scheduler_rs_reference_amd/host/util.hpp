@@ -21,6 +21,10 @@ namespace ksched_host {
 
 class Snapshot;
 
+// One event of a node WATCH (the reflector behind node_store, src/main.rs:134-139): Applied = Added / Modified (the node as it is now),
+// Deleted = Deleted.
+enum class NodeEvent { Applied, Deleted };
+
 // The slice of kube::Api<Pod> the path uses (src/predicates.rs:21-34).
 struct PodLister {
     virtual ~PodLister() = default;
@@ -65,6 +69,11 @@ struct Context {
 
     // (Re)build `snapshot` from node_store and one LIST per node.
     void refresh_snapshot();
+    // Keep node_store and the snapshot current from node watch events, the way the reflector's writer does: an Applied node already in
+    // the store is replaced in place, an unknown one appended, a Deleted one erased.  The snapshot follows (Snapshot::observe_nodes,
+    // its store <-> canonical maps included) and is changed first: on EncodeError neither has changed.  Without a snapshot yet only
+    // node_store changes (the next refresh_snapshot builds it).  Returns how many events changed what the predicates read.
+    size_t observe_nodes(const std::vector<std::pair<NodeEvent, const corev1::Node *>> &events);
 
     static std::function<void(const std::string &)> default_warn_sink();
 };

@@ -91,6 +91,9 @@ extern "C" {
     pub fn ksched_update_nodes(
         ctx: *mut ksched_ctx, count: u32, node_index: *const u32, avail_cpu_milli: *const i64, avail_mem_bytes: *const i64,
     ) -> c_int;
+    pub fn ksched_update_node_labels(
+        ctx: *mut ksched_ctx, count: u32, node_index: *const u32, label_val_ids: *const u32, taints: *const u64,
+    ) -> c_int;
     pub fn ksched_apply_bindings_device(
         ctx: *mut ksched_ctx, p: u32, bindings: *const i32, req_cpu_milli: *const i64, req_mem_bytes: *const i64, ok: *const u8,
         flags: u32, status_out: *mut i32, hip_stream: *mut c_void,
@@ -201,6 +204,7 @@ pub fn symbol_table() -> Vec<(&'static str, usize)> {
         ("ksched_set_option", ksched_set_option as usize),
         ("ksched_set_nodes", ksched_set_nodes as usize),
         ("ksched_update_nodes", ksched_update_nodes as usize),
+        ("ksched_update_node_labels", ksched_update_node_labels as usize),
         ("ksched_apply_bindings_device", ksched_apply_bindings_device as usize),
         ("ksched_read_nodes", ksched_read_nodes as usize),
         ("ksched_forget_stream", ksched_forget_stream as usize),

@@ -1,0 +1,348 @@
+"""ksched_update_node_labels on the device: the node-watch twin of ksched_update_nodes.
+
+After a label / taint update every evaluation entry point must give the bits a ksched_set_nodes with the updated columns gives (expected
+values: capi.eval_encoded on those columns).  While the planned layout holds, the bitmap index must moreover be bit-identical to a fresh
+build of the same columns, device-built and host-spec-built (KSCHED_OPT_INDEX_BUILD 0 and 1); when it does not, the layout is planned again
+and the index rebuilt from the columns on the device.
+"""
+import numpy as np
+import pytest
+
+from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, SEL, SEL_NEVER, TAINT, Evaluator, KschedError, _lib, synth
+from oracle import capi
+from oracle.oracle_ref import apply_bindings_exact
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ev(built):
+    e = Evaluator(0)
+    yield e
+    e.close()
+
+
+def checksums(ev, cols, host):
+    ev.set_option(_lib.OPT_INDEX_BUILD, 1 if host else 0)
+    try:
+        ev.set_nodes(**cols)
+        return ev.index_checksum()
+    finally:
+        ev.set_option(_lib.OPT_INDEX_BUILD, 0)
+
+
+def apply_rows(lab, tnt, idx, rows_lab, rows_tnt):
+    """the columns after an update: a node listed twice takes its last row"""
+    lab = None if lab is None else lab.copy()
+    tnt = None if tnt is None else tnt.copy()
+    idx = np.asarray(idx, dtype=np.int64)
+    _, first_of_reversed = np.unique(idx[::-1], return_index=True)
+    pos = idx.size - 1 - first_of_reversed
+    if lab is not None and lab.shape[0]:
+        lab[:, idx[pos]] = rows_lab[:, pos]
+    if rows_tnt is not None:
+        if tnt is None:
+            tnt = np.zeros(lab.shape[1] if lab is not None else int(idx.max()) + 1, np.uint64)
+        tnt[idx[pos]] = rows_tnt[pos]
+    return lab, tnt
+
+
+def top_bit(t):
+    x = int(np.bitwise_or.reduce(t)) if t is not None and t.size else 0
+    return x.bit_length()
+
+
+def in_layout_rows(rng, lab, tnt, idx):
+    """random rows that keep every key's largest id and the highest taint bit, so a fresh build plans the same layout; one more row for
+    idx[0] restores them when the random rows took them away.  -> idx, rows_lab, rows_tnt"""
+    K = lab.shape[0]
+    lmax = lab.max(axis=1).astype(np.int64)
+    tb = top_bit(tnt)
+    rows_lab = rng.integers(0, lmax[:, None] + 1, (K, idx.size)).astype(np.uint32)
+    rows_tnt = rng.integers(0, 1 << tb, idx.size, dtype=np.uint64) if tnt is not None else None
+    new_lab, new_tnt = apply_rows(lab, tnt, idx, rows_lab, rows_tnt)
+    if (new_lab.max(axis=1) != lmax).any() or (tnt is not None and top_bit(new_tnt) != tb):
+        a = idx[0]
+        extra = new_lab[:, a].copy()
+        miss = new_lab.max(axis=1) != lmax
+        extra[miss] = lmax[miss]
+        idx = np.append(idx, a).astype(np.uint32)
+        rows_lab = np.concatenate([rows_lab, extra[:, None]], axis=1)
+        if tnt is not None:
+            rows_tnt = np.append(rows_tnt, np.uint64(int(new_tnt[a]) | ((1 << (tb - 1)) if tb else 0)))
+    return idx.astype(np.uint32), np.ascontiguousarray(rows_lab), rows_tnt
+
+
+@pytest.mark.parametrize("count", [1, 16, 17, 700, "all"])
+def test_in_layout_update_is_bit_identical_to_a_fresh_build(ev, count):
+    c = synth.make_cluster(64, 5300, n_keys=8, n_taints=16, seed=0x1AB + (0 if count == "all" else count))
+    cols = c.node_columns()
+    lab, tnt = cols["label_val_ids"].copy(), cols["taints"].copy()
+    ev.set_nodes(**cols)
+    rng = np.random.default_rng(7 if count == "all" else count)
+    if count == "all":
+        idx = rng.permutation(c.N).astype(np.uint32)
+    else:
+        idx = rng.integers(0, c.N, count).astype(np.uint32)
+        if count >= 16:
+            idx[1] = c.N - 1  # the partial last tile
+            idx[-1] = idx[0]  # a node listed twice: its last row counts
+    idx, rows_lab, rows_tnt = in_layout_rows(rng, lab, tnt, idx)
+    ev.update_node_labels(idx, rows_lab, rows_tnt)
+    got = ev.index_checksum()
+    new_lab, new_tnt = apply_rows(lab, tnt, idx, rows_lab, rows_tnt)
+    fresh = dict(cols, label_val_ids=new_lab, taints=new_tnt)
+    assert got[0] != 0
+    assert got == checksums(ev, fresh, host=False), "device-built fresh index"
+    assert got == checksums(ev, fresh, host=True), "host-spec fresh index"
+    # labels only (taints unchanged), on top of a first update
+    ev.set_nodes(**cols)
+    ev.update_node_labels(idx, rows_lab, rows_tnt)
+    idx2, rows2, _ = in_layout_rows(rng, new_lab, new_tnt, idx[: max(1, idx.size // 2)].copy())
+    ev.update_node_labels(idx2, rows2)
+    lab3, _ = apply_rows(new_lab, None, idx2, rows2, None)
+    assert ev.index_checksum() == checksums(ev, dict(fresh, label_val_ids=lab3), host=True)
+
+
+def _matrix():
+    from tests import apply_paths_worker as W
+    return W
+
+
+@pytest.mark.parametrize("kind", ["taints", "list-key"])
+def test_every_evaluation_path_after_random_updates(ev, kind):
+    """masks (and WANT_FIT_MASK), the sampled pick in every fused-pick form, best fit in one and two stages, ksched_explain and the direct
+    kernel (tests/apply_paths_worker.check_matrix) after in-layout updates -- including the list key relabelled -- and after an update that
+    re-plans the layout"""
+    W = _matrix()
+    S = W.snapshot(kind, 3000, 1500, seed=0x5A + len(kind))
+    cpu, mem = S["cpu"], S["mem"]
+    W.set_nodes(ev, S, cpu, mem)
+    rng = np.random.default_rng(11)
+    seen = set()
+    for rnd in range(3):
+        idx = rng.integers(0, S["N"], 400).astype(np.uint32)
+        lab = S["lab"]
+        if rnd < 2:  # in the layout: ids up to each key's maximum; the list key's (hostname-like) values move between nodes
+            rows = rng.integers(0, lab.max(axis=1).astype(np.int64)[:, None] + 1, (lab.shape[0], idx.size)).astype(np.uint32)
+            rows[-1] = lab[-1, rng.permutation(idx)] if kind == "list-key" else rows[-1]
+        else:  # ids above the maxima: the layout is planned again
+            rows = lab[:, idx].copy()
+            rows[0, :50] = lab[0].max() + 1 + rng.integers(0, 3, 50)
+            rows[-1, :50] = lab[-1].max() + 1 + np.arange(50)
+            sel = S["sel"].copy()
+            sel[0, :100] = lab[0].max() + 1
+            sel[-1, 100:140] = rows[-1, :40]
+            S = dict(S, sel=sel)
+        rows_t = None
+        if S["tnt"] is not None and rnd == 1:
+            rows_t = rng.integers(0, 1 << top_bit(S["tnt"]), idx.size, dtype=np.uint64)
+        ev.update_node_labels(idx, rows, rows_t)
+        new_lab, new_tnt = apply_rows(lab, S["tnt"], idx, rows, rows_t)
+        S = dict(S, lab=np.ascontiguousarray(new_lab), tnt=new_tnt)
+        W.check_matrix(ev, S, cpu, mem, seen, f"{kind} round {rnd}", rng)
+    assert "select" in seen, seen
+
+
+def replan(kind, S, rng):
+    """-> (idx, rows_lab, rows_tnt, S after the update, indexed afterwards)"""
+    N, lab = S["N"], S["lab"]
+    if kind == "id-above-max":
+        idx = rng.choice(N, 50, replace=False).astype(np.uint32)
+        rows = lab[:, idx].copy()
+        rows[2] = lab[2].max() + 1 + rng.integers(0, 3, 50)
+        sel = S["sel"].copy()
+        sel[2, ::7] = lab[2].max() + 1
+        return idx, rows, None, dict(S, sel=sel), True
+    if kind == "row-to-list":  # 1200 distinct values of key 0: too many rows for the named-row budget, the key becomes a list
+        idx = np.arange(1200, dtype=np.uint32)
+        rows = lab[:, idx].copy()
+        rows[0] = 1 + rng.permutation(1200)
+        sel = S["sel"].copy()
+        sel[0, ::3] = rng.integers(1, 1300, sel[0, ::3].size)
+        return idx, rows, None, dict(S, sel=sel), True
+    if kind == "third-list-key":  # two more hostname-like keys next to the list key: outside the fused kernel's limits
+        idx = np.arange(N, dtype=np.uint32)
+        rows = lab.copy()
+        rows[0] = 2000 + 1 + rng.permutation(N)
+        rows[1] = 4000 + 1 + rng.permutation(N)
+        sel = S["sel"].copy()
+        sel[0, ::5] = rows[0, rng.integers(0, N, sel[0, ::5].size)]
+        return idx, rows, None, dict(S, sel=sel), False
+    if kind == "taints-appear":  # a snapshot set without taints gets some
+        idx = rng.choice(N, 300, replace=False).astype(np.uint32)
+        rows_t = rng.integers(0, 1 << 12, 300, dtype=np.uint64) & rng.integers(0, 1 << 12, 300, dtype=np.uint64)
+        tol = rng.integers(0, 1 << 12, S["P"], dtype=np.uint64)
+        return idx, lab[:, idx].copy(), rows_t, dict(S, tol=tol, preds=[FIT | SEL | TAINT, FIT | SEL]), True
+    if kind == "taint-outside-groups":  # bit 40: beyond the taint groups the layout planned
+        idx = rng.choice(N, 100, replace=False).astype(np.uint32)
+        rows_t = S["tnt"][idx] | (np.uint64(1) << np.uint64(40))
+        tol = S["tol"].copy()
+        tol[::2] |= np.uint64(1) << np.uint64(40)
+        return idx, lab[:, idx].copy(), rows_t, dict(S, tol=tol), True
+    raise ValueError(kind)
+
+
+@pytest.mark.parametrize("kind,base", [("id-above-max", "taints"), ("row-to-list", "taints"), ("third-list-key", "list-key"),
+                                       ("taints-appear", "many-keys"), ("taint-outside-groups", "taints")])
+def test_replanned_layout_equals_the_oracle(ev, kind, base):
+    W = _matrix()
+    S = W.snapshot(base, 2500, 1200, seed=0x77 + len(kind))
+    cpu, mem = S["cpu"], S["mem"]
+    W.set_nodes(ev, S, cpu, mem)
+    assert ev.index_checksum()[0] != 0
+    rng = np.random.default_rng(len(kind))
+    idx, rows, rows_t, S2, indexed = replan(kind, S, rng)
+    ev.update_node_labels(idx, rows, rows_t)
+    new_lab, new_tnt = apply_rows(S["lab"], S["tnt"], idx, rows, rows_t)
+    if new_tnt is None and rows_t is not None:
+        new_tnt = np.zeros(S["N"], np.uint64)
+    S2 = dict(S2, lab=np.ascontiguousarray(new_lab), tnt=new_tnt, indexed=indexed)
+    assert (ev.index_checksum()[0] != 0) == indexed
+    W.check_matrix(ev, S2, cpu, mem, set(), kind, rng, reduced=True)
+    # and an in-layout update on top of the re-planned one
+    idx3 = rng.integers(0, S["N"], 64).astype(np.uint32)
+    rows3 = new_lab[:, rng.permutation(idx3)]
+    ev.update_node_labels(idx3, rows3)
+    lab3, _ = apply_rows(new_lab, None, idx3, rows3, None)
+    W.check_matrix(ev, dict(S2, lab=np.ascontiguousarray(lab3)), cpu, mem, set(), kind + " + in-layout", rng, reduced=True)
+
+
+def test_interleaved_with_update_nodes_and_apply_bindings(ev):
+    """label updates between ksched_update_nodes and ksched_apply_bindings_device; best fit after a label-only change (its rows rebuilt
+    without the sorts) equals the oracle"""
+    import torch
+    c = synth.make_cluster(3000, 5000, n_keys=8, n_taints=16, seed=0xB1)
+    ev.set_kernel("auto")
+    ev.set_nodes(**c.node_columns())
+    dev = torch.device("cuda", ev.device)
+    cpu, mem, lab, tnt = c.avail_cpu.copy(), c.avail_mem.copy(), c.node_labels.copy(), c.node_taints.copy()
+    rng = np.random.default_rng(5)
+    pc = c.pod_columns()
+    fl = FIT | SEL | TAINT
+
+    def check(what):
+        for stages in (1, 2):
+            ev.set_option(_lib.OPT_BESTFIT_STAGES, stages)
+            r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], None, fl | PICK_BESTFIT, want_mask=False)
+            want = capi.eval_encoded(cpu, mem, lab, tnt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, None, fl | PICK_BESTFIT, want_mask=False)[2]
+            assert np.array_equal(r.binding, want), f"{what}: best fit, {stages} stage(s)"
+        ev.set_option(_lib.OPT_BESTFIT_STAGES, 0)
+        r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], c.samples, fl | PICK_SAMPLED)
+        feas, _, want = capi.eval_encoded(cpu, mem, lab, tnt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, c.samples, fl | PICK_SAMPLED)
+        assert np.array_equal(r.feasible, feas) and np.array_equal(r.binding, want), f"{what}: mask / sampled pick"
+        return want
+
+    check("start")
+    for rnd in range(3):
+        idx, rows, rows_t = in_layout_rows(rng, lab, tnt, rng.integers(0, c.N, 200).astype(np.uint32))
+        ev.update_node_labels(idx, rows, rows_t if rnd != 1 else None)
+        lab, tnt = apply_rows(lab, tnt, idx, rows, rows_t if rnd != 1 else None)
+        want = check(f"round {rnd}: after the label update")
+        u = np.unique(rng.integers(0, c.N, 40)).astype(np.uint32)
+        cpu[u] -= rng.integers(0, 1000, u.size)
+        ev.update_nodes(u, cpu[u], mem[u])
+        check(f"round {rnd}: after ksched_update_nodes")
+        b = torch.from_numpy(want.astype(np.int32)).to(dev)
+        rc_t, rm_t = torch.from_numpy(c.req_cpu).to(dev), torch.from_numpy(c.req_mem).to(dev)
+        ev.apply_bindings_device(b, rc_t, rm_t)
+        cpu, mem, _ = apply_bindings_exact(cpu, mem, want, c.req_cpu, c.req_mem)
+        torch.cuda.synchronize()
+        idx, rows, rows_t = in_layout_rows(rng, lab, tnt, rng.integers(0, c.N, 17).astype(np.uint32))
+        ev.update_node_labels(idx, rows, rows_t)
+        lab, tnt = apply_rows(lab, tnt, idx, rows, rows_t)
+        check(f"round {rnd}: after the apply and a label update")
+
+
+@pytest.mark.parametrize("n_streams,own_stream", [(1, 0), (2, 0), (1, 1), (3, 0)])
+def test_label_updates_and_evaluations_interleaved_without_host_waits(ev, n_streams, own_stream):
+    """label updates, updates of `available` and device evaluations interleave with no host synchronisation: every evaluation sees the
+    labels that were current when it was enqueued"""
+    import torch
+    ev.set_option(_lib.OPT_SNAPSHOT_STREAM, own_stream)
+    c = synth.make_cluster(2000, 4100, n_keys=8, n_taints=16, seed=0x61)
+    ev.set_kernel("auto")
+    ev.set_nodes(**c.node_columns())
+    dev = torch.device("cuda", ev.device)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+    d_cpu, d_mem, d_sel, d_tol = t(c.req_cpu, np.int64), t(c.req_mem, np.int64), t(c.pod_sel, np.int32), t(c.pod_tol, np.int64)
+    streams = [torch.cuda.Stream(device=dev) for _ in range(n_streams)]
+    torch.cuda.synchronize()
+    flags = FIT | SEL | TAINT | PICK_BESTFIT
+    cpu, mem, lab, tnt = c.avail_cpu.copy(), c.avail_mem.copy(), c.node_labels.copy(), c.node_taints.copy()
+    rng = np.random.default_rng(19)
+    pending = []
+    for it in range(40):
+        if it % 5 == 4:
+            u = np.unique(rng.integers(0, c.N, 5)).astype(np.uint32)
+            cpu[u] -= rng.integers(0, 2000, u.size)
+            ev.update_nodes(u, cpu[u], mem[u])
+        else:
+            idx = rng.integers(0, c.N, int(rng.choice([1, 3, 30]))).astype(np.uint32)
+            idx, rows, rows_t = in_layout_rows(rng, lab, tnt, idx)
+            with_t = it % 3 == 0
+            ev.update_node_labels(idx, rows, rows_t if with_t else None)
+            lab, tnt = apply_rows(lab, tnt, idx, rows, rows_t if with_t else None)
+        s = streams[it % n_streams]
+        mask, bind = ev.alloc_mask(c.P), torch.empty((c.P,), dtype=torch.int32, device=dev)
+        with torch.cuda.stream(s):
+            ev.eval_device(d_cpu, d_mem, d_sel, d_tol, None, flags, out_feasible=mask, out_binding=bind, stream=s)
+        pending.append((mask, bind, cpu.copy(), mem.copy(), lab.copy(), tnt.copy()))
+    torch.cuda.synchronize()
+    for it, (mask, bind, pc, pm, pl, pt) in enumerate(pending):
+        feas, _, want = capi.eval_encoded(pc, pm, pl, pt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, None, flags)
+        assert np.array_equal(mask.contiguous().cpu().numpy().view(np.uint64), feas), f"iteration {it}: mask is not of the labels current at enqueue time"
+        assert np.array_equal(bind.cpu().numpy(), want), f"iteration {it}: best-fit pick"
+    for s in streams:
+        ev.forget_stream(s)
+    ev.set_option(_lib.OPT_SNAPSHOT_STREAM, 0)
+
+
+def test_errors_change_nothing(built):
+    e = Evaluator(0)
+    try:
+        one = np.zeros(1, np.uint32)
+        with pytest.raises(KschedError) as ei:
+            e.update_node_labels(one, np.zeros((0, 1), np.uint32))
+        assert ei.value.code == _lib.E_STATE
+        c = synth.make_cluster(16, 2100, n_keys=3, n_taints=4, seed=3)
+        e.set_nodes(**c.node_columns())
+        before = e.index_checksum()
+        lab = np.ones((3, 2), np.uint32)
+        cases = [
+            ("index >= n", np.array([0, c.N], np.uint32), lab),
+            ("SEL_NEVER id", np.array([0, 1], np.uint32), np.where(np.arange(6).reshape(3, 2) == 5, SEL_NEVER, 1).astype(np.uint32)),
+            ("NULL labels with keys", np.array([0, 1], np.uint32), None),
+        ]
+        for what, idx, rows in cases:
+            with pytest.raises(KschedError) as ei:
+                e.update_node_labels(idx, rows, np.zeros(2, np.uint64))
+            assert ei.value.code == _lib.E_INVAL, what
+            assert e.index_checksum() == before, what
+        e.update_node_labels(np.zeros(0, np.uint32), np.zeros((3, 0), np.uint32))  # count == 0: a no-op
+        assert e.index_checksum() == before
+        assert e.n == c.N
+    finally:
+        e.close()
+
+
+def test_c5_shard_scattered_relabels(ev):
+    """the C5 shard (50 000 nodes, 8 keys, taints): 7 143 scattered relabels, then every binding and a sample of mask rows equal the oracle"""
+    c = synth.make_cluster(20_000, 50_000, n_keys=8, n_taints=16, seed=0xC5)
+    ev.set_kernel("auto")
+    ev.set_nodes(**c.node_columns())
+    rng = np.random.default_rng(0xC5)
+    idx = rng.choice(c.N, 7143, replace=False).astype(np.uint32)
+    idx, rows, rows_t = in_layout_rows(rng, c.node_labels, c.node_taints, idx)
+    ev.update_node_labels(idx, rows, rows_t)
+    lab, tnt = apply_rows(c.node_labels, c.node_taints, idx, rows, rows_t)
+    pc = c.pod_columns()
+    fl = FIT | SEL | TAINT
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], c.samples, fl | PICK_SAMPLED)
+    feas, _, want = capi.eval_encoded(c.avail_cpu, c.avail_mem, lab, tnt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, c.samples, fl | PICK_SAMPLED)
+    assert np.array_equal(r.binding, want), "sampled pick"
+    rows_s = rng.choice(c.P, 512, replace=False)
+    assert np.array_equal(r.feasible[rows_s], feas[rows_s]), "sampled mask rows"
+    rb = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], None, fl | PICK_BESTFIT, want_mask=False)
+    wb = capi.eval_encoded(c.avail_cpu, c.avail_mem, lab, tnt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, None, fl | PICK_BESTFIT, want_mask=False)[2]
+    assert np.array_equal(rb.binding, wb), "best fit"

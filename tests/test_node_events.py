@@ -1,0 +1,43 @@
+"""Snapshot::observe_nodes / Context::observe_nodes, the node-watch twin of observe_pods (kube_scheduler_rs_reference_amd/host).
+The tests are C++ (tests/cpp/node_events_tests.cpp); this file builds and runs them: the event sequences on an encode-only snapshot here
+on the CPU, objects -> events -> reconcile_batch on the GPU, through one device and through the forced one-device sharded path."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "tests", "cpp", "node_events_tests")
+HOOKS_DIR = os.path.join(ROOT, "tests", "cpp", "hooks")
+
+
+def _run(mode, env=None):
+    if os.path.exists("/opt/rocm/bin/hipcc"):
+        subprocess.check_call(["make", "-C", ROOT, "-s", "host"])
+    assert os.path.exists(BIN), "tests/cpp/node_events_tests has not been built (make host)"
+    r = subprocess.run([BIN, mode], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, LD_LIBRARY_PATH=HOOKS_DIR + os.pathsep + os.environ.get("LD_LIBRARY_PATH", ""), **(env or {})))
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "0 failed check(s)" in r.stdout
+    return r.stdout
+
+
+def test_node_event_sequences_equal_a_rebuild():
+    out = _run("cpu")
+    for step in ("label change", "new label value", "key removed", "taint added", "taint removed", "allocatable change",
+                 "status-only Modified", "Added", "Deleted (b)", "Deleted of an unknown node", "EncodeError events change nothing"):
+        assert f"ok  {step}" in out, step
+    assert "FAIL" not in out
+
+
+@pytest.mark.gpu
+def test_node_events_then_reconcile_batch_on_the_device():
+    out = _run("gpu")
+    assert "ok  objects -> node events -> reconcile_batch" in out
+
+
+@pytest.mark.gpu
+def test_node_events_then_reconcile_batch_through_the_sharded_path():
+    out = _run("gpu", env={"KSCHED_SHARDED": "1"})
+    assert "ok  objects -> node events -> reconcile_batch" in out
