@@ -33,6 +33,7 @@ OBJ_TOOL := tests/cpp/objects_eval
 FAKE_RCCL := tests/cpp/libfake_rccl.so
 INDEX_TEST := tests/cpp/index_tests
 NODE_EVENTS_TEST := tests/cpp/node_events_tests
+SUMMARY_TEST := tests/cpp/summary_tests
 
 PMC_CALIB := tools/pmc_calib
 
@@ -59,7 +60,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c -o tests/cpp/hooks/test_hooks.o tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(INDEX_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -75,6 +76,10 @@ $(HOST_TEST): tests/cpp/host_tests.cpp $(LIB_HOST) $(HOST_HDRS)
 # C++ tests of Snapshot::observe_nodes / Context::observe_nodes (tests/cpp/node_events_tests.cpp; driven by tests/test_node_events.py)
 $(NODE_EVENTS_TEST): tests/cpp/node_events_tests.cpp $(LIB_HOST) $(HOST_HDRS)
 	$(CXX) $(CXXFLAGS) -o $@ tests/cpp/node_events_tests.cpp -L$(PKG) -lksched_host -lksched_hip -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread
+
+# C++ tests of explain_unschedulable / format_unschedulable / Context::explain_no_node_found (tests/cpp/summary_tests.cpp; driven by tests/test_summary_host.py)
+$(SUMMARY_TEST): tests/cpp/summary_tests.cpp tests/cpp/json_min.hpp $(LIB_HOST) $(HOST_HDRS)
+	$(CXX) $(CXXFLAGS) -o $@ tests/cpp/summary_tests.cpp -L$(PKG) -lksched_host -lksched_hip -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread
 
 # objects JSON -> host encoder -> device, printed for the Python parity tests (tests/test_gpu_objects.py)
 $(OBJ_TOOL): tests/cpp/objects_eval.cpp tests/cpp/json_min.hpp $(LIB_HOST) $(HOST_HDRS)
@@ -109,4 +114,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(INDEX_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

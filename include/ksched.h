@@ -97,6 +97,8 @@ extern "C" {
 #define KSCHED_OPT_TIMING 2
 /* KSCHED_OPT_DEBUG: ablation bits for kernel timing experiments (tools/); any non-zero value makes results invalid */
 #define KSCHED_OPT_DEBUG 3
+/* (bit 30: ksched_summarize* combines a pod's per-tile counts with atomic adds instead of partial words and a reduce kernel -- the
+ * design that lost the measurement, kept for re-measuring it (tools/summary_cost.py); the only debug bit that leaves results valid) */
 
 /* KSCHED_OPT_TRACE: 1 = the fused kernel records per-block phase timestamps (diagnostics; see ksched_trace_read) */
 #define KSCHED_OPT_TRACE 4
@@ -469,6 +471,36 @@ int ksched_reason(const uint64_t *feasible_row, const uint64_t *fit_row, uint32_
 int ksched_explain(ksched_ctx *ctx, uint32_t p, const int64_t *req_cpu_milli, const int64_t *req_mem_bytes,
                    const uint32_t *sel_val_ids, const uint64_t *tolerations, uint32_t count, const uint32_t *pair_pod,
                    const uint32_t *pair_node, uint32_t flags, int32_t *out_reason);
+
+/* ---- why is a pod unschedulable: per-pod node counts by reason, on the device ------------------------
+ * The reference ends a pod that found no node with a bare NoNodeFound (src/main.rs:116-118) after ATTEMPTS blind draws, and
+ * ksched_explain only decides the listed pairs (the rejected draws of src/main.rs:62).  This entry point makes the statement about
+ * the whole cluster ("0/5000 nodes are available: 3120 NotEnoughResources, 1880 NodeSelectorMismatch") without a mask:
+ * for pod i, out_counts[i][r] is the number of nodes n < ksched_num_nodes for which check_node_validity (src/predicates.rs:63-77)
+ * returns reason r, with the precedence ksched_explain documents: resources first (:68-70), then the selector (:72-74), then the taint
+ * extension.  Index r is the KSCHED_REASON_* value, so word 0 (KSCHED_REASON_OK) is the number of feasible nodes.  The four words of a
+ * pod always add up to ksched_num_nodes; padding bits never count.  Unlike ksched_reason on two masks it tells selector failures from
+ * taint failures when both predicates are selected (it sees the three predicates separately).
+ *   flags      : a non-empty subset of KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT; predicates not selected are treated as true
+ *   pod columns: as in ksched_eval_device (sel_val_ids == NULL = no pod has a selector, tolerations == NULL = tolerate nothing)
+ *   out_counts : [p][KSCHED_SUMMARY_WORDS] uint32, device memory; need not be zeroed.  Same inputs, same bits, on every run.
+ * It reads the snapshot like an evaluation: a snapshot change (set, update, apply) enqueued before it is visible, one enqueued after it
+ * is not; `hip_stream` (a hipStream_t, NULL = default stream) is remembered like the streams of the *_device evaluations, and the host
+ * does not wait.  It works on every snapshot an evaluation works on; KSCHED_OPT_KERNEL selects between the kernel over the per-tile
+ * bitmap index and the direct one as it does for evaluations (ksched_last_kernel: "fused" / "direct"; KSCHED_OPT_TIMING brackets the
+ * call's kernels for ksched_kernel_time_ms).  Cost: the staging, rank searches and row reads of a mask evaluation, 8 bytes written per
+ * (pod, 1024-node tile) into ctx-owned scratch and 16 bytes per pod of output instead of the mask.
+ * Errors: KSCHED_E_INVAL for a NULL ctx or required pointer (req_cpu_milli, req_mem_bytes, out_counts with p > 0), a flag bit outside
+ * the three predicates, or no predicate at all; KSCHED_E_STATE before ksched_set_nodes; p == 0 is a no-op.
+ * ksched_summarize is the host-pointer form: copies in, runs on the ctx's own stream, copies out and waits.
+ * Added in ABI 7 without a version change: detect them by symbol. */
+#define KSCHED_SUMMARY_WORDS 4u /* per pod: [FEASIBLE, NOT_ENOUGH_RESOURCES, NODE_SELECTOR_MISMATCH, TAINT_NOT_TOLERATED] */
+int ksched_summarize_device(ksched_ctx *ctx, uint32_t p, const int64_t *req_cpu_milli, const int64_t *req_mem_bytes,
+                            const uint32_t *sel_val_ids, const uint64_t *tolerations, uint32_t flags,
+                            uint32_t *out_counts /* [p][KSCHED_SUMMARY_WORDS], device */, void *hip_stream);
+int ksched_summarize(ksched_ctx *ctx, uint32_t p, const int64_t *req_cpu_milli, const int64_t *req_mem_bytes,
+                     const uint32_t *sel_val_ids, const uint64_t *tolerations, uint32_t flags,
+                     uint32_t *out_counts /* [p][KSCHED_SUMMARY_WORDS], host */);
 
 /* ---- multi-GPU: all-gather of the (pod -> node) bindings over RCCL / xGMI --------------------
  * The pod batch row-shards over the GPUs of one node (north_star): rank r evaluates pod rows

@@ -50,6 +50,7 @@ REASON_NOT_ENOUGH_RESOURCES = 1
 REASON_NODE_SELECTOR_MISMATCH = 2
 REASON_TAINT_NOT_TOLERATED = 3
 REASON_NAMES = {0: "Ok", 1: "NotEnoughResources", 2: "NodeSelectorMismatch", 3: "TaintNotTolerated"}
+SUMMARY_WORDS = 4  # ksched_summarize*: per pod [feasible, NotEnoughResources, NodeSelectorMismatch, TaintNotTolerated] node counts
 
 OPT_KERNEL = 1
 OPT_TIMING = 2
@@ -138,6 +139,8 @@ SYMBOLS = {
     "ksched_kernel_time_ms": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "ksched_kernel_time_samples": (C.c_int, [_vp, _vp, _u32]),
     "ksched_explain": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp]),
+    "ksched_summarize_device": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "ksched_summarize": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp]),
     "ksched_index_checksum": (C.c_int, [_vp, _vp]),
     "ksched_trace_read": (C.c_int, [_vp, _vp, C.c_uint32]),
     "ksched_last_kernel": (C.c_char_p, [_vp]),

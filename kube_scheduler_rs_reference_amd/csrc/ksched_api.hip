@@ -23,6 +23,7 @@
 #include "kernels_build.hpp"
 #include "kernels_direct.hpp"
 #include "kernels_fused.hpp"
+#include "kernels_summary.hpp"
 #include "mask_alloc.hpp"
 #include "tile_index.hpp"
 
@@ -144,6 +145,8 @@ struct ksched_ctx {
     DevBuf<int32_t> gathered;  // ksched_gather_buffer: the all-gathered binding table of a host that drives several devices
     DevBuf<uint32_t> xpairs;  // ksched_explain: [pair_pod][pair_node]
     DevBuf<int32_t> xreason;
+    DevBuf<uint64_t> sum_part;  // ksched_summarize*: [tiles][p] per-tile counts of the indexed kernel (scratch: one stream at a time, scratch_enter)
+    DevBuf<uint32_t> sum_out;   // ksched_summarize: the [p][4] table of the host-pointer form
     // scratch mask when a pick is requested without an output mask
     DevBuf<uint64_t> scratch_mask;
 
@@ -1223,7 +1226,7 @@ void ksched_destroy(ksched_ctx *c) try {
         c->ncpu.release(); c->nmem.release(); c->nrec.release(); c->nlab.release(); c->ntaint.release();
         c->bf_order.release(); c->bf_rank.release(); c->bf_mem.release(); c->bf_cpu.release(); c->cpu_sorted.release(); c->bf_rows.release(); c->bf_samples.release(); c->bf_levels.release(); c->bf_fallback.release(); c->bf_fallback_zeroed_cap = 0;
         c->pcpu.release(); c->pmem.release(); c->psel.release(); c->psamples.release();
-        c->ptol.release(); c->feas.release(); c->fit.release(); c->binding.release(); c->gathered.release(); c->xpairs.release(); c->xreason.release();
+        c->ptol.release(); c->feas.release(); c->fit.release(); c->binding.release(); c->gathered.release(); c->xpairs.release(); c->xreason.release(); c->sum_part.release(); c->sum_out.release();
         c->scratch_mask.release(); c->trace.release();
         c->by_cpu.release(); c->cpurank.release(); c->d_stage.release();
         for (int b = 0; b < 2; ++b) { c->srt_k0[b].release(); c->srt_k1[b].release(); c->srt_idx[b].release(); }
@@ -2272,6 +2275,110 @@ int ksched_explain(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t
     hipLaunchKernelGGL(k_explain_pairs, dim3((count + 255u) / 256u), dim3(256), 0, s, q);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out_reason, c->xreason.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return KSCHED_OK;
+} KSCHED_ABI_CATCH(c)
+
+// ---- per-pod node counts by reason (kernels_summary.hpp) ------------------------------------------------------------------------
+namespace {
+int check_summary_args(const ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, uint32_t flags, const uint32_t *out) {
+    if (!c) return KSCHED_E_INVAL;
+    if ((flags & ~(KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT)) || !(flags & (KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
+    if (p > 0 && (!pcpu || !pmem || !out)) return KSCHED_E_INVAL;
+    return KSCHED_OK;
+}
+
+// device pointers; the caller holds the ctx's mutex, has checked the arguments and set the device
+int summarize_on_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, const uint64_t *ptol,
+                        uint32_t flags, uint32_t *out, hipStream_t s) {
+    if (p == 0) return KSCHED_OK;
+    if (int rce = stream_enter(c, s)) return rce;  // `s` waits for the latest snapshot change; remembered for the next one
+    if (c->n == 0) {  // no nodes: nothing is feasible and nothing is rejected
+        HIPCHK(c, hipMemsetAsync(out, 0, (size_t)p * KSCHED_SUMMARY_WORDS * sizeof(uint32_t), s));
+        return KSCHED_OK;
+    }
+    fault_point(c);
+    // kernel choice as for evaluations: over the bitmap index when the snapshot has one, else the always-applicable direct kernel
+    const bool can_indexed = summary_indexed_applicable(c->idx);
+    int kern = c->opt_kernel;
+    if (kern == KSCHED_KERNEL_AUTO) kern = can_indexed ? KSCHED_KERNEL_FUSED : KSCHED_KERNEL_DIRECT;
+    if (kern == KSCHED_KERNEL_FUSED && !can_indexed) {
+        c->last_error = "fused kernel not applicable to this snapshot/request: " + (c->index_reason.empty() ? std::string("the bitmap index does not fit LDS") : c->index_reason);
+        return KSCHED_E_UNSUPPORTED;
+    }
+    size_t slot = 0;
+    const bool timed = c->opt_timing && c->ev_used < 65536u && (c->timing_seq++ % c->opt_timing) == 0;
+    if (timed) {
+        if (int trc = timing_slot(c, &slot)) return trc;
+        HIPCHK(c, hipEventRecord(c->ev_pool[slot].a, s));
+    }
+    if (kern == KSCHED_KERNEL_FUSED) {
+        // (KSCHED_OPT_DEBUG bit 30: the atomic cross-tile combine, for re-measuring the choice; it needs the table on an 8-byte boundary)
+        const bool atomic = (c->opt_debug & 0x40000000u) && !(reinterpret_cast<uintptr_t>(out) & 7u);
+        if (!atomic) {
+            if (int rsc = scratch_enter(c, s)) return rsc;
+            HIPCHK(c, c->sum_part.reserve(summary_partial_words(c->idx, p)));
+        }
+        hipError_t e = run_summary_indexed(c->idx, p, pcpu, pmem, psel, ptol, flags, out, c->sum_part.ptr, atomic, s);
+        if (e != hipSuccess) return fail_hip(c, e, "run_summary_indexed");
+        c->last_kernel = "fused";
+    } else {
+        SummaryDirectArgs a{};
+        a.n = c->n;
+        a.p = p;
+        a.nkeys = c->nkeys;
+        a.do_fit = (flags & KSCHED_FIT) ? 1u : 0u;
+        a.aligned = (reinterpret_cast<uintptr_t>(out) & 15u) ? 0u : 1u;
+        const bool sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
+        const bool taint = (flags & KSCHED_TAINT) && c->have_taints;
+        hipLaunchKernelGGL(k_summarize_direct, dim3((p + 63u) / 64u), dim3(64 * kSummaryDirectWaves), 0, s, c->ncpu.ptr, c->nmem.ptr, c->nlab.ptr,
+                           taint ? c->ntaint.ptr : nullptr, pcpu, pmem, sel ? psel : nullptr, ptol, out, a);
+        HIPCHK(c, hipGetLastError());
+        c->last_kernel = "direct";
+    }
+    if (timed) HIPCHK(c, hipEventRecord(c->ev_pool[slot].b, s));
+    return KSCHED_OK;
+}
+}  // namespace
+
+int ksched_summarize_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, const uint64_t *ptol,
+                            uint32_t flags, uint32_t *out_counts, void *hip_stream) try {
+    if (int rc = check_summary_args(c, p, pcpu, pmem, flags, out_counts)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    DeviceGuard g(c->device);
+    if (!g.ok) return KSCHED_E_HIP;
+    return summarize_on_device(c, p, pcpu, pmem, psel, ptol, flags, out_counts, (hipStream_t)hip_stream);
+} KSCHED_ABI_CATCH(c)
+
+int ksched_summarize(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, const uint64_t *ptol,
+                     uint32_t flags, uint32_t *out_counts) try {
+    if (int rc = check_summary_args(c, p, pcpu, pmem, flags, out_counts)) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->have_nodes) return KSCHED_E_STATE;
+    if (p == 0) return KSCHED_OK;
+    DeviceGuard g(c->device);
+    if (!g.ok) return KSCHED_E_HIP;
+    hipStream_t s = c->stream;
+    const bool use_sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
+    const bool use_tol = (flags & KSCHED_TAINT) && ptol;
+    HIPCHK(c, c->pcpu.reserve(p));
+    HIPCHK(c, c->pmem.reserve(p));
+    HIPCHK(c, c->sum_out.reserve((size_t)p * KSCHED_SUMMARY_WORDS));
+    HIPCHK(c, hipMemcpyAsync(c->pcpu.ptr, pcpu, (size_t)p * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, pmem, (size_t)p * 8, hipMemcpyHostToDevice, s));
+    if (use_sel) {
+        HIPCHK(c, c->psel.reserve((size_t)p * c->nkeys));
+        HIPCHK(c, hipMemcpyAsync(c->psel.ptr, psel, (size_t)p * c->nkeys * 4, hipMemcpyHostToDevice, s));
+    }
+    if (use_tol) {
+        HIPCHK(c, c->ptol.reserve(p));
+        HIPCHK(c, hipMemcpyAsync(c->ptol.ptr, ptol, (size_t)p * 8, hipMemcpyHostToDevice, s));
+    }
+    if (int rc = summarize_on_device(c, p, c->pcpu.ptr, c->pmem.ptr, use_sel ? c->psel.ptr : nullptr, use_tol ? c->ptol.ptr : nullptr, flags,
+                                     c->sum_out.ptr, s))
+        return rc;
+    HIPCHK(c, hipMemcpyAsync(out_counts, c->sum_out.ptr, (size_t)p * KSCHED_SUMMARY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return KSCHED_OK;
 } KSCHED_ABI_CATCH(c)

@@ -57,6 +57,22 @@ class _StreamWork:
             cur.wait_stream(self._stream)
 
 
+def _abi_shard_bounds(lib, p: int, world: int, rank: int) -> Tuple[int, int]:
+    """rows [lo, hi) of rank `rank`: ksched_shard_bounds, the one definition of the row split"""
+    import ctypes as C
+    lo, hi, cpr = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    lib.ksched_shard_bounds(int(p), int(world), int(rank), C.byref(lo), C.byref(hi), C.byref(cpr))
+    return lo.value, hi.value
+
+
+def _summarize_rows(ev, lo: int, hi: int, req_cpu, req_mem, sel_val_ids, tolerations, flags: int):
+    """Evaluator.summarize over rows [lo, hi) of a whole batch's host columns ([p], sel_val_ids [n_keys][p])"""
+    import numpy as np
+    sel = None if sel_val_ids is None else np.ascontiguousarray(np.asarray(sel_val_ids)[:, lo:hi])
+    tol = None if tolerations is None else np.asarray(tolerations)[lo:hi]
+    return ev.summarize(np.asarray(req_cpu)[lo:hi], np.asarray(req_mem)[lo:hi], sel, tol, flags)
+
+
 class AbiComm:
     """RCCL communicator behind the C ABI (ksched_comm_*), one process per GPU.
 
@@ -135,6 +151,14 @@ class AbiComm:
         stream = stream or torch.cuda.current_stream(self._ev.device)
         self._check(self._lib.ksched_apply_bindings_sharded(self._ev._h, self._h, args[0], int(row_lo), *args[1:5], int(flags), args[5],
                                                             C.c_void_p(stream.cuda_stream)), "ksched_apply_bindings_sharded")
+
+    def summarize(self, req_cpu, req_mem, sel_val_ids=None, tolerations=None, flags: int = 1):
+        """This rank's part of a row-sharded batch's summary (Evaluator.summarize): the arguments are the WHOLE batch's host columns,
+        the rows are cut with ksched_shard_bounds.  -> (lo, hi, counts [hi - lo, SUMMARY_WORDS]).  Pod rows shard and the snapshot is
+        replicated, so there is nothing to merge per pod and no collective; a caller that wants the table on every rank pushes it
+        through all_gather as SUMMARY_WORDS int32 per pod."""
+        lo, hi = _abi_shard_bounds(self._lib, len(req_cpu), self.world, self.rank)
+        return lo, hi, _summarize_rows(self._ev, lo, hi, req_cpu, req_mem, sel_val_ids, tolerations, flags)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -227,6 +251,21 @@ class LocalClique:
                                                                   vp(keep[1]), vp(keep[2]), vp(keep[3]), int(flags), vp(keep[4]),
                                                                   vp(self._streams(streams))),
                     "ksched_apply_bindings_sharded_local")
+
+    def summarize(self, req_cpu, req_mem, sel_val_ids=None, tolerations=None, flags: int = 1):
+        """The summary of a row-sharded batch (Evaluator.summarize): rank i summarises rows ksched_shard_bounds gives it against its
+        replica of the snapshot, the parts are concatenated in rank order.  Host columns of the whole batch in, [p, SUMMARY_WORDS]
+        uint32 out; no collective (nothing to merge per pod)."""
+        import numpy as np
+        from . import _lib as L
+        self._live()
+        p = len(req_cpu)
+        out = np.empty((p, L.SUMMARY_WORDS), dtype=np.uint32)
+        for i, ev in enumerate(self._evs):
+            lo, hi = _abi_shard_bounds(self._lib, p, self.n, i)
+            if hi > lo:
+                out[lo:hi] = _summarize_rows(ev, lo, hi, req_cpu, req_mem, sel_val_ids, tolerations, flags)
+        return out
 
     def close(self):
         if getattr(self, "_comms", None) is not None:

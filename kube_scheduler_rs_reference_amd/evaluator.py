@@ -447,6 +447,54 @@ class Evaluator:
         self._check(rc, "ksched_explain")
         return out
 
+    def summarize(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, flags: int = L.FIT) -> np.ndarray:
+        """ksched_summarize: per pod the number of nodes check_node_validity accepts / rejects by reason, [p, SUMMARY_WORDS] uint32
+        (column r = REASON_*; column 0 = feasible nodes; every row adds up to the node count)."""
+        cpu = _np(req_cpu_milli, np.int64, "req_cpu_milli")
+        mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
+        p = cpu.shape[0]
+        if cpu.ndim != 1 or mem.shape != (p,):
+            raise ValueError("req_cpu_milli, req_mem_bytes must be 1-D of one length")
+        sel = _np(sel_val_ids, np.uint32, "sel_val_ids")
+        if sel is not None and sel.shape != (self.n_keys, p):
+            raise ValueError(f"sel_val_ids must be [{self.n_keys}][{p}]")
+        tol = _np(tolerations, np.uint64, "tolerations")
+        if tol is not None and tol.shape != (p,):
+            raise ValueError(f"tolerations must be [{p}]")
+        out = np.empty((p, L.SUMMARY_WORDS), dtype=np.uint32)
+        rc = self._lib.ksched_summarize(self._h, p, _ptr(cpu), _ptr(mem), _ptr(sel), _ptr(tol), int(flags), _ptr(out))
+        self._check(rc, "ksched_summarize")
+        return out
+
+    def summarize_device(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, flags: int = L.FIT, out=None, stream=None):
+        """ksched_summarize_device on torch CUDA tensors (int64 stands in for uint64, int32 for uint32); enqueued on `stream`
+        (default: torch's current stream), the host does not wait.  `out`: a contiguous [p, SUMMARY_WORDS] int32/uint32 tensor
+        (allocated when None; it need not be zeroed).  Returns it."""
+        import torch
+
+        def dp(t, dtypes, shape):
+            if t is None:
+                return None
+            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.dtype not in dtypes:
+                raise ValueError(f"expected contiguous {dtypes} CUDA tensor on cuda:{self.device}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"expected shape {shape}, got {tuple(t.shape)}")
+            return C.c_void_p(t.data_ptr())
+
+        p = int(req_cpu_milli.shape[0])
+        u64 = (torch.int64, torch.uint64)
+        u32 = (torch.int32, torch.uint32)
+        if out is None:
+            out = torch.empty((p, L.SUMMARY_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        rc = self._lib.ksched_summarize_device(
+            self._h, p, dp(req_cpu_milli, (torch.int64,), (p,)), dp(req_mem_bytes, (torch.int64,), (p,)),
+            dp(sel_val_ids, u32, (self.n_keys, p)), dp(tolerations, u64, (p,)), int(flags), dp(out, u32, (p, L.SUMMARY_WORDS)),
+            C.c_void_p(stream.cuda_stream))
+        self._check(rc, "ksched_summarize_device")
+        return out
+
     def reason(self, feasible_row: np.ndarray, fit_row: Optional[np.ndarray], node: int, flags: int) -> int:
         f = np.ascontiguousarray(feasible_row, dtype=np.uint64)
         r = None if fit_row is None else np.ascontiguousarray(fit_row, dtype=np.uint64)

@@ -358,5 +358,61 @@ std::vector<Validity> explain_pairs(const std::vector<const corev1::Pod *> &pods
     return out;
 }
 
+std::vector<uint32_t> summarize_batch(const std::vector<const corev1::Pod *> &pods, Context &ctx, bool taints) {
+    if (!ctx.snapshot) ctx.refresh_snapshot();
+    Snapshot &snap = *ctx.snapshot;
+    if (taints && snap.has_taints()) snap.enable_taints();
+    const bool with_taints = taints && snap.has_taints();
+    const uint32_t flags = KSCHED_FIT | KSCHED_SEL | (with_taints ? KSCHED_TAINT : 0u);
+    const uint32_t n = snap.n(), W = snap.mask_words();
+    std::vector<uint32_t> out(pods.size() * KSCHED_SUMMARY_WORDS, 0u);
+    if (pods.empty() || n == 0) return out;  // an empty store: nothing is feasible and nothing is rejected
+    for (const KeyRange &r : key_ranges(pods)) {
+        uint32_t *rows = out.data() + r.lo * KSCHED_SUMMARY_WORDS;
+        if (!r.wide) {
+            const std::vector<const corev1::Pod *> part(pods.begin() + (std::ptrdiff_t)r.lo, pods.begin() + (std::ptrdiff_t)r.hi);
+            PodColumns pc = snap.encode_pods(part);
+            if (ShardedContext *sh = snap.sharded()) {
+                sh->summarize(pc, flags, rows);
+                continue;
+            }
+            DeviceEvaluator &dev = snap.device();
+            dev.check(ksched_summarize(dev.handle(), pc.p, pc.req_cpu_milli.data(), pc.req_mem_bytes.data(), pc.n_keys ? pc.sel_val_ids.data() : nullptr,
+                                       with_taints ? pc.tolerations.data() : nullptr, flags, rows),
+                      "ksched_summarize");
+            continue;
+        }
+        // a wide pod: F & S over its key groups (does_node_selector_match is a conjunction over the keys, src/predicates.rs:48-53; the
+        // fit mask is the same in every group), T once, and the four counts in check_node_validity's order on the host
+        DeviceEvaluator &dev = snap.device();
+        std::vector<uint64_t> fs(W, ~0ull), fit(W, 0ull), f(W), ft(W), tnt(W, ~0ull);
+        for (const corev1::Pod &part : split_wide_pod(*pods[r.lo])) {
+            PodColumns pc = snap.encode_pods({&part});  // (re-uploads the label columns of this group's keys)
+            dev.check(ksched_eval(dev.handle(), 1, pc.req_cpu_milli.data(), pc.req_mem_bytes.data(), pc.n_keys ? pc.sel_val_ids.data() : nullptr, nullptr,
+                                  nullptr, 0, KSCHED_FIT | KSCHED_SEL | KSCHED_WANT_FIT_MASK, f.data(), ft.data(), nullptr),
+                      "ksched_eval");
+            for (uint32_t w = 0; w < W; ++w) fs[w] &= f[w];
+            fit = ft;
+            if (with_taints)  // (the pod's tolerations are the same in every group: the last group's answer is the pod's)
+                dev.check(ksched_eval(dev.handle(), 1, pc.req_cpu_milli.data(), pc.req_mem_bytes.data(), nullptr, pc.tolerations.data(), nullptr, 0,
+                                      KSCHED_TAINT, tnt.data(), nullptr, nullptr),
+                          "ksched_eval");
+        }
+        uint32_t c_ok = 0, c_fit = 0, c_sel = 0, c_taint = 0;
+        for (uint32_t w = 0; w < W; ++w) {
+            // (padding bits are zero in fit, hence in every term)
+            c_fit += (uint32_t)__builtin_popcountll(fit[w]);
+            c_ok += (uint32_t)__builtin_popcountll(fs[w] & tnt[w]);
+            c_sel += (uint32_t)__builtin_popcountll(fit[w] & ~fs[w]);
+            c_taint += (uint32_t)__builtin_popcountll(fs[w] & ~tnt[w]);
+        }
+        rows[KSCHED_REASON_OK] = c_ok;
+        rows[KSCHED_REASON_NOT_ENOUGH_RESOURCES] = n - c_fit;
+        rows[KSCHED_REASON_NODE_SELECTOR_MISMATCH] = c_sel;
+        rows[KSCHED_REASON_TAINT_NOT_TOLERATED] = c_taint;
+    }
+    return out;
+}
+
 }  // namespace predicates
 }  // namespace ksched_host

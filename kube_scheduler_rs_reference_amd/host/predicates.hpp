@@ -87,5 +87,13 @@ std::vector<DeviceCall> device_calls(const std::vector<const corev1::Pod *> &pod
 std::vector<Validity> explain_pairs(const std::vector<const corev1::Pod *> &pods, Context &ctx,
                                     const std::vector<std::pair<uint32_t, uint32_t>> &pairs, bool taints = false);
 
+// Why is a pod unschedulable: for every pod of the batch, how many nodes of ctx.snapshot check_node_validity accepts and how many it
+// rejects for each InvalidNodeReason (ksched_summarize: one device call per key-budget range, through the sharded context when the
+// snapshot has one; no mask is computed).  -> [p][KSCHED_SUMMARY_WORDS], word r = KSCHED_REASON_* (word 0 = feasible nodes); every row
+// adds up to the node count.  A pod whose selector has more keys than one call takes cannot be summed from per-group counts (a node
+// may fail in one group and not in another): its counts are taken on the host from the masks of its key groups -- FIT | SEL per
+// group, ANDed, the fit mask for the precedence, and the taint mask once.
+std::vector<uint32_t> summarize_batch(const std::vector<const corev1::Pod *> &pods, Context &ctx, bool taints = false);
+
 }  // namespace predicates
 }  // namespace ksched_host

@@ -161,6 +161,43 @@ void warn_rejected(const std::vector<const corev1::Pod *> &pods, Context &ctx, c
         for (const RejectedCandidate &r : rejected[i]) ctx.warn(rejected_line(*pods[i], r));
 }
 
+std::vector<Unschedulable> explain_unschedulable(const std::vector<const corev1::Pod *> &pods, Context &ctx, bool taints) {
+    const std::vector<uint32_t> counts = predicates::summarize_batch(pods, ctx, taints);
+    const uint32_t n = ctx.snapshot ? ctx.snapshot->n() : 0u;
+    std::vector<Unschedulable> out(pods.size());
+    for (size_t i = 0; i < pods.size(); ++i) {
+        const uint32_t *c = counts.data() + i * KSCHED_SUMMARY_WORDS;
+        out[i].nodes = n;
+        out[i].ok = c[KSCHED_REASON_OK];
+        out[i].not_enough_resources = c[KSCHED_REASON_NOT_ENOUGH_RESOURCES];
+        out[i].node_selector_mismatch = c[KSCHED_REASON_NODE_SELECTOR_MISMATCH];
+        out[i].taint_not_tolerated = c[KSCHED_REASON_TAINT_NOT_TOLERATED];
+    }
+    return out;
+}
+
+std::string format_unschedulable(const Unschedulable &u) {
+    std::string s = std::to_string(u.ok) + "/" + std::to_string(u.nodes) + " nodes are available";
+    const std::pair<uint32_t, predicates::InvalidNodeReason> parts[] = {
+        {u.not_enough_resources, predicates::InvalidNodeReason::NotEnoughResources},
+        {u.node_selector_mismatch, predicates::InvalidNodeReason::NodeSelectorMismatch},
+        {u.taint_not_tolerated, predicates::InvalidNodeReason::TaintNotTolerated},
+    };
+    bool any = false;
+    for (const auto &part : parts) {
+        if (!part.first) continue;
+        s += any ? ", " : ": ";
+        s += std::to_string(part.first) + " " + predicates::debug_name(part.second);
+        any = true;
+    }
+    if (any) s += ".";
+    return s;
+}
+
+std::string unschedulable_line(const corev1::Pod &pod, const Unschedulable &u) {
+    return "pod " + full_name(pod.metadata) + " found no node: " + format_unschedulable(u);
+}
+
 const char *debug_name(ReconcileError e) {
     switch (e) {
         case ReconcileError::CreateBindingFailed: return "CreateBindingFailed";
@@ -178,10 +215,39 @@ Action error_policy(const corev1::Pod &pod, ReconcileError error, Context &ctx) 
 
 namespace {
 // what the Controller does with a failed reconcile: error_policy (src/main.rs:141-144) -- here for every failed outcome of a batch, in batch order
-void warn_failed(const std::vector<const corev1::Pod *> &pods, const std::vector<ReconcileOutcome> &out, Context &ctx) {
+// `why`: Context::explain_no_node_found's lines, by pod (empty = none): each follows its pod's "reconcile failed" line
+void warn_failed(const std::vector<const corev1::Pod *> &pods, const std::vector<ReconcileOutcome> &out, Context &ctx,
+                 const std::vector<std::string> *why = nullptr) {
     if (!ctx.warn) return;
     for (size_t i = 0; i < pods.size() && i < out.size(); ++i)
-        if (!out[i].ok) (void)error_policy(*pods[i], out[i].error, ctx);
+        if (!out[i].ok) {
+            (void)error_policy(*pods[i], out[i].error, ctx);
+            if (why && i < why->size() && !(*why)[i].empty()) ctx.warn((*why)[i]);
+        }
+}
+
+// Context::explain_no_node_found: the lines for the pods of `batch` that were given no node (`no_node[j]`), into why[where[j]].  Called
+// right after the batch's evaluation, BEFORE its bindings change the snapshot: the counts are those of the state the picks were made
+// against (a node that this very batch fills still counts as available to the pods it turned away).  One ksched_summarize call per
+// key-budget range over exactly those pods; nothing happens when the option or the WARN level is off.  A log line: a failure to produce
+// it degrades to one warning and never costs the batch its bindings.
+void explain_no_node(const std::vector<const corev1::Pod *> &batch, const std::vector<bool> &no_node, const std::vector<size_t> &where, Context &ctx,
+                     std::vector<std::string> &why) {
+    if (!ctx.explain_no_node_found || !ctx.warn) return;
+    std::vector<const corev1::Pod *> lost;
+    std::vector<size_t> slot;
+    for (size_t j = 0; j < batch.size(); ++j)
+        if (no_node[j]) {
+            lost.push_back(batch[j]);
+            slot.push_back(where[j]);
+        }
+    if (lost.empty()) return;
+    try {
+        const std::vector<Unschedulable> u = explain_unschedulable(lost, ctx);
+        for (size_t k = 0; k < lost.size(); ++k) why[slot[k]] = unschedulable_line(*lost[k], u[k]);
+    } catch (const std::exception &e) {
+        ctx.warn(std::string("the pods without a node of this batch could not be explained: ") + e.what());
+    }
 }
 }  // namespace
 
@@ -281,6 +347,15 @@ std::vector<ReconcileOutcome> reconcile_batch(const std::vector<const corev1::Po
     std::vector<const corev1::Node *> chosen(pending.size(), nullptr);
     for (size_t j = 0; j < pending.size(); ++j)
         if (sel.node_store_index[j] >= 0) chosen[j] = &ctx.node_store[(size_t)sel.node_store_index[j]];
+    // Context::explain_no_node_found (opt-in): why the pods without a node found none, against the snapshot they were evaluated against --
+    // here, before the bindings of this batch are staged or committed
+    std::vector<std::string> why;
+    if (ctx.explain_no_node_found && ctx.warn) {
+        why.assign(pods.size(), std::string());
+        std::vector<bool> no_node(pending.size());
+        for (size_t j = 0; j < pending.size(); ++j) no_node[j] = chosen[j] == nullptr;
+        explain_no_node(pending, no_node, where, ctx, why);
+    }
     // The bindings count against their nodes for the NEXT batch (the reference gets that from re-LISTing on every evaluation,
     // src/predicates.rs:34-38; here the snapshot is patched in one device update).  Everything of that update that only READS the
     // snapshot -- the pods' keys, what the bookkeeping holds for them, the per-node sums -- is worked out WHILE THE POSTS ARE IN FLIGHT
@@ -348,7 +423,7 @@ std::vector<ReconcileOutcome> reconcile_batch(const std::vector<const corev1::Po
     } catch (const std::exception &e) {
         if (ctx.warn) ctx.warn(std::string("the rejected candidates of this batch could not be listed: ") + e.what());
     }
-    warn_failed(pods, out, ctx);
+    warn_failed(pods, out, ctx, why.empty() ? nullptr : &why);
     if (timing) {
         const auto t4 = std::chrono::steady_clock::now();
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -369,12 +444,19 @@ std::vector<ReconcileOutcome> reconcile_batch_sequential(const std::vector<const
         if (!is_pod_bound(*pods[i])) pending.push_back(i);  // src/main.rs:74-76
     if (!ctx.snapshot) ctx.refresh_snapshot();
     SequentialStats st;
+    const bool explain = ctx.explain_no_node_found && ctx.warn;
+    std::vector<std::string> why(explain ? pods.size() : 0);
     while (!pending.empty() && st.rounds < max_rounds) {
         ++st.rounds;
         std::vector<const corev1::Pod *> batch;
         for (size_t i : pending) batch.push_back(pods[i]);
         const BatchSelection sel = select_nodes_for_pods(batch, ctx, chooser);  // one device evaluation + pick
         warn_rejected(batch, ctx, sel);
+        if (explain) {  // this round's NoNodeFound pods, against the snapshot the round was evaluated against (before observe_bound below)
+            std::vector<bool> no_node(pending.size());
+            for (size_t j = 0; j < pending.size(); ++j) no_node[j] = sel.node_store_index[j] < 0;
+            explain_no_node(batch, no_node, pending, ctx, why);
+        }
         std::vector<size_t> next;
         std::vector<bool> taken(ctx.node_store.size(), false);
         std::vector<std::pair<const corev1::Pod *, const std::string *>> landed;  // (pod, the node it was bound to), for the snapshot update
@@ -398,9 +480,14 @@ std::vector<ReconcileOutcome> reconcile_batch_sequential(const std::vector<const
         ctx.snapshot->observe_bound(landed);
         pending.swap(next);
     }
+    if (explain && !pending.empty()) {  // still colliding after max_rounds: against the snapshot as the last round left it
+        std::vector<const corev1::Pod *> batch;
+        for (size_t i : pending) batch.push_back(pods[i]);
+        explain_no_node(batch, std::vector<bool>(pending.size(), true), pending, ctx, why);
+    }
     for (size_t i : pending) out[i] = bind(*pods[i], nullptr, sink);  // still colliding after max_rounds
     if (stats) *stats = st;
-    warn_failed(pods, out, ctx);
+    warn_failed(pods, out, ctx, explain ? &why : nullptr);
     return out;
 }
 

@@ -80,6 +80,25 @@ std::string rejected_line(const corev1::Pod &pod, const RejectedCandidate &r);
 // emits them through ctx.warn, pod by pod, draw by draw (nothing happens -- and nothing is asked of the device -- when the level is off)
 void warn_rejected(const std::vector<const corev1::Pod *> &pods, Context &ctx, const BatchSelection &sel);
 
+// ---- why a pod is unschedulable --------------------------------------------------------------------
+// The reference ends a pod that found no node with a bare NoNodeFound (src/main.rs:116-118) after ATTEMPTS blind draws.  This is the
+// statement about the whole cluster behind it: how many of the snapshot's nodes check_node_validity (src/predicates.rs:63-77) accepts
+// for the pod and how many it rejects for each InvalidNodeReason, resources first (:68-70), then the selector (:72-74), then the
+// taint extension.  nodes == ok + the three rejections.
+struct Unschedulable {
+    uint32_t nodes = 0, ok = 0, not_enough_resources = 0, node_selector_mismatch = 0, taint_not_tolerated = 0;
+};
+// One ksched_summarize per key-budget range of the batch (predicates::summarize_batch: through the sharded context when the snapshot
+// has one; a pod with more selector keys than one call takes is counted from its key groups' masks), against ctx.snapshot as it is
+// now.  `taints` adds extension E2, as in check_node_validity_batch.
+std::vector<Unschedulable> explain_unschedulable(const std::vector<const corev1::Pod *> &pods, Context &ctx, bool taints = false);
+// "0/5000 nodes are available: 3120 NotEnoughResources, 1880 NodeSelectorMismatch." -- the reasons in InvalidNodeReason order with their
+// Debug names, zero counts left out; "{ok}/{nodes} nodes are available" alone when nothing is rejected.
+std::string format_unschedulable(const Unschedulable &u);
+// the line reconcile_batch / reconcile_batch_sequential emit per NoNodeFound pod with Context::explain_no_node_found:
+// "pod {namespace/name} found no node: {format_unschedulable}"
+std::string unschedulable_line(const corev1::Pod &pod, const Unschedulable &u);
+
 // ---- reconcile ------------------------------------------------------------------------------------
 
 enum class ReconcileError { CreateBindingFailed, CreateBindingObjectFailed, NoNodeFound };  // src/error.rs:5-15

@@ -134,4 +134,28 @@ void ShardedContext::eval(const PodColumns &pc, const uint32_t *samples, uint32_
     ++batches_;
 }
 
+void ShardedContext::summarize(const PodColumns &pc, uint32_t flags, uint32_t *out_counts) {
+    const uint32_t n = size(), p = pc.p;
+    if (p == 0) return;
+    // (the host-pointer entry point takes packed [n_keys][rows] selector columns: a shard's rows are cut out of the batch's [n_keys][p])
+    std::vector<uint32_t> sel;
+    for (uint32_t r = 0; r < n; ++r) {
+        const ShardBounds b = shard_bounds(p, n, r);
+        const uint32_t lo = b.lo, rows = b.hi - b.lo;
+        if (rows == 0) continue;
+        const uint32_t *sel_ptr = nullptr;
+        if (pc.n_keys) {
+            sel.resize((size_t)pc.n_keys * rows);
+            for (uint32_t k = 0; k < pc.n_keys; ++k)
+                std::memcpy(sel.data() + (size_t)k * rows, pc.sel_val_ids.data() + (size_t)k * p + lo, (size_t)rows * sizeof(uint32_t));
+            sel_ptr = sel.data();
+        }
+        const int rc = ksched_summarize(devs_[r]->handle(), rows, pc.req_cpu_milli.data() + lo, pc.req_mem_bytes.data() + lo, sel_ptr,
+                                        (flags & KSCHED_TAINT) && !pc.tolerations.empty() ? pc.tolerations.data() + lo : nullptr, flags,
+                                        out_counts + (size_t)lo * KSCHED_SUMMARY_WORDS);
+        if (rc != KSCHED_OK)
+            throw EncodeError("ksched_summarize on shard " + std::to_string(r) + ": " + ksched_strerror(rc) + " (" + ksched_last_error(devs_[r]->handle()) + ")");
+    }
+}
+
 }  // namespace ksched_host

@@ -62,6 +62,10 @@ public:
     void eval(const PodColumns &pc, const uint32_t *samples, uint32_t attempts, uint32_t flags, uint32_t W, uint64_t *out_feasible,
               uint64_t *out_fit, int32_t *out_binding);
 
+    // ksched_summarize over the devices: pod rows shard (ksched_shard_bounds), the snapshot is replicated, so every device summarises
+    // its own rows and there is nothing to merge per pod -- no collective.  out_counts: [pc.p][KSCHED_SUMMARY_WORDS], host.
+    void summarize(const PodColumns &pc, uint32_t flags, uint32_t *out_counts);
+
     uint64_t batches() const { return batches_; }  // observability: evaluations that went through the exchange
     bool broken() const { return broken_; }        // a failed exchange aborted the communicator: every further eval throws
 

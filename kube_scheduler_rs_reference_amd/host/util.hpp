@@ -67,6 +67,12 @@ struct Context {
     // for it: the batched path asks the device for the rejected draws' reasons (ksched_explain) only when somebody listens.
     std::function<void(const std::string &)> warn = default_warn_sink();
 
+    // Opt-in (default off): with the WARN level on, reconcile_batch / reconcile_batch_sequential follow every NoNodeFound pod's
+    // "reconcile failed" line with one line saying why -- "pod ns/name found no node: 0/5000 nodes are available: 3120 NotEnoughResources,
+    // 1880 NodeSelectorMismatch." (scheduler.hpp: explain_unschedulable) -- from ONE ksched_summarize call per batch over exactly those pods,
+    // against the snapshot the batch was evaluated against.  Off: not one byte of output and no device call changes.
+    bool explain_no_node_found = false;
+
     // (Re)build `snapshot` from node_store and one LIST per node.
     void refresh_snapshot();
     // Keep node_store and the snapshot current from node watch events, the way the reflector's writer does: an Applied node already in

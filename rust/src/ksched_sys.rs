@@ -52,6 +52,7 @@ pub const KSCHED_REASON_OK: c_int = 0;
 pub const KSCHED_REASON_NOT_ENOUGH_RESOURCES: c_int = 1; // InvalidNodeReason::NotEnoughResources   (src/predicates.rs:16)
 pub const KSCHED_REASON_NODE_SELECTOR_MISMATCH: c_int = 2; // InvalidNodeReason::NodeSelectorMismatch (src/predicates.rs:17)
 pub const KSCHED_REASON_TAINT_NOT_TOLERATED: c_int = 3; // extension E2 only
+pub const KSCHED_SUMMARY_WORDS: u32 = 4; // ksched_summarize*: per pod [feasible, NotEnoughResources, NodeSelectorMismatch, TaintNotTolerated]
 
 pub const KSCHED_OPT_KERNEL: c_int = 1;
 pub const KSCHED_OPT_TIMING: c_int = 2;
@@ -157,6 +158,15 @@ extern "C" {
         ctx: *mut ksched_ctx, p: u32, req_cpu_milli: *const i64, req_mem_bytes: *const i64, sel_val_ids: *const u32,
         tolerations: *const u64, count: u32, pair_pod: *const u32, pair_node: *const u32, flags: u32, out_reason: *mut i32,
     ) -> c_int;
+    // ---- per-pod node counts by reason (what stands behind NoNodeFound, src/main.rs:116-118)
+    pub fn ksched_summarize_device(
+        ctx: *mut ksched_ctx, p: u32, req_cpu_milli: *const i64, req_mem_bytes: *const i64, sel_val_ids: *const u32,
+        tolerations: *const u64, flags: u32, out_counts: *mut u32, hip_stream: *mut c_void,
+    ) -> c_int;
+    pub fn ksched_summarize(
+        ctx: *mut ksched_ctx, p: u32, req_cpu_milli: *const i64, req_mem_bytes: *const i64, sel_val_ids: *const u32,
+        tolerations: *const u64, flags: u32, out_counts: *mut u32,
+    ) -> c_int;
     // ---- multi-GPU: RCCL all-gather of the (pod -> node) bindings
     pub fn ksched_comm_unique_id(id: *mut u8) -> c_int;
     pub fn ksched_comm_create(ctx: *mut ksched_ctx, id: *const u8, rank: c_int, nranks: c_int, out: *mut *mut ksched_comm) -> c_int;
@@ -232,6 +242,8 @@ pub fn symbol_table() -> Vec<(&'static str, usize)> {
         ("ksched_pipe_slot_stream", ksched_pipe_slot_stream as usize),
         ("ksched_reason", ksched_reason as usize),
         ("ksched_explain", ksched_explain as usize),
+        ("ksched_summarize_device", ksched_summarize_device as usize),
+        ("ksched_summarize", ksched_summarize as usize),
         ("ksched_comm_unique_id", ksched_comm_unique_id as usize),
         ("ksched_comm_create", ksched_comm_create as usize),
         ("ksched_comm_create_local", ksched_comm_create_local as usize),
@@ -286,6 +298,7 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_REASON_NOT_ENOUGH_RESOURCES", KSCHED_REASON_NOT_ENOUGH_RESOURCES as i64),
         ("KSCHED_REASON_NODE_SELECTOR_MISMATCH", KSCHED_REASON_NODE_SELECTOR_MISMATCH as i64),
         ("KSCHED_REASON_TAINT_NOT_TOLERATED", KSCHED_REASON_TAINT_NOT_TOLERATED as i64),
+        ("KSCHED_SUMMARY_WORDS", KSCHED_SUMMARY_WORDS as i64),
         ("KSCHED_OPT_KERNEL", KSCHED_OPT_KERNEL as i64),
         ("KSCHED_OPT_TIMING", KSCHED_OPT_TIMING as i64),
         ("KSCHED_OPT_DEBUG", KSCHED_OPT_DEBUG as i64),

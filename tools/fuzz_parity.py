@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Randomised differential test of the HIP path against the oracle (GPU box): random shapes, key counts and cardinalities (incl.
-list keys and > 8 keys), taints, predicate subsets, both picks, snapshot updates between evaluations, both kernels, per-pair reasons (ksched_explain),
+list keys and > 8 keys), taints, predicate subsets, both picks, snapshot updates between evaluations, both kernels, per-pair reasons (ksched_explain), per-pod node counts by reason (ksched_summarize),
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
 ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts),
 the two halves of ksched_eval over 1 .. 5 row shards (ksched_shard_bounds / ksched_eval_begin / ksched_eval_end) and -- with the test hooks on
@@ -301,6 +301,24 @@ while time.time() < t_end:
             if not np.array_equal(got_r, want_r[pp, pn]):
                 fails += 1
                 print(f"FAIL explain case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} preds={preds:#x}", flush=True)
+        # ksched_summarize of the batch just evaluated == the popcounts of three single-predicate oracle masks, in check_node_validity's
+        # order.  The decision comes from a generator of its own: the sequence of cases of a seed is what it was without this step.
+        r_sum = np.random.default_rng([cs, 0x5C0])
+        if r_sum.random() < 0.25:
+            full = np.full((P, (N + 63) // 64), np.uint64(0xFFFFFFFFFFFFFFFF))
+            if N % 64:
+                full[:, -1] = np.uint64((1 << (N % 64)) - 1)
+            mask = lambda f: capi.eval_encoded(cpu, mem, lab, taints, rc, rm, sel, tol, None, f)[0] if preds & f else full  # noqa: E731
+            mF, mS, mT = mask(L.FIT), mask(L.SEL), mask(L.TAINT)
+            pop = lambda m: np.bitwise_count(m).sum(axis=1) if hasattr(np, "bitwise_count") else np.unpackbits(np.ascontiguousarray(m).view(np.uint8), axis=1).sum(axis=1)  # noqa: E731
+            want_c = np.stack([pop(mF & mS & mT), N - pop(mF), pop(mF & ~mS), pop(mF & mS & ~mT)], axis=1).astype(np.uint32)
+            ev.set_kernel(str(r_sum.choice(["auto", "auto", "direct"])))
+            got_c = ev.summarize(rc, rm, sel if K else None, tol if (preds & L.TAINT) else None, preds)
+            ev.set_kernel("auto")
+            if not np.array_equal(got_c, want_c):
+                fails += 1
+                print(f"FAIL summarize case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} preds={preds:#x} kernel={ev.last_kernel}", flush=True)
+            picks["summarize"] = picks.get("summarize", 0) + 1
     except Exception as e:  # noqa: BLE001
         fails += 1
         print(f"EXCEPTION case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} flags={flags:#x}: {e}", flush=True)
