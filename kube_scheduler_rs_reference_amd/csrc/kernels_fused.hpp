@@ -42,6 +42,7 @@
 
 #include <type_traits>
 
+#include "eval_request.hpp"
 #include "kernarg.hpp"
 #include "kernels_direct.hpp"  // SelectArgs, select_one_pod: the sampled pick that rides in this kernel's fill (PICK)
 #include "tile_index.hpp"
@@ -1144,16 +1145,27 @@ inline bool fused_applicable(const IndexedSnapshot &s, uint32_t flags) {
     return fused_lds_bytes(s.lay, flags & KSCHED_FIT, (flags & KSCHED_SEL) && s.lay.nkeys, (flags & KSCHED_TAINT) && s.lay.ngroups) <= kLdsBudget;
 }
 
-// pitch = words between consecutive pod rows of the output masks (>= W; W = packed).
-inline hipError_t run_fused(const IndexedSnapshot &s, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
-                            const uint64_t *ptol, uint32_t flags, uint64_t *out_feas, uint64_t *out_fit, uint32_t pitch, hipStream_t stream,
-                            uint32_t debug = 0, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, uint64_t *trace = nullptr,
-                            uint32_t trace_blocks = 0, const SelectArgs *pick = nullptr, int pick_form = 1, uint64_t *pick_acc = nullptr,
-                            uint32_t grid_cus = 0, int round_order = 0) {
+// what a fused launch takes besides the request
+struct FusedOptions {
+    uint32_t debug = 0;                                // KSCHED_OPT_DEBUG
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // timing events carried on the dispatch packet
+    uint64_t *trace = nullptr;                         // per-block phase time stamps, for launches of at most trace_blocks blocks
+    uint32_t trace_blocks = 0;
+    const SelectArgs *pick = nullptr;                  // the sampled pick riding in the launch: form 1 = waves of the fill, 2 = tile tests (with their accumulators)
+    int pick_form = 1;
+    uint64_t *pick_acc = nullptr;
+    uint32_t grid_cus = 0;                             // KSCHED_OPT_GRID_CUS
+    int round_order = 0;                               // KSCHED_OPT_ROUND_ORDER
+};
+
+// out_feas: where the feasible mask goes (the request's, or the caller's scratch one)
+inline hipError_t run_fused(const IndexedSnapshot &s, const EvalRequest &r, uint64_t *out_feas, const FusedOptions &o) {
+    const uint32_t p = r.p, debug = o.debug;
+    const SelectArgs *const pick = o.pick;
     const IndexedLayout &l = s.lay;
     FusedArgs a{};
     a.W = l.W;
-    a.pitch = pitch;
+    a.pitch = r.pitch;
     a.tiles = l.tiles;
     a.rows = l.rows;
     a.nkeys = l.nkeys;
@@ -1173,13 +1185,13 @@ inline hipError_t run_fused(const IndexedSnapshot &s, uint32_t p, const int64_t 
     a.p = p;
     a.units = (p + 7u) / 8u;
     a.debug = debug;
-    a.has_tol = ptol != nullptr ? 1u : 0u;
-    const bool do_fit = flags & KSCHED_FIT;
-    const bool do_sel = (flags & KSCHED_SEL) && psel && l.nkeys;
-    const bool do_taint = (flags & KSCHED_TAINT) && l.ngroups;
-    const bool tile_pick = pick && pick_form == 2;
+    a.has_tol = r.ptol != nullptr ? 1u : 0u;
+    const bool do_fit = r.fit();
+    const bool do_sel = r.sel(l.nkeys);
+    const bool do_taint = r.taint(l.ngroups != 0);  // (the layout's taint groups, not the snapshot's have_taints)
+    const bool tile_pick = pick && o.pick_form == 2;
     const uint32_t lds = fused_lds_bytes(l, do_fit, do_sel, do_taint, &a, tile_pick);
-    a.pick_acc = pick_acc;
+    a.pick_acc = o.pick_acc;
 
     // chunks: as many pod ranges as keep every block resident at once (256 CUs x blocks per CU), but no
     // more than one round (64 pods) per wave needs.
@@ -1195,14 +1207,14 @@ inline hipError_t run_fused(const IndexedSnapshot &s, uint32_t p, const int64_t 
     const uint32_t want = (rounds + per_block - 1u) / per_block;
     // grid_cus (KSCHED_OPT_GRID_CUS): the launch keeps to that many compute units, so that the launches of the FOLLOWING batches
     // (other streams) find free ones and fill while this one stores; 0 = the whole chip
-    const uint32_t cus = grid_cus ? std::min(256u, grid_cus) : 256u;
+    const uint32_t cus = o.grid_cus ? std::min(256u, o.grid_cus) : 256u;
     a.chunks = std::max(1u, std::min((cus * blocks_per_cu) / l.tiles, want));
     // Interleaved orders, launches of TWO rounds per wave (C3: 1 563 rounds over 51 x 16 waves): the launch lasts as long as its two-round waves, and
     // at the largest resident chunk count one wave in twelve has only one -- the smallest chunk count that still needs no third round (49: 784 waves x 2
     // rounds) fills fewer blocks for the same two rounds: step 18.05 -> 17.6 us (sweep of 44 .. 51 chunks, session r7i: 18.43 18.25 17.94 17.91 17.77
     // 17.6 17.8 18.05).  Longer launches are bound by their stores, not by the quantisation, and want every compute unit (session r7k, even / largest
     // chunk count: 150 k pods 23.5 / 23.3 us, 300 k 43.3 / 40.0, 400 k 55.7 / 52.4); one-round launches keep the finer cut (a riding pick's pods spread wider).
-    if (round_order != 1 && !(debug & 0x80000000u)) {  // (debug bit 31: the largest resident chunk count, the A/B of this rule)
+    if (o.round_order != 1 && !(debug & 0x80000000u)) {  // (debug bit 31: the largest resident chunk count, the A/B of this rule)
         const uint32_t streams = a.chunks * kFusedWaves;
         const uint32_t per_wave = (rounds + streams - 1u) / streams;
         if (per_wave == 2u) a.chunks = std::max(1u, std::min(a.chunks, (rounds + 2u * kFusedWaves - 1u) / (2u * kFusedWaves)));
@@ -1210,23 +1222,23 @@ inline hipError_t run_fused(const IndexedSnapshot &s, uint32_t p, const int64_t 
     a.unit_q = a.units / a.chunks;
     a.unit_rem = a.units % a.chunks;
     // KSCHED_OPT_ROUND_ORDER: 0 = interleaved, wave-major (default); 1 = blocked; 2 = interleaved, chunk-major
-    a.u_stride = round_order == 1 ? 8u : a.chunks * kFusedWaves * 8u;
-    a.wave_major = round_order == 2 ? 0u : 1u;
+    a.u_stride = o.round_order == 1 ? 8u : a.chunks * kFusedWaves * 8u;
+    a.wave_major = o.round_order == 2 ? 0u : 1u;
     a.tiles_rcp = (uint32_t)std::min<uint64_t>((1ull << 32) / l.tiles, 0xFFFFFFFFull);
     const uint32_t total = a.chunks * l.tiles;
     a.run = (total + 7u) / 8u;
     const dim3 grid((debug & 32u) ? total : a.run * 8u);
-    a.trace = (trace && grid.x <= trace_blocks) ? trace : nullptr;
-    const bool want_fit = (flags & KSCHED_WANT_FIT_MASK) && out_fit;
+    a.trace = (o.trace && grid.x <= o.trace_blocks) ? o.trace : nullptr;
+    const bool want_fit = r.want_fit();
     const int sel = do_sel ? 1 : 0, tnt = do_taint ? 1 : 0, fit = do_fit ? 1 : 0;
     const bool list = do_sel && l.nlist > 0;
     if (pick && (want_fit || list)) return hipErrorInvalidValue;  // (the caller checks fused_pick_applicable first: a pick is never dropped silently)
-    if (tile_pick && (!pick_acc || do_taint || (do_sel && l.nkeys > 8u) || pick->attempts != kPickAttempts || lds > kLdsBudget)) return hipErrorInvalidValue;
+    if (tile_pick && (!o.pick_acc || do_taint || (do_sel && l.nkeys > 8u) || pick->attempts != kPickAttempts || lds > kLdsBudget)) return hipErrorInvalidValue;
     if (pick) {
         a.pick_ppb = (p + total - 1u) / total;
         a.pick_waves = std::max(1u, std::min(8u, (a.pick_ppb + 63u) / 64u));
     }
-    const FusedLaunch q{grid, lds, stream, &s, pcpu, pmem, psel, ptol, out_feas, out_fit, ev_start, ev_stop, pick, pick_form};
+    const FusedLaunch q{grid, lds, r.stream, &s, r.pcpu, r.pmem, r.psel, r.ptol, out_feas, r.out_fit, o.ev_start, o.ev_stop, pick, o.pick_form};
     a.nlist = list ? l.nlist : 0u;
     a.list_mask8 = 0;
     for (uint32_t j = 0; j < a.nlist; ++j) {

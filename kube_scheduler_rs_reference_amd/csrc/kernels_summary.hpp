@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eval_request.hpp"
 #include "kernarg.hpp"
 #include "kernels_fused.hpp"  // kFusedThreads, u32x4
 #include "tile_index.hpp"
@@ -424,9 +425,11 @@ inline bool summary_indexed_applicable(const IndexedSnapshot &s) { return s.buil
 inline size_t summary_partial_words(const IndexedSnapshot &s, uint32_t p) { return (size_t)s.lay.tiles * p; }
 
 // out: [p][KSCHED_SUMMARY_WORDS]; partial: [tiles][p], or unused with atomic = true (`out` must then sit on an 8-byte boundary)
-inline hipError_t run_summary_indexed(const IndexedSnapshot &s, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
-                                      const uint64_t *ptol, uint32_t flags, uint32_t *out, uint64_t *partial, bool atomic, hipStream_t stream) {
+// (of the request: p, pcpu, pmem, psel, ptol, flags and the stream)
+inline hipError_t run_summary_indexed(const IndexedSnapshot &s, const EvalRequest &r, uint32_t *out, uint64_t *partial, bool atomic) {
     const IndexedLayout &l = s.lay;
+    const uint32_t p = r.p;
+    const hipStream_t stream = r.stream;
     SummaryArgs a{};
     a.n = l.n;
     a.p = p;
@@ -445,11 +448,11 @@ inline hipError_t run_summary_indexed(const IndexedSnapshot &s, uint32_t p, cons
     }
     a.lab_meta = s.d_lab_meta;
     a.zero64 = reinterpret_cast<const uint64_t *>(s.d_lab_meta + 64);
-    a.has_tol = ptol != nullptr ? 1u : 0u;
+    a.has_tol = r.ptol != nullptr ? 1u : 0u;
     a.atomic = atomic ? 1u : 0u;
-    const bool do_fit = flags & KSCHED_FIT;
-    const bool do_sel = (flags & KSCHED_SEL) && psel && l.nkeys;
-    const bool do_taint = (flags & KSCHED_TAINT) && l.ngroups;
+    const bool do_fit = r.fit();
+    const bool do_sel = r.sel(l.nkeys);
+    const bool do_taint = r.taint(l.ngroups != 0);
     const bool list = do_sel && l.nlist > 0;
     const uint32_t lds = summary_lds_bytes(l, &a);
     if (lds > kLdsBudget) return hipErrorInvalidValue;
@@ -462,7 +465,7 @@ inline hipError_t run_summary_indexed(const IndexedSnapshot &s, uint32_t p, cons
     a.rounds = (p + 63u) / 64u;
     const uint32_t blocks_per_cu = std::max(1u, std::min(kLdsBudget / lds, 2048u / kSummaryThreads));
     a.chunks = std::max(1u, std::min((256u * blocks_per_cu) / l.tiles, (a.rounds + kSummaryWaves - 1u) / kSummaryWaves));
-    const SummaryLaunch q{&s, pcpu, pmem, psel, ptol, partial, out, dim3(a.chunks * l.tiles), lds, stream};
+    const SummaryLaunch q{&s, r.pcpu, r.pmem, r.psel, r.ptol, partial, out, dim3(a.chunks * l.tiles), lds, stream};
     hipError_t e;
     if (atomic) {
         if (reinterpret_cast<uintptr_t>(out) & 7u) return hipErrorInvalidValue;

@@ -20,6 +20,8 @@
 
 
 #include "comm_rccl.hpp"
+#include "eval_plan.hpp"
+#include "eval_request.hpp"
 #include "kernels_build.hpp"
 #include "kernels_direct.hpp"
 #include "kernels_fused.hpp"
@@ -686,7 +688,9 @@ int index_build(ksched_ctx *c, const IndexPlan &p, bool host, const int64_t *cpu
     return KSCHED_OK;
 }
 
-// ---- mask kernel dispatch ---------------------------------------------------------------------
+// ---- evaluation dispatch: request -> plan -> launchers ---------------------------------------------------------------
+// An EvalRequest (eval_request.hpp) is the batch as an entry point hands it on; plan_eval (eval_plan.hpp) says which kernels it
+// runs; the launchers below enqueue them.  eval_on_device strings the three together.
 
 struct DirectPtrs {
     const int64_t *ncpu, *nmem;
@@ -708,33 +712,34 @@ void launch_direct_t(const DirectPtrs &q, const DirectArgs &a, dim3 grid, bool w
                            q.ntaint, q.pcpu, q.pmem, q.psel, q.ptol, q.out_feas, q.out_fit, a);
 }
 
-int run_direct(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
-               const uint64_t *ptol, uint32_t flags, uint64_t *out_feas, uint64_t *out_fit, uint32_t pitch, hipStream_t s) {
+// out_feas: where the feasible mask goes (the request's, or the ctx's scratch one)
+int run_direct(ksched_ctx *c, const EvalRequest &r, uint64_t *out_feas) {
+    const hipStream_t s = r.stream;
     DirectPtrs q{};
     q.ncpu = c->ncpu.ptr;
     q.nmem = c->nmem.ptr;
     q.nlab = c->nlab.ptr;
     q.ntaint = c->have_taints ? c->ntaint.ptr : nullptr;
-    q.pcpu = pcpu;
-    q.pmem = pmem;
-    q.psel = psel;
-    q.ptol = ptol;
+    q.pcpu = r.pcpu;
+    q.pmem = r.pmem;
+    q.psel = r.psel;
+    q.ptol = r.ptol;
     q.out_feas = out_feas;
-    q.out_fit = out_fit;
+    q.out_fit = r.out_fit;
     DirectArgs a{};
     a.n = c->n;
-    a.p = p;
+    a.p = r.p;
     a.W = c->W;
-    a.pitch = pitch;
-    a.do_fit = (flags & KSCHED_FIT) ? 1u : 0u;
+    a.pitch = r.pitch;
+    a.do_fit = r.fit() ? 1u : 0u;
 
-    const bool sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-    const bool taint = (flags & KSCHED_TAINT) != 0;
-    const bool want_fit = (flags & KSCHED_WANT_FIT_MASK) && out_fit;
+    const bool sel = r.sel(c->nkeys);
+    const bool taint = r.taint_flag();  // (the flag alone: without taints in the snapshot the kernel gets a null taint column)
+    const bool want_fit = r.want_fit();
 
     const uint32_t words_per_block = kDirectCW * kDirectWaves;
     const uint32_t gx = (c->W + words_per_block - 1) / words_per_block;
-    const uint32_t pod_tiles = (p + 63) / 64;
+    const uint32_t pod_tiles = (r.p + 63) / 64;
     // aim for >= ~2048 blocks so all 256 CUs (8 XCDs) stay busy, but keep a block on its node
     // columns for as many pods as possible (node registers are loaded once per block)
     uint32_t gy = std::max(1u, std::min(pod_tiles, (2048u + gx - 1) / gx));
@@ -761,30 +766,68 @@ int run_direct(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pm
             b.nkeys = std::min(c->nkeys - k0, (uint32_t)kDirectKeys);
             b.accumulate = 1;
             b.do_fit = 0;
-            DirectPtrs r = q;
-            r.out_fit = nullptr;
-            r.ptol = nullptr;
-            launch_direct_t<true, false>(r, b, grid, false, s);
+            DirectPtrs r2 = q;
+            r2.out_fit = nullptr;
+            r2.ptol = nullptr;
+            launch_direct_t<true, false>(r2, b, grid, false, s);
         }
     }
     HIPCHK(c, hipGetLastError());
-    c->last_kernel = "direct";
     return KSCHED_OK;
 }
 
 // the pick of select_node_for_pod (src/main.rs:51-71) / the best-fit extension, from a feasibility mask on the device
-int launch_pick(ksched_ctx *c, uint32_t p, const uint64_t *feas, uint32_t pitch, const int64_t *pmem, const uint32_t *samples,
-                uint32_t attempts, uint32_t flags, int32_t *out_binding, hipStream_t s) {
-    if ((flags & KSCHED_PICK_BESTFIT) && c->n > 0)
+// (`feas`, rows r.pitch words apart; of the request: p, pmem, samples, attempts, flags, out_binding, stream)
+int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
+    const hipStream_t s = r.stream;
+    if ((r.flags & KSCHED_PICK_BESTFIT) && c->n > 0)
         if (int rcb = ensure_bestfit(c)) return rcb;
     if (int rce = stream_enter(c, s)) return rce;
-    if (flags & KSCHED_PICK_SAMPLED) {
-        hipLaunchKernelGGL(k_pick_sampled, dim3((p + 255) / 256), dim3(256), 0, s, feas, samples, out_binding, p, c->n,
-                           pitch, attempts);
-    } else if (flags & KSCHED_PICK_BESTFIT) {
-        hipLaunchKernelGGL(k_pick_bestfit, dim3((p + 3) / 4), dim3(256), 0, s, feas, c->bf_order.ptr, c->bf_rank.ptr,
-                           c->bf_mem.ptr, pmem, out_binding, p, c->n, c->W, pitch, (flags & KSCHED_FIT) ? 1u : 0u);
+    if (r.flags & KSCHED_PICK_SAMPLED) {
+        hipLaunchKernelGGL(k_pick_sampled, dim3((r.p + 255) / 256), dim3(256), 0, s, feas, r.samples, r.out_binding, r.p, c->n,
+                           r.pitch, r.attempts);
+    } else if (r.flags & KSCHED_PICK_BESTFIT) {
+        hipLaunchKernelGGL(k_pick_bestfit, dim3((r.p + 3) / 4), dim3(256), 0, s, feas, c->bf_order.ptr, c->bf_rank.ptr,
+                           c->bf_mem.ptr, r.pmem, r.out_binding, r.p, c->n, c->W, r.pitch, r.fit() ? 1u : 0u);
     }
+    HIPCHK(c, hipGetLastError());
+    return KSCHED_OK;
+}
+
+SelectArgs make_select_args(const ksched_ctx *c, const EvalRequest &r) {
+    const bool sel = r.sel(c->nkeys);
+    SelectArgs q{};
+    q.nrec = c->nrec.ptr;
+    q.nlab = c->nlab.ptr;
+    q.pcpu = r.pcpu;
+    q.pmem = r.pmem;
+    q.psel = sel ? r.psel : nullptr;
+    q.ptol = r.ptol;
+    q.samples = r.samples;
+    q.binding = r.out_binding;
+    q.p = r.p;
+    q.n = c->n;
+    q.nkeys = sel ? c->nkeys : 0u;
+    q.attempts = r.attempts;
+    q.do_fit = r.fit() ? 1u : 0u;
+    q.do_taint = r.taint(c->have_taints) ? 1u : 0u;
+    return q;
+}
+
+// select_node_for_pod the reference's way: only the sampled candidates are tested, from the columns (k_select_sampled)
+int launch_select(ksched_ctx *c, const EvalRequest &r) {
+    const hipStream_t s = r.stream;
+    const SelectArgs q = make_select_args(c, r);
+    const dim3 grid((r.p + 255) / 256), block(256);  // (64- and 128-thread blocks measured slower: 6.6 / 6.5 us against 5.7 at C3)
+    if (r.attempts <= 5) {
+        switch ((c->opt_debug >> 8) & 3u) {  // KSCHED_OPT_DEBUG bits 8-9: A/B of the number of eagerly fetched draws (tools/)
+            case 1: hipLaunchKernelGGL((k_select_sampled<5, 3>), grid, block, 0, s, q); break;
+            case 2: hipLaunchKernelGGL((k_select_sampled<5, 5>), grid, block, 0, s, q); break;
+            case 3: hipLaunchKernelGGL((k_select_sampled<5, 2>), grid, block, 0, s, q); break;
+            default: hipLaunchKernelGGL((k_select_sampled<5, 1>), grid, block, 0, s, q);  // rocprofv3 at C3, in the step: 1 eager draw 5.79 us, 2: 6.08, 3: 6.78, 5: 7.25
+        }
+    }
+    else hipLaunchKernelGGL((k_select_sampled<8, 2>), grid, block, 0, s, q);
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
@@ -844,325 +887,343 @@ void bestfit_trace_report(ksched_ctx *c, uint32_t p, size_t slots2, hipStream_t 
     line("exit after the first entry", x2);
 }
 
-SelectArgs make_select_args(const ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
-                            const uint64_t *ptol, const uint32_t *samples, uint32_t attempts, uint32_t flags, int32_t *out_binding) {
-    const bool sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-    const bool taint = (flags & KSCHED_TAINT) && c->have_taints;
-    SelectArgs q{};
-    q.nrec = c->nrec.ptr;
-    q.nlab = c->nlab.ptr;
-    q.pcpu = pcpu;
-    q.pmem = pmem;
-    q.psel = sel ? psel : nullptr;
-    q.ptol = ptol;
-    q.samples = samples;
-    q.binding = out_binding;
+// The best-fit pick from bitmaps kept in best-fit order (k_pick_bestfit_rows), no mask involved: one stage, two, or two plus the
+// listed kernel, as the plan says
+int launch_bestfit_rows(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
+    const hipStream_t s = r.stream;
+    const uint32_t p = r.p;
+    const IndexedLayout &l = c->idx.lay;
+    BestfitRowsArgs q{};
+    const bool sel = r.sel(c->nkeys);
+    q.rows = c->bf_rows.ptr;
+    q.lab_meta = c->idx.d_lab_meta;
+    q.cpu_sorted = c->cpu_sorted.ptr;
+    q.bf_mem = c->bf_mem.ptr;
+    q.bf_cpu = c->bf_cpu.ptr;
+    q.bf_order = c->bf_order.ptr;
+    if (c->n <= 64u * 64u * 64u) {  // three rounds of 64 cover the array
+        q.mem_s1 = c->bf_samples.ptr;
+        q.mem_s2 = q.mem_s1 + c->bf_n1;
+        q.cpu_s1 = q.mem_s2 + c->bf_n2;
+        q.cpu_s2 = q.cpu_s1 + c->bf_n1;
+    }
+    q.pcpu = r.pcpu;
+    q.pmem = r.pmem;
+    q.psel = sel ? r.psel : nullptr;
+    q.ptol = r.ptol;
+    q.binding = r.out_binding;
     q.p = p;
     q.n = c->n;
+    q.Wbf = c->bf_W;
     q.nkeys = sel ? c->nkeys : 0u;
-    q.attempts = attempts;
-    q.do_fit = (flags & KSCHED_FIT) ? 1u : 0u;
-    q.do_taint = taint ? 1u : 0u;
-    return q;
-}
-
-// select_node_for_pod the reference's way: only the sampled candidates are tested, from the columns (k_select_sampled)
-int launch_select(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, const uint64_t *ptol,
-                  const uint32_t *samples, uint32_t attempts, uint32_t flags, int32_t *out_binding, hipStream_t s) {
-    const SelectArgs q = make_select_args(c, p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_binding);
-    const dim3 grid((p + 255) / 256), block(256);  // (64- and 128-thread blocks measured slower: 6.6 / 6.5 us against 5.7 at C3)
-    if (attempts <= 5) {
-        switch ((c->opt_debug >> 8) & 3u) {  // KSCHED_OPT_DEBUG bits 8-9: A/B of the number of eagerly fetched draws (tools/)
-            case 1: hipLaunchKernelGGL((k_select_sampled<5, 3>), grid, block, 0, s, q); break;
-            case 2: hipLaunchKernelGGL((k_select_sampled<5, 5>), grid, block, 0, s, q); break;
-            case 3: hipLaunchKernelGGL((k_select_sampled<5, 2>), grid, block, 0, s, q); break;
-            default: hipLaunchKernelGGL((k_select_sampled<5, 1>), grid, block, 0, s, q);  // rocprofv3 at C3, in the step: 1 eager draw 5.79 us, 2: 6.08, 3: 6.78, 5: 7.25
-        }
+    q.ngroups = l.ngroups;
+    q.row_valid = l.row_valid;
+    q.row_zero = l.row_zero;
+    q.row_taint = l.row_taint;
+    q.row_cpu0 = c->bf_row_cpu0;
+    q.q = c->bf_q;
+    q.do_fit = r.fit() ? 1u : 0u;
+    q.do_taint = r.taint(c->have_taints) ? 1u : 0u;
+    for (int k = 0; k < 8; ++k) {
+        q.lab_base8[k] = l.lab_base[k];
+        q.lab_max8[k] = l.lab_max[k];
     }
-    else hipLaunchKernelGGL((k_select_sampled<8, 2>), grid, block, 0, s, q);
+    if (plan.bestfit == BestfitPick::kRowsOneStage) {
+        // one wave per pod, one wave per block (scans differ tenfold in length: with four waves per block the long ones hold up the
+        // placement of whole blocks; 158 against 172 us for 125 k pods at the C5 shard)
+        hipLaunchKernelGGL(k_pick_bestfit_rows, dim3(p), dim3(64), 0, s, q);
+        HIPCHK(c, hipGetLastError());
+        return KSCHED_OK;
+    }
+    // two stages: one lane per pod decides from the first two candidate words; the rare rest goes to the wave-per-pod kernel
+    const bool lists = plan.bestfit == BestfitPick::kRowsTwoStagesListed;  // pods that constrain a list key are split off by the first stage
+    if (int rsc = scratch_enter(c, s)) return rsc;
+    // [3 sets of kBfSublists counters, one per 128-byte line, in rotation][listed mask: ceil(p / 64) words][64-byte hand-over records:
+    // kBfSublists lists of sub_cap slots]; each call zeroes the NEXT call's counters (no memset launch)
+    const size_t waves1 = ((size_t)p + 63) / 64, sub_cap = ((waves1 + kBfSublists - 1) / kBfSublists) * 64;
+    const size_t ctr_u32 = 3 * (size_t)kBfSublists * 32, mask_u32 = ((waves1 * 2 + 15) / 16) * 16;  // (records stay 64-byte aligned)
+    HIPCHK(c, c->bf_fallback.reserve(ctr_u32 + mask_u32 + 16 * (size_t)kBfSublists * sub_cap));
+    if (c->bf_fallback_zeroed_cap != c->bf_fallback.cap) {  // a fresh allocation: all counters once
+        HIPCHK(c, hipMemsetAsync(c->bf_fallback.ptr, 0, ctr_u32 * 4, s));
+        c->bf_fallback_zeroed_cap = c->bf_fallback.cap;
+        c->bf_slot = 0;
+    }
+    q.handover_count = c->bf_fallback.ptr + (size_t)c->bf_slot * kBfSublists * 32;
+    q.zero_next = c->bf_fallback.ptr + (size_t)((c->bf_slot + 1u) % 3u) * kBfSublists * 32;
+    q.sub_cap = (uint32_t)sub_cap;
+    q.lvl = c->bf_levels.ptr;
+    q.nlev = c->bf_nlev;
+    q.lvl_half = c->bf_lvl_half;
+    for (uint32_t k = 0; k < 6; ++k) q.lvl_off[k] = c->bf_lvl_off[k];
+    q.handover_recs = c->bf_fallback.ptr + ctr_u32 + mask_u32;
+    q.nlist = lists ? l.nlist : 0u;
+    for (uint32_t j = 0; j < q.nlist; ++j) q.list_col[j] = l.list_col[j];
+    q.listed_mask = lists ? reinterpret_cast<uint64_t *>(c->bf_fallback.ptr + ctr_u32) : nullptr;
+    q.lane_blocks = ((c->opt_debug >> 12) & 15u) ? ((c->opt_debug >> 12) & 15u) : 2u;  // KSCHED_OPT_DEBUG bits 12-15: A/B of the hand-over point (in 64-byte blocks of 8 words)
+    const bool tracing = (c->opt_debug & 0x100000u) != 0u;
+    if (tracing) {
+        HIPCHK(c, c->bf_trace.reserve(waves1 * 8 + (size_t)kBfSublists * sub_cap * 4));
+        HIPCHK(c, hipMemsetAsync(c->bf_trace.ptr, 0, (waves1 * 8 + (size_t)kBfSublists * sub_cap * 4) * 8, s));
+        q.trace = c->bf_trace.ptr;
+        q.trace2 = c->bf_trace.ptr + waves1 * 8;
+    }
+    hipLaunchKernelGGL(k_pick_bestfit_lanes, dim3((p + 255) / 256), dim3(256), 0, s, q);
+    HIPCHK(c, hipGetLastError());
+    c->bf_slot = (c->bf_slot + 1u) % 3u;  // (only once the kernel that zeroes the next set is on its way)
+    BestfitRowsArgs q2 = q;
+    q2.sub_count = q.handover_count;
+    q2.pod_recs = q.handover_recs;
+    // one wave per block; the grid covers 1 / 2^k of the lists' capacity (KSCHED_OPT_DEBUG bits 21-22: k = 2 by default, A/B 0 / 1 / 3)
+    const uint32_t gshift = ((c->opt_debug >> 21) & 3u) == 0u ? 2u : ((c->opt_debug >> 21) & 3u) == 1u ? 0u : ((c->opt_debug >> 21) & 3u) == 2u ? 1u : 3u;
+    const uint32_t per_list = std::max<uint32_t>(1u, (uint32_t)sub_cap >> gshift);
+    hipLaunchKernelGGL(k_pick_bestfit_handed, dim3(kBfSublists * per_list), dim3(64), 0, s, q2);
+    if (tracing) bestfit_trace_report(c, p, (size_t)kBfSublists * sub_cap, s);
+    if (lists) {
+        BestfitListedArgs la{};
+        la.lists = c->idx.d_list;
+        la.nrec = c->nrec.ptr;
+        la.nlab = c->nlab.ptr;
+        la.bf_rank = c->bf_rank.ptr;
+        la.bf_order = c->bf_order.ptr;
+        la.pcpu = r.pcpu;
+        la.pmem = r.pmem;
+        la.psel = r.psel;
+        la.ptol = r.ptol;
+        la.listed_mask = q.listed_mask;
+        la.binding = r.out_binding;
+        la.p = p;
+        la.n = c->n;
+        la.nkeys = c->nkeys;
+        la.tiles = l.tiles;
+        la.nlist = l.nlist;
+        for (uint32_t j = 0; j < l.nlist; ++j) la.list_col[j] = l.list_col[j];
+        la.do_fit = q.do_fit;
+        la.do_taint = q.do_taint;
+        hipLaunchKernelGGL(k_pick_bestfit_listed, dim3((p + 3) / 4), dim3(256), 0, s, la);
+    }
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
 
-int eval_on_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
-                   const uint64_t *ptol, const uint32_t *samples, uint32_t attempts, uint32_t flags,
-                   uint64_t *out_feas, uint64_t *out_fit, int32_t *out_binding, uint32_t pitch, hipStream_t s) {
-    const bool pick_s = flags & KSCHED_PICK_SAMPLED, pick_b = flags & KSCHED_PICK_BESTFIT;
-    if (p == 0) return KSCHED_OK;
-    if (pick_b && c->n > 0)
-        if (int rcb = ensure_bestfit(c)) return rcb;  // lazily (re)built after a snapshot change, on the ctx's stream
-    if (int rce = stream_enter(c, s)) return rce;      // `s` waits for the latest snapshot change; remembered for the next one
-    if (c->n == 0) {
-        // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
-        // yields None on every attempt, src/main.rs:56,70)
-        if ((pick_s || pick_b) && out_binding) HIPCHK(c, hipMemsetAsync(out_binding, 0xFF, (size_t)p * sizeof(int32_t), s));
-        return KSCHED_OK;
+// the accumulators of the tile-test pick for launches on `s` (ksched_ctx::pick_acc): one buffer per stream, all zero between launches
+int pick_acc_for(ksched_ctx *c, uint32_t p, hipStream_t s, uint64_t **out) {
+    ksched_ctx::PickAcc *pa = nullptr;
+    for (auto &x : c->pick_acc)
+        if (x.s == s) pa = &x;
+    if (!pa) {
+        c->pick_acc.emplace_back();
+        pa = &c->pick_acc.back();
+        pa->s = s;
     }
-    fault_point(c);
-    // kernel choice: fused (one launch over the bitmap index) when the snapshot has an index that fits LDS, else the
-    // always-applicable direct kernel; KSCHED_OPT_KERNEL can force one.
-    const bool want_mask = out_feas || out_fit;
-    const bool can_fused = fused_applicable(c->idx, flags);
-    int kern = c->opt_kernel;
-    if (kern == KSCHED_KERNEL_AUTO) kern = can_fused ? KSCHED_KERNEL_FUSED : KSCHED_KERNEL_DIRECT;
-    // The sampled pick tests only the drawn candidates, from the node records: it does not need the mask.  When a mask is
-    // asked for too and the fused kernel runs, the pick RIDES in that launch (KSCHED_OPT_FUSED_PICK, kernels_fused.hpp "PICK":
-    // a step is one kernel); otherwise it is its own launch, first (nothing waits on a mask kernel), and a bindings-only
-    // request launches no mask kernel at all.  KSCHED_OPT_PICK_FROM_MASK restores the mask-reading pick (a cross-check).
-    const bool select_direct = pick_s && !c->opt_pick_from_mask;
-    // Does a riding pick pay?  Two forms (kernels_fused.hpp PICK): TILE TESTS -- every tile-block of a pod range tests the draws that fall into
-    // its tile from the rows it holds -- and WAVES OF THE FILL, which run select_one_pod while the tile is staged.
-    //  * Waves of the fill only hide in the fill: they ride when a wave has at most five rounds (C3: 2, the C4 shard: 5; beyond that they cost
-    //    twice the stand-alone kernel, round 3's measurement, re-measured in round 6: 400 k x 5 k 67.1 us riding against 66.1).
-    //  * Tile tests re-read a pod's operands and draws once per tile; the tile-blocks of a pod range sit on one XCD, so tiles - 1 of those reads
-    //    come from that XCD's L2 -- as long as the XCD's share of the batch's operands and draws (68 B per pod / 8 XCDs) stays in its 4 MiB.
-    //    Round 6 (session r7a, interleaved round order, step us riding / own launch): 100 k x 5 k  17.6 / 22.6;  400 k x 5 k  53.4 / 65.9;
-    //    250 k x 10 k  64.8 / 75.0;  500 k x 10 k  123.3 / 142.8;  but 800 k x 5 k  143.4 / 125.3, 1 M x 10 k  322.0 / 288.6, 1.6 M x 5 k  281.8 / 241.6.
-    //    (Rounds 3 - 5 had the tile tests stop riding at five rounds per wave too: with every wave on its own contiguous pod range the blocks of
-    //    a pod range drifted apart much earlier.)  They ride up to 524 288 pods per call.
-    const bool tile_form = c->opt_fused_pick == 3 || (c->opt_fused_pick == 1 && can_fused && c->idx.lay.tiles >= 2u && c->idx.lay.tiles <= 12u &&
-                                                      fused_tile_pick_applicable(c->idx, flags, attempts, psel != nullptr));
-    bool ride_pays = true;
-    if (c->opt_fused_pick == 1 && can_fused) {
-        if (tile_form) {
-            ride_pays = p <= (1u << 19);
-        } else {
-            const uint32_t tiles = std::max(1u, c->idx.lay.tiles), cus = c->opt_grid_cus ? c->opt_grid_cus : 256u;
-            const uint32_t chunks = std::max(1u, std::min(cus / tiles, (p + 255u) / 256u));
-            ride_pays = (uint64_t)p <= (uint64_t)chunks * 5u * 64u * kFusedWaves;
-        }
+    const size_t units = ((size_t)p + 7) / 8 + 8;  // one word per unit of eight pods (+ slack: the lanes past a batch's last unit compute an address, never use it)
+    if (pa->buf.cap < units) {  // (re)allocated: zero once; from then on the kernel leaves every word it used at zero
+        HIPCHK(c, pa->buf.reserve(units));
+        HIPCHK(c, hipMemsetAsync(pa->buf.ptr, 0, units * 8, s));
     }
-    const bool pick_rides = select_direct && want_mask && c->opt_fused_pick && kern == KSCHED_KERNEL_FUSED && can_fused && ride_pays &&
-                            fused_pick_applicable(c->idx, flags, (flags & KSCHED_WANT_FIT_MASK) && out_fit, p);
-    SelectArgs ride{};
-    int ride_form = 1;
-    uint64_t *ride_acc = nullptr;
-    if (pick_rides) {
-        ride = make_select_args(c, p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_binding);
-        // the form: tile tests in phase 1 (no node records fetched, no wave taken off the staging) where the request allows it, else
-        // waves of the fill running select_one_pod
-        const bool tile_ok = fused_tile_pick_applicable(c->idx, flags, attempts, psel != nullptr);
-        // Which form when both apply: the tile tests cost every (pod, tile) pair five draw loads and a handful of LDS reads, the waves
-        // of the fill cost every block a longer fill.  Measured (session r3g3, rotated outputs, step): 5 tiles (C3) 19.8 us against 21.6;
-        // 10 tiles (the C4 shard) 45.3 us against 42.1; 1 tile (C2) 7.1 us against 6.8.  With one device-scope atomic per unit of eight pods and
-        // the draws loaded coalesced (later in round 3) the C4 shard reads 40.9 - 41.5 us against 42.1 - 42.3, C2 6.8 against 6.4: 2 .. 12 tiles.
-        const bool tile_pays = c->idx.lay.tiles >= 2u && c->idx.lay.tiles <= 12u;
-        if (((c->opt_fused_pick == 1 && tile_pays) || c->opt_fused_pick == 3) && tile_ok) {
-            ksched_ctx::PickAcc *pa = nullptr;
-            for (auto &x : c->pick_acc)
-                if (x.s == s) pa = &x;
-            if (!pa) {
-                c->pick_acc.emplace_back();
-                pa = &c->pick_acc.back();
-                pa->s = s;
-            }
-            const size_t units = ((size_t)p + 7) / 8 + 8;  // one word per unit of eight pods (+ slack: the lanes past a batch's last unit compute an address, never use it)
-            if (pa->buf.cap < units) {  // (re)allocated: zero once; from then on the kernel leaves every word it used at zero
-                HIPCHK(c, pa->buf.reserve(units));
-                HIPCHK(c, hipMemsetAsync(pa->buf.ptr, 0, units * 8, s));
-            }
-            ride_form = 2;
-            ride_acc = pa->buf.ptr;
-        } else if (c->opt_fused_pick == 3) {
-            c->last_error = "the tile-test pick is not applicable to this request (attempts != 5, taints, more than eight label keys, or no room in LDS)";
-            return KSCHED_E_UNSUPPORTED;
-        }
-    }
-    c->last_pick = "none";
-    if (select_direct && !pick_rides) {
-        int rcs = launch_select(c, p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_binding, s);
-        if (rcs) return rcs;
-        c->last_pick = "select";
-        if (!want_mask) return KSCHED_OK;
-    }
-    // The best-fit pick likewise: from bitmaps kept in best-fit order (k_pick_bestfit_rows), no mask involved.
-    const bool bestfit_rows = pick_b && !c->opt_pick_from_mask && c->bf_rows_built;
-    if (bestfit_rows) {
-        const IndexedLayout &l = c->idx.lay;
-        BestfitRowsArgs q{};
-        const bool sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-        q.rows = c->bf_rows.ptr;
-        q.lab_meta = c->idx.d_lab_meta;
-        q.cpu_sorted = c->cpu_sorted.ptr;
-        q.bf_mem = c->bf_mem.ptr;
-        q.bf_cpu = c->bf_cpu.ptr;
-        q.bf_order = c->bf_order.ptr;
-        if (c->n <= 64u * 64u * 64u) {  // three rounds of 64 cover the array
-            q.mem_s1 = c->bf_samples.ptr;
-            q.mem_s2 = q.mem_s1 + c->bf_n1;
-            q.cpu_s1 = q.mem_s2 + c->bf_n2;
-            q.cpu_s2 = q.cpu_s1 + c->bf_n1;
-        }
-        q.pcpu = pcpu;
-        q.pmem = pmem;
-        q.psel = sel ? psel : nullptr;
-        q.ptol = ptol;
-        q.binding = out_binding;
-        q.p = p;
-        q.n = c->n;
-        q.Wbf = c->bf_W;
-        q.nkeys = sel ? c->nkeys : 0u;
-        q.ngroups = l.ngroups;
-        q.row_valid = l.row_valid;
-        q.row_zero = l.row_zero;
-        q.row_taint = l.row_taint;
-        q.row_cpu0 = c->bf_row_cpu0;
-        q.q = c->bf_q;
-        q.do_fit = (flags & KSCHED_FIT) ? 1u : 0u;
-        q.do_taint = ((flags & KSCHED_TAINT) && c->have_taints) ? 1u : 0u;
-        for (int k = 0; k < 8; ++k) {
-            q.lab_base8[k] = l.lab_base[k];
-            q.lab_max8[k] = l.lab_max[k];
-        }
-        // one stage (a wave per pod) or two (a lane per pod first): the second launch and the hand-over list pay off from tens of
-        // thousands of pods on (20k pods: 33 us against 44; 125k pods: 160 against 120) -- KSCHED_OPT_BESTFIT_STAGES overrides
-        const bool lists = sel && l.nlist > 0;  // pods that constrain a list key are split off by the first stage: two stages it is
-        const bool two_stage = lists || c->opt_bestfit_stages == 2 || (c->opt_bestfit_stages == 0 && p >= 24576u);  // (measured crossover at the C5 shard's snapshot: ~24 k pods)
-        if (!lists && (!two_stage || (c->opt_debug & 0x400u) || c->n > (1u << 21))) {
-            // one wave per pod, one wave per block (scans differ tenfold in length: with four waves per block the long ones hold up the
-            // placement of whole blocks; 158 against 172 us for 125 k pods at the C5 shard)
-            hipLaunchKernelGGL(k_pick_bestfit_rows, dim3(p), dim3(64), 0, s, q);
-        } else {
-            // two stages: one lane per pod decides from the first two candidate words; the rare rest goes to the wave-per-pod kernel
-            if (c->n > (1u << 21)) {
-                c->last_error = "best fit over a snapshot with list keys supports at most 2097152 nodes";
-                return KSCHED_E_UNSUPPORTED;
-            }
-            if (int rsc = scratch_enter(c, s)) return rsc;
-            // [3 sets of kBfSublists counters, one per 128-byte line, in rotation][listed mask: ceil(p / 64) words][64-byte hand-over records:
-            // kBfSublists lists of sub_cap slots]; each call zeroes the NEXT call's counters (no memset launch)
-            const size_t waves1 = ((size_t)p + 63) / 64, sub_cap = ((waves1 + kBfSublists - 1) / kBfSublists) * 64;
-            const size_t ctr_u32 = 3 * (size_t)kBfSublists * 32, mask_u32 = ((waves1 * 2 + 15) / 16) * 16;  // (records stay 64-byte aligned)
-            HIPCHK(c, c->bf_fallback.reserve(ctr_u32 + mask_u32 + 16 * (size_t)kBfSublists * sub_cap));
-            if (c->bf_fallback_zeroed_cap != c->bf_fallback.cap) {  // a fresh allocation: all counters once
-                HIPCHK(c, hipMemsetAsync(c->bf_fallback.ptr, 0, ctr_u32 * 4, s));
-                c->bf_fallback_zeroed_cap = c->bf_fallback.cap;
-                c->bf_slot = 0;
-            }
-            q.handover_count = c->bf_fallback.ptr + (size_t)c->bf_slot * kBfSublists * 32;
-            q.zero_next = c->bf_fallback.ptr + (size_t)((c->bf_slot + 1u) % 3u) * kBfSublists * 32;
-            q.sub_cap = (uint32_t)sub_cap;
-            q.lvl = c->bf_levels.ptr;
-            q.nlev = c->bf_nlev;
-            q.lvl_half = c->bf_lvl_half;
-            for (uint32_t k = 0; k < 6; ++k) q.lvl_off[k] = c->bf_lvl_off[k];
-            q.handover_recs = c->bf_fallback.ptr + ctr_u32 + mask_u32;
-            q.nlist = lists ? l.nlist : 0u;
-            for (uint32_t j = 0; j < q.nlist; ++j) q.list_col[j] = l.list_col[j];
-            q.listed_mask = lists ? reinterpret_cast<uint64_t *>(c->bf_fallback.ptr + ctr_u32) : nullptr;
-            q.lane_blocks = ((c->opt_debug >> 12) & 15u) ? ((c->opt_debug >> 12) & 15u) : 2u;  // KSCHED_OPT_DEBUG bits 12-15: A/B of the hand-over point (in 64-byte blocks of 8 words)
-            const bool tracing = (c->opt_debug & 0x100000u) != 0u;
-            if (tracing) {
-                HIPCHK(c, c->bf_trace.reserve(waves1 * 8 + (size_t)kBfSublists * sub_cap * 4));
-                HIPCHK(c, hipMemsetAsync(c->bf_trace.ptr, 0, (waves1 * 8 + (size_t)kBfSublists * sub_cap * 4) * 8, s));
-                q.trace = c->bf_trace.ptr;
-                q.trace2 = c->bf_trace.ptr + waves1 * 8;
-            }
-            hipLaunchKernelGGL(k_pick_bestfit_lanes, dim3((p + 255) / 256), dim3(256), 0, s, q);
-            HIPCHK(c, hipGetLastError());
-            c->bf_slot = (c->bf_slot + 1u) % 3u;  // (only once the kernel that zeroes the next set is on its way)
-            BestfitRowsArgs q2 = q;
-            q2.sub_count = q.handover_count;
-            q2.pod_recs = q.handover_recs;
-            // one wave per block; the grid covers 1 / 2^k of the lists' capacity (KSCHED_OPT_DEBUG bits 21-22: k = 2 by default, A/B 0 / 1 / 3)
-            const uint32_t gshift = ((c->opt_debug >> 21) & 3u) == 0u ? 2u : ((c->opt_debug >> 21) & 3u) == 1u ? 0u : ((c->opt_debug >> 21) & 3u) == 2u ? 1u : 3u;
-            const uint32_t per_list = std::max<uint32_t>(1u, (uint32_t)sub_cap >> gshift);
-            hipLaunchKernelGGL(k_pick_bestfit_handed, dim3(kBfSublists * per_list), dim3(64), 0, s, q2);
-            if (tracing) bestfit_trace_report(c, p, (size_t)kBfSublists * sub_cap, s);
-            if (lists) {
-                BestfitListedArgs la{};
-                la.lists = c->idx.d_list;
-                la.nrec = c->nrec.ptr;
-                la.nlab = c->nlab.ptr;
-                la.bf_rank = c->bf_rank.ptr;
-                la.bf_order = c->bf_order.ptr;
-                la.pcpu = pcpu;
-                la.pmem = pmem;
-                la.psel = psel;
-                la.ptol = ptol;
-                la.listed_mask = q.listed_mask;
-                la.binding = out_binding;
-                la.p = p;
-                la.n = c->n;
-                la.nkeys = c->nkeys;
-                la.tiles = l.tiles;
-                la.nlist = l.nlist;
-                for (uint32_t j = 0; j < l.nlist; ++j) la.list_col[j] = l.list_col[j];
-                la.do_fit = q.do_fit;
-                la.do_taint = q.do_taint;
-                hipLaunchKernelGGL(k_pick_bestfit_listed, dim3((p + 3) / 4), dim3(256), 0, s, la);
-            }
-        }
-        HIPCHK(c, hipGetLastError());
-        c->last_pick = "bestfit-rows";
-        if (!out_feas && !out_fit) return KSCHED_OK;
-    }
-    uint64_t *feas = out_feas;
-    if (!feas) {  // the mask kernels always write the feasible mask: a pick that reads it, or a fit-mask-only request, gets a scratch one
-        if (int rsc = scratch_enter(c, s)) return rsc;
-        HIPCHK(c, c->scratch_mask.reserve((size_t)p * pitch));
-        feas = c->scratch_mask.ptr;
-    }
+    *out = pa->buf.ptr;
+    return KSCHED_OK;
+}
 
-    // (the fused kernel carries its timing events on the dispatch packet itself -- hipExtLaunchKernel --, the multi-launch
-    // paths are bracketed by stream events)
-    int rc;
-    if (kern == KSCHED_KERNEL_FUSED && !can_fused) {
-        c->last_error = "fused kernel not applicable to this snapshot/request: " + (c->index_reason.empty() ? std::string("the bitmap index does not fit LDS") : c->index_reason);
-        return KSCHED_E_UNSUPPORTED;
-    }
-    size_t slot = 0;
+// One launch in every opt_timing carries a pair of events from the pool (ksched_kernel_time_ms).  on_stream: the pair brackets the
+// launches on the stream; otherwise the kernel carries it on its dispatch packet itself (run_fused: hipExtLaunchKernel).
+struct TimingBracket {
+    hipEvent_t a = nullptr, b = nullptr;  // null: this launch is not timed
+    bool on_stream = false;
+};
+
+int timing_begin(ksched_ctx *c, hipStream_t s, bool on_stream, TimingBracket &t) {
     // (at most 65536 unread samples: a caller that switches timing on and never reads it does not grow the event pool for ever)
     const bool timed = c->opt_timing && c->ev_used < 65536u && (c->timing_seq++ % c->opt_timing) == 0;
-    if (timed) {
-        int trc = timing_slot(c, &slot);
-        if (trc) return trc;
-        if (kern != KSCHED_KERNEL_FUSED) HIPCHK(c, hipEventRecord(c->ev_pool[slot].a, s));
+    if (!timed) return KSCHED_OK;
+    size_t slot = 0;
+    if (int trc = timing_slot(c, &slot)) return trc;
+    t.a = c->ev_pool[slot].a;
+    t.b = c->ev_pool[slot].b;
+    t.on_stream = on_stream;
+    if (on_stream) HIPCHK(c, hipEventRecord(t.a, s));
+    return KSCHED_OK;
+}
+
+int timing_end(ksched_ctx *c, hipStream_t s, const TimingBracket &t) {
+    if (t.b && t.on_stream) HIPCHK(c, hipEventRecord(t.b, s));
+    return KSCHED_OK;
+}
+
+// KSCHED_OPT_KERNEL forces the fused kernel where it does not apply (evaluations and summaries alike)
+int fail_fused_not_applicable(ksched_ctx *c) {
+    c->last_error = "fused kernel not applicable to this snapshot/request: " + (c->index_reason.empty() ? std::string("the bitmap index does not fit LDS") : c->index_reason);
+    return KSCHED_E_UNSUPPORTED;
+}
+
+// the mask kernel of the plan -- with the riding pick, if one rides -- and the pick that reads the mask, if one does
+int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
+    const hipStream_t s = r.stream;
+    const bool fused = plan.mask == MaskKernel::kFused;
+    FusedOptions o;
+    SelectArgs ride{};
+    if (plan.pick_rides()) {
+        ride = make_select_args(c, r);
+        o.pick = &ride;
+        if (plan.sampled == SampledPick::kRidesTiles) {
+            o.pick_form = 2;
+            if (int rc = pick_acc_for(c, r.p, s, &o.pick_acc)) return rc;
+        }
     }
-    if (kern == KSCHED_KERNEL_FUSED) {
+    uint64_t *feas = r.out_feas;
+    if (plan.scratch_mask) {
+        if (int rsc = scratch_enter(c, s)) return rsc;
+        HIPCHK(c, c->scratch_mask.reserve((size_t)r.p * r.pitch));
+        feas = c->scratch_mask.ptr;
+    }
+    // (the fused kernel carries its timing events on the dispatch packet itself -- hipExtLaunchKernel --, the multi-launch
+    // paths are bracketed by stream events)
+    TimingBracket t;
+    if (int trc = timing_begin(c, s, !fused, t)) return trc;
+    if (fused) {
         constexpr uint32_t kTraceBlocks = 8192;
         if (c->opt_trace) {
             DeviceGuard g2(c->device);
             if (int rsc = scratch_enter(c, s)) return rsc;
             HIPCHK(c, c->trace.reserve((size_t)kTraceBlocks * KSCHED_TRACE_WORDS));
             HIPCHK(c, hipMemsetAsync(c->trace.ptr, 0, (size_t)kTraceBlocks * KSCHED_TRACE_WORDS * 8, s));
+            o.trace = c->trace.ptr;
+            o.trace_blocks = kTraceBlocks;
         }
-        hipError_t e = run_fused(c->idx, p, pcpu, pmem, psel, ptol, flags, feas, out_fit, pitch, s, c->opt_debug,
-                                 timed ? c->ev_pool[slot].a : nullptr, timed ? c->ev_pool[slot].b : nullptr,
-                                 c->opt_trace ? c->trace.ptr : nullptr, kTraceBlocks, pick_rides ? &ride : nullptr, ride_form, ride_acc,
-                                 c->opt_grid_cus, c->opt_round_order);
+        o.debug = c->opt_debug;
+        o.ev_start = t.a;
+        o.ev_stop = t.b;
+        o.grid_cus = c->opt_grid_cus;
+        o.round_order = c->opt_round_order;
+        hipError_t e = run_fused(c->idx, r, feas, o);
         if (e != hipSuccess) return fail_hip(c, e, "run_fused");
-        c->last_kernel = "fused";
-        if (pick_rides) c->last_pick = ride_form == 2 ? "fused-tile" : "fused";
-        rc = KSCHED_OK;
-    } else {
-        rc = run_direct(c, p, pcpu, pmem, psel, ptol, flags, feas, out_fit, pitch, s);
+    } else if (int rc = run_direct(c, r, feas)) {
+        return rc;
     }
-    if (rc) return rc;
-    if (timed && kern != KSCHED_KERNEL_FUSED) HIPCHK(c, hipEventRecord(c->ev_pool[slot].b, s));
-
-    if (select_direct || bestfit_rows || !(pick_s || pick_b)) return KSCHED_OK;  // (a riding pick is a select_direct one)
-    c->last_pick = "from-mask";
-    return launch_pick(c, p, feas, pitch, pmem, samples, attempts, flags, out_binding, s);
+    c->last_kernel = plan.last_kernel;
+    if (int trc = timing_end(c, s, t)) return trc;
+    if (plan.sampled != SampledPick::kFromMask && plan.bestfit != BestfitPick::kFromMask) return KSCHED_OK;
+    return launch_pick(c, r, feas);
 }
 
-int check_eval_args(const ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *samples,
-                    uint32_t attempts, uint32_t flags, const uint64_t *out_feas, const uint64_t *out_fit,
-                    const int32_t *out_binding) {
+// what plan_eval decides by, read off the ctx and the request
+EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
+    EvalFacts f;
+    f.p = r.p;
+    f.n = c->n;
+    f.attempts = r.attempts;
+    f.flags = r.flags;
+    f.nkeys = c->nkeys;
+    f.have_feas = r.out_feas != nullptr;
+    f.have_fit = r.out_fit != nullptr;
+    f.have_psel = r.psel != nullptr;
+    f.tiles = c->idx.lay.tiles;
+    f.nlist = c->idx.lay.nlist;
+    f.fused_applicable = fused_applicable(c->idx, r.flags);
+    f.fused_pick_applicable = fused_pick_applicable(c->idx, r.flags, r.want_fit(), r.p);
+    f.fused_tile_pick_applicable = fused_tile_pick_applicable(c->idx, r.flags, r.attempts, r.psel != nullptr);
+    f.bf_rows_built = c->bf_rows_built;
+    f.fused_waves = kFusedWaves;
+    f.opt_kernel = c->opt_kernel;
+    f.opt_fused_pick = c->opt_fused_pick;
+    f.opt_bestfit_stages = c->opt_bestfit_stages;
+    f.opt_pick_from_mask = c->opt_pick_from_mask;
+    f.opt_grid_cus = c->opt_grid_cus;
+    f.debug = c->opt_debug;
+    return f;
+}
+
+int fail_plan(ksched_ctx *c, const EvalPlan &plan) {
+    switch (plan.why) {
+        case PlanError::kTilePickNotApplicable:
+            c->last_error = "the tile-test pick is not applicable to this request (attempts != 5, taints, more than eight label keys, or no room in LDS)";
+            break;
+        case PlanError::kListKeysTooManyNodes:
+            c->last_error = "best fit over a snapshot with list keys supports at most 2097152 nodes";
+            break;
+        default: return fail_fused_not_applicable(c);
+    }
+    return plan.error;
+}
+
+int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
+    const bool pick_s = r.flags & KSCHED_PICK_SAMPLED, pick_b = r.flags & KSCHED_PICK_BESTFIT;
+    if (r.p == 0) return KSCHED_OK;
+    if (pick_b && c->n > 0)
+        if (int rcb = ensure_bestfit(c)) return rcb;  // lazily (re)built after a snapshot change, on the ctx's stream
+    if (int rce = stream_enter(c, r.stream)) return rce;  // the stream waits for the latest snapshot change; remembered for the next one
+    if (c->n == 0) {
+        // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
+        // yields None on every attempt, src/main.rs:56,70)
+        if ((pick_s || pick_b) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
+        return KSCHED_OK;
+    }
+    fault_point(c);
+    const EvalPlan plan = plan_eval(eval_facts(c, r));
+    if (plan.error) return fail_plan(c, plan);  // (nothing has been enqueued)
+    c->last_pick = plan.last_pick;
+    if (plan.sampled == SampledPick::kOwnLaunch)  // first: nothing waits on a mask kernel
+        if (int rc = launch_select(c, r)) return rc;
+    if (plan.bestfit_rows())
+        if (int rc = launch_bestfit_rows(c, r, plan)) return rc;
+    if (plan.mask != MaskKernel::kNone) return launch_mask(c, r, plan);
+    return KSCHED_OK;
+}
+
+// ---- host staging ------------------------------------------------------------------------------------------------
+// The operands of a host batch that a host-pointer entry point uploads into the ctx's pcpu / pmem / psel / ptol / psamples
+// buffers: the caller states which by leaving the others null.
+struct HostBatch {
+    const int64_t *pcpu = nullptr, *pmem = nullptr;
+    const uint32_t *psel = nullptr;  // [n_keys][sel_stride], of which the first p entries of every column are the batch's
+    uint32_t sel_stride = 0;
+    const uint64_t *ptol = nullptr;
+    const uint32_t *samples = nullptr;  // [p][attempts]
+    uint32_t attempts = 0;
+};
+
+int stage_batch(ksched_ctx *c, uint32_t p, const HostBatch &h, hipStream_t s) {
+    if (h.pcpu) {
+        HIPCHK(c, c->pcpu.reserve(p));
+        HIPCHK(c, hipMemcpyAsync(c->pcpu.ptr, h.pcpu, (size_t)p * 8, hipMemcpyHostToDevice, s));
+    }
+    if (h.pmem) {
+        HIPCHK(c, c->pmem.reserve(p));
+        HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, h.pmem, (size_t)p * 8, hipMemcpyHostToDevice, s));
+    }
+    if (h.psel) {
+        HIPCHK(c, c->psel.reserve((size_t)p * c->nkeys));
+        if (h.sel_stride == p)
+            HIPCHK(c, hipMemcpyAsync(c->psel.ptr, h.psel, (size_t)p * c->nkeys * 4, hipMemcpyHostToDevice, s));
+        else  // rows [lo, lo + p) of a [n_keys][sel_stride] array: column k of the shard starts sel_stride entries after column k - 1's
+            HIPCHK(c, hipMemcpy2DAsync(c->psel.ptr, (size_t)p * 4, h.psel, (size_t)h.sel_stride * 4, (size_t)p * 4, c->nkeys, hipMemcpyHostToDevice, s));
+    }
+    if (h.ptol) {
+        HIPCHK(c, c->ptol.reserve(p));
+        HIPCHK(c, hipMemcpyAsync(c->ptol.ptr, h.ptol, (size_t)p * 8, hipMemcpyHostToDevice, s));
+    }
+    if (h.samples) {
+        HIPCHK(c, c->psamples.reserve((size_t)p * h.attempts));
+        HIPCHK(c, hipMemcpyAsync(c->psamples.ptr, h.samples, (size_t)p * h.attempts * 4, hipMemcpyHostToDevice, s));
+    }
+    return KSCHED_OK;
+}
+
+// the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed)
+int check_eval_args(const EvalRequest &r) {
+    const uint32_t flags = r.flags;
     const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT |
                            KSCHED_WANT_FIT_MASK;
     if (flags & ~known) return KSCHED_E_INVAL;
     if ((flags & KSCHED_PICK_SAMPLED) && (flags & KSCHED_PICK_BESTFIT)) return KSCHED_E_INVAL;
-    if (p > 0 && (!pcpu || !pmem)) return KSCHED_E_INVAL;
+    if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
     if (flags & KSCHED_PICK_SAMPLED) {
-        if (!out_binding || attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS) return KSCHED_E_INVAL;
-        if (p > 0 && !samples) return KSCHED_E_INVAL;
+        if (!r.out_binding || r.attempts == 0 || r.attempts > KSCHED_MAX_ATTEMPTS) return KSCHED_E_INVAL;
+        if (r.p > 0 && !r.samples) return KSCHED_E_INVAL;
     }
-    if ((flags & KSCHED_PICK_BESTFIT) && !out_binding) return KSCHED_E_INVAL;
-    if ((flags & KSCHED_WANT_FIT_MASK) && !out_fit) return KSCHED_E_INVAL;
-    if (!(flags & KSCHED_WANT_FIT_MASK) && out_fit) return KSCHED_E_INVAL;
-    if (!(flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) && !out_feas && !out_fit) return KSCHED_E_INVAL;
-    (void)c;
+    if ((flags & KSCHED_PICK_BESTFIT) && !r.out_binding) return KSCHED_E_INVAL;
+    if ((flags & KSCHED_WANT_FIT_MASK) && !r.out_fit) return KSCHED_E_INVAL;
+    if (!(flags & KSCHED_WANT_FIT_MASK) && r.out_fit) return KSCHED_E_INVAL;
+    if (!(flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) && !r.out_feas && !r.out_fit) return KSCHED_E_INVAL;
     return KSCHED_OK;
 }
 
@@ -1628,13 +1689,13 @@ int ksched_eval_device_pitched(ksched_ctx *c, uint32_t p, const int64_t *pcpu, c
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    int rc = check_eval_args(c, p, pcpu, pmem, samples, attempts, flags, out_feas, out_fit, out_binding);
+    const EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit, out_binding, mask_pitch_words, (hipStream_t)hip_stream};
+    int rc = check_eval_args(r);
     if (rc) return rc;
     if (mask_pitch_words < c->W) return KSCHED_E_INVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
-    return eval_on_device(c, p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit, out_binding,
-                          mask_pitch_words, (hipStream_t)hip_stream);
+    return eval_on_device(c, r);
 } KSCHED_ABI_CATCH(c)
 
 int ksched_eval_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
@@ -1735,7 +1796,8 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     if (!c->have_nodes) return KSCHED_E_STATE;
     const uint32_t pick = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT);
     if (!pick || (flags & KSCHED_WANT_FIT_MASK) || !mask) return KSCHED_E_INVAL;
-    int rc = check_eval_args(c, p, pcpu, pmem, samples, attempts, flags, mask, nullptr, binding);
+    EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, mask, nullptr, binding, mask_pitch_words, nullptr};  // (the stream: chosen below)
+    int rc = check_eval_args(r);
     if (rc) return rc;
     if (mask_pitch_words < c->W) return KSCHED_E_INVAL;
     DeviceGuard g(c->device);
@@ -1743,8 +1805,8 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     // Does the pick read the mask?  By default it does not (sampled: the drawn candidates are tested from the columns;
     // best fit: bitmaps kept in best-fit order), so the two streams need no ordering at all: each is in order by itself
     // (mask kernels of successive batches on one, picks on the other), which also covers the reuse of a slot's buffers.
-    const bool pick_reads_mask = c->opt_pick_from_mask || ((pick & KSCHED_PICK_BESTFIT) && !bf_rows_expected(c));
-    if (c->opt_pipe_mode >= 1 && !pick_reads_mask) {
+    const bool reads_mask = pick_reads_mask(flags, c->opt_pick_from_mask, bf_rows_expected(c));
+    if (c->opt_pipe_mode >= 1 && !reads_mask) {
         // alternate: the whole evaluation of the slot on ONE of the pipe's streams (one launch when the pick rides in the mask
         // kernel), stream = slot mod k.  A slot comes back to the same stream as long as the mode stays what it is, so the reuse of
         // its buffers is ordered by the stream itself; when the slot's previous use ran elsewhere -- another k, or the split mode,
@@ -1761,8 +1823,8 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
         q->last_split[slot] = 0;
         q->slot_stream[slot] = st;
         q->pick_stream[slot] = st;
-        rc = eval_on_device(c, p, pcpu, pmem, psel, ptol, samples, attempts, flags, mask, nullptr, binding, mask_pitch_words, st);
-        if (rc) return rc;
+        r.stream = st;
+        if ((rc = eval_on_device(c, r))) return rc;
         HIPCHK(c, hipEventRecord(q->pick_done[slot], st));
         return KSCHED_OK;
     }
@@ -1773,21 +1835,21 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     }
     q->slot_stream[slot] = sm;
     q->pick_stream[slot] = q->s_pick;
-    if (pick_reads_mask) HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));  // the slot's mask may be overwritten once its pick has run
+    if (reads_mask) HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));  // the slot's mask may be overwritten once its pick has run
     q->last_split[slot] = 1;
-    rc = eval_on_device(c, p, pcpu, pmem, psel, ptol, nullptr, 0, flags & ~pick, mask, nullptr, nullptr, mask_pitch_words, sm);
-    if (rc) return rc;
+    if ((rc = eval_on_device(c, EvalRequest{p, pcpu, pmem, psel, ptol, nullptr, 0, flags & ~pick, mask, nullptr, nullptr, mask_pitch_words, sm}))) return rc;
     HIPCHK(c, hipEventRecord(q->mask_done[slot], sm));  // (always: a later submit of this slot in the alternate mode orders itself behind this mask kernel)
-    if (pick_reads_mask) {
+    r.stream = q->s_pick;
+    if (reads_mask) {
         HIPCHK(c, hipStreamWaitEvent(q->s_pick, q->mask_done[slot], 0));
         if (p > 0) {
             if (c->n == 0) HIPCHK(c, hipMemsetAsync(binding, 0xFF, (size_t)p * sizeof(int32_t), q->s_pick));
-            else if ((rc = launch_pick(c, p, mask, mask_pitch_words, pmem, samples, attempts, flags, binding, q->s_pick))) return rc;
+            else if ((rc = launch_pick(c, r, mask))) return rc;
         }
     } else {
         // bindings-only evaluation on the pick stream: launches the pick kernel alone
-        rc = eval_on_device(c, p, pcpu, pmem, psel, ptol, samples, attempts, flags, nullptr, nullptr, binding, mask_pitch_words, q->s_pick);
-        if (rc) return rc;
+        r.out_feas = nullptr;
+        if ((rc = eval_on_device(c, r))) return rc;
     }
     HIPCHK(c, hipEventRecord(q->pick_done[slot], q->s_pick));
     return KSCHED_OK;
@@ -1835,7 +1897,7 @@ int ksched_pick_device(ksched_ctx *c, uint32_t p, const uint64_t *feasible, uint
         HIPCHK(c, hipMemsetAsync(out_binding, 0xFF, (size_t)p * sizeof(int32_t), s));
         return KSCHED_OK;
     }
-    return launch_pick(c, p, feasible, mask_pitch_words, req_mem_bytes, samples, attempts, flags, out_binding, s);
+    return launch_pick(c, EvalRequest{p, nullptr, req_mem_bytes, nullptr, nullptr, samples, attempts, flags, nullptr, nullptr, out_binding, mask_pitch_words, s}, feasible);
 } KSCHED_ABI_CATCH(c)
 
 // The pick alone from HOST masks (packed rows of W words): copies in, ksched_pick_device on the ctx's stream, copies out, waits.
@@ -1865,17 +1927,13 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
     HIPCHK(c, c->feas.reserve((size_t)p * W));
     HIPCHK(c, c->binding.reserve(p));
     HIPCHK(c, hipMemcpyAsync(c->feas.ptr, feasible, (size_t)p * W * 8, hipMemcpyHostToDevice, s));
-    if (req_mem_bytes) {
-        HIPCHK(c, c->pmem.reserve(p));
-        HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, req_mem_bytes, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    }
-    if (pick_s) {
-        HIPCHK(c, c->psamples.reserve((size_t)p * attempts));
-        HIPCHK(c, hipMemcpyAsync(c->psamples.ptr, samples, (size_t)p * attempts * 4, hipMemcpyHostToDevice, s));
-    }
-    if (int rc = launch_pick(c, p, c->feas.ptr, (uint32_t)W, req_mem_bytes ? c->pmem.ptr : nullptr, pick_s ? c->psamples.ptr : nullptr, attempts, flags,
-                             c->binding.ptr, s))
-        return rc;
+    HostBatch h;
+    h.pmem = req_mem_bytes;
+    if (pick_s) h.samples = samples, h.attempts = attempts;
+    if (int rc = stage_batch(c, p, h, s)) return rc;
+    const EvalRequest r{p, nullptr, req_mem_bytes ? c->pmem.ptr : nullptr, nullptr, nullptr, pick_s ? c->psamples.ptr : nullptr, attempts, flags,
+                        nullptr, nullptr, c->binding.ptr, (uint32_t)W, s};
+    if (int rc = launch_pick(c, r, c->feas.ptr)) return rc;
     HIPCHK(c, hipMemcpyAsync(out_binding, c->binding.ptr, (size_t)p * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return KSCHED_OK;
@@ -1884,17 +1942,22 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
 // ---- the host-pointer evaluation in two halves (include/ksched.h "one host thread, several devices") -------------------------
 // eval_begin_locked: copy the batch in, enqueue the evaluation and the copies of the masks back -- all on the ctx's own stream, no
 // host wait.  The bindings stay in a ctx-owned device buffer of `capacity` >= p entries; entries [p, capacity) are -1 (the padding
-// an all-gather of unequal shards needs).  The caller holds the ctx's mutex and has checked the arguments.
+// an all-gather of unequal shards needs).  The caller holds the ctx's mutex and has checked the arguments.  `h`: the batch as the
+// caller gave it -- HOST pointers, selectors sel_stride entries per key apart, packed output masks.
 namespace {
-int eval_begin_locked(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, uint32_t sel_stride,
-                      const uint64_t *ptol, const uint32_t *samples, uint32_t attempts, uint32_t flags, uint64_t *out_feas,
-                      uint64_t *out_fit, uint32_t capacity, int32_t **binding_dev) {
+int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, uint32_t capacity, int32_t **binding_dev) {
     hipStream_t s = c->stream;
+    const uint32_t p = h.p, flags = h.flags;
+    uint64_t *const out_feas = h.out_feas, *const out_fit = h.out_fit;
     const size_t W = c->W;
     const size_t pitch = ksched_mask_pitch(c->n);
     const bool pick = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT);
-    const bool use_sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-    const bool use_tol = (flags & KSCHED_TAINT) && ptol;
+    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled pick
+    b.pcpu = h.pcpu;
+    b.pmem = h.pmem;
+    if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride;
+    if (h.taint_flag()) b.ptol = h.ptol;
+    if (flags & KSCHED_PICK_SAMPLED) b.samples = h.samples, b.attempts = h.attempts;
     int32_t *d_bind = nullptr;
     if (pick) {
         const size_t cap = std::max<size_t>(capacity, p);
@@ -1905,30 +1968,10 @@ int eval_begin_locked(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int6
     if (binding_dev) *binding_dev = d_bind;
     if (p == 0) return KSCHED_OK;  // (a rank whose shard is empty still takes part in the exchange with `capacity` rows of -1)
 
-    HIPCHK(c, c->pcpu.reserve(p));
-    HIPCHK(c, c->pmem.reserve(p));
-    HIPCHK(c, hipMemcpyAsync(c->pcpu.ptr, pcpu, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, pmem, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    if (use_sel) {
-        HIPCHK(c, c->psel.reserve((size_t)p * c->nkeys));
-        if (sel_stride == p)
-            HIPCHK(c, hipMemcpyAsync(c->psel.ptr, psel, (size_t)p * c->nkeys * 4, hipMemcpyHostToDevice, s));
-        else  // rows [lo, lo + p) of a [n_keys][sel_stride] array: column k of the shard starts sel_stride entries after column k - 1's
-            HIPCHK(c, hipMemcpy2DAsync(c->psel.ptr, (size_t)p * 4, psel, (size_t)sel_stride * 4, (size_t)p * 4, c->nkeys, hipMemcpyHostToDevice, s));
-    }
-    if (use_tol) {
-        HIPCHK(c, c->ptol.reserve(p));
-        HIPCHK(c, hipMemcpyAsync(c->ptol.ptr, ptol, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    }
-    if (flags & KSCHED_PICK_SAMPLED) {
-        HIPCHK(c, c->psamples.reserve((size_t)p * attempts));
-        HIPCHK(c, hipMemcpyAsync(c->psamples.ptr, samples, (size_t)p * attempts * 4, hipMemcpyHostToDevice, s));
-    }
+    if (int rc = stage_batch(c, p, b, s)) return rc;
     uint64_t *d_feas = nullptr, *d_fit = nullptr;
     // a mask is needed when the caller wants it, or when the pick reads it (best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
-    const bool pick_reads_mask = (flags & (KSCHED_PICK_BESTFIT | KSCHED_PICK_SAMPLED)) &&
-                                 (c->opt_pick_from_mask || ((flags & KSCHED_PICK_BESTFIT) && !bf_rows_expected(c)));
-    if (out_feas || pick_reads_mask) {
+    if (out_feas || pick_reads_mask(flags, c->opt_pick_from_mask, bf_rows_expected(c))) {
         HIPCHK(c, c->feas.reserve((size_t)p * pitch));
         d_feas = c->feas.ptr;
     }
@@ -1936,9 +1979,9 @@ int eval_begin_locked(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int6
         HIPCHK(c, c->fit.reserve((size_t)p * pitch));
         d_fit = c->fit.ptr;
     }
-    int rc = eval_on_device(c, p, c->pcpu.ptr, c->pmem.ptr, use_sel ? c->psel.ptr : nullptr, use_tol ? c->ptol.ptr : nullptr,
-                            c->psamples.ptr, attempts, flags, d_feas, d_fit, d_bind, (uint32_t)pitch, s);
-    if (rc) return rc;
+    if (int rc = eval_on_device(c, EvalRequest{p, c->pcpu.ptr, c->pmem.ptr, b.psel ? c->psel.ptr : nullptr, b.ptol ? c->ptol.ptr : nullptr, c->psamples.ptr,
+                                               h.attempts, flags, d_feas, d_fit, d_bind, (uint32_t)pitch, s}))
+        return rc;
     // device rows are line-aligned (pitch words apart); the caller's rows are packed (W words)
     if (out_feas && W)
         HIPCHK(c, hipMemcpy2DAsync(out_feas, W * 8, d_feas, pitch * 8, W * 8, p, hipMemcpyDeviceToHost, s));
@@ -1954,13 +1997,14 @@ int ksched_eval(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *p
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    int rc = check_eval_args(c, p, pcpu, pmem, samples, attempts, flags, out_feas, out_fit, out_binding);
+    const EvalRequest h{p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit, out_binding, 0, c->stream};
+    int rc = check_eval_args(h);
     if (rc) return rc;
     if (p == 0) return KSCHED_OK;
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
     int32_t *d_bind = nullptr;
-    rc = eval_begin_locked(c, p, pcpu, pmem, psel, p, ptol, samples, attempts, flags, out_feas, out_fit, p, &d_bind);
+    rc = eval_begin_locked(c, h, p, p, &d_bind);
     if (rc) return rc;
     if (d_bind && out_binding) HIPCHK(c, hipMemcpyAsync(out_binding, d_bind, (size_t)p * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1986,12 +2030,13 @@ int ksched_eval_begin(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int6
     if (!c->have_nodes) return KSCHED_E_STATE;
     if (psel && sel_stride < p) return KSCHED_E_INVAL;
     int32_t sentinel = 0;  // (the bindings stay on the device: check_eval_args only wants to know that a pick has somewhere to go)
-    int rc = check_eval_args(c, p, pcpu, pmem, samples, attempts, flags, out_feas, out_fit,
-                             (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) ? &sentinel : nullptr);
+    const EvalRequest h{p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit,
+                        (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) ? &sentinel : nullptr, 0, c->stream};
+    int rc = check_eval_args(h);
     if (rc) return rc;
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
-    rc = eval_begin_locked(c, p, pcpu, pmem, psel, sel_stride, ptol, samples, attempts, flags, out_feas, out_fit, binding_capacity, binding_dev);
+    rc = eval_begin_locked(c, h, sel_stride, binding_capacity, binding_dev);
     if (rc) return rc;
     *hip_stream = (void *)c->stream;
     return KSCHED_OK;
@@ -2068,11 +2113,11 @@ int mask_alloc_probe(ksched_ctx *c, uint32_t p, uint32_t pitch, size_t bytes, Ma
         constexpr int kReps = 4;
         for (int pass = 0; pass < 2 && rc == KSCHED_OK; ++pass)  // two passes: the first candidates of the first pass carry the warm-up
             for (size_t i = 0; i < cand.size() && rc == KSCHED_OK; ++i) {
-                rc = eval_on_device(c, p, c->pcpu.ptr, c->pmem.ptr, nullptr, nullptr, nullptr, 0, KSCHED_FIT, (uint64_t *)cand[i].ptr, nullptr, nullptr, pitch, c->stream);
+                rc = eval_on_device(c, EvalRequest{p, c->pcpu.ptr, c->pmem.ptr, nullptr, nullptr, nullptr, 0, KSCHED_FIT, (uint64_t *)cand[i].ptr, nullptr, nullptr, pitch, c->stream});
                 if (rc) break;
                 if (hipEventRecord(e0, c->stream) != hipSuccess) rc = KSCHED_E_HIP;
                 for (int r = 0; r < kReps && rc == KSCHED_OK; ++r)
-                    rc = eval_on_device(c, p, c->pcpu.ptr, c->pmem.ptr, nullptr, nullptr, nullptr, 0, KSCHED_FIT, (uint64_t *)cand[i].ptr, nullptr, nullptr, pitch, c->stream);
+                    rc = eval_on_device(c, EvalRequest{p, c->pcpu.ptr, c->pmem.ptr, nullptr, nullptr, nullptr, 0, KSCHED_FIT, (uint64_t *)cand[i].ptr, nullptr, nullptr, pitch, c->stream});
                 if (rc == KSCHED_OK && (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess)) rc = KSCHED_E_HIP;
                 float ms = 0;
                 if (rc == KSCHED_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = KSCHED_E_HIP;
@@ -2234,23 +2279,15 @@ int ksched_explain(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t
     fault_point(c);
     hipStream_t s = c->stream;
     if (int rce = stream_enter(c, s)) return rce;  // behind the latest snapshot change, whichever stream carried it
-    const bool use_fit = flags & KSCHED_FIT;
-    const bool use_sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-    const bool use_taint = (flags & KSCHED_TAINT) && c->have_taints;
-    if (use_fit) {
-        HIPCHK(c, c->pcpu.reserve(p));
-        HIPCHK(c, c->pmem.reserve(p));
-        HIPCHK(c, hipMemcpyAsync(c->pcpu.ptr, pcpu, (size_t)p * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, pmem, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    }
-    if (use_sel) {
-        HIPCHK(c, c->psel.reserve((size_t)p * c->nkeys));
-        HIPCHK(c, hipMemcpyAsync(c->psel.ptr, psel, (size_t)p * c->nkeys * 4, hipMemcpyHostToDevice, s));
-    }
-    if (use_taint && ptol) {
-        HIPCHK(c, c->ptol.reserve(p));
-        HIPCHK(c, hipMemcpyAsync(c->ptol.ptr, ptol, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    }
+    EvalRequest h;  // (host pointers: the normalised terms are all that is read)
+    h.psel = psel;
+    h.flags = flags;
+    const bool use_fit = h.fit(), use_sel = h.sel(c->nkeys), use_taint = h.taint(c->have_taints);
+    HostBatch b;  // requests only with KSCHED_FIT, tolerations only when the snapshot has taints
+    if (use_fit) b.pcpu = pcpu, b.pmem = pmem;
+    if (use_sel) b.psel = psel, b.sel_stride = p;
+    if (use_taint) b.ptol = ptol;
+    if (int rc = stage_batch(c, p, b, s)) return rc;
     HIPCHK(c, c->xpairs.reserve((size_t)count * 2));
     HIPCHK(c, c->xreason.reserve(count));
     HIPCHK(c, hipMemcpyAsync(c->xpairs.ptr, pair_pod, (size_t)count * 4, hipMemcpyHostToDevice, s));
@@ -2289,8 +2326,10 @@ int check_summary_args(const ksched_ctx *c, uint32_t p, const int64_t *pcpu, con
 }
 
 // device pointers; the caller holds the ctx's mutex, has checked the arguments and set the device
-int summarize_on_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, const uint64_t *ptol,
-                        uint32_t flags, uint32_t *out, hipStream_t s) {
+// (of the request: p, pcpu, pmem, psel, ptol, flags and the stream)
+int summarize_on_device(ksched_ctx *c, const EvalRequest &r, uint32_t *out) {
+    const hipStream_t s = r.stream;
+    const uint32_t p = r.p;
     if (p == 0) return KSCHED_OK;
     if (int rce = stream_enter(c, s)) return rce;  // `s` waits for the latest snapshot change; remembered for the next one
     if (c->n == 0) {  // no nodes: nothing is feasible and nothing is rejected
@@ -2300,18 +2339,10 @@ int summarize_on_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const in
     fault_point(c);
     // kernel choice as for evaluations: over the bitmap index when the snapshot has one, else the always-applicable direct kernel
     const bool can_indexed = summary_indexed_applicable(c->idx);
-    int kern = c->opt_kernel;
-    if (kern == KSCHED_KERNEL_AUTO) kern = can_indexed ? KSCHED_KERNEL_FUSED : KSCHED_KERNEL_DIRECT;
-    if (kern == KSCHED_KERNEL_FUSED && !can_indexed) {
-        c->last_error = "fused kernel not applicable to this snapshot/request: " + (c->index_reason.empty() ? std::string("the bitmap index does not fit LDS") : c->index_reason);
-        return KSCHED_E_UNSUPPORTED;
-    }
-    size_t slot = 0;
-    const bool timed = c->opt_timing && c->ev_used < 65536u && (c->timing_seq++ % c->opt_timing) == 0;
-    if (timed) {
-        if (int trc = timing_slot(c, &slot)) return trc;
-        HIPCHK(c, hipEventRecord(c->ev_pool[slot].a, s));
-    }
+    const int kern = choose_kernel(c->opt_kernel, can_indexed);
+    if (kern == KSCHED_KERNEL_FUSED && !can_indexed) return fail_fused_not_applicable(c);
+    TimingBracket t;
+    if (int trc = timing_begin(c, s, true, t)) return trc;
     if (kern == KSCHED_KERNEL_FUSED) {
         // (KSCHED_OPT_DEBUG bit 30: the atomic cross-tile combine, for re-measuring the choice; it needs the table on an 8-byte boundary)
         const bool atomic = (c->opt_debug & 0x40000000u) && !(reinterpret_cast<uintptr_t>(out) & 7u);
@@ -2319,7 +2350,7 @@ int summarize_on_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const in
             if (int rsc = scratch_enter(c, s)) return rsc;
             HIPCHK(c, c->sum_part.reserve(summary_partial_words(c->idx, p)));
         }
-        hipError_t e = run_summary_indexed(c->idx, p, pcpu, pmem, psel, ptol, flags, out, c->sum_part.ptr, atomic, s);
+        hipError_t e = run_summary_indexed(c->idx, r, out, c->sum_part.ptr, atomic);
         if (e != hipSuccess) return fail_hip(c, e, "run_summary_indexed");
         c->last_kernel = "fused";
     } else {
@@ -2327,17 +2358,14 @@ int summarize_on_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const in
         a.n = c->n;
         a.p = p;
         a.nkeys = c->nkeys;
-        a.do_fit = (flags & KSCHED_FIT) ? 1u : 0u;
+        a.do_fit = r.fit() ? 1u : 0u;
         a.aligned = (reinterpret_cast<uintptr_t>(out) & 15u) ? 0u : 1u;
-        const bool sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-        const bool taint = (flags & KSCHED_TAINT) && c->have_taints;
         hipLaunchKernelGGL(k_summarize_direct, dim3((p + 63u) / 64u), dim3(64 * kSummaryDirectWaves), 0, s, c->ncpu.ptr, c->nmem.ptr, c->nlab.ptr,
-                           taint ? c->ntaint.ptr : nullptr, pcpu, pmem, sel ? psel : nullptr, ptol, out, a);
+                           r.taint(c->have_taints) ? c->ntaint.ptr : nullptr, r.pcpu, r.pmem, r.sel(c->nkeys) ? r.psel : nullptr, r.ptol, out, a);
         HIPCHK(c, hipGetLastError());
         c->last_kernel = "direct";
     }
-    if (timed) HIPCHK(c, hipEventRecord(c->ev_pool[slot].b, s));
-    return KSCHED_OK;
+    return timing_end(c, s, t);
 }
 }  // namespace
 
@@ -2348,7 +2376,9 @@ int ksched_summarize_device(ksched_ctx *c, uint32_t p, const int64_t *pcpu, cons
     if (!c->have_nodes) return KSCHED_E_STATE;
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
-    return summarize_on_device(c, p, pcpu, pmem, psel, ptol, flags, out_counts, (hipStream_t)hip_stream);
+    EvalRequest r;
+    r.p = p, r.pcpu = pcpu, r.pmem = pmem, r.psel = psel, r.ptol = ptol, r.flags = flags, r.stream = (hipStream_t)hip_stream;
+    return summarize_on_device(c, r, out_counts);
 } KSCHED_ABI_CATCH(c)
 
 int ksched_summarize(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel, const uint64_t *ptol,
@@ -2360,24 +2390,16 @@ int ksched_summarize(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int64
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
     hipStream_t s = c->stream;
-    const bool use_sel = (flags & KSCHED_SEL) && psel && c->nkeys > 0;
-    const bool use_tol = (flags & KSCHED_TAINT) && ptol;
-    HIPCHK(c, c->pcpu.reserve(p));
-    HIPCHK(c, c->pmem.reserve(p));
+    EvalRequest r;  // first with the caller's host pointers, for the terms; then with the staged ones
+    r.p = p, r.psel = psel, r.flags = flags, r.stream = s;
+    HostBatch b;
+    b.pcpu = pcpu, b.pmem = pmem;
+    if (r.sel(c->nkeys)) b.psel = psel, b.sel_stride = p;
+    if (r.taint_flag()) b.ptol = ptol;
     HIPCHK(c, c->sum_out.reserve((size_t)p * KSCHED_SUMMARY_WORDS));
-    HIPCHK(c, hipMemcpyAsync(c->pcpu.ptr, pcpu, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, pmem, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    if (use_sel) {
-        HIPCHK(c, c->psel.reserve((size_t)p * c->nkeys));
-        HIPCHK(c, hipMemcpyAsync(c->psel.ptr, psel, (size_t)p * c->nkeys * 4, hipMemcpyHostToDevice, s));
-    }
-    if (use_tol) {
-        HIPCHK(c, c->ptol.reserve(p));
-        HIPCHK(c, hipMemcpyAsync(c->ptol.ptr, ptol, (size_t)p * 8, hipMemcpyHostToDevice, s));
-    }
-    if (int rc = summarize_on_device(c, p, c->pcpu.ptr, c->pmem.ptr, use_sel ? c->psel.ptr : nullptr, use_tol ? c->ptol.ptr : nullptr, flags,
-                                     c->sum_out.ptr, s))
-        return rc;
+    if (int rc = stage_batch(c, p, b, s)) return rc;
+    r.pcpu = c->pcpu.ptr, r.pmem = c->pmem.ptr, r.psel = b.psel ? c->psel.ptr : nullptr, r.ptol = b.ptol ? c->ptol.ptr : nullptr;
+    if (int rc = summarize_on_device(c, r, c->sum_out.ptr)) return rc;
     HIPCHK(c, hipMemcpyAsync(out_counts, c->sum_out.ptr, (size_t)p * KSCHED_SUMMARY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return KSCHED_OK;
