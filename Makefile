@@ -33,6 +33,7 @@ OBJ_TOOL := tests/cpp/objects_eval
 FAKE_RCCL := tests/cpp/libfake_rccl.so
 INDEX_TEST := tests/cpp/index_tests
 PLAN_TEST := tests/cpp/plan_tests
+CHANGE_TEST := tests/cpp/snapshot_change_tests
 NODE_EVENTS_TEST := tests/cpp/node_events_tests
 SUMMARY_TEST := tests/cpp/summary_tests
 
@@ -61,7 +62,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c -o tests/cpp/hooks/test_hooks.o tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(CHANGE_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -71,6 +72,9 @@ $(INDEX_TEST): tests/cpp/index_tests.cpp $(CSRC)/tile_index.hpp
 # host-only check of the evaluation plan (csrc/eval_plan.hpp: which kernels a request runs; no GPU, no HIP header): tests/test_eval_plan_host.py runs it
 $(PLAN_TEST): tests/cpp/plan_tests.cpp $(CSRC)/eval_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/plan_tests.cpp
+# host-only check of the pure parts of a snapshot change (csrc/snapshot_change.hpp: kept rows, layout decision, staging offsets, what is stale; no GPU, no HIP header): tests/test_snapshot_change_host.py runs it
+$(CHANGE_TEST): tests/cpp/snapshot_change_tests.cpp $(CSRC)/snapshot_change.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/snapshot_change_tests.cpp
 $(LIB_HOST): $(HOST_SRCS) $(HOST_HDRS) $(LIB_HIP)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRCS) -L$(PKG) -lksched_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 # C++ tests of the host mirror (tests/cpp/host_tests.cpp; driven by tests/test_host_mirror.py)
@@ -118,4 +122,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(CHANGE_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

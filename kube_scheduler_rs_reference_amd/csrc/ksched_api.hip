@@ -27,11 +27,13 @@
 #include "kernels_fused.hpp"
 #include "kernels_summary.hpp"
 #include "mask_alloc.hpp"
+#include "snapshot_change.hpp"
 #include "tile_index.hpp"
 
 using namespace ksched;
 
 static_assert(kListBytes == 6144u && kTileNodes == 1024, "k_pick_bestfit_listed (kernels_direct.hpp) addresses the tile lists with these sizes");
+static_assert(kChangeTileNodes == (uint32_t)kTileNodes, "snapshot_change.hpp lists the tiles an update touches");
 
 namespace {
 
@@ -39,19 +41,17 @@ template <class T>
 struct DevBuf {
     T *ptr = nullptr;
     size_t cap = 0;  // elements
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc((void **)&ptr, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
     void release() {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
         cap = 0;
+    }
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc((void **)&ptr, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) cap = n;
+        return e;
     }
 };
 
@@ -107,7 +107,7 @@ struct ksched_ctx {
     uint32_t apply_gen = 0;       // generation of the latest call
     hipEvent_t ev_apply = nullptr;  // the caller's stream, when the change rides another one
     std::string index_reason;  // why the snapshot has no bitmap index (the fused kernel is then not applicable)
-    // host -> device staging for the snapshot calls: pinned, so the copies are asynchronous on the ctx's stream
+    // host -> device staging for the snapshot calls: pinned, so the copies are asynchronous on the change stream
     uint8_t *h_stage = nullptr;
     size_t h_stage_cap = 0;
     hipEvent_t ev_stage = nullptr;  // the last copy out of h_stage
@@ -267,15 +267,27 @@ int timing_slot(ksched_ctx *c, size_t *slot) {
 
 // ---- stream ordering (see ksched_ctx::user_streams) ---------------------------------------------------------------
 
+// `s`, whose generation is `gen`, waits for the latest snapshot change if it is behind
+int stream_catch_up(ksched_ctx *c, hipStream_t s, uint64_t &gen) {
+    if (gen != c->build_gen) {
+        HIPCHK(c, hipStreamWaitEvent(s, c->ev_build, 0));
+        gen = c->build_gen;
+    }
+    return KSCHED_OK;
+}
+
+// `s` has met the latest snapshot change (it carried the change, or has just been made to wait for it); a stream the ctx does not know
+// has no generation to keep
+void stream_met(ksched_ctx *c, hipStream_t s) {
+    if (s == c->stream) c->own_gen = c->build_gen;
+    for (auto &u : c->user_streams)
+        if (u.s == s) u.gen = c->build_gen;
+}
+
 // remember `s` as a stream evaluations are enqueued on; make it wait for the latest snapshot change if it has not yet
 int stream_enter(ksched_ctx *c, hipStream_t s) {
-    if (s == c->stream) {  // the ctx's own stream: in order by itself unless the latest change went onto a caller's stream
-        if (c->own_gen != c->build_gen) {
-            HIPCHK(c, hipStreamWaitEvent(s, c->ev_build, 0));
-            c->own_gen = c->build_gen;
-        }
-        return KSCHED_OK;
-    }
+    // the ctx's own stream: in order by itself unless the latest change went onto a caller's stream
+    if (s == c->stream) return stream_catch_up(c, s, c->own_gen);
     ksched_ctx::UserStream *u = nullptr;
     for (auto &x : c->user_streams)
         if (x.s == s) u = &x;
@@ -285,11 +297,7 @@ int stream_enter(ksched_ctx *c, hipStream_t s) {
         c->user_streams.push_back(n);
         u = &c->user_streams.back();
     }
-    if (u->gen != c->build_gen) {
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_build, 0));
-        u->gen = c->build_gen;
-    }
-    return KSCHED_OK;
+    return stream_catch_up(c, s, u->gen);
 }
 
 // `s` is about to enqueue work that uses the ctx-owned scratch buffers
@@ -337,19 +345,15 @@ int snapshot_begin(ksched_ctx *c) {
         auto &u = c->user_streams[0];
         const hipError_t q = hipStreamQuery(u.s);  // host-side probe: a stream the caller destroyed without telling is not used
         if (q == hipSuccess || q == hipErrorNotReady) {
-            if (u.gen != c->build_gen) {  // (an earlier change went onto the ctx's stream and this stream has not met it yet)
-                HIPCHK(c, hipStreamWaitEvent(u.s, c->ev_build, 0));
-                u.gen = c->build_gen;
-            }
+            // (an earlier change may have gone onto the ctx's stream, and this stream not have met it yet)
+            if (int rc = stream_catch_up(c, u.s, u.gen)) return rc;
             c->change_stream = u.s;
             return KSCHED_OK;
         }
         (void)hipGetLastError();  // fall through: the loop below forgets the stream
     }
-    if (c->own_gen != c->build_gen) {  // an earlier change went onto a caller's stream: this one is ordered behind it
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_build, 0));
-        c->own_gen = c->build_gen;
-    }
+    // an earlier change may have gone onto a caller's stream: this one is ordered behind it
+    if (int rc = stream_catch_up(c, c->stream, c->own_gen)) return rc;
     for (size_t i = 0; i < c->user_streams.size();) {
         auto &u = c->user_streams[i];
         if (hipEventRecord(u.ev, u.s) != hipSuccess) {  // the caller destroyed that stream: forget it
@@ -366,17 +370,15 @@ int snapshot_begin(ksched_ctx *c) {
 
 // after the change has been enqueued on change_stream: ev_build marks it for every other stream
 int snapshot_end(ksched_ctx *c) {
-    const hipStream_t s = c->change_stream;
-    HIPCHK(c, hipEventRecord(c->ev_build, s));
+    HIPCHK(c, hipEventRecord(c->ev_build, c->change_stream));
     ++c->build_gen;
-    if (s == c->stream) c->own_gen = c->build_gen;
-    for (auto &u : c->user_streams)
-        if (u.s == s) u.gen = c->build_gen;  // the stream that carries the change is behind it by itself
+    stream_met(c, c->change_stream);  // the stream that carries the change is behind it by itself
     return KSCHED_OK;
 }
 
-// A snapshot change that can stop halfway, by an error return or a throw: once snapshot_begin has succeeded (`c` set), the ctx refuses
-// evaluations until its next ksched_set_nodes unless the change is marked done -- columns, index and apply scratch may disagree.
+// Every change of the node snapshot, in three calls: begin -> stage, fill, upload (a change that brings data) ->
+// the caller's kernels on change_stream -> commit.  A change can stop halfway, by an error return or a throw: once armed, the ctx
+// refuses evaluations until its next ksched_set_nodes unless the change is committed -- columns, index and apply scratch may disagree.
 struct SnapshotChange {
     ksched_ctx *c = nullptr;
     bool done = false;
@@ -386,26 +388,54 @@ struct SnapshotChange {
             c->apply_n = 0;
         }
     }
-};
-
-// pinned staging: returns a host pointer to `bytes` bytes whose previous use (an async copy) has completed
-int stage_reserve(ksched_ctx *c, size_t bytes, uint8_t **out) {
-    if (c->h_stage) HIPCHK(c, hipEventSynchronize(c->ev_stage));
-    if (bytes > c->h_stage_cap) {
-        if (c->h_stage) (void)hipHostFree(c->h_stage);
-        c->h_stage = nullptr;
-        c->h_stage_cap = 0;
-        const size_t cap = std::max<size_t>(bytes + bytes / 4, 1u << 16);
-        HIPCHK(c, hipHostMalloc((void **)&c->h_stage, cap, hipHostMallocDefault));
-        c->h_stage_cap = cap;
+    // (ksched_set_nodes alone is armed from the start, SnapshotChange chg{c}: whatever stops it, the old snapshot is gone)
+    // Evaluations already enqueued read the snapshot as it was (snapshot_begin: events, no host wait; it chooses change_stream).  A
+    // failure up to here leaves the snapshot as it was, one after it does not.
+    int begin(ksched_ctx *ctx) {
+        if (int rc = snapshot_begin(ctx)) return rc;
+        c = ctx;
+        return KSCHED_OK;
     }
-    *out = c->h_stage;
-    return KSCHED_OK;
-}
+    // The pinned block, `bytes` long, whose previous use (an async copy) has completed -- the caller fills it after a StageLayout --
+    // and the device block (ksched_ctx::d_stage) for its first `dev_bytes` bytes.
+    int stage(size_t bytes, size_t dev_bytes, uint8_t **h) {
+        if (c->h_stage) HIPCHK(c, hipEventSynchronize(c->ev_stage));
+        if (bytes > c->h_stage_cap) {
+            if (c->h_stage) (void)hipHostFree(c->h_stage);
+            c->h_stage = nullptr;
+            c->h_stage_cap = 0;
+            const size_t cap = std::max<size_t>(bytes + bytes / 4, 1u << 16);
+            HIPCHK(c, hipHostMalloc((void **)&c->h_stage, cap, hipHostMallocDefault));
+            c->h_stage_cap = cap;
+        }
+        *h = c->h_stage;
+        HIPCHK(c, c->d_stage.reserve(dev_bytes));
+        return KSCHED_OK;
+    }
+    // the pinned block's first `dev_bytes` bytes -> the device block, one copy on the change stream; ev_stage: the last copy out of the
+    // pinned block (the caller's own copies out of it come before this call)
+    int upload(size_t dev_bytes) {
+        const hipStream_t s = c->change_stream;
+        if (dev_bytes) HIPCHK(c, hipMemcpyAsync(c->d_stage.ptr, c->h_stage, dev_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipEventRecord(c->ev_stage, s));
+        return KSCHED_OK;
+    }
+    // everything is enqueued: mark what the change made stale (the best-fit structures are rebuilt by the next PICK_BESTFIT request,
+    // ensure_bestfit, not here), let the other streams see the change (snapshot_end), validate the snapshot
+    int commit(Stale what) {
+        if (stale_order(what)) c->bf_dirty = true;
+        if (stale_rows_only(what)) c->bf_rows_dirty = true;
+        if (what == Stale::kEverything) c->bf_rows_built = false;
+        if (int rc = snapshot_end(c)) return rc;
+        c->have_nodes = true;
+        done = true;
+        return KSCHED_OK;
+    }
+};
 
 // ---- index and best-fit build (kernels_build.hpp) --------------------------------------------------------------------
 
-// (re)build the fit part of the listed tiles (or of every tile: tiles == nullptr) on the ctx's stream
+// (re)build the fit part of the listed tiles (or of every tile: tiles == nullptr) on the change stream
 int launch_build_fit(ksched_ctx *c, const uint32_t *d_tile_list, uint32_t count, const uint32_t *d_dirty = nullptr) {
     const IndexedLayout &l = c->idx.lay;
     BuildFitArgs a{};
@@ -465,17 +495,12 @@ int launch_build_named(ksched_ctx *c, const uint32_t *d_tile_list = nullptr, uin
 // Best-fit candidate order of the snapshot, ascending (avail_mem, avail_cpu, node), its inverse, the node
 // columns in that order, the sorted cpu column with the sample arrays of the two rank searches, and -- when the snapshot has a
 // bitmap index -- the named rows once more over best-fit positions plus the 257 cpu threshold rows (k_pick_bestfit_rows).
-// Two device merge sorts (kernels_build.hpp: k_sort_runs + k_merge_pass) and two kernels, on the ctx's stream; called lazily by the first PICK_BESTFIT request
+// Two device merge sorts (kernels_build.hpp: k_sort_runs + k_merge_pass) and two kernels, on the change stream; called lazily by the first PICK_BESTFIT request
 // after the snapshot changed (ksched_set_nodes / ksched_update_nodes only mark it dirty).
 int build_bestfit_rows(ksched_ctx *c);
 int build_bestfit(ksched_ctx *c) {
     const uint32_t n = c->n;
     c->bf_rows_built = false;
-    if (n == 0) {
-        c->bf_dirty = false;
-        c->bf_rows_dirty = false;
-        return KSCHED_OK;
-    }
     hipStream_t s = c->change_stream;
     const uint32_t n1 = (n + 63u) / 64u, n2 = (n + 4095u) / 4096u;
     HIPCHK(c, c->by_cpu.reserve(n));
@@ -498,22 +523,14 @@ int build_bestfit(ksched_ctx *c) {
         for (uint64_t run = 1024; run < n; run <<= 1) ++passes;
         // buffer of pass i's output: the destination arrays for the last one, the ping-pong sets before it
         auto out_of = [&](uint32_t i, SortArgs &q) {  // i = 0: k_sort_runs, i = 1 .. passes: merge passes
-            if (i == passes) {
-                q.k0_out = dst_k0;
-                q.k1_out = k1 ? c->srt_k1[i & 1].ptr : nullptr;  // (nobody reads the second key of the final order)
-                q.idx_out = dst_idx;
-            } else {
-                q.k0_out = c->srt_k0[i & 1].ptr;
-                q.k1_out = k1 ? c->srt_k1[i & 1].ptr : nullptr;
-                q.idx_out = c->srt_idx[i & 1].ptr;
-            }
+            q.k0_out = i == passes ? dst_k0 : c->srt_k0[i & 1].ptr;
+            q.k1_out = k1 ? c->srt_k1[i & 1].ptr : nullptr;  // (nobody reads the second key of the final order)
+            q.idx_out = i == passes ? dst_idx : c->srt_idx[i & 1].ptr;
         };
-        SortArgs q{};
+        SortArgs q{};  // (no idx_in, run 0: the runs are sorted from the columns)
         q.n = n;
         q.k0_in = k0;
         q.k1_in = k1;
-        q.idx_in = nullptr;
-        q.run = 0;
         out_of(0, q);
         hipLaunchKernelGGL(k_sort_runs, dim3((n + 1023u) / 1024u), dim3(1024), 0, s, q);
         HIPCHK(c, hipGetLastError());
@@ -577,9 +594,7 @@ int build_bestfit(ksched_ctx *c) {
             HIPCHK(c, hipGetLastError());
         }
     }
-    if (int rc = build_bestfit_rows(c)) return rc;
-    c->bf_dirty = false;
-    return KSCHED_OK;
+    return build_bestfit_rows(c);
 }
 
 // The row bitmaps in best-fit order alone, over the current order: what a label / taint change (ksched_update_node_labels) makes
@@ -618,7 +633,6 @@ int build_bestfit_rows(ksched_ctx *c) {
         c->bf_q = q;
         c->bf_rows_built = true;
     }
-    c->bf_rows_dirty = false;
     return KSCHED_OK;
 }
 
@@ -627,11 +641,15 @@ inline bool bf_rows_expected(const ksched_ctx *c) { return c->idx.built && c->n 
 
 // a PICK_BESTFIT request is about to be enqueued: make sure the structures match the snapshot
 int ensure_bestfit(ksched_ctx *c) {
-    if (!c->bf_dirty && !c->bf_rows_dirty) return KSCHED_OK;
-    int rc = snapshot_begin(c);  // picks already enqueued read the previous order
-    if (rc) return rc;
-    if ((rc = c->bf_dirty ? build_bestfit(c) : build_bestfit_rows(c))) return rc;  // (rows only: no sort)
-    return snapshot_end(c);
+    if (c->n == 0 || (!c->bf_dirty && !c->bf_rows_dirty)) return KSCHED_OK;
+    SnapshotChange chg;
+    if (int rc = chg.begin(c)) return rc;  // picks already enqueued read the previous order
+    if (int rc = c->bf_dirty ? build_bestfit(c) : build_bestfit_rows(c)) {  // (rows only: no sort)
+        chg.done = true;  // columns and index are untouched and the stale flags still set: nothing to invalidate, the next request tries again
+        return rc;
+    }
+    c->bf_dirty = c->bf_rows_dirty = false;
+    return chg.commit(Stale::kNothing);
 }
 
 // ---- the bitmap index's layout: plan -> reserve -> build ----------------------------------------------------------------
@@ -644,7 +662,7 @@ struct IndexPlan {
     bool indexed = false;
     uint32_t meta[72] = {};
 };
-constexpr size_t kPlanMetaBytes = sizeof(IndexPlan::meta);
+constexpr size_t kPlanMetaBytes = sizeof(IndexPlan::meta), kPlanMetaWords = kPlanMetaBytes / 4;
 
 // the layout for these per-key maxima and taint bits; they become the ctx's plan inputs
 void index_plan(ksched_ctx *c, uint32_t n, uint32_t n_keys, const uint32_t *lab_max, uint64_t all_taints, IndexPlan &p) {
@@ -1149,7 +1167,7 @@ int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
     const bool pick_s = r.flags & KSCHED_PICK_SAMPLED, pick_b = r.flags & KSCHED_PICK_BESTFIT;
     if (r.p == 0) return KSCHED_OK;
     if (pick_b && c->n > 0)
-        if (int rcb = ensure_bestfit(c)) return rcb;  // lazily (re)built after a snapshot change, on the ctx's stream
+        if (int rcb = ensure_bestfit(c)) return rcb;  // lazily (re)built after a snapshot change, on the change stream
     if (int rce = stream_enter(c, r.stream)) return rce;  // the stream waits for the latest snapshot change; remembered for the next one
     if (c->n == 0) {
         // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
@@ -1423,18 +1441,13 @@ int ksched_set_nodes(ksched_ctx *c, uint32_t n, const int64_t *cpu, const int64_
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
-    c->have_nodes = false;  // stays false if anything below fails (or throws): a half-built snapshot is never evaluated
+    SnapshotChange chg{c};  // armed before the fault point: if anything below fails (or throws), a half-built snapshot is never evaluated
     fault_point(c);
-    // evaluations already enqueued on the caller's streams read the previous snapshot: the ctx's stream waits for them
-    // (events; the host does not)
-    if (int rc = snapshot_begin(c)) return rc;
+    if (int rc = chg.begin(c)) return rc;
     c->n = n;
     c->nkeys = n_keys;
     c->W = ksched_mask_words(n);
     c->have_taints = taints != nullptr;
-    c->bf_dirty = true;
-    c->bf_rows_built = false;
-    c->idx.built = false;
     HIPCHK(c, c->ncpu.reserve(n));
     HIPCHK(c, c->nmem.reserve(n));
     HIPCHK(c, c->nrec.reserve((size_t)n * kNodeRecWords));
@@ -1451,33 +1464,31 @@ int ksched_set_nodes(ksched_ctx *c, uint32_t n, const int64_t *cpu, const int64_
     index_plan(c, n, n_keys, lab_max, all_taints, plan);
     // the caller's arrays (and the index's meta words) -> pinned staging -> asynchronous copies on the chosen stream; nothing is
     // copied from pageable or stack memory, so the call never waits for work already queued on that stream
-    const size_t b_col = (size_t)n * 8, b_lab = (size_t)n * n_keys * 4, b_taint = taints ? b_col : 0, b_meta = plan.indexed ? kPlanMetaBytes : 0;
-    const size_t o_meta = 2 * b_col + b_lab + b_taint;
+    StageLayout f;  // [cpu][mem][ids n_keys x n][taints][meta words]: each column is copied to its own device buffer
+    const size_t o_cpu = f.add<int64_t>(n), o_mem = f.add<int64_t>(n), o_lab = f.add<uint32_t>((size_t)n * n_keys);
+    const size_t o_taint = f.add<uint64_t>(taints ? n : 0), o_meta = f.add<uint32_t>(plan.indexed ? kPlanMetaWords : 0);
     uint8_t *h = nullptr;
-    if (n > 0 || b_meta) {
-        if (int rc = stage_reserve(c, o_meta + b_meta, &h)) return rc;
-    }
+    if (int rc = f.total ? chg.stage(f.total, 0, &h) : KSCHED_OK) return rc;
     if (n > 0) {
-        memcpy(h, cpu, b_col);
-        memcpy(h + b_col, mem, b_col);
-        if (b_lab) memcpy(h + 2 * b_col, lab, b_lab);
-        if (b_taint) memcpy(h + 2 * b_col + b_lab, taints, b_taint);
-        HIPCHK(c, hipMemcpyAsync(c->ncpu.ptr, h, b_col, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->nmem.ptr, h + b_col, b_col, hipMemcpyHostToDevice, s));
-        if (b_lab) HIPCHK(c, hipMemcpyAsync(c->nlab.ptr, h + 2 * b_col, b_lab, hipMemcpyHostToDevice, s));
-        if (b_taint) HIPCHK(c, hipMemcpyAsync(c->ntaint.ptr, h + 2 * b_col + b_lab, b_taint, hipMemcpyHostToDevice, s));
+        const size_t b_col = (size_t)n * 8, b_lab = (size_t)n * n_keys * 4;
+        memcpy(h + o_cpu, cpu, b_col);
+        memcpy(h + o_mem, mem, b_col);
+        if (b_lab) memcpy(h + o_lab, lab, b_lab);
+        if (taints) memcpy(h + o_taint, taints, b_col);
+        HIPCHK(c, hipMemcpyAsync(c->ncpu.ptr, h + o_cpu, b_col, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(c->nmem.ptr, h + o_mem, b_col, hipMemcpyHostToDevice, s));
+        if (b_lab) HIPCHK(c, hipMemcpyAsync(c->nlab.ptr, h + o_lab, b_lab, hipMemcpyHostToDevice, s));
+        if (taints) HIPCHK(c, hipMemcpyAsync(c->ntaint.ptr, h + o_taint, b_col, hipMemcpyHostToDevice, s));
     }
     if (int rc = index_reserve(c, plan, h + o_meta)) return rc;
-    if (h) HIPCHK(c, hipEventRecord(c->ev_stage, s));  // the last copy out of the staging block
+    if (int rc = h ? chg.upload(0) : KSCHED_OK) return rc;  // (the copies above were the block's)
     if (n > 0) {
         hipLaunchKernelGGL(k_build_nrec, dim3((n + 255u) / 256u), dim3(256), 0, s, (const int64_t *)c->ncpu.ptr, (const int64_t *)c->nmem.ptr,
                            taints ? (const uint64_t *)c->ntaint.ptr : nullptr, (const uint32_t *)c->nlab.ptr, n_keys, c->nrec.ptr, n);
         HIPCHK(c, hipGetLastError());
     }
     if (int rc = index_build(c, plan, true, cpu, mem, lab, taints)) return rc;
-    if (int rc = snapshot_end(c)) return rc;
-    c->have_nodes = true;
-    return KSCHED_OK;
+    return chg.commit(Stale::kEverything);
 } KSCHED_ABI_CATCH(c)
 
 int ksched_update_node_labels(ksched_ctx *c, uint32_t count, const uint32_t *node_index, const uint32_t *lab, const uint64_t *taints) try {
@@ -1495,92 +1506,65 @@ int ksched_update_node_labels(ksched_ctx *c, uint32_t count, const uint32_t *nod
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
     fault_point(c);  // (nothing has changed yet)
-    // a node listed twice takes its last row: keep the last occurrence of every index (the patch kernel's threads are unordered)
-    std::vector<uint32_t> keep;
-    {
-        std::vector<uint32_t> order(count);
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return node_index[a] < node_index[b]; });
-        for (uint32_t i = 0; i < count; ++i)
-            if (i + 1 == count || node_index[order[i + 1]] != node_index[order[i]]) keep.push_back(order[i]);
-    }
+    std::vector<uint32_t> keep, tiles;
+    last_wins(node_index, count, keep, tiles);
     const uint32_t m = (uint32_t)keep.size();
-    std::vector<uint32_t> tiles;
-    for (uint32_t i : keep) tiles.push_back(node_index[i] / kTileNodes);  // ascending already
-    tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
-    // Does the planned layout still hold?  Every new id at most its key's planned maximum, every new taint bit inside the planned taint
-    // groups.  Otherwise re-plan with the union of the old and the new maxima and bits, and rebuild the whole index.
+    // Does the planned layout still hold?  Otherwise re-plan with the union of the old and the new maxima and bits, and rebuild the
+    // whole index.  (The ctx's plan inputs change only once the change has begun.)
     uint32_t lab_max[KSCHED_MAX_KEYS];
-    for (uint32_t k = 0; k < KSCHED_MAX_KEYS; ++k) lab_max[k] = c->plan_lab_max[k];
+    std::copy(c->plan_lab_max, c->plan_lab_max + KSCHED_MAX_KEYS, lab_max);
     uint64_t all_taints = c->plan_taints;
-    bool holds = c->idx.built;
-    for (uint32_t k = 0; k < nkeys; ++k)
-        for (uint32_t i : keep) {
-            const uint32_t id = lab[(size_t)k * count + i];
-            if (id > lab_max[k]) {
-                lab_max[k] = id;
-                holds = false;
-            }
-        }
-    if (taints) {
-        for (uint32_t i : keep) all_taints |= taints[i];
-        const uint32_t groups = c->idx.built ? c->idx.lay.ngroups : 0u;
-        const uint64_t covered = groups >= 16u ? ~0ull : (1ull << (4u * groups)) - 1ull;
-        if (all_taints & ~covered) holds = false;
-    }
-    if (int rc = snapshot_begin(c)) return rc;  // evaluations already enqueued read the snapshot as it was (events, no host wait)
-    SnapshotChange chg{c};
-    hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
+    const bool holds = label_layout_holds(lab_max, &all_taints, c->idx.built, c->idx.lay.ngroups, nkeys, count, keep.data(), m, lab, taints);
+    SnapshotChange chg;
+    if (int rc = chg.begin(c)) return rc;
     IndexPlan plan;
     if (holds) c->plan_taints = all_taints;  // (same groups)
     else index_plan(c, n, nkeys, lab_max, all_taints, plan);
-    // the kept rows -> pinned staging -> one copy: [taints u64 m][node u32 m][ids u32 nkeys x m][tiles u32]; the meta words (re-plan) after it
-    const size_t b_taint = taints ? (size_t)m * 8 : 0, b_idx = (size_t)m * 4, b_lab = (size_t)nkeys * m * 4, b_tiles = tiles.size() * 4;
-    const size_t b_dev = b_taint + b_idx + b_lab + b_tiles, b_meta = plan.indexed ? kPlanMetaBytes : 0;
+    // the kept rows -> pinned staging -> one copy: [taints m][node m][ids nkeys x m][tiles]; the meta words (re-plan) lie after what
+    // is copied and travel by index_reserve
+    StageLayout f;
+    const size_t o_taint = f.add<uint64_t>(taints ? m : 0), o_idx = f.add<uint32_t>(m), o_lab = f.add<uint32_t>((size_t)nkeys * m);
+    const size_t o_tiles = f.add<uint32_t>(tiles.size()), b_dev = f.total, o_meta = f.add<uint32_t>(plan.indexed ? kPlanMetaWords : 0);
     uint8_t *h = nullptr;
-    if (int rc = stage_reserve(c, b_dev + b_meta, &h)) return rc;
-    uint64_t *ht = reinterpret_cast<uint64_t *>(h);
-    uint32_t *hi = reinterpret_cast<uint32_t *>(h + b_taint), *hl = hi + m, *hs = hl + (size_t)nkeys * m;
+    if (int rc = chg.stage(f.total, b_dev, &h)) return rc;
+    uint64_t *ht = reinterpret_cast<uint64_t *>(h + o_taint);
+    uint32_t *hi = reinterpret_cast<uint32_t *>(h + o_idx), *hl = reinterpret_cast<uint32_t *>(h + o_lab);
     for (uint32_t j = 0; j < m; ++j) {
         const uint32_t i = keep[j];
         hi[j] = node_index[i];
         if (taints) ht[j] = taints[i];
         for (uint32_t k = 0; k < nkeys; ++k) hl[(size_t)k * m + j] = lab[(size_t)k * count + i];
     }
-    memcpy(hs, tiles.data(), b_tiles);
-    HIPCHK(c, c->d_stage.reserve(b_dev));
-    HIPCHK(c, hipMemcpyAsync(c->d_stage.ptr, h, b_dev, hipMemcpyHostToDevice, s));
+    memcpy(h + o_tiles, tiles.data(), tiles.size() * 4);
     if (!holds)
-        if (int rc = index_reserve(c, plan, h + b_dev)) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_stage, s));
+        if (int rc = index_reserve(c, plan, h + o_meta)) return rc;
+    if (int rc = chg.upload(b_dev)) return rc;
     if (taints && !c->have_taints) {  // taints on a snapshot set without them: every other node has none
-        HIPCHK(c, hipMemsetAsync(c->ntaint.ptr, 0, (size_t)n * 8, s));
+        HIPCHK(c, hipMemsetAsync(c->ntaint.ptr, 0, (size_t)n * 8, c->change_stream));
         c->have_taints = true;
     }
     PatchLabelsArgs pa{};
     pa.nlab = c->nlab.ptr;
     pa.ntaint = taints ? c->ntaint.ptr : nullptr;
     pa.nrec = c->nrec.ptr;
-    pa.taints = taints ? reinterpret_cast<const uint64_t *>(c->d_stage.ptr) : nullptr;
-    pa.idx = reinterpret_cast<const uint32_t *>(c->d_stage.ptr + b_taint);
-    pa.lab = pa.idx + m;
+    const uint8_t *d = c->d_stage.ptr;
+    pa.taints = taints ? reinterpret_cast<const uint64_t *>(d + o_taint) : nullptr;
+    pa.idx = reinterpret_cast<const uint32_t *>(d + o_idx);
+    pa.lab = reinterpret_cast<const uint32_t *>(d + o_lab);
     pa.count = m;
     pa.n = n;
     pa.nkeys = nkeys;
-    hipLaunchKernelGGL(k_patch_labels, dim3((m + 255u) / 256u), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(k_patch_labels, dim3((m + 255u) / 256u), dim3(256), 0, c->change_stream, pa);
     HIPCHK(c, hipGetLastError());
     if (holds) {
         // only the touched 1024-node tiles are re-indexed: their named rows and list slots (the fit part reads `available` only)
-        const uint32_t *d_tiles = pa.lab + (size_t)nkeys * m;
+        const uint32_t *d_tiles = reinterpret_cast<const uint32_t *>(d + o_tiles);
         if (int rc = launch_build_named(c, d_tiles, (uint32_t)tiles.size())) return rc;
         if (int rc = launch_build_lists(c, d_tiles, (uint32_t)tiles.size())) return rc;
     } else {
         if (int rc = index_build(c, plan, false, nullptr, nullptr, nullptr, nullptr)) return rc;
     }
-    c->bf_rows_dirty = true;  // the best-fit ORDER reads `available` only: the next PICK_BESTFIT request rebuilds the rows alone
-    if (int rc = snapshot_end(c)) return rc;
-    chg.done = true;
-    return KSCHED_OK;
+    return chg.commit(Stale::kLabels);  // the best-fit ORDER reads `available` only: the next PICK_BESTFIT request rebuilds the rows alone
 } KSCHED_ABI_CATCH(c)
 
 int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_index, const int64_t *cpu, const int64_t *mem) try {
@@ -1594,32 +1578,17 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
     fault_point(c);  // (nothing has changed yet: an exception up to snapshot_begin leaves the snapshot as it was)
-    // a node listed twice takes its last values: keep the last occurrence of every index (the patch kernel's threads are unordered)
-    std::vector<uint32_t> keep;
-    if (count > 1) {
-        std::vector<uint32_t> order(count);
-        std::iota(order.begin(), order.end(), 0u);
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return node_index[a] < node_index[b]; });
-        for (uint32_t i = 0; i < count; ++i)
-            if (i + 1 == count || node_index[order[i + 1]] != node_index[order[i]]) keep.push_back(order[i]);
-    } else {
-        keep.push_back(0u);
-    }
+    std::vector<uint32_t> keep, tiles;
+    last_wins(node_index, count, keep, tiles);
     const uint32_t m = (uint32_t)keep.size();
-    std::vector<uint32_t> tiles;
-    for (uint32_t i : keep) tiles.push_back(node_index[i] / kTileNodes);  // ascending already
-    tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
-    // evaluations already enqueued read the snapshot as it was (events, no host wait)
-    if (int rc = snapshot_begin(c)) return rc;
-    SnapshotChange chg{c};
-    hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
+    SnapshotChange chg;
+    if (int rc = chg.begin(c)) return rc;
     PatchArgs pa{};
     pa.ncpu = c->ncpu.ptr;
     pa.nmem = c->nmem.ptr;
     pa.nrec = c->nrec.ptr;
     pa.count = m;
     const uint32_t *d_tiles = nullptr;
-    const bool want_tiles = c->idx.built;
     if (m <= kPatchInline && tiles.size() <= kPatchInline) {
         // small updates (the watch-event case) travel in kernel arguments: no copy, no staging buffer
         for (uint32_t j = 0; j < m; ++j) {
@@ -1628,42 +1597,39 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
             pa.mem_in[j] = mem[keep[j]];
         }
     } else {
-        const size_t b_idx = ((size_t)m * 4 + 7) & ~(size_t)7, b_val = (size_t)m * 8, b_tiles = tiles.size() * 4;
+        StageLayout f;  // [node m][cpu m][mem m][tiles], one copy
+        const size_t o_idx = f.add<uint32_t>(m), o_cpu = f.add<int64_t>(m), o_mem = f.add<int64_t>(m), o_tiles = f.add<uint32_t>(tiles.size());
         uint8_t *h = nullptr;
-        if (int rc = stage_reserve(c, b_idx + 2 * b_val + b_tiles, &h)) return rc;
-        uint32_t *hi = reinterpret_cast<uint32_t *>(h);
-        int64_t *hc = reinterpret_cast<int64_t *>(h + b_idx), *hm = hc + m;
+        if (int rc = chg.stage(f.total, f.total, &h)) return rc;
+        uint32_t *hi = reinterpret_cast<uint32_t *>(h + o_idx);
+        int64_t *hc = reinterpret_cast<int64_t *>(h + o_cpu), *hm = reinterpret_cast<int64_t *>(h + o_mem);
         for (uint32_t j = 0; j < m; ++j) {
             hi[j] = node_index[keep[j]];
             hc[j] = cpu[keep[j]];
             hm[j] = mem[keep[j]];
         }
-        memcpy(h + b_idx + 2 * b_val, tiles.data(), b_tiles);
-        HIPCHK(c, c->d_stage.reserve(b_idx + 2 * b_val + b_tiles));
-        HIPCHK(c, hipMemcpyAsync(c->d_stage.ptr, h, b_idx + 2 * b_val + b_tiles, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipEventRecord(c->ev_stage, s));
-        pa.idx = reinterpret_cast<const uint32_t *>(c->d_stage.ptr);
-        pa.cpu = reinterpret_cast<const int64_t *>(c->d_stage.ptr + b_idx);
-        pa.mem = pa.cpu + m;
-        d_tiles = reinterpret_cast<const uint32_t *>(c->d_stage.ptr + b_idx + 2 * b_val);
+        memcpy(h + o_tiles, tiles.data(), tiles.size() * 4);
+        if (int rc = chg.upload(f.total)) return rc;
+        const uint8_t *d = c->d_stage.ptr;
+        pa.idx = reinterpret_cast<const uint32_t *>(d + o_idx);
+        pa.cpu = reinterpret_cast<const int64_t *>(d + o_cpu);
+        pa.mem = reinterpret_cast<const int64_t *>(d + o_mem);
+        d_tiles = reinterpret_cast<const uint32_t *>(d + o_tiles);
     }
-    if (want_tiles && !d_tiles) {  // small update: the tile list rides in the patch kernel's arguments
+    if (c->idx.built && !d_tiles) {  // small update: the tile list rides in the patch kernel's arguments
         HIPCHK(c, c->d_stage.reserve(kPatchInline * 4));
         pa.tile_out = reinterpret_cast<uint32_t *>(c->d_stage.ptr);
         pa.ntiles = (uint32_t)tiles.size();
         for (size_t j = 0; j < tiles.size(); ++j) pa.tiles_in[j] = tiles[j];
         d_tiles = pa.tile_out;
     }
-    hipLaunchKernelGGL(k_patch_nodes, dim3((m + 255u) / 256u), dim3(256), 0, s, pa);
+    hipLaunchKernelGGL(k_patch_nodes, dim3((m + 255u) / 256u), dim3(256), 0, c->change_stream, pa);
     HIPCHK(c, hipGetLastError());
-    if (want_tiles) {
+    if (c->idx.built) {
         // only the touched 1024-node tiles are re-indexed (fit rows, search trees, cnt tables); label and taint rows are untouched
         if (int rc = launch_build_fit(c, d_tiles, (uint32_t)tiles.size())) return rc;
     }
-    c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
-    if (int rc = snapshot_end(c)) return rc;
-    chg.done = true;
-    return KSCHED_OK;
+    return chg.commit(Stale::kAvailable);
 } KSCHED_ABI_CATCH(c)
 
 int ksched_read_nodes(ksched_ctx *c, uint32_t first, uint32_t count, int64_t *out_cpu, int64_t *out_mem) try {
@@ -2598,7 +2564,7 @@ struct ApplyCall {
     hipStream_t hs = nullptr;  // the caller's stream
     uint32_t count = 0;        // the rank's rows
     ApplyArgs a{};
-    SnapshotChange chg;        // marked done when every rank's change has finished
+    SnapshotChange chg;        // done when every rank's change has been committed (apply_run)
 };
 
 dim3 pod_grid(uint32_t p) { return dim3(std::min<uint32_t>((p + 255u) / 256u, 2048u)); }
@@ -2642,8 +2608,7 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
                 const uint8_t *ok, uint32_t flags, int32_t *status_out) {
     ksched_ctx *c = x.c;
     fault_point(c);  // (nothing has changed yet)
-    if (int rc = snapshot_begin(c)) return rc;
-    x.chg.c = c;
+    if (int rc = x.chg.begin(c)) return rc;
     const hipStream_t s = c->change_stream;
     if (s != x.hs) {
         if (!c->ev_apply) HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
@@ -2652,7 +2617,6 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
     }
     if (int rc = apply_scratch_ready(c, s)) return rc;
     const uint32_t n = c->n;
-    if (x.q) HIPCHK(c, c->apply_gath.reserve((size_t)x.q->nranks * n * 4));
     ApplyArgs &a = x.a;
     a.bindings = bindings;
     a.req_cpu = req_cpu;
@@ -2673,6 +2637,7 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
     a.first_per_node = (flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
     a.release = (flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
     if (x.q) {
+        HIPCHK(c, c->apply_gath.reserve((size_t)x.q->nranks * n * 4));
         a.row_lo = row_lo;
         a.sharded = 1;
         a.gathered = c->apply_gath.ptr;
@@ -2720,13 +2685,10 @@ int apply_finish(ApplyCall &x) {
             HIPCHK(c, hipGetLastError());
         }
     }
-    c->bf_dirty = true;  // the best-fit order is rebuilt by the next PICK_BESTFIT request, not here
-    if (int rc = snapshot_end(c)) return rc;
+    if (int rc = x.chg.commit(Stale::kAvailable)) return rc;
     if (s != x.hs) {
         HIPCHK(c, hipStreamWaitEvent(x.hs, c->ev_build, 0));
-        if (x.hs == c->stream) c->own_gen = c->build_gen;
-        for (auto &u : c->user_streams)
-            if (u.s == x.hs) u.gen = c->build_gen;
+        stream_met(c, x.hs);
     }
     return KSCHED_OK;
 }
@@ -2767,13 +2729,14 @@ int apply_run(ApplyCall *v, int k, const uint32_t *row_lo, const int32_t *const 
     }
     if (comm && n > 0)  // the split sums as 32-bit words: 8 per node
         if (int rc = apply_allgather(v, k, false, (size_t)n * 8, "ncclAllGather (sums)")) return rc;
-    for (int i = 0; i < k; ++i) {
+    int rc = KSCHED_OK;
+    for (int i = 0; i < k && !rc; ++i) {
         DeviceGuard g(v[i].c->device);
-        if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = apply_finish(v[i])) return rc;
+        rc = g.ok ? apply_finish(v[i]) : KSCHED_E_HIP;
     }
-    for (int i = 0; i < k; ++i) v[i].chg.done = true;
-    return KSCHED_OK;
+    if (rc)  // every replica is invalidated, also a rank whose own change is committed
+        for (int i = 0; i < k; ++i) v[i].chg.done = false;
+    return rc;
 }
 
 }  // namespace
@@ -2789,10 +2752,7 @@ int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindi
     if (!c->have_nodes) return KSCHED_E_STATE;
     if (p == 0) return KSCHED_OK;
     const uint32_t row_lo = 0;
-    ApplyCall x;
-    x.c = c;
-    x.hs = (hipStream_t)hip_stream;
-    x.count = p;
+    ApplyCall x{c, nullptr, (hipStream_t)hip_stream, p};
     return apply_run(&x, 1, &row_lo, &bindings, &req_cpu, &req_mem, &ok, flags, &status_out);
 } KSCHED_ABI_CATCH(c)
 
@@ -2802,11 +2762,7 @@ int ksched_apply_bindings_sharded(ksched_ctx *c, ksched_comm *q, uint32_t count,
     if (int rc = sharded_check(c, q, count, row_lo, bindings, req_cpu, req_mem, flags)) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    ApplyCall x;
-    x.c = c;
-    x.q = q;
-    x.hs = (hipStream_t)hip_stream;
-    x.count = count;
+    ApplyCall x{c, q, (hipStream_t)hip_stream, count};
     return apply_run(&x, 1, &row_lo, &bindings, &req_cpu, &req_mem, &ok, flags, &status_out);
 } KSCHED_ABI_CATCH_COMM
 
