@@ -33,6 +33,7 @@ OBJ_TOOL := tests/cpp/objects_eval
 FAKE_RCCL := tests/cpp/libfake_rccl.so
 INDEX_TEST := tests/cpp/index_tests
 PLAN_TEST := tests/cpp/plan_tests
+LAUNCH_TEST := tests/cpp/tile_launch_tests
 CHANGE_TEST := tests/cpp/snapshot_change_tests
 NODE_EVENTS_TEST := tests/cpp/node_events_tests
 SUMMARY_TEST := tests/cpp/summary_tests
@@ -62,7 +63,8 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c -o tests/cpp/hooks/test_hooks.o tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(CHANGE_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+# (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -72,6 +74,9 @@ $(INDEX_TEST): tests/cpp/index_tests.cpp $(CSRC)/tile_index.hpp
 # host-only check of the evaluation plan (csrc/eval_plan.hpp: which kernels a request runs; no GPU, no HIP header): tests/test_eval_plan_host.py runs it
 $(PLAN_TEST): tests/cpp/plan_tests.cpp $(CSRC)/eval_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/plan_tests.cpp
+# host-only check of a tile-kernel launch's description (csrc/tile_launch.hpp: LDS carve-up, launch geometry, argument fill, predicate dispatch; no GPU, no HIP runtime call): tests/test_tile_launch_host.py runs it
+$(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/tile_index.hpp $(CSRC)/eval_request.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -Wno-attributes -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/cpp/tile_launch_tests.cpp
 # host-only check of the pure parts of a snapshot change (csrc/snapshot_change.hpp: kept rows, layout decision, staging offsets, what is stale; no GPU, no HIP header): tests/test_snapshot_change_host.py runs it
 $(CHANGE_TEST): tests/cpp/snapshot_change_tests.cpp $(CSRC)/snapshot_change.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/snapshot_change_tests.cpp
@@ -122,4 +127,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(CHANGE_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

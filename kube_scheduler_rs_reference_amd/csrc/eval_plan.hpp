@@ -33,7 +33,7 @@ struct EvalFacts {
     uint32_t nkeys = 0;
     bool have_feas = false, have_fit = false, have_psel = false;  // which outputs the caller gave, and whether it gave selectors
     uint32_t tiles = 0, nlist = 0;  // the bitmap index's layout: tiles, list keys (read only where the index is known to exist)
-    // kernels_fused.hpp's answers (they need fused_lds_bytes): fused_applicable, fused_pick_applicable, fused_tile_pick_applicable
+    // kernels_fused.hpp's answers (they need the LDS carve-up, tile_launch.hpp): fused_applicable, fused_pick_applicable, fused_tile_pick_applicable
     bool fused_applicable = false, fused_pick_applicable = false, fused_tile_pick_applicable = false;
     bool bf_rows_built = false;
     uint32_t fused_waves = 0;  // kFusedWaves

@@ -30,7 +30,7 @@
 // are 128 contiguous bytes = 32 distinct banks), two pods per group: a group conflicts only when its
 // two pods read different rows of the same bank half.
 //
-// Work split (host side, run_fused): the unit is 8 pods (one phase-2 instruction).  Units are cut
+// Work split (host side, fused_geometry in tile_launch.hpp): the unit is 8 pods (one phase-2 instruction).  Units are cut
 // evenly into `chunks` pod ranges; the (chunk, tile) blocks are dealt to the 8 XCDs in contiguous
 // chunk-major runs (block id % 8 = XCD, observed dispatch order; speed only), so the 128-byte
 // segments of one pod row that adjacent tiles write meet in ONE L2 (tools/ubench3.hip: the pattern
@@ -46,6 +46,7 @@
 #include "kernarg.hpp"
 #include "kernels_direct.hpp"  // SelectArgs, select_one_pod: the sampled pick that rides in this kernel's fill (PICK)
 #include "tile_index.hpp"
+#include "tile_launch.hpp"  // kFusedThreads, the LDS carve-up, the launch geometry, the argument fill, with_predicates
 
 // Build-time variants (tools/build_variants.sh builds one library per setting for A/B timing; the shipped library
 // uses the defaults below, chosen from the measurements under profiles/):
@@ -63,15 +64,12 @@
 //                        its step 197 - 209 -> 193 us; the C4 shard 37.2 -> 36.9 us, C3 unchanged (17.4 us, steadier).  More of them loses again (every other step:
 //                        = policy 5; three in four: C3 + 0.9 us, the C5 shard + 10 us), and the odd store has to be write-through and temporal (sc1 or sc0 sc1; plain
 //                        write-back + 1.5 us at the C5 shard, nt alone nothing): sessions r8g - r8j, profiles/r06_r8g_r8j_mixed_store_policy.txt.
-//   KSCHED_FUSED_THREADS threads per block (waves x 64)
+//   KSCHED_FUSED_THREADS threads per block (waves x 64): tile_launch.hpp
 #ifndef KSCHED_STORE_POLICY
 #define KSCHED_STORE_POLICY 6
 #endif
 #ifndef KSCHED_STORE_ALT  // policy 6: which pod-row step of a round (0 .. 7) is stored without the nt hint
 #define KSCHED_STORE_ALT(it) ((it) == 7u)
-#endif
-#ifndef KSCHED_FUSED_THREADS
-#define KSCHED_FUSED_THREADS 1024
 #endif
 //   KSCHED_PROFILE       1 = diagnostics build (tools/trace_fused.py --profile): wave 0 of every block accumulates the core
 //                        cycles it spends in phase 2, in the operand wait and in phase 1, and leaves them in trace words 1..4
@@ -89,9 +87,6 @@
 #endif
 
 namespace ksched {
-
-constexpr uint32_t kFusedThreads = KSCHED_FUSED_THREADS;
-constexpr uint32_t kFusedWaves = kFusedThreads / 64;
 
 // Kernel arguments: plain scalars only (they live in SGPRs; keep this small).
 struct FusedArgs {
@@ -117,47 +112,6 @@ struct FusedArgs {
     uint32_t off_pf;                // LDS byte offset of the 256-byte dump area of the operand prefetch, or 0xFFFFFFFF: no room, no prefetch
     uint64_t *trace;  // diagnostics: per-block phase timestamps (100 MHz), or nullptr
 };
-
-// LDS carve-up: [rows * 128 : bitmap rows][aux block: 2 search trees + 2 cnt tables (FIT)]
-//               per wave x 64 pods: [16 B fit record (FIT)][16 B label rows 1..8 (SEL)][8 B taint rows (TAINT)]
-//               [nlist * 6 KiB: the tile's list keys][per wave x 64 pods: 16 B list record]   (snapshots with list keys only)
-constexpr uint32_t kPickAttempts = 5;  // draws per pod the tile-test pick (PICK == 2) handles: ATTEMPTS of src/main.rs:49
-constexpr uint32_t kPickParkBytes = kFusedWaves * kPickAttempts * 64u * 4u;
-constexpr uint32_t kPrefetchDumpBytes = 256u;  // one dword per lane: where the operand prefetch's LDS-DMA loads land (shared by the block's waves: nobody reads it)
-inline uint32_t fused_lds_bytes(const IndexedLayout &l, bool fit, bool sel, bool taint, FusedArgs *a = nullptr, bool park = false) {
-    uint32_t off = l.rows * 128u;
-    const uint32_t off_aux = off;
-    if (fit) off += kAuxWords * 8u;
-    const uint32_t off_fit = off;
-    if (fit) off += kFusedWaves * 64u * 16u;
-    const uint32_t off_lab = off;
-    if (sel) off += kFusedWaves * 64u * 16u;
-    const uint32_t off_trow = off;
-    if (taint) off += kFusedWaves * 64u * 8u;
-    const uint32_t off_list = off;
-    if (sel && l.nlist) off += l.nlist * kListBytes;
-    const uint32_t off_lrec = off;
-    if (sel && l.nlist) off += kFusedWaves * 64u * kListRecBytes;
-    const uint32_t off_park = off;
-    if (park) off += kPickParkBytes;
-    // the operand prefetch's dump area: only where it fits (it never decides whether the fused kernel applies)
-    uint32_t off_pf = 0xFFFFFFFFu;
-    if (off + kPrefetchDumpBytes <= kLdsBudget) {
-        off_pf = off;
-        off += kPrefetchDumpBytes;
-    }
-    if (a) {
-        a->off_pf = off_pf;
-        a->off_park = off_park;
-        a->off_list = off_list;
-        a->off_lrec = off_lrec;
-        a->off_aux = off_aux;
-        a->off_fit = off_fit;
-        a->off_lab = off_lab;
-        a->off_trow = off_trow;
-    }
-    return off;
-}
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
@@ -1126,23 +1080,19 @@ inline hipError_t launch_fused_t(bool want_fit, bool list, const FusedLaunch &q,
 }
 
 // can this request's sampled pick ride in the fused launch?  (plain variants only: no second mask, no list keys)
-inline bool fused_pick_applicable(const IndexedSnapshot &s, uint32_t flags, bool want_fit, uint32_t p) {
-    const bool list = (flags & KSCHED_SEL) && s.lay.nkeys && s.lay.nlist > 0;
-    return s.built && !want_fit && !list && p < (1u << 31);
+inline bool fused_pick_applicable(const IndexedSnapshot &s, const TileTerms &t, uint32_t p) {
+    return s.built && !t.want_fit && !t.list && p < (1u << 31);
 }
 // ... and as the tile-test form (PICK == 2)?  ATTEMPTS draws per pod, the reference's two predicates, at most eight label keys
 // (a pod's selector then fits the eight slots of its record), and room in LDS for the per-wave park of the draws
-inline bool fused_tile_pick_applicable(const IndexedSnapshot &s, uint32_t flags, uint32_t attempts, bool have_psel) {
-    const IndexedLayout &l = s.lay;
-    if (attempts != kPickAttempts || ((flags & KSCHED_TAINT) && l.ngroups)) return false;
-    const bool sel = (flags & KSCHED_SEL) && have_psel && l.nkeys;
-    if (sel && l.nkeys > 8u) return false;
-    return fused_lds_bytes(l, flags & KSCHED_FIT, sel, false, nullptr, true) <= kLdsBudget;
+inline bool fused_tile_pick_applicable(const IndexedLayout &l, const TileTerms &t, uint32_t attempts) {
+    if (attempts != kPickAttempts || t.taint) return false;
+    if (t.sel && l.nkeys > 8u) return false;
+    return tile_lds_layout(l, lds_want(t, true)).bytes <= kLdsBudget;
 }
 
-inline bool fused_applicable(const IndexedSnapshot &s, uint32_t flags) {
-    if (!s.built) return false;
-    return fused_lds_bytes(s.lay, flags & KSCHED_FIT, (flags & KSCHED_SEL) && s.lay.nkeys, (flags & KSCHED_TAINT) && s.lay.ngroups) <= kLdsBudget;
+inline bool fused_applicable(const IndexedSnapshot &s, const TileTerms &t) {
+    return s.built && tile_lds_layout(s.lay, lds_want(t, false)).bytes <= kLdsBudget;
 }
 
 // what a fused launch takes besides the request
@@ -1160,103 +1110,38 @@ struct FusedOptions {
 
 // out_feas: where the feasible mask goes (the request's, or the caller's scratch one)
 inline hipError_t run_fused(const IndexedSnapshot &s, const EvalRequest &r, uint64_t *out_feas, const FusedOptions &o) {
-    const uint32_t p = r.p, debug = o.debug;
     const SelectArgs *const pick = o.pick;
     const IndexedLayout &l = s.lay;
+    const TileTerms t = tile_terms(r, l);
+    const bool tile_pick = pick && o.pick_form == 2;
+    const TileLds lds = tile_lds_layout(l, lds_want(t, tile_pick));
+    const FusedGeometry g = fused_geometry({r.p, l.tiles, lds.bytes, pick != nullptr, o.grid_cus, o.round_order, o.debug});
     FusedArgs a{};
+    fill_tile_args(a, s, lds, t, r);
     a.W = l.W;
     a.pitch = r.pitch;
-    a.tiles = l.tiles;
-    a.rows = l.rows;
-    a.nkeys = l.nkeys;
-    a.ngroups = l.ngroups;
-    a.row_zero = l.row_zero;
-    a.row_valid = l.row_valid;
-    a.row_cpu = l.row_cpu;
     a.row_mem = l.row_mem;
-    a.row_taint = l.row_taint;
-    for (int k = 0; k < 8; ++k) {
-        const bool is_list = l.lab_base[k] == kLabList;  // no rows: phase 1 skips the column (list_mask8)
-        a.lab_off[k] = is_list ? 0u : (l.lab_base[k] - 1u) * 128u;  // id s -> row lab_base + s - 1 (ids start at 1; keys without rows never match s != 0 below nkeys)
-        a.lab_mx1[k] = is_list ? 0u : l.lab_max[k] + 1u;
-    }
-    a.lab_meta = s.d_lab_meta;
-    a.zero64 = reinterpret_cast<const uint64_t *>(s.d_lab_meta + 64);
-    a.p = p;
-    a.units = (p + 7u) / 8u;
-    a.debug = debug;
-    a.has_tol = r.ptol != nullptr ? 1u : 0u;
-    const bool do_fit = r.fit();
-    const bool do_sel = r.sel(l.nkeys);
-    const bool do_taint = r.taint(l.ngroups != 0);  // (the layout's taint groups, not the snapshot's have_taints)
-    const bool tile_pick = pick && o.pick_form == 2;
-    const uint32_t lds = fused_lds_bytes(l, do_fit, do_sel, do_taint, &a, tile_pick);
+    a.units = g.units;
+    a.chunks = g.chunks;
+    a.run = g.run;
+    a.unit_q = g.unit_q;
+    a.unit_rem = g.unit_rem;
+    a.tiles_rcp = g.tiles_rcp;
+    a.wave_major = g.wave_major;
+    a.u_stride = g.u_stride;
+    a.debug = o.debug;
+    a.pick_ppb = g.pick_ppb;
+    a.pick_waves = g.pick_waves;
     a.pick_acc = o.pick_acc;
-
-    // chunks: as many pod ranges as keep every block resident at once (256 CUs x blocks per CU), but no
-    // more than one round (64 pods) per wave needs.
-    const uint32_t blocks_per_cu = std::max(1u, std::min(kLdsBudget / lds, 2048u / kFusedThreads));
-    const uint32_t rounds = (a.units + 7u) / 8u;
-    // chunks that give every wave one round; small batches whose pick rides along are cut finer (a block's time is its fill plus
-    // ONE round either way, and the pick's pods spread over more CUs).  debug bits 18-19: A/B of that divisor (0: default).
-    uint32_t per_block = kFusedWaves;
-    if (pick) per_block = 4u;
-    if (((debug >> 18) & 3u) == 1u) per_block = kFusedWaves;
-    if (((debug >> 18) & 3u) == 2u) per_block = 4u;
-    if (((debug >> 18) & 3u) == 3u) per_block = 1u;
-    const uint32_t want = (rounds + per_block - 1u) / per_block;
-    // grid_cus (KSCHED_OPT_GRID_CUS): the launch keeps to that many compute units, so that the launches of the FOLLOWING batches
-    // (other streams) find free ones and fill while this one stores; 0 = the whole chip
-    const uint32_t cus = o.grid_cus ? std::min(256u, o.grid_cus) : 256u;
-    a.chunks = std::max(1u, std::min((cus * blocks_per_cu) / l.tiles, want));
-    // Interleaved orders, launches of TWO rounds per wave (C3: 1 563 rounds over 51 x 16 waves): the launch lasts as long as its two-round waves, and
-    // at the largest resident chunk count one wave in twelve has only one -- the smallest chunk count that still needs no third round (49: 784 waves x 2
-    // rounds) fills fewer blocks for the same two rounds: step 18.05 -> 17.6 us (sweep of 44 .. 51 chunks, session r7i: 18.43 18.25 17.94 17.91 17.77
-    // 17.6 17.8 18.05).  Longer launches are bound by their stores, not by the quantisation, and want every compute unit (session r7k, even / largest
-    // chunk count: 150 k pods 23.5 / 23.3 us, 300 k 43.3 / 40.0, 400 k 55.7 / 52.4); one-round launches keep the finer cut (a riding pick's pods spread wider).
-    if (o.round_order != 1 && !(debug & 0x80000000u)) {  // (debug bit 31: the largest resident chunk count, the A/B of this rule)
-        const uint32_t streams = a.chunks * kFusedWaves;
-        const uint32_t per_wave = (rounds + streams - 1u) / streams;
-        if (per_wave == 2u) a.chunks = std::max(1u, std::min(a.chunks, (rounds + 2u * kFusedWaves - 1u) / (2u * kFusedWaves)));
-    }
-    a.unit_q = a.units / a.chunks;
-    a.unit_rem = a.units % a.chunks;
-    // KSCHED_OPT_ROUND_ORDER: 0 = interleaved, wave-major (default); 1 = blocked; 2 = interleaved, chunk-major
-    a.u_stride = o.round_order == 1 ? 8u : a.chunks * kFusedWaves * 8u;
-    a.wave_major = o.round_order == 2 ? 0u : 1u;
-    a.tiles_rcp = (uint32_t)std::min<uint64_t>((1ull << 32) / l.tiles, 0xFFFFFFFFull);
-    const uint32_t total = a.chunks * l.tiles;
-    a.run = (total + 7u) / 8u;
-    const dim3 grid((debug & 32u) ? total : a.run * 8u);
-    a.trace = (o.trace && grid.x <= o.trace_blocks) ? o.trace : nullptr;
-    const bool want_fit = r.want_fit();
-    const int sel = do_sel ? 1 : 0, tnt = do_taint ? 1 : 0, fit = do_fit ? 1 : 0;
-    const bool list = do_sel && l.nlist > 0;
-    if (pick && (want_fit || list)) return hipErrorInvalidValue;  // (the caller checks fused_pick_applicable first: a pick is never dropped silently)
-    if (tile_pick && (!o.pick_acc || do_taint || (do_sel && l.nkeys > 8u) || pick->attempts != kPickAttempts || lds > kLdsBudget)) return hipErrorInvalidValue;
-    if (pick) {
-        a.pick_ppb = (p + total - 1u) / total;
-        a.pick_waves = std::max(1u, std::min(8u, (a.pick_ppb + 63u) / 64u));
-    }
-    const FusedLaunch q{grid, lds, r.stream, &s, r.pcpu, r.pmem, r.psel, r.ptol, out_feas, r.out_fit, o.ev_start, o.ev_stop, pick, o.pick_form};
-    a.nlist = list ? l.nlist : 0u;
-    a.list_mask8 = 0;
-    for (uint32_t j = 0; j < a.nlist; ++j) {
-        a.list_col[j] = l.list_col[j];
-        if (l.list_col[j] < 8u) a.list_mask8 |= 1u << l.list_col[j];
-    }
-#define KSCHED_FUSED_CASE(F, S, T) return launch_fused_t<F, S, T>(want_fit, list, q, a)
-    switch (fit * 4 + sel * 2 + tnt) {
-        case 0: KSCHED_FUSED_CASE(false, false, false);
-        case 1: KSCHED_FUSED_CASE(false, false, true);
-        case 2: KSCHED_FUSED_CASE(false, true, false);
-        case 3: KSCHED_FUSED_CASE(false, true, true);
-        case 4: KSCHED_FUSED_CASE(true, false, false);
-        case 5: KSCHED_FUSED_CASE(true, false, true);
-        case 6: KSCHED_FUSED_CASE(true, true, false);
-        default: KSCHED_FUSED_CASE(true, true, true);
-    }
-#undef KSCHED_FUSED_CASE
+    a.off_park = lds.off_park;
+    a.off_pf = lds.off_pf;
+    a.trace = (o.trace && g.grid <= o.trace_blocks) ? o.trace : nullptr;
+    if (pick && (t.want_fit || t.list)) return hipErrorInvalidValue;  // (the caller checks fused_pick_applicable first: a pick is never dropped silently)
+    if (tile_pick && (!o.pick_acc || !fused_tile_pick_applicable(l, t, pick->attempts))) return hipErrorInvalidValue;
+    const FusedLaunch q{dim3(g.grid), lds.bytes, r.stream, &s, r.pcpu, r.pmem, r.psel, r.ptol, out_feas, r.out_fit, o.ev_start, o.ev_stop, pick, o.pick_form};
+    return with_predicates(t.fit, t.sel, t.taint, [&](auto F, auto S, auto T) {
+        return launch_fused_t<decltype(F)::value, decltype(S)::value, decltype(T)::value>(t.want_fit, t.list, q, a);
+    });
 }
 
 }  // namespace ksched

@@ -29,8 +29,9 @@
 
 #include "eval_request.hpp"
 #include "kernarg.hpp"
-#include "kernels_fused.hpp"  // kFusedThreads, u32x4
+#include "kernels_fused.hpp"  // u32x4
 #include "tile_index.hpp"
+#include "tile_launch.hpp"  // kFusedThreads, the LDS carve-up (every region), the launch geometry, the argument fill, with_predicates
 
 namespace ksched {
 
@@ -53,36 +54,6 @@ struct SummaryArgs {
     uint32_t has_tol;
     uint32_t atomic;                  // cross-tile combine: 0 = partial words + k_summary_reduce, 1 = atomic adds into out_counts
 };
-
-// LDS carve-up: [rows * 128 : bitmap rows][aux block][per wave x 64 pods: 16 B fit record][16 B label rows 1..8][8 B taint rows]
-//               [nlist * 6 KiB: the tile's list keys][per wave x 64 pods: 8 B list record]
-// Every region is there whatever the predicates: a pod's fit and label records take its lanes' packed counts afterwards.
-// indexed_plan (tile_index.hpp) has checked exactly this sum against the LDS budget, so every indexed snapshot fits.
-inline uint32_t summary_lds_bytes(const IndexedLayout &l, SummaryArgs *a = nullptr) {
-    uint32_t off = l.rows * 128u;
-    const uint32_t off_aux = off;
-    off += kAuxWords * 8u;
-    const uint32_t off_fit = off;
-    off += kSummaryWaves * 64u * 16u;
-    const uint32_t off_lab = off;
-    off += kSummaryWaves * 64u * 16u;
-    const uint32_t off_trow = off;
-    off += kSummaryWaves * 64u * 8u;
-    const uint32_t off_list = off;
-    off += l.nlist * kListBytes;
-    const uint32_t off_lrec = off;
-    if (l.nlist) off += kSummaryWaves * 64u * kListRecBytes;
-    if (a) {
-        a->off_aux = off_aux;
-        a->off_fit = off_fit;
-        a->off_lab = off_lab;
-        a->off_trow = off_trow;
-        a->off_list = off_list;
-        a->off_lrec = off_lrec;
-    }
-    return off;
-}
-static_assert(kSummaryWaves * 64u * 40u == 1024u * 40u, "the per-pod records are what kLdsNonRowBytesMax reserves");
 
 __device__ __forceinline__ uint32_t popc4(const u32x4 v, uint32_t acc = 0u) {
     return __popc(v.x) + (__popc(v.y) + (__popc(v.z) + (__popc(v.w) + acc)));
@@ -419,7 +390,8 @@ inline hipError_t launch_summary_k(const SummaryLaunch &q, const SummaryArgs &a)
     return hipGetLastError();
 }
 
-inline bool summary_indexed_applicable(const IndexedSnapshot &s) { return s.built && summary_lds_bytes(s.lay) <= kLdsBudget; }
+// (true of every indexed snapshot: tile_launch.hpp's static_assert on what indexed_plan has checked)
+inline bool summary_indexed_applicable(const IndexedSnapshot &s) { return s.built && tile_lds_layout(s.lay, kLdsEveryRegion).bytes <= kLdsBudget; }
 
 // words of ctx-owned scratch the partial form needs
 inline size_t summary_partial_words(const IndexedSnapshot &s, uint32_t p) { return (size_t)s.lay.tiles * p; }
@@ -429,66 +401,30 @@ inline size_t summary_partial_words(const IndexedSnapshot &s, uint32_t p) { retu
 inline hipError_t run_summary_indexed(const IndexedSnapshot &s, const EvalRequest &r, uint32_t *out, uint64_t *partial, bool atomic) {
     const IndexedLayout &l = s.lay;
     const uint32_t p = r.p;
-    const hipStream_t stream = r.stream;
+    const TileTerms t = tile_terms(r, l);
+    const TileLds lds = tile_lds_layout(l, kLdsEveryRegion);
+    if (lds.bytes > kLdsBudget) return hipErrorInvalidValue;
+    const SummaryGeometry g = summary_geometry(p, l.tiles, lds.bytes);
     SummaryArgs a{};
+    fill_tile_args(a, s, lds, t, r);
     a.n = l.n;
-    a.p = p;
-    a.tiles = l.tiles;
-    a.rows = l.rows;
-    a.nkeys = l.nkeys;
-    a.ngroups = l.ngroups;
-    a.row_zero = l.row_zero;
-    a.row_valid = l.row_valid;
-    a.row_cpu = l.row_cpu;
-    a.row_taint = l.row_taint;
-    for (int k = 0; k < 8; ++k) {
-        const bool is_list = l.lab_base[k] == kLabList;
-        a.lab_off[k] = is_list ? 0u : (l.lab_base[k] - 1u) * 128u;
-        a.lab_mx1[k] = is_list ? 0u : l.lab_max[k] + 1u;
-    }
-    a.lab_meta = s.d_lab_meta;
-    a.zero64 = reinterpret_cast<const uint64_t *>(s.d_lab_meta + 64);
-    a.has_tol = r.ptol != nullptr ? 1u : 0u;
+    a.chunks = g.chunks;
+    a.rounds = g.rounds;
     a.atomic = atomic ? 1u : 0u;
-    const bool do_fit = r.fit();
-    const bool do_sel = r.sel(l.nkeys);
-    const bool do_taint = r.taint(l.ngroups != 0);
-    const bool list = do_sel && l.nlist > 0;
-    const uint32_t lds = summary_lds_bytes(l, &a);
-    if (lds > kLdsBudget) return hipErrorInvalidValue;
-    a.nlist = list ? l.nlist : 0u;
-    for (uint32_t j = 0; j < a.nlist; ++j) {
-        a.list_col[j] = l.list_col[j];
-        if (l.list_col[j] < 8u) a.list_mask8 |= 1u << l.list_col[j];
-    }
-    // blocks per tile: as many as the chip holds at once (a block fills a compute unit's LDS), no more than one round per wave needs
-    a.rounds = (p + 63u) / 64u;
-    const uint32_t blocks_per_cu = std::max(1u, std::min(kLdsBudget / lds, 2048u / kSummaryThreads));
-    a.chunks = std::max(1u, std::min((256u * blocks_per_cu) / l.tiles, (a.rounds + kSummaryWaves - 1u) / kSummaryWaves));
-    const SummaryLaunch q{&s, r.pcpu, r.pmem, r.psel, r.ptol, partial, out, dim3(a.chunks * l.tiles), lds, stream};
+    const SummaryLaunch q{&s, r.pcpu, r.pmem, r.psel, r.ptol, partial, out, dim3(g.grid), lds.bytes, r.stream};
     hipError_t e;
     if (atomic) {
         if (reinterpret_cast<uintptr_t>(out) & 7u) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_summary_zero, dim3((2u * p + 255u) / 256u), dim3(256), 0, stream, reinterpret_cast<unsigned long long *>(out), p);
+        hipLaunchKernelGGL(k_summary_zero, dim3((2u * p + 255u) / 256u), dim3(256), 0, r.stream, reinterpret_cast<unsigned long long *>(out), p);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-#define KSCHED_SUMMARY_CASE(F, S, T)                                 \
-    e = (S && list) ? launch_summary_k<F, S, T, S>(q, a) : launch_summary_k<F, S, T, false>(q, a); \
-    break
-    switch ((do_fit ? 4 : 0) + (do_sel ? 2 : 0) + (do_taint ? 1 : 0)) {
-        case 0: KSCHED_SUMMARY_CASE(false, false, false);
-        case 1: KSCHED_SUMMARY_CASE(false, false, true);
-        case 2: KSCHED_SUMMARY_CASE(false, true, false);
-        case 3: KSCHED_SUMMARY_CASE(false, true, true);
-        case 4: KSCHED_SUMMARY_CASE(true, false, false);
-        case 5: KSCHED_SUMMARY_CASE(true, false, true);
-        case 6: KSCHED_SUMMARY_CASE(true, true, false);
-        default: KSCHED_SUMMARY_CASE(true, true, true);
-    }
-#undef KSCHED_SUMMARY_CASE
+    e = with_predicates(t.fit, t.sel, t.taint, [&](auto F, auto S, auto T) {
+        constexpr bool kF = decltype(F)::value, kS = decltype(S)::value, kT = decltype(T)::value;
+        return (kS && t.list) ? launch_summary_k<kF, kS, kT, kS>(q, a) : launch_summary_k<kF, kS, kT, false>(q, a);
+    });
     if (e != hipSuccess) return e;
     if (!atomic) {
-        hipLaunchKernelGGL(k_summary_reduce, dim3((p + 255u) / 256u), dim3(256), 0, stream, partial, out, p, l.tiles, l.n,
+        hipLaunchKernelGGL(k_summary_reduce, dim3((p + 255u) / 256u), dim3(256), 0, r.stream, partial, out, p, l.tiles, l.n,
                            (reinterpret_cast<uintptr_t>(out) & 15u) ? 0u : 1u);
         e = hipGetLastError();
     }

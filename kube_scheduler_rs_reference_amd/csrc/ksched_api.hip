@@ -769,13 +769,9 @@ int run_direct(ksched_ctx *c, const EvalRequest &r, uint64_t *out_feas) {
     a.key0 = 0;
     a.nkeys = sel ? std::min(c->nkeys, (uint32_t)kDirectKeys) : 0;
     a.accumulate = 0;
-    if (sel) {
-        if (taint) launch_direct_t<true, true>(q, a, grid, want_fit, s);
-        else launch_direct_t<true, false>(q, a, grid, want_fit, s);
-    } else {
-        if (taint) launch_direct_t<false, true>(q, a, grid, want_fit, s);
-        else launch_direct_t<false, false>(q, a, grid, want_fit, s);
-    }
+    // (the fit term is a kernel argument here, not an instantiation.  The two terms go in negated: the instantiations are then first named
+    // <true, true> ... <false, false>, the order in which the code object has always carried these kernels -- tools/same_device_code.py)
+    with_predicates(false, !sel, !taint, [&](auto, auto NS, auto NT) { launch_direct_t<!decltype(NS)::value, !decltype(NT)::value>(q, a, grid, want_fit, s); });
     // further passes: 8 more keys each, ANDed into the feasible mask
     if (sel && out_feas) {
         for (uint32_t k0 = kDirectKeys; k0 < c->nkeys; k0 += kDirectKeys) {
@@ -1136,9 +1132,10 @@ EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
     f.have_psel = r.psel != nullptr;
     f.tiles = c->idx.lay.tiles;
     f.nlist = c->idx.lay.nlist;
-    f.fused_applicable = fused_applicable(c->idx, r.flags);
-    f.fused_pick_applicable = fused_pick_applicable(c->idx, r.flags, r.want_fit(), r.p);
-    f.fused_tile_pick_applicable = fused_tile_pick_applicable(c->idx, r.flags, r.attempts, r.psel != nullptr);
+    const TileTerms t = tile_terms(r, c->idx.lay);
+    f.fused_applicable = fused_applicable(c->idx, t);
+    f.fused_pick_applicable = fused_pick_applicable(c->idx, t, r.p);
+    f.fused_tile_pick_applicable = fused_tile_pick_applicable(c->idx.lay, t, r.attempts);
     f.bf_rows_built = c->bf_rows_built;
     f.fused_waves = kFusedWaves;
     f.opt_kernel = c->opt_kernel;

@@ -56,8 +56,9 @@ constexpr uint32_t kLdsBudget = 160u * 1024u;
 // per-tile "aux" block (global image = LDS image): [tree cpu][tree mem][cnt cpu][cnt mem], 8-byte words
 constexpr uint32_t kAuxTreeWords = kTileNodes;
 constexpr uint32_t kAuxWords = 2u * kAuxTreeWords + 2u * kCntEntries;  // 4100 words = 32800 bytes
-// LDS the kernel needs besides the bitmap rows: the aux block and up to 40 bytes of per-pod records for
-// 16 waves x 64 pods (kernels_fused.hpp: fused_lds_bytes)
+// LDS the kernels need besides the bitmap rows: the aux block and up to 40 bytes of per-pod records for 16 waves x 64 pods, and
+// per list key the tile's list plus once the pods' list records.  The carve-up itself is tile_lds_layout (tile_launch.hpp), which
+// is static_asserted to come to exactly this with every region present.
 constexpr uint32_t kLdsNonRowBytesMax = kAuxWords * 8u + 1024u * 40u;
 // High-cardinality label keys (e.g. kubernetes.io/hostname: one value per node) do not get one bitmap row per value -- 5000
 // values x 128 B would not fit any LDS.  Such a key is kept per tile as a LIST instead: the tile's nodes sorted by the key's
@@ -68,6 +69,7 @@ constexpr uint32_t kMaxListKeys = 2;
 constexpr uint32_t kListBytes = kTileNodes * 4u + kTileNodes * 2u;  // per (tile, list key): 6 KiB
 constexpr uint32_t kListRecBytes = 8u;                              // per pod of a round: kMaxListKeys x (first entry u16 | count u16)
 constexpr uint32_t kLabList = 0xFFFFFFFFu;                          // lab_base of a list key
+constexpr uint32_t lds_non_row_bytes(uint32_t nlist) { return kLdsNonRowBytesMax + nlist * kListBytes + (nlist ? 1024u * kListRecBytes : 0u); }
 
 struct IndexedLayout {
     uint32_t n, W, tiles, rows, nkeys, ngroups;
@@ -180,8 +182,7 @@ inline bool indexed_plan(IndexedLayout &l, uint32_t n, uint32_t nkeys, const uin
         uint64_t label_rows = 0;
         for (uint32_t k = 0; k < nkeys; ++k)
             if (!is_list[k]) label_rows += (uint64_t)lab_max[k] + 1u;  // + the key's all-zero row (ids above the max clamp to it)
-        const uint64_t lds = (r + label_rows + 2u * kFitRows) * 128u + kLdsNonRowBytesMax + (uint64_t)l.nlist * kListBytes +
-                             (l.nlist ? 1024u * kListRecBytes : 0u);
+        const uint64_t lds = (r + label_rows + 2u * kFitRows) * 128u + lds_non_row_bytes(l.nlist);
         if (lds <= kLdsBudget && (r + label_rows) * 128u <= 65536u) break;
         if (l.nlist == kMaxListKeys) {
             *why = "more than two high-cardinality label keys: their (key, value) rows exceed the LDS budget of the fused kernel";

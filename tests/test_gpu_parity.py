@@ -423,6 +423,55 @@ def test_pitched_device_masks(evaluator, kernel, P, N):
     ev.set_kernel("auto")
 
 
+_CHUNK_RULE = {}
+
+
+def _chunk_rule_case():
+    """One 50-tile cluster for the sizes below and its oracle result, computed once: a pod's mask row and binding depend on that pod alone,
+    so the first P pods of the largest batch are the batch of P pods."""
+    if not _CHUNK_RULE:
+        c = synth.make_cluster(10_241, 50_200, n_keys=8, n_taints=0, seed=50_200)
+        flags = FIT | SEL | PICK_SAMPLED
+        feas, _, bind = capi.eval_encoded(c.avail_cpu, c.avail_mem, c.node_labels, None, c.req_cpu, c.req_mem, np.ascontiguousarray(c.pod_sel), None,
+                                          np.ascontiguousarray(c.samples), flags)
+        _CHUNK_RULE.update(c=c, flags=flags, feas=feas, bind=bind)
+    return _CHUNK_RULE
+
+
+@pytest.mark.parametrize("P", [5_120, 5_121, 10_240, 10_241])
+def test_chunk_count_rule_at_fifty_tiles(evaluator, P):
+    """The chunk-count rule of the fused launch (tile_launch.hpp, fused_geometry) at a size that runs in seconds: 50 200 nodes = 50 tiles, the last
+    one partial; a block fills a compute unit, so 5 chunks are resident = 80 streams of 64 pods.  5 120 pods: one round per wave; 5 121: two rounds,
+    the rule cuts 5 chunks to 3; 10 240: two rounds, the rule leaves 5; 10 241: three rounds, rule off.  With the rule and with KSCHED_OPT_DEBUG
+    bit 31 (the largest resident chunk count): the fused kernel ran, every mask word and binding identical between the two, and == the oracle."""
+    import torch
+    k = _chunk_rule_case()
+    c, flags = k["c"], k["flags"]
+    ev = evaluator
+    dev = torch.device("cuda", ev.device)
+    ev.set_nodes(**c.node_columns())
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+    d_cpu, d_mem, d_sel, d_smp = t(c.req_cpu[:P], np.int64), t(c.req_mem[:P], np.int64), t(c.pod_sel[:, :P], np.int32), t(c.samples[:P], np.int32)
+    ev.set_kernel("auto")
+    out = []
+    try:
+        for dbg in (0, 0x80000000):
+            ev.set_option(_lib.OPT_DEBUG, dbg)
+            feas = ev.alloc_mask(P, pitched=True)
+            bind = torch.full((P,), -7, dtype=torch.int32, device=dev)
+            ev.eval_device(d_cpu, d_mem, d_sel, None, d_smp, flags, out_feasible=feas, out_binding=bind)
+            torch.cuda.synchronize()
+            assert ev.last_kernel == "fused", ev.last_kernel
+            out.append((feas, bind))
+    finally:
+        ev.set_option(_lib.OPT_DEBUG, 0)
+    assert torch.equal(out[0][0], out[1][0]), "the mask differs with the chunk-count rule on / off"
+    assert torch.equal(out[0][1], out[1][1]), "the bindings differ with the chunk-count rule on / off"
+    for feas, bind in out:
+        assert np.array_equal(feas.contiguous().cpu().numpy().view(np.uint64), k["feas"][:P])
+        assert np.array_equal(bind.cpu().numpy(), k["bind"][:P])
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("count", [1, 7, 200])
 def test_update_nodes_matches_fresh_snapshot(evaluator, kernel, count):
