@@ -37,6 +37,8 @@ LAUNCH_TEST := tests/cpp/tile_launch_tests
 CHANGE_TEST := tests/cpp/snapshot_change_tests
 NODE_EVENTS_TEST := tests/cpp/node_events_tests
 SUMMARY_TEST := tests/cpp/summary_tests
+UNIFORM_PLAN_TEST := tests/cpp/uniform_plan_tests
+UNIFORM_PICK_TEST := tests/cpp/uniform_pick_tests
 
 PMC_CALIB := tools/pmc_calib
 
@@ -64,7 +66,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
 # (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -80,6 +82,9 @@ $(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/
 # host-only check of the pure parts of a snapshot change (csrc/snapshot_change.hpp: kept rows, layout decision, staging offsets, what is stale; no GPU, no HIP header): tests/test_snapshot_change_host.py runs it
 $(CHANGE_TEST): tests/cpp/snapshot_change_tests.cpp $(CSRC)/snapshot_change.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/snapshot_change_tests.cpp
+# host-only check of the plan of a KSCHED_PICK_UNIFORM request (csrc/eval_plan.hpp; no GPU, no HIP header): tests/test_uniform_plan_host.py runs it
+$(UNIFORM_PLAN_TEST): tests/cpp/uniform_plan_tests.cpp $(CSRC)/eval_plan.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/uniform_plan_tests.cpp
 $(LIB_HOST): $(HOST_SRCS) $(HOST_HDRS) $(LIB_HIP)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRCS) -L$(PKG) -lksched_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 # C++ tests of the host mirror (tests/cpp/host_tests.cpp; driven by tests/test_host_mirror.py)
@@ -93,6 +98,10 @@ $(NODE_EVENTS_TEST): tests/cpp/node_events_tests.cpp $(LIB_HOST) $(HOST_HDRS)
 # C++ tests of explain_unschedulable / format_unschedulable / Context::explain_no_node_found (tests/cpp/summary_tests.cpp; driven by tests/test_summary_host.py)
 $(SUMMARY_TEST): tests/cpp/summary_tests.cpp tests/cpp/json_min.hpp $(LIB_HOST) $(HOST_HDRS)
 	$(CXX) $(CXXFLAGS) -o $@ tests/cpp/summary_tests.cpp -L$(PKG) -lksched_host -lksched_hip -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread
+
+# C++ tests of Context::pick_uniform (tests/cpp/uniform_pick_tests.cpp; driven by tests/test_uniform_host.py)
+$(UNIFORM_PICK_TEST): tests/cpp/uniform_pick_tests.cpp tests/cpp/json_min.hpp $(LIB_HOST) $(HOST_HDRS) $(FAKE_RCCL) $(LIB_HIP_TEST)
+	$(CXX) $(CXXFLAGS) -o $@ tests/cpp/uniform_pick_tests.cpp -L$(PKG) -lksched_host -lksched_hip -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread
 
 # objects JSON -> host encoder -> device, printed for the Python parity tests (tests/test_gpu_objects.py)
 $(OBJ_TOOL): tests/cpp/objects_eval.cpp tests/cpp/json_min.hpp $(LIB_HOST) $(HOST_HDRS)
@@ -127,4 +136,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

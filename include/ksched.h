@@ -20,6 +20,7 @@
  *   select_node_for_pod    src/main.rs:49-71             KSCHED_PICK_SAMPLED (injected sample indices), ksched_pick_device
  *   (extension E1, BASELINE.json config 5)               KSCHED_PICK_BESTFIT
  *   (extension E2, BASELINE.json config 5)               KSCHED_TAINT
+ *   (extension E3: the batch holds every pod's whole row)  KSCHED_PICK_UNIFORM
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -80,6 +81,23 @@ extern "C" {
 #define KSCHED_PICK_SAMPLED 0x08u  /* first feasible of the injected samples, else -1 */
 #define KSCHED_PICK_BESTFIT 0x10u  /* lexicographic min (mem residual, cpu residual, node) (extension E1) */
 #define KSCHED_WANT_FIT_MASK 0x20u /* also write the fit-only mask (to rebuild InvalidNodeReason) */
+/* KSCHED_PICK_UNIFORM (extension E3): uniformly among the pod's feasible nodes; -1 only when it has none.  At most one KSCHED_PICK_*
+ * flag per call.  Added in ABI 7 without a version change and without a new symbol: detect it by this constant and its behaviour.
+ *   draw    : ONE injected 32-bit draw per pod, u = samples[pod * attempts + 0], 1 <= attempts <= KSCHED_MAX_ATTEMPTS; the other entries
+ *             of the pod's row are not read (the same [p][5] table serves either pick).  Here a draw is a number, not a node index.
+ *   result  : c = set bits of the pod's feasible row over nodes [0, n).  c == 0: binding -1.  Otherwise k = (uint64(u) * c) >> 32 and the
+ *             binding is the index of the k-th set bit (0-based, ascending node index).
+ *   exact   : integer arithmetic only -- same inputs, same bits, on every run.  u = 0 gives the lowest feasible node, u = 0xFFFFFFFF the
+ *             highest.  For uniform u every feasible node is chosen with probability floor or ceil of 2^32 / c over 2^32: a bias below c / 2^32.
+ *   ignored : bits at or beyond n in a row's last word and the words [W, pitch) are never counted and never chosen -- also in the masks a
+ *             caller hands to ksched_pick_device / ksched_pick.
+ *   n == 0 gives -1 for every pod; p == 0 is a no-op.
+ * Accepted, with identical results, by ksched_eval, ksched_eval_begin / ksched_eval_end, ksched_eval_device, ksched_eval_device_pitched,
+ * ksched_pick_device, ksched_pick and ksched_pipe_submit (ksched_summarize* takes no pick flag).  KSCHED_E_INVAL for two pick flags at
+ * once, out_binding == NULL, samples == NULL with p > 0, attempts == 0 or above the maximum.  The pick always reads the mask, behind the
+ * mask kernel: a request without out_feasible evaluates into the ctx's scratch mask, ksched_pipe_submit takes its
+ * split route with events, and KSCHED_OPT_PICK_FROM_MASK / KSCHED_OPT_FUSED_PICK have no effect on it.  ksched_last_pick: "uniform". */
+#define KSCHED_PICK_UNIFORM 0x40u
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0
@@ -293,6 +311,7 @@ uint32_t ksched_num_keys(const ksched_ctx *ctx);
  *   tolerations   : [p] or NULL (= tolerate nothing)        -- only read with KSCHED_TAINT
  *   samples       : [p][attempts] node indices or NULL       -- only read with KSCHED_PICK_SAMPLED
  *                   an index >= n is treated as an infeasible draw
+ *                   (with KSCHED_PICK_UNIFORM: 32-bit draws, of which entry 0 of every row is read)
  *   out_feasible  : [p][W] or NULL
  *   out_fit       : [p][W] or NULL; requires KSCHED_WANT_FIT_MASK
  *   out_binding   : [p] or NULL; requires one of the KSCHED_PICK_* flags; -1 = no node
@@ -401,9 +420,10 @@ int ksched_mask_probe_report(ksched_ctx *ctx, double *out_us, uint32_t cap);
 /* The pick alone, from a feasibility mask already on the device (a previous ksched_eval_device* call): lets a caller
  * run the mask kernel of batch i + 1 and the pick of batch i on different HIP streams (the two do not depend on each
  * other; the mask of batch i must stay untouched until its pick has run).
- *   flags        : exactly one of KSCHED_PICK_SAMPLED (select_node_for_pod, src/main.rs:51-71: `samples`, `attempts`)
- *                  and KSCHED_PICK_BESTFIT (extension E1); KSCHED_FIT tells the best-fit pick that the mask includes
- *                  the resource fit (then `req_mem_bytes` [p] is read to skip candidates that cannot fit)
+ *   flags        : exactly one of KSCHED_PICK_SAMPLED (select_node_for_pod, src/main.rs:51-71: `samples`, `attempts`),
+ *                  KSCHED_PICK_BESTFIT (extension E1) and KSCHED_PICK_UNIFORM (extension E3: `samples`, `attempts`);
+ *                  KSCHED_FIT tells the best-fit pick that the mask includes the resource fit (then `req_mem_bytes` [p]
+ *                  is read to skip candidates that cannot fit)
  *   feasible     : [p] rows, mask_pitch_words apart, as written by ksched_eval_device_pitched
  * Results are identical to requesting the pick in the ksched_eval_device* call that produced the mask. */
 int ksched_pick_device(ksched_ctx *ctx, uint32_t p, const uint64_t *feasible, uint32_t mask_pitch_words,
@@ -593,7 +613,7 @@ int ksched_index_checksum(ksched_ctx *ctx, uint64_t *out /* [2] */);
 const char *ksched_last_kernel(const ksched_ctx *ctx);
 /* how the pick of the last ksched_eval* ran: "fused-tile" / "fused" (it rode in the fused mask launch as tile tests / as waves of
  * the fill, KSCHED_OPT_FUSED_PICK), "select" (its own launch testing the drawn candidates), "bestfit-rows", "from-mask"
- * (KSCHED_OPT_PICK_FROM_MASK / no bitmap index), "none" */
+ * (KSCHED_OPT_PICK_FROM_MASK / no bitmap index), "uniform" (KSCHED_PICK_UNIFORM), "none" */
 const char *ksched_last_pick(const ksched_ctx *ctx);
 
 #ifdef __cplusplus

@@ -35,6 +35,7 @@ TAINT = 0x04
 PICK_SAMPLED = 0x08
 PICK_BESTFIT = 0x10
 WANT_FIT_MASK = 0x20
+PICK_UNIFORM = 0x40  # extension E3: uniformly among the pod's feasible nodes, one 32-bit draw per pod (samples[:, 0])
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

@@ -25,6 +25,7 @@
 #include "kernels_build.hpp"
 #include "kernels_direct.hpp"
 #include "kernels_fused.hpp"
+#include "kernels_pick_uniform.hpp"
 #include "kernels_summary.hpp"
 #include "mask_alloc.hpp"
 #include "snapshot_change.hpp"
@@ -803,6 +804,9 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
     } else if (r.flags & KSCHED_PICK_BESTFIT) {
         hipLaunchKernelGGL(k_pick_bestfit, dim3((r.p + 3) / 4), dim3(256), 0, s, feas, c->bf_order.ptr, c->bf_rank.ptr,
                            c->bf_mem.ptr, r.pmem, r.out_binding, r.p, c->n, c->W, r.pitch, r.fit() ? 1u : 0u);
+    } else if (r.flags & KSCHED_PICK_UNIFORM) {  // (every caller has c->n > 0 here: an empty snapshot's bindings are a memset)
+        hipLaunchKernelGGL(k_pick_uniform, dim3((r.p + kUniformWaves - 1) / kUniformWaves), dim3(64 * kUniformWaves), 0, s, feas, r.samples,
+                           r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
     }
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
@@ -1115,7 +1119,7 @@ int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
     }
     c->last_kernel = plan.last_kernel;
     if (int trc = timing_end(c, s, t)) return trc;
-    if (plan.sampled != SampledPick::kFromMask && plan.bestfit != BestfitPick::kFromMask) return KSCHED_OK;
+    if (!plan.pick_from_mask()) return KSCHED_OK;
     return launch_pick(c, r, feas);
 }
 
@@ -1169,7 +1173,7 @@ int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
     if (c->n == 0) {
         // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
         // yields None on every attempt, src/main.rs:56,70)
-        if ((pick_s || pick_b) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
+        if ((pick_s || pick_b || (r.flags & KSCHED_PICK_UNIFORM)) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
         return KSCHED_OK;
     }
     fault_point(c);
@@ -1223,22 +1227,28 @@ int stage_batch(ksched_ctx *c, uint32_t p, const HostBatch &h, hipStream_t s) {
     return KSCHED_OK;
 }
 
+// the pick flags: at most one per call
+constexpr uint32_t kPickFlags = KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM;
+inline bool at_most_one_pick(uint32_t flags) {
+    const uint32_t pick = flags & kPickFlags;
+    return (pick & (pick - 1u)) == 0;
+}
+
 // the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed)
 int check_eval_args(const EvalRequest &r) {
     const uint32_t flags = r.flags;
-    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT |
-                           KSCHED_WANT_FIT_MASK;
+    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | kPickFlags | KSCHED_WANT_FIT_MASK;
     if (flags & ~known) return KSCHED_E_INVAL;
-    if ((flags & KSCHED_PICK_SAMPLED) && (flags & KSCHED_PICK_BESTFIT)) return KSCHED_E_INVAL;
+    if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
-    if (flags & KSCHED_PICK_SAMPLED) {
+    if (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM)) {  // the picks that read draws
         if (!r.out_binding || r.attempts == 0 || r.attempts > KSCHED_MAX_ATTEMPTS) return KSCHED_E_INVAL;
         if (r.p > 0 && !r.samples) return KSCHED_E_INVAL;
     }
     if ((flags & KSCHED_PICK_BESTFIT) && !r.out_binding) return KSCHED_E_INVAL;
     if ((flags & KSCHED_WANT_FIT_MASK) && !r.out_fit) return KSCHED_E_INVAL;
     if (!(flags & KSCHED_WANT_FIT_MASK) && r.out_fit) return KSCHED_E_INVAL;
-    if (!(flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) && !r.out_feas && !r.out_fit) return KSCHED_E_INVAL;
+    if (!(flags & kPickFlags) && !r.out_feas && !r.out_fit) return KSCHED_E_INVAL;
     return KSCHED_OK;
 }
 
@@ -1757,7 +1767,7 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     ksched_ctx *c = q->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    const uint32_t pick = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT);
+    const uint32_t pick = flags & kPickFlags;
     if (!pick || (flags & KSCHED_WANT_FIT_MASK) || !mask) return KSCHED_E_INVAL;
     EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, mask, nullptr, binding, mask_pitch_words, nullptr};  // (the stream: chosen below)
     int rc = check_eval_args(r);
@@ -1847,8 +1857,9 @@ int ksched_pick_device(ksched_ctx *c, uint32_t p, const uint64_t *feasible, uint
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    const bool pick_s = flags & KSCHED_PICK_SAMPLED, pick_b = flags & KSCHED_PICK_BESTFIT;
-    if (pick_s == pick_b || (flags & ~(KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
+    // (pick_s: the pick reads draws -- sampled or uniform)
+    const bool pick_s = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM), pick_b = flags & KSCHED_PICK_BESTFIT;
+    if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
     if (!out_binding || (p > 0 && c->n > 0 && !feasible) || mask_pitch_words < c->W) return KSCHED_E_INVAL;
     if (pick_s && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
     if (pick_b && (flags & KSCHED_FIT) && p > 0 && !req_mem_bytes) return KSCHED_E_INVAL;
@@ -1869,8 +1880,9 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    const bool pick_s = flags & KSCHED_PICK_SAMPLED, pick_b = flags & KSCHED_PICK_BESTFIT;
-    if (pick_s == pick_b || (flags & ~(KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
+    // (pick_s: the pick reads draws -- sampled or uniform)
+    const bool pick_s = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM), pick_b = flags & KSCHED_PICK_BESTFIT;
+    if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
     if (!out_binding || (p > 0 && c->n > 0 && !feasible)) return KSCHED_E_INVAL;
     if (pick_s && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
     if (pick_b && (flags & KSCHED_FIT) && p > 0 && !req_mem_bytes) return KSCHED_E_INVAL;
@@ -1914,13 +1926,13 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
     uint64_t *const out_feas = h.out_feas, *const out_fit = h.out_fit;
     const size_t W = c->W;
     const size_t pitch = ksched_mask_pitch(c->n);
-    const bool pick = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT);
-    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled pick
+    const bool pick = flags & kPickFlags;
+    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled or uniform pick
     b.pcpu = h.pcpu;
     b.pmem = h.pmem;
     if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride;
     if (h.taint_flag()) b.ptol = h.ptol;
-    if (flags & KSCHED_PICK_SAMPLED) b.samples = h.samples, b.attempts = h.attempts;
+    if (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM)) b.samples = h.samples, b.attempts = h.attempts;
     int32_t *d_bind = nullptr;
     if (pick) {
         const size_t cap = std::max<size_t>(capacity, p);
@@ -1933,7 +1945,7 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
 
     if (int rc = stage_batch(c, p, b, s)) return rc;
     uint64_t *d_feas = nullptr, *d_fit = nullptr;
-    // a mask is needed when the caller wants it, or when the pick reads it (best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
+    // a mask is needed when the caller wants it, or when the pick reads it (uniform; best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
     if (out_feas || pick_reads_mask(flags, c->opt_pick_from_mask, bf_rows_expected(c))) {
         HIPCHK(c, c->feas.reserve((size_t)p * pitch));
         d_feas = c->feas.ptr;
@@ -1994,7 +2006,7 @@ int ksched_eval_begin(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int6
     if (psel && sel_stride < p) return KSCHED_E_INVAL;
     int32_t sentinel = 0;  // (the bindings stay on the device: check_eval_args only wants to know that a pick has somewhere to go)
     const EvalRequest h{p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit,
-                        (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) ? &sentinel : nullptr, 0, c->stream};
+                        (flags & kPickFlags) ? &sentinel : nullptr, 0, c->stream};
     int rc = check_eval_args(h);
     if (rc) return rc;
     DeviceGuard g(c->device);

@@ -32,12 +32,17 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+_DRAWS = L.PICK_SAMPLED | L.PICK_UNIFORM                 # the picks that read `samples`
+_PICKS = L.PICK_SAMPLED | L.PICK_BESTFIT | L.PICK_UNIFORM  # at most one per call
+
+
 def _attempts(samples, flags: int, p: int) -> int:
-    """Draws per pod of a device `samples` tensor; a wrong shape would be an out-of-bounds device read, so it is refused here."""
-    if not (flags & L.PICK_SAMPLED):
+    """Draws per pod of a device `samples` tensor (PICK_SAMPLED: node indices; PICK_UNIFORM: 32-bit draws, column 0 is read); a wrong
+    shape would be an out-of-bounds device read, so it is refused here."""
+    if not (flags & _DRAWS):
         return 0
     if samples is None or samples.dim() != 2 or int(samples.shape[0]) != p or int(samples.shape[1]) == 0 or not samples.is_contiguous():
-        raise ValueError(f"samples must be a contiguous [{p}, attempts] tensor with KSCHED_PICK_SAMPLED")
+        raise ValueError(f"samples must be a contiguous [{p}, attempts] tensor with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM")
     return int(samples.shape[1])
 
 
@@ -157,7 +162,7 @@ class Evaluator:
 
     @property
     def last_pick(self) -> str:
-        """How the latest evaluation's pick ran: "fused-tile" / "fused" (inside the mask launch), "select", "bestfit-rows", "from-mask", "none"."""
+        """How the latest evaluation's pick ran: "fused-tile" / "fused" (inside the mask launch), "select", "bestfit-rows", "from-mask", "uniform", "none"."""
         return self._lib.ksched_last_pick(self._h).decode()
 
     @property
@@ -235,7 +240,9 @@ class Evaluator:
     # -- evaluation, host buffers ------------------------------------------------------------------
     def eval(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, samples=None, flags: int = L.FIT,
              want_mask: bool = True, out: "EvalResult | None" = None) -> EvalResult:
-        """`out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
+        """flags: predicates, at most one of PICK_SAMPLED (samples [p][attempts] node indices), PICK_BESTFIT and PICK_UNIFORM (samples [p][attempts]
+        32-bit draws of which column 0 is read: uniformly among the pod's feasible nodes), WANT_FIT_MASK.
+        `out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4)."""
         cpu = _np(req_cpu_milli, np.int64, "req_cpu_milli")
         mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
@@ -246,7 +253,7 @@ class Evaluator:
         tol = _np(tolerations, np.uint64, "tolerations")
         smp = _np(samples, np.uint32, "samples")
         attempts = 0
-        if flags & L.PICK_SAMPLED:
+        if flags & _DRAWS:
             if smp is None or smp.ndim != 2 or smp.shape[0] != p:
                 raise ValueError("samples must be [p][attempts]")
             attempts = smp.shape[1]
@@ -261,7 +268,7 @@ class Evaluator:
             res.feasible = buf(out.feasible if out is not None else None, (p, W), np.uint64)
         if flags & L.WANT_FIT_MASK:
             res.fit = buf(out.fit if out is not None else None, (p, W), np.uint64)
-        if flags & (L.PICK_SAMPLED | L.PICK_BESTFIT):
+        if flags & _PICKS:
             res.binding = buf(out.binding if out is not None else None, (p,), np.int32)
         rc = self._lib.ksched_eval(self._h, p, _ptr(cpu), _ptr(mem), _ptr(sel), _ptr(tol), _ptr(smp), attempts, flags,
                                    _ptr(res.feasible), _ptr(res.fit), _ptr(res.binding))
@@ -272,7 +279,8 @@ class Evaluator:
     def eval_device(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, samples=None,
                     flags: int = L.FIT, out_feasible=None, out_fit=None, out_binding=None, stream=None):
         """All arguments are torch CUDA tensors on this evaluator's device (int64 stands in for
-        uint64, int32 for uint32).  Work is enqueued on `stream` (default: torch's current stream)."""
+        uint64, int32 for uint32).  Work is enqueued on `stream` (default: torch's current stream).  `samples` [p, attempts] is read with
+        PICK_SAMPLED (node indices) and with PICK_UNIFORM (32-bit draws, column 0)."""
         import torch
 
         def dp(t, dtypes, shape=None):
@@ -302,9 +310,9 @@ class Evaluator:
         i64 = (torch.int64,)
         u64 = (torch.int64, torch.uint64)
         u32 = (torch.int32, torch.uint32)
-        attempts = int(samples.shape[1]) if (flags & L.PICK_SAMPLED and samples is not None) else 0
-        if flags & L.PICK_SAMPLED and (samples is None or samples.dim() != 2 or samples.shape[0] != p or attempts == 0):
-            raise ValueError(f"samples must be a [{p}, attempts] tensor with KSCHED_PICK_SAMPLED")  # a wrong shape would be an out-of-bounds device read
+        attempts = int(samples.shape[1]) if (flags & _DRAWS and samples is not None and samples.dim() == 2) else 0
+        if flags & _DRAWS and (samples is None or samples.dim() != 2 or samples.shape[0] != p or attempts == 0):
+            raise ValueError(f"samples must be a [{p}, attempts] tensor with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM")  # a wrong shape would be an out-of-bounds device read
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         pf, pitch = mask_ptr(out_feasible, None)
@@ -365,8 +373,9 @@ class Evaluator:
 
     def pick_device(self, feasible, flags: int, out_binding, req_mem_bytes=None, samples=None, stream=None):
         """The pick alone (ksched_pick_device) from a [p, W] device mask written by eval_device: torch CUDA tensors,
-        enqueued on `stream` (default: torch's current stream).  flags: PICK_SAMPLED (+ samples [p, attempts]) or
-        PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
+        enqueued on `stream` (default: torch's current stream).  flags: PICK_SAMPLED (+ samples [p, attempts]),
+        PICK_UNIFORM (+ samples [p, attempts]: 32-bit draws, column 0 is read) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask
+        includes the resource fit)."""
         import torch
         p, W = int(feasible.shape[0]), self.W
         if not feasible.is_cuda or feasible.dim() != 2 or feasible.shape[1] != W or (W and feasible.stride(1) != 1):
@@ -384,8 +393,8 @@ class Evaluator:
 
     def pick(self, feasible: np.ndarray, flags: int, req_mem_bytes=None, samples=None) -> np.ndarray:
         """The pick alone from HOST masks (ksched_pick): `feasible` = [p, W] uint64 rows as `eval` returns them (or as a caller has combined
-        them: ANDed masks of a selector evaluated in key groups).  flags: PICK_SAMPLED (+ samples [p, attempts]) or PICK_BESTFIT (+ FIT and
-        req_mem_bytes when the mask includes the resource fit)."""
+        them: ANDed masks of a selector evaluated in key groups).  flags: PICK_SAMPLED (+ samples [p, attempts]), PICK_UNIFORM (+ samples
+        [p, attempts]: 32-bit draws, column 0 is read) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
         f = np.ascontiguousarray(feasible, dtype=np.uint64)
         if f.ndim != 2 or f.shape[1] != self.W:
             raise ValueError(f"feasible must be [p, {self.W}] uint64")
@@ -393,7 +402,7 @@ class Evaluator:
         mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
         smp = _np(samples, np.uint32, "samples")
         attempts = 0
-        if flags & L.PICK_SAMPLED:
+        if flags & _DRAWS:
             if smp is None or smp.ndim != 2 or smp.shape[0] != p:
                 raise ValueError("samples must be [p][attempts]")
             attempts = smp.shape[1]
@@ -557,7 +566,8 @@ class Pipe:
         return int(self._lib.ksched_pipe_slot_stream(self._h, slot) or 0)
 
     def submit(self, slot: int, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags: int, mask, binding):
-        """torch CUDA tensors (see Evaluator.eval_device); `mask` is a [p, W] (possibly pitched) view, `binding` int32 [p]."""
+        """torch CUDA tensors (see Evaluator.eval_device); `mask` is a [p, W] (possibly pitched) view, `binding` int32 [p].  flags carry one
+        of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM (the uniform pick reads the mask: its slot runs in the split mode, ordered by events)."""
         p, W = int(req_cpu_milli.shape[0]), self.ev.W
         pitch = int(mask.stride(0)) if p > 1 else W
         attempts = _attempts(samples, flags, p)

@@ -64,6 +64,22 @@ BatchSelection select_nodes_for_pods(const std::vector<const corev1::Pod *> &pod
     const uint32_t p = (uint32_t)pods.size(), n = snap.n();
     BatchSelection out;
     out.node_store_index.assign(p, -1);
+    if (ctx.pick_uniform) {
+        // extension E3: one 32-bit draw per pod, in pod order; the device ranks it among the pod's feasible nodes (KSCHED_PICK_UNIFORM).
+        // No draw is ever rejected: `rejected` stays empty.  The masks ride along when the caller asked for the rejected draws' reasons.
+        if (n == 0 || p == 0 || ctx.node_store.size() == 0) return out;
+        PhaseClock clock("select (uniform)");
+        std::vector<uint32_t> draws(p);
+        for (uint32_t i = 0; i < p; ++i) draws[i] = (uint32_t)chooser.choose(size_t(1) << 32).value_or(0);
+        out.validity = predicates::check_node_validity_batch(pods, ctx, /*taints=*/false, KSCHED_PICK_UNIFORM, &draws, 1, /*want_masks=*/want_rejected);
+        out.samples = std::move(draws);
+        clock.lap("draws + check_node_validity_batch");
+        for (uint32_t i = 0; i < p; ++i) {
+            const int32_t b = out.validity.binding[i];
+            if (b >= 0) out.node_store_index[i] = (int32_t)snap.store_index((uint32_t)b);
+        }
+        return out;
+    }
     if (want_rejected) out.rejected.resize(p);
     // the draws, in the reference's order: pod by pod, attempt by attempt, over the store's own ordering;
     // converted to canonical column indices for the device (an empty store gives "no draw" = index n)

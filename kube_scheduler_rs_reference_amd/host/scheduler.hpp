@@ -62,11 +62,16 @@ std::optional<corev1::Node> select_node_for_pod(const corev1::Pod &pod, Context 
 // pod in pod order (the reference stops drawing after the first success; with an injected chooser the
 // results are identical draw for draw because unused draws do not influence the outcome).
 // Returns for every pod the chosen node's index into ctx.node_store, or -1.
+// With Context::pick_uniform (extension E3) the device picks uniformly among each pod's feasible nodes instead (KSCHED_PICK_UNIFORM): one
+// draw per pod in pod order, chooser.choose(2^32), handed over as a [p][1] table (an empty store: no draws, -1 for every pod); pod i's
+// node is set bit number (draw * c) >> 32 of its feasible row, c = the row's set bits, and -1 only when c == 0.  There are no rejected
+// draws: `rejected` stays empty and warn_rejected emits nothing.
 struct BatchSelection {
     std::vector<int32_t> node_store_index;             // [p] index into ctx.node_store or -1
     std::vector<std::vector<RejectedCandidate>> rejected;  // [p] candidates tried and refused, in order (filled on request)
     predicates::BatchValidity validity;                // the bindings; with want_rejected also both masks (canonical node order): without it no mask is computed or copied
     std::vector<uint32_t> samples;                     // [p][ATTEMPTS] the draws as canonical node indices (n = "no draw": empty store)
+                                                       // (Context::pick_uniform: [p][1] 32-bit draws; empty when the store is)
 };
 BatchSelection select_nodes_for_pods(const std::vector<const corev1::Pod *> &pods, Context &ctx, NodeChooser &chooser,
                                      bool want_rejected = false);

@@ -73,6 +73,12 @@ struct Context {
     // against the snapshot the batch was evaluated against.  Off: not one byte of output and no device call changes.
     bool explain_no_node_found = false;
 
+    // Opt-in (default off; extension E3): select_nodes_for_pods -- and with it reconcile_batch / reconcile_batch_sequential -- picks
+    // UNIFORMLY AMONG EACH POD'S FEASIBLE NODES on the device (KSCHED_PICK_UNIFORM) instead of testing ATTEMPTS blind draws: a pod ends
+    // with NoNodeFound only when no node passes.  One draw per pod, chooser.choose(2^32), in pod order.  Outside the parity claim (the
+    // reference tests five blind draws, src/main.rs:51-71).  Off: nothing changes, draw for draw.
+    bool pick_uniform = false;
+
     // (Re)build `snapshot` from node_store and one LIST per node.
     void refresh_snapshot();
     // Keep node_store and the snapshot current from node watch events, the way the reflector's writer does: an Applied node already in

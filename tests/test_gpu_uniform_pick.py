@@ -1,0 +1,420 @@
+"""KSCHED_PICK_UNIFORM (extension E3) on the GPU through every entry point that accepts it, against tests/uniform_ref.py (the numpy
+restatement, pinned by tests/test_uniform_restatement.py) applied to the ORACLE's feasibility mask.  Exact integers: every binding and
+every mask word must be identical.  Shapes are the smallest at which the kernel takes each of its paths: rows within one wave pass
+(W <= 128 words), longer rows (two passes over 128-word chunks), a last word with one valid bit, pitches that leave rows 8-byte
+aligned only, pod counts around a wave and a block."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_UNIFORM, SEL, TAINT, KschedError, _lib, synth,
+                                             unpack_mask)
+from oracle import capi
+from tests.uniform_ref import uniform_pick
+
+pytestmark = pytest.mark.gpu
+
+# (P, N, n_keys, n_taints, seed)
+CLUSTERS = [(700, 130, 8, 16, 7), (1200, 2600, 8, 0, 55), (900, 8200, 8, 16, 11), (600, 50200, 8, 16, 5), (333, 65, 2, 0, 2), (300, 1, 0, 0, 1)]
+MID = (1200, 2600, 8, 0, 55)
+_CASES = {}
+
+
+def case(spec):
+    """The cluster, its predicate flags, the oracle's feasible mask and a [P, 5] table of full-range 32-bit draws: computed once per cluster."""
+    if spec not in _CASES:
+        P, N, n_keys, n_taints, seed = spec
+        c = synth.make_cluster(P, N, n_keys=n_keys, n_taints=n_taints, seed=seed)
+        flags = FIT | (SEL if n_keys else 0) | (TAINT if n_taints else 0)
+        feas = oracle_mask(c, flags)
+        feas.setflags(write=False)
+        draws = np.random.default_rng(seed * 1000 + 17).integers(0, 1 << 32, size=(P, 5), dtype=np.uint64).astype(np.uint32)
+        draws.setflags(write=False)
+        _CASES[spec] = dict(c=c, flags=flags, feas=feas, draws=draws, want=uniform_pick(feas, draws[:, 0], N))
+    return _CASES[spec]
+
+
+def oracle_mask(c, flags, cpu=None, mem=None):
+    feas, _, _ = capi.eval_encoded(c.avail_cpu if cpu is None else cpu, c.avail_mem if mem is None else mem,
+                                   c.node_labels if c.n_keys else None, c.node_taints if c.n_taints else None, c.req_cpu, c.req_mem,
+                                   np.ascontiguousarray(c.pod_sel) if c.n_keys else None, c.pod_tol if c.n_taints else None, None, flags)
+    return feas
+
+
+def dev_of(ev):
+    import torch
+    return torch.device("cuda", ev.device)
+
+
+def to_dev(ev, a, dt):
+    import torch
+    return torch.from_numpy(np.array(a, order="C").view(dt)).to(dev_of(ev))  # (a copy: the shared cases are read-only)
+
+
+def pod_tensors(ev, c, lo=0, hi=None):
+    hi = c.P if hi is None else hi
+    return (to_dev(ev, c.req_cpu[lo:hi], np.int64), to_dev(ev, c.req_mem[lo:hi], np.int64),
+            to_dev(ev, c.pod_sel[:, lo:hi], np.int32) if c.n_keys else None, to_dev(ev, c.pod_tol[lo:hi], np.int64) if c.n_taints else None)
+
+
+def pitched_mask(ev, p, pitch, fill=0x5A):
+    """a [p, W] view with rows `pitch` words apart over a buffer filled with a sentinel"""
+    import torch
+    buf = torch.empty((max(p, 1), max(pitch, 1)), dtype=torch.int64, device=dev_of(ev))
+    buf.untyped_storage().fill_(fill)
+    return buf[:p, :ev.W]
+
+
+def mask_np(m):
+    return m.contiguous().cpu().numpy().view(np.uint64)
+
+
+@pytest.fixture
+def ev(evaluator):
+    evaluator.set_kernel("auto")
+    yield evaluator
+    evaluator.set_kernel("auto")
+    evaluator.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+# ---- 1. parity ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kernel", ["auto", "direct"])
+@pytest.mark.parametrize("spec", CLUSTERS, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_parity_in_every_output_form(ev, spec, kernel):
+    import torch
+    k = case(spec)
+    c, flags, feas, draws, want = k["c"], k["flags"] | PICK_UNIFORM, k["feas"], k["draws"], k["want"]
+    if c.N >= 130:  # the input condition: the test cannot pass vacuously
+        cnt = unpack_mask(feas, c.N).sum(axis=1)
+        print(f"{c.P} x {c.N}: {100 * (cnt >= 2).mean():.1f} % of the pods have two or more feasible nodes, {100 * (cnt == 0).mean():.1f} % none")
+        assert (cnt >= 2).mean() >= 0.50 and (cnt == 0).mean() >= 0.01
+    ev.set_kernel(kernel)
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    smp = to_dev(ev, draws, np.int32)
+    # the mask pitched (rows on cache-line boundaries)
+    m = ev.alloc_mask(c.P, pitched=True)
+    b = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+    ev.eval_device(cpu, mem, sel, tol, smp, flags, out_feasible=m, out_binding=b)
+    torch.cuda.synchronize()
+    assert ev.last_pick == "uniform" and (kernel == "auto" or ev.last_kernel == "direct")
+    assert np.array_equal(mask_np(m), feas), "pitched mask"
+    assert np.array_equal(b.cpu().numpy(), want), "bindings beside the pitched mask"
+    # the mask packed: ksched_eval_device itself (pitch = W: rows 8-byte aligned only when W is odd)
+    m2 = torch.full((c.P, ev.W), 0x5A5A5A5A, dtype=torch.int64, device=dev_of(ev))
+    b2 = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = ev._lib.ksched_eval_device(ev._h, c.P, ptr(cpu), ptr(mem), ptr(sel), ptr(tol), ptr(smp), 5, flags, ptr(m2), None, ptr(b2),
+                                    C.c_void_p(torch.cuda.current_stream(ev.device).cuda_stream))
+    assert rc == _lib.OK
+    torch.cuda.synchronize()
+    assert np.array_equal(mask_np(m2), feas), "packed mask"
+    assert np.array_equal(b2.cpu().numpy(), want), "bindings beside the packed mask"
+    # bindings only: the mask kernel writes the ctx's scratch mask
+    b3 = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+    ev.eval_device(cpu, mem, sel, tol, smp, flags, out_binding=b3)
+    torch.cuda.synchronize()
+    assert ev.last_pick == "uniform"
+    assert np.array_equal(b3.cpu().numpy(), want), "bindings only"
+    # host pointers: ksched_eval, with and without the mask
+    pc = c.pod_columns()
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags)
+    assert np.array_equal(r.feasible, feas) and np.array_equal(r.binding, want), "ksched_eval"
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags, want_mask=False)
+    assert r.feasible is None and np.array_equal(r.binding, want), "ksched_eval, bindings only"
+
+
+# ---- 2. a self-check that does not go through the restatement ------------------------------------------------------------------
+@pytest.mark.parametrize("spec", [MID, (900, 8200, 8, 16, 11)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_a_binding_exists_exactly_where_a_node_is_feasible_and_its_bit_is_set(ev, spec):
+    import torch
+    k = case(spec)
+    c = k["c"]
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    m = ev.alloc_mask(c.P, pitched=True)
+    b = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+    ev.eval_device(cpu, mem, sel, tol, to_dev(ev, k["draws"], np.int32), k["flags"] | PICK_UNIFORM, out_feasible=m, out_binding=b)
+    torch.cuda.synchronize()
+    bits = unpack_mask(mask_np(m), c.N)
+    got = b.cpu().numpy()
+    assert np.array_equal(got >= 0, bits.any(axis=1))
+    assert (got < c.N).all() and (got >= -1).all()
+    bound = np.nonzero(got >= 0)[0]
+    assert bits[bound, got[bound]].all()
+
+
+# ---- 3. extreme draws ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("spec", [MID, (600, 50200, 8, 16, 5)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_zero_draws_give_the_lowest_and_all_ones_the_highest_feasible_node(ev, spec):
+    import torch
+    k = case(spec)
+    c = k["c"]
+    bits = unpack_mask(k["feas"], c.N)
+    some = bits.any(axis=1)
+    lowest = np.where(some, bits.argmax(axis=1), -1)
+    highest = np.where(some, c.N - 1 - bits[:, ::-1].argmax(axis=1), -1)
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    for value, want in ((0, lowest), (0xFFFFFFFF, highest)):
+        smp = to_dev(ev, np.full((c.P, 1), value, np.uint32), np.int32)
+        b = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+        ev.eval_device(cpu, mem, sel, tol, smp, k["flags"] | PICK_UNIFORM, out_binding=b)
+        torch.cuda.synchronize()
+        assert np.array_equal(b.cpu().numpy(), want.astype(np.int32)), hex(value)
+
+
+# ---- 4. attempts --------------------------------------------------------------------------------------------------------------
+def test_only_the_first_entry_of_a_pods_row_of_draws_is_read(ev):
+    import torch
+    k = case(MID)
+    c = k["c"]
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    got = []
+    one = np.ascontiguousarray(k["draws"][:, :1])
+    ones = np.full((c.P, 5), 0xFFFFFFFF, np.uint32)
+    ones[:, 0] = one[:, 0]
+    rnd = np.random.default_rng(4).integers(0, 1 << 32, size=(c.P, 5), dtype=np.uint64).astype(np.uint32)
+    rnd[:, 0] = one[:, 0]
+    for table in (one, ones, rnd):
+        b = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+        ev.eval_device(cpu, mem, sel, tol, to_dev(ev, table, np.int32), k["flags"] | PICK_UNIFORM, out_binding=b)
+        torch.cuda.synchronize()
+        got.append(b.cpu().numpy())
+    assert np.array_equal(got[0], k["want"]) and np.array_equal(got[1], got[0]) and np.array_equal(got[2], got[0])
+
+
+# ---- 5. caller masks ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pitch", [79, 80, 83])
+def test_caller_masks_through_pick_device_and_pick(ev, pitch):
+    import torch
+    n, W = 4993, 79  # 78 full words and ONE valid bit in the last
+    ones = np.uint64(0xFFFFFFFFFFFFFFFF)
+    node_cols = synth.make_cluster(1, n, n_keys=0, n_taints=0, seed=9)
+    ev.set_nodes(**node_cols.node_columns())
+    assert ev.W == W
+    rows, expect = [], []  # valid bits of each row, and what the contract says without the restatement (None: ask the restatement only)
+    for node in (0, 63, 64, n - 1):
+        r = np.zeros(W, np.uint64)
+        r[node // 64] = np.uint64(1) << np.uint64(node % 64)
+        rows.append(r)
+        expect.append(lambda u, node=node: node)
+    full = np.full(W, ones, np.uint64)
+    full[W - 1] = np.uint64(1)
+    rows.append(full)
+    expect.append(lambda u: (u * n) >> 32)
+    rows.append(np.zeros(W, np.uint64))
+    expect.append(lambda u: -1)
+    draws_per_row = [0, 1, 0x7FFFFFFF, 0x80000000, 0xDEADBEEF, 0xFFFFFFFF]
+    valid = np.repeat(np.stack(rows), len(draws_per_row), axis=0)
+    u = np.tile(np.array(draws_per_row, np.uint32), len(rows))
+    want = np.array([expect[i // len(draws_per_row)](int(u[i])) for i in range(len(u))], np.int32)
+    assert np.array_equal(uniform_pick(valid, u, n), want)
+    p = valid.shape[0]
+    smp = np.stack([u, np.zeros_like(u)], axis=1)  # attempts = 2
+    for pad in (0, ones):  # padding bits of the last word and the words [W, pitch): all zero, all ones -- never counted, never chosen
+        host = np.full((p, pitch), pad, np.uint64)
+        host[:, :W] = valid
+        host[:, W - 1] |= np.uint64(pad) & ~np.uint64(1)
+        d = to_dev(ev, host, np.int64)[:, :W]
+        assert d.stride(0) == pitch
+        b = torch.full((p,), -7, dtype=torch.int32, device=dev_of(ev))
+        ev.pick_device(d, PICK_UNIFORM, b, samples=to_dev(ev, smp, np.int32))
+        torch.cuda.synchronize()
+        assert np.array_equal(b.cpu().numpy(), want), f"ksched_pick_device, padding {int(pad):#x}"
+        assert np.array_equal(ev.pick(np.ascontiguousarray(host[:, :W]), PICK_UNIFORM, samples=smp), want), f"ksched_pick, padding {int(pad):#x}"
+
+
+# ---- 6. pod-count edges -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", [1, 63, 64, 65, 257])
+def test_pod_counts_around_a_wave_and_a_block(ev, p):
+    import torch
+    k = case(MID)
+    c = k["c"]
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c, 0, p)
+    buf = torch.full((p + 8,), -7, dtype=torch.int32, device=dev_of(ev))
+    ev.eval_device(cpu, mem, sel, tol, to_dev(ev, k["draws"][:p], np.int32), k["flags"] | PICK_UNIFORM, out_binding=buf[:p])
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert np.array_equal(got[:p], k["want"][:p]) and (got[p:] == -7).all()
+
+
+# ---- 7. degenerate snapshots --------------------------------------------------------------------------------------------------
+def test_no_nodes_and_no_pods(ev):
+    import torch
+    z5 = np.zeros(5, np.int64)
+    ev.set_nodes(np.zeros(0, np.int64), np.zeros(0, np.int64))
+    r = ev.eval(z5, z5, samples=np.full((5, 1), 0xFFFFFFFF, np.uint32), flags=FIT | PICK_UNIFORM)
+    assert r.feasible.shape == (5, 0) and (r.binding == -1).all()
+    b = torch.full((5,), -7, dtype=torch.int32, device=dev_of(ev))
+    smp = to_dev(ev, np.zeros((5, 1), np.uint32), np.int32)
+    ev.eval_device(to_dev(ev, z5, np.int64), to_dev(ev, z5, np.int64), None, None, smp, FIT | PICK_UNIFORM, out_binding=b)
+    torch.cuda.synchronize()
+    assert (b.cpu().numpy() == -1).all()
+    b.fill_(-7)
+    ev.pick_device(torch.empty((5, 0), dtype=torch.int64, device=dev_of(ev)), PICK_UNIFORM, b, samples=smp)
+    torch.cuda.synchronize()
+    assert (b.cpu().numpy() == -1).all()
+    assert (ev.pick(np.zeros((5, 0), np.uint64), PICK_UNIFORM, samples=np.zeros((5, 1), np.uint32)) == -1).all()
+    # no pods: KSCHED_OK, nothing written
+    ev.set_nodes(np.ones(10, np.int64), np.ones(10, np.int64))
+    lib, h = ev._lib, ev._h
+    guard = torch.full((4,), -7, dtype=torch.int32, device=dev_of(ev))
+    gp = C.c_void_p(guard.data_ptr())
+    host_guard = np.full(4, -7, np.int32)
+    hp = host_guard.ctypes.data_as(C.c_void_p)
+    assert lib.ksched_eval_device(h, 0, None, None, None, None, None, 1, FIT | PICK_UNIFORM, None, None, gp, None) == _lib.OK
+    assert lib.ksched_pick_device(h, 0, None, 1, None, None, 1, PICK_UNIFORM, gp, None) == _lib.OK
+    assert lib.ksched_eval(h, 0, None, None, None, None, None, 1, FIT | PICK_UNIFORM, None, None, hp) == _lib.OK
+    assert lib.ksched_pick(h, 0, None, None, None, 1, PICK_UNIFORM, hp) == _lib.OK
+    torch.cuda.synchronize()
+    assert (guard.cpu().numpy() == -7).all() and (host_guard == -7).all()
+
+
+# ---- 8. argument errors -------------------------------------------------------------------------------------------------------
+def test_argument_errors(ev):
+    import torch
+    ev.set_nodes(np.ones(10, np.int64), np.ones(10, np.int64))
+    lib, h = ev._lib, ev._h
+    z = np.zeros(4, np.int64)
+    smp = np.zeros((4, 64), np.uint32)
+    mask = np.zeros((4, 1), np.uint64)
+    out = np.full(4, -7, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    d_z, d_smp, d_mask = to_dev(ev, z, np.int64), to_dev(ev, smp, np.int32), to_dev(ev, mask, np.int64)
+    d_out = torch.full((4,), -7, dtype=torch.int32, device=dev_of(ev))
+    dp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    pipe = ev.pipe(1)
+    # (flags, samples given, attempts, binding given)
+    bad = [(PICK_UNIFORM | PICK_SAMPLED, True, 5, True), (PICK_UNIFORM | PICK_BESTFIT, True, 5, True), (PICK_UNIFORM, False, 5, True),
+           (PICK_UNIFORM, True, 0, True), (PICK_UNIFORM, True, 65, True), (PICK_UNIFORM, True, 5, False)]
+    for flags, have_smp, attempts, have_out in bad:
+        what = (hex(flags), have_smp, attempts, have_out)
+        assert lib.ksched_eval(h, 4, p(z), p(z), None, None, p(smp) if have_smp else None, attempts, FIT | flags, None, None,
+                               p(out) if have_out else None) == _lib.E_INVAL, what
+        assert lib.ksched_eval_device(h, 4, dp(d_z), dp(d_z), None, None, dp(d_smp) if have_smp else None, attempts, FIT | flags, None, None,
+                                      dp(d_out) if have_out else None, None) == _lib.E_INVAL, what
+        assert lib.ksched_pick_device(h, 4, dp(d_mask), 1, None, dp(d_smp) if have_smp else None, attempts, flags,
+                                      dp(d_out) if have_out else None, None) == _lib.E_INVAL, what
+        assert lib.ksched_pick(h, 4, p(mask), None, p(smp) if have_smp else None, attempts, flags, p(out) if have_out else None) == _lib.E_INVAL, what
+        assert lib.ksched_pipe_submit(pipe._h, 0, 4, dp(d_z), dp(d_z), None, None, dp(d_smp) if have_smp else None, attempts, FIT | flags,
+                                      dp(d_mask), 1, dp(d_out) if have_out else None) == _lib.E_INVAL, what
+    pipe.close()
+    torch.cuda.synchronize()
+    assert (out == -7).all() and (d_out.cpu().numpy() == -7).all()
+    # the summaries take no pick flag
+    with pytest.raises(KschedError) as e:
+        ev.summarize(z, z, flags=FIT | PICK_UNIFORM)
+    assert e.value.code == _lib.E_INVAL
+    # and a valid call still works on this ctx
+    r = ev.eval(z, z, samples=smp[:, :5], flags=FIT | PICK_UNIFORM)
+    assert (r.binding == 0).all()  # every node fits a zero request; u = 0 gives the lowest
+
+
+# ---- 9. after a snapshot change -----------------------------------------------------------------------------------------------
+def test_after_update_nodes_and_apply_bindings(ev):
+    import torch
+    k = case(MID)
+    c, flags = k["c"], k["flags"]
+    ev.set_nodes(**c.node_columns())
+    cpu_t, mem_t, sel, tol = pod_tensors(ev, c)
+    smp = to_dev(ev, k["draws"], np.int32)
+    cpu, mem = c.avail_cpu.copy(), c.avail_mem.copy()
+    # one update: 40 nodes that some pod could use become over-committed, node n - 1 becomes huge
+    usable = np.nonzero(unpack_mask(k["feas"], c.N).any(axis=0))[0][:40]
+    idx = np.concatenate([usable, [c.N - 1]]).astype(np.uint32)
+    new_cpu = np.concatenate([np.full(len(usable), -5, np.int64), [1 << 50]])
+    new_mem = np.concatenate([c.avail_mem[usable], [1 << 60]])
+    ev.update_nodes(idx, new_cpu, new_mem)
+    cpu[idx], mem[idx] = new_cpu, new_mem
+    feas1 = oracle_mask(c, flags, cpu, mem)
+    assert not np.array_equal(feas1, k["feas"])
+    b = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+    ev.eval_device(cpu_t, mem_t, sel, tol, smp, flags | PICK_UNIFORM, out_binding=b)
+    torch.cuda.synchronize()
+    bind1 = b.cpu().numpy()
+    assert np.array_equal(bind1, uniform_pick(feas1, k["draws"][:, 0], c.N))
+    # one apply of those bindings on the device: every bound pod's request leaves its node
+    ev.apply_bindings_device(b, cpu_t, mem_t)
+    bound = bind1 >= 0
+    np.subtract.at(cpu, bind1[bound], c.req_cpu[bound])
+    np.subtract.at(mem, bind1[bound], c.req_mem[bound])
+    got_cpu, got_mem = ev.read_nodes()
+    assert np.array_equal(got_cpu, cpu) and np.array_equal(got_mem, mem)
+    feas2 = oracle_mask(c, flags, cpu, mem)
+    assert not np.array_equal(feas2, feas1)
+    m = ev.alloc_mask(c.P, pitched=True)
+    b2 = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+    ev.eval_device(cpu_t, mem_t, sel, tol, smp, flags | PICK_UNIFORM, out_feasible=m, out_binding=b2)
+    torch.cuda.synchronize()
+    assert np.array_equal(mask_np(m), feas2)
+    assert np.array_equal(b2.cpu().numpy(), uniform_pick(feas2, k["draws"][:, 0], c.N))
+
+
+# ---- 10. the pipe -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [0, 2])
+def test_pipe_submit_equals_eval_device_pitched(ev, mode):
+    import torch
+    k = case(MID)
+    c, flags = k["c"], k["flags"] | PICK_UNIFORM
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    tables = [k["draws"], np.ascontiguousarray(k["draws"][:, ::-1])]  # one batch of draws per slot
+    smps = [to_dev(ev, t, np.int32) for t in tables]
+    ref = []
+    for s in smps:
+        m = ev.alloc_mask(c.P, pitched=True)
+        b = torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev))
+        ev.eval_device(cpu, mem, sel, tol, s, flags, out_feasible=m, out_binding=b)
+        ref.append((m, b))
+    torch.cuda.synchronize()
+    for (m, b), t in zip(ref, tables):
+        assert np.array_equal(mask_np(m), k["feas"]) and np.array_equal(b.cpu().numpy(), uniform_pick(k["feas"], t[:, 0], c.N))
+    ev.set_option(_lib.OPT_PIPE_MODE, mode)
+    pipe = ev.pipe(2)
+    try:
+        masks = [ev.alloc_mask(c.P, pitched=True) for _ in range(2)]
+        outs = [torch.full((c.P,), -7, dtype=torch.int32, device=dev_of(ev)) for _ in range(2)]
+        for m in masks:
+            m.fill_(0)
+        torch.cuda.synchronize()
+        for slot in range(2):
+            pipe.submit(slot, cpu, mem, sel, tol, smps[slot], flags, masks[slot], outs[slot])
+        for slot in range(2):
+            pipe.wait(slot, host=True)
+            pipe.wait_mask(slot, host=True)
+        for slot in range(2):
+            assert torch.equal(masks[slot], ref[slot][0]), f"mask of slot {slot}"
+            assert torch.equal(outs[slot], ref[slot][1]), f"bindings of slot {slot}"
+    finally:
+        pipe.close()
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+# ---- 11. seeded differential loop ---------------------------------------------------------------------------------------------
+def test_seeded_differential_loop(ev):
+    import torch
+    for seed in range(12):
+        rng = np.random.default_rng(0xD1FF + seed)
+        P, N = int(rng.integers(2, 401)), int(rng.integers(1, 3001))
+        n_keys, n_taints = int(rng.choice([0, 3, 8])), int(rng.choice([0, 16]))
+        c = synth.make_cluster(P, N, n_keys=n_keys, n_taints=n_taints, seed=1000 + seed)
+        flags = int(rng.choice([FIT, FIT | SEL, FIT | TAINT, SEL | TAINT, FIT | SEL | TAINT, SEL]))
+        flags &= FIT | (SEL if n_keys else 0) | (TAINT if n_taints else 0)
+        flags = flags or FIT
+        feas = oracle_mask(c, flags)
+        draws = rng.integers(0, 1 << 32, size=(P, 1), dtype=np.uint64).astype(np.uint32)
+        ev.set_kernel(str(rng.choice(["auto", "direct"])))
+        ev.set_nodes(**c.node_columns())
+        cpu, mem, sel, tol = pod_tensors(ev, c)
+        pitch = ev.W + int(rng.integers(0, 4))
+        m = pitched_mask(ev, P, pitch)
+        b = torch.full((P,), -7, dtype=torch.int32, device=dev_of(ev))
+        ev.eval_device(cpu, mem, sel, tol, to_dev(ev, draws, np.int32), flags | PICK_UNIFORM, out_feasible=m, out_binding=b)
+        torch.cuda.synchronize()
+        what = f"seed {seed}: {P} x {N}, flags {flags:#x}, pitch {pitch}, kernel {ev.last_kernel}"
+        assert np.array_equal(mask_np(m), feas), what
+        assert np.array_equal(b.cpu().numpy(), uniform_pick(feas, draws[:, 0], N)), what
