@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "../../include/ksched.h"
+#include "bestfit_layout.hpp"
 
 namespace ksched {
 
@@ -145,12 +146,14 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
         const bool sel = (flags & KSCHED_SEL) && f.have_psel && f.nkeys > 0;
         // one stage (a wave per pod) or two (a lane per pod first): the second launch and the hand-over list pay off from tens of
         // thousands of pods on (20k pods: 33 us against 44; 125k pods: 160 against 120) -- KSCHED_OPT_BESTFIT_STAGES overrides
-        const bool lists = sel && f.nlist > 0;  // pods that constrain a list key are split off by the first stage: two stages it is
+        // pods that constrain a list key are split off by the first stage: two stages it is.  (Only with the selector term active: the
+        // listed kernel is then given the selector columns and key count every other pick of the request is given, launch_bestfit_listed.)
+        const bool lists = sel && f.nlist > 0;
         const bool two_stage = lists || f.opt_bestfit_stages == 2 || (f.opt_bestfit_stages == 0 && p >= 24576u);  // (measured crossover at the C5 shard's snapshot: ~24 k pods)
-        if (!lists && (!two_stage || (f.debug & 0x400u) || f.n > (1u << 21))) {
+        if (!lists && (!two_stage || (f.debug & 0x400u) || f.n > kBfLanesMaxNodes)) {  // (the first stage's searches carry kBfMaxLevels level arrays)
             plan.bestfit = BestfitPick::kRowsOneStage;
         } else {
-            if (f.n > (1u << 21)) return plan_unsupported(PlanError::kListKeysTooManyNodes);
+            if (f.n > kBfLanesMaxNodes) return plan_unsupported(PlanError::kListKeysTooManyNodes);
             plan.bestfit = lists ? BestfitPick::kRowsTwoStagesListed : BestfitPick::kRowsTwoStages;
         }
         plan.last_pick = "bestfit-rows";

@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/ksched.h"
+#include "bestfit_layout.hpp"
 #include "kernarg.hpp"
 
 // clang (ROCm 7.2) exposes no __builtin_amdgcn_writelane; bind the LLVM intrinsic by name.
@@ -405,9 +406,8 @@ __global__ __launch_bounds__(256) void k_pick_bestfit(const uint64_t *__restrict
 // do, so only candidates in the difference (at most q nodes of the whole snapshot) are tested individually.  The first
 // set bit of the lowest word wins.  No mask is read: like the sampled pick, this runs before and independently of
 // the mask kernel, and a bindings-only request launches no mask kernel.
-// The first stage appends the pods it hands over to kBfSublists lists, wave w to list w % kBfSublists: ONE list with one counter made
-// 2 000 waves queue for a returning atomic on one address (~8 ns each, up to 10 us of waiting per wave at the C5 shard).
-constexpr uint32_t kBfSublists = 128;
+// The first stage appends the pods it hands over to kBfSublists lists, wave w to list w % kBfSublists (bestfit_layout.hpp, with every
+// other number these structures are sized by).
 struct BestfitRowsArgs {
     const uint64_t *rows;          // [rows][Wbf] bitmaps over bf_order positions; Wbf = ceil(n / 64) rounded up to a multiple of 8 (rows are whole 64-byte lines)
     const uint32_t *lab_meta;      // lab_base[32], lab_max[32] (row numbers shared with the tile index)

@@ -16,9 +16,11 @@
 #include <numeric>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 
+#include "bestfit_layout.hpp"
 #include "comm_rccl.hpp"
 #include "eval_plan.hpp"
 #include "eval_request.hpp"
@@ -35,13 +37,23 @@ using namespace ksched;
 
 static_assert(kListBytes == 6144u && kTileNodes == 1024, "k_pick_bestfit_listed (kernels_direct.hpp) addresses the tile lists with these sizes");
 static_assert(kChangeTileNodes == (uint32_t)kTileNodes, "snapshot_change.hpp lists the tiles an update touches");
+static_assert(sizeof(BestfitRowsArgs::lvl_off) == 4 * kBfMaxLevels && sizeof(BfLevelsArgs::lvl_off) == 4 * kBfMaxLevels, "bestfit_layout.hpp sizes the level arrays the kernels carry");
 
 namespace {
 
+// a device allocation that grows on demand and is released with its owner (the owner's device must be current then: ksched_destroy)
 template <class T>
 struct DevBuf {
     T *ptr = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }  // (move-only: the copy operations are deleted with these two declared)
+    DevBuf &operator=(DevBuf &&o) noexcept {  // `o` leaves with what this one held, and releases it
+        std::swap(ptr, o.ptr);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { release(); }
     void release() {
         if (ptr) (void)hipFree(ptr);
         ptr = nullptr;
@@ -54,6 +66,46 @@ struct DevBuf {
         if (e == hipSuccess) cap = n;
         return e;
     }
+};
+
+// ---- the best-fit index: buffers and state ("the best-fit pick" below builds it and launches over it) -------------------------
+// Everything a PICK_BESTFIT request reads beyond the snapshot's columns, sized by bestfit_layout.hpp.  Built lazily, by the first
+// PICK_BESTFIT request after the snapshot changed: order_stale = the order (and with it everything) is stale, rows_stale = only the
+// row bitmaps are (labels or taints changed, `available` did not).
+struct BestfitIndex {
+    DevBuf<uint32_t> bf_order, bf_rank;  // node at best-fit position i, and the inverse
+    DevBuf<int64_t> bf_mem, bf_cpu;      // node columns once more, in best-fit order
+    DevBuf<int64_t> cpu_sorted;          // ascending avail_cpu (rank of a cpu request)
+    DevBuf<uint32_t> by_cpu, cpurank;    // node with cpu rank r, and the inverse
+    DevBuf<int64_t> samples;             // sample arrays of bf_mem and cpu_sorted (BfOrderLayout)
+    DevBuf<int64_t> levels;              // 8-ary level arrays of bf_mem / cpu_sorted (k_pick_bestfit_lanes)
+    DevBuf<uint64_t> rows;               // [rows][Wbf] bitmaps over best-fit positions (k_pick_bestfit_rows); built with the tile index's row numbering
+    DevBuf<int64_t> srt_k0[2], srt_k1[2];  // ping-pong sets of the orders' merge sort (kernels_build.hpp)
+    DevBuf<uint32_t> srt_idx[2];
+    DevBuf<uint32_t> handover;           // the two-stage pick's hand-over (BfHandoverLayout): counter sets in rotation, the listed mask, the sub-lists' 64-byte records
+    DevBuf<uint64_t> trace;              // KSCHED_OPT_DEBUG bit 20: per-wave time stamps of the two stages (tools/bestfit_ab.py --trace)
+    BfOrderLayout order;  // as of the latest build_bestfit
+    BfRowLayout row;      // as of the latest build_bestfit_rows (rows_built)
+    BfRotation rotation;  // which counter set of `handover` the next two-stage pick uses
+    bool rows_built = false;
+    bool order_stale = true, rows_stale = false;
+
+    // the five arrays ksched_set_nodes reserves with the snapshot's columns; the lazy build reserves the rest
+    hipError_t reserve_for(uint32_t n) {
+        hipError_t e = bf_order.reserve(n);
+        if (e == hipSuccess) e = bf_rank.reserve(n);
+        if (e == hipSuccess) e = bf_mem.reserve(bf_searched_elems(n));
+        if (e == hipSuccess) e = bf_cpu.reserve(n);
+        if (e == hipSuccess) e = cpu_sorted.reserve(bf_searched_elems(n));
+        return e;
+    }
+    // a committed snapshot change (SnapshotChange::commit)
+    void mark(Stale what) {
+        if (stale_order(what)) order_stale = true;
+        if (stale_rows_only(what)) rows_stale = true;
+        if (what == Stale::kEverything) rows_built = false;
+    }
+    bool stale() const { return order_stale || rows_stale; }
 };
 
 }  // namespace
@@ -72,27 +124,7 @@ struct ksched_ctx {
     DevBuf<int64_t> nrec;  // 64-byte node records (kernels_direct.hpp): one cache line per candidate for the candidate-testing picks
     DevBuf<uint32_t> nlab;
     DevBuf<uint64_t> ntaint;
-    DevBuf<uint32_t> bf_order, bf_rank;
-    DevBuf<int64_t> bf_mem, bf_cpu;  // node columns once more, in best-fit order
-    DevBuf<int64_t> cpu_sorted;      // ascending avail_cpu (rank of a cpu request)
-    DevBuf<int64_t> bf_samples;      // sample arrays of bf_mem and cpu_sorted: [mem s1][mem s2][cpu s1][cpu s2]
-    uint32_t bf_n1 = 0, bf_n2 = 0;
-    DevBuf<int64_t> bf_levels;       // 8-ary level arrays of bf_mem / cpu_sorted (k_pick_bestfit_lanes)
-    uint32_t bf_nlev = 0, bf_lvl_half = 0, bf_lvl_off[6] = {};
-    DevBuf<uint32_t> bf_fallback;    // hand-over of the two-stage best-fit pick: 3 sets of sub-list counters in rotation, the listed mask, the sub-lists' 64-byte records
-    uint32_t bf_slot = 0;            // which of the three counter sets the next two-stage pick uses (the call before zeroed it)
-    size_t bf_fallback_zeroed_cap = 0;
-    DevBuf<uint64_t> bf_trace;       // KSCHED_OPT_DEBUG bit 20: per-wave time stamps of the two best-fit stages (tools/bestfit_ab.py --trace)
-    DevBuf<uint64_t> bf_rows;        // [rows][Wbf] bitmaps over best-fit positions (k_pick_bestfit_rows); built with the tile index
-    bool bf_rows_built = false;
-    uint32_t bf_row_cpu0 = 0, bf_q = 1, bf_W = 0;
-    // the best-fit structures are built lazily, by the first PICK_BESTFIT request after the snapshot changed: bf_dirty = the order
-    // (and with it everything) is stale, bf_rows_dirty = only the row bitmaps are (labels or taints changed, `available` did not)
-    bool bf_dirty = true;
-    bool bf_rows_dirty = false;
-    DevBuf<uint32_t> by_cpu, cpurank;
-    DevBuf<int64_t> srt_k0[2], srt_k1[2];  // ping-pong sets of the best-fit orders' merge sort (kernels_build.hpp)
-    DevBuf<uint32_t> srt_idx[2];
+    BestfitIndex bestfit;  // the best-fit orders, rows and hand-over scratch, built lazily (ensure_bestfit)
     IndexedSnapshot idx;  // per-tile bitmap index (tile_index.hpp), built on the device (kernels_build.hpp)
     // what the index layout was planned for (index_plan), indexed or not: per key the largest id, and every taint bit; a label
     // update whose ids and bits stay within them keeps the layout
@@ -133,7 +165,7 @@ struct ksched_ctx {
     hipStream_t change_stream = nullptr;
     uint64_t own_gen = 0;  // snapshot generation the ctx's own stream is ordered behind
     bool opt_own_stream = false;
-    // The ctx-owned device scratch that evaluations on the caller's streams use (bf_fallback, scratch_mask, trace) belongs to one
+    // The ctx-owned device scratch that evaluations on the caller's streams use (the best-fit hand-over, scratch_mask, trace) belongs to one
     // stream at a time: when another stream is about to use it, that stream first waits for what the previous one holds
     // (scratch_enter; an event recorded at that moment, nothing on the common one-stream path).
     hipStream_t scratch_stream = nullptr;
@@ -319,7 +351,6 @@ void stream_forget(ksched_ctx *c, hipStream_t s) {
     for (size_t i = 0; i < c->pick_acc.size(); ++i)
         if (c->pick_acc[i].s == s) {  // (its launches are ordered before whatever the caller does to the stream next: freeing is safe after a sync there;
                                       // hipFree synchronises the device itself)
-            c->pick_acc[i].buf.release();
             c->pick_acc.erase(c->pick_acc.begin() + (std::ptrdiff_t)i);
             break;
         }
@@ -424,9 +455,7 @@ struct SnapshotChange {
     // everything is enqueued: mark what the change made stale (the best-fit structures are rebuilt by the next PICK_BESTFIT request,
     // ensure_bestfit, not here), let the other streams see the change (snapshot_end), validate the snapshot
     int commit(Stale what) {
-        if (stale_order(what)) c->bf_dirty = true;
-        if (stale_rows_only(what)) c->bf_rows_dirty = true;
-        if (what == Stale::kEverything) c->bf_rows_built = false;
+        c->bestfit.mark(what);
         if (int rc = snapshot_end(c)) return rc;
         c->have_nodes = true;
         done = true;
@@ -493,164 +522,344 @@ int launch_build_named(ksched_ctx *c, const uint32_t *d_tile_list = nullptr, uin
     return KSCHED_OK;
 }
 
+// The pod operands every pick's argument struct carries (SelectArgs, BestfitRowsArgs, BestfitListedArgs), with the request's terms
+// normalised: no selector columns and no keys unless the selector term is active, the taint term only over a snapshot with taints.
+template <class A>
+void fill_pod_operands(A &a, const ksched_ctx *c, const EvalRequest &r) {
+    const bool sel = r.sel(c->nkeys);
+    a.pcpu = r.pcpu;
+    a.pmem = r.pmem;
+    a.psel = sel ? r.psel : nullptr;
+    a.ptol = r.ptol;
+    a.binding = r.out_binding;
+    a.p = r.p;
+    a.n = c->n;
+    a.nkeys = sel ? c->nkeys : 0u;
+    a.do_fit = r.fit() ? 1u : 0u;
+    a.do_taint = r.taint(c->have_taints) ? 1u : 0u;
+}
+
+// ---- the best-fit pick: build and launches over the BestfitIndex (sized by bestfit_layout.hpp) ---------------------------------
+
+// one order by the merge sort of kernels_build.hpp: ascending (k0, k1, node) -- k1 may be null -- of the snapshot's n nodes; runs of
+// 1024 sorted in LDS, then merged by ranking, ping-pong between two sets of (k0, k1, idx) arrays; the last pass lands in dst_k0 /
+// dst_idx, the arrays the pick kernels read
+int bestfit_sort(ksched_ctx *c, const int64_t *k0, const int64_t *k1, int64_t *dst_k0, uint32_t *dst_idx) {
+    BestfitIndex &bi = c->bestfit;
+    const uint32_t n = c->n, passes = bi.order.merge_passes;
+    const hipStream_t s = c->change_stream;
+    if (n > (1u << 31)) {  // (the merge passes index records with 32 bits; no snapshot of that size fits a GPU's memory anyway)
+        c->last_error = "best-fit structures: more than 2^31 nodes";
+        return KSCHED_E_INVAL;
+    }
+    // buffer of pass i's output: the destination arrays for the last one, the ping-pong sets before it
+    auto out_of = [&](uint32_t i, SortArgs &q) {  // i = 0: k_sort_runs, i = 1 .. passes: merge passes
+        q.k0_out = i == passes ? dst_k0 : bi.srt_k0[i & 1].ptr;
+        q.k1_out = k1 ? bi.srt_k1[i & 1].ptr : nullptr;  // (nobody reads the second key of the final order)
+        q.idx_out = i == passes ? dst_idx : bi.srt_idx[i & 1].ptr;
+    };
+    SortArgs q{};  // (no idx_in, run 0: the runs are sorted from the columns)
+    q.n = n;
+    q.k0_in = k0;
+    q.k1_in = k1;
+    out_of(0, q);
+    hipLaunchKernelGGL(k_sort_runs, dim3((n + 1023u) / 1024u), dim3(1024), 0, s, q);
+    HIPCHK(c, hipGetLastError());
+    for (uint32_t i = 1; i <= passes; ++i) {
+        SortArgs m{};
+        m.n = n;
+        m.run = 1024u << (i - 1u);
+        m.k0_in = q.k0_out;
+        m.k1_in = q.k1_out;
+        m.idx_in = q.idx_out;
+        out_of(i, m);
+        hipLaunchKernelGGL(k_merge_pass, dim3((n + 255u) / 256u), dim3(256), 0, s, m);
+        HIPCHK(c, hipGetLastError());
+        q = m;
+    }
+    return KSCHED_OK;
+}
+
 // Best-fit candidate order of the snapshot, ascending (avail_mem, avail_cpu, node), its inverse, the node
 // columns in that order, the sorted cpu column with the sample arrays of the two rank searches, and -- when the snapshot has a
 // bitmap index -- the named rows once more over best-fit positions plus the 257 cpu threshold rows (k_pick_bestfit_rows).
-// Two device merge sorts (kernels_build.hpp: k_sort_runs + k_merge_pass) and two kernels, on the change stream; called lazily by the first PICK_BESTFIT request
-// after the snapshot changed (ksched_set_nodes / ksched_update_nodes only mark it dirty).
+// Two device merge sorts (bestfit_sort) and two kernels, on the change stream; called lazily by the first PICK_BESTFIT request
+// after the snapshot changed (ksched_set_nodes / ksched_update_nodes only mark it stale).
 int build_bestfit_rows(ksched_ctx *c);
 int build_bestfit(ksched_ctx *c) {
+    BestfitIndex &bi = c->bestfit;
     const uint32_t n = c->n;
-    c->bf_rows_built = false;
+    bi.rows_built = false;
     hipStream_t s = c->change_stream;
-    const uint32_t n1 = (n + 63u) / 64u, n2 = (n + 4095u) / 4096u;
-    HIPCHK(c, c->by_cpu.reserve(n));
-    HIPCHK(c, c->cpurank.reserve(n));
-    HIPCHK(c, c->bf_samples.reserve(2 * (size_t)(n1 + n2)));
-    const dim3 grid((n + 255u) / 256u), block(256);
-    // The two orders, by the merge sort of kernels_build.hpp: runs of 1024 sorted in LDS, then merged by ranking, ping-pong between two
-    // sets of (k0, k1, idx) arrays; the last pass of each sort lands in the arrays the pick kernels read.
+    const BfOrderLayout &o = bi.order = bf_order_layout(n);
+    HIPCHK(c, bi.by_cpu.reserve(n));
+    HIPCHK(c, bi.cpurank.reserve(n));
+    HIPCHK(c, bi.samples.reserve(o.sample_elems()));
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(c, c->srt_k0[b].reserve(n));
-        HIPCHK(c, c->srt_k1[b].reserve(n));
-        HIPCHK(c, c->srt_idx[b].reserve(n));
+        HIPCHK(c, bi.srt_k0[b].reserve(n));
+        HIPCHK(c, bi.srt_k1[b].reserve(n));
+        HIPCHK(c, bi.srt_idx[b].reserve(n));
     }
-    auto device_sort = [&](const int64_t *k0, const int64_t *k1, int64_t *dst_k0, uint32_t *dst_idx) -> int {
-        if (n > (1u << 31)) {  // (the merge passes index records with 32 bits; no snapshot of that size fits a GPU's memory anyway)
-            c->last_error = "best-fit structures: more than 2^31 nodes";
-            return KSCHED_E_INVAL;
-        }
-        uint32_t passes = 0;
-        for (uint64_t run = 1024; run < n; run <<= 1) ++passes;
-        // buffer of pass i's output: the destination arrays for the last one, the ping-pong sets before it
-        auto out_of = [&](uint32_t i, SortArgs &q) {  // i = 0: k_sort_runs, i = 1 .. passes: merge passes
-            q.k0_out = i == passes ? dst_k0 : c->srt_k0[i & 1].ptr;
-            q.k1_out = k1 ? c->srt_k1[i & 1].ptr : nullptr;  // (nobody reads the second key of the final order)
-            q.idx_out = i == passes ? dst_idx : c->srt_idx[i & 1].ptr;
-        };
-        SortArgs q{};  // (no idx_in, run 0: the runs are sorted from the columns)
-        q.n = n;
-        q.k0_in = k0;
-        q.k1_in = k1;
-        out_of(0, q);
-        hipLaunchKernelGGL(k_sort_runs, dim3((n + 1023u) / 1024u), dim3(1024), 0, s, q);
-        HIPCHK(c, hipGetLastError());
-        uint32_t i = 0;
-        for (uint64_t run = 1024; run < n; run <<= 1) {
-            SortArgs m{};
-            m.n = n;
-            m.run = (uint32_t)run;
-            m.k0_in = q.k0_out;
-            m.k1_in = q.k1_out;
-            m.idx_in = q.idx_out;
-            out_of(++i, m);
-            hipLaunchKernelGGL(k_merge_pass, grid, block, 0, s, m);
-            HIPCHK(c, hipGetLastError());
-            q = m;
-        }
-        return KSCHED_OK;
-    };
     // order 1: ascending (cpu, node) -> cpu_sorted (the sorted cpu column), by_cpu (node with cpu rank r)
-    if (int rc = device_sort(c->ncpu.ptr, nullptr, c->cpu_sorted.ptr, c->by_cpu.ptr)) return rc;
+    if (int rc = bestfit_sort(c, c->ncpu.ptr, nullptr, bi.cpu_sorted.ptr, bi.by_cpu.ptr)) return rc;
     // order 2: ascending (mem, cpu, node) -> bf_mem, bf_order
-    if (int rc = device_sort(c->nmem.ptr, c->ncpu.ptr, c->bf_mem.ptr, c->bf_order.ptr)) return rc;
+    if (int rc = bestfit_sort(c, c->nmem.ptr, c->ncpu.ptr, bi.bf_mem.ptr, bi.bf_order.ptr)) return rc;
     BfGatherArgs g{};
     g.ncpu = c->ncpu.ptr;
     g.nmem = c->nmem.ptr;
-    g.bf_order = c->bf_order.ptr;
-    g.by_cpu = c->by_cpu.ptr;
-    g.bf_rank = c->bf_rank.ptr;
-    g.cpurank = c->cpurank.ptr;
-    g.bf_mem = c->bf_mem.ptr;
-    g.bf_cpu = c->bf_cpu.ptr;
-    g.cpu_sorted = c->cpu_sorted.ptr;
-    g.samples = c->bf_samples.ptr;
+    g.bf_order = bi.bf_order.ptr;
+    g.by_cpu = bi.by_cpu.ptr;
+    g.bf_rank = bi.bf_rank.ptr;
+    g.cpurank = bi.cpurank.ptr;
+    g.bf_mem = bi.bf_mem.ptr;
+    g.bf_cpu = bi.bf_cpu.ptr;
+    g.cpu_sorted = bi.cpu_sorted.ptr;
+    g.samples = bi.samples.ptr;
     g.n = n;
-    g.n1 = n1;
-    g.n2 = n2;
-    hipLaunchKernelGGL(k_bf_gather, grid, block, 0, s, g);
+    g.n1 = o.n1;
+    g.n2 = o.n2;
+    hipLaunchKernelGGL(k_bf_gather, dim3((n + 255u) / 256u), dim3(256), 0, s, g);
     HIPCHK(c, hipGetLastError());
-    c->bf_n1 = n1;
-    c->bf_n2 = n2;
-    {   // 8-ary level arrays for the lane-per-pod searches: level k = last element of every block of 8^k entries
+    // 8-ary level arrays for the lane-per-pod searches
+    HIPCHK(c, bi.levels.reserve(o.level_elems()));
+    if (o.nlev) {
         BfLevelsArgs lv{};
-        uint32_t nk = n, off = 0;
-        c->bf_nlev = 0;
-        while (nk > 8u && c->bf_nlev < 6u) {
-            nk = (nk + 7u) / 8u;
-            c->bf_lvl_off[c->bf_nlev++] = off;
-            off += (nk + 7u) & ~7u;  // every level starts on a 64-byte boundary and may be read in whole blocks of eight
-        }
-        c->bf_lvl_half = off;
-        HIPCHK(c, c->bf_levels.reserve(2 * (size_t)off + 8));
-        if (c->bf_nlev) {
-            lv.bf_mem = c->bf_mem.ptr;
-            lv.cpu_sorted = c->cpu_sorted.ptr;
-            lv.lvl = c->bf_levels.ptr;
-            lv.n = n;
-            lv.nlev = c->bf_nlev;
-            lv.lvl_half = off;
-            for (uint32_t k = 0; k < 6; ++k) lv.lvl_off[k] = c->bf_lvl_off[k];
-            hipLaunchKernelGGL(k_bf_levels, dim3(((n + 7u) / 8u + 255u) / 256u), dim3(256), 0, s, lv);
-            HIPCHK(c, hipGetLastError());
-        }
+        lv.bf_mem = bi.bf_mem.ptr;
+        lv.cpu_sorted = bi.cpu_sorted.ptr;
+        lv.lvl = bi.levels.ptr;
+        lv.n = n;
+        lv.nlev = o.nlev;
+        lv.lvl_half = o.lvl_half;
+        for (uint32_t k = 0; k < kBfMaxLevels; ++k) lv.lvl_off[k] = o.lvl_off[k];
+        hipLaunchKernelGGL(k_bf_levels, dim3(((n + 7u) / 8u + 255u) / 256u), dim3(256), 0, s, lv);
+        HIPCHK(c, hipGetLastError());
     }
     return build_bestfit_rows(c);
-}
-
-// The row bitmaps in best-fit order alone, over the current order: what a label / taint change (ksched_update_node_labels) makes
-// stale -- it cannot move the order, which reads `available` only.
-int build_bestfit_rows(ksched_ctx *c) {
-    const uint32_t n = c->n;
-    hipStream_t s = c->change_stream;
-    c->bf_rows_built = false;
-    if (c->idx.built && n > 0) {  // (list keys have no rows: pods that constrain one are picked from the key's sorted lists, k_pick_bestfit_listed)
-        const IndexedLayout &l = c->idx.lay;
-        const uint32_t Wbf = ((n + 63u) / 64u + 7u) & ~7u, named = l.row_cpu;  // (rows padded to whole 64-byte lines: k_pick_bestfit_lanes reads aligned blocks of 8 words)
-        const uint32_t levels = 256u, q = (n + levels - 1u) / levels;
-        const uint32_t rows = named + levels + 1u;
-        HIPCHK(c, c->bf_rows.reserve((size_t)rows * Wbf));
-        HIPCHK(c, hipMemsetAsync(c->bf_rows.ptr, 0, (size_t)rows * Wbf * 8, s));
-        BfRowsArgs r{};
-        r.nlab = c->nlab.ptr;
-        r.ntaint = c->have_taints ? c->ntaint.ptr : nullptr;
-        r.bf_order = c->bf_order.ptr;
-        r.cpurank = c->cpurank.ptr;
-        r.lab_meta = c->idx.d_lab_meta;
-        r.rows = c->bf_rows.ptr;
-        r.n = n;
-        r.Wbf = Wbf;
-        r.nkeys = c->nkeys;
-        r.ngroups = l.ngroups;
-        r.row_valid = l.row_valid;
-        r.row_taint = l.row_taint;
-        r.row_cpu0 = named;
-        r.q = q;
-        r.levels = levels;
-        hipLaunchKernelGGL(k_bf_rows, dim3((Wbf + 3u) / 4u), dim3(256), 0, s, r);
-        HIPCHK(c, hipGetLastError());
-        c->bf_row_cpu0 = named;
-        c->bf_W = Wbf;
-        c->bf_q = q;
-        c->bf_rows_built = true;
-    }
-    return KSCHED_OK;
 }
 
 // will the best-fit rows exist once ensure_bestfit has run?  (they are built with the bitmap index's row numbering)
 inline bool bf_rows_expected(const ksched_ctx *c) { return c->idx.built && c->n > 0; }
 
+// The row bitmaps in best-fit order alone, over the current order: what a label / taint change (ksched_update_node_labels) makes
+// stale -- it cannot move the order, which reads `available` only.
+int build_bestfit_rows(ksched_ctx *c) {
+    BestfitIndex &bi = c->bestfit;
+    const uint32_t n = c->n;
+    hipStream_t s = c->change_stream;
+    bi.rows_built = false;
+    if (!bf_rows_expected(c)) return KSCHED_OK;  // (list keys have no rows: pods that constrain one are picked from the key's sorted lists, k_pick_bestfit_listed)
+    const IndexedLayout &l = c->idx.lay;
+    const BfRowLayout w = bf_row_layout(n, l.row_cpu);
+    HIPCHK(c, bi.rows.reserve(w.words()));
+    HIPCHK(c, hipMemsetAsync(bi.rows.ptr, 0, w.words() * 8, s));
+    BfRowsArgs r{};
+    r.nlab = c->nlab.ptr;
+    r.ntaint = c->have_taints ? c->ntaint.ptr : nullptr;
+    r.bf_order = bi.bf_order.ptr;
+    r.cpurank = bi.cpurank.ptr;
+    r.lab_meta = c->idx.d_lab_meta;
+    r.rows = bi.rows.ptr;
+    r.n = n;
+    r.Wbf = w.Wbf;
+    r.nkeys = c->nkeys;
+    r.ngroups = l.ngroups;
+    r.row_valid = l.row_valid;
+    r.row_taint = l.row_taint;
+    r.row_cpu0 = w.row_cpu0;
+    r.q = w.q;
+    r.levels = w.levels;
+    hipLaunchKernelGGL(k_bf_rows, dim3((w.Wbf + 3u) / 4u), dim3(256), 0, s, r);
+    HIPCHK(c, hipGetLastError());
+    bi.row = w;
+    bi.rows_built = true;
+    return KSCHED_OK;
+}
+
 // a PICK_BESTFIT request is about to be enqueued: make sure the structures match the snapshot
 int ensure_bestfit(ksched_ctx *c) {
-    if (c->n == 0 || (!c->bf_dirty && !c->bf_rows_dirty)) return KSCHED_OK;
+    BestfitIndex &bi = c->bestfit;
+    if (c->n == 0 || !bi.stale()) return KSCHED_OK;
     SnapshotChange chg;
     if (int rc = chg.begin(c)) return rc;  // picks already enqueued read the previous order
-    if (int rc = c->bf_dirty ? build_bestfit(c) : build_bestfit_rows(c)) {  // (rows only: no sort)
+    if (int rc = bi.order_stale ? build_bestfit(c) : build_bestfit_rows(c)) {  // (rows only: no sort)
         chg.done = true;  // columns and index are untouched and the stale flags still set: nothing to invalidate, the next request tries again
         return rc;
     }
-    c->bf_dirty = c->bf_rows_dirty = false;
+    bi.order_stale = bi.rows_stale = false;
     return chg.commit(Stale::kNothing);
+}
+
+// BestfitRowsArgs as all three kernels over the rows take them: the index's arrays, its layouts and the bitmap index's row numbers,
+// and the request.  The hand-over members stay null / 0: the one-stage kernel reads none of them, launch_bestfit_two_stages adds them.
+BestfitRowsArgs make_bestfit_rows_args(const ksched_ctx *c, const EvalRequest &r) {
+    const BestfitIndex &bi = c->bestfit;
+    const IndexedLayout &l = c->idx.lay;
+    BestfitRowsArgs q{};
+    q.rows = bi.rows.ptr;
+    q.lab_meta = c->idx.d_lab_meta;
+    q.cpu_sorted = bi.cpu_sorted.ptr;
+    q.bf_mem = bi.bf_mem.ptr;
+    q.bf_cpu = bi.bf_cpu.ptr;
+    q.bf_order = bi.bf_order.ptr;
+    if (bi.order.sampled) {
+        q.mem_s1 = bi.samples.ptr;
+        q.mem_s2 = bi.samples.ptr + bi.order.mem_s2();
+        q.cpu_s1 = bi.samples.ptr + bi.order.cpu_s1();
+        q.cpu_s2 = bi.samples.ptr + bi.order.cpu_s2();
+    }
+    fill_pod_operands(q, c, r);
+    q.Wbf = bi.row.Wbf;
+    q.ngroups = l.ngroups;
+    q.row_valid = l.row_valid;
+    q.row_zero = l.row_zero;
+    q.row_taint = l.row_taint;
+    q.row_cpu0 = bi.row.row_cpu0;
+    q.q = bi.row.q;
+    for (int k = 0; k < 8; ++k) {
+        q.lab_base8[k] = l.lab_base[k];
+        q.lab_max8[k] = l.lab_max[k];
+    }
+    return q;
+}
+
+// one wave per pod, one wave per block (scans differ tenfold in length: with four waves per block the long ones hold up the
+// placement of whole blocks; 158 against 172 us for 125 k pods at the C5 shard)
+int launch_bestfit_one_stage(ksched_ctx *c, const EvalRequest &r) {
+    const BestfitRowsArgs q = make_bestfit_rows_args(c, r);
+    hipLaunchKernelGGL(k_pick_bestfit_rows, dim3(r.p), dim3(64), 0, r.stream, q);
+    HIPCHK(c, hipGetLastError());
+    return KSCHED_OK;
+}
+
+// KSCHED_OPT_DEBUG bit 20: where the waves of the two best-fit stages spend their time (synchronous; stderr; tools only)
+void bestfit_trace_report(ksched_ctx *c, uint32_t p, size_t slots2, hipStream_t s) {
+    const size_t waves1 = (p + 63) / 64, total = waves1 * 8 + slots2 * 4;
+    std::vector<uint64_t> h(total);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h.data(), c->bestfit.trace.ptr, total * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
+    if (const char *path = getenv("KSCHED_BF_TRACE_FILE"))  // the raw stamps: [waves of stage 1][8] then [hand-over slots][4] uint64
+        if (FILE *f = fopen(path, "wb")) {
+            fwrite(h.data(), 8, total, f);
+            fclose(f);
+        }
+    auto pct = [](std::vector<double> &v, double f) { return v.empty() ? 0.0 : v[(size_t)(f * (double)(v.size() - 1))]; };
+    const double ghz = 0.1;  // s_memrealtime: the constant 100 MHz reference clock
+    uint64_t t0 = ~0ull;
+    for (size_t w = 0; w < waves1; ++w)
+        if (h[w * 8]) t0 = std::min(t0, h[w * 8]);
+    const char *names[4] = {"operands", "searches", "word trips", "hand-over"};
+    std::vector<double> ph[4], entry, exit_, und;
+    for (size_t w = 0; w < waves1; ++w) {
+        const uint64_t *r = &h[w * 8];
+        if (!r[0] || !r[4]) continue;
+        for (int i = 0; i < 4; ++i) ph[i].push_back((double)(r[i + 1] - r[i]) / ghz * 1e-3);
+        entry.push_back((double)(r[0] - t0) / ghz * 1e-3);
+        exit_.push_back((double)(r[4] - t0) / ghz * 1e-3);
+        und.push_back((double)r[5]);
+    }
+    auto line = [&](const char *what, std::vector<double> &v) {
+        std::sort(v.begin(), v.end());
+        double sum = 0;
+        for (double x : v) sum += x;
+        fprintf(stderr, "  %-28s mean %7.2f   p10 %7.2f  p50 %7.2f  p90 %7.2f  max %7.2f   (%zu waves)\n", what, v.empty() ? 0.0 : sum / (double)v.size(), pct(v, 0.1), pct(v, 0.5), pct(v, 0.9),
+                pct(v, 1.0), v.size());
+    };
+    fprintf(stderr, "best-fit stage 1 (k_pick_bestfit_lanes), us:\n");
+    line("entry after the first wave", entry);
+    for (int i = 0; i < 4; ++i) line(names[i], ph[i]);
+    line("exit after the first entry", exit_);
+    line("lanes handed over per wave", und);
+    const uint64_t *t2 = &h[waves1 * 8];
+    uint64_t t20 = ~0ull;
+    std::vector<double> e2, d2, x2, words;
+    for (size_t w = 0; w < slots2; ++w)
+        if (t2[w * 4]) t20 = std::min(t20, t2[w * 4]);
+    for (size_t w = 0; w < slots2; ++w) {
+        const uint64_t *r = &t2[w * 4];
+        if (!r[0] || !r[1]) continue;
+        e2.push_back((double)(r[0] - t20) / ghz * 1e-3);
+        d2.push_back((double)(r[1] - r[0]) / ghz * 1e-3);
+        x2.push_back((double)(r[1] - t20) / ghz * 1e-3);
+    }
+    fprintf(stderr, "best-fit stage 2 (k_pick_bestfit_handed), us:   first entry %.2f us after stage 1's first entry\n", t20 == ~0ull ? 0.0 : (double)(t20 - t0) / ghz * 1e-3);
+    line("entry after the first wave", e2);
+    line("scan of one pod", d2);
+    line("exit after the first entry", x2);
+}
+
+// Two stages: one lane per pod decides from the first candidate words (k_pick_bestfit_lanes); the rare rest goes to the wave-per-pod
+// kernel through the hand-over buffer (k_pick_bestfit_handed).  `lists`: pods that constrain a list key are split off by the first
+// stage into the listed mask, for launch_bestfit_listed.
+int launch_bestfit_two_stages(ksched_ctx *c, const EvalRequest &r, bool lists) {
+    BestfitIndex &bi = c->bestfit;
+    const hipStream_t s = r.stream;
+    const IndexedLayout &l = c->idx.lay;
+    const BfHandoverLayout h = bf_handover_layout(r.p);
+    const BfDebug dbg = bf_debug(c->opt_debug);
+    BestfitRowsArgs q = make_bestfit_rows_args(c, r);
+    if (int rsc = scratch_enter(c, s)) return rsc;
+    HIPCHK(c, bi.handover.reserve(h.total_u32()));
+    if (bi.rotation.fresh(bi.handover.cap)) {  // a fresh allocation: all counters once
+        HIPCHK(c, hipMemsetAsync(bi.handover.ptr, 0, h.ctr_u32 * 4, s));
+        bi.rotation.zeroed(bi.handover.cap);
+    }
+    uint32_t *const words = bi.handover.ptr;
+    q.handover_count = words + h.ctr_off(bi.rotation.use());
+    q.zero_next = words + h.ctr_off(bi.rotation.zero());
+    q.sub_cap = (uint32_t)h.sub_cap;
+    q.lvl = bi.levels.ptr;
+    q.nlev = bi.order.nlev;
+    q.lvl_half = bi.order.lvl_half;
+    for (uint32_t k = 0; k < kBfMaxLevels; ++k) q.lvl_off[k] = bi.order.lvl_off[k];
+    q.handover_recs = words + h.rec_off();
+    q.nlist = lists ? l.nlist : 0u;
+    for (uint32_t j = 0; j < q.nlist; ++j) q.list_col[j] = l.list_col[j];
+    q.listed_mask = lists ? reinterpret_cast<uint64_t *>(words + h.mask_off()) : nullptr;
+    q.lane_blocks = dbg.lane_blocks;
+    if (dbg.tracing) {
+        HIPCHK(c, bi.trace.reserve(h.trace_u64()));
+        HIPCHK(c, hipMemsetAsync(bi.trace.ptr, 0, h.trace_u64() * 8, s));
+        q.trace = bi.trace.ptr;
+        q.trace2 = bi.trace.ptr + h.trace1_u64();
+    }
+    hipLaunchKernelGGL(k_pick_bestfit_lanes, dim3((r.p + 255) / 256), dim3(256), 0, s, q);
+    HIPCHK(c, hipGetLastError());
+    bi.rotation.advance();  // (only once the kernel that zeroes the next set is on its way)
+    BestfitRowsArgs q2 = q;
+    q2.sub_count = q.handover_count;
+    q2.pod_recs = q.handover_recs;
+    hipLaunchKernelGGL(k_pick_bestfit_handed, dim3(bf_handed_grid(h.sub_cap, dbg.grid_shift)), dim3(64), 0, s, q2);
+    if (dbg.tracing) bestfit_trace_report(c, r.p, h.slots2(), s);
+    return KSCHED_OK;  // (launch_bestfit_rows checks the second stage's launch, with the listed kernel's if one follows)
+}
+
+// the pods the first stage split off (they constrain a list key): picked from the key's sorted lists in the bitmap index.
+// plan_eval sets kRowsTwoStagesListed only when the selector term is active, so the psel / nkeys the shared fill gives are the
+// unconditional r.psel / c->nkeys this kernel has always been given.
+void launch_bestfit_listed(ksched_ctx *c, const EvalRequest &r) {
+    const BestfitIndex &bi = c->bestfit;
+    const IndexedLayout &l = c->idx.lay;
+    BestfitListedArgs la{};
+    la.lists = c->idx.d_list;
+    la.nrec = c->nrec.ptr;
+    la.nlab = c->nlab.ptr;
+    la.bf_rank = bi.bf_rank.ptr;
+    la.bf_order = bi.bf_order.ptr;
+    fill_pod_operands(la, c, r);
+    la.listed_mask = reinterpret_cast<uint64_t *>(bi.handover.ptr + bf_handover_layout(r.p).mask_off());  // (where the first stage has just written it)
+    la.tiles = l.tiles;
+    la.nlist = l.nlist;
+    for (uint32_t j = 0; j < l.nlist; ++j) la.list_col[j] = l.list_col[j];
+    hipLaunchKernelGGL(k_pick_bestfit_listed, dim3((r.p + 3) / 4), dim3(256), 0, r.stream, la);
+}
+
+// The best-fit pick from bitmaps kept in best-fit order, no mask involved: one stage, two, or two plus the listed kernel, as the plan says
+int launch_bestfit_rows(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
+    if (plan.bestfit == BestfitPick::kRowsOneStage) return launch_bestfit_one_stage(c, r);
+    const bool lists = plan.bestfit == BestfitPick::kRowsTwoStagesListed;
+    if (int rc = launch_bestfit_two_stages(c, r, lists)) return rc;
+    if (lists) launch_bestfit_listed(c, r);
+    HIPCHK(c, hipGetLastError());
+    return KSCHED_OK;
 }
 
 // ---- the bitmap index's layout: plan -> reserve -> build ----------------------------------------------------------------
@@ -802,8 +1011,9 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
         hipLaunchKernelGGL(k_pick_sampled, dim3((r.p + 255) / 256), dim3(256), 0, s, feas, r.samples, r.out_binding, r.p, c->n,
                            r.pitch, r.attempts);
     } else if (r.flags & KSCHED_PICK_BESTFIT) {
-        hipLaunchKernelGGL(k_pick_bestfit, dim3((r.p + 3) / 4), dim3(256), 0, s, feas, c->bf_order.ptr, c->bf_rank.ptr,
-                           c->bf_mem.ptr, r.pmem, r.out_binding, r.p, c->n, c->W, r.pitch, r.fit() ? 1u : 0u);
+        const BestfitIndex &bi = c->bestfit;  // (the order and its inverse: no rows)
+        hipLaunchKernelGGL(k_pick_bestfit, dim3((r.p + 3) / 4), dim3(256), 0, s, feas, bi.bf_order.ptr, bi.bf_rank.ptr, bi.bf_mem.ptr, r.pmem,
+                           r.out_binding, r.p, c->n, c->W, r.pitch, r.fit() ? 1u : 0u);
     } else if (r.flags & KSCHED_PICK_UNIFORM) {  // (every caller has c->n > 0 here: an empty snapshot's bindings are a memset)
         hipLaunchKernelGGL(k_pick_uniform, dim3((r.p + kUniformWaves - 1) / kUniformWaves), dim3(64 * kUniformWaves), 0, s, feas, r.samples,
                            r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
@@ -813,22 +1023,12 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
 }
 
 SelectArgs make_select_args(const ksched_ctx *c, const EvalRequest &r) {
-    const bool sel = r.sel(c->nkeys);
     SelectArgs q{};
     q.nrec = c->nrec.ptr;
     q.nlab = c->nlab.ptr;
-    q.pcpu = r.pcpu;
-    q.pmem = r.pmem;
-    q.psel = sel ? r.psel : nullptr;
-    q.ptol = r.ptol;
+    fill_pod_operands(q, c, r);
     q.samples = r.samples;
-    q.binding = r.out_binding;
-    q.p = r.p;
-    q.n = c->n;
-    q.nkeys = sel ? c->nkeys : 0u;
     q.attempts = r.attempts;
-    q.do_fit = r.fit() ? 1u : 0u;
-    q.do_taint = r.taint(c->have_taints) ? 1u : 0u;
     return q;
 }
 
@@ -846,179 +1046,6 @@ int launch_select(ksched_ctx *c, const EvalRequest &r) {
         }
     }
     else hipLaunchKernelGGL((k_select_sampled<8, 2>), grid, block, 0, s, q);
-    HIPCHK(c, hipGetLastError());
-    return KSCHED_OK;
-}
-
-// KSCHED_OPT_DEBUG bit 20: where the waves of the two best-fit stages spend their time (synchronous; stderr; tools only)
-void bestfit_trace_report(ksched_ctx *c, uint32_t p, size_t slots2, hipStream_t s) {
-    const size_t waves1 = (p + 63) / 64, total = waves1 * 8 + slots2 * 4;
-    std::vector<uint64_t> h(total);
-    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h.data(), c->bf_trace.ptr, total * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-    if (const char *path = getenv("KSCHED_BF_TRACE_FILE"))  // the raw stamps: [waves of stage 1][8] then [hand-over slots][4] uint64
-        if (FILE *f = fopen(path, "wb")) {
-            fwrite(h.data(), 8, total, f);
-            fclose(f);
-        }
-    auto pct = [](std::vector<double> &v, double f) { return v.empty() ? 0.0 : v[(size_t)(f * (double)(v.size() - 1))]; };
-    const double ghz = 0.1;  // s_memrealtime: the constant 100 MHz reference clock
-    uint64_t t0 = ~0ull;
-    for (size_t w = 0; w < waves1; ++w)
-        if (h[w * 8]) t0 = std::min(t0, h[w * 8]);
-    const char *names[4] = {"operands", "searches", "word trips", "hand-over"};
-    std::vector<double> ph[4], entry, exit_, und;
-    for (size_t w = 0; w < waves1; ++w) {
-        const uint64_t *r = &h[w * 8];
-        if (!r[0] || !r[4]) continue;
-        for (int i = 0; i < 4; ++i) ph[i].push_back((double)(r[i + 1] - r[i]) / ghz * 1e-3);
-        entry.push_back((double)(r[0] - t0) / ghz * 1e-3);
-        exit_.push_back((double)(r[4] - t0) / ghz * 1e-3);
-        und.push_back((double)r[5]);
-    }
-    auto line = [&](const char *what, std::vector<double> &v) {
-        std::sort(v.begin(), v.end());
-        double sum = 0;
-        for (double x : v) sum += x;
-        fprintf(stderr, "  %-28s mean %7.2f   p10 %7.2f  p50 %7.2f  p90 %7.2f  max %7.2f   (%zu waves)\n", what, v.empty() ? 0.0 : sum / (double)v.size(), pct(v, 0.1), pct(v, 0.5), pct(v, 0.9),
-                pct(v, 1.0), v.size());
-    };
-    fprintf(stderr, "best-fit stage 1 (k_pick_bestfit_lanes), us:\n");
-    line("entry after the first wave", entry);
-    for (int i = 0; i < 4; ++i) line(names[i], ph[i]);
-    line("exit after the first entry", exit_);
-    line("lanes handed over per wave", und);
-    const uint64_t *t2 = &h[waves1 * 8];
-    uint64_t t20 = ~0ull;
-    std::vector<double> e2, d2, x2, words;
-    for (size_t w = 0; w < slots2; ++w)
-        if (t2[w * 4]) t20 = std::min(t20, t2[w * 4]);
-    for (size_t w = 0; w < slots2; ++w) {
-        const uint64_t *r = &t2[w * 4];
-        if (!r[0] || !r[1]) continue;
-        e2.push_back((double)(r[0] - t20) / ghz * 1e-3);
-        d2.push_back((double)(r[1] - r[0]) / ghz * 1e-3);
-        x2.push_back((double)(r[1] - t20) / ghz * 1e-3);
-    }
-    fprintf(stderr, "best-fit stage 2 (k_pick_bestfit_handed), us:   first entry %.2f us after stage 1's first entry\n", t20 == ~0ull ? 0.0 : (double)(t20 - t0) / ghz * 1e-3);
-    line("entry after the first wave", e2);
-    line("scan of one pod", d2);
-    line("exit after the first entry", x2);
-}
-
-// The best-fit pick from bitmaps kept in best-fit order (k_pick_bestfit_rows), no mask involved: one stage, two, or two plus the
-// listed kernel, as the plan says
-int launch_bestfit_rows(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
-    const hipStream_t s = r.stream;
-    const uint32_t p = r.p;
-    const IndexedLayout &l = c->idx.lay;
-    BestfitRowsArgs q{};
-    const bool sel = r.sel(c->nkeys);
-    q.rows = c->bf_rows.ptr;
-    q.lab_meta = c->idx.d_lab_meta;
-    q.cpu_sorted = c->cpu_sorted.ptr;
-    q.bf_mem = c->bf_mem.ptr;
-    q.bf_cpu = c->bf_cpu.ptr;
-    q.bf_order = c->bf_order.ptr;
-    if (c->n <= 64u * 64u * 64u) {  // three rounds of 64 cover the array
-        q.mem_s1 = c->bf_samples.ptr;
-        q.mem_s2 = q.mem_s1 + c->bf_n1;
-        q.cpu_s1 = q.mem_s2 + c->bf_n2;
-        q.cpu_s2 = q.cpu_s1 + c->bf_n1;
-    }
-    q.pcpu = r.pcpu;
-    q.pmem = r.pmem;
-    q.psel = sel ? r.psel : nullptr;
-    q.ptol = r.ptol;
-    q.binding = r.out_binding;
-    q.p = p;
-    q.n = c->n;
-    q.Wbf = c->bf_W;
-    q.nkeys = sel ? c->nkeys : 0u;
-    q.ngroups = l.ngroups;
-    q.row_valid = l.row_valid;
-    q.row_zero = l.row_zero;
-    q.row_taint = l.row_taint;
-    q.row_cpu0 = c->bf_row_cpu0;
-    q.q = c->bf_q;
-    q.do_fit = r.fit() ? 1u : 0u;
-    q.do_taint = r.taint(c->have_taints) ? 1u : 0u;
-    for (int k = 0; k < 8; ++k) {
-        q.lab_base8[k] = l.lab_base[k];
-        q.lab_max8[k] = l.lab_max[k];
-    }
-    if (plan.bestfit == BestfitPick::kRowsOneStage) {
-        // one wave per pod, one wave per block (scans differ tenfold in length: with four waves per block the long ones hold up the
-        // placement of whole blocks; 158 against 172 us for 125 k pods at the C5 shard)
-        hipLaunchKernelGGL(k_pick_bestfit_rows, dim3(p), dim3(64), 0, s, q);
-        HIPCHK(c, hipGetLastError());
-        return KSCHED_OK;
-    }
-    // two stages: one lane per pod decides from the first two candidate words; the rare rest goes to the wave-per-pod kernel
-    const bool lists = plan.bestfit == BestfitPick::kRowsTwoStagesListed;  // pods that constrain a list key are split off by the first stage
-    if (int rsc = scratch_enter(c, s)) return rsc;
-    // [3 sets of kBfSublists counters, one per 128-byte line, in rotation][listed mask: ceil(p / 64) words][64-byte hand-over records:
-    // kBfSublists lists of sub_cap slots]; each call zeroes the NEXT call's counters (no memset launch)
-    const size_t waves1 = ((size_t)p + 63) / 64, sub_cap = ((waves1 + kBfSublists - 1) / kBfSublists) * 64;
-    const size_t ctr_u32 = 3 * (size_t)kBfSublists * 32, mask_u32 = ((waves1 * 2 + 15) / 16) * 16;  // (records stay 64-byte aligned)
-    HIPCHK(c, c->bf_fallback.reserve(ctr_u32 + mask_u32 + 16 * (size_t)kBfSublists * sub_cap));
-    if (c->bf_fallback_zeroed_cap != c->bf_fallback.cap) {  // a fresh allocation: all counters once
-        HIPCHK(c, hipMemsetAsync(c->bf_fallback.ptr, 0, ctr_u32 * 4, s));
-        c->bf_fallback_zeroed_cap = c->bf_fallback.cap;
-        c->bf_slot = 0;
-    }
-    q.handover_count = c->bf_fallback.ptr + (size_t)c->bf_slot * kBfSublists * 32;
-    q.zero_next = c->bf_fallback.ptr + (size_t)((c->bf_slot + 1u) % 3u) * kBfSublists * 32;
-    q.sub_cap = (uint32_t)sub_cap;
-    q.lvl = c->bf_levels.ptr;
-    q.nlev = c->bf_nlev;
-    q.lvl_half = c->bf_lvl_half;
-    for (uint32_t k = 0; k < 6; ++k) q.lvl_off[k] = c->bf_lvl_off[k];
-    q.handover_recs = c->bf_fallback.ptr + ctr_u32 + mask_u32;
-    q.nlist = lists ? l.nlist : 0u;
-    for (uint32_t j = 0; j < q.nlist; ++j) q.list_col[j] = l.list_col[j];
-    q.listed_mask = lists ? reinterpret_cast<uint64_t *>(c->bf_fallback.ptr + ctr_u32) : nullptr;
-    q.lane_blocks = ((c->opt_debug >> 12) & 15u) ? ((c->opt_debug >> 12) & 15u) : 2u;  // KSCHED_OPT_DEBUG bits 12-15: A/B of the hand-over point (in 64-byte blocks of 8 words)
-    const bool tracing = (c->opt_debug & 0x100000u) != 0u;
-    if (tracing) {
-        HIPCHK(c, c->bf_trace.reserve(waves1 * 8 + (size_t)kBfSublists * sub_cap * 4));
-        HIPCHK(c, hipMemsetAsync(c->bf_trace.ptr, 0, (waves1 * 8 + (size_t)kBfSublists * sub_cap * 4) * 8, s));
-        q.trace = c->bf_trace.ptr;
-        q.trace2 = c->bf_trace.ptr + waves1 * 8;
-    }
-    hipLaunchKernelGGL(k_pick_bestfit_lanes, dim3((p + 255) / 256), dim3(256), 0, s, q);
-    HIPCHK(c, hipGetLastError());
-    c->bf_slot = (c->bf_slot + 1u) % 3u;  // (only once the kernel that zeroes the next set is on its way)
-    BestfitRowsArgs q2 = q;
-    q2.sub_count = q.handover_count;
-    q2.pod_recs = q.handover_recs;
-    // one wave per block; the grid covers 1 / 2^k of the lists' capacity (KSCHED_OPT_DEBUG bits 21-22: k = 2 by default, A/B 0 / 1 / 3)
-    const uint32_t gshift = ((c->opt_debug >> 21) & 3u) == 0u ? 2u : ((c->opt_debug >> 21) & 3u) == 1u ? 0u : ((c->opt_debug >> 21) & 3u) == 2u ? 1u : 3u;
-    const uint32_t per_list = std::max<uint32_t>(1u, (uint32_t)sub_cap >> gshift);
-    hipLaunchKernelGGL(k_pick_bestfit_handed, dim3(kBfSublists * per_list), dim3(64), 0, s, q2);
-    if (tracing) bestfit_trace_report(c, p, (size_t)kBfSublists * sub_cap, s);
-    if (lists) {
-        BestfitListedArgs la{};
-        la.lists = c->idx.d_list;
-        la.nrec = c->nrec.ptr;
-        la.nlab = c->nlab.ptr;
-        la.bf_rank = c->bf_rank.ptr;
-        la.bf_order = c->bf_order.ptr;
-        la.pcpu = r.pcpu;
-        la.pmem = r.pmem;
-        la.psel = r.psel;
-        la.ptol = r.ptol;
-        la.listed_mask = q.listed_mask;
-        la.binding = r.out_binding;
-        la.p = p;
-        la.n = c->n;
-        la.nkeys = c->nkeys;
-        la.tiles = l.tiles;
-        la.nlist = l.nlist;
-        for (uint32_t j = 0; j < l.nlist; ++j) la.list_col[j] = l.list_col[j];
-        la.do_fit = q.do_fit;
-        la.do_taint = q.do_taint;
-        hipLaunchKernelGGL(k_pick_bestfit_listed, dim3((p + 3) / 4), dim3(256), 0, s, la);
-    }
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
@@ -1140,7 +1167,7 @@ EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
     f.fused_applicable = fused_applicable(c->idx, t);
     f.fused_pick_applicable = fused_pick_applicable(c->idx, t, r.p);
     f.fused_tile_pick_applicable = fused_tile_pick_applicable(c->idx.lay, t, r.attempts);
-    f.bf_rows_built = c->bf_rows_built;
+    f.bf_rows_built = c->bestfit.rows_built;
     f.fused_waves = kFusedWaves;
     f.opt_kernel = c->opt_kernel;
     f.opt_fused_pick = c->opt_fused_pick;
@@ -1157,7 +1184,7 @@ int fail_plan(ksched_ctx *c, const EvalPlan &plan) {
             c->last_error = "the tile-test pick is not applicable to this request (attempts != 5, taints, more than eight label keys, or no room in LDS)";
             break;
         case PlanError::kListKeysTooManyNodes:
-            c->last_error = "best fit over a snapshot with list keys supports at most 2097152 nodes";
+            c->last_error = "best fit over a snapshot with list keys supports at most " + std::to_string(kBfLanesMaxNodes) + " nodes";
             break;
         default: return fail_fused_not_applicable(c);
     }
@@ -1309,21 +1336,12 @@ void ksched_destroy(ksched_ctx *c) try {
     {
         DeviceGuard g(c->device);
         (void)hipDeviceSynchronize();
-        c->ncpu.release(); c->nmem.release(); c->nrec.release(); c->nlab.release(); c->ntaint.release();
-        c->bf_order.release(); c->bf_rank.release(); c->bf_mem.release(); c->bf_cpu.release(); c->cpu_sorted.release(); c->bf_rows.release(); c->bf_samples.release(); c->bf_levels.release(); c->bf_fallback.release(); c->bf_fallback_zeroed_cap = 0;
-        c->pcpu.release(); c->pmem.release(); c->psel.release(); c->psamples.release();
-        c->ptol.release(); c->feas.release(); c->fit.release(); c->binding.release(); c->gathered.release(); c->xpairs.release(); c->xreason.release(); c->sum_part.release(); c->sum_out.release();
-        c->scratch_mask.release(); c->trace.release();
-        c->by_cpu.release(); c->cpurank.release(); c->d_stage.release();
-        for (int b = 0; b < 2; ++b) { c->srt_k0[b].release(); c->srt_k1[b].release(); c->srt_idx[b].release(); }
         if (c->h_stage) (void)hipHostFree(c->h_stage);
-        for (auto &x : c->pick_acc) x.buf.release();
         for (auto &u : c->user_streams) (void)hipEventDestroy(u.ev);
         if (c->ev_build) (void)hipEventDestroy(c->ev_build);
         if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
         if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
         if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
-        c->apply_acc.release(); c->apply_claim.release(); c->apply_ovf.release(); c->apply_dirty.release(); c->apply_gath.release();
         indexed_release(c->idx);
         {  // masks the caller never handed back (ksched_mask_alloc)
             MaskRegistry &reg = mask_registry();
@@ -1339,8 +1357,8 @@ void ksched_destroy(ksched_ctx *c) try {
             (void)hipEventDestroy(ep.b);
         }
         if (c->stream) (void)hipStreamDestroy(c->stream);
+        delete c;  // every device buffer goes with its owner, while the ctx's device is still the current one
     }
-    delete c;
 } catch (...) {  // nothing unwinds across the C ABI
 }
 
@@ -1460,11 +1478,7 @@ int ksched_set_nodes(ksched_ctx *c, uint32_t n, const int64_t *cpu, const int64_
     HIPCHK(c, c->nrec.reserve((size_t)n * kNodeRecWords));
     HIPCHK(c, c->nlab.reserve((size_t)n * n_keys));
     HIPCHK(c, c->ntaint.reserve(n));
-    HIPCHK(c, c->bf_order.reserve(n));
-    HIPCHK(c, c->bf_rank.reserve(n));
-    HIPCHK(c, c->bf_mem.reserve((size_t)n + 8));  // (+8: the 8-ary searches read whole blocks of eight)
-    HIPCHK(c, c->bf_cpu.reserve(n));
-    HIPCHK(c, c->cpu_sorted.reserve((size_t)n + 8));
+    HIPCHK(c, c->bestfit.reserve_for(n));
     hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
     // the per-tile bitmap index: layout on the host (it fixes kernel arguments and LDS sizes), contents on the device
     IndexPlan plan;

@@ -74,7 +74,7 @@ struct StageLayout {
 // What a committed change makes stale, in rising order.  The best-fit structures are rebuilt lazily (ensure_bestfit): their ORDER reads
 // `available` only, their row bitmaps read labels and taints too, in that order.  kEverything is ksched_set_nodes: a new snapshot.
 enum class Stale { kNothing, kLabels, kAvailable, kEverything };
-inline bool stale_order(Stale s) { return s >= Stale::kAvailable; }     // bf_dirty: the order, and the rows with it
-inline bool stale_rows_only(Stale s) { return s == Stale::kLabels; }    // bf_rows_dirty
+inline bool stale_order(Stale s) { return s >= Stale::kAvailable; }     // BestfitIndex::order_stale: the order, and the rows with it
+inline bool stale_rows_only(Stale s) { return s == Stale::kLabels; }    // BestfitIndex::rows_stale
 
 }  // namespace ksched
