@@ -81,7 +81,6 @@ MASK_ALLOC_SCATTER_2M = 8
 MASK_ALLOC_SCATTER_16M = 9
 MASK_ALLOC_PROBE = 11
 MASK_ALLOC_LAST = 11
-MASK_ALLOC_NAMES = {0: "auto", 1: "plain", 2: "vmm", 4: "vmm-min", 5: "contiguous", 8: "scatter-2m", 9: "scatter-16m", 11: "probe"}
 MASK_PROBE_MIN_BYTES = 128 << 20
 MASK_ALLOC_NAMES = {0: "auto", 1: "plain", 2: "vmm", 3: "vmm-1g", 4: "vmm-min", 5: "contiguous", 6: "uncached", 7: "pool", 8: "scatter-2m", 9: "scatter-16m", 10: "scatter-64k", 11: "probe"}
 

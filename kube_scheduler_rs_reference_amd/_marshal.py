@@ -1,0 +1,140 @@
+"""Caller's arrays -> checked pointers: the one place where the binding turns a tensor or a numpy array into an address.
+
+The C ABI receives bare pointers and a pod count and cannot know how large a buffer is, so this is the boundary at which a wrong shape,
+dtype, device or row pitch can still be refused (ValueError naming the argument) before it becomes an out-of-bounds access.  Every
+rule is stated once here; evaluator.py and dist.py call nothing else to obtain an address.  torch is imported on first use only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from . import _lib as L
+
+DRAWS = L.PICK_SAMPLED | L.PICK_UNIFORM  # the picks that read `samples`
+
+# element kinds of the C ABI: the torch dtypes that may stand for them (int64 stands in for uint64, int32 for uint32, bool for uint8)
+KINDS = {"i64": ("int64",), "u64": ("int64", "uint64"), "i32": ("int32",), "u32": ("int32", "uint32"), "u8": ("uint8", "bool")}
+_NP = {"i64": np.int64, "u64": np.uint64, "i32": np.int32, "u32": np.uint32}
+_torch_kinds = {}
+
+
+def _dtypes(kind: str):
+    if not _torch_kinds:
+        import torch
+        _torch_kinds.update({k: tuple(getattr(torch, n) for n in names) for k, names in KINDS.items()})
+    return _torch_kinds[kind]
+
+
+def _on_device(t, name: str, kind: str, device: int):
+    if not t.is_cuda or t.device.index != device or t.dtype not in _dtypes(kind):
+        raise ValueError(f"{name}: expected a {'/'.join(KINDS[kind])} CUDA tensor on cuda:{device}, got {t.dtype} on {t.device}")
+
+
+def device_ptr(t, name: str, kind: str, shape, device: int) -> Optional[int]:
+    """Address of a contiguous CUDA tensor of `kind` on cuda:`device` with exactly `shape` (None: any shape); None for an absent
+    tensor (and for an empty one, whose address nobody reads)."""
+    if t is None:
+        return None
+    _on_device(t, name, kind, device)
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor, got strides {tuple(t.stride())}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t.data_ptr() or None
+
+
+def mask_rows(p: int, W: int, device: int, *named_masks):
+    """([address or None per (name, mask)], row pitch in words) of the [p, W] mask views of one call: int64/uint64 CUDA tensors with unit
+    column stride, rows `pitch` >= W words apart, one pitch for all of them.  A single row (or none) has no pitch of its own: W."""
+    ptrs, pitch = [], None
+    for name, t in named_masks:
+        if t is not None:
+            _on_device(t, name, "u64", device)
+            if tuple(t.shape) != (p, W) or (W and t.stride(1) != 1) or (p > 1 and t.stride(0) < W):
+                raise ValueError(f"{name}: expected a [{p}, {W}] view with unit column stride and rows at least {W} words apart, "
+                                 f"got {tuple(t.shape)} with strides {tuple(t.stride())}")
+            tp = int(t.stride(0)) if p > 1 else W
+            if pitch is not None and tp != pitch:
+                raise ValueError(f"{name}: every mask of one call must have the same row pitch ({tp} != {pitch})")
+            pitch = tp
+        ptrs.append(None if t is None else t.data_ptr() or None)
+    return ptrs, W if pitch is None else pitch
+
+
+def host_array(a, name: str, kind: str, shape=None):
+    """C-contiguous numpy array of `kind` from whatever the caller passed (lists and strided arrays are converted), None for None;
+    `shape`: the exact shape, an entry None = any length."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=_NP[kind])
+    if shape is not None and (a.ndim != len(shape) or any(s is not None and s != d for s, d in zip(shape, a.shape))):
+        raise ValueError(f"{name}: expected shape [{', '.join('*' if s is None else str(s) for s in shape)}], got {list(a.shape)}")
+    return a
+
+
+def host_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _vp(address: Optional[int]):
+    return None if address is None else C.c_void_p(address)
+
+
+def draws(samples, name: str, flags: int, p: int, device: Optional[int] = None):
+    """(address, attempts, what the address points into): `samples` is read exactly when flags carry PICK_SAMPLED (node indices) or
+    PICK_UNIFORM (32-bit draws, column 0) and must then be a contiguous [p, attempts >= 1] uint32 array (device None: whatever numpy
+    converts) or CUDA tensor on cuda:`device`; a wrong shape would be an out-of-bounds read.  Without either flag attempts is 0 and
+    nothing reads it, whatever its shape."""
+    if device is None:
+        samples = host_array(samples, name, "u32")
+    attempts = 0
+    if flags & DRAWS:
+        if samples is None or len(samples.shape) != 2 or int(samples.shape[0]) != p or int(samples.shape[1]) < 1:
+            raise ValueError(f"{name}: expected a contiguous [{p}, attempts >= 1] array with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM, "
+                             f"got {None if samples is None else tuple(samples.shape)}")
+        attempts = int(samples.shape[1])
+    return host_ptr(samples) if device is None else _vp(device_ptr(samples, name, "u32", None, device)), attempts, samples
+
+
+class Batch(NamedTuple):
+    """One pod batch as the C ABI takes it; [:8] is the argument run every evaluation entry point shares."""
+    p: int
+    cpu: Optional[C.c_void_p]
+    mem: Optional[C.c_void_p]
+    sel: Optional[C.c_void_p]
+    tol: Optional[C.c_void_p]
+    smp: Optional[C.c_void_p]
+    attempts: int
+    flags: int
+    keep: tuple  # what the addresses point into
+
+
+def _rows(req_cpu, name: str, p: Optional[int]) -> int:
+    if p is not None:
+        return int(p)
+    if req_cpu is None or len(req_cpu.shape) != 1:
+        raise ValueError(f"{name}: expected a 1-D array of the pods' requests, got {None if req_cpu is None else tuple(req_cpu.shape)}")
+    return int(req_cpu.shape[0])
+
+
+def device_batch(device: int, n_keys: int, req_cpu, req_mem, sel_val_ids, tolerations, samples, flags: int, p: Optional[int] = None) -> Batch:
+    """torch CUDA tensors on cuda:`device`: requests int64 [p], sel_val_ids int32/uint32 [n_keys, p], tolerations int64/uint64 [p],
+    samples int32/uint32 [p, attempts] (see draws); any of them may be None.  p = len(req_cpu) unless given (the pick alone)."""
+    p = _rows(req_cpu, "req_cpu_milli", p)
+    smp, attempts, _ = draws(samples, "samples", flags, p, device)
+    cols = ((req_cpu, "req_cpu_milli", "i64", (p,)), (req_mem, "req_mem_bytes", "i64", (p,)), (sel_val_ids, "sel_val_ids", "u32", (n_keys, p)),
+            (tolerations, "tolerations", "u64", (p,)))
+    return Batch(p, *[_vp(device_ptr(*col, device)) for col in cols], smp, attempts, int(flags), (req_cpu, req_mem, sel_val_ids, tolerations, samples))
+
+
+def host_batch(n_keys: int, req_cpu, req_mem, sel_val_ids, tolerations, samples, flags: int, p: Optional[int] = None) -> Batch:
+    """The same batch from host memory: whatever numpy converts, every column 1-D of length p, sel_val_ids [n_keys][p]."""
+    cpu = host_array(req_cpu, "req_cpu_milli", "i64")
+    p = _rows(cpu, "req_cpu_milli", p)
+    smp, attempts, samples = draws(samples, "samples", flags, p)
+    keep = (cpu, host_array(req_mem, "req_mem_bytes", "i64", (p,)), host_array(sel_val_ids, "sel_val_ids", "u32", (n_keys, p)),
+            host_array(tolerations, "tolerations", "u64", (p,)))
+    return Batch(p, *map(host_ptr, keep), smp, attempts, int(flags), keep + (samples,))

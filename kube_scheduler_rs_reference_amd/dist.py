@@ -30,6 +30,7 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _marshal as M
 from .evaluator import _apply_args
 
 
@@ -63,6 +64,13 @@ def _abi_shard_bounds(lib, p: int, world: int, rank: int) -> Tuple[int, int]:
     lo, hi, cpr = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     lib.ksched_shard_bounds(int(p), int(world), int(rank), C.byref(lo), C.byref(hi), C.byref(cpr))
     return lo.value, hi.value
+
+
+def _gather_count(local) -> int:
+    """entries every rank contributes to an all-gather of bindings: `local` is 1-D"""
+    if local is None or len(local.shape) != 1:
+        raise ValueError("local: expected a 1-D int32 tensor of this rank's bindings")
+    return int(local.shape[0])
 
 
 def _summarize_rows(ev, lo: int, hi: int, req_cpu, req_mem, sel_val_ids, tolerations, flags: int):
@@ -112,30 +120,25 @@ class AbiComm:
 
     def all_gather(self, gathered: torch.Tensor, local: torch.Tensor, stream=None) -> None:
         """gathered[r * len(local) + i] = rank r's local[i] (int32 CUDA tensors), enqueued on `stream` (default: current)."""
+        rc = self._lib.ksched_allgather_bindings(*self._gather_args(gathered, local, stream or torch.cuda.current_stream(local.device)))
+        if rc != 0:
+            self._check(rc, "ksched_allgather_bindings")
+
+    def _gather_args(self, gathered, local, stream):
+        """the checked argument tuple of ksched_allgather_bindings"""
         import ctypes as C
-        if local.dtype != torch.int32 or gathered.dtype != torch.int32 or not local.is_contiguous() or not gathered.is_contiguous():
-            raise ValueError("bindings must be contiguous int32 CUDA tensors")
-        if gathered.numel() != local.numel() * self.world:
-            raise ValueError("gathered must hold world * len(local) entries")
-        stream = stream or torch.cuda.current_stream(local.device)
-        self._check(self._lib.ksched_allgather_bindings(self._h, C.c_void_p(local.data_ptr()), C.c_void_p(gathered.data_ptr()),
-                                                        local.numel(), C.c_void_p(stream.cuda_stream)), "ksched_allgather_bindings")
+        count = _gather_count(local)
+        return (self._h, C.c_void_p(M.device_ptr(local, "local", "i32", (count,), self._ev.device)),
+                C.c_void_p(M.device_ptr(gathered, "gathered", "i32", (count * self.world,), self._ev.device)), count, C.c_void_p(stream.cuda_stream))
 
     def bind_all_gather(self, gathered: torch.Tensor, local: torch.Tensor, stream):
         """The same call pre-marshalled (the checks of all_gather done once): returns a zero-argument callable that enqueues
         ksched_allgather_bindings for exactly these buffers on exactly this stream.  A step of the pipelined scheduler is tens of
         microseconds of device time; per-call argument checks and ctypes conversions are a measurable part of a host loop at that rate."""
-        import ctypes as C
-        if local.dtype != torch.int32 or gathered.dtype != torch.int32 or not local.is_contiguous() or not gathered.is_contiguous():
-            raise ValueError("bindings must be contiguous int32 CUDA tensors")
-        if gathered.numel() != local.numel() * self.world:
-            raise ValueError("gathered must hold world * len(local) entries")
-        fn, h = self._lib.ksched_allgather_bindings, self._h
-        a_local, a_gathered, a_count, a_stream = C.c_void_p(local.data_ptr()), C.c_void_p(gathered.data_ptr()), C.c_uint32(local.numel()), C.c_void_p(stream.cuda_stream)
-        check = self._check
+        fn, check, args = self._lib.ksched_allgather_bindings, self._check, self._gather_args(gathered, local, stream)
 
-        def call():
-            rc = fn(h, a_local, a_gathered, a_count, a_stream)
+        def call(_keep=(gathered, local)):
+            rc = fn(*args)
             if rc != 0:
                 check(rc, "ksched_allgather_bindings")
         return call
@@ -217,15 +220,10 @@ class LocalClique:
         self._live()
         if len(local) != self.n or len(gathered) != self.n:
             raise ValueError(f"expected {self.n} local and {self.n} gathered tensors")
-        count = int(local[0].numel())
-        for i in range(self.n):
-            for t in (local[i], gathered[i]):
-                if t.dtype != torch.int32 or not t.is_cuda or t.device.index != self._evs[i].device or not t.is_contiguous():
-                    raise ValueError(f"rank {i}: bindings must be contiguous int32 CUDA tensors on cuda:{self._evs[i].device}")
-            if local[i].numel() != count or gathered[i].numel() != count * self.n:
-                raise ValueError(f"rank {i}: every rank passes {count} bindings and receives {count * self.n}")
-        lp = (C.c_void_p * self.n)(*[t.data_ptr() for t in local])
-        gp = (C.c_void_p * self.n)(*[t.data_ptr() for t in gathered])
+        count = _gather_count(local[0])
+        lp = (C.c_void_p * self.n)(*[M.device_ptr(t, f"local[{i}]", "i32", (count,), e.device) for i, (t, e) in enumerate(zip(local, self._evs))])
+        gp = (C.c_void_p * self.n)(*[M.device_ptr(t, f"gathered[{i}]", "i32", (count * self.n,), e.device)
+                                     for i, (t, e) in enumerate(zip(gathered, self._evs))])
         self._check(self._lib.ksched_allgather_bindings_local(C.cast(self._comms, C.c_void_p), self.n, C.cast(lp, C.c_void_p),
                                                               C.cast(gp, C.c_void_p), count, C.cast(self._streams(streams), C.c_void_p)),
                     "ksched_allgather_bindings_local")

@@ -15,56 +15,26 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
+from . import _marshal as M
 
 
 def mask_words(n_nodes: int) -> int:
     return (int(n_nodes) + 63) // 64
 
 
-def _np(a, dtype, name):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=dtype)
-    return a
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-_DRAWS = L.PICK_SAMPLED | L.PICK_UNIFORM                 # the picks that read `samples`
 _PICKS = L.PICK_SAMPLED | L.PICK_BESTFIT | L.PICK_UNIFORM  # at most one per call
-
-
-def _attempts(samples, flags: int, p: int) -> int:
-    """Draws per pod of a device `samples` tensor (PICK_SAMPLED: node indices; PICK_UNIFORM: 32-bit draws, column 0 is read); a wrong
-    shape would be an out-of-bounds device read, so it is refused here."""
-    if not (flags & _DRAWS):
-        return 0
-    if samples is None or samples.dim() != 2 or int(samples.shape[0]) != p or int(samples.shape[1]) == 0 or not samples.is_contiguous():
-        raise ValueError(f"samples must be a contiguous [{p}, attempts] tensor with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM")
-    return int(samples.shape[1])
+_ptr = M.host_ptr
 
 
 def _apply_args(ev, bindings, req_cpu, req_mem, ok, status_out):
     """(count, bindings, req_cpu, req_mem, ok, status_out) of one apply on `ev`'s device (one rank's rows of a sharded one), checked: all
     [count] contiguous CUDA tensors, bindings int32, requests int64, ok uint8/bool, status_out int32.  Pointers as ints, None for an absent
     tensor (and may be None when count is 0)."""
-    import torch
-    if bindings.dim() != 1:
+    if bindings is None or len(bindings.shape) != 1:
         raise ValueError("bindings must be a 1-D int32 tensor")
     p = int(bindings.shape[0])
-
-    def dp(t, dtypes, name):
-        if t is None:
-            return None
-        if not t.is_cuda or t.device.index != ev.device or not t.is_contiguous() or t.dtype not in dtypes:
-            raise ValueError(f"{name}: expected a contiguous {dtypes} CUDA tensor on cuda:{ev.device}")
-        if tuple(t.shape) != (p,):
-            raise ValueError(f"{name}: expected shape ({p},), got {tuple(t.shape)}")
-        return t.data_ptr() or None
-    return (p, dp(bindings, (torch.int32,), "bindings"), dp(req_cpu, (torch.int64,), "req_cpu"), dp(req_mem, (torch.int64,), "req_mem"),
-            dp(ok, (torch.uint8, torch.bool), "ok"), dp(status_out, (torch.int32,), "status_out"))
+    cols = ((bindings, "bindings", "i32"), (req_cpu, "req_cpu", "i64"), (req_mem, "req_mem", "i64"), (ok, "ok", "u8"), (status_out, "status_out", "i32"))
+    return (p, *[M.device_ptr(*col, (p,), ev.device) for col in cols])
 
 
 @dataclass
@@ -171,20 +141,12 @@ class Evaluator:
 
     # -- snapshot --------------------------------------------------------------------------------
     def set_nodes(self, avail_cpu_milli, avail_mem_bytes, label_val_ids=None, taints=None):
-        cpu = _np(avail_cpu_milli, np.int64, "avail_cpu_milli")
-        mem = _np(avail_mem_bytes, np.int64, "avail_mem_bytes")
+        cpu = M.host_array(avail_cpu_milli, "avail_cpu_milli", "i64", (None,))
         n = cpu.shape[0]
-        if mem.shape != (n,):
-            raise ValueError("avail_mem_bytes shape")
-        lab = _np(label_val_ids, np.uint32, "label_val_ids")
-        n_keys = 0
-        if lab is not None:
-            if lab.ndim != 2 or lab.shape[1] != n:
-                raise ValueError("label_val_ids must be [n_keys][n]")
-            n_keys = lab.shape[0]
-        tnt = _np(taints, np.uint64, "taints")
-        if tnt is not None and tnt.shape != (n,):
-            raise ValueError("taints shape")
+        mem = M.host_array(avail_mem_bytes, "avail_mem_bytes", "i64", (n,))
+        lab = M.host_array(label_val_ids, "label_val_ids", "u32", (None, n))
+        n_keys = 0 if lab is None else lab.shape[0]
+        tnt = M.host_array(taints, "taints", "u64", (n,))
         rc = self._lib.ksched_set_nodes(self._h, n, _ptr(cpu), _ptr(mem), _ptr(lab) if n_keys else None, n_keys, _ptr(tnt))
         self._check(rc, "ksched_set_nodes")
         self.n = n
@@ -192,26 +154,18 @@ class Evaluator:
 
     def update_nodes(self, node_index, avail_cpu_milli, avail_mem_bytes):
         """New `available` values for the listed canonical node indices (ksched_update_nodes)."""
-        idx = _np(node_index, np.uint32, "node_index")
-        cpu = _np(avail_cpu_milli, np.int64, "avail_cpu_milli")
-        mem = _np(avail_mem_bytes, np.int64, "avail_mem_bytes")
-        if idx.ndim != 1 or cpu.shape != idx.shape or mem.shape != idx.shape:
-            raise ValueError("node_index, avail_cpu_milli, avail_mem_bytes must be 1-D of one length")
+        idx = M.host_array(node_index, "node_index", "u32", (None,))
+        cpu = M.host_array(avail_cpu_milli, "avail_cpu_milli", "i64", idx.shape)
+        mem = M.host_array(avail_mem_bytes, "avail_mem_bytes", "i64", idx.shape)
         self._check(self._lib.ksched_update_nodes(self._h, idx.shape[0], _ptr(idx), _ptr(cpu), _ptr(mem)), "ksched_update_nodes")
 
     def update_node_labels(self, node_index, label_val_ids=None, taints=None):
         """New label ids of every key ([n_keys][count]) and, with `taints` ([count]), new taint bits for the listed canonical node
         indices (ksched_update_node_labels); `available` is not touched."""
-        idx = _np(node_index, np.uint32, "node_index")
-        if idx.ndim != 1:
-            raise ValueError("node_index must be 1-D")
+        idx = M.host_array(node_index, "node_index", "u32", (None,))
         count = idx.shape[0]
-        lab = _np(label_val_ids, np.uint32, "label_val_ids")
-        if lab is not None and (lab.ndim != 2 or lab.shape != (self.n_keys, count)):
-            raise ValueError(f"label_val_ids must be [{self.n_keys}][{count}]")
-        tnt = _np(taints, np.uint64, "taints")
-        if tnt is not None and tnt.shape != (count,):
-            raise ValueError("taints shape")
+        lab = M.host_array(label_val_ids, "label_val_ids", "u32", (self.n_keys, count))
+        tnt = M.host_array(taints, "taints", "u64", (count,))
         rc = self._lib.ksched_update_node_labels(self._h, count, _ptr(idx), _ptr(lab) if lab is not None and lab.size else None, _ptr(tnt))
         self._check(rc, "ksched_update_node_labels")
 
@@ -244,20 +198,8 @@ class Evaluator:
         32-bit draws of which column 0 is read: uniformly among the pod's feasible nodes), WANT_FIT_MASK.
         `out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4)."""
-        cpu = _np(req_cpu_milli, np.int64, "req_cpu_milli")
-        mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
-        p = cpu.shape[0]
-        sel = _np(sel_val_ids, np.uint32, "sel_val_ids")
-        if sel is not None and sel.shape != (self.n_keys, p):
-            raise ValueError(f"sel_val_ids must be [{self.n_keys}][{p}]")
-        tol = _np(tolerations, np.uint64, "tolerations")
-        smp = _np(samples, np.uint32, "samples")
-        attempts = 0
-        if flags & _DRAWS:
-            if smp is None or smp.ndim != 2 or smp.shape[0] != p:
-                raise ValueError("samples must be [p][attempts]")
-            attempts = smp.shape[1]
-        W = self.W
+        b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
+        p, W = b.p, self.W
         res = EvalResult()
 
         def buf(prev, shape, dtype):
@@ -270,8 +212,7 @@ class Evaluator:
             res.fit = buf(out.fit if out is not None else None, (p, W), np.uint64)
         if flags & _PICKS:
             res.binding = buf(out.binding if out is not None else None, (p,), np.int32)
-        rc = self._lib.ksched_eval(self._h, p, _ptr(cpu), _ptr(mem), _ptr(sel), _ptr(tol), _ptr(smp), attempts, flags,
-                                   _ptr(res.feasible), _ptr(res.fit), _ptr(res.binding))
+        rc = self._lib.ksched_eval(self._h, *b[:8], _ptr(res.feasible), _ptr(res.fit), _ptr(res.binding))
         self._check(rc, "ksched_eval")
         return res
 
@@ -281,49 +222,21 @@ class Evaluator:
         """All arguments are torch CUDA tensors on this evaluator's device (int64 stands in for
         uint64, int32 for uint32).  Work is enqueued on `stream` (default: torch's current stream).  `samples` [p, attempts] is read with
         PICK_SAMPLED (node indices) and with PICK_UNIFORM (32-bit draws, column 0)."""
+        calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
+                                             [out_feasible], out_fit, [out_binding], stream)
+        self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
+
+    def _marshal_eval_device(self, cols, flags, masks, out_fit, outs, stream):
+        """calls[i][m] = the checked argument tuple of ksched_eval_device_pitched that writes bindings outs[i] and mask masks[m], and
+        what those addresses point into."""
         import torch
-
-        def dp(t, dtypes, shape=None):
-            if t is None:
-                return None
-            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.dtype not in dtypes:
-                raise ValueError(f"expected contiguous {dtypes} CUDA tensor on cuda:{self.device}")
-            if shape is not None and tuple(t.shape) != tuple(shape):
-                raise ValueError(f"expected shape {shape}, got {tuple(t.shape)}")
-            return C.c_void_p(t.data_ptr())
-
-        def mask_ptr(t, pitch):
-            """[p, W] view of a (possibly pitched) mask buffer: rows `pitch` words apart."""
-            if t is None:
-                return None, pitch
-            if not t.is_cuda or t.device.index != self.device or t.dtype not in u64 or t.dim() != 2:
-                raise ValueError(f"mask must be a 2-D int64/uint64 CUDA tensor on cuda:{self.device}")
-            if tuple(t.shape) != (p, W) or (W and t.stride(1) != 1) or (p > 1 and t.stride(0) < W):
-                raise ValueError(f"mask must be [{p}, {W}] with unit column stride, got {tuple(t.shape)} strides {t.stride()}")
-            tp = int(t.stride(0)) if p > 1 else max(W, pitch or W)
-            if pitch is not None and tp != pitch and p > 1:
-                raise ValueError("out_feasible and out_fit must share one row pitch")
-            return C.c_void_p(t.data_ptr()), tp
-
-        p = int(req_cpu_milli.shape[0])
-        W = self.W
-        i64 = (torch.int64,)
-        u64 = (torch.int64, torch.uint64)
-        u32 = (torch.int32, torch.uint32)
-        attempts = int(samples.shape[1]) if (flags & _DRAWS and samples is not None and samples.dim() == 2) else 0
-        if flags & _DRAWS and (samples is None or samples.dim() != 2 or samples.shape[0] != p or attempts == 0):
-            raise ValueError(f"samples must be a [{p}, attempts] tensor with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM")  # a wrong shape would be an out-of-bounds device read
+        b = M.device_batch(self.device, self.n_keys, *cols, flags)
+        (*pm, pr), pitch = M.mask_rows(b.p, self.W, self.device, *[("out_feasible", m) for m in masks], ("out_fit", out_fit))
+        po = [M.device_ptr(o, "out_binding", "i32", (b.p,), self.device) for o in outs]
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        pf, pitch = mask_ptr(out_feasible, None)
-        pr, pitch = mask_ptr(out_fit, pitch)
-        rc = self._lib.ksched_eval_device_pitched(
-            self._h, p, dp(req_cpu_milli, i64, (p,)), dp(req_mem_bytes, i64, (p,)),
-            dp(sel_val_ids, u32, (self.n_keys, p)) if sel_val_ids is not None else None,
-            dp(tolerations, u64, (p,)), dp(samples, u32), attempts, flags,
-            pf, pr, dp(out_binding, (torch.int32,), (p,)), pitch if pitch is not None else W,
-            C.c_void_p(stream.cuda_stream))
-        self._check(rc, "ksched_eval_device_pitched")
+        vp, st = C.c_void_p, C.c_void_p(stream.cuda_stream)
+        return [[(self._h, *b[:8], vp(m), vp(pr), vp(o), pitch, st) for m in pm] for o in po], (b.keep, masks, out_fit, outs)
 
     def bind_eval_device(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, samples=None, flags: int = L.FIT,
                          out_feasible=None, out_fit=None, out_bindings=(), stream=None):
@@ -331,39 +244,10 @@ class Evaluator:
         that enqueues the evaluation writing out_bindings[i] (and, when `out_feasible` is a LIST of equally shaped masks, the
         mask out_feasible[m]: a loop can rotate its output over several buffers).  Saves the per-call tensor checks and pointer
         conversions (tens of microseconds of Python per step)."""
-        import torch
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
-        p, W = int(req_cpu_milli.shape[0]), self.W
-        outs = list(out_bindings) or [None]
         masks = list(out_feasible) if isinstance(out_feasible, (list, tuple)) else [out_feasible]
-        for t, dt in ((req_cpu_milli, (torch.int64,)), (req_mem_bytes, (torch.int64,))):
-            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.dtype not in dt or tuple(t.shape) != (p,):
-                raise ValueError("bind_eval_device: request columns must be contiguous int64 [p] CUDA tensors on this device")
-        if sel_val_ids is not None and (tuple(sel_val_ids.shape) != (self.n_keys, p) or not sel_val_ids.is_contiguous()):
-            raise ValueError(f"sel_val_ids must be contiguous [{self.n_keys}][{p}]")
-        for b in outs:
-            if b is not None and (b.dtype != torch.int32 or tuple(b.shape) != (p,) or not b.is_contiguous()):
-                raise ValueError("out_bindings must be contiguous int32 [p] CUDA tensors")
-        pitch = None
-        for m in masks + [out_fit]:
-            if m is not None:
-                if tuple(m.shape) != (p, W) or (W and m.stride(1) != 1):
-                    raise ValueError(f"mask must be a [{p}, {W}] view with unit column stride")
-                mp = int(m.stride(0)) if p > 1 else W
-                if pitch is not None and mp != pitch:
-                    raise ValueError("every mask of one bound evaluation must have the same row pitch")
-                pitch = mp
-        if pitch is None:
-            pitch = W
-        attempts = _attempts(samples, flags, p)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        head = (self._h, p, ptr(req_cpu_milli), ptr(req_mem_bytes), ptr(sel_val_ids), ptr(tolerations), ptr(samples), attempts, flags)
-        mids = [(ptr(m), ptr(out_fit)) for m in masks]
-        tails = [(ptr(b), pitch, C.c_void_p(stream.cuda_stream)) for b in outs]
-        keep = (req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, masks, out_fit, outs)
+        calls, keep = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
+                                                masks, out_fit, list(out_bindings) or [None], stream)
         fn, check = self._lib.ksched_eval_device_pitched, self._check
-        calls = [[head + mid + tail for mid in mids] for tail in tails]  # the whole argument tuple per (binding buffer, mask buffer), built once
 
         def run(i: int = 0, m: int = 0, _keep=keep):
             rc = fn(*calls[i][m])
@@ -377,37 +261,24 @@ class Evaluator:
         PICK_UNIFORM (+ samples [p, attempts]: 32-bit draws, column 0 is read) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask
         includes the resource fit)."""
         import torch
-        p, W = int(feasible.shape[0]), self.W
-        if not feasible.is_cuda or feasible.dim() != 2 or feasible.shape[1] != W or (W and feasible.stride(1) != 1):
-            raise ValueError(f"feasible must be a [p, {W}] CUDA mask with unit column stride")
-        pitch = int(feasible.stride(0)) if p > 1 else W  # a single row: any pitch >= W
-        if out_binding.dtype != torch.int32 or tuple(out_binding.shape) != (p,) or not out_binding.is_contiguous():
-            raise ValueError("out_binding must be a contiguous int32 [p] CUDA tensor")
-        attempts = _attempts(samples, flags, p)
+        if feasible is None or len(feasible.shape) != 2:
+            raise ValueError(f"feasible must be a [p, {self.W}] CUDA mask with unit column stride")
+        b = M.device_batch(self.device, self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=feasible.shape[0])
+        (pf,), pitch = M.mask_rows(b.p, self.W, self.device, ("feasible", feasible))
+        po = M.device_ptr(out_binding, "out_binding", "i32", (b.p,), self.device)
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        rc = self._lib.ksched_pick_device(self._h, p, ptr(feasible), pitch, ptr(req_mem_bytes), ptr(samples), attempts, flags,
-                                          ptr(out_binding), C.c_void_p(stream.cuda_stream))
+        rc = self._lib.ksched_pick_device(self._h, b.p, pf, pitch, b.mem, b.smp, b.attempts, b.flags, po, C.c_void_p(stream.cuda_stream))
         self._check(rc, "ksched_pick_device")
 
     def pick(self, feasible: np.ndarray, flags: int, req_mem_bytes=None, samples=None) -> np.ndarray:
         """The pick alone from HOST masks (ksched_pick): `feasible` = [p, W] uint64 rows as `eval` returns them (or as a caller has combined
         them: ANDed masks of a selector evaluated in key groups).  flags: PICK_SAMPLED (+ samples [p, attempts]), PICK_UNIFORM (+ samples
         [p, attempts]: 32-bit draws, column 0 is read) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
-        f = np.ascontiguousarray(feasible, dtype=np.uint64)
-        if f.ndim != 2 or f.shape[1] != self.W:
-            raise ValueError(f"feasible must be [p, {self.W}] uint64")
-        p = f.shape[0]
-        mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
-        smp = _np(samples, np.uint32, "samples")
-        attempts = 0
-        if flags & _DRAWS:
-            if smp is None or smp.ndim != 2 or smp.shape[0] != p:
-                raise ValueError("samples must be [p][attempts]")
-            attempts = smp.shape[1]
-        out = np.empty((p,), dtype=np.int32)
-        rc = self._lib.ksched_pick(self._h, p, _ptr(f), _ptr(mem), _ptr(smp), attempts, flags, _ptr(out))
+        f = M.host_array(feasible, "feasible", "u64", (None, self.W))
+        b = M.host_batch(self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=f.shape[0])
+        out = np.empty((b.p,), dtype=np.int32)
+        rc = self._lib.ksched_pick(self._h, b.p, _ptr(f), b.mem, b.smp, b.attempts, b.flags, _ptr(out))
         self._check(rc, "ksched_pick")
         return out
 
@@ -441,37 +312,20 @@ class Evaluator:
     # -- reasons -------------------------------------------------------------------------------------
     def explain(self, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, pair_pod, pair_node, flags: int) -> np.ndarray:
         """ksched_explain: REASON_* of check_node_validity for the listed (pod, node) pairs, decided on the device."""
-        cpu = _np(req_cpu_milli, np.int64, "req_cpu_milli")
-        mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
-        p = cpu.shape[0]
-        sel = _np(sel_val_ids, np.uint32, "sel_val_ids")
-        if sel is not None and sel.shape != (self.n_keys, p):
-            raise ValueError(f"sel_val_ids must be [{self.n_keys}][{p}]")
-        tol = _np(tolerations, np.uint64, "tolerations")
-        pp, pn = _np(pair_pod, np.uint32, "pair_pod"), _np(pair_node, np.uint32, "pair_node")
-        if pp.ndim != 1 or pp.shape != pn.shape:
-            raise ValueError("pair_pod, pair_node must be 1-D of one length")
-        out = np.empty((pp.shape[0],), dtype=np.int32)
-        rc = self._lib.ksched_explain(self._h, p, _ptr(cpu), _ptr(mem), _ptr(sel), _ptr(tol), pp.shape[0], _ptr(pp), _ptr(pn), flags, _ptr(out))
+        b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
+        pp = M.host_array(pair_pod, "pair_pod", "u32", (None,))
+        pn = M.host_array(pair_node, "pair_node", "u32", pp.shape)
+        out = np.empty(pp.shape, dtype=np.int32)
+        rc = self._lib.ksched_explain(self._h, *b[:5], pp.shape[0], _ptr(pp), _ptr(pn), flags, _ptr(out))
         self._check(rc, "ksched_explain")
         return out
 
     def summarize(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, flags: int = L.FIT) -> np.ndarray:
         """ksched_summarize: per pod the number of nodes check_node_validity accepts / rejects by reason, [p, SUMMARY_WORDS] uint32
         (column r = REASON_*; column 0 = feasible nodes; every row adds up to the node count)."""
-        cpu = _np(req_cpu_milli, np.int64, "req_cpu_milli")
-        mem = _np(req_mem_bytes, np.int64, "req_mem_bytes")
-        p = cpu.shape[0]
-        if cpu.ndim != 1 or mem.shape != (p,):
-            raise ValueError("req_cpu_milli, req_mem_bytes must be 1-D of one length")
-        sel = _np(sel_val_ids, np.uint32, "sel_val_ids")
-        if sel is not None and sel.shape != (self.n_keys, p):
-            raise ValueError(f"sel_val_ids must be [{self.n_keys}][{p}]")
-        tol = _np(tolerations, np.uint64, "tolerations")
-        if tol is not None and tol.shape != (p,):
-            raise ValueError(f"tolerations must be [{p}]")
-        out = np.empty((p, L.SUMMARY_WORDS), dtype=np.uint32)
-        rc = self._lib.ksched_summarize(self._h, p, _ptr(cpu), _ptr(mem), _ptr(sel), _ptr(tol), int(flags), _ptr(out))
+        b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
+        out = np.empty((b.p, L.SUMMARY_WORDS), dtype=np.uint32)
+        rc = self._lib.ksched_summarize(self._h, *b[:5], int(flags), _ptr(out))
         self._check(rc, "ksched_summarize")
         return out
 
@@ -480,33 +334,18 @@ class Evaluator:
         (default: torch's current stream), the host does not wait.  `out`: a contiguous [p, SUMMARY_WORDS] int32/uint32 tensor
         (allocated when None; it need not be zeroed).  Returns it."""
         import torch
-
-        def dp(t, dtypes, shape):
-            if t is None:
-                return None
-            if not t.is_cuda or t.device.index != self.device or not t.is_contiguous() or t.dtype not in dtypes:
-                raise ValueError(f"expected contiguous {dtypes} CUDA tensor on cuda:{self.device}")
-            if tuple(t.shape) != tuple(shape):
-                raise ValueError(f"expected shape {shape}, got {tuple(t.shape)}")
-            return C.c_void_p(t.data_ptr())
-
-        p = int(req_cpu_milli.shape[0])
-        u64 = (torch.int64, torch.uint64)
-        u32 = (torch.int32, torch.uint32)
+        b = M.device_batch(self.device, self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         if out is None:
-            out = torch.empty((p, L.SUMMARY_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
+            out = torch.empty((b.p, L.SUMMARY_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
+        po = M.device_ptr(out, "out", "u32", (b.p, L.SUMMARY_WORDS), self.device)
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
-        rc = self._lib.ksched_summarize_device(
-            self._h, p, dp(req_cpu_milli, (torch.int64,), (p,)), dp(req_mem_bytes, (torch.int64,), (p,)),
-            dp(sel_val_ids, u32, (self.n_keys, p)), dp(tolerations, u64, (p,)), int(flags), dp(out, u32, (p, L.SUMMARY_WORDS)),
-            C.c_void_p(stream.cuda_stream))
+        rc = self._lib.ksched_summarize_device(self._h, *b[:5], int(flags), po, C.c_void_p(stream.cuda_stream))
         self._check(rc, "ksched_summarize_device")
         return out
 
     def reason(self, feasible_row: np.ndarray, fit_row: Optional[np.ndarray], node: int, flags: int) -> int:
-        f = np.ascontiguousarray(feasible_row, dtype=np.uint64)
-        r = None if fit_row is None else np.ascontiguousarray(fit_row, dtype=np.uint64)
+        f, r = M.host_array(feasible_row, "feasible_row", "u64"), M.host_array(fit_row, "fit_row", "u64")
         return self._lib.ksched_reason(_ptr(f), _ptr(r), int(node), int(flags))
 
 
@@ -565,31 +404,32 @@ class Pipe:
         """ksched_pipe_slot_stream as the raw hipStream_t (0 before the slot's first submit): the cheap form for a per-step check."""
         return int(self._lib.ksched_pipe_slot_stream(self._h, slot) or 0)
 
+    def _marshal(self, cols, flags, masks, bindings):
+        """(the batch, [(mask, pitch, binding) per slot]) as ksched_pipe_submit takes them, checked"""
+        ev = self.ev
+        b = M.device_batch(ev.device, ev.n_keys, *cols, flags)
+        per_slot = []
+        for m, o in zip(masks, bindings):
+            (pm,), pitch = M.mask_rows(b.p, ev.W, ev.device, ("mask", m))
+            per_slot.append((C.c_void_p(pm), pitch, C.c_void_p(M.device_ptr(o, "binding", "i32", (b.p,), ev.device))))
+        return b, per_slot
+
     def submit(self, slot: int, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags: int, mask, binding):
         """torch CUDA tensors (see Evaluator.eval_device); `mask` is a [p, W] (possibly pitched) view, `binding` int32 [p].  flags carry one
         of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM (the uniform pick reads the mask: its slot runs in the split mode, ordered by events)."""
-        p, W = int(req_cpu_milli.shape[0]), self.ev.W
-        pitch = int(mask.stride(0)) if p > 1 else W
-        attempts = _attempts(samples, flags, p)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        rc = self._lib.ksched_pipe_submit(self._h, slot, p, ptr(req_cpu_milli), ptr(req_mem_bytes), ptr(sel_val_ids), ptr(tolerations),
-                                          ptr(samples), attempts, flags, ptr(mask), pitch, ptr(binding))
-        self.ev._check(rc, "ksched_pipe_submit")
+        b, per_slot = self._marshal((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags, [mask], [binding])
+        self.ev._check(self._lib.ksched_pipe_submit(self._h, slot, *b[:8], *per_slot[0]), "ksched_pipe_submit")
 
     def bind(self, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags: int, masks, bindings):
         """Pre-marshal a batch whose inputs stay in place (steady-state loops): returns submit(slot) for slot-indexed `masks` /
         `bindings` lists.  Saves the per-call tensor -> pointer conversions (the host would otherwise bound the step rate)."""
-        p, W = int(req_cpu_milli.shape[0]), self.ev.W
-        attempts = _attempts(samples, flags, p)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        fixed = (ptr(req_cpu_milli), ptr(req_mem_bytes), ptr(sel_val_ids), ptr(tolerations), ptr(samples), attempts, flags)
-        per_slot = [(ptr(m), int(m.stride(0)) if p > 1 else W, ptr(b)) for m, b in zip(masks, bindings)]
-        keep = (req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, list(masks), list(bindings))  # keep the tensors alive
+        masks, bindings = list(masks), list(bindings)
+        b, per_slot = self._marshal((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags, masks, bindings)
+        fixed, keep = b[:8], (b.keep, masks, bindings)  # keep the tensors alive
         fn, h, check = self._lib.ksched_pipe_submit, self._h, self.ev._check
 
         def submit(slot: int, _keep=keep):
-            m, pitch, b = per_slot[slot]
-            rc = fn(h, slot, p, *fixed, m, pitch, b)
+            rc = fn(h, slot, *fixed, *per_slot[slot])
             if rc:
                 check(rc, "ksched_pipe_submit")
         return submit
