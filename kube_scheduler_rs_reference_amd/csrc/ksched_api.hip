@@ -1703,6 +1703,7 @@ struct ksched_pipe {
     std::vector<hipStream_t> slot_stream;  // the stream that carries the slot's mask kernel (alternate mode: also its pick)
     std::vector<hipStream_t> pick_stream;  // the stream that carried the slot's latest pick (ksched_pipe_slot_stream)
     std::vector<uint8_t> last_split;       // the slot's latest submit ran in the split mode (its mask kernel and its pick on different streams)
+    std::vector<uint8_t> pick_read_mask;   // the slot's latest pick read the slot's mask (split mode): the next mask kernel into it waits for that pick
 };
 
 int ksched_pipe_create(ksched_ctx *c, uint32_t depth, ksched_pipe **out) try {
@@ -1719,6 +1720,7 @@ int ksched_pipe_create(ksched_ctx *c, uint32_t depth, ksched_pipe **out) try {
     q->slot_stream.assign(depth, nullptr);
     q->pick_stream.assign(depth, nullptr);
     q->last_split.assign(depth, 0);
+    q->pick_read_mask.assign(depth, 0);
     for (uint32_t i = 0; ok && i < 2 * depth; ++i) {
         hipEvent_t e;
         ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
@@ -1808,6 +1810,7 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
         if (q->pick_stream[slot] && (q->pick_stream[slot] != st || q->last_split[slot])) HIPCHK(c, hipStreamWaitEvent(st, q->pick_done[slot], 0));
         if (q->last_split[slot] && q->slot_stream[slot] != st) HIPCHK(c, hipStreamWaitEvent(st, q->mask_done[slot], 0));  // (the split mode records it after every mask kernel)
         q->last_split[slot] = 0;
+        q->pick_read_mask[slot] = 0;
         q->slot_stream[slot] = st;
         q->pick_stream[slot] = st;
         r.stream = st;
@@ -1822,7 +1825,10 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     }
     q->slot_stream[slot] = sm;
     q->pick_stream[slot] = q->s_pick;
-    if (reads_mask) HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));  // the slot's mask may be overwritten once its pick has run
+    // the slot's mask may be overwritten once the pick that reads it has run: this submit's own pick orders the slot's NEXT mask kernel, and
+    // the previous submit's pick this one (also when this submit's pick reads no mask: a sampled submit into a slot whose last pick was uniform)
+    if (reads_mask || q->pick_read_mask[slot]) HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));
+    q->pick_read_mask[slot] = reads_mask ? 1 : 0;
     q->last_split[slot] = 1;
     if ((rc = eval_on_device(c, EvalRequest{p, pcpu, pmem, psel, ptol, nullptr, 0, flags & ~pick, mask, nullptr, nullptr, mask_pitch_words, sm}))) return rc;
     HIPCHK(c, hipEventRecord(q->mask_done[slot], sm));  // (always: a later submit of this slot in the alternate mode orders itself behind this mask kernel)

@@ -17,10 +17,11 @@ import sys
 import numpy as np
 import torch
 
-from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth
+from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth, unpack_mask
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact
 from tests.test_gpu_apply_bindings import random_bindings
+from tests.uniform_ref import uniform_pick_blocks
 
 DEV = torch.device("cuda:0")
 FPN, REL = _lib.APPLY_FIRST_PER_NODE, _lib.APPLY_RELEASE
@@ -73,7 +74,9 @@ def snapshot(kind, N, P, seed):
         raise ValueError(kind)
     return dict(kind=kind, N=N, P=P, cpu=c.avail_cpu.copy(), mem=c.avail_mem.copy(), lab=np.ascontiguousarray(lab), tnt=tnt,
                 rc=c.req_cpu, rm=c.req_mem, sel=np.ascontiguousarray(sel), tol=tol, preds=preds, indexed=kind != "unindexed",
-                smp5=rng.integers(0, N + 2, (P, 5)).astype(np.uint32), smp3=rng.integers(0, N, (P, 3)).astype(np.uint32))
+                smp5=rng.integers(0, N + 2, (P, 5)).astype(np.uint32), smp3=rng.integers(0, N, (P, 3)).astype(np.uint32),
+                # full-range 32-bit draws for the uniform pick, from a generator of their own: every other value is what it was without them
+                smpU=np.random.default_rng([seed, 0x55]).integers(0, 1 << 32, (P, 5), dtype=np.uint64).astype(np.uint32))
 
 
 def set_nodes(ev, S, cpu, mem):
@@ -97,10 +100,20 @@ def want_reasons(S, cpu, mem, preds, pp, pn):
                     np.where(~ok_t, _lib.REASON_TAINT_NOT_TOLERATED, _lib.REASON_OK))).astype(np.int32)
 
 
-def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False):
+def assert_input_condition(feas, N, what):
+    """the uniform legs cannot pass vacuously: half the pods or more choose among two or more feasible nodes (the rank arithmetic runs), and
+    one in a hundred or more has none (the rule of tests/test_gpu_uniform_pick.py)"""
+    cnt = unpack_mask(feas, N).sum(axis=1)
+    two, none = float((cnt >= 2).mean()), float((cnt == 0).mean())
+    print(f"{what}: {100 * two:.1f} % of the pods have two or more feasible nodes, {100 * none:.1f} % none")
+    assert two >= 0.50 and none >= 0.01, f"{what}: {100 * two:.1f} % of the pods have two or more feasible nodes, {100 * none:.1f} % none"
+
+
+def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False):
     """every evaluation path of `ev` (whose snapshot should hold cpu / mem) against the oracle; the names of the picks that ran go into
     `seen`.  reduced: the kernels and options at their defaults, plus the direct kernel, the waves-form pick, bindings-only "select",
-    best fit, ksched_pick and ksched_explain.  -> the device bindings of a sampled pick (a real evaluation's bindings for the next apply)"""
+    best fit, the uniform pick, ksched_pick and ksched_explain.  input_condition: assert_input_condition on every predicate set's mask.
+    -> the device bindings of a sampled pick, or with hand_on="uniform" of a uniform pick (a real evaluation's bindings for the next apply)"""
     P, N = S["P"], S["N"]
     rc, rm, sel = S["rc"], S["rm"], S["sel"]
     out_b = None
@@ -111,6 +124,9 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False):
         feas, fit, bind_s = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, S["smp5"], preds | PICK_SAMPLED | WANT_FIT_MASK)
         bind_b = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, None, preds | PICK_BESTFIT, want_mask=False)[2]
         bind_3 = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, S["smp3"], preds | PICK_SAMPLED, want_mask=False)[2]
+        bind_u = uniform_pick_blocks(feas, S["smpU"][:, 0], N)  # KSCHED_PICK_UNIFORM restated, on the oracle's mask
+        if input_condition:
+            assert_input_condition(feas, N, w)
 
         def run(flags, smp=None, want_mask=True, expect_b=None, label=""):
             r = ev.eval(rc, rm, sel, tol, smp, flags, want_mask=want_mask)
@@ -148,10 +164,12 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False):
                 ev.set_option(_lib.OPT_BESTFIT_STAGES, stages)
                 run(preds | PICK_BESTFIT, expect_b=bind_b, label=f"{k} best fit stages={stages}")
             ev.set_option(_lib.OPT_BESTFIT_STAGES, 0)
+            run(preds | PICK_UNIFORM, S["smpU"], expect_b=bind_u, label=f"{k} uniform")
         ev.set_kernel("auto")
         # bindings only: the sampled pick is its own launch ("select"), best fit reads no mask
         run(preds | PICK_SAMPLED, S["smp5"], want_mask=False, expect_b=bind_s, label="sampled, bindings only")
         run(preds | PICK_BESTFIT, want_mask=False, expect_b=bind_b, label="best fit, bindings only")
+        run(preds | PICK_UNIFORM, S["smpU"], want_mask=False, expect_b=bind_u, label="uniform, bindings only")  # the mask goes to the ctx's scratch
         if not reduced:  # the mask-reading picks
             ev.set_option(_lib.OPT_PICK_FROM_MASK, 1)
             run(preds | PICK_SAMPLED, S["smp5"], expect_b=bind_s, label="sampled from the mask")
@@ -171,14 +189,26 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False):
         seen.add(ev.last_pick)
         torch.cuda.synchronize()
         assert np.array_equal(m.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask"
-        for got, want, lbl in ((bs, bind_s, "sampled"), (bs0, bind_s, "sampled, bindings only"), (bb, bind_b, "best fit")):
+        smpu_t = t(S["smpU"], np.int32)
+        mu = torch.empty((P, ev.W), dtype=torch.int64, device=DEV)
+        bu, bu0 = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smpu_t, preds | PICK_UNIFORM, out_feasible=mu, out_binding=bu)
+        assert ev.last_pick == "uniform", f"{w}: a uniform pick beside the mask ran as {ev.last_pick}"
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smpu_t, preds | PICK_UNIFORM, out_binding=bu0)
+        assert ev.last_pick == "uniform", f"{w}: a bindings-only uniform pick ran as {ev.last_pick}"
+        seen.add(ev.last_pick)
+        torch.cuda.synchronize()
+        assert np.array_equal(mu.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask beside the uniform pick"
+        for got, want, lbl in ((bs, bind_s, "sampled"), (bs0, bind_s, "sampled, bindings only"), (bb, bind_b, "best fit"),
+                               (bu, bind_u, "uniform"), (bu0, bind_u, "uniform, bindings only")):
             assert np.array_equal(got.cpu().numpy(), want), f"{w}: eval_device {lbl} bindings"
         if out_b is None:
-            out_b = bs.cpu().numpy()
+            out_b = (bu if hand_on == "uniform" else bs).cpu().numpy()
         # the pick alone from the oracle's host mask (ksched_pick)
         assert np.array_equal(ev.pick(feas, PICK_SAMPLED, samples=S["smp5"]), bind_s), f"{w}: ksched_pick sampled"
         assert np.array_equal(ev.pick(feas, PICK_BESTFIT | (preds & FIT), req_mem_bytes=rm if preds & FIT else None), bind_b), \
             f"{w}: ksched_pick best fit"
+        assert np.array_equal(ev.pick(feas, PICK_UNIFORM, samples=S["smpU"]), bind_u), f"{w}: ksched_pick uniform"
         # per-pair reasons
         n_pairs = 4000
         pp, pn = rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
@@ -227,7 +257,10 @@ def case_single(spec):
         else:
             assert ev.index_checksum() == (0, 0), f"{kind} N={N}: the snapshot was indexed"
         rng = np.random.default_rng(N)
-        bind = check_matrix(ev, S, cpu, mem, seen, f"{kind} N={N} before any apply", rng)
+        # real bindings come from the sampled pick and, every second time, from the uniform pick: more pods bound, the lowest feasible nodes
+        # not favoured (the rounds that apply real bindings are those with i + r even)
+        hand_on = lambda r: "uniform" if ((i + r) // 2) % 2 else "sampled"  # noqa: E731
+        bind = check_matrix(ev, S, cpu, mem, seen, f"{kind} N={N} before any apply", rng, hand_on=hand_on(0), input_condition=N >= 1025)
         applied = 0
         for r in range(rounds):
             src, flags, use_ok = FORMS[(i + r) % len(FORMS)]
@@ -238,12 +271,12 @@ def case_single(spec):
             what = f"{kind} N={N} round {r} ({src} bindings, flags={flags}, ok={use_ok})"
             cpu, mem, st = apply_and_check(ev, ref, S, cpu, mem, b, ok if use_ok else None, flags, what)
             applied += int((st == _lib.APPLY_APPLIED).sum())
-            bind = check_matrix(ev, S, cpu, mem, seen, what, rng)
+            bind = check_matrix(ev, S, cpu, mem, seen, what, rng, hand_on=hand_on(r + 1))
         assert applied > 0, f"{kind} N={N}: no pod was applied"
-    want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask"},
-            "many-keys": {"select", "fused", "bestfit-rows", "from-mask"},
-            "list-key": {"select", "bestfit-rows", "from-mask"},
-            "unindexed": {"select", "from-mask"}}[kind]
+    want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask", "uniform"},
+            "many-keys": {"select", "fused", "bestfit-rows", "from-mask", "uniform"},
+            "list-key": {"select", "bestfit-rows", "from-mask", "uniform"},
+            "unindexed": {"select", "from-mask", "uniform"}}[kind]
     assert want <= seen, f"{kind}: picks reached {sorted(seen)}, missing {sorted(want - seen)}"
     print(f"{kind}: picks reached {sorted(seen)}")
     ev.close()

@@ -383,7 +383,8 @@ def case_paths(spec):
             R = Ranks(n, dict(avail_cpu_milli=S["cpu"], avail_mem_bytes=S["mem"], label_val_ids=S["lab"], taints=S["tnt"]))
             cpu, mem = S["cpu"], S["mem"]
             rng = np.random.default_rng(N + n)
-            bind = check_matrix(R.evs[0], S, cpu, mem, seen, f"{kind} N={N} before any apply", rng, reduced=True)
+            bind = check_matrix(R.evs[0], S, cpu, mem, seen, f"{kind} N={N} before any apply", rng, reduced=True, hand_on="uniform" if k % 4 else "sampled",
+                                input_condition=N >= 1025)  # (round 0 applies these bindings: every second snapshot the uniform pick's)
             for r in range(2):
                 k += 1
                 flags, use_ok = (0, FPN, REL, FPN | REL)[k % 4], k % 3 != 0
@@ -402,7 +403,7 @@ def case_paths(spec):
                     if q == 0:
                         bind = bq
             R.close()
-    assert {"select", "fused", "bestfit-rows"} <= seen, f"picks reached {sorted(seen)}"
+    assert {"select", "fused", "bestfit-rows", "uniform"} <= seen, f"picks reached {sorted(seen)}"
     print(f"{k} sharded applies, picks reached {sorted(seen)}")
 
 

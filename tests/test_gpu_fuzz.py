@@ -1,8 +1,10 @@
 """A short run of the randomised differential test (tools/fuzz_parity.py): random shapes, key counts / cardinalities (rows, list
-keys, more than eight keys), taints, predicate subsets, both picks, snapshot updates and on-device applies of the previous
-evaluation's bindings between evaluations, both kernels -- every mask word and binding against the oracle.  (A 240 s run of the same
-tool: 1217 cases, 0 failures.)"""
+keys, more than eight keys), taints, predicate subsets, the sampled and best-fit picks, snapshot updates (available, or labels and taints)
+and on-device applies of the previous evaluation's bindings between evaluations, both kernels -- every mask word and binding against the
+oracle; and at every step the uniform pick against tests/uniform_ref.py on the oracle's mask.  (A 240 s run of the same tool:
+profiles/uniform_pick_standing_checks.txt.)"""
 import os
+import re
 import subprocess
 import sys
 
@@ -12,11 +14,24 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def tally(out, name):
+    m = re.search(rf"'{re.escape(name)}': (\d+)", out)
+    return int(m.group(1)) if m else 0
+
+
+def assert_new_tallies(out):
+    print(out[-1500:])
+    assert tally(out, "uniform") > 0, "no evaluation ran the uniform pick"
+    assert tally(out, "uniform-ranked") > 0, "no uniform pick chose among two or more feasible nodes"
+    assert tally(out, "labels") > 0, "no case updated node labels between evaluations"
+
+
 def test_fuzz_parity_short(built):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_parity.py"), "12", "20260923"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert "0 failures" in r.stdout
     assert "'apply': " in r.stdout, "no case applied an evaluation's bindings on the device"
+    assert_new_tallies(r.stdout)
 
 
 def test_fuzz_parity_short_with_the_multi_device_sequence(built):
@@ -32,3 +47,6 @@ def test_fuzz_parity_short_with_the_multi_device_sequence(built):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert "gathered-over-" in r.stdout and " 0 failures" in r.stdout
     assert "'apply': " in r.stdout and "'sharded-apply-over-" in r.stdout, "no case applied bindings on the device, or none over replicas"
+    assert_new_tallies(r.stdout)
+    assert re.search(r"'gathered-over-\d': [1-9]", r.stdout), "no sampled or best-fit case went through the multi-device sequence"
+    assert re.search(r"'uniform-gathered-over-\d': [1-9]", r.stdout), "no uniform pick went through the multi-device sequence"

@@ -394,6 +394,103 @@ def test_pipe_submit_equals_eval_device_pitched(ev, mode):
         ev.set_option(_lib.OPT_PIPE_MODE, 0)
 
 
+# ---- 10b. one pipe, mixed picks ----------------------------------------------------------------------------------------------
+def mid_sampled():
+    """the oracle's sampled bindings of the MID cluster (its own [P, 5] table of node draws), computed once"""
+    k = case(MID)
+    if "sampled" not in k:
+        c = k["c"]
+        k["sampled"] = capi.eval_encoded(c.avail_cpu, c.avail_mem, c.node_labels, None, c.req_cpu, c.req_mem, np.ascontiguousarray(c.pod_sel), None,
+                                         c.samples, k["flags"] | PICK_SAMPLED, want_mask=False)[2]
+    return k["sampled"]
+
+
+def mid_batch(ev, lo, hi, uniform):
+    """pods [lo, hi) of the MID cluster as one pipe submit: (device columns incl. the draws, flags, expected mask, expected bindings)"""
+    k = case(MID)
+    c = k["c"]
+    cols = pod_tensors(ev, c, lo, hi) + (to_dev(ev, (k["draws"] if uniform else c.samples)[lo:hi], np.int32),)
+    want = k["want"] if uniform else mid_sampled()
+    return cols, k["flags"] | (PICK_UNIFORM if uniform else PICK_SAMPLED), k["feas"][lo:hi], want[lo:hi]
+
+
+@pytest.mark.parametrize("mode", [0, 2, 3])
+def test_one_pipe_alternates_uniform_and_sampled_submits_on_the_same_slots(ev, mode):
+    """Nine submits into a pipe of depth 3, uniform and sampled in turn (slot 0: U S U, slot 1: S U S, slot 2: U S U), every submit a
+    different slice of the MID cluster into the slot's one mask and one binding buffer, with no host wait in between.  The bindings of every
+    submit (copied on the slot's pick stream right behind it) and the final mask and bindings of every slot equal the oracle's.
+
+    The orderings of ksched_pipe_submit this goes through.  The uniform pick reads the mask, so its submits always take the split route:
+    mask kernel on the mask stream behind the slot's previous pick (its mask may be overwritten only once that pick has run), pick on the
+    pick stream behind that mask kernel.  Mode 0: the sampled submits take the split route too, and a sampled submit's mask kernel waits for
+    the slot's previous pick where that pick read the mask (U -> S).  Modes 2 and 3: a sampled submit runs whole on stream slot mod k, which
+    first waits for the split submit's mask kernel and pick (U -> S); the next uniform submit's two streams wait for that stream's pick
+    (S -> U), unless it was the pick stream itself (slot 1 mod k)."""
+    import torch
+    P, step, size, submits = 1200, 100, 300, 9
+    ev.set_nodes(**case(MID)["c"].node_columns())
+    ev.set_option(_lib.OPT_PIPE_MODE, mode)
+    pipe = ev.pipe(3)
+    try:
+        masks = [ev.alloc_mask(size, pitched=True) for _ in range(3)]
+        outs = [torch.full((size,), -7, dtype=torch.int32, device=dev_of(ev)) for _ in range(3)]
+        copies = torch.full((submits, size), -7, dtype=torch.int32, device=dev_of(ev))
+        torch.cuda.synchronize()
+        batches = [mid_batch(ev, i * step, i * step + size, uniform=i % 2 == 0) for i in range(submits)]  # (inputs stay alive and untouched)
+        assert batches[-1][2].shape[0] == size and (submits - 1) * step + size <= P
+        torch.cuda.synchronize()
+        for i, (cols, flags, _, _) in enumerate(batches):
+            slot = i % 3
+            pipe.submit(slot, *cols, flags, masks[slot], outs[slot])
+            with torch.cuda.stream(pipe.slot_stream(slot)):
+                copies[i].copy_(outs[slot])
+        for slot in range(3):
+            pipe.wait(slot, host=True)
+            pipe.wait_mask(slot, host=True)
+        torch.cuda.synchronize()
+        got = copies.cpu().numpy()
+        for i, (_, flags, _, want) in enumerate(batches):
+            assert np.array_equal(got[i], want), f"mode {mode}: bindings of submit {i} (slot {i % 3}, {'uniform' if flags & PICK_UNIFORM else 'sampled'})"
+        for slot in range(3):
+            _, _, feas, want = batches[submits - 3 + slot]
+            assert np.array_equal(mask_np(masks[slot]), feas), f"mode {mode}: final mask of slot {slot}"
+            assert np.array_equal(outs[slot].cpu().numpy(), want), f"mode {mode}: final bindings of slot {slot}"
+    finally:
+        pipe.close()
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+def test_a_sampled_submit_does_not_overwrite_the_mask_its_slots_uniform_pick_still_reads(ev):
+    """The reduced case of a missing ordering in the split route: a uniform submit whose pick is held up on the pick stream (by the caller's
+    own work enqueued there, here a short device-side spin), then a sampled submit of another batch into the same slot.  The sampled
+    submit's mask kernel must wait for the uniform pick, or that pick ranks the set bits of the other batch's mask."""
+    import torch
+    ev.set_nodes(**case(MID)["c"].node_columns())
+    ev.set_option(_lib.OPT_PIPE_MODE, 0)
+    pipe = ev.pipe(1)
+    try:
+        size = 300
+        mask = ev.alloc_mask(size, pitched=True)
+        out = torch.full((size,), -7, dtype=torch.int32, device=dev_of(ev))
+        first = torch.full((size,), -7, dtype=torch.int32, device=dev_of(ev))
+        a, b = mid_batch(ev, 0, size, uniform=True), mid_batch(ev, 600, 600 + size, uniform=False)
+        assert not np.array_equal(a[2], b[2])
+        torch.cuda.synchronize()
+        with torch.cuda.stream(pipe.stream(1)):
+            torch.cuda._sleep(10_000_000)  # some milliseconds of the pick stream: longer than the two submits take to enqueue
+        pipe.submit(0, *a[0], a[1], mask, out)
+        with torch.cuda.stream(pipe.slot_stream(0)):
+            first.copy_(out)
+        pipe.submit(0, *b[0], b[1], mask, out)
+        pipe.wait(0, host=True)
+        pipe.wait_mask(0, host=True)
+        torch.cuda.synchronize()
+        assert np.array_equal(first.cpu().numpy(), a[3]), "the uniform pick read a mask that the slot's next submit had overwritten"
+        assert np.array_equal(mask_np(mask), b[2]) and np.array_equal(out.cpu().numpy(), b[3])
+    finally:
+        pipe.close()
+
+
 # ---- 11. seeded differential loop ---------------------------------------------------------------------------------------------
 def test_seeded_differential_loop(ev):
     import torch

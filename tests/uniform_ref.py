@@ -25,3 +25,13 @@ def uniform_pick(mask: np.ndarray, draws: np.ndarray, n: int) -> np.ndarray:
     node = (rank > k.astype(np.int64)[:, None]).argmax(axis=1)
     out[c > 0] = node[c > 0].astype(np.int32)
     return out
+
+
+def uniform_pick_blocks(mask: np.ndarray, draws: np.ndarray, n: int, cells: int = 1 << 24) -> np.ndarray:
+    """uniform_pick in blocks of pods: the restatement holds a [pods, n] int64 table, so a block is at most `cells` entries of it."""
+    p = mask.shape[0]
+    step = max(1, cells // max(int(n), 1))
+    if p <= step:
+        return uniform_pick(mask, draws, n)
+    draws = np.asarray(draws)
+    return np.concatenate([uniform_pick(mask[lo:lo + step], draws[lo:lo + step], n) for lo in range(0, p, step)])

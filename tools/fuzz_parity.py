@@ -1,11 +1,23 @@
 #!/usr/bin/env python
 """Randomised differential test of the HIP path against the oracle (GPU box): random shapes, key counts and cardinalities (incl.
-list keys and > 8 keys), taints, predicate subsets, both picks, snapshot updates between evaluations, both kernels, per-pair reasons (ksched_explain), per-pod node counts by reason (ksched_summarize),
+list keys and > 8 keys), taints, predicate subsets, the sampled and best-fit picks, snapshot updates between evaluations (ksched_update_nodes or,
+as its alternative, ksched_update_node_labels: ids within each key's current maximum, or above it -- the layout is planned again -- with taints
+now and then), both kernels, per-pair reasons (ksched_explain), per-pod node counts by reason (ksched_summarize),
+the uniform pick (KSCHED_PICK_UNIFORM) at every step of every case -- both kernels, with and without the mask, now and then with
+WANT_FIT_MASK, full-range 32-bit draws with an occasional all-zero or all-ones column -- against tests/uniform_ref.py on the oracle's mask,
+and through ksched_pick (the oracle's mask and a thinned one), the row shards and the multi-device sequence below; about one case in ten
+has 8192, 8193 or 12 500 nodes (rows of more than 128 words: the two-pass form of k_pick_uniform),
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
 ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts),
 the two halves of ksched_eval over 1 .. 5 row shards (ksched_shard_bounds / ksched_eval_begin / ksched_eval_end) and -- with the test hooks on
 (KSCHED_TEST_HOOKS=1 KSCHED_RCCL_LIB=tests/cpp/libfake_rccl.so) -- the whole multi-device sequence over 2 .. 4 evaluators on the one GPU:
 ksched_comm_create_local, ksched_eval_begin on every replica, ksched_gather_buffer, ksched_allgather_bindings_local, ksched_eval_end(gathered_0).
+A case's decisions come from two generators seeded from the case seed: `r` draws what the tool has always drawn, in the same order (a
+case that keeps its node count is the case an older log names by that seed), `r2` every decision added since (the uniform legs, the wider
+snapshots, the label updates).
+The summary's tallies: pick launches by name ('uniform': evaluations whose last_pick was "uniform"; 'uniform-ranked': those in which some
+pod had two or more feasible nodes, so the rank arithmetic ran), 'labels' (label updates), 'apply', 'host-masks', 'sharded-halves',
+'gathered-over-n' (and their 'uniform-' twins), 'summarize'.
 usage: python tools/fuzz_parity.py [seconds] [seed]       prints one line per failure and a summary; exit code 1 on any failure"""
 import os, sys, time
 import numpy as np
@@ -15,6 +27,8 @@ from oracle import capi
 # the exact-integer apply rule (oracle_ref.apply_bindings_exact) under the name the GPU tests import it by: through that name the tool
 # also runs with an oracle/ that predates the shared restatement
 from tests.test_gpu_apply_bindings import restate as apply_bindings_exact
+from tests.test_gpu_node_labels import apply_rows  # the columns after ksched_update_node_labels: a node listed twice takes its last row
+from tests.uniform_ref import uniform_pick  # KSCHED_PICK_UNIFORM restated
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -26,6 +40,14 @@ if HOOKS and not hasattr(L.load(), "ksched_test_hooks_linked"):  # the stand-in 
     print("fuzz: KSCHED_TEST_HOOKS is set but the loaded library is the shipped one (no hooks): the n > 1 multi-device cases are left out; set KSCHED_LIB=tests/cpp/hooks/libksched_hip.so", flush=True)
     HOOKS = False
 replicas, cliques = [], {}
+
+
+def uniform_pick_blocks(mask, draws, n, cells=1 << 24):
+    """uniform_pick in blocks of pods: the restatement holds a [pods, n] int64 table, and a case here has up to 52 225 pods"""
+    step = max(1, cells // max(int(n), 1))
+    if mask.shape[0] <= step:
+        return uniform_pick(mask, draws, n)
+    return np.concatenate([uniform_pick(mask[lo:lo + step], draws[lo:lo + step], n) for lo in range(0, mask.shape[0], step)])
 
 
 def clique(n_sh):
@@ -44,7 +66,7 @@ def clique(n_sh):
     return reps, cliques[n_sh]
 
 
-def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm):
+def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm, relabelled=False):
     """apply `bindings` (the previous evaluation's) on the device -- random flags, ok, now and then RELEASE; with the hooks, now and then
     also as a sharded apply over replicas with ragged cuts, every replica then equal to `ev` -- and advance cpu / mem (in place) by the
     exact-integer restatement.  -> the number of failures"""
@@ -91,12 +113,132 @@ def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm):
     if not (np.array_equal(st.cpu().numpy(), want_st) and np.array_equal(got[0], ncpu) and np.array_equal(got[1], nmem)):
         bad += 1
         print(f"FAIL apply case seed {cs}: N={N} P={P} flags={af} ok={okv is not None}", flush=True)
-    if reps and any(e.index_checksum() != ev.index_checksum() for e in reps):
+    # the replicas were set afresh; `ev` after ksched_update_node_labels keeps a layout planned for the union of the old and the new maxima
+    # (include/ksched.h), so its index is comparable with theirs only while its labels are the ones it was set with -- else the replicas among themselves
+    if reps and any(e.index_checksum() != (reps[0] if relabelled else ev).index_checksum() for e in reps):
         bad += 1
         print(f"FAIL sharded apply index case seed {cs}: N={N} P={P} flags={af} replicas={len(reps)}", flush=True)
     picks["apply"] = picks.get("apply", 0) + 1
     cpu[:], mem[:] = ncpu, nmem
     return bad
+
+
+def row_popcounts(m):
+    """set bits per mask row"""
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(m).sum(axis=1)
+    return np.unpackbits(np.ascontiguousarray(m).view(np.uint8), axis=1).sum(axis=1)
+
+
+def shard_halves(g, cs, tag, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, attempts, want):
+    """the host-side row shard (include/ksched.h "one host thread, several devices"): the batch cut into 1 .. 5 shards with
+    ksched_shard_bounds, every shard through ksched_eval_begin (selector columns addressed inside the whole batch's array with its
+    stride, the draws `smp` [P, attempts] at 4 * attempts * lo bytes, bindings padded to ceil(P / n) with -1) + ksched_eval_end, merged
+    like an all-gathered table -- on this one evaluator, shard after shard.  `g` draws the shard count.  -> the number of failures"""
+    bad = 0
+    import ctypes as C
+    n_sh = int(g.choice([1, 2, 3, 5]))
+    W = ev.W
+    lo_, hi_, cpr_ = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc_c, rm_c = np.ascontiguousarray(rc), np.ascontiguousarray(rm)
+    sel_c = np.ascontiguousarray(sel) if K else None
+    tol_c = np.ascontiguousarray(tol) if (preds & L.TAINT) else None
+    smp_c = np.ascontiguousarray(smp) if smp is not None else None
+    feas_s = np.zeros((P, W), dtype=np.uint64)
+    fit_s = np.zeros((P, W), dtype=np.uint64)
+    bind_s = np.full((P,), 777, dtype=np.int32)
+    for rank in range(n_sh):
+        ev._lib.ksched_shard_bounds(P, n_sh, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
+        lo, hi, cpr = lo_.value, hi_.value, cpr_.value
+        dev_b, stream = C.c_void_p(), C.c_void_p()
+        rcode = ev._lib.ksched_eval_begin(
+            ev._h, hi - lo, C.c_void_p(rc_c.ctypes.data + 8 * lo), C.c_void_p(rm_c.ctypes.data + 8 * lo),
+            C.c_void_p(sel_c.ctypes.data + 4 * lo) if K else None, P, C.c_void_p(tol_c.ctypes.data + 8 * lo) if tol_c is not None else None,
+            C.c_void_p(smp_c.ctypes.data + 4 * attempts * lo) if smp_c is not None else None, attempts, flags,
+            C.c_void_p(feas_s.ctypes.data + 8 * W * lo), C.c_void_p(fit_s.ctypes.data + 8 * W * lo) if flags & L.WANT_FIT_MASK else None, cpr,
+            C.byref(dev_b), C.byref(stream))
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_eval_begin", ev._lib.ksched_last_error(ev._h).decode())
+        part = np.full((cpr,), 555, dtype=np.int32)
+        rcode = ev._lib.ksched_eval_end(ev._h, dev_b, cpr, part.ctypes.data_as(C.c_void_p))
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_eval_end", ev._lib.ksched_last_error(ev._h).decode())
+        bind_s[lo:hi] = part[:hi - lo]
+        if not (part[hi - lo:] == -1).all():
+            bad += 1
+            print(f"FAIL {tag}shard padding case seed {cs}: P={P} shards={n_sh} rank={rank}", flush=True)
+    if not (np.array_equal(feas_s, want[0]) and (not (flags & L.WANT_FIT_MASK) or np.array_equal(fit_s, want[1])) and np.array_equal(bind_s, want[2])):
+        bad += 1
+        print(f"FAIL {tag}sharded halves case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} shards={n_sh}", flush=True)
+    picks[tag + "sharded-halves"] = picks.get(tag + "sharded-halves", 0) + 1
+    return bad
+
+
+def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, attempts, want):
+    """the whole multi-device sequence over 2 .. 4 replicas on the one GPU (test hooks): ksched_eval_begin on every replica,
+    ksched_gather_buffer, ksched_allgather_bindings_local, ksched_eval_end(gathered_0).  `g` draws the replica count and the replicas'
+    options.  -> (the number of failures, the last_pick names of the replicas whose shard held a pod)"""
+    bad = 0
+    ran = []
+    import ctypes as C
+    n_sh = int(g.choice([2, 3, 4]))
+    reps, comms = clique(n_sh)
+    lib = ev._lib
+    for e in reps:  # the snapshot is replicated (the current values: the updates above are in cpu / mem)
+        e.set_option(L.OPT_BESTFIT_STAGES, int(g.choice([0, 1, 2])))
+        e.set_nodes(cpu, mem, lab, taints)
+    W = ev.W
+    lo_, hi_, cpr_ = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    rc_c, rm_c = np.ascontiguousarray(rc), np.ascontiguousarray(rm)
+    sel_c = np.ascontiguousarray(sel) if K else None
+    tol_c = np.ascontiguousarray(tol) if (preds & L.TAINT) else None
+    smp_c = np.ascontiguousarray(smp) if smp is not None else None
+    feas_s, fit_s = np.zeros((P, W), dtype=np.uint64), np.zeros((P, W), dtype=np.uint64)
+    local, gathered, streams = (C.c_void_p * n_sh)(), (C.c_void_p * n_sh)(), (C.c_void_p * n_sh)()
+    lib.ksched_shard_bounds(P, n_sh, 0, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
+    cpr = cpr_.value
+    for rank, e in enumerate(reps):
+        lib.ksched_shard_bounds(P, n_sh, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
+        lo, hi = lo_.value, hi_.value
+        dev_b, stream = C.c_void_p(), C.c_void_p()
+        rcode = lib.ksched_eval_begin(
+            e._h, hi - lo, C.c_void_p(rc_c.ctypes.data + 8 * lo), C.c_void_p(rm_c.ctypes.data + 8 * lo),
+            C.c_void_p(sel_c.ctypes.data + 4 * lo) if K else None, P, C.c_void_p(tol_c.ctypes.data + 8 * lo) if tol_c is not None else None,
+            C.c_void_p(smp_c.ctypes.data + 4 * attempts * lo) if smp_c is not None else None, attempts, flags,
+            C.c_void_p(feas_s.ctypes.data + 8 * W * lo), C.c_void_p(fit_s.ctypes.data + 8 * W * lo) if flags & L.WANT_FIT_MASK else None, cpr,
+            C.byref(dev_b), C.byref(stream))
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_eval_begin", lib.ksched_last_error(e._h).decode())
+        local[rank], streams[rank] = dev_b.value, stream.value
+        if hi > lo:
+            ran.append(e)
+        gbuf = C.c_void_p()
+        rcode = lib.ksched_gather_buffer(e._h, n_sh * cpr, C.byref(gbuf))
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_gather_buffer", lib.ksched_last_error(e._h).decode())
+        gathered[rank] = gbuf.value
+    rcode = lib.ksched_allgather_bindings_local(comms, n_sh, local, gathered, cpr, streams)
+    if rcode != 0:
+        raise L.KschedError(rcode, "ksched_allgather_bindings_local", lib.ksched_comm_last_error().decode())
+    table = np.full((n_sh * cpr,), 555, dtype=np.int32)
+    for rank, e in enumerate(reps):
+        rcode = lib.ksched_eval_end(e._h, C.c_void_p(gathered[0]) if rank == 0 else None, n_sh * cpr if rank == 0 else 0,
+                                    table.ctypes.data_as(C.c_void_p) if rank == 0 else None)
+        if rcode != 0:
+            raise L.KschedError(rcode, "ksched_eval_end", lib.ksched_last_error(e._h).decode())
+    bind_s = np.full((P,), 777, dtype=np.int32)
+    pad_ok = True
+    for rank in range(n_sh):
+        lib.ksched_shard_bounds(P, n_sh, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
+        bind_s[lo_.value:hi_.value] = table[rank * cpr: rank * cpr + hi_.value - lo_.value]
+        pad_ok = pad_ok and bool((table[rank * cpr + hi_.value - lo_.value: (rank + 1) * cpr] == -1).all())
+    if not (pad_ok and np.array_equal(feas_s, want[0]) and (not (flags & L.WANT_FIT_MASK) or np.array_equal(fit_s, want[1])) and np.array_equal(bind_s, want[2])):
+        bad += 1
+        print(f"FAIL {tag}multi-device sequence case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} replicas={n_sh}", flush=True)
+    picks[f"{tag}gathered-over-{n_sh}"] = picks.get(f"{tag}gathered-over-{n_sh}", 0) + 1
+    return bad, {e.last_pick for e in ran}
+
+
 t_end = time.time() + budget
 cases = fails = 0
 picks = {}
@@ -105,10 +247,15 @@ while time.time() < t_end:
     cases += 1
     cs = int(rng.integers(0, 1 << 31))
     r = np.random.default_rng(cs)
+    r2 = np.random.default_rng([cs, 0x0E3])  # every decision added after the sequence of `r` was fixed (see the docstring)
+    wide = int(r2.choice([8192, 8193, 12_500])) if r2.random() < 0.1 else 0  # rows of more than 128 words: k_pick_uniform's two-pass form (8192: the longest one-pass row)
     N = int(r.choice([1, 2, 63, 64, 65, 300, 1023, 1024, 1025, 2500, 4097, 6000]))
     P = int(r.choice([1, 7, 64, 65, 500, 1500, 3000]))
+    N = wide or N
     if r.random() < 0.05:  # now and then a batch long enough for two or more rounds per wave of a whole-chip launch (run_fused's chunk-count rule, the riding pick's longer forms)
         P = int(r.choice([12_000, 20_011, 40_000, 52_225]))
+    if wide:
+        P = min(P, 1500)  # the oracle's time
     K = int(r.choice([0, 1, 3, 8, 9, 12]))
     cards = [int(r.choice([1, 2, 5, 40, 300, N, 4 * N + 7])) for _ in range(K)]
     scale = int(r.choice([10, 1000, 1 << 20]))
@@ -136,22 +283,53 @@ while time.time() < t_end:
         preds = L.FIT
     pick = int(r.choice([0, L.PICK_SAMPLED, L.PICK_BESTFIT]))
     flags = preds | pick | (L.WANT_FIT_MASK if r.random() < 0.5 else 0)
+    # the uniform pick's draws: full-range 32-bit, column 0 (the one that is read) now and then all zero or all ones
+    att_u = int(r2.choice([1, 3, 5]))
+    smp_u = r2.integers(0, 1 << 32, (P, att_u), dtype=np.uint64).astype(np.uint32)
+    if r2.random() < 0.15:
+        smp_u[:, int(r2.integers(0, att_u))] = 0 if r2.random() < 0.5 else 0xFFFFFFFF
+    if r2.random() < 0.1:
+        smp_u[:, 0] = 0 if r2.random() < 0.5 else 0xFFFFFFFF
     try:
         ev.set_option(L.OPT_BESTFIT_STAGES, int(r.choice([0, 1, 2])))
         ev.set_option(L.OPT_GRID_CUS, int(r.choice([0, 0, 0, 8, 17, 96, 200])))  # fewer compute units per launch: same results
         ev.set_option(L.OPT_ROUND_ORDER, int(r.choice([0, 0, 1, 2])))  # which wave takes which round: same results
         ev.set_option(L.OPT_FUSED_PICK, int(r.choice([0, 1, 1, 2])))  # 3 (tile tests or E_UNSUPPORTED) below, where it applies
         ev.set_nodes(cpu, mem, lab, taints)
-        last_b = None
+        last_b, relabelled = None, False
         for step in range(int(r.choice([1, 2, 3]))):
             if step and last_b is not None and r.random() < 0.6:  # the previous evaluation's bindings applied on the device
-                fails += apply_step(r, cs, cpu, mem, lab, taints, last_b, rc, rm)
+                fails += apply_step(r, cs, cpu, mem, lab, taints, last_b, rc, rm, relabelled)
             elif step:  # a snapshot update between evaluations
                 idx = r.integers(0, N, int(r.choice([1, 5, 40, N]))).astype(np.uint32)
                 nc, nm = r.integers(-scale, 64 * scale, idx.size).astype(np.int64), r.integers(-scale, 64 * scale, idx.size).astype(np.int64)
-                ev.update_nodes(idx, nc, nm)
-                for j in range(idx.size):
-                    cpu[idx[j]], mem[idx[j]] = nc[j], nm[j]
+                if (K or nt) and r2.random() < 0.5:  # instead: the labels (and taints) of random rows change
+                    lidx = r2.integers(0, N, int(r2.choice([1, 5, 40, N]))).astype(np.uint32)
+                    lmax = lab.max(axis=1).astype(np.int64) if K else None
+                    rows_t = None
+                    if r2.random() < 2 / 3:  # ids within each key's current maximum, taint bits within the highest one
+                        rows = r2.integers(0, lmax[:, None] + 1, (K, lidx.size)).astype(np.uint32) if K else None
+                        if nt and (not K or r2.random() < 0.5):  # (without label keys the taints are all the call can change)
+                            rows_t = r2.integers(0, 1 << nt, lidx.size, dtype=np.uint64) & r2.integers(0, 1 << nt, lidx.size, dtype=np.uint64)
+                    else:  # ids above a key's maximum (the layout is planned again), some pods selecting them; now and then a taint bit above the others
+                        rows = np.ascontiguousarray(lab[:, lidx]) if K else None
+                        if K:
+                            key = int(r2.integers(0, K))
+                            rows[key, : max(1, lidx.size // 2)] = lmax[key] + 1 + r2.integers(0, 3, max(1, lidx.size // 2))
+                            sel[key, r2.integers(0, P, max(1, P // 10))] = lmax[key] + 1
+                        if nt and (not K or r2.random() < 0.3):
+                            top = np.uint64(1) << np.uint64(min(nt, 63))
+                            rows_t = taints[lidx] | top
+                            tol[r2.integers(0, P, max(1, P // 2))] |= top
+                    ev.update_node_labels(lidx, rows, rows_t)
+                    lab, taints = apply_rows(lab, taints, lidx, rows, rows_t)
+                    lab = None if lab is None else np.ascontiguousarray(lab)
+                    picks["labels"] = picks.get("labels", 0) + 1
+                    relabelled = True
+                else:
+                    ev.update_nodes(idx, nc, nm)
+                    for j in range(idx.size):
+                        cpu[idx[j]], mem[idx[j]] = nc[j], nm[j]
             want = capi.eval_encoded(cpu, mem, lab, taints if (preds & L.TAINT) else None, rc, rm, sel, tol if (preds & L.TAINT) else None, smp, flags)
             for kernel in ("auto", "direct"):
                 ev.set_kernel(kernel)
@@ -178,7 +356,47 @@ while time.time() < t_end:
                         raise
                     picks["tile-unsupported"] = picks.get("tile-unsupported", 0) + 1
                 ev.set_option(L.OPT_FUSED_PICK, 1)
+            # the uniform pick on the same snapshot: both kernels, with and without the mask, now and then with the fit mask (where the
+            # oracle computed one) -- against the restatement on the oracle's mask
+            want_u = uniform_pick_blocks(want[0], smp_u[:, 0], N)
+            ranked = bool((row_popcounts(want[0]) >= 2).any())
+            fl_u = preds | L.PICK_UNIFORM | (L.WANT_FIT_MASK if (flags & L.WANT_FIT_MASK) and r2.random() < 0.5 else 0)
+            for kernel in ("auto", "direct"):
+                ev.set_kernel(kernel)
+                for want_mask in (True, False):
+                    fl = fl_u if want_mask else fl_u & ~L.WANT_FIT_MASK
+                    got = ev.eval(rc, rm, sel if K else None, tol if (preds & L.TAINT) else None, smp_u, fl, want_mask=want_mask)
+                    ok = (not want_mask or np.array_equal(got.feasible, want[0])) and np.array_equal(got.binding, want_u) and \
+                        (not (fl & L.WANT_FIT_MASK) or np.array_equal(got.fit, want[1]))
+                    if not ok:
+                        fails += 1
+                        print(f"FAIL uniform case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} flags={fl_u:#x} kernel={kernel}/{ev.last_kernel} pick={ev.last_pick} mask={want_mask} step={step}", flush=True)
+                    if ev.last_pick == "uniform":
+                        picks["uniform"] = picks.get("uniform", 0) + 1
+                        picks["uniform-ranked"] = picks.get("uniform-ranked", 0) + int(ranked)
+                    else:  # a KSCHED_PICK_UNIFORM request has one launch form
+                        fails += 1
+                        print(f"FAIL uniform case seed {cs}: N={N} P={P} K={K} flags={fl_u:#x} kernel={kernel} mask={want_mask} step={step}: the pick ran as {ev.last_pick!r}", flush=True)
         ev.set_kernel("auto")
+        want3_u = (want[0], want[1], want_u)
+        if r2.random() < 0.4:  # ksched_pick with the uniform pick: the oracle's mask, and that mask thinned by random words -- the restatement on either
+            thin_u = want[0] & r2.integers(0, 1 << 63, want[0].shape, dtype=np.uint64)
+            if not (np.array_equal(ev.pick(want[0], L.PICK_UNIFORM, samples=smp_u), want_u) and
+                    np.array_equal(ev.pick(thin_u, L.PICK_UNIFORM, samples=smp_u), uniform_pick_blocks(thin_u, smp_u[:, 0], N))):
+                fails += 1
+                print(f"FAIL uniform ksched_pick case seed {cs}: N={N} P={P} K={K} nt={nt} preds={preds:#x}", flush=True)
+            picks["uniform-host-masks"] = picks.get("uniform-host-masks", 0) + 1
+        if r2.random() < 0.35:
+            fails += shard_halves(r2, cs, "uniform-", N, P, K, nt, preds, fl_u, rc, rm, sel, tol, smp_u, att_u, want3_u)
+        if HOOKS and r2.random() < 0.35:
+            bad_u, names = gathered_sequence(r2, cs, "uniform-", cpu, mem, lab, taints, N, P, K, nt, preds, fl_u, rc, rm, sel, tol, smp_u, att_u, want3_u)
+            fails += bad_u
+            if names == {"uniform"}:
+                picks["uniform"] = picks.get("uniform", 0) + 1
+                picks["uniform-ranked"] = picks.get("uniform-ranked", 0) + int(ranked)
+            else:
+                fails += 1
+                print(f"FAIL uniform multi-device sequence case seed {cs}: the replicas' picks ran as {sorted(names)}", flush=True)
         if pick and r.random() < 0.4:
             # the pick alone from HOST masks (ksched_pick, what a selector evaluated in key groups uses): from the oracle's mask it is the oracle's
             # binding; from that mask thinned by random words (an AND with another group's mask) the sampled pick is the first draw whose bit is set
@@ -199,96 +417,11 @@ while time.time() < t_end:
             # ksched_shard_bounds, every shard through ksched_eval_begin (selector columns addressed inside the whole batch's array with its
             # stride, bindings padded to ceil(P / n) with -1) + ksched_eval_end, merged like an all-gathered table -- on this one evaluator,
             # shard after shard
-            import ctypes as C
-            n_sh = int(r.choice([1, 2, 3, 5]))
-            W = ev.W
-            lo_, hi_, cpr_ = C.c_uint32(), C.c_uint32(), C.c_uint32()
-            rc_c, rm_c = np.ascontiguousarray(rc), np.ascontiguousarray(rm)
-            sel_c = np.ascontiguousarray(sel) if K else None
-            tol_c = np.ascontiguousarray(tol) if (preds & L.TAINT) else None
-            smp_c = np.ascontiguousarray(smp)
-            feas_s = np.zeros((P, W), dtype=np.uint64)
-            fit_s = np.zeros((P, W), dtype=np.uint64)
-            bind_s = np.full((P,), 777, dtype=np.int32)
-            for rank in range(n_sh):
-                ev._lib.ksched_shard_bounds(P, n_sh, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
-                lo, hi, cpr = lo_.value, hi_.value, cpr_.value
-                dev_b, stream = C.c_void_p(), C.c_void_p()
-                rcode = ev._lib.ksched_eval_begin(
-                    ev._h, hi - lo, C.c_void_p(rc_c.ctypes.data + 8 * lo), C.c_void_p(rm_c.ctypes.data + 8 * lo),
-                    C.c_void_p(sel_c.ctypes.data + 4 * lo) if K else None, P, C.c_void_p(tol_c.ctypes.data + 8 * lo) if tol_c is not None else None,
-                    C.c_void_p(smp_c.ctypes.data + 20 * lo) if pick == L.PICK_SAMPLED else None, 5 if pick == L.PICK_SAMPLED else 0, flags,
-                    C.c_void_p(feas_s.ctypes.data + 8 * W * lo), C.c_void_p(fit_s.ctypes.data + 8 * W * lo) if flags & L.WANT_FIT_MASK else None, cpr,
-                    C.byref(dev_b), C.byref(stream))
-                if rcode != 0:
-                    raise L.KschedError(rcode, "ksched_eval_begin", ev._lib.ksched_last_error(ev._h).decode())
-                part = np.full((cpr,), 555, dtype=np.int32)
-                rcode = ev._lib.ksched_eval_end(ev._h, dev_b, cpr, part.ctypes.data_as(C.c_void_p))
-                if rcode != 0:
-                    raise L.KschedError(rcode, "ksched_eval_end", ev._lib.ksched_last_error(ev._h).decode())
-                bind_s[lo:hi] = part[:hi - lo]
-                if not (part[hi - lo:] == -1).all():
-                    fails += 1
-                    print(f"FAIL shard padding case seed {cs}: P={P} shards={n_sh} rank={rank}", flush=True)
-            if not (np.array_equal(feas_s, want[0]) and (not (flags & L.WANT_FIT_MASK) or np.array_equal(fit_s, want[1])) and np.array_equal(bind_s, want[2])):
-                fails += 1
-                print(f"FAIL sharded halves case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} shards={n_sh}", flush=True)
-            picks["sharded-halves"] = picks.get("sharded-halves", 0) + 1
+            fails += shard_halves(r, cs, "", N, P, K, nt, preds, flags, rc, rm, sel, tol, smp if pick == L.PICK_SAMPLED else None,
+                                  5 if pick == L.PICK_SAMPLED else 0, want)
         if HOOKS and pick and r.random() < 0.35:
-            import ctypes as C
-            n_sh = int(r.choice([2, 3, 4]))
-            reps, comms = clique(n_sh)
-            lib = ev._lib
-            for e in reps:  # the snapshot is replicated (the current values: the updates above are in cpu / mem)
-                e.set_option(L.OPT_BESTFIT_STAGES, int(r.choice([0, 1, 2])))
-                e.set_nodes(cpu, mem, lab, taints)
-            W = ev.W
-            lo_, hi_, cpr_ = C.c_uint32(), C.c_uint32(), C.c_uint32()
-            rc_c, rm_c = np.ascontiguousarray(rc), np.ascontiguousarray(rm)
-            sel_c = np.ascontiguousarray(sel) if K else None
-            tol_c = np.ascontiguousarray(tol) if (preds & L.TAINT) else None
-            smp_c = np.ascontiguousarray(smp)
-            feas_s, fit_s = np.zeros((P, W), dtype=np.uint64), np.zeros((P, W), dtype=np.uint64)
-            local, gathered, streams = (C.c_void_p * n_sh)(), (C.c_void_p * n_sh)(), (C.c_void_p * n_sh)()
-            lib.ksched_shard_bounds(P, n_sh, 0, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
-            cpr = cpr_.value
-            for rank, e in enumerate(reps):
-                lib.ksched_shard_bounds(P, n_sh, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
-                lo, hi = lo_.value, hi_.value
-                dev_b, stream = C.c_void_p(), C.c_void_p()
-                rcode = lib.ksched_eval_begin(
-                    e._h, hi - lo, C.c_void_p(rc_c.ctypes.data + 8 * lo), C.c_void_p(rm_c.ctypes.data + 8 * lo),
-                    C.c_void_p(sel_c.ctypes.data + 4 * lo) if K else None, P, C.c_void_p(tol_c.ctypes.data + 8 * lo) if tol_c is not None else None,
-                    C.c_void_p(smp_c.ctypes.data + 20 * lo) if pick == L.PICK_SAMPLED else None, 5 if pick == L.PICK_SAMPLED else 0, flags,
-                    C.c_void_p(feas_s.ctypes.data + 8 * W * lo), C.c_void_p(fit_s.ctypes.data + 8 * W * lo) if flags & L.WANT_FIT_MASK else None, cpr,
-                    C.byref(dev_b), C.byref(stream))
-                if rcode != 0:
-                    raise L.KschedError(rcode, "ksched_eval_begin", lib.ksched_last_error(e._h).decode())
-                local[rank], streams[rank] = dev_b.value, stream.value
-                g = C.c_void_p()
-                rcode = lib.ksched_gather_buffer(e._h, n_sh * cpr, C.byref(g))
-                if rcode != 0:
-                    raise L.KschedError(rcode, "ksched_gather_buffer", lib.ksched_last_error(e._h).decode())
-                gathered[rank] = g.value
-            rcode = lib.ksched_allgather_bindings_local(comms, n_sh, local, gathered, cpr, streams)
-            if rcode != 0:
-                raise L.KschedError(rcode, "ksched_allgather_bindings_local", lib.ksched_comm_last_error().decode())
-            table = np.full((n_sh * cpr,), 555, dtype=np.int32)
-            for rank, e in enumerate(reps):
-                rcode = lib.ksched_eval_end(e._h, C.c_void_p(gathered[0]) if rank == 0 else None, n_sh * cpr if rank == 0 else 0,
-                                            table.ctypes.data_as(C.c_void_p) if rank == 0 else None)
-                if rcode != 0:
-                    raise L.KschedError(rcode, "ksched_eval_end", lib.ksched_last_error(e._h).decode())
-            bind_s = np.full((P,), 777, dtype=np.int32)
-            pad_ok = True
-            for rank in range(n_sh):
-                lib.ksched_shard_bounds(P, n_sh, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
-                bind_s[lo_.value:hi_.value] = table[rank * cpr: rank * cpr + hi_.value - lo_.value]
-                pad_ok = pad_ok and bool((table[rank * cpr + hi_.value - lo_.value: (rank + 1) * cpr] == -1).all())
-            if not (pad_ok and np.array_equal(feas_s, want[0]) and (not (flags & L.WANT_FIT_MASK) or np.array_equal(fit_s, want[1])) and np.array_equal(bind_s, want[2])):
-                fails += 1
-                print(f"FAIL multi-device sequence case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} replicas={n_sh}", flush=True)
-            picks[f"gathered-over-{n_sh}"] = picks.get(f"gathered-over-{n_sh}", 0) + 1
+            fails += gathered_sequence(r, cs, "", cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol,
+                                       smp if pick == L.PICK_SAMPLED else None, 5 if pick == L.PICK_SAMPLED else 0, want)[0]
         if r.random() < 0.3:  # ksched_explain on random pairs == the reason rebuilt from three single-predicate oracle masks
             from kube_scheduler_rs_reference_amd.evaluator import unpack_mask
             one = lambda f: unpack_mask(capi.eval_encoded(cpu, mem, lab, taints, rc, rm, sel, tol, None, f)[0], N)  # noqa: E731
