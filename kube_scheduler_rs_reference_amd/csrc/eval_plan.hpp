@@ -17,9 +17,9 @@ namespace ksched {
 // Does the pick read the feasibility mask?  By default it does not (sampled: the drawn candidates are tested from the columns;
 // best fit: bitmaps kept in best-fit order); it does with KSCHED_OPT_PICK_FROM_MASK, and a best-fit pick does when the snapshot
 // has no best-fit rows (`bf_rows`: they exist, or will once ensure_bestfit has run).  The uniform pick (KSCHED_PICK_UNIFORM) always does:
-// it counts and ranks the row's set bits.
+// it counts and ranks the row's set bits; so does the spread pick (KSCHED_PICK_SPREAD), once per draw.
 inline bool pick_reads_mask(uint32_t flags, bool opt_pick_from_mask, bool bf_rows) {
-    if (flags & KSCHED_PICK_UNIFORM) return true;
+    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD)) return true;
     return (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) && (opt_pick_from_mask || ((flags & KSCHED_PICK_BESTFIT) && !bf_rows));
 }
 
@@ -50,6 +50,7 @@ enum class MaskKernel { kNone, kFused, kDirect };
 enum class SampledPick { kNone, kOwnLaunch, kRidesFill, kRidesTiles, kFromMask };
 enum class BestfitPick { kNone, kRowsOneStage, kRowsTwoStages, kRowsTwoStagesListed, kFromMask };
 enum class UniformPick { kNone, kFromMask };  // k_pick_uniform behind the mask kernel: the only form
+enum class SpreadPick { kNone, kFromMask };   // k_pick_spread behind the mask kernel: the only form
 enum class PlanError { kNone, kFusedNotApplicable, kTilePickNotApplicable, kListKeysTooManyNodes };
 
 struct EvalPlan {
@@ -60,13 +61,14 @@ struct EvalPlan {
     SampledPick sampled = SampledPick::kNone;
     BestfitPick bestfit = BestfitPick::kNone;
     UniformPick uniform = UniformPick::kNone;
+    SpreadPick spread = SpreadPick::kNone;
     const char *last_kernel = nullptr;  // ksched_last_kernel after the launch; nullptr = no mask kernel runs, it stays what it was
     const char *last_pick = "none";     // ksched_last_pick
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
     // a pick launch follows the mask kernel and reads what it wrote
-    bool pick_from_mask() const { return sampled == SampledPick::kFromMask || bestfit == BestfitPick::kFromMask || uniform == UniformPick::kFromMask; }
+    bool pick_from_mask() const { return sampled == SampledPick::kFromMask || bestfit == BestfitPick::kFromMask || uniform == UniformPick::kFromMask || spread == SpreadPick::kFromMask; }
 };
 
 inline EvalPlan plan_unsupported(PlanError why) {
@@ -87,11 +89,17 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     const int kern = choose_kernel(f.opt_kernel, can_fused);
     // The uniform pick counts and ranks the set bits of the pod's whole row: the mask kernel always runs (into the ctx's scratch mask when
     // the caller gave none), the pick is its own launch behind it, and neither KSCHED_OPT_PICK_FROM_MASK nor KSCHED_OPT_FUSED_PICK applies.
-    if (flags & KSCHED_PICK_UNIFORM) {
+    // The spread pick (KSCHED_PICK_SPREAD) does the same once per draw and compares the candidates: the same plan, its own kernel.
+    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD)) {
         if (kern == KSCHED_KERNEL_FUSED && !can_fused) return plan_unsupported(PlanError::kFusedNotApplicable);
         plan.scratch_mask = !f.have_feas;
         plan.mask = kern == KSCHED_KERNEL_FUSED ? MaskKernel::kFused : MaskKernel::kDirect;
         plan.last_kernel = kern == KSCHED_KERNEL_FUSED ? "fused" : "direct";
+        if (flags & KSCHED_PICK_SPREAD) {
+            plan.spread = SpreadPick::kFromMask;
+            plan.last_pick = "spread";
+            return plan;
+        }
         plan.uniform = UniformPick::kFromMask;
         plan.last_pick = "uniform";
         return plan;

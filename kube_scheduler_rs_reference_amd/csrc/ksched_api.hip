@@ -29,6 +29,7 @@
 #include "kernels_fused.hpp"
 #include "kernels_pick_uniform.hpp"
 #include "kernels_summary.hpp"
+#include "kernels_pick_spread.hpp"  // (uses kernels_pick_uniform.hpp's helpers)
 #include "mask_alloc.hpp"
 #include "snapshot_change.hpp"
 #include "tile_index.hpp"
@@ -1017,6 +1018,9 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
     } else if (r.flags & KSCHED_PICK_UNIFORM) {  // (every caller has c->n > 0 here: an empty snapshot's bindings are a memset)
         hipLaunchKernelGGL(k_pick_uniform, dim3((r.p + kUniformWaves - 1) / kUniformWaves), dim3(64 * kUniformWaves), 0, s, feas, r.samples,
                            r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
+    } else if (r.flags & KSCHED_PICK_SPREAD) {  // (c->n > 0 likewise; the stream_enter above puts the columns it reads behind the latest snapshot change)
+        hipLaunchKernelGGL(k_pick_spread, dim3((r.p + kSpreadWaves - 1) / kSpreadWaves), dim3(64 * kSpreadWaves), 0, s, feas, r.samples,
+                           (const int64_t *)c->nmem.ptr, (const int64_t *)c->ncpu.ptr, r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
     }
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
@@ -1200,7 +1204,7 @@ int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
     if (c->n == 0) {
         // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
         // yields None on every attempt, src/main.rs:56,70)
-        if ((pick_s || pick_b || (r.flags & KSCHED_PICK_UNIFORM)) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
+        if ((pick_s || pick_b || (r.flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD))) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
         return KSCHED_OK;
     }
     fault_point(c);
@@ -1255,7 +1259,9 @@ int stage_batch(ksched_ctx *c, uint32_t p, const HostBatch &h, hipStream_t s) {
 }
 
 // the pick flags: at most one per call
-constexpr uint32_t kPickFlags = KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM;
+constexpr uint32_t kPickFlags = KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD;
+// the picks that read `samples`: node indices (sampled), 32-bit draws (uniform: entry 0 of every row; spread: all `attempts` of them)
+constexpr uint32_t kDrawPicks = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD;
 inline bool at_most_one_pick(uint32_t flags) {
     const uint32_t pick = flags & kPickFlags;
     return (pick & (pick - 1u)) == 0;
@@ -1268,7 +1274,7 @@ int check_eval_args(const EvalRequest &r) {
     if (flags & ~known) return KSCHED_E_INVAL;
     if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
-    if (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM)) {  // the picks that read draws
+    if (flags & kDrawPicks) {
         if (!r.out_binding || r.attempts == 0 || r.attempts > KSCHED_MAX_ATTEMPTS) return KSCHED_E_INVAL;
         if (r.p > 0 && !r.samples) return KSCHED_E_INVAL;
     }
@@ -1826,7 +1832,7 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     q->slot_stream[slot] = sm;
     q->pick_stream[slot] = q->s_pick;
     // the slot's mask may be overwritten once the pick that reads it has run: this submit's own pick orders the slot's NEXT mask kernel, and
-    // the previous submit's pick this one (also when this submit's pick reads no mask: a sampled submit into a slot whose last pick was uniform)
+    // the previous submit's pick this one (also when this submit's pick reads no mask: a sampled submit into a slot whose last pick was uniform or spread)
     if (reads_mask || q->pick_read_mask[slot]) HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));
     q->pick_read_mask[slot] = reads_mask ? 1 : 0;
     q->last_split[slot] = 1;
@@ -1877,8 +1883,8 @@ int ksched_pick_device(ksched_ctx *c, uint32_t p, const uint64_t *feasible, uint
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    // (pick_s: the pick reads draws -- sampled or uniform)
-    const bool pick_s = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM), pick_b = flags & KSCHED_PICK_BESTFIT;
+    // (pick_s: the pick reads draws -- sampled, uniform or spread)
+    const bool pick_s = flags & kDrawPicks, pick_b = flags & KSCHED_PICK_BESTFIT;
     if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
     if (!out_binding || (p > 0 && c->n > 0 && !feasible) || mask_pitch_words < c->W) return KSCHED_E_INVAL;
     if (pick_s && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
@@ -1900,8 +1906,8 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    // (pick_s: the pick reads draws -- sampled or uniform)
-    const bool pick_s = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM), pick_b = flags & KSCHED_PICK_BESTFIT;
+    // (pick_s: the pick reads draws -- sampled, uniform or spread)
+    const bool pick_s = flags & kDrawPicks, pick_b = flags & KSCHED_PICK_BESTFIT;
     if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
     if (!out_binding || (p > 0 && c->n > 0 && !feasible)) return KSCHED_E_INVAL;
     if (pick_s && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
@@ -1947,12 +1953,12 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
     const size_t W = c->W;
     const size_t pitch = ksched_mask_pitch(c->n);
     const bool pick = flags & kPickFlags;
-    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled or uniform pick
+    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled, uniform or spread pick
     b.pcpu = h.pcpu;
     b.pmem = h.pmem;
     if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride;
     if (h.taint_flag()) b.ptol = h.ptol;
-    if (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM)) b.samples = h.samples, b.attempts = h.attempts;
+    if (flags & kDrawPicks) b.samples = h.samples, b.attempts = h.attempts;
     int32_t *d_bind = nullptr;
     if (pick) {
         const size_t cap = std::max<size_t>(capacity, p);
@@ -1965,7 +1971,7 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
 
     if (int rc = stage_batch(c, p, b, s)) return rc;
     uint64_t *d_feas = nullptr, *d_fit = nullptr;
-    // a mask is needed when the caller wants it, or when the pick reads it (uniform; best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
+    // a mask is needed when the caller wants it, or when the pick reads it (uniform and spread; best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
     if (out_feas || pick_reads_mask(flags, c->opt_pick_from_mask, bf_rows_expected(c))) {
         HIPCHK(c, c->feas.reserve((size_t)p * pitch));
         d_feas = c->feas.ptr;

@@ -79,6 +79,13 @@ struct Context {
     // reference tests five blind draws, src/main.rs:51-71).  Off: nothing changes, draw for draw.
     bool pick_uniform = false;
 
+    // Opt-in (0 = off, the default; extension E4): select_nodes_for_pods picks THE LEAST LOADED OF d = pick_spread UNIFORMLY DRAWN FEASIBLE
+    // NODES on the device (KSCHED_PICK_SPREAD; 1 <= d <= KSCHED_MAX_ATTEMPTS): d draws per pod, chooser.choose(2^32), in pod order and
+    // draw-major within a pod; the largest (available memory, available cpu) of the snapshot the batch is evaluated against wins, the
+    // lowest node index among equals.  Not together with pick_uniform: refused before anything is evaluated.  Outside the parity claim.
+    // 0: nothing changes, draw for draw.
+    uint32_t pick_spread = 0;
+
     // (Re)build `snapshot` from node_store and one LIST per node.
     void refresh_snapshot();
     // Keep node_store and the snapshot current from node watch events, the way the reflector's writer does: an Applied node already in

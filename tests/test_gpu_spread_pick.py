@@ -1,0 +1,547 @@
+"""KSCHED_PICK_SPREAD (extension E4) on the GPU through every entry point that accepts it, against tests/spread_ref.py (the numpy
+restatement, pinned by tests/test_spread_restatement.py) applied to the ORACLE's feasibility mask and the snapshot's columns.  Exact
+integers: every binding and every mask word must be identical.  Shapes are the smallest at which the kernel takes each of its paths:
+rows within one wave pass (W <= 128 words), the shortest two-pass row (W = 129), a row of seven chunks, a last word with one valid bit,
+d = 1 (the uniform pick), 2, 5 and 64 (every lane of the wave holds a candidate), pod counts around a block of four waves."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM, SEL, TAINT, KschedError, _lib, synth,
+                                             unpack_mask)
+from oracle import capi
+from tests.spread_ref import best_of, spread_candidates, spread_candidates_listed, spread_pick
+from tests.test_gpu_uniform_pick import dev_of, mask_np, oracle_mask, pitched_mask, pod_tensors, to_dev
+from tests.uniform_ref import uniform_pick
+
+pytestmark = pytest.mark.gpu
+
+# (P, N, n_keys, n_taints, seed)
+MID = (1200, 2600, 8, 0, 55)
+TWO_PASS = (900, 8200, 8, 16, 11)  # W = 129: the shortest two-pass row
+CLUSTERS = [(700, 130, 8, 16, 7), MID, TWO_PASS, (600, 50200, 8, 16, 5), (333, 65, 2, 0, 2), (300, 1, 0, 0, 1)]
+DS = [1, 2, 5, 64]
+_CASES = {}
+
+
+def case(spec):
+    """The cluster, its predicate flags, the oracle's feasible mask, a [P, 64] table of full-range 32-bit draws and every draw's candidate:
+    computed once per cluster.  want(d): the restatement's bindings for the first d columns."""
+    if spec not in _CASES:
+        P, N, n_keys, n_taints, seed = spec
+        c = synth.make_cluster(P, N, n_keys=n_keys, n_taints=n_taints, seed=seed)
+        flags = FIT | (SEL if n_keys else 0) | (TAINT if n_taints else 0)
+        feas = oracle_mask(c, flags)
+        feas.setflags(write=False)
+        draws = np.random.default_rng(seed * 1000 + 17).integers(0, 1 << 32, size=(P, 64), dtype=np.uint64).astype(np.uint32)
+        draws.setflags(write=False)
+        cand = spread_candidates_listed(feas, draws, N)
+        for j in (0, 63):  # (the listed route is pinned without a GPU; here once more against the restatement's own, at this shape)
+            assert np.array_equal(cand[:, j], uniform_pick(feas, draws[:, j], N))
+        cand.setflags(write=False)
+        _CASES[spec] = dict(c=c, flags=flags, feas=feas, draws=draws, cand=cand, want={})
+    return _CASES[spec]
+
+
+def want_of(k, d):
+    if d not in k["want"]:
+        k["want"][d] = best_of(k["cand"][:, :d], k["c"].avail_mem, k["c"].avail_cpu)
+        k["want"][d].setflags(write=False)
+    return k["want"][d]
+
+
+def table(k, d, lo=0, hi=None):
+    return np.ascontiguousarray(k["draws"][lo:hi, :d])
+
+
+def fresh(ev, p, extra=0):
+    import torch
+    return torch.full((p + extra,), -7, dtype=torch.int32, device=dev_of(ev))
+
+
+@pytest.fixture
+def ev(evaluator):
+    evaluator.set_kernel("auto")
+    yield evaluator
+    evaluator.set_kernel("auto")
+    evaluator.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+# ---- 1. parity ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d", DS)
+@pytest.mark.parametrize("spec,kernel", [(s, "auto") for s in CLUSTERS] + [(MID, "direct")], ids=lambda v: v if isinstance(v, str) else f"{v[0]}x{v[1]}")
+def test_parity_in_every_output_form(ev, spec, kernel, d):
+    import torch
+    k = case(spec)
+    c, flags, feas = k["c"], k["flags"] | PICK_SPREAD, k["feas"]
+    draws, want = table(k, d), want_of(k, d)
+    if c.N >= 130 and d == 5:  # the input condition: the test cannot pass vacuously
+        other = (want >= 0) & (want != k["cand"][:, 0])
+        none = k["cand"][:, 0] < 0
+        print(f"{c.P} x {c.N}: {100 * other.mean():.1f} % of the pods bind to another node than their candidate 0, {100 * none.mean():.1f} % have no feasible node")
+        assert other.mean() >= 0.35 and none.mean() >= 0.01
+    ev.set_kernel(kernel)
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    smp = to_dev(ev, draws, np.int32)
+    # the mask pitched (rows on cache-line boundaries)
+    m = ev.alloc_mask(c.P, pitched=True)
+    b = fresh(ev, c.P)
+    ev.eval_device(cpu, mem, sel, tol, smp, flags, out_feasible=m, out_binding=b)
+    torch.cuda.synchronize()
+    assert ev.last_pick == "spread" and (kernel == "auto" or ev.last_kernel == "direct")
+    assert np.array_equal(mask_np(m), feas), "pitched mask"
+    assert np.array_equal(b.cpu().numpy(), want), "bindings beside the pitched mask"
+    # the mask packed: ksched_eval_device itself (pitch = W: rows 8-byte aligned only when W is odd)
+    m2 = torch.full((c.P, ev.W), 0x5A5A5A5A, dtype=torch.int64, device=dev_of(ev))
+    b2 = fresh(ev, c.P)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = ev._lib.ksched_eval_device(ev._h, c.P, ptr(cpu), ptr(mem), ptr(sel), ptr(tol), ptr(smp), d, flags, ptr(m2), None, ptr(b2),
+                                    C.c_void_p(torch.cuda.current_stream(ev.device).cuda_stream))
+    assert rc == _lib.OK
+    torch.cuda.synchronize()
+    assert np.array_equal(mask_np(m2), feas), "packed mask"
+    assert np.array_equal(b2.cpu().numpy(), want), "bindings beside the packed mask"
+    # bindings only: the mask kernel writes the ctx's scratch mask
+    b3 = fresh(ev, c.P)
+    ev.eval_device(cpu, mem, sel, tol, smp, flags, out_binding=b3)
+    torch.cuda.synchronize()
+    assert ev.last_pick == "spread"
+    assert np.array_equal(b3.cpu().numpy(), want), "bindings only"
+    # host pointers: ksched_eval, with and without the mask
+    pc = c.pod_columns()
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags)
+    assert np.array_equal(r.feasible, feas) and np.array_equal(r.binding, want), "ksched_eval"
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags, want_mask=False)
+    assert r.feasible is None and np.array_equal(r.binding, want), "ksched_eval, bindings only"
+    if d == 1:  # bit for bit what the device gives for the uniform pick of the same column
+        b4 = fresh(ev, c.P)
+        ev.eval_device(cpu, mem, sel, tol, smp, k["flags"] | PICK_UNIFORM, out_binding=b4)
+        torch.cuda.synchronize()
+        assert ev.last_pick == "uniform"
+        assert np.array_equal(b4.cpu().numpy(), want), "d = 1 against the device's uniform pick"
+
+
+# ---- 2. each key decides ------------------------------------------------------------------------------------------------------
+def quantised(a):
+    """every node's value replaced by the smallest value of its rank quartile (stable ascending rank)"""
+    order = np.argsort(a, kind="stable")
+    rank = np.empty(a.size, np.int64)
+    rank[order] = np.arange(a.size)
+    quartile = rank * 4 // a.size
+    floor = np.array([a[order][quartile[order] == q][0] for q in range(4)], dtype=a.dtype)
+    return floor[quartile]
+
+
+def decided_by(cand, want, mem, cpu):
+    """per bound pod what settled the comparison among its DISTINCT candidates: 0 memory (one of them has the largest), 1 cpu (several tie in
+    memory, one of those has the largest cpu), 2 the node index (several tie in both), -1 nothing (one distinct candidate, or no node)"""
+    out = np.full(cand.shape[0], -1)
+    for i in np.nonzero(want >= 0)[0]:
+        v = np.unique(cand[i])
+        if v.size < 2:
+            continue
+        top = v[mem[v] == mem[v].max()]
+        if top.size == 1:
+            out[i] = 0
+            continue
+        top = top[cpu[top] == cpu[top].max()]
+        out[i] = 1 if top.size == 1 else 2
+    return out
+
+
+def test_memory_cpu_and_the_node_index_each_decide(ev):
+    import torch
+    k = case(MID)
+    c, flags, d = k["c"], k["flags"], 5
+    draws = table(k, d)
+    q_mem, q_cpu = quantised(c.avail_mem), quantised(c.avail_cpu)
+    assert np.unique(q_mem).size <= 4 and np.unique(q_cpu).size <= 4
+    cpu_t, mem_t, sel, tol = pod_tensors(ev, c)
+    smp = to_dev(ev, draws, np.int32)
+    snapshots = [("both columns quantised", q_mem, q_cpu), ("all memory equal", np.full(c.N, q_mem.max()), q_cpu),
+                 ("both columns equal", np.full(c.N, q_mem.max()), np.full(c.N, q_cpu.max()))]
+    for name, mem, cpu in snapshots:
+        feas = oracle_mask(c, flags, cpu, mem)  # (the fit is taken over these columns)
+        cand = spread_candidates(feas, draws, c.N)
+        want = best_of(cand, mem, cpu)
+        ev.set_nodes(**dict(c.node_columns(), avail_cpu_milli=cpu, avail_mem_bytes=mem))
+        m = ev.alloc_mask(c.P, pitched=True)
+        b = fresh(ev, c.P)
+        ev.eval_device(cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, out_feasible=m, out_binding=b)
+        torch.cuda.synchronize()
+        assert np.array_equal(mask_np(m), feas), name
+        assert np.array_equal(b.cpu().numpy(), want), name
+        why = decided_by(cand, want, mem, cpu)
+        bound = (want >= 0).sum()
+        share = [float((why == r).sum()) / bound for r in range(3)]
+        print(f"{name}: memory decides {100 * share[0]:.1f} %, cpu {100 * share[1]:.1f} %, the node index {100 * share[2]:.1f} % of {bound} bound pods")
+        if name == "both columns quantised":
+            assert min(share) >= 0.15
+        elif name == "all memory equal":
+            assert share[0] == 0 and share[1] > 0 and share[2] > 0
+        else:
+            assert share[0] == 0 and share[1] == 0 and share[2] > 0
+            assert np.array_equal(want[want >= 0], cand[want >= 0].min(axis=1)), "all equal: the lowest candidate"
+
+
+# ---- 4. shape edges -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", [1, 3, 4, 5, 257])
+def test_pod_counts_around_a_block_under_every_edge_of_attempts(ev, p):
+    import torch
+    k = case(MID)
+    c = k["c"]
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c, 0, p)
+    for d in (1, 2, 63, 64):
+        want = best_of(k["cand"][:p, :d], c.avail_mem, c.avail_cpu)
+        buf = fresh(ev, p, 8)
+        ev.eval_device(cpu, mem, sel, tol, to_dev(ev, table(k, d, 0, p), np.int32), k["flags"] | PICK_SPREAD, out_binding=buf[:p])
+        torch.cuda.synchronize()
+        got = buf.cpu().numpy()
+        assert np.array_equal(got[:p], want) and (got[p:] == -7).all(), f"p = {p}, attempts = {d}"
+
+
+def test_no_nodes_and_no_pods(ev):
+    import torch
+    z5 = np.zeros(5, np.int64)
+    ev.set_nodes(np.zeros(0, np.int64), np.zeros(0, np.int64))
+    r = ev.eval(z5, z5, samples=np.full((5, 3), 0xFFFFFFFF, np.uint32), flags=FIT | PICK_SPREAD)
+    assert r.feasible.shape == (5, 0) and (r.binding == -1).all()
+    b = fresh(ev, 5)
+    smp = to_dev(ev, np.zeros((5, 3), np.uint32), np.int32)
+    ev.eval_device(to_dev(ev, z5, np.int64), to_dev(ev, z5, np.int64), None, None, smp, FIT | PICK_SPREAD, out_binding=b)
+    torch.cuda.synchronize()
+    assert (b.cpu().numpy() == -1).all()
+    b.fill_(-7)
+    ev.pick_device(torch.empty((5, 0), dtype=torch.int64, device=dev_of(ev)), PICK_SPREAD, b, samples=smp)
+    torch.cuda.synchronize()
+    assert (b.cpu().numpy() == -1).all()
+    assert (ev.pick(np.zeros((5, 0), np.uint64), PICK_SPREAD, samples=np.zeros((5, 3), np.uint32)) == -1).all()
+    # no pods: KSCHED_OK, nothing written
+    ev.set_nodes(np.ones(10, np.int64), np.ones(10, np.int64))
+    lib, h = ev._lib, ev._h
+    guard = fresh(ev, 4)
+    gp = C.c_void_p(guard.data_ptr())
+    host_guard = np.full(4, -7, np.int32)
+    hp = host_guard.ctypes.data_as(C.c_void_p)
+    assert lib.ksched_eval_device(h, 0, None, None, None, None, None, 2, FIT | PICK_SPREAD, None, None, gp, None) == _lib.OK
+    assert lib.ksched_pick_device(h, 0, None, 1, None, None, 2, PICK_SPREAD, gp, None) == _lib.OK
+    assert lib.ksched_eval(h, 0, None, None, None, None, None, 2, FIT | PICK_SPREAD, None, None, hp) == _lib.OK
+    assert lib.ksched_pick(h, 0, None, None, None, 2, PICK_SPREAD, hp) == _lib.OK
+    torch.cuda.synchronize()
+    assert (guard.cpu().numpy() == -7).all() and (host_guard == -7).all()
+
+
+def test_argument_errors(ev):
+    import torch
+    ev.set_nodes(np.ones(10, np.int64), np.arange(10, dtype=np.int64))
+    lib, h = ev._lib, ev._h
+    z = np.zeros(4, np.int64)
+    smp = np.zeros((4, 64), np.uint32)
+    mask = np.zeros((4, 1), np.uint64)
+    out = np.full(4, -7, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    d_z, d_smp, d_mask = to_dev(ev, z, np.int64), to_dev(ev, smp, np.int32), to_dev(ev, mask, np.int64)
+    d_out = fresh(ev, 4)
+    dp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    pipe = ev.pipe(1)
+    # (flags, samples given, attempts, binding given)
+    bad = [(PICK_SPREAD | PICK_SAMPLED, True, 5, True), (PICK_SPREAD | PICK_BESTFIT, True, 5, True), (PICK_SPREAD | PICK_UNIFORM, True, 5, True),
+           (PICK_SPREAD, False, 5, True), (PICK_SPREAD, True, 0, True), (PICK_SPREAD, True, 65, True), (PICK_SPREAD, True, 5, False)]
+    for flags, have_smp, attempts, have_out in bad:
+        what = (hex(flags), have_smp, attempts, have_out)
+        assert lib.ksched_eval(h, 4, p(z), p(z), None, None, p(smp) if have_smp else None, attempts, FIT | flags, None, None,
+                               p(out) if have_out else None) == _lib.E_INVAL, what
+        assert lib.ksched_eval_device(h, 4, dp(d_z), dp(d_z), None, None, dp(d_smp) if have_smp else None, attempts, FIT | flags, None, None,
+                                      dp(d_out) if have_out else None, None) == _lib.E_INVAL, what
+        assert lib.ksched_pick_device(h, 4, dp(d_mask), 1, None, dp(d_smp) if have_smp else None, attempts, flags,
+                                      dp(d_out) if have_out else None, None) == _lib.E_INVAL, what
+        assert lib.ksched_pick(h, 4, p(mask), None, p(smp) if have_smp else None, attempts, flags, p(out) if have_out else None) == _lib.E_INVAL, what
+        assert lib.ksched_pipe_submit(pipe._h, 0, 4, dp(d_z), dp(d_z), None, None, dp(d_smp) if have_smp else None, attempts, FIT | flags,
+                                      dp(d_mask), 1, dp(d_out) if have_out else None) == _lib.E_INVAL, what
+    pipe.close()
+    torch.cuda.synchronize()
+    assert (out == -7).all() and (d_out.cpu().numpy() == -7).all()
+    # the summaries take no pick flag
+    with pytest.raises(KschedError) as e:
+        ev.summarize(z, z, flags=FIT | PICK_SPREAD)
+    assert e.value.code == _lib.E_INVAL
+    # KSCHED_E_STATE where the uniform pick returns it: a ctx without a snapshot
+    from kube_scheduler_rs_reference_amd import Evaluator
+    with Evaluator(ev.device) as bare:
+        for flag in (PICK_UNIFORM, PICK_SPREAD):
+            assert bare._lib.ksched_eval(bare._h, 4, p(z), p(z), None, None, p(smp), 5, FIT | flag, None, None, p(out)) == _lib.E_STATE
+            assert bare._lib.ksched_pick(bare._h, 4, p(mask), None, p(smp), 5, flag, p(out)) == _lib.E_STATE
+            assert bare._lib.ksched_pick_device(bare._h, 4, dp(d_mask), 1, None, dp(d_smp), 5, flag, dp(d_out), None) == _lib.E_STATE
+    assert (out == -7).all()
+    # and a valid call still works on this ctx: every node fits a zero request; memory grows with the index, so the best of (0, 0, ...) is node 0
+    r = ev.eval(z, z, samples=smp[:, :5], flags=FIT | PICK_SPREAD)
+    assert (r.binding == 0).all()
+    full = np.full((4, 2), 0xFFFFFFFF, np.uint32)
+    full[:, 1] = 0
+    assert (ev.eval(z, z, samples=full, flags=FIT | PICK_SPREAD).binding == 9).all()  # candidates 9 and 0: 9 has the most memory
+
+
+# ---- 5. the snapshot the pick reads -------------------------------------------------------------------------------------------
+def test_the_pick_reads_the_snapshot_an_evaluation_enqueued_at_that_point_sees(ev):
+    """ksched_pick_device on ONE mask (the oracle's, of the first snapshot) while the columns change: the candidates stay what they are,
+    the winner among them follows the columns."""
+    import torch
+    k = case(TWO_PASS)
+    c, d = k["c"], 5
+    cand = k["cand"][:, :d]
+    ev.set_nodes(**c.node_columns())
+    mask = to_dev(ev, k["feas"], np.int64)
+    smp = to_dev(ev, table(k, d), np.int32)
+    cpu_t, mem_t, _, _ = pod_tensors(ev, c)
+
+    def pick(stream=None):
+        b = fresh(ev, c.P)
+        ev.pick_device(mask, PICK_SPREAD, b, samples=smp, stream=stream)
+        return b
+
+    b0 = pick()
+    torch.cuda.synchronize()
+    want0 = want_of(k, d)
+    assert np.array_equal(b0.cpu().numpy(), want0)
+    # an update that inverts the order of the candidates: memory and cpu negated on every node some pod drew
+    mem, cpu = c.avail_mem.copy(), c.avail_cpu.copy()
+    idx = np.unique(cand[cand >= 0]).astype(np.uint32)
+    ev.update_nodes(idx, -cpu[idx], -mem[idx])
+    cpu[idx], mem[idx] = -cpu[idx], -mem[idx]
+    want1 = best_of(cand, mem, cpu)
+    assert (want1 != want0).mean() >= 0.25
+    b1 = pick()
+    torch.cuda.synchronize()
+    assert np.array_equal(b1.cpu().numpy(), want1), "after ksched_update_nodes"
+    # an apply of those bindings on the device: every bound pod's request leaves its node
+    ev.apply_bindings_device(b1, cpu_t, mem_t)
+    bound = want1 >= 0
+    np.subtract.at(cpu, want1[bound], c.req_cpu[bound])
+    np.subtract.at(mem, want1[bound], c.req_mem[bound])
+    want2 = best_of(cand, mem, cpu)
+    assert not np.array_equal(want2, want1)
+    b2 = pick()
+    torch.cuda.synchronize()
+    got_cpu, got_mem = ev.read_nodes()
+    assert np.array_equal(got_cpu, cpu) and np.array_equal(got_mem, mem)
+    assert np.array_equal(b2.cpu().numpy(), want2), "after ksched_apply_bindings_device"
+    # a pick enqueued on a second stream right before an update, no host wait between them: the OLD columns.  (The stream is kept busy for
+    # some milliseconds first, so the update is enqueued while the pick has not yet run.)
+    second = torch.cuda.Stream(device=dev_of(ev))
+    try:
+        with torch.cuda.stream(second):
+            torch.cuda._sleep(10_000_000)
+        b3 = pick(stream=second)
+        ev.update_nodes(idx, -cpu[idx], -mem[idx])
+        b4 = pick(stream=second)
+        torch.cuda.synchronize()
+        assert np.array_equal(b3.cpu().numpy(), want2), "a pick enqueued before the update saw the update"
+        cpu[idx], mem[idx] = -cpu[idx], -mem[idx]
+        want4 = best_of(cand, mem, cpu)
+        assert (want4 != want2).mean() >= 0.25
+        assert np.array_equal(b4.cpu().numpy(), want4), "a pick enqueued after the update did not see it"
+    finally:
+        torch.cuda.synchronize()
+        ev.forget_stream(second)
+
+
+# ---- 6. the pipe --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [0, 2])
+def test_pipe_submit_equals_eval_device_pitched(ev, mode):
+    import torch
+    k = case(MID)
+    c, flags, d = k["c"], k["flags"] | PICK_SPREAD, 5
+    ev.set_nodes(**c.node_columns())
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    tables = [table(k, d), np.ascontiguousarray(k["draws"][:, 10:13])]  # one batch of draws per slot: d = 5 and d = 3
+    wants = [want_of(k, d), best_of(k["cand"][:, 10:13], c.avail_mem, c.avail_cpu)]
+    smps = [to_dev(ev, t, np.int32) for t in tables]
+    ref = []
+    for s in smps:
+        m = ev.alloc_mask(c.P, pitched=True)
+        b = fresh(ev, c.P)
+        ev.eval_device(cpu, mem, sel, tol, s, flags, out_feasible=m, out_binding=b)
+        ref.append((m, b))
+    torch.cuda.synchronize()
+    for (m, b), w in zip(ref, wants):
+        assert np.array_equal(mask_np(m), k["feas"]) and np.array_equal(b.cpu().numpy(), w)
+    ev.set_option(_lib.OPT_PIPE_MODE, mode)
+    pipe = ev.pipe(2)
+    try:
+        masks = [ev.alloc_mask(c.P, pitched=True) for _ in range(2)]
+        outs = [fresh(ev, c.P) for _ in range(2)]
+        for m in masks:
+            m.fill_(0)
+        torch.cuda.synchronize()
+        for slot in range(2):
+            pipe.submit(slot, cpu, mem, sel, tol, smps[slot], flags, masks[slot], outs[slot])
+        for slot in range(2):
+            pipe.wait(slot, host=True)
+            pipe.wait_mask(slot, host=True)
+        for slot in range(2):
+            assert torch.equal(masks[slot], ref[slot][0]), f"mask of slot {slot}"
+            assert torch.equal(outs[slot], ref[slot][1]), f"bindings of slot {slot}"
+    finally:
+        pipe.close()
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+def mid_sampled():
+    """the oracle's sampled bindings of the MID cluster (its own [P, 5] table of node draws), computed once"""
+    k = case(MID)
+    if "sampled" not in k:
+        c = k["c"]
+        k["sampled"] = capi.eval_encoded(c.avail_cpu, c.avail_mem, c.node_labels, None, c.req_cpu, c.req_mem, np.ascontiguousarray(c.pod_sel), None,
+                                         c.samples, k["flags"] | PICK_SAMPLED, want_mask=False)[2]
+    return k["sampled"]
+
+
+def mid_batch(ev, lo, hi, spread, d=5):
+    """pods [lo, hi) of the MID cluster as one pipe submit: (device columns incl. the draws, flags, expected mask, expected bindings)"""
+    k = case(MID)
+    c = k["c"]
+    cols = pod_tensors(ev, c, lo, hi) + (to_dev(ev, table(k, d, lo, hi) if spread else c.samples[lo:hi], np.int32),)
+    want = want_of(k, d) if spread else mid_sampled()
+    return cols, k["flags"] | (PICK_SPREAD if spread else PICK_SAMPLED), k["feas"][lo:hi], want[lo:hi]
+
+
+@pytest.mark.parametrize("mode", [0, 2, 3])
+def test_one_pipe_alternates_spread_and_sampled_submits_on_the_same_slots(ev, mode):
+    """Nine submits into a pipe of depth 3, spread and sampled in turn (slot 0: S s S, slot 1: s S s, slot 2: S s S), every submit a
+    different slice of the MID cluster into the slot's one mask and one binding buffer, with no host wait in between.  The bindings of every
+    submit (copied on the slot's pick stream right behind it) and the final mask and bindings of every slot equal the oracle's.  The spread
+    pick reads the mask, so its submits take the split route, like the uniform pick's."""
+    import torch
+    P, step, size, submits = 1200, 100, 300, 9
+    ev.set_nodes(**case(MID)["c"].node_columns())
+    ev.set_option(_lib.OPT_PIPE_MODE, mode)
+    pipe = ev.pipe(3)
+    try:
+        masks = [ev.alloc_mask(size, pitched=True) for _ in range(3)]
+        outs = [fresh(ev, size) for _ in range(3)]
+        copies = torch.full((submits, size), -7, dtype=torch.int32, device=dev_of(ev))
+        torch.cuda.synchronize()
+        batches = [mid_batch(ev, i * step, i * step + size, spread=i % 2 == 0) for i in range(submits)]  # (inputs stay alive and untouched)
+        assert batches[-1][2].shape[0] == size and (submits - 1) * step + size <= P
+        torch.cuda.synchronize()
+        for i, (cols, flags, _, _) in enumerate(batches):
+            slot = i % 3
+            pipe.submit(slot, *cols, flags, masks[slot], outs[slot])
+            with torch.cuda.stream(pipe.slot_stream(slot)):
+                copies[i].copy_(outs[slot])
+        for slot in range(3):
+            pipe.wait(slot, host=True)
+            pipe.wait_mask(slot, host=True)
+        torch.cuda.synchronize()
+        got = copies.cpu().numpy()
+        for i, (_, flags, _, want) in enumerate(batches):
+            assert np.array_equal(got[i], want), f"mode {mode}: bindings of submit {i} (slot {i % 3}, {'spread' if flags & PICK_SPREAD else 'sampled'})"
+        for slot in range(3):
+            _, _, feas, want = batches[submits - 3 + slot]
+            assert np.array_equal(mask_np(masks[slot]), feas), f"mode {mode}: final mask of slot {slot}"
+            assert np.array_equal(outs[slot].cpu().numpy(), want), f"mode {mode}: final bindings of slot {slot}"
+    finally:
+        pipe.close()
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+def test_a_sampled_submit_does_not_overwrite_the_mask_its_slots_spread_pick_still_reads(ev):
+    """A spread submit whose pick is held up on the pick stream (by the caller's own work enqueued there, a short device-side spin), then a
+    sampled submit of another batch into the same slot: the sampled submit's mask kernel must wait for the spread pick, or that pick ranks
+    the set bits of the other batch's mask."""
+    import torch
+    ev.set_nodes(**case(MID)["c"].node_columns())
+    ev.set_option(_lib.OPT_PIPE_MODE, 0)
+    pipe = ev.pipe(1)
+    try:
+        size = 300
+        mask = ev.alloc_mask(size, pitched=True)
+        out, first = fresh(ev, size), fresh(ev, size)
+        a, b = mid_batch(ev, 0, size, spread=True), mid_batch(ev, 600, 600 + size, spread=False)
+        assert not np.array_equal(a[2], b[2])
+        torch.cuda.synchronize()
+        with torch.cuda.stream(pipe.stream(1)):
+            torch.cuda._sleep(10_000_000)  # some milliseconds of the pick stream: longer than the two submits take to enqueue
+        pipe.submit(0, *a[0], a[1], mask, out)
+        with torch.cuda.stream(pipe.slot_stream(0)):
+            first.copy_(out)
+        pipe.submit(0, *b[0], b[1], mask, out)
+        pipe.wait(0, host=True)
+        pipe.wait_mask(0, host=True)
+        torch.cuda.synchronize()
+        assert np.array_equal(first.cpu().numpy(), a[3]), "the spread pick read a mask that the slot's next submit had overwritten"
+        assert np.array_equal(mask_np(mask), b[2]) and np.array_equal(out.cpu().numpy(), b[3])
+    finally:
+        pipe.close()
+
+
+# ---- 7. seeded differential loop ---------------------------------------------------------------------------------------------
+def test_seeded_differential_loop(ev):
+    import torch
+    entries = ["eval_device", "eval_device, bindings only", "eval", "pick_device", "pick", "pipe"]
+    seen = set()
+    for seed in range(12):
+        rng = np.random.default_rng(0x5EED + seed)
+        P, N = int(rng.integers(2, 401)), int(rng.choice([int(rng.integers(1, 3001)), int(rng.integers(8193, 9001))], p=[0.75, 0.25]))
+        d = int(rng.choice([1, 2, 3, 5, 8, 33, 64]))
+        n_keys, n_taints = int(rng.choice([0, 3, 8])), int(rng.choice([0, 16]))
+        c = synth.make_cluster(P, N, n_keys=n_keys, n_taints=n_taints, seed=2000 + seed)
+        flags = int(rng.choice([FIT, FIT | SEL, FIT | TAINT, SEL | TAINT, FIT | SEL | TAINT, SEL]))
+        flags &= FIT | (SEL if n_keys else 0) | (TAINT if n_taints else 0)
+        flags = flags or FIT
+        entry = entries[(seed + int(rng.integers(0, 2)) * 3) % 6] if seed >= 6 else entries[seed]  # every entry point at least once
+        seen.add(entry)
+        # columns with ties: a few distinct values; in every second case a quarter of the nodes negative in either column (such a node fits
+        # no pod, and stays a candidate where the fit term is off)
+        mem = c.avail_mem if rng.random() < 0.5 else (c.avail_mem >> 32) << 32
+        cpu = c.avail_cpu if rng.random() < 0.5 else (c.avail_cpu // 4000) * 4000
+        if seed % 2:
+            mem = np.where(rng.random(N) < 0.25, -mem - 1, mem)
+            cpu = np.where(rng.random(N) < 0.25, -cpu - 1, cpu)
+        feas = oracle_mask(c, flags, cpu, mem)
+        draws = rng.integers(0, 1 << 32, size=(P, d), dtype=np.uint64).astype(np.uint32)
+        want = spread_pick(feas, draws, N, mem, cpu)
+        ev.set_kernel(str(rng.choice(["auto", "direct"])))
+        ev.set_nodes(**dict(c.node_columns(), avail_cpu_milli=cpu, avail_mem_bytes=mem))
+        cpu_t, mem_t, sel, tol = pod_tensors(ev, c)
+        smp = to_dev(ev, draws, np.int32)
+        pitch = ev.W + int(rng.integers(0, 4))
+        what = f"seed {seed}: {P} x {N}, d = {d}, flags {flags:#x}, pitch {pitch}, {entry}"
+        b = fresh(ev, P)
+        got_mask = None
+        if entry == "eval_device":
+            m = pitched_mask(ev, P, pitch)
+            ev.eval_device(cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, out_feasible=m, out_binding=b)
+            got_mask = m
+        elif entry == "eval_device, bindings only":
+            ev.eval_device(cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, out_binding=b)
+        elif entry == "eval":
+            pc = c.pod_columns()
+            r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags | PICK_SPREAD)
+            assert np.array_equal(r.feasible, feas) and np.array_equal(r.binding, want), what
+            continue
+        elif entry == "pick_device":
+            host = np.full((P, pitch), 0xFFFFFFFFFFFFFFFF, np.uint64)  # (padding words all ones)
+            host[:, :ev.W] = feas
+            ev.pick_device(to_dev(ev, host, np.int64)[:, :ev.W], PICK_SPREAD, b, samples=smp)
+        elif entry == "pick":
+            assert np.array_equal(ev.pick(feas, PICK_SPREAD, samples=draws), want), what
+            continue
+        else:
+            m = pitched_mask(ev, P, pitch)
+            pipe = ev.pipe(1)
+            try:
+                pipe.submit(0, cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, m, b)
+                pipe.wait(0, host=True)
+                pipe.wait_mask(0, host=True)
+            finally:
+                pipe.close()
+            got_mask = m
+        torch.cuda.synchronize()
+        if got_mask is not None:
+            assert np.array_equal(mask_np(got_mask), feas), what
+        assert np.array_equal(b.cpu().numpy(), want), what
+    assert seen == set(entries)

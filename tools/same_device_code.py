@@ -8,11 +8,17 @@ Compiles kube_scheduler_rs_reference_amd/csrc/ksched_api.hip to device assembly 
 two files line by line.  Lines that name __hip_cuid_ are left out: that symbol carries a hash of the whole translation unit, so
 it changes with any edit, host code included.  Exit status 0: identical; 1: they differ (the first differing lines are printed).
 
+When the files differ the functions are compared one by one as well, by name, with the function's ordinal masked in its local labels
+(.LBB<n>_<block>, .Lfunc_end<n>, "Header=BB<n>_<block>" comments): a change that ADDS a kernel moves the ordinals of the functions
+emitted after it and nothing else of them.  The last line then names the functions added, removed and changed; exit status 2 when none
+was removed or changed (every function of REV is in the work tree with the same instructions), 1 otherwise.
+
 What it is for: a refactor of the host side (the dispatch, the ABI functions) must leave every kernel as it was; with this
 check passing, any difference in results or speed is in the host path.  No GPU is needed; each compile takes about 45 s, the two
 run side by side."""
 import io
 import os
+import re
 import subprocess
 import sys
 import tarfile
@@ -32,6 +38,20 @@ def compile_command():
 def device_lines(path):
     with open(path) as f:
         return [ln for ln in f if "__hip_cuid_" not in ln]
+
+
+def functions(lines):
+    """{name: its lines between "Begin function" and "End function", the function's ordinal masked in local labels}"""
+    out, cur = {}, None
+    for ln in lines:
+        m = re.search(r"; -- Begin function (\S+)", ln)
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif "; -- End function" in ln:
+            cur = None
+        elif cur is not None:
+            cur.append(re.sub(r"(\.LBB|\bBB|\.Lfunc_begin|\.Lfunc_end|\.Ltmp)\d+(?=_|\b)", r"\1N", ln))
+    return out
 
 
 def main():
@@ -60,7 +80,13 @@ def main():
             print(f"line {i + 1}:\n  {rev}: {b.rstrip()}\n  work tree: {a.rstrip()}")
             shown += 1
     print(f"device code DIFFERS: {len(new_s)} lines in the work tree, {len(old_s)} in {rev}")
-    return 1
+    new_f, old_f = functions(new_s), functions(old_s)
+    added = sorted(set(new_f) - set(old_f))
+    removed = sorted(set(old_f) - set(new_f))
+    changed = sorted(k for k in old_f if k in new_f and old_f[k] != new_f[k])
+    print(f"function by function (local label ordinals masked): {len(old_f) - len(removed) - len(changed)} of {rev}'s {len(old_f)} functions have the same "
+          f"instructions in the work tree; added {added}; removed {removed}; changed {changed}")
+    return 1 if removed or changed else 2
 
 
 if __name__ == "__main__":
