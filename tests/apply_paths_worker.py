@@ -7,7 +7,13 @@ An apply writes `available` in three places -- the columns, the node records (re
 form, ksched_explain and the list-key best fit) and the dirty tiles of the bitmap index -- so after each apply every path that reads any
 of them is run and compared with the oracle (capi.eval_encoded, and for ksched_explain the reason rebuilt from single-predicate oracle
 masks) on the columns the exact-integer restatement (oracle_ref.apply_bindings_exact) gives.  Every mask word, fit-mask word, binding and
-reason is compared.  A case prints "ok <case>" as its last line when all its checks passed.
+reason is compared.  The spread pick (KSCHED_PICK_SPREAD) is the one pick whose bindings depend on the VALUES of the columns and not only
+on which nodes are feasible: its expected bindings are tests/spread_ref.py on the oracle's mask and on the restated columns, so a column
+left stale by an apply on some stream shows as a few wrong bindings.  A case prints "ok <case>" as its last line when all its checks passed.
+
+The sequence of a case (snapshots, rounds, which pick's bindings an apply takes, the input conditions) is walk_single, which takes the
+device as three callables: tests/test_apply_paths_host.py walks it with the oracle and the restatements alone and asserts the same
+input conditions without a GPU.
 """
 from __future__ import annotations
 
@@ -17,9 +23,11 @@ import sys
 import numpy as np
 import torch
 
-from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth, unpack_mask
+from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator,
+                                             KschedError, _lib, synth, unpack_mask)
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact
+from tests.spread_ref import spread_pick_blocks
 from tests.test_gpu_apply_bindings import random_bindings
 from tests.uniform_ref import uniform_pick_blocks
 
@@ -76,7 +84,9 @@ def snapshot(kind, N, P, seed):
                 rc=c.req_cpu, rm=c.req_mem, sel=np.ascontiguousarray(sel), tol=tol, preds=preds, indexed=kind != "unindexed",
                 smp5=rng.integers(0, N + 2, (P, 5)).astype(np.uint32), smp3=rng.integers(0, N, (P, 3)).astype(np.uint32),
                 # full-range 32-bit draws for the uniform pick, from a generator of their own: every other value is what it was without them
-                smpU=np.random.default_rng([seed, 0x55]).integers(0, 1 << 32, (P, 5), dtype=np.uint64).astype(np.uint32))
+                smpU=np.random.default_rng([seed, 0x55]).integers(0, 1 << 32, (P, 5), dtype=np.uint64).astype(np.uint32),
+                # and for the spread pick: 64 columns, of which a leg reads the first d
+                smpS=np.random.default_rng([seed, 0x5E]).integers(0, 1 << 32, (P, 64), dtype=np.uint64).astype(np.uint32))
 
 
 def set_nodes(ev, S, cpu, mem):
@@ -109,15 +119,73 @@ def assert_input_condition(feas, N, what):
     assert two >= 0.50 and none >= 0.01, f"{what}: {100 * two:.1f} % of the pods have two or more feasible nodes, {100 * none:.1f} % none"
 
 
+def spread_restated(S, feas, cpu, mem, d):
+    """KSCHED_PICK_SPREAD restated for the first d columns of the snapshot's draw table, on the mask `feas` and the columns cpu / mem"""
+    return spread_pick_blocks(feas, S["smpS"][:, :d], S["N"], mem, cpu)
+
+
+def assert_spread_input_condition(S, feas, bind_p5, what):
+    """the spread legs cannot pass vacuously (the rule of tests/test_gpu_spread_pick.py::test_parity_in_every_output_form): 35 % of the pods
+    or more are bound by the d = 5 restatement to another node than their candidate 0, so an evaluation that ranked nothing fails"""
+    cand0 = uniform_pick_blocks(feas, S["smpS"][:, 0], S["N"])
+    other = float(((bind_p5 >= 0) & (bind_p5 != cand0)).mean())
+    print(f"{what}: the spread pick (d = 5) binds {100 * other:.1f} % of the pods to another node than their candidate 0")
+    assert other >= 0.35, f"{what}: the spread pick (d = 5) binds {100 * other:.1f} % of the pods to another node than their candidate 0"
+
+
+def oracle_mask(S, cpu, mem, preds):
+    return capi.eval_encoded(cpu, mem, S["lab"], S["tnt"] if preds & TAINT else None, S["rc"], S["rm"], S["sel"],
+                             S["tol"] if preds & TAINT else None, None, preds)[0]
+
+
+def stale_spread_bindings(S, cpu, mem, cpu_before, mem_before):
+    """how many pods the d = 5 spread restatement binds differently on the columns from before an apply than on those after it, both on the
+    mask after it (first predicate set): an evaluation that read a stale column after that apply is wrong for so many pods"""
+    feas = oracle_mask(S, cpu, mem, S["preds"][0])
+    return int((spread_restated(S, feas, cpu, mem, 5) != spread_restated(S, feas, cpu_before, mem_before, 5)).sum())
+
+
+def explain_pairs(rng, P, N, n_pairs=4000):
+    return rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
+
+
+def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False):
+    """check_matrix without a device: what it returns when every comparison holds -- the oracle's or the restatement's bindings of the
+    `hand_on` pick under the first predicate set -- with the same input conditions asserted and the generator advanced alike"""
+    out_b = None
+    for k, preds in enumerate(S["preds"]):
+        w = f"{what} preds={preds:#x}"
+        if input_condition or (k == 0 and hand_on in ("uniform", "spread")):
+            feas = oracle_mask(S, cpu, mem, preds)
+        if input_condition:
+            assert_input_condition(feas, S["N"], w)
+            assert_spread_input_condition(S, feas, spread_restated(S, feas, cpu, mem, 5), w)
+        if k == 0 and hand_on == "sampled":
+            out_b = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"] if preds & TAINT else None, S["rc"], S["rm"], S["sel"],
+                                      S["tol"] if preds & TAINT else None, S["smp5"], preds | PICK_SAMPLED, want_mask=False)[2]
+        elif k == 0 and hand_on == "uniform":
+            out_b = uniform_pick_blocks(feas, S["smpU"][:, 0], S["N"])
+        elif k == 0 and hand_on == "spread":
+            out_b = spread_restated(S, feas, cpu, mem, 5)
+        explain_pairs(rng, S["P"], S["N"])
+    return out_b
+
+
 def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False):
     """every evaluation path of `ev` (whose snapshot should hold cpu / mem) against the oracle; the names of the picks that ran go into
     `seen`.  reduced: the kernels and options at their defaults, plus the direct kernel, the waves-form pick, bindings-only "select",
-    best fit, the uniform pick, ksched_pick and ksched_explain.  input_condition: assert_input_condition on every predicate set's mask.
-    -> the device bindings of a sampled pick, or with hand_on="uniform" of a uniform pick (a real evaluation's bindings for the next apply)"""
+    best fit, the uniform pick, the spread pick, ksched_pick and ksched_explain.  input_condition: assert_input_condition and
+    assert_spread_input_condition on every predicate set's mask.
+    The spread legs, per predicate set, against tests/spread_ref.py on the oracle's mask and on cpu / mem (the columns after the apply):
+    d = 5 beside the mask on every kernel choice; d = 2, bindings only, through host and device pointers; ksched_eval_device with d = 5
+    beside a mask (last_pick == "spread" in both forms); ksched_pick from the oracle's host mask with d = 64; and once per matrix d = 1,
+    which must be the restatement's uniform pick for column 0 of the same draws.
+    -> the device bindings, under the first predicate set, of the pick `hand_on` names: "sampled", "uniform" or "spread" (a real
+    evaluation's bindings for the next apply); None with hand_on=None"""
     P, N = S["P"], S["N"]
     rc, rm, sel = S["rc"], S["rm"], S["sel"]
     out_b = None
-    for preds in S["preds"]:
+    for n_set, preds in enumerate(S["preds"]):
         tnt = S["tnt"] if preds & TAINT else None
         tol = S["tol"] if preds & TAINT else None
         w = f"{what} preds={preds:#x}"
@@ -125,8 +193,12 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
         bind_b = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, None, preds | PICK_BESTFIT, want_mask=False)[2]
         bind_3 = capi.eval_encoded(cpu, mem, S["lab"], tnt, rc, rm, sel, tol, S["smp3"], preds | PICK_SAMPLED, want_mask=False)[2]
         bind_u = uniform_pick_blocks(feas, S["smpU"][:, 0], N)  # KSCHED_PICK_UNIFORM restated, on the oracle's mask
+        # KSCHED_PICK_SPREAD restated, on the oracle's mask and the columns this matrix was called with
+        bind_p5, bind_p2, bind_p64 = (spread_restated(S, feas, cpu, mem, d) for d in (5, 2, 64))
+        smpS5, smpS2 = np.ascontiguousarray(S["smpS"][:, :5]), np.ascontiguousarray(S["smpS"][:, :2])
         if input_condition:
             assert_input_condition(feas, N, w)
+            assert_spread_input_condition(S, feas, bind_p5, w)
 
         def run(flags, smp=None, want_mask=True, expect_b=None, label=""):
             r = ev.eval(rc, rm, sel, tol, smp, flags, want_mask=want_mask)
@@ -165,11 +237,16 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
                 run(preds | PICK_BESTFIT, expect_b=bind_b, label=f"{k} best fit stages={stages}")
             ev.set_option(_lib.OPT_BESTFIT_STAGES, 0)
             run(preds | PICK_UNIFORM, S["smpU"], expect_b=bind_u, label=f"{k} uniform")
+            run(preds | PICK_SPREAD, smpS5, expect_b=bind_p5, label=f"{k} spread d=5")
+            assert ev.last_pick == "spread", f"{w} {k}: a spread pick beside the mask ran as {ev.last_pick}"
         ev.set_kernel("auto")
         # bindings only: the sampled pick is its own launch ("select"), best fit reads no mask
         run(preds | PICK_SAMPLED, S["smp5"], want_mask=False, expect_b=bind_s, label="sampled, bindings only")
         run(preds | PICK_BESTFIT, want_mask=False, expect_b=bind_b, label="best fit, bindings only")
         run(preds | PICK_UNIFORM, S["smpU"], want_mask=False, expect_b=bind_u, label="uniform, bindings only")  # the mask goes to the ctx's scratch
+        run(preds | PICK_SPREAD, smpS2, want_mask=False, expect_b=bind_p2, label="spread d=2, bindings only")  # likewise
+        if n_set == 0:  # d = 1 is the uniform pick: the restatement's own (uniform_ref), for column 0 of the spread draws
+            run(preds | PICK_SPREAD, np.ascontiguousarray(S["smpS"][:, :1]), expect_b=uniform_pick_blocks(feas, S["smpS"][:, 0], N), label="spread d=1")
         if not reduced:  # the mask-reading picks
             ev.set_option(_lib.OPT_PICK_FROM_MASK, 1)
             run(preds | PICK_SAMPLED, S["smp5"], expect_b=bind_s, label="sampled from the mask")
@@ -199,19 +276,34 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
         seen.add(ev.last_pick)
         torch.cuda.synchronize()
         assert np.array_equal(mu.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask beside the uniform pick"
+        smps5_t, smps2_t = t(smpS5, np.int32), t(smpS2, np.int32)
+        mp = torch.empty((P, ev.W), dtype=torch.int64, device=DEV)
+        bp, bp0 = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smps5_t, preds | PICK_SPREAD, out_feasible=mp, out_binding=bp)
+        assert ev.last_pick == "spread", f"{w}: a spread pick beside the mask ran as {ev.last_pick}"
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smps2_t, preds | PICK_SPREAD, out_binding=bp0)
+        assert ev.last_pick == "spread", f"{w}: a bindings-only spread pick ran as {ev.last_pick}"
+        seen.add(ev.last_pick)
+        torch.cuda.synchronize()
+        assert np.array_equal(mp.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask beside the spread pick"
         for got, want, lbl in ((bs, bind_s, "sampled"), (bs0, bind_s, "sampled, bindings only"), (bb, bind_b, "best fit"),
-                               (bu, bind_u, "uniform"), (bu0, bind_u, "uniform, bindings only")):
+                               (bu, bind_u, "uniform"), (bu0, bind_u, "uniform, bindings only"),
+                               (bp, bind_p5, "spread d=5"), (bp0, bind_p2, "spread d=2, bindings only")):
             assert np.array_equal(got.cpu().numpy(), want), f"{w}: eval_device {lbl} bindings"
-        if out_b is None:
-            out_b = (bu if hand_on == "uniform" else bs).cpu().numpy()
+        if out_b is None and hand_on is not None:
+            out_b = {"sampled": bs, "uniform": bu, "spread": bp}[hand_on].cpu().numpy()
         # the pick alone from the oracle's host mask (ksched_pick)
         assert np.array_equal(ev.pick(feas, PICK_SAMPLED, samples=S["smp5"]), bind_s), f"{w}: ksched_pick sampled"
         assert np.array_equal(ev.pick(feas, PICK_BESTFIT | (preds & FIT), req_mem_bytes=rm if preds & FIT else None), bind_b), \
             f"{w}: ksched_pick best fit"
         assert np.array_equal(ev.pick(feas, PICK_UNIFORM, samples=S["smpU"]), bind_u), f"{w}: ksched_pick uniform"
+        assert np.array_equal(ev.pick(feas, PICK_SPREAD, samples=S["smpS"]), bind_p64), f"{w}: ksched_pick spread d=64"
         # per-pair reasons
         n_pairs = 4000
-        pp, pn = rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
+        # `rng` is drawn from HERE ONLY in this function, once per predicate set: restated_matrix, the walk without a device, advances it by
+        # the same call.  A second use of `rng` in check_matrix must be mirrored there, or the CPU walk's bindings and condition (b) counts stop
+        # being this walk's (tests/test_apply_paths_host.py::test_restated_matrix_draws_what_check_matrix_draws pins restated_matrix's side)
+        pp, pn = explain_pairs(rng, P, N, n_pairs)
         got_r = ev.explain(rc, rm, sel, tol, pp, pn, preds)
         want_r = want_reasons(S, cpu, mem, preds, pp.astype(np.int64), pn.astype(np.int64))
         assert np.array_equal(got_r, want_r), f"{w}: ksched_explain ({int((got_r != want_r).sum())} of {n_pairs} pairs differ)"
@@ -242,26 +334,43 @@ def apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, what):
 FORMS = [("real", 0, False), ("random", FPN, True), ("real", REL, True), ("random", 0, False), ("real", FPN, False), ("random", FPN | REL, True)]
 
 
-def case_single(spec):
-    """per node count: the matrix, then rounds of [apply (the previous evaluation's bindings or random ones) -> the matrix]"""
+# the pick whose device bindings an apply of "real" bindings takes: the case's real applies take them in turn.  The turn starts with the
+# spread pick so that it also hands on at 50 000 nodes: with 600 pods there, only an apply of its own bindings moves a column that its
+# next evaluation ranks by (restated: 3 to 13 pods change; after the sampled or the uniform pick's bindings 0 or 1)
+PICKS = ("spread", "sampled", "uniform")
+
+
+def walk_single(spec, begin, matrix, apply):
+    """case_single's sequence with the device behind three callables: begin(S, cpu, mem, what) loads the snapshot; matrix(S, cpu, mem,
+    what, rng, hand_on=, input_condition=) checks every path and -> the bindings of the pick `hand_on` names; apply(S, cpu, mem, b, ok,
+    flags, what) -> (cpu, mem, statuses) after the apply.  Per node count: the matrix, then rounds of [apply (the previous evaluation's
+    bindings or random ones) -> the matrix].
+    Real bindings come from the spread, the sampled and the uniform pick in turn over the case's real applies (the rounds with i + r
+    even): the uniform pick binds more pods and does not favour the lowest feasible nodes, the spread pick's bindings are the ones whose
+    apply moves the columns its own next evaluation ranks by.  Asserted here, so with or without a device: each of the three hands on
+    in both classes of node counts (below 1025, and from 1025 on, where the input conditions hold); and at every node count from 1025
+    on, summed over its applies of real bindings, the d = 5 spread restatement after the apply differs between the columns after and the
+    columns before it for at least one pod (stale_spread_bindings) -- a stale column cannot pass."""
     kind, rounds = spec["kind"], spec.get("rounds", 2)
-    seen = set()
-    ev, ref = Evaluator(0), Evaluator(0)
+    reals = 0
+    handed = {}
     for i, N in enumerate(spec["nodes"]):
         P = spec["pods"] if N <= 5000 else spec["pods_big"]
         S = snapshot(kind, N, P, 0xAB00 + 17 * N + KINDS.index(kind))
         cpu, mem = S["cpu"], S["mem"]
-        set_nodes(ev, S, cpu, mem)
-        if S["indexed"]:
-            assert ev.index_checksum() != (0, 0), f"{kind} N={N}: no index"
-        else:
-            assert ev.index_checksum() == (0, 0), f"{kind} N={N}: the snapshot was indexed"
+        begin(S, cpu, mem, f"{kind} N={N}")
         rng = np.random.default_rng(N)
-        # real bindings come from the sampled pick and, every second time, from the uniform pick: more pods bound, the lowest feasible nodes
-        # not favoured (the rounds that apply real bindings are those with i + r even)
-        hand_on = lambda r: "uniform" if ((i + r) // 2) % 2 else "sampled"  # noqa: E731
-        bind = check_matrix(ev, S, cpu, mem, seen, f"{kind} N={N} before any apply", rng, hand_on=hand_on(0), input_condition=N >= 1025)
-        applied = 0
+
+        def hand_on(r):  # the pick that hands its bindings to round r; None when that round applies random ones (or does not exist)
+            nonlocal reals
+            if r >= rounds or FORMS[(i + r) % len(FORMS)][0] != "real":
+                return None
+            reals += 1
+            handed.setdefault(N >= 1025, []).append(PICKS[(reals - 1) % len(PICKS)])
+            return handed[N >= 1025][-1]
+
+        bind = matrix(S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on(0), input_condition=N >= 1025)
+        applied = stale = 0
         for r in range(rounds):
             src, flags, use_ok = FORMS[(i + r) % len(FORMS)]
             if src == "random":
@@ -269,14 +378,41 @@ def case_single(spec):
             else:  # ok: 0 for a fifth of the pods, any of 1 .. 255 (all of them "landed") for the others
                 b, ok = bind, np.where(rng.random(P) < 0.2, 0, rng.integers(1, 256, P)).astype(np.uint8)
             what = f"{kind} N={N} round {r} ({src} bindings, flags={flags}, ok={use_ok})"
-            cpu, mem, st = apply_and_check(ev, ref, S, cpu, mem, b, ok if use_ok else None, flags, what)
+            cpu0, mem0 = cpu, mem
+            cpu, mem, st = apply(S, cpu, mem, b, ok if use_ok else None, flags, what)
             applied += int((st == _lib.APPLY_APPLIED).sum())
-            bind = check_matrix(ev, S, cpu, mem, seen, what, rng, hand_on=hand_on(r + 1))
+            if src == "real":
+                k = stale_spread_bindings(S, cpu, mem, cpu0, mem0)
+                print(f"{what}: the columns from before this apply would change {k} of {P} spread bindings (d = 5)")
+                stale += k
+            bind = matrix(S, cpu, mem, what, rng, hand_on=hand_on(r + 1))
         assert applied > 0, f"{kind} N={N}: no pod was applied"
-    want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask", "uniform"},
-            "many-keys": {"select", "fused", "bestfit-rows", "from-mask", "uniform"},
-            "list-key": {"select", "bestfit-rows", "from-mask", "uniform"},
-            "unindexed": {"select", "from-mask", "uniform"}}[kind]
+        assert stale > 0 or N < 1025, f"{kind} N={N}: no spread binding depends on what this node count's applies changed"
+    for big, picks in handed.items():  # (a class with fewer real applies than picks cannot see them all: the committed spec has 3 and 5, asserted
+        # by tests/test_apply_paths_host.py on what is returned here)
+        assert len(picks) < len(PICKS) or set(picks) == set(PICKS), f"{kind}: real bindings came from {picks} (node counts from 1025 on: {big})"
+    return handed  # which picks handed on, by class of node count
+
+
+def case_single(spec):
+    """walk_single on one ctx: the matrix is check_matrix, the apply is apply_and_check against a second ctx set afresh"""
+    kind = spec["kind"]
+    seen = set()
+    ev, ref = Evaluator(0), Evaluator(0)
+
+    def begin(S, cpu, mem, what):
+        set_nodes(ev, S, cpu, mem)
+        if S["indexed"]:
+            assert ev.index_checksum() != (0, 0), f"{what}: no index"
+        else:
+            assert ev.index_checksum() == (0, 0), f"{what}: the snapshot was indexed"
+
+    walk_single(spec, begin, lambda S, cpu, mem, what, rng, **kw: check_matrix(ev, S, cpu, mem, seen, what, rng, **kw),
+                lambda S, cpu, mem, b, ok, flags, what: apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, what))
+    want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask", "uniform", "spread"},
+            "many-keys": {"select", "fused", "bestfit-rows", "from-mask", "uniform", "spread"},
+            "list-key": {"select", "bestfit-rows", "from-mask", "uniform", "spread"},
+            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind]
     assert want <= seen, f"{kind}: picks reached {sorted(seen)}, missing {sorted(want - seen)}"
     print(f"{kind}: picks reached {sorted(seen)}")
     ev.close()

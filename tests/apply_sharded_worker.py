@@ -368,42 +368,88 @@ def case_rank(spec):
     dist.destroy_process_group()
 
 
-def case_paths(spec):
-    """after each sharded apply every replica runs the reduced evaluation matrix of tests/apply_paths_worker.py against the oracle on the
-    restated columns: the "select" pick, the riding pick in its waves form, ksched_explain, the direct kernel and (list key) best fit from
-    the key's lists -- the paths that read the node records the gathered commit writes"""
-    from tests.apply_paths_worker import check_matrix, snapshot
+def walk_paths(spec, begin, matrix, apply, end):
+    """case_paths' sequence with the replicas behind callables (tests/apply_paths_worker.walk_single's arrangement; walked without a GPU
+    by tests/test_apply_paths_host.py): begin(S, what) loads every replica; matrix(q, S, cpu, mem, what, rng, hand_on=,
+    input_condition=) runs replica q's reduced matrix and -> the bindings of the pick `hand_on` names; apply(S, cpu, mem, bounds, b, ok,
+    flags, use_ok, what) -> (cpu, mem, statuses) after the sharded apply; end() closes the replicas.
+    Per snapshot round 0 applies real bindings, round 1 random ones.  Which pick hands the real ones on goes by the node count: above
+    5000 nodes the spread pick, from 1025 on the sampled and the uniform pick (one per kind, swapped with the number of ranks), below
+    1025 each of the three in turn over the kinds and n = 1, 2, 3 -- so every pick hands on in both classes of node counts.  At every
+    snapshot from 1025 nodes on, the columns from before the apply of real bindings must change at least one restated spread binding
+    (apply_paths_worker.stale_spread_bindings): a replica left behind by the gathered commit cannot pass.  One exception, stated where it is
+    asserted: a RELEASE of the spread pick's own bindings above 5000 nodes, which counts in its node count's sum only."""
+    from tests.apply_paths_worker import PICKS, snapshot, stale_spread_bindings
     n = spec["n"]
-    seen = set()
     k = 0
-    for kind in ("taints", "list-key"):
+    changed = {}
+    for ki, kind in enumerate(("taints", "list-key")):
         for N in spec["nodes"]:
             P = 1500 if N <= 5000 else 600
             S = snapshot(kind, N, P, 0x5B + N)
-            R = Ranks(n, dict(avail_cpu_milli=S["cpu"], avail_mem_bytes=S["mem"], label_val_ids=S["lab"], taints=S["tnt"]))
+            begin(S, f"n={n} {kind} N={N}")
             cpu, mem = S["cpu"], S["mem"]
             rng = np.random.default_rng(N + n)
-            bind = check_matrix(R.evs[0], S, cpu, mem, seen, f"{kind} N={N} before any apply", rng, reduced=True, hand_on="uniform" if k % 4 else "sampled",
-                                input_condition=N >= 1025)  # (round 0 applies these bindings: every second snapshot the uniform pick's)
+            if N > 5000:  # 600 pods: only an apply of the spread pick's own bindings moves a column its next evaluation ranks by
+                hand_on = "spread"
+            elif N >= 1025:
+                hand_on = ("sampled", "uniform")[(ki + n) % 2]
+            else:
+                hand_on = PICKS[(ki + n) % len(PICKS)]
+            bind = matrix(0, S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on, input_condition=N >= 1025)
             for r in range(2):
                 k += 1
                 flags, use_ok = (0, FPN, REL, FPN | REL)[k % 4], k % 3 != 0
                 b, ok = random_bindings(rng, N, P) if r else (bind, (rng.random(P) > 0.2).astype(np.uint8))
                 bounds = cuts(rng, P, n, "ragged")
                 what = f"n={n} {kind} N={N} round {r} flags={flags} ok={use_ok}"
-                st, want = R.apply(bounds, b, ok, S["rc"], S["rm"], flags, use_ok)
-                got = R.check_equal(what)
-                cpu, mem, exp = restate(cpu, mem, b, S["rc"], S["rm"], ok if use_ok else None, flags)
-                assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem) and np.array_equal(exp, want), f"{what}: exact rule"
-                for q in range(n):
-                    assert np.array_equal(st[q], want[bounds[q]:bounds[q + 1]]), f"{what}: rank {q} status"
+                cpu0, mem0 = cpu, mem
+                cpu, mem, want = apply(S, cpu, mem, bounds, b, ok, flags, use_ok, what)
                 assert (want == _lib.APPLY_APPLIED).any(), f"{what}: nothing applied"
-                for q, e in enumerate(R.evs):
-                    bq = check_matrix(e, S, cpu, mem, seen, f"{what} rank {q}", rng, reduced=True)
-                    if q == 0:
-                        bind = bq
-            R.close()
-    assert {"select", "fused", "bestfit-rows", "uniform"} <= seen, f"picks reached {sorted(seen)}"
+                if r == 0:
+                    stale = stale_spread_bindings(S, cpu, mem, cpu0, mem0)
+                    print(f"{what} ({hand_on} bindings): the columns from before this apply would change {stale} of {P} spread bindings (d = 5)")
+                    changed[N] = changed.get(N, 0) + stale
+                    # per snapshot wherever it can hold.  The one exception: RELEASE of the spread pick's OWN bindings above 5000 nodes gives
+                    # every winner more, so its next evaluation ranks as before -- restated, 0 or 1 of 600 pods change there, and as few with
+                    # 1000 or 1500 pods (a larger P does not help); that snapshot counts only in its node count's sum below
+                    release_of_own = hand_on == "spread" and bool(flags & REL) and N > 5000
+                    assert stale > 0 or N < 1025 or release_of_own, \
+                        f"{what}: no spread binding depends on what this apply of {hand_on} bindings changed (only a RELEASE of the spread pick's own bindings above 5000 nodes may show none)"
+                for q in range(n):
+                    matrix(q, S, cpu, mem, f"{what} rank {q}", rng, hand_on=None)
+            end()
+    # and summed over a node count's rounds (both kinds), which covers the excepted snapshot's node count through the other kind
+    for N, total in changed.items():
+        assert total > 0 or N < 1025, f"n={n} N={N}: no spread binding depends on what this node count's applies of real bindings changed"
+    return k
+
+
+def case_paths(spec):
+    """after each sharded apply every replica runs the reduced evaluation matrix of tests/apply_paths_worker.py against the oracle on the
+    restated columns: the "select" pick, the riding pick in its waves form, ksched_explain, the direct kernel and (list key) best fit from
+    the key's lists -- the paths that read the node records the gathered commit writes -- and the uniform and the spread pick; the spread
+    pick ranks by the columns that commit has just written on every replica (walk_paths)"""
+    from tests.apply_paths_worker import check_matrix
+    n = spec["n"]
+    seen = set()
+    R = [None]
+
+    def begin(S, what):
+        R[0] = Ranks(n, dict(avail_cpu_milli=S["cpu"], avail_mem_bytes=S["mem"], label_val_ids=S["lab"], taints=S["tnt"]))
+
+    def apply(S, cpu, mem, bounds, b, ok, flags, use_ok, what):
+        st, want = R[0].apply(bounds, b, ok, S["rc"], S["rm"], flags, use_ok)
+        got = R[0].check_equal(what)
+        cpu, mem, exp = restate(cpu, mem, b, S["rc"], S["rm"], ok if use_ok else None, flags)
+        assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem) and np.array_equal(exp, want), f"{what}: exact rule"
+        for q in range(n):
+            assert np.array_equal(st[q], want[bounds[q]:bounds[q + 1]]), f"{what}: rank {q} status"
+        return cpu, mem, want
+
+    k = walk_paths(spec, begin, lambda q, S, cpu, mem, what, rng, **kw: check_matrix(R[0].evs[q], S, cpu, mem, seen, what, rng, reduced=True, **kw),
+                   apply, lambda: R[0].close())
+    assert {"select", "fused", "bestfit-rows", "uniform", "spread"} <= seen, f"picks reached {sorted(seen)}"
     print(f"{k} sharded applies, picks reached {sorted(seen)}")
 
 

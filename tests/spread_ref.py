@@ -63,3 +63,16 @@ def best_of(cand: np.ndarray, avail_mem: np.ndarray, avail_cpu: np.ndarray) -> n
 def spread_pick(mask: np.ndarray, draws: np.ndarray, n: int, avail_mem: np.ndarray, avail_cpu: np.ndarray) -> np.ndarray:
     """mask [p, >= ceil(n / 64)] uint64, draws [p, d], the snapshot's [n] int64 columns -> int32 [p]."""
     return best_of(spread_candidates(mask, draws, n), avail_mem, avail_cpu)
+
+
+def spread_pick_blocks(mask: np.ndarray, draws: np.ndarray, n: int, avail_mem: np.ndarray, avail_cpu: np.ndarray, cells: int = 1 << 24) -> np.ndarray:
+    """spread_pick by the listed route in blocks of pods (the counterpart of uniform_ref.uniform_pick_blocks): spread_candidates_listed
+    unpacks a [pods, n] table of bits, so a block is at most `cells` entries of it.  tests/test_spread_restatement.py pins it equal to
+    spread_pick."""
+    draws = np.asarray(draws)
+    p = mask.shape[0]
+    step = max(1, cells // max(int(n), 1))
+    if p <= step:
+        return best_of(spread_candidates_listed(mask, draws, n), avail_mem, avail_cpu)
+    return np.concatenate([best_of(spread_candidates_listed(mask[lo:lo + step], draws[lo:lo + step], n), avail_mem, avail_cpu)
+                           for lo in range(0, p, step)])

@@ -6,6 +6,13 @@ the fused, direct and auto kernels; no pick, the sampled pick in every form (its
 tests "fused-tile", from the mask) and best fit (bitmap rows in one or two stages, the list-key lists, from the mask); ksched_eval and
 ksched_eval_device with and without a mask; ksched_pick from the oracle's host mask; ksched_explain on 4000 random pairs.  Snapshots: up to
 eight keys with taints, ten keys, a list key, and one that indexed_plan refuses (no index: every evaluation reads columns and records).
+The uniform pick runs on every kernel choice, bindings only, through ksched_eval_device and ksched_pick, against tests/uniform_ref.py.
+The spread pick -- the one pick that reads the VALUES of the columns an apply has just written -- runs against tests/spread_ref.py on the
+oracle's mask and the restated columns: d = 5 beside the mask on every kernel choice, d = 2 bindings only (host and device pointers),
+ksched_eval_device beside a mask, ksched_pick with d = 64, d = 1 against the restatement's uniform pick.  Real bindings come from the
+sampled, the uniform and the spread pick in turn.  Two input conditions keep the spread legs from passing vacuously (walk_single; asserted
+without a GPU by tests/test_apply_paths_host.py): before any apply 35 % of the pods or more bind to another node than their candidate 0,
+and at every node count from 1025 on the columns from before an apply of real bindings would change at least one spread binding.
 """
 import json
 import os
@@ -17,6 +24,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODES = [1, 63, 1025, 4097, 50_000]
+SINGLE = {"nodes": NODES, "pods": 2000, "pods_big": 600, "rounds": 3}  # (tests/test_apply_paths_host.py walks the same spec without a GPU)
 
 
 def run(case, spec, timeout=300):
@@ -32,7 +40,8 @@ def run(case, spec, timeout=300):
 def test_every_path_after_an_apply(built, kind):
     """per node count: the matrix, then three rounds of [apply -> the matrix]; the applies rotate over plain, FIRST_PER_NODE, RELEASE and
     both, with and without ok, on the previous evaluation's device bindings and on random ones"""
-    run("single", {"kind": kind, "nodes": NODES, "pods": 2000, "pods_big": 600, "rounds": 3})
+    out = run("single", dict(SINGLE, kind=kind))
+    assert "'spread'" in out.rsplit("picks reached", 1)[-1], "the spread pick is not among the picks reached"
 
 
 def test_snapshot_sizes_and_updates_between_applies_on_one_ctx(built):

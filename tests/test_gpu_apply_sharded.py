@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOOKS = {"KSCHED_TEST_HOOKS": "1", "KSCHED_LIB": os.path.join(ROOT, "tests", "cpp", "hooks", "libksched_hip.so"),
          "KSCHED_RCCL_LIB": os.path.join(ROOT, "tests", "cpp", "libfake_rccl.so")}
 NODES = [1, 1023, 1025, 5000, 50_000]
+PATHS_NODES = [63, 4097, 50_000]  # of the "paths" case (tests/test_apply_paths_host.py walks the same without a GPU)
 
 
 def _cmd(case, spec):
@@ -59,9 +60,11 @@ def test_chain_bestfit_at_c5_shard(built):
 
 @pytest.mark.parametrize("n", [1, 2, 3])
 def test_every_replica_evaluates_right_after_a_sharded_apply(built, n):
-    """the select pick, the waves-form riding pick, ksched_explain, the direct kernel and list-key best fit on every replica, against the
-    oracle; n = 1 over the real RCCL"""
-    run("paths", {"n": n, "nodes": [63, 4097, 50_000]}, hooks=n > 1, timeout=900)
+    """the select pick, the waves-form riding pick, ksched_explain, the direct kernel, list-key best fit, the uniform and the spread pick on
+    every replica, against the oracle (the spread pick: tests/spread_ref.py on the columns the gathered commit must have left on that
+    replica); n = 1 over the real RCCL"""
+    out = run("paths", {"n": n, "nodes": PATHS_NODES}, hooks=n > 1, timeout=900)
+    assert "'spread'" in out.rsplit("picks reached", 1)[-1], "the spread pick is not among the picks reached"
 
 
 def test_shards_longer_than_one_stride_of_the_pod_kernels(built):

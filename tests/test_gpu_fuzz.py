@@ -1,8 +1,11 @@
 """A short run of the randomised differential test (tools/fuzz_parity.py): random shapes, key counts / cardinalities (rows, list
 keys, more than eight keys), taints, predicate subsets, the sampled and best-fit picks, snapshot updates (available, or labels and taints)
 and on-device applies of the previous evaluation's bindings between evaluations, both kernels -- every mask word and binding against the
-oracle; and at every step the uniform pick against tests/uniform_ref.py on the oracle's mask.  (A 240 s run of the same tool:
-profiles/uniform_pick_standing_checks.txt.)"""
+oracle; and at every step the uniform pick against tests/uniform_ref.py on the oracle's mask, and the spread pick (d of 1, 2, 3, 5, 8, 33,
+64; both kernels, with and without the mask) against tests/spread_ref.py on the oracle's mask and on the columns the step's updates and
+applies must have left -- the one pick that goes wrong, for a few pods, when a column is stale.  With the hooks the spread pick also goes
+through the multi-device sequence, a sharded apply of its gathered bindings and the sequence again on the replicas' columns.  (240 s runs of
+the same tool: profiles/uniform_pick_standing_checks.txt, profiles/spread_pick_standing_checks.txt.)"""
 import os
 import re
 import subprocess
@@ -32,6 +35,8 @@ def test_fuzz_parity_short(built):
     assert "0 failures" in r.stdout
     assert "'apply': " in r.stdout, "no case applied an evaluation's bindings on the device"
     assert_new_tallies(r.stdout)
+    assert tally(r.stdout, "spread") > 0, "no evaluation ran the spread pick"
+    assert tally(r.stdout, "spread-ranked") > 0, "no spread pick bound a pod to another node than its candidate 0"
 
 
 def test_fuzz_parity_short_with_the_multi_device_sequence(built):
@@ -50,3 +55,4 @@ def test_fuzz_parity_short_with_the_multi_device_sequence(built):
     assert_new_tallies(r.stdout)
     assert re.search(r"'gathered-over-\d': [1-9]", r.stdout), "no sampled or best-fit case went through the multi-device sequence"
     assert re.search(r"'uniform-gathered-over-\d': [1-9]", r.stdout), "no uniform pick went through the multi-device sequence"
+    assert re.search(r"'spread-gathered-over-\d': [1-9]", r.stdout), "no spread pick went through the multi-device sequence"

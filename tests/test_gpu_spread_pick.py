@@ -11,6 +11,7 @@ import pytest
 from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM, SEL, TAINT, KschedError, _lib, synth,
                                              unpack_mask)
 from oracle import capi
+from oracle.oracle_ref import apply_bindings_exact
 from tests.spread_ref import best_of, spread_candidates, spread_candidates_listed, spread_pick
 from tests.test_gpu_uniform_pick import dev_of, mask_np, oracle_mask, pitched_mask, pod_tensors, to_dev
 from tests.uniform_ref import uniform_pick
@@ -476,6 +477,126 @@ def test_a_sampled_submit_does_not_overwrite_the_mask_its_slots_spread_pick_stil
         assert np.array_equal(mask_np(mask), b[2]) and np.array_equal(out.cpu().numpy(), b[3])
     finally:
         pipe.close()
+
+
+def changing_snapshot(change):
+    """The two snapshots of the TWO_PASS cluster between which test_pipe_submits_around_a_snapshot_change goes back and forth, with what
+    the pipe must give on each: -> (predicate flags, [old, new]) where each state is dict(cpu, mem, feas, want) -- the columns, the oracle's
+    mask on them and the d = 5 restatement on that mask and those columns -- and `new` also carries how to get there.  change:
+      "negated"   ksched_update_nodes, section 5's update: both columns negated on every node some pod drew; the fit term off (a negative
+                  column fits no pod), so the mask stays and only the ranking turns over
+      "permuted"  ksched_update_nodes: the (cpu, mem) pairs of the drawn nodes permuted among them; the fit term on, so the mask moves too
+      "apply"     ksched_apply_bindings_device of the old snapshot's own spread bindings (back: the same bindings with APPLY_RELEASE)
+    Computed once per change and shared."""
+    k = case(TWO_PASS)
+    if ("changing", change) not in k:
+        c, d = k["c"], 5
+        flags = k["flags"] & ~FIT if change == "negated" else k["flags"]
+        draws = table(k, d)
+
+        def state(cpu, mem):
+            feas = oracle_mask(c, flags, cpu, mem)
+            cand = spread_candidates_listed(feas, draws, c.N)
+            return dict(cpu=cpu, mem=mem, feas=feas, cand=cand, want=best_of(cand, mem, cpu))
+
+        old = state(c.avail_cpu.copy(), c.avail_mem.copy())
+        cpu, mem = old["cpu"].copy(), old["mem"].copy()
+        idx = np.unique(old["cand"][old["cand"] >= 0]).astype(np.uint32)
+        if change == "negated":
+            cpu[idx], mem[idx] = -cpu[idx], -mem[idx]
+        elif change == "permuted":
+            src = idx[np.random.default_rng(0x9E12).permutation(idx.size)]
+            cpu[idx], mem[idx] = old["cpu"][src], old["mem"][src]
+        else:
+            cpu, mem, st = apply_bindings_exact(cpu, mem, old["want"], c.req_cpu, c.req_mem, None, 0)
+            assert (st == _lib.APPLY_APPLIED).sum() == (old["want"] >= 0).sum() > 0
+            back = apply_bindings_exact(cpu, mem, old["want"], c.req_cpu, c.req_mem, None, _lib.APPLY_RELEASE)
+            assert np.array_equal(back[0], old["cpu"]) and np.array_equal(back[1], old["mem"])
+        new = dict(state(cpu, mem), idx=idx)
+        k[("changing", change)] = (flags, [old, new])
+    return k[("changing", change)]
+
+
+def assert_old_and_new_can_be_told_apart(change):
+    """the input condition of test_pipe_submits_around_a_snapshot_change (no device; tests/test_apply_paths_host.py asserts it too): an update
+    changes a quarter or more of the restated bindings.  An apply is what slot 0's own bindings make it: 900 pods' requests taken from 8200
+    nodes change only the pods whose candidates include a node another pod was bound to.  Restated: 13.0 % of the bindings differ between
+    the two snapshots (the mask moves with the fit term), and on the new mask the old columns change 15 of 900 -- thin discrimination, so a
+    floor of 10 is asserted: the case cannot shrink to a single pod unnoticed"""
+    flags, (old, new) = changing_snapshot(change)
+    moved = float((old["want"] != new["want"]).mean())
+    stale = int((best_of(new["cand"], old["mem"], old["cpu"]) != new["want"]).sum())  # on the new mask: the old columns against the new
+    print(f"{change}: {100 * moved:.1f} % of the restated bindings differ between the two snapshots; on the new mask the old columns change {stale}")
+    if change == "apply":
+        assert moved >= 0.10 and stale >= 10
+    else:
+        assert moved >= 0.25 and stale >= 0.25 * old["want"].size
+    assert (change == "negated") == np.array_equal(old["feas"], new["feas"])
+
+
+@pytest.mark.parametrize("change", ["negated", "permuted", "apply"])
+@pytest.mark.parametrize("mode", [0, 2, 3])
+def test_pipe_submits_around_a_snapshot_change(ev, mode, change):
+    """Two submits of the same pods and draws (900 x 8200, d = 5: a two-pass row) into slots 0 and 1 with a snapshot change enqueued between
+    them and no host wait anywhere: slot 0's mask and bindings are the oracle's and the restatement's on the OLD snapshot, slot 1's those on
+    the NEW one.  The slot's pick stream is kept busy for some milliseconds first, so the change is enqueued while slot 0's pick has not
+    run.  The change: ksched_update_nodes, or ksched_apply_bindings_device of slot 0's own bindings on a stream ordered behind slot 0 with
+    pipe.wait(0, stream=...).  A second round on the same slots takes the change back (the update with the old values; the same bindings
+    with APPLY_RELEASE): slot 0 is reused on the new snapshot, slot 1 on the old one again."""
+    import torch
+    k = case(TWO_PASS)
+    c, d = k["c"], 5
+    assert_old_and_new_can_be_told_apart(change)
+    flags, states = changing_snapshot(change)
+    idx = states[1]["idx"]
+    ev.set_nodes(**c.node_columns())
+    cpu_t, mem_t, sel, tol = pod_tensors(ev, c)
+    smp = to_dev(ev, table(k, d), np.int32)
+    ev.set_option(_lib.OPT_PIPE_MODE, mode)
+    pipe = ev.pipe(2)
+    side = torch.cuda.Stream(device=dev_of(ev))
+    try:
+        masks = [ev.alloc_mask(c.P, pitched=True) for _ in range(2)]
+        outs = [fresh(ev, c.P) for _ in range(2)]
+        applied = fresh(ev, c.P)  # the bindings the apply took, kept for the release
+        torch.cuda.synchronize()
+        for rnd in range(2):
+            before, after = states[rnd % 2], states[(rnd + 1) % 2]
+            busy = pipe.slot_stream(0) or pipe.stream(1)  # (before its first submit a slot has no stream yet: the pick stream)
+            with torch.cuda.stream(busy):
+                torch.cuda._sleep(10_000_000)
+            pipe.submit(0, cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, masks[0], outs[0])
+            # the spread pick reads the mask, so in every pipe mode its slot takes the split route and its pick the pick stream: the stream
+            # that was put to sleep is the one that carries slot 0's pick, in round 0 too
+            assert pipe.slot_stream_handle(0) == busy.cuda_stream, f"mode {mode}, {change}, round {rnd}: slot 0's pick is not on the stream that was kept busy"
+            if change == "apply":
+                pipe.wait(0, stream=side)
+                if rnd == 0:
+                    with torch.cuda.stream(side):
+                        applied.copy_(outs[0])
+                ev.apply_bindings_device(outs[0] if rnd == 0 else applied, cpu_t, mem_t, None, _lib.APPLY_RELEASE if rnd else 0, stream=side)
+            else:
+                ev.update_nodes(idx, after["cpu"][idx], after["mem"][idx])
+            pipe.submit(1, cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, masks[1], outs[1])
+            for slot in range(2):
+                pipe.wait(slot, host=True)
+                pipe.wait_mask(slot, host=True)
+            torch.cuda.synchronize()
+            what = f"mode {mode}, {change}, round {rnd}"
+            assert np.array_equal(mask_np(masks[0]), before["feas"]), f"{what}: slot 0's mask is not the one of the snapshot before the change"
+            got0, got1 = outs[0].cpu().numpy(), outs[1].cpu().numpy()
+            assert np.array_equal(got0, before["want"]), \
+                f"{what}: slot 0, enqueued before the change ({int((got0 != before['want']).sum())} bindings differ, {int((got0 == after['want']).sum())} of {c.P} are the new snapshot's)"
+            assert np.array_equal(mask_np(masks[1]), after["feas"]), f"{what}: slot 1's mask is not the one of the snapshot after the change"
+            assert np.array_equal(got1, after["want"]), \
+                f"{what}: slot 1, enqueued after the change ({int((got1 != after['want']).sum())} bindings differ, {int((got1 == before['want']).sum())} of {c.P} are the old snapshot's)"
+            got_cpu, got_mem = ev.read_nodes()
+            assert np.array_equal(got_cpu, after["cpu"]) and np.array_equal(got_mem, after["mem"]), f"{what}: the columns"
+    finally:
+        torch.cuda.synchronize()
+        pipe.close()
+        ev.forget_stream(side)
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
 
 
 # ---- 7. seeded differential loop ---------------------------------------------------------------------------------------------

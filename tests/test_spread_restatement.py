@@ -2,7 +2,7 @@
 hand-written cases and by an independent per-pod loop in Python integers.  No GPU, no library."""
 import numpy as np
 
-from tests.spread_ref import best_of, spread_candidates, spread_candidates_listed, spread_pick
+from tests.spread_ref import best_of, spread_candidates, spread_candidates_listed, spread_pick, spread_pick_blocks
 from tests.uniform_ref import uniform_pick
 
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
@@ -125,3 +125,28 @@ def test_the_listed_route_to_the_candidates_equals_uniform_pick_per_column():
             assert np.array_equal(best_of(want, mem, cpu), spread_pick(m, u, n, mem, cpu))
     assert spread_candidates_listed(np.zeros((2, 0), np.uint64), np.ones((2, 3), np.uint32), 0).tolist() == [[-1] * 3] * 2
     assert spread_candidates_listed(np.zeros((0, 2), np.uint64), np.zeros((0, 2), np.uint32), 100).shape == (0, 2)
+
+
+def test_blocks_of_pods_equal_the_whole():
+    """spread_pick_blocks (the listed route, a block of pods at a time) == spread_pick: block lengths of 1, 7 and 8 pods over 50 (a last
+    block of one pod, of one row short, every block full but the last), one block for all, a block longer than the batch; an empty row
+    first in its block, last in its block and in the middle; d = 1, 5 and 64; columns with ties"""
+    rng = np.random.default_rng(0xB10C)
+    for n in (1, 130, 250, 8200):
+        W = (n + 63) // 64
+        p = 50
+        bits = rng.random((p, (W + 1) * 64)) < 0.3  # (one padding word, set at the same density)
+        for empty in (0, 6, 7, 20, 49):
+            bits[empty] = False
+        m = np.packbits(bits, axis=1, bitorder="little").view(np.uint64)
+        mem, cpu = rng.integers(-3, 3, n), rng.integers(-3, 3, n)
+        for d in (1, 5, 64):
+            u = rng.integers(0, 1 << 32, size=(p, d), dtype=np.uint64).astype(np.uint32)
+            want = spread_pick(m, u, n, mem, cpu)
+            assert (want[[0, 6, 7, 20, 49]] == -1).all() and (n < 130 or (want >= 0).sum() == p - 5)
+            for pods_per_block in (1, 7, 8, 49, 50, 51):
+                got = spread_pick_blocks(m, u, n, mem, cpu, cells=n * pods_per_block)
+                assert got.dtype == np.int32 and np.array_equal(got, want), (n, d, pods_per_block)
+            assert np.array_equal(spread_pick_blocks(m, u, n, mem, cpu), want), (n, d)
+    z = np.zeros(100, np.int64)
+    assert spread_pick_blocks(np.zeros((0, 2), np.uint64), np.zeros((0, 3), np.uint32), 100, z, z).shape == (0,)

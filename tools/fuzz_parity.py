@@ -7,17 +7,27 @@ the uniform pick (KSCHED_PICK_UNIFORM) at every step of every case -- both kerne
 WANT_FIT_MASK, full-range 32-bit draws with an occasional all-zero or all-ones column -- against tests/uniform_ref.py on the oracle's mask,
 and through ksched_pick (the oracle's mask and a thinned one), the row shards and the multi-device sequence below; about one case in ten
 has 8192, 8193 or 12 500 nodes (rows of more than 128 words: the two-pass form of k_pick_uniform),
+the spread pick (KSCHED_PICK_SPREAD) at every step of every case as well -- d drawn from 1, 2, 3, 5, 8, 33, 64, both kernels, with and without the
+mask -- against tests/spread_ref.py on the oracle's mask AND on the step's restated columns: it is the one pick that reads the values an update or an
+apply has just written, so a column left stale shows as a few wrong bindings; through ksched_pick, the row shards and the multi-device sequence too,
+the latter followed by a sharded apply of the gathered bindings over the same replicas and a second sequence on the columns that apply left (no
+ksched_set_nodes in between); the wide cases take k_pick_spread's two-pass form, with draws that arrive out of chunk order,
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
 ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts),
 the two halves of ksched_eval over 1 .. 5 row shards (ksched_shard_bounds / ksched_eval_begin / ksched_eval_end) and -- with the test hooks on
 (KSCHED_TEST_HOOKS=1 KSCHED_RCCL_LIB=tests/cpp/libfake_rccl.so) -- the whole multi-device sequence over 2 .. 4 evaluators on the one GPU:
 ksched_comm_create_local, ksched_eval_begin on every replica, ksched_gather_buffer, ksched_allgather_bindings_local, ksched_eval_end(gathered_0).
-A case's decisions come from two generators seeded from the case seed: `r` draws what the tool has always drawn, in the same order (a
-case that keeps its node count is the case an older log names by that seed), `r2` every decision added since (the uniform legs, the wider
-snapshots, the label updates).
+A case's decisions come from three generators seeded from the case seed: `r` draws what the tool has always drawn, in the same order (a
+case that keeps its node count is the case an older log names by that seed), `r2` every decision added with the uniform pick (the uniform legs,
+the wider snapshots, the label updates), in its order, and `r3` every decision added since (the spread legs): a seed names the case it named
+before the spread legs, with those legs added.
 The summary's tallies: pick launches by name ('uniform': evaluations whose last_pick was "uniform"; 'uniform-ranked': those in which some
 pod had two or more feasible nodes, so the rank arithmetic ran), 'labels' (label updates), 'apply', 'host-masks', 'sharded-halves',
-'gathered-over-n' (and their 'uniform-' twins), 'summarize'.
+'gathered-over-n' (and their 'uniform-' and 'spread-' twins), 'summarize'; 'spread': evaluations whose last_pick was "spread" (one per
+ksched_eval; a multi-device sequence counts as one, whatever the number of replicas, as it does for 'uniform');
+'spread-ranked': those in which some pod was bound to another node than its candidate 0; 'spread-tied': those in which some pod's winner was
+decided by cpu or by the node index (two distinct candidates with the same, largest memory); 'spread-gathered-moved': second sequences in which
+the columns from before the gathered apply would have given some pod another binding.
 usage: python tools/fuzz_parity.py [seconds] [seed]       prints one line per failure and a summary; exit code 1 on any failure"""
 import os, sys, time
 import numpy as np
@@ -29,6 +39,7 @@ from oracle import capi
 from tests.test_gpu_apply_bindings import restate as apply_bindings_exact
 from tests.test_gpu_node_labels import apply_rows  # the columns after ksched_update_node_labels: a node listed twice takes its last row
 from tests.uniform_ref import uniform_pick  # KSCHED_PICK_UNIFORM restated
+from tests.spread_ref import best_of, spread_candidates_listed  # KSCHED_PICK_SPREAD restated: every draw's candidate, the best of them
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -50,6 +61,24 @@ def uniform_pick_blocks(mask, draws, n, cells=1 << 24):
     return np.concatenate([uniform_pick(mask[lo:lo + step], draws[lo:lo + step], n) for lo in range(0, mask.shape[0], step)])
 
 
+def spread_restated(mask, draws, n, mem, cpu, cells=1 << 24):
+    """tests/spread_ref.py in blocks of pods (spread_pick_blocks, keeping the candidates for the tallies) -> (the bindings, whether some pod
+    is bound to another node than its candidate 0, whether some pod's largest memory is shared by two distinct candidates)"""
+    step = max(1, cells // max(int(n), 1))
+    out, ranked, tied = [], False, False
+    for lo in range(0, mask.shape[0], step):
+        cand = spread_candidates_listed(mask[lo:lo + step], draws[lo:lo + step], n)
+        b = best_of(cand, mem, cpu)
+        out.append(b)
+        ranked = ranked or bool(((b >= 0) & (b != cand[:, 0])).any())
+        v = cand[cand[:, 0] >= 0].astype(np.int64)
+        if v.size and not tied:
+            m = mem[v]
+            top = m == m.max(axis=1, keepdims=True)
+            tied = bool((np.where(top, v, n).min(axis=1) != np.where(top, v, -1).max(axis=1)).any())
+    return np.concatenate(out), ranked, tied
+
+
 def clique(n_sh):
     """the first n_sh replicas and their comms (ksched_comm_create_local), made on first use"""
     import ctypes as C
@@ -64,6 +93,29 @@ def clique(n_sh):
             raise L.KschedError(rcode, "ksched_comm_create_local", ev._lib.ksched_comm_last_error().decode())
         cliques[n_sh] = comms
     return reps, cliques[n_sh]
+
+
+def sharded_apply(reps, comms, cut, bt, rct, rmt, okt, af, wait=True):
+    """ksched_apply_bindings_sharded_local over `reps`: replica q applies rows [cut[q], cut[q + 1]) of the device tensors.  -> the
+    statuses of all rows after a host wait; with wait=False the status tensors at once, the applies still in flight"""
+    import ctypes as C
+    import torch
+    n_sh = len(reps)
+    sts = [torch.full((cut[q + 1] - cut[q],), -7, dtype=torch.int32, device=bt.device) for q in range(n_sh)]
+    ptrs = lambda xs: (C.c_void_p * n_sh)(*xs)  # noqa: E731
+    part = lambda x, q, w: None if x is None or cut[q + 1] == cut[q] else x.data_ptr() + w * cut[q]  # noqa: E731
+    rcode = ev._lib.ksched_apply_bindings_sharded_local(
+        C.cast(ptrs([e._h for e in reps]), C.c_void_p), C.cast(comms, C.c_void_p), n_sh,
+        C.cast((C.c_uint32 * n_sh)(*[cut[q + 1] - cut[q] for q in range(n_sh)]), C.c_void_p), C.cast((C.c_uint32 * n_sh)(*cut[:n_sh]), C.c_void_p),
+        C.cast(ptrs([part(bt, q, 4) for q in range(n_sh)]), C.c_void_p), C.cast(ptrs([part(rct, q, 8) for q in range(n_sh)]), C.c_void_p),
+        C.cast(ptrs([part(rmt, q, 8) for q in range(n_sh)]), C.c_void_p), C.cast(ptrs([part(okt, q, 1) for q in range(n_sh)]), C.c_void_p) if okt is not None else None,
+        af, C.cast(ptrs([s_.data_ptr() if s_.numel() else None for s_ in sts]), C.c_void_p), None)
+    if rcode != 0:
+        raise L.KschedError(rcode, "ksched_apply_bindings_sharded_local", ev._lib.ksched_comm_last_error().decode())
+    if not wait:
+        return sts
+    torch.cuda.synchronize()
+    return np.concatenate([s_.cpu().numpy() for s_ in sts])
 
 
 def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm, relabelled=False):
@@ -86,19 +138,7 @@ def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm, relabelled=False)
         for e in reps:
             e.set_nodes(cpu, mem, lab, taints)
         cut = [0] + sorted(int(x) for x in r.integers(0, P + 1, n_sh - 1)) + [P]
-        sts = [torch.full((cut[q + 1] - cut[q],), -7, dtype=torch.int32, device=dev) for q in range(n_sh)]
-        ptrs = lambda xs: (C.c_void_p * n_sh)(*xs)  # noqa: E731
-        part = lambda x, q, w: None if x is None or cut[q + 1] == cut[q] else x.data_ptr() + w * cut[q]  # noqa: E731
-        rcode = ev._lib.ksched_apply_bindings_sharded_local(
-            C.cast(ptrs([e._h for e in reps]), C.c_void_p), C.cast(comms, C.c_void_p), n_sh,
-            C.cast((C.c_uint32 * n_sh)(*[cut[q + 1] - cut[q] for q in range(n_sh)]), C.c_void_p), C.cast((C.c_uint32 * n_sh)(*cut[:n_sh]), C.c_void_p),
-            C.cast(ptrs([part(bt, q, 4) for q in range(n_sh)]), C.c_void_p), C.cast(ptrs([part(rct, q, 8) for q in range(n_sh)]), C.c_void_p),
-            C.cast(ptrs([part(rmt, q, 8) for q in range(n_sh)]), C.c_void_p), C.cast(ptrs([part(okt, q, 1) for q in range(n_sh)]), C.c_void_p) if okt is not None else None,
-            af, C.cast(ptrs([s_.data_ptr() if s_.numel() else None for s_ in sts]), C.c_void_p), None)
-        if rcode != 0:
-            raise L.KschedError(rcode, "ksched_apply_bindings_sharded_local", ev._lib.ksched_comm_last_error().decode())
-        torch.cuda.synchronize()
-        st_sh = np.concatenate([s_.cpu().numpy() for s_ in sts])
+        st_sh = sharded_apply(reps, comms, cut, bt, rct, rmt, okt, af)
         cols = [e.read_nodes() for e in reps]
         if not (np.array_equal(st_sh, want_st) and all(np.array_equal(c_[0], ncpu) and np.array_equal(c_[1], nmem) for c_ in cols)):
             bad += 1
@@ -169,22 +209,24 @@ def shard_halves(g, cs, tag, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, a
             print(f"FAIL {tag}shard padding case seed {cs}: P={P} shards={n_sh} rank={rank}", flush=True)
     if not (np.array_equal(feas_s, want[0]) and (not (flags & L.WANT_FIT_MASK) or np.array_equal(fit_s, want[1])) and np.array_equal(bind_s, want[2])):
         bad += 1
-        print(f"FAIL {tag}sharded halves case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} shards={n_sh}", flush=True)
+        print(f"FAIL {tag}sharded halves case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} attempts={attempts} shards={n_sh}", flush=True)
     picks[tag + "sharded-halves"] = picks.get(tag + "sharded-halves", 0) + 1
     return bad
 
 
-def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, attempts, want):
+def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, attempts, want, n_sh=None):
     """the whole multi-device sequence over 2 .. 4 replicas on the one GPU (test hooks): ksched_eval_begin on every replica,
     ksched_gather_buffer, ksched_allgather_bindings_local, ksched_eval_end(gathered_0).  `g` draws the replica count and the replicas'
-    options.  -> (the number of failures, the last_pick names of the replicas whose shard held a pod)"""
+    options.  With n_sh given, that many replicas evaluate on the snapshots they hold (nothing is drawn, nothing set: the columns are what
+    the calls before left on each).  -> (the number of failures, the last_pick names of the replicas whose shard held a pod)"""
     bad = 0
     ran = []
     import ctypes as C
-    n_sh = int(g.choice([2, 3, 4]))
+    keep = n_sh is not None
+    n_sh = n_sh if keep else int(g.choice([2, 3, 4]))
     reps, comms = clique(n_sh)
     lib = ev._lib
-    for e in reps:  # the snapshot is replicated (the current values: the updates above are in cpu / mem)
+    for e in ([] if keep else reps):  # the snapshot is replicated (the current values: the updates above are in cpu / mem)
         e.set_option(L.OPT_BESTFIT_STAGES, int(g.choice([0, 1, 2])))
         e.set_nodes(cpu, mem, lab, taints)
     W = ev.W
@@ -234,9 +276,49 @@ def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, fla
         pad_ok = pad_ok and bool((table[rank * cpr + hi_.value - lo_.value: (rank + 1) * cpr] == -1).all())
     if not (pad_ok and np.array_equal(feas_s, want[0]) and (not (flags & L.WANT_FIT_MASK) or np.array_equal(fit_s, want[1])) and np.array_equal(bind_s, want[2])):
         bad += 1
-        print(f"FAIL {tag}multi-device sequence case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} replicas={n_sh}", flush=True)
+        print(f"FAIL {tag}multi-device sequence case seed {cs}: N={N} P={P} K={K} nt={nt} flags={flags:#x} attempts={attempts} replicas={n_sh}{' (on the snapshots the replicas held)' if keep else ''}", flush=True)
     picks[f"{tag}gathered-over-{n_sh}"] = picks.get(f"{tag}gathered-over-{n_sh}", 0) + 1
     return bad, {e.last_pick for e in ran}
+
+
+def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, ranked, tied):
+    """the multi-device sequence with the spread pick, twice: on freshly set replicas; then -- after ksched_apply_bindings_sharded_local of
+    the gathered bindings over the same replicas, ragged cuts, no ksched_set_nodes -- on the columns that apply left on every replica: the
+    oracle's mask and the restatement on the exact-integer apply of those bindings.  A replica whose columns the gathered commit left behind
+    ranks its rows by old values.  Every replica's pick must run as "spread".  `ev`, cpu and mem are not touched.  -> the number of failures"""
+    import torch
+    n_sh = int(g.choice([2, 3, 4]))
+    for e in clique(n_sh)[0]:
+        e.set_nodes(cpu, mem, lab, taints)
+    bad, names = gathered_sequence(g, cs, "spread-", cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, n_sh=n_sh)
+    tally = [(names, ranked, tied)]
+    af = int(g.choice([0, L.APPLY_FIRST_PER_NODE])) | (L.APPLY_RELEASE if g.random() < 0.2 else 0)
+    ncpu, nmem, want_st = apply_bindings_exact(cpu, mem, want[2], rc, rm, None, af)
+    reps, comms = clique(n_sh)
+    dev = torch.device("cuda:0")
+    bt, rct, rmt = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (want[2], rc, rm))
+    cut = [0] + sorted(int(x) for x in g.integers(0, P + 1, n_sh - 1)) + [P]
+    sts = sharded_apply(reps, comms, cut, bt, rct, rmt, None, af, wait=False)  # no host wait before the replicas evaluate again
+    picks[f"spread-gathered-apply-over-{n_sh}"] = picks.get(f"spread-gathered-apply-over-{n_sh}", 0) + 1
+    want2 = capi.eval_encoded(ncpu, nmem, lab, taints if (preds & L.TAINT) else None, rc, rm, sel, tol if (preds & L.TAINT) else None, None, flags & ~L.PICK_SPREAD)
+    b2, ranked2, tied2 = spread_restated(want2[0], smp, N, nmem, ncpu)
+    bad2, names2 = gathered_sequence(g, cs, "spread-", ncpu, nmem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, (want2[0], want2[1], b2), n_sh=n_sh)
+    tally.append((names2, ranked2, tied2))
+    torch.cuda.synchronize()
+    if not np.array_equal(np.concatenate([s_.cpu().numpy() for s_ in sts]), want_st):
+        bad += 1
+        print(f"FAIL spread gathered apply case seed {cs}: N={N} P={P} flags={af} cuts={cut}: statuses", flush=True)
+    if not np.array_equal(b2, spread_restated(want2[0], smp, N, mem, cpu)[0]):  # (the old columns would show)
+        picks["spread-gathered-moved"] = picks.get("spread-gathered-moved", 0) + 1
+    for nm, rk, td in tally:
+        if nm == {"spread"}:
+            picks["spread"] = picks.get("spread", 0) + len(nm)
+            picks["spread-ranked"] = picks.get("spread-ranked", 0) + int(rk) * len(nm)
+            picks["spread-tied"] = picks.get("spread-tied", 0) + int(td) * len(nm)
+        else:
+            bad += 1
+            print(f"FAIL spread multi-device sequence case seed {cs}: N={N} P={P} d={d}: the replicas' picks ran as {sorted(nm)}", flush=True)
+    return bad + bad2
 
 
 t_end = time.time() + budget
@@ -248,6 +330,7 @@ while time.time() < t_end:
     cs = int(rng.integers(0, 1 << 31))
     r = np.random.default_rng(cs)
     r2 = np.random.default_rng([cs, 0x0E3])  # every decision added after the sequence of `r` was fixed (see the docstring)
+    r3 = np.random.default_rng([cs, 0x5E4])  # every decision added after the sequence of `r2` was fixed: the spread legs
     wide = int(r2.choice([8192, 8193, 12_500])) if r2.random() < 0.1 else 0  # rows of more than 128 words: k_pick_uniform's two-pass form (8192: the longest one-pass row)
     N = int(r.choice([1, 2, 63, 64, 65, 300, 1023, 1024, 1025, 2500, 4097, 6000]))
     P = int(r.choice([1, 7, 64, 65, 500, 1500, 3000]))
@@ -290,6 +373,10 @@ while time.time() < t_end:
         smp_u[:, int(r2.integers(0, att_u))] = 0 if r2.random() < 0.5 else 0xFFFFFFFF
     if r2.random() < 0.1:
         smp_u[:, 0] = 0 if r2.random() < 0.5 else 0xFFFFFFFF
+    # the spread pick's draws: full-range 32-bit, 64 columns of which a step reads the first d; now and then a column all zero or all ones
+    smp_s64 = r3.integers(0, 1 << 32, (P, 64), dtype=np.uint64).astype(np.uint32)
+    if r3.random() < 0.15:
+        smp_s64[:, int(r3.integers(0, 8))] = 0 if r3.random() < 0.5 else 0xFFFFFFFF
     try:
         ev.set_option(L.OPT_BESTFIT_STAGES, int(r.choice([0, 1, 2])))
         ev.set_option(L.OPT_GRID_CUS, int(r.choice([0, 0, 0, 8, 17, 96, 200])))  # fewer compute units per launch: same results
@@ -377,8 +464,44 @@ while time.time() < t_end:
                     else:  # a KSCHED_PICK_UNIFORM request has one launch form
                         fails += 1
                         print(f"FAIL uniform case seed {cs}: N={N} P={P} K={K} flags={fl_u:#x} kernel={kernel} mask={want_mask} step={step}: the pick ran as {ev.last_pick!r}", flush=True)
+            # the spread pick on the same snapshot, d drawn anew at every step: both kernels, with and without the mask -- against the
+            # restatement on the oracle's mask and on cpu / mem as the updates and applies above left them
+            d_s = int(r3.choice([1, 2, 3, 5, 8, 33, 64]))
+            smp_s = np.ascontiguousarray(smp_s64[:, :d_s])
+            want_s, ranked_s, tied_s = spread_restated(want[0], smp_s, N, mem, cpu)
+            fl_s = preds | L.PICK_SPREAD | (L.WANT_FIT_MASK if (flags & L.WANT_FIT_MASK) and r3.random() < 0.5 else 0)
+            for kernel in ("auto", "direct"):
+                ev.set_kernel(kernel)
+                for want_mask in (True, False):
+                    fl = fl_s if want_mask else fl_s & ~L.WANT_FIT_MASK
+                    got = ev.eval(rc, rm, sel if K else None, tol if (preds & L.TAINT) else None, smp_s, fl, want_mask=want_mask)
+                    ok = (not want_mask or np.array_equal(got.feasible, want[0])) and np.array_equal(got.binding, want_s) and \
+                        (not (fl & L.WANT_FIT_MASK) or np.array_equal(got.fit, want[1]))
+                    if not ok:
+                        fails += 1
+                        print(f"FAIL spread case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} flags={fl_s:#x} d={d_s} kernel={kernel}/{ev.last_kernel} pick={ev.last_pick} mask={want_mask} step={step}"
+                              f" ({int((got.binding != want_s).sum())} bindings differ)", flush=True)
+                    if ev.last_pick == "spread":
+                        picks["spread"] = picks.get("spread", 0) + 1
+                        picks["spread-ranked"] = picks.get("spread-ranked", 0) + int(ranked_s)
+                        picks["spread-tied"] = picks.get("spread-tied", 0) + int(tied_s)
+                    else:  # a KSCHED_PICK_SPREAD request has one launch form
+                        fails += 1
+                        print(f"FAIL spread case seed {cs}: N={N} P={P} K={K} flags={fl_s:#x} d={d_s} kernel={kernel} mask={want_mask} step={step}: the pick ran as {ev.last_pick!r}", flush=True)
         ev.set_kernel("auto")
         want3_u = (want[0], want[1], want_u)
+        want3_s = (want[0], want[1], want_s)
+        if r3.random() < 0.4:  # ksched_pick with the spread pick: the oracle's mask, and that mask thinned by random words -- the restatement on either, on the current columns
+            thin_s = want[0] & r3.integers(0, 1 << 63, want[0].shape, dtype=np.uint64)
+            if not (np.array_equal(ev.pick(want[0], L.PICK_SPREAD, samples=smp_s), want_s) and
+                    np.array_equal(ev.pick(thin_s, L.PICK_SPREAD, samples=smp_s), spread_restated(thin_s, smp_s, N, mem, cpu)[0])):
+                fails += 1
+                print(f"FAIL spread ksched_pick case seed {cs}: N={N} P={P} K={K} nt={nt} preds={preds:#x} d={d_s} step={step}", flush=True)
+            picks["spread-host-masks"] = picks.get("spread-host-masks", 0) + 1
+        if r3.random() < 0.35:
+            fails += shard_halves(r3, cs, "spread-", N, P, K, nt, preds, fl_s, rc, rm, sel, tol, smp_s, d_s, want3_s)
+        if HOOKS and r3.random() < 0.35:
+            fails += spread_gathered(r3, cs, cpu, mem, lab, taints, N, P, K, nt, preds, fl_s, rc, rm, sel, tol, smp_s, d_s, want3_s, ranked_s, tied_s)
         if r2.random() < 0.4:  # ksched_pick with the uniform pick: the oracle's mask, and that mask thinned by random words -- the restatement on either
             thin_u = want[0] & r2.integers(0, 1 << 63, want[0].shape, dtype=np.uint64)
             if not (np.array_equal(ev.pick(want[0], L.PICK_UNIFORM, samples=smp_u), want_u) and
