@@ -192,8 +192,9 @@ extern "C" {
  * stream.  m >= 1 = alternate: the WHOLE evaluation of a slot -- one launch when the pick rides in the mask kernel -- goes onto
  * stream (slot mod k), k = max(2, m) <= KSCHED_PIPE_MAX_STREAMS: consecutive batches overlap (the next launch's blocks fill while
  * the previous one's blocks still store -- as far as the chip has room for them: KSCHED_OPT_GRID_CUS).  Same results either way;
- * in every mode, and across a change of mode, a slot's mask is not overwritten by a later submit before the slot's previous pick,
- * where that pick reads the mask (the uniform and the spread pick always do), has run.  ksched_pipe_wait / ksched_pipe_wait_mask order a consumer behind the slot's work, ksched_pipe_slot_stream names its stream. */
+ * in every mode, and across a change of mode, a slot's mask kernel runs behind the slot's previous mask kernel, its pick behind the
+ * slot's previous pick, and a slot's mask is not overwritten by a later submit before the slot's previous pick, where that pick
+ * reads the mask (the uniform and the spread pick always do), has run.  ksched_pipe_wait / ksched_pipe_wait_mask order a consumer behind the slot's work, ksched_pipe_slot_stream names its stream. */
 #define KSCHED_OPT_PIPE_MODE 11
 #define KSCHED_PIPE_MAX_STREAMS 8u
 /* KSCHED_OPT_GRID_CUS: how many of the chip's 256 compute units ONE fused mask launch may occupy (0, the default, = all of them;

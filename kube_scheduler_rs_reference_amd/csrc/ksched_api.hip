@@ -31,6 +31,7 @@
 #include "kernels_summary.hpp"
 #include "kernels_pick_spread.hpp"  // (uses kernels_pick_uniform.hpp's helpers)
 #include "mask_alloc.hpp"
+#include "pipe_plan.hpp"
 #include "snapshot_change.hpp"
 #include "tile_index.hpp"
 
@@ -1026,6 +1027,15 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
     return KSCHED_OK;
 }
 
+// launch_pick for a caller that has not looked at the snapshot: no pods, nothing; no nodes, every binding -1 (choose() on an empty
+// store yields None on every attempt, src/main.rs:56,70)
+int pick_from_mask(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
+    if (r.p == 0) return KSCHED_OK;
+    if (c->n > 0) return launch_pick(c, r, feas);
+    HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
+    return KSCHED_OK;
+}
+
 SelectArgs make_select_args(const ksched_ctx *c, const EvalRequest &r) {
     SelectArgs q{};
     q.nrec = c->nrec.ptr;
@@ -1282,6 +1292,16 @@ int check_eval_args(const EvalRequest &r) {
     if ((flags & KSCHED_WANT_FIT_MASK) && !r.out_fit) return KSCHED_E_INVAL;
     if (!(flags & KSCHED_WANT_FIT_MASK) && r.out_fit) return KSCHED_E_INVAL;
     if (!(flags & kPickFlags) && !r.out_feas && !r.out_fit) return KSCHED_E_INVAL;
+    return KSCHED_OK;
+}
+
+// the arguments of a pick from the caller's masks (ksched_pick, ksched_pick_device) over a snapshot of n nodes
+int check_pick_args(uint32_t n, uint32_t p, const uint64_t *feasible, const int64_t *req_mem_bytes, const uint32_t *samples, uint32_t attempts,
+                    uint32_t flags, const int32_t *out_binding) {
+    if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
+    if (!out_binding || (p > 0 && n > 0 && !feasible)) return KSCHED_E_INVAL;
+    if ((flags & kDrawPicks) && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
+    if ((flags & KSCHED_PICK_BESTFIT) && (flags & KSCHED_FIT) && p > 0 && !req_mem_bytes) return KSCHED_E_INVAL;
     return KSCHED_OK;
 }
 
@@ -1703,13 +1723,9 @@ uint32_t ksched_mask_pitch(uint32_t n_nodes) { return (ksched_mask_words(n_nodes
 struct ksched_pipe {
     ksched_ctx *ctx = nullptr;
     uint32_t depth = 0;
-    hipStream_t s_mask = nullptr, s_pick = nullptr;
-    std::vector<hipStream_t> extra;  // streams 2 .. of the alternate mode over more than two streams (created on first use)
+    std::vector<hipStream_t> streams;  // by pipe_plan.hpp's index: 0 the mask stream, 1 the pick stream, 2 .. the alternate mode's further ones (created on first use)
     std::vector<hipEvent_t> mask_done, pick_done;
-    std::vector<hipStream_t> slot_stream;  // the stream that carries the slot's mask kernel (alternate mode: also its pick)
-    std::vector<hipStream_t> pick_stream;  // the stream that carried the slot's latest pick (ksched_pipe_slot_stream)
-    std::vector<uint8_t> last_split;       // the slot's latest submit ran in the split mode (its mask kernel and its pick on different streams)
-    std::vector<uint8_t> pick_read_mask;   // the slot's latest pick read the slot's mask (split mode): the next mask kernel into it waits for that pick
+    std::vector<PipeSlot> slots;  // what plan_pipe_submit orders a slot's next submit by
 };
 
 int ksched_pipe_create(ksched_ctx *c, uint32_t depth, ksched_pipe **out) try {
@@ -1721,12 +1737,13 @@ int ksched_pipe_create(ksched_ctx *c, uint32_t depth, ksched_pipe **out) try {
     if (!q) return KSCHED_E_NOMEM;
     q->ctx = c;
     q->depth = depth;
-    bool ok = hipStreamCreateWithFlags(&q->s_mask, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&q->s_pick, hipStreamNonBlocking) == hipSuccess;
-    q->slot_stream.assign(depth, nullptr);
-    q->pick_stream.assign(depth, nullptr);
-    q->last_split.assign(depth, 0);
-    q->pick_read_mask.assign(depth, 0);
+    q->slots.assign(depth, PipeSlot{});
+    bool ok = true;
+    for (int i = 0; ok && i <= kPipePickStream; ++i) {  // the mask stream and the pick stream
+        hipStream_t s = nullptr;
+        ok = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+        if (ok) q->streams.push_back(s);
+    }
     for (uint32_t i = 0; ok && i < 2 * depth; ++i) {
         hipEvent_t e;
         ok = hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
@@ -1744,20 +1761,14 @@ void ksched_pipe_destroy(ksched_pipe *q) try {
     if (!q) return;
     {
         DeviceGuard g(q->ctx->device);
-        if (q->s_mask) (void)hipStreamSynchronize(q->s_mask);
-        if (q->s_pick) (void)hipStreamSynchronize(q->s_pick);
-        for (auto st : q->extra) (void)hipStreamSynchronize(st);
+        for (auto st : q->streams) (void)hipStreamSynchronize(st);
         {
             std::lock_guard<std::mutex> lk(q->ctx->mu);  // the ctx must not record events on streams that are about to go away
-            stream_forget(q->ctx, q->s_mask);
-            stream_forget(q->ctx, q->s_pick);
-            for (auto st : q->extra) stream_forget(q->ctx, st);
+            for (auto st : q->streams) stream_forget(q->ctx, st);
         }
         for (auto e : q->mask_done) (void)hipEventDestroy(e);
         for (auto e : q->pick_done) (void)hipEventDestroy(e);
-        if (q->s_mask) (void)hipStreamDestroy(q->s_mask);
-        if (q->s_pick) (void)hipStreamDestroy(q->s_pick);
-        for (auto st : q->extra) (void)hipStreamDestroy(st);
+        for (auto st : q->streams) (void)hipStreamDestroy(st);
     }
     delete q;
 } catch (...) {  // nothing unwinds across the C ABI
@@ -1765,9 +1776,8 @@ void ksched_pipe_destroy(ksched_pipe *q) try {
 
 void *ksched_pipe_stream(ksched_pipe *q, int which) try {
     if (!q || which < 0) return nullptr;
-    if (which < 2) return (void *)(which == 0 ? q->s_mask : q->s_pick);
-    std::lock_guard<std::mutex> lk(q->ctx->mu);  // (ksched_pipe_submit grows `extra` under the same lock)
-    return (size_t)(which - 2) < q->extra.size() ? (void *)q->extra[(size_t)(which - 2)] : nullptr;
+    std::lock_guard<std::mutex> lk(q->ctx->mu);  // (ksched_pipe_submit grows `streams` under the same lock)
+    return (size_t)which < q->streams.size() ? (void *)q->streams[(size_t)which] : nullptr;
 } catch (...) {
     return nullptr;
 }
@@ -1777,11 +1787,12 @@ void *ksched_pipe_stream(ksched_pipe *q, int which) try {
 void *ksched_pipe_slot_stream(ksched_pipe *q, uint32_t slot) try {
     if (!q || slot >= q->depth) return nullptr;
     std::lock_guard<std::mutex> lk(q->ctx->mu);
-    return (void *)q->pick_stream[slot];
+    return q->slots[slot].used() ? (void *)q->streams[(size_t)q->slots[slot].pick_stream] : nullptr;
 } catch (...) {
     return nullptr;
 }
 
+// check, plan (pipe_plan.hpp: the streams, the waits and their reasons), execute
 int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t *pcpu, const int64_t *pmem, const uint32_t *psel,
                        const uint64_t *ptol, const uint32_t *samples, uint32_t attempts, uint32_t flags, uint64_t *mask,
                        uint32_t mask_pitch_words, int32_t *binding) try {
@@ -1791,66 +1802,36 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     if (!c->have_nodes) return KSCHED_E_STATE;
     const uint32_t pick = flags & kPickFlags;
     if (!pick || (flags & KSCHED_WANT_FIT_MASK) || !mask) return KSCHED_E_INVAL;
-    EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, mask, nullptr, binding, mask_pitch_words, nullptr};  // (the stream: chosen below)
+    EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, mask, nullptr, binding, mask_pitch_words, nullptr};  // (the stream: the plan's)
     int rc = check_eval_args(r);
     if (rc) return rc;
     if (mask_pitch_words < c->W) return KSCHED_E_INVAL;
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
-    // Does the pick read the mask?  By default it does not (sampled: the drawn candidates are tested from the columns;
-    // best fit: bitmaps kept in best-fit order), so the two streams need no ordering at all: each is in order by itself
-    // (mask kernels of successive batches on one, picks on the other), which also covers the reuse of a slot's buffers.
     const bool reads_mask = pick_reads_mask(flags, c->opt_pick_from_mask, bf_rows_expected(c));
-    if (c->opt_pipe_mode >= 1 && !reads_mask) {
-        // alternate: the whole evaluation of the slot on ONE of the pipe's streams (one launch when the pick rides in the mask
-        // kernel), stream = slot mod k.  A slot comes back to the same stream as long as the mode stays what it is, so the reuse of
-        // its buffers is ordered by the stream itself; when the slot's previous use ran elsewhere -- another k, or the split mode,
-        // whose mask kernel sits on the mask stream un-ordered against anything -- its new stream first waits for that use.
-        const uint32_t k = std::max(2u, (uint32_t)c->opt_pipe_mode), which = slot % k;
-        while (which >= 2u && q->extra.size() < (size_t)which - 1u) {
-            hipStream_t ns = nullptr;
-            HIPCHK(c, hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
-            q->extra.push_back(ns);
-        }
-        hipStream_t st = which == 0u ? q->s_mask : which == 1u ? q->s_pick : q->extra[which - 2u];
-        if (q->pick_stream[slot] && (q->pick_stream[slot] != st || q->last_split[slot])) HIPCHK(c, hipStreamWaitEvent(st, q->pick_done[slot], 0));
-        if (q->last_split[slot] && q->slot_stream[slot] != st) HIPCHK(c, hipStreamWaitEvent(st, q->mask_done[slot], 0));  // (the split mode records it after every mask kernel)
-        q->last_split[slot] = 0;
-        q->pick_read_mask[slot] = 0;
-        q->slot_stream[slot] = st;
-        q->pick_stream[slot] = st;
-        r.stream = st;
+    const PipePlan pl = plan_pipe_submit(q->slots[slot], slot, c->opt_pipe_mode, reads_mask);
+    const hipEvent_t mask_done = q->mask_done[slot], pick_done = q->pick_done[slot];
+    while (q->streams.size() <= (size_t)pl.pick_stream) {  // a further stream of the alternate mode, on first use (pl.mask_stream is the same one, or stream 0)
+        hipStream_t ns = nullptr;
+        HIPCHK(c, hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
+        q->streams.push_back(ns);
+    }
+    const hipStream_t sm = q->streams[(size_t)pl.mask_stream], sp = q->streams[(size_t)pl.pick_stream];
+    if (pl.mask_waits_pick_done) HIPCHK(c, hipStreamWaitEvent(sm, pick_done, 0));
+    if (pl.mask_waits_mask_done) HIPCHK(c, hipStreamWaitEvent(sm, mask_done, 0));
+    if (pl.pick_waits_pick_done) HIPCHK(c, hipStreamWaitEvent(sp, pick_done, 0));
+    q->slots[slot] = pl.next;
+    r.stream = sp;
+    if (pl.whole) {  // one launch when the pick rides in the mask kernel
         if ((rc = eval_on_device(c, r))) return rc;
-        HIPCHK(c, hipEventRecord(q->pick_done[slot], st));
-        return KSCHED_OK;
-    }
-    hipStream_t sm = q->s_mask;
-    if (q->pick_stream[slot] && q->pick_stream[slot] != q->s_pick) {  // the slot last ran in the alternate mode on another stream
-        HIPCHK(c, hipStreamWaitEvent(q->s_pick, q->pick_done[slot], 0));
-        HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));
-    }
-    q->slot_stream[slot] = sm;
-    q->pick_stream[slot] = q->s_pick;
-    // the slot's mask may be overwritten once the pick that reads it has run: this submit's own pick orders the slot's NEXT mask kernel, and
-    // the previous submit's pick this one (also when this submit's pick reads no mask: a sampled submit into a slot whose last pick was uniform or spread)
-    if (reads_mask || q->pick_read_mask[slot]) HIPCHK(c, hipStreamWaitEvent(sm, q->pick_done[slot], 0));
-    q->pick_read_mask[slot] = reads_mask ? 1 : 0;
-    q->last_split[slot] = 1;
-    if ((rc = eval_on_device(c, EvalRequest{p, pcpu, pmem, psel, ptol, nullptr, 0, flags & ~pick, mask, nullptr, nullptr, mask_pitch_words, sm}))) return rc;
-    HIPCHK(c, hipEventRecord(q->mask_done[slot], sm));  // (always: a later submit of this slot in the alternate mode orders itself behind this mask kernel)
-    r.stream = q->s_pick;
-    if (reads_mask) {
-        HIPCHK(c, hipStreamWaitEvent(q->s_pick, q->mask_done[slot], 0));
-        if (p > 0) {
-            if (c->n == 0) HIPCHK(c, hipMemsetAsync(binding, 0xFF, (size_t)p * sizeof(int32_t), q->s_pick));
-            else if ((rc = launch_pick(c, r, mask))) return rc;
-        }
     } else {
-        // bindings-only evaluation on the pick stream: launches the pick kernel alone
-        r.out_feas = nullptr;
-        if ((rc = eval_on_device(c, r))) return rc;
+        if ((rc = eval_on_device(c, EvalRequest{p, pcpu, pmem, psel, ptol, nullptr, 0, flags & ~pick, mask, nullptr, nullptr, mask_pitch_words, sm}))) return rc;
+        if (pl.record_mask_done) HIPCHK(c, hipEventRecord(mask_done, sm));
+        if (pl.pick_waits_mask_done) HIPCHK(c, hipStreamWaitEvent(sp, mask_done, 0));
+        r.out_feas = nullptr;  // (no mask kernel on the pick stream: the pick from the mask, or the bindings-only evaluation, which launches the pick kernel alone)
+        if ((rc = reads_mask ? pick_from_mask(c, r, mask) : eval_on_device(c, r))) return rc;
     }
-    HIPCHK(c, hipEventRecord(q->pick_done[slot], q->s_pick));
+    HIPCHK(c, hipEventRecord(pick_done, sp));
     return KSCHED_OK;
 } KSCHED_ABI_CATCH((q ? q->ctx : nullptr))
 
@@ -1872,7 +1853,8 @@ int ksched_pipe_wait_mask(ksched_pipe *q, uint32_t slot, void *hip_stream) try {
     if (!g.ok) return KSCHED_E_HIP;
     // The mask stream is in order: "everything enqueued on it so far" contains the slot's latest mask kernel.  Recorded here, on
     // demand, so that the submit path carries no event for consumers that never read the masks.
-    HIPCHK(c, hipEventRecord(q->mask_done[slot], q->slot_stream[slot] ? q->slot_stream[slot] : q->s_mask));
+    const PipeSlot &sl = q->slots[slot];
+    HIPCHK(c, hipEventRecord(q->mask_done[slot], q->streams[(size_t)(sl.used() ? sl.mask_stream : kPipeMaskStream)]));
     if (hip_stream) HIPCHK(c, hipStreamWaitEvent((hipStream_t)hip_stream, q->mask_done[slot], 0));
     else HIPCHK(c, hipEventSynchronize(q->mask_done[slot]));
     return KSCHED_OK;
@@ -1883,21 +1865,12 @@ int ksched_pick_device(ksched_ctx *c, uint32_t p, const uint64_t *feasible, uint
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    // (pick_s: the pick reads draws -- sampled, uniform or spread)
-    const bool pick_s = flags & kDrawPicks, pick_b = flags & KSCHED_PICK_BESTFIT;
-    if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
-    if (!out_binding || (p > 0 && c->n > 0 && !feasible) || mask_pitch_words < c->W) return KSCHED_E_INVAL;
-    if (pick_s && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
-    if (pick_b && (flags & KSCHED_FIT) && p > 0 && !req_mem_bytes) return KSCHED_E_INVAL;
+    if (int rc = check_pick_args(c->n, p, feasible, req_mem_bytes, samples, attempts, flags, out_binding)) return rc;
+    if (mask_pitch_words < c->W) return KSCHED_E_INVAL;
     if (p == 0) return KSCHED_OK;
     DeviceGuard g(c->device);
     if (!g.ok) return KSCHED_E_HIP;
-    hipStream_t s = (hipStream_t)hip_stream;
-    if (c->n == 0) {  // choose() on an empty store yields None on every attempt (src/main.rs:56,70)
-        HIPCHK(c, hipMemsetAsync(out_binding, 0xFF, (size_t)p * sizeof(int32_t), s));
-        return KSCHED_OK;
-    }
-    return launch_pick(c, EvalRequest{p, nullptr, req_mem_bytes, nullptr, nullptr, samples, attempts, flags, nullptr, nullptr, out_binding, mask_pitch_words, s}, feasible);
+    return pick_from_mask(c, EvalRequest{p, nullptr, req_mem_bytes, nullptr, nullptr, samples, attempts, flags, nullptr, nullptr, out_binding, mask_pitch_words, (hipStream_t)hip_stream}, feasible);
 } KSCHED_ABI_CATCH(c)
 
 // The pick alone from HOST masks (packed rows of W words): copies in, ksched_pick_device on the ctx's stream, copies out, waits.
@@ -1908,10 +1881,7 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
     if (!c->have_nodes) return KSCHED_E_STATE;
     // (pick_s: the pick reads draws -- sampled, uniform or spread)
     const bool pick_s = flags & kDrawPicks, pick_b = flags & KSCHED_PICK_BESTFIT;
-    if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
-    if (!out_binding || (p > 0 && c->n > 0 && !feasible)) return KSCHED_E_INVAL;
-    if (pick_s && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
-    if (pick_b && (flags & KSCHED_FIT) && p > 0 && !req_mem_bytes) return KSCHED_E_INVAL;
+    if (int rc = check_pick_args(c->n, p, feasible, req_mem_bytes, samples, attempts, flags, out_binding)) return rc;
     if (p == 0) return KSCHED_OK;
     if (c->n == 0) {  // choose() on an empty store yields None on every attempt (src/main.rs:56,70)
         for (uint32_t i = 0; i < p; ++i) out_binding[i] = -1;

@@ -491,6 +491,39 @@ def test_a_sampled_submit_does_not_overwrite_the_mask_its_slots_uniform_pick_sti
         pipe.close()
 
 
+def test_a_split_submit_does_not_overtake_the_mask_kernel_its_slot_ran_on_the_pick_stream(ev):
+    """The reduced case of a missing ordering across a change of mode (csrc/pipe_plan.hpp, invariant 1): slot 1 takes a sampled submit
+    at mode 2, whole on stream 1 mod 2 = 1 -- the pick stream, here held up by a short device-side spin --, then the mode changes to 0 and
+    the slot takes a sampled submit of another batch into the same mask.  The second submit's mask kernel, on the mask stream, must wait for
+    the first one's on the pick stream, or the first one's mask is what the slot is left with."""
+    import torch
+    ev.set_nodes(**case(MID)["c"].node_columns())
+    pipe = ev.pipe(2)
+    try:
+        size = 300
+        mask = ev.alloc_mask(size, pitched=True)
+        out = torch.full((size,), -7, dtype=torch.int32, device=dev_of(ev))
+        a, b = mid_batch(ev, 0, size, uniform=False), mid_batch(ev, 600, 600 + size, uniform=False)
+        assert not np.array_equal(a[2], b[2])
+        held = int(pipe._lib.ksched_pipe_stream(pipe._h, 1))
+        torch.cuda.synchronize()
+        with torch.cuda.stream(pipe.stream(1)):
+            torch.cuda._sleep(10_000_000)  # some milliseconds of the pick stream: longer than the two submits take to enqueue
+        ev.set_option(_lib.OPT_PIPE_MODE, 2)
+        pipe.submit(1, *a[0], a[1], mask, out)
+        assert pipe.slot_stream_handle(1) == held
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
+        pipe.submit(1, *b[0], b[1], mask, out)
+        pipe.wait(1, host=True)
+        pipe.wait_mask(1, host=True)
+        torch.cuda.synchronize()
+        assert np.array_equal(mask_np(mask), b[2]), "the slot's mask is not its latest submit's"
+        assert np.array_equal(out.cpu().numpy(), b[3])
+    finally:
+        pipe.close()
+        ev.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
 # ---- 11. seeded differential loop ---------------------------------------------------------------------------------------------
 def test_seeded_differential_loop(ev):
     import torch
