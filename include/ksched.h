@@ -310,11 +310,34 @@ int ksched_update_node_labels(ksched_ctx *ctx, uint32_t count, const uint32_t *n
  * If a HIP call fails midway the snapshot is invalidated (KSCHED_E_STATE until the next ksched_set_nodes). */
 #define KSCHED_APPLY_FIRST_PER_NODE 0x01u /* per node accept only the lowest pod index among the eligible pods */
 #define KSCHED_APPLY_RELEASE 0x02u        /* add the requests back instead of subtracting (pods deleted / unbound) */
+/* KSCHED_APPLY_WHILE_FIT: admit the bindings in pod order while they still fit -- no node is over-committed, and a node takes as many
+ * pods of one call as it has room for.  (0x04 and 0x80 are not flags: callers probe with them for KSCHED_E_INVAL.)  An older library of
+ * ABI 7 answers KSCHED_E_INVAL to this flag: detect the rule by the constant and that answer; no symbol was added.
+ *   Eligibility and the statuses that precede are unchanged: UNBOUND (binding < 0), then BAD_NODE (binding >= n), then NOT_OK.
+ *   Per node: the eligible pods bound to it are taken in ascending pod index.  R = (R_cpu, R_mem) starts as the node's `available` at
+ *   the call's place in the order of snapshot changes -- so the first pod of a node is checked against the CURRENT value too, which
+ *   guards a pipelined caller whose batch i + 1 was evaluated before batch i's apply against stale bindings.
+ *     - pod i is admitted iff req_cpu[i] <= R_cpu && req_mem[i] <= R_mem, signed 64-bit compares (can_pod_fit,
+ *       src/predicates.rs:37-42): a zero request fits a node at exactly 0 and does not fit a negative one;
+ *     - an admitted pod gives R -= req on both resources and reports KSCHED_APPLY_APPLIED;
+ *     - a pod that does not fit reports KSCHED_APPLY_DEFERRED and changes nothing; the walk GOES ON behind it (skip, not stop): a
+ *       later, smaller pod may still be admitted;
+ *     - a pod that fits but whose subtraction would take either resource past INT64_MAX (a negative request only) is not admitted and
+ *       reports KSCHED_APPLY_OVERFLOW; the walk goes on -- unlike the summed rule, one such pod does not freeze the node.
+ *   The node's new `available` is the final R; a node whose admitted requests sum to zero on both resources is left untouched (its
+ *   index tile is not rebuilt for it).  Integer arithmetic in a fixed order: same inputs, same bits, on every run.
+ *   KSCHED_APPLY_WHILE_FIT | KSCHED_APPLY_RELEASE and KSCHED_APPLY_WHILE_FIT | KSCHED_APPLY_FIRST_PER_NODE are KSCHED_E_INVAL with
+ *   nothing changed; more than 2^31 pods in one call likewise.  Everything else is as without the flag: ordering and
+ *   KSCHED_OPT_SNAPSHOT_STREAM, `ok`, `status_out` (may be NULL), p == 0, KSCHED_E_STATE, the invalidation when a HIP call fails after
+ *   the change began (the call's scratch is reserved before), the stale best-fit order, the re-index of the touched tiles only.
+ *   ksched_apply_bindings_sharded and _sharded_local answer KSCHED_E_UNSUPPORTED to it, with nothing changed, no collective entered
+ *   and the clique usable as before: admission needs every rank's requests per node, which the per-node exchange does not carry. */
+#define KSCHED_APPLY_WHILE_FIT 0x08u
 #define KSCHED_APPLY_APPLIED 0
 #define KSCHED_APPLY_UNBOUND 1   /* binding < 0: nothing to apply (no node found) */
 #define KSCHED_APPLY_NOT_OK 2    /* ok[p] == 0: the POST did not land (src/main.rs:103-108) */
-#define KSCHED_APPLY_DEFERRED 3  /* FIRST_PER_NODE: a lower pod index took this node in this call */
-#define KSCHED_APPLY_OVERFLOW 4  /* the node's new value would leave int64: node left unchanged */
+#define KSCHED_APPLY_DEFERRED 3  /* FIRST_PER_NODE: a lower pod index took this node in this call; WHILE_FIT: the pod did not fit what was left */
+#define KSCHED_APPLY_OVERFLOW 4  /* the node's new value would leave int64: node left unchanged (WHILE_FIT: this pod alone is not admitted) */
 #define KSCHED_APPLY_BAD_NODE 5  /* binding >= ksched_num_nodes */
 int ksched_apply_bindings_device(ksched_ctx *ctx, uint32_t p, const int32_t *bindings, const int64_t *req_cpu_milli,
                                  const int64_t *req_mem_bytes, const uint8_t *ok /* [p] or NULL = all landed */,

@@ -40,6 +40,7 @@ PICK_SPREAD = 0x80  # extension E4: the least loaded (available memory, then cpu
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02
+APPLY_WHILE_FIT = 0x08  # admit the bindings in pod order while they still fit (0x04 is not a flag)
 APPLY_APPLIED = 0
 APPLY_UNBOUND = 1
 APPLY_NOT_OK = 2

@@ -22,12 +22,15 @@
 //                       k_build_tile_fit then re-indexes the dirty tiles.  With a communicator only, the claims and the partial sums of
 //                       every rank are all-gathered between the passes: k_apply_claim_merge takes the per-node minimum claim and
 //                       k_apply_commit_gathered commits the merged sums in place of k_apply_commit (ksched_api.hip "applying")
+//   k_apply_keys, k_apply_admit   KSCHED_APPLY_WHILE_FIT: the eligible pods keyed by node, sorted by (node, pod) with the merge sort
+//                       below, then a wave per node admits its pods in pod order while they fit (apply_admit.hpp)
 //   k_bf_*              best-fit order and its row bitmaps (built lazily, on the first PICK_BESTFIT after a change)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/ksched.h"
+#include "apply_admit.hpp"
 #include "kernels_direct.hpp"
 #include "tile_index.hpp"
 
@@ -498,6 +501,113 @@ __global__ __launch_bounds__(1024) void k_apply_commit_gathered(const ApplyArgs 
 __global__ __launch_bounds__(256) void k_apply_status(const ApplyArgs a) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.p; i += gridDim.x * blockDim.x) {
         if (a.status[i] == KSCHED_APPLY_APPLIED && a.ovf[a.bindings[i]]) a.status[i] = KSCHED_APPLY_OVERFLOW;
+    }
+}
+
+// ---- KSCHED_APPLY_WHILE_FIT: per node, its eligible pods in pod order while they still fit ----------------------------------------
+// k_apply_keys -> k_sort_runs / k_merge_pass (below; k1 absent, idx = position) -> k_apply_admit -> k_build_tile_fit over the dirty
+// tiles.  The sort's total order on (k0, idx) = (node, pod index) puts every node's eligible pods side by side in ascending pod index,
+// the ineligible ones (key INT64_MAX) behind them all.  Then nothing is shared between nodes: a wave per node, no atomics, no LDS, no
+// barrier, nothing of acc / claim / ovf.  Integer arithmetic in a fixed order per node: the same bits on every run and for any grid.
+struct AdmitArgs {
+    const int32_t *bindings;
+    const int64_t *req_cpu, *req_mem;
+    const uint8_t *ok;     // [p] or nullptr = every POST landed
+    int32_t *status;       // [p] or nullptr
+    int64_t *keys;         // k_apply_keys: [p] out, the node of an eligible pod, INT64_MAX otherwise
+    const int64_t *k0;     // k_apply_admit: [p] the keys, sorted
+    const uint32_t *idx;   // k_apply_admit: [p] the pod index of every sorted key
+    uint32_t *dirty;       // [tiles + 1], as ApplyArgs::dirty
+    int64_t *ncpu, *nmem, *nrec;
+    uint32_t p, n, tiles, gen;
+};
+
+// a lane per pod: the final status of the ineligible pods, the sort key of every pod; thread 0 stamps the call's generation
+__global__ __launch_bounds__(256) void k_apply_keys(const AdmitArgs a) {
+    const uint32_t t0 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t0 == 0) a.dirty[a.tiles] = a.gen;
+    for (uint32_t i = t0; i < a.p; i += gridDim.x * blockDim.x) {
+        const int32_t b = a.bindings[i];
+        int32_t st = KSCHED_APPLY_APPLIED;  // (eligible: k_apply_admit decides)
+        if (b < 0) st = KSCHED_APPLY_UNBOUND;
+        else if ((uint32_t)b >= a.n) st = KSCHED_APPLY_BAD_NODE;
+        else if (a.ok && a.ok[i] == 0) st = KSCHED_APPLY_NOT_OK;
+        a.keys[i] = st == KSCHED_APPLY_APPLIED ? (int64_t)b : INT64_MAX;
+        if (a.status && st != KSCHED_APPLY_APPLIED) a.status[i] = st;
+    }
+}
+
+// the first position of the sorted keys that holds `key` or more (every lane of the wave searches the same key)
+__device__ __forceinline__ uint32_t admit_lower_bound(const int64_t *__restrict__ k0, uint32_t lo, uint32_t hi, int64_t key) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (k0[mid] < key) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int64_t admit_scan(int64_t v, uint32_t lane) {  // inclusive prefix sum over the wave's lanes
+#pragma unroll
+    for (uint32_t d = 1; d < kAdmitLanes; d <<= 1) {
+        const int64_t t = (int64_t)__shfl_up((long long)v, d, (int)kAdmitLanes);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// a wave per node: its segment of the sorted keys in chunks of 64 pods, the steps of apply_admit.hpp per chunk; the node's columns,
+// record words 0 and 1 (what apply_node writes) and its tile's mark are stored only when what is left differs from what was there
+__global__ __launch_bounds__(256) void k_apply_admit(const AdmitArgs a) {
+    const uint32_t lane = threadIdx.x & (kAdmitLanes - 1u);
+    const uint32_t node = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x / kAdmitLanes) + threadIdx.x / kAdmitLanes));
+    if (node >= a.n) return;
+    const uint32_t seg_lo = admit_lower_bound(a.k0, 0u, a.p, (int64_t)node);
+    const uint32_t seg_hi = admit_lower_bound(a.k0, seg_lo, a.p, (int64_t)node + 1);
+    if (seg_lo == seg_hi) return;
+    const int64_t old_cpu = a.ncpu[node], old_mem = a.nmem[node];
+    int64_t r_cpu = old_cpu, r_mem = old_mem;
+    for (uint32_t g = seg_lo; g < seg_hi; g += kAdmitLanes) {  // (p <= 2^31: g + 64 does not wrap)
+        const bool live = lane < seg_hi - g;
+        uint32_t pod = 0;
+        int64_t c = 0, m = 0;
+        if (live) {
+            pod = a.idx[g + lane];
+            c = a.req_cpu[pod];
+            m = a.req_mem[pod];
+        }
+        const bool shrink_only = __ballot(live && (c < 0 || m < 0)) == 0ull;  // no negative request: R cannot grow inside the chunk
+        bool undecided = live;
+        int32_t st = KSCHED_APPLY_APPLIED;
+        while (__ballot(undecided) != 0ull) {
+            if (shrink_only && undecided && !admit_fits(r_cpu, r_mem, c, m)) {
+                st = KSCHED_APPLY_DEFERRED;
+                undecided = false;
+            }
+            const int64_t hc = undecided ? admit_hi(c) : 0, lc = undecided ? admit_lo(c) : 0;
+            const int64_t hm = undecided ? admit_hi(m) : 0, lm = undecided ? admit_lo(m) : 0;
+            const int64_t shc = admit_scan(hc, lane), slc = admit_scan(lc, lane), shm = admit_scan(hm, lane), slm = admit_scan(lm, lane);
+            const AdmitVerdict v = admit_lane_test(r_cpu, r_mem, admit_join(shc - hc, slc - lc), admit_join(shm - hm, slm - lm), c, m);
+            const uint32_t f = admit_first_failing(__ballot(undecided && v != kAdmitPass));
+            if (lane == f) st = v == kAdmitOverflow ? KSCHED_APPLY_OVERFLOW : KSCHED_APPLY_DEFERRED;
+            if (lane <= f) undecided = false;  // (the undecided lanes before f are admitted: st is APPLIED already)
+            // the prefix before f: lane f's exclusive sums, or with no failing lane the last lane's inclusive ones
+            const bool all = f == kAdmitLanes;
+            const int src = all ? (int)kAdmitLanes - 1 : (int)f;
+            const int64_t phc = (int64_t)__shfl((long long)(all ? shc : shc - hc), src, (int)kAdmitLanes);
+            const int64_t plc = (int64_t)__shfl((long long)(all ? slc : slc - lc), src, (int)kAdmitLanes);
+            const int64_t phm = (int64_t)__shfl((long long)(all ? shm : shm - hm), src, (int)kAdmitLanes);
+            const int64_t plm = (int64_t)__shfl((long long)(all ? slm : slm - lm), src, (int)kAdmitLanes);
+            r_cpu = admit_carry(r_cpu, admit_join(phc, plc));
+            r_mem = admit_carry(r_mem, admit_join(phm, plm));
+        }
+        if (live && a.status) a.status[pod] = st;
+    }
+    if (lane == 0 && (r_cpu != old_cpu || r_mem != old_mem)) {
+        a.ncpu[node] = r_cpu;
+        a.nmem[node] = r_mem;
+        a.nrec[(size_t)kNodeRecWords * node] = r_cpu;
+        a.nrec[(size_t)kNodeRecWords * node + 1] = r_mem;
+        a.dirty[node / kTileNodes] = a.gen;  // (plain store: every writer of a tile stores the same word)
     }
 }
 

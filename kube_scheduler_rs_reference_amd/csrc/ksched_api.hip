@@ -140,6 +140,8 @@ struct ksched_ctx {
     DevBuf<uint64_t> apply_gath;  // ksched_apply_bindings_sharded*: every rank's acc [nranks][n][4] (or claims [nranks][n] uint32)
     uint32_t apply_n = 0;         // nodes the scratch holds in its idle state (0 = not yet, or a failed call left it unknown)
     uint32_t apply_gen = 0;       // generation of the latest call
+    DevBuf<int64_t> admit_k0[2];  // KSCHED_APPLY_WHILE_FIT: ping-pong sets of the (node, pod) merge sort, [p] each, grown on demand
+    DevBuf<uint32_t> admit_idx[2];
     hipEvent_t ev_apply = nullptr;  // the caller's stream, when the change rides another one
     std::string index_reason;  // why the snapshot has no bitmap index (the fused kernel is then not applicable)
     // host -> device staging for the snapshot calls: pinned, so the copies are asynchronous on the change stream
@@ -2561,6 +2563,8 @@ int ksched_allgather_bindings_local(ksched_comm *const *comms, int n, const int3
 // batch, the claims and the partial sums are all-gathered between the phases, and the commit merges them.  Everything of one rank rides
 // its ctx's change stream; the all-gathers are enqueued there too.  The runner takes each phase through every rank before the
 // collective that joins them, so the one-process form issues the per-device calls of a collective together in one group.
+// KSCHED_APPLY_WHILE_FIT (single ctx only) keeps the bracket -- apply_begin orders the change, apply_finish re-indexes and commits --
+// and runs keys -> sort by (node, pod) -> admit in place of accumulate -> commit -> status (apply_admit_sort, k_apply_admit).
 namespace {
 
 struct ApplyCall {
@@ -2569,6 +2573,8 @@ struct ApplyCall {
     hipStream_t hs = nullptr;  // the caller's stream
     uint32_t count = 0;        // the rank's rows
     ApplyArgs a{};
+    bool admit = false;        // KSCHED_APPLY_WHILE_FIT (single-ctx only): keys, sort and admit in place of accumulate, commit and status
+    AdmitArgs w{};
     SnapshotChange chg;        // done when every rank's change has been committed (apply_run)
 };
 
@@ -2595,11 +2601,36 @@ int apply_scratch_ready(ksched_ctx *c, hipStream_t s) {
     return KSCHED_OK;
 }
 
+// flags every entry point refuses: unknown bits, and WHILE_FIT with another admission rule or with RELEASE (nothing is admitted there)
+int apply_flags_check(uint32_t flags) {
+    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE | KSCHED_APPLY_WHILE_FIT)) return KSCHED_E_INVAL;
+    if ((flags & KSCHED_APPLY_WHILE_FIT) && (flags & (KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE))) return KSCHED_E_INVAL;
+    return KSCHED_OK;
+}
+
+// KSCHED_APPLY_WHILE_FIT: the sort's two buffer sets for p records, grown on demand (apply_begin calls this BEFORE the change begins:
+// a failed allocation leaves the snapshot as it was)
+int admit_scratch_ready(ksched_ctx *c, uint32_t p) {
+    if (p > (1u << 31)) {  // (the merge passes index records with 32 bits, as bestfit_sort)
+        c->last_error = "ksched_apply_bindings_device: KSCHED_APPLY_WHILE_FIT with more than 2^31 pods";
+        return KSCHED_E_INVAL;
+    }
+    if (p <= c->admit_k0[0].cap && p <= c->admit_k0[1].cap && p <= c->admit_idx[0].cap && p <= c->admit_idx[1].cap) return KSCHED_OK;
+    const size_t cap = std::max<size_t>((size_t)p + p / 4, 1024);
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(c, c->admit_k0[i].reserve(cap));
+        HIPCHK(c, c->admit_idx[i].reserve(cap));
+    }
+    return KSCHED_OK;
+}
+
 // argument checks of one rank of a sharded call that need no lock and no device
 int sharded_check(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu,
                   const int64_t *req_mem, uint32_t flags) {
     if (!c || !q || !q->comm) return KSCHED_E_INVAL;
-    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE)) return KSCHED_E_INVAL;
+    if (int rc = apply_flags_check(flags)) return rc;
+    // (admission needs every rank's requests per node, in pod order; the per-node exchange of claims and sums cannot carry that)
+    if (flags & KSCHED_APPLY_WHILE_FIT) return KSCHED_E_UNSUPPORTED;
     if (count > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
     if ((uint64_t)row_lo + count > (uint64_t)kApplyUnclaimed) return KSCHED_E_INVAL;  // global pod indexes stay below the idle claim
     if (q->device != c->device) return KSCHED_E_INVAL;
@@ -2613,6 +2644,9 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
                 const uint8_t *ok, uint32_t flags, int32_t *status_out) {
     ksched_ctx *c = x.c;
     fault_point(c);  // (nothing has changed yet)
+    x.admit = (flags & KSCHED_APPLY_WHILE_FIT) != 0u;
+    if (x.admit)
+        if (int rc = admit_scratch_ready(c, x.count)) return rc;
     if (int rc = x.chg.begin(c)) return rc;
     const hipStream_t s = c->change_stream;
     if (s != x.hs) {
@@ -2653,6 +2687,60 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
         hipLaunchKernelGGL(k_apply_claim, pod_grid(a.p), dim3(256), 0, s, a);
         HIPCHK(c, hipGetLastError());
     }
+    if (x.admit) {
+        AdmitArgs &w = x.w;
+        w.bindings = bindings;
+        w.req_cpu = req_cpu;
+        w.req_mem = req_mem;
+        w.ok = ok;
+        w.status = status_out;
+        w.dirty = a.dirty;
+        w.ncpu = a.ncpu;
+        w.nmem = a.nmem;
+        w.nrec = a.nrec;
+        w.p = a.p;
+        w.n = n;
+        w.tiles = a.tiles;
+        w.gen = a.gen;
+    }
+    return KSCHED_OK;
+}
+
+// phase 2 of KSCHED_APPLY_WHILE_FIT, in place of the accumulate pass: the pods' sort keys (and the ineligible pods' statuses), then
+// the records (node, pod index) sorted as bestfit_sort sorts -- runs of 1024 in LDS, merged by ranking, ping-pong between the ctx's
+// two sets; the keys start in set 1, so every pass reads one set and writes the other.  x.w.k0 / x.w.idx: where the last pass landed.
+int apply_admit_sort(ApplyCall &x) {
+    ksched_ctx *c = x.c;
+    const hipStream_t s = c->change_stream;
+    AdmitArgs &w = x.w;
+    const uint32_t p = w.p;
+    if (p == 0) return KSCHED_OK;
+    w.keys = c->admit_k0[1].ptr;
+    hipLaunchKernelGGL(k_apply_keys, pod_grid(p), dim3(256), 0, s, w);
+    HIPCHK(c, hipGetLastError());
+    if (w.n == 0) return KSCHED_OK;  // (every pod is UNBOUND or BAD_NODE: final)
+    SortArgs q{};  // (no second key, no idx_in: idx = position = the pod index)
+    q.n = p;
+    q.k0_in = w.keys;
+    q.k0_out = c->admit_k0[0].ptr;
+    q.idx_out = c->admit_idx[0].ptr;
+    hipLaunchKernelGGL(k_sort_runs, dim3((p + 1023u) / 1024u), dim3(1024), 0, s, q);
+    HIPCHK(c, hipGetLastError());
+    uint32_t set = 0;
+    for (uint64_t run = 1024; run < p; run <<= 1) {
+        SortArgs m{};
+        m.n = p;
+        m.run = (uint32_t)run;
+        m.k0_in = c->admit_k0[set].ptr;
+        m.idx_in = c->admit_idx[set].ptr;
+        set ^= 1u;
+        m.k0_out = c->admit_k0[set].ptr;
+        m.idx_out = c->admit_idx[set].ptr;
+        hipLaunchKernelGGL(k_merge_pass, dim3((p + 255u) / 256u), dim3(256), 0, s, m);
+        HIPCHK(c, hipGetLastError());
+    }
+    w.k0 = c->admit_k0[set].ptr;
+    w.idx = c->admit_idx[set].ptr;
     return KSCHED_OK;
 }
 
@@ -2678,14 +2766,16 @@ int apply_finish(ApplyCall &x) {
     ksched_ctx *c = x.c;
     const hipStream_t s = c->change_stream;
     if (x.a.tiles > 0) {
-        if (x.q) hipLaunchKernelGGL(k_apply_commit_gathered, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
+        if (x.admit) {  // a wave per node, four to a block
+            if (x.w.p > 0) hipLaunchKernelGGL(k_apply_admit, dim3((x.w.n + 3u) / 4u), dim3(256), 0, s, x.w);
+        } else if (x.q) hipLaunchKernelGGL(k_apply_commit_gathered, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
         else hipLaunchKernelGGL(k_apply_commit, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
         HIPCHK(c, hipGetLastError());
         if (c->idx.built) {
             // only the dirty tiles are re-indexed: every tile's block reads its generation and the clean ones exit
             if (int rc = launch_build_fit(c, nullptr, 0, c->apply_dirty.ptr)) return rc;
         }
-        if (x.a.status && x.a.p > 0) {  // (every status but OVERFLOW is final after the accumulate pass; with no node, all of them)
+        if (!x.admit && x.a.status && x.a.p > 0) {  // (every status but OVERFLOW is final after the accumulate pass; with no node, all of them)
             hipLaunchKernelGGL(k_apply_status, pod_grid(x.a.p), dim3(256), 0, s, x.a);
             HIPCHK(c, hipGetLastError());
         }
@@ -2730,7 +2820,7 @@ int apply_run(ApplyCall *v, int k, const uint32_t *row_lo, const int32_t *const 
     for (int i = 0; i < k; ++i) {
         DeviceGuard g(v[i].c->device);
         if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = apply_accumulate(v[i])) return rc;
+        if (int rc = v[i].admit ? apply_admit_sort(v[i]) : apply_accumulate(v[i])) return rc;
     }
     if (comm && n > 0)  // the split sums as 32-bit words: 8 per node
         if (int rc = apply_allgather(v, k, false, (size_t)n * 8, "ncclAllGather (sums)")) return rc;
@@ -2751,7 +2841,7 @@ extern "C" {
 int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
                                  const uint8_t *ok, uint32_t flags, int32_t *status_out, void *hip_stream) try {
     if (!c) return KSCHED_E_INVAL;
-    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE)) return KSCHED_E_INVAL;
+    if (int rc = apply_flags_check(flags)) return rc;
     if (p > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;

@@ -171,7 +171,10 @@ class Evaluator:
 
     def apply_bindings_device(self, bindings, req_cpu_milli, req_mem_bytes, ok=None, flags: int = 0, status_out=None, stream=None):
         """Apply a batch's bindings to the snapshot on the device (ksched_apply_bindings_device): `available` of every node shrinks by the
-        requests of the eligible pods bound to it (grows with APPLY_RELEASE).  torch CUDA tensors on this evaluator's device, all [p]:
+        requests of the eligible pods bound to it (grows with APPLY_RELEASE).  flags: 0 accepts every eligible pod, APPLY_FIRST_PER_NODE one
+        pod per node (the others DEFERRED), APPLY_WHILE_FIT per node the pods in ascending index while they still fit what is left (a pod
+        that does not fit is DEFERRED and the walk goes on: no node is over-committed; not with the other two flags).  torch CUDA tensors on
+        this evaluator's device, all [p]:
         bindings int32, requests int64, ok uint8/bool or None (= every POST landed), status_out int32 or None.  Enqueued on `stream`
         (default: torch's current stream) behind whatever wrote `bindings` there; the host does not wait."""
         import torch

@@ -43,6 +43,7 @@ pub const KSCHED_WANT_FIT_MASK: u32 = 0x20;
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
 pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
+pub const KSCHED_APPLY_WHILE_FIT: u32 = 0x08; // per node in pod order while the pods still fit; an older library answers KSCHED_E_INVAL
 pub const KSCHED_APPLY_APPLIED: c_int = 0; // ksched_apply_bindings_device per-pod status
 pub const KSCHED_APPLY_UNBOUND: c_int = 1;
 pub const KSCHED_APPLY_NOT_OK: c_int = 2;
@@ -292,6 +293,7 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_WANT_FIT_MASK", KSCHED_WANT_FIT_MASK as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
+        ("KSCHED_APPLY_WHILE_FIT", KSCHED_APPLY_WHILE_FIT as i64),
         ("KSCHED_APPLY_APPLIED", KSCHED_APPLY_APPLIED as i64),
         ("KSCHED_APPLY_UNBOUND", KSCHED_APPLY_UNBOUND as i64),
         ("KSCHED_APPLY_NOT_OK", KSCHED_APPLY_NOT_OK as i64),

@@ -13,7 +13,9 @@ apply has just written, so a column left stale shows as a few wrong bindings; th
 the latter followed by a sharded apply of the gathered bindings over the same replicas and a second sequence on the columns that apply left (no
 ksched_set_nodes in between); the wide cases take k_pick_spread's two-pass form, with draws that arrive out of chunk order,
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
-ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts),
+ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts; about one apply in four with KSCHED_APPLY_WHILE_FIT, against
+tests/admit_ref.py -- the sharded entry point must then refuse with KSCHED_E_UNSUPPORTED and leave every replica as it was; tallies
+'apply-while-fit', 'apply-while-fit-deferred' for those that deferred a pod, 'while-fit-refused-sharded'),
 the two halves of ksched_eval over 1 .. 5 row shards (ksched_shard_bounds / ksched_eval_begin / ksched_eval_end) and -- with the test hooks on
 (KSCHED_TEST_HOOKS=1 KSCHED_RCCL_LIB=tests/cpp/libfake_rccl.so) -- the whole multi-device sequence over 2 .. 4 evaluators on the one GPU:
 ksched_comm_create_local, ksched_eval_begin on every replica, ksched_gather_buffer, ksched_allgather_bindings_local, ksched_eval_end(gathered_0).
@@ -37,6 +39,7 @@ from oracle import capi
 # the exact-integer apply rule (oracle_ref.apply_bindings_exact) under the name the GPU tests import it by: through that name the tool
 # also runs with an oracle/ that predates the shared restatement
 from tests.test_gpu_apply_bindings import restate as apply_bindings_exact
+from tests.admit_ref import apply_while_fit_exact  # KSCHED_APPLY_WHILE_FIT restated
 from tests.test_gpu_node_labels import apply_rows  # the columns after ksched_update_node_labels: a node listed twice takes its last row
 from tests.uniform_ref import uniform_pick  # KSCHED_PICK_UNIFORM restated
 from tests.spread_ref import best_of, spread_candidates_listed  # KSCHED_PICK_SPREAD restated: every draw's candidate, the best of them
@@ -127,7 +130,13 @@ def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm, relabelled=False)
     P, N = bindings.shape[0], cpu.shape[0]
     okv = np.where(r.random(P) < 0.15, 0, r.integers(1, 256, P)).astype(np.uint8) if r.random() < 0.5 else None
     af = int(r.choice([0, L.APPLY_FIRST_PER_NODE])) | (L.APPLY_RELEASE if r.random() < 0.2 else 0)
-    ncpu, nmem, want_st = apply_bindings_exact(cpu, mem, bindings, rc, rm, okv, af)
+    # (a decision added after the sequence of `r` was fixed: its own generator, one per apply of the case)
+    admit = np.random.default_rng([cs, 0xAD3, picks.get("apply", 0)]).random() < 0.25
+    if admit:
+        af = L.APPLY_WHILE_FIT
+        ncpu, nmem, want_st = apply_while_fit_exact(cpu, mem, bindings, rc, rm, okv)
+    else:
+        ncpu, nmem, want_st = apply_bindings_exact(cpu, mem, bindings, rc, rm, okv, af)
     dev = torch.device("cuda:0")
     bt, rct, rmt = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (bindings, rc, rm))
     okt = None if okv is None else torch.from_numpy(okv).to(dev)
@@ -138,12 +147,24 @@ def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm, relabelled=False)
         for e in reps:
             e.set_nodes(cpu, mem, lab, taints)
         cut = [0] + sorted(int(x) for x in r.integers(0, P + 1, n_sh - 1)) + [P]
-        st_sh = sharded_apply(reps, comms, cut, bt, rct, rmt, okt, af)
+        if admit:  # the sharded entry point refuses the flag and leaves every replica as it was
+            try:
+                sharded_apply(reps, comms, cut, bt, rct, rmt, okt, af)
+                refused = False
+            except L.KschedError as e:
+                refused = e.code == L.E_UNSUPPORTED
+            if not (refused and all(np.array_equal(c_[0], cpu) and np.array_equal(c_[1], mem) for c_ in (e.read_nodes() for e in reps))):
+                bad += 1
+                print(f"FAIL sharded refusal of APPLY_WHILE_FIT case seed {cs}: N={N} P={P} cuts={cut}", flush=True)
+            picks["while-fit-refused-sharded"] = picks.get("while-fit-refused-sharded", 0) + 1
+            reps = []
+        st_sh = sharded_apply(reps, comms, cut, bt, rct, rmt, okt, af) if reps else None
         cols = [e.read_nodes() for e in reps]
-        if not (np.array_equal(st_sh, want_st) and all(np.array_equal(c_[0], ncpu) and np.array_equal(c_[1], nmem) for c_ in cols)):
+        if reps and not (np.array_equal(st_sh, want_st) and all(np.array_equal(c_[0], ncpu) and np.array_equal(c_[1], nmem) for c_ in cols)):
             bad += 1
             print(f"FAIL sharded apply case seed {cs}: N={N} P={P} flags={af} ok={okv is not None} cuts={cut}", flush=True)
-        picks[f"sharded-apply-over-{n_sh}"] = picks.get(f"sharded-apply-over-{n_sh}", 0) + 1
+        if reps:
+            picks[f"sharded-apply-over-{n_sh}"] = picks.get(f"sharded-apply-over-{n_sh}", 0) + 1
     else:
         reps = []
     st = torch.full((P,), -7, dtype=torch.int32, device=dev)
@@ -159,6 +180,10 @@ def apply_step(r, cs, cpu, mem, lab, taints, bindings, rc, rm, relabelled=False)
         bad += 1
         print(f"FAIL sharded apply index case seed {cs}: N={N} P={P} flags={af} replicas={len(reps)}", flush=True)
     picks["apply"] = picks.get("apply", 0) + 1
+    if admit:
+        picks["apply-while-fit"] = picks.get("apply-while-fit", 0) + 1
+        if (want_st == L.APPLY_DEFERRED).any():
+            picks["apply-while-fit-deferred"] = picks.get("apply-while-fit-deferred", 0) + 1
     cpu[:], mem[:] = ncpu, nmem
     return bad
 
