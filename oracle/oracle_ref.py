@@ -528,8 +528,11 @@ def apply_bindings_exact(cpu, mem, bindings, req_cpu, req_mem, ok=None, flags: i
     A pod is eligible when 0 <= binding < n and ok (when given) is nonzero.  Without APPLY_FIRST_PER_NODE every eligible pod is
     accepted; with it, per node only the lowest eligible pod index (the others report DEFERRED).  Per node the accepted pods' requests
     are summed, and old - sum (old + sum with APPLY_RELEASE) replaces `available` when both resources stay inside int64; otherwise the
-    node keeps both old values and its accepted pods report OVERFLOW."""
+    node keeps both old values and its accepted pods report OVERFLOW.  Any other flag bit is another rule (KSCHED_APPLY_WHILE_FIT is
+    tests/admit_ref.py): ValueError, never a silent restatement of flags = 0."""
     import numpy as np
+    if flags & ~(APPLY_FIRST_PER_NODE | APPLY_RELEASE):
+        raise ValueError(f"apply_bindings_exact restates FIRST_PER_NODE and RELEASE only: flags {flags:#x}")
     cpu, mem = [int(x) for x in cpu], [int(x) for x in mem]
     b_, rc, rm = np.asarray(bindings).tolist(), np.asarray(req_cpu).tolist(), np.asarray(req_mem).tolist()
     okl = None if ok is None else np.asarray(ok).tolist()

@@ -8,6 +8,9 @@ either resource past INT64_MAX (a negative request) reports OVERFLOW and changes
 and the walk goes on behind it.  No numpy arithmetic: nothing can wrap."""
 import numpy as np
 
+from oracle.oracle_ref import APPLY_FIRST_PER_NODE, APPLY_RELEASE, apply_bindings_exact
+
+WHILE_FIT = 0x08  # KSCHED_APPLY_WHILE_FIT
 APPLIED, UNBOUND, NOT_OK, DEFERRED, OVERFLOW, BAD_NODE = 0, 1, 2, 3, 4, 5
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
 
@@ -37,6 +40,16 @@ def apply_while_fit_exact(cpu, mem, bindings, req_cpu, req_mem, ok=None):
     return np.array(cpu, dtype=np.int64).reshape(-1), np.array(mem, dtype=np.int64).reshape(-1), np.array(status, dtype=np.int32).reshape(-1)
 
 
+def apply_exact(cpu, mem, bindings, req_cpu, req_mem, ok, flags):
+    """one apply restated by its flags: WHILE_FIT alone -> apply_while_fit_exact, any combination of FIRST_PER_NODE / RELEASE ->
+    oracle_ref.apply_bindings_exact; everything else (WHILE_FIT with another flag, an unknown bit) is refused, as the library refuses it"""
+    if flags == WHILE_FIT:
+        return apply_while_fit_exact(cpu, mem, bindings, req_cpu, req_mem, ok)
+    if flags & ~(APPLY_FIRST_PER_NODE | APPLY_RELEASE):
+        raise ValueError(f"no restatement of an apply with flags {flags:#x}")
+    return apply_bindings_exact(cpu, mem, bindings, req_cpu, req_mem, ok, flags)
+
+
 def longest_segment(bindings, n, ok=None):
     """the most eligible pods bound to one node"""
     b = np.asarray(bindings)
@@ -44,12 +57,15 @@ def longest_segment(bindings, n, ok=None):
     return int(np.bincount(b[elig], minlength=1).max()) if elig.any() else 0
 
 
-def admitted_behind_deferred(bindings, status):
-    """pods admitted although a lower pod of their node was DEFERRED: the skip rule seen"""
+def admitted_behind_deferred(bindings, status, nodes=None):
+    """pods admitted although a lower pod of their node was DEFERRED: the skip rule seen.  nodes: a set that receives the nodes where
+    that happened"""
     seen, k = set(), 0
     for b, s in zip(np.asarray(bindings).tolist(), np.asarray(status).tolist()):
         if s == DEFERRED:
             seen.add(b)
         elif s == APPLIED and b in seen:
             k += 1
+            if nodes is not None:
+                nodes.add(b)
     return k

@@ -6,7 +6,8 @@ path after ksched_apply_bindings_device on one ctx.
 An apply writes `available` in three places -- the columns, the node records (read by the "select" pick, the riding pick in its waves
 form, ksched_explain and the list-key best fit) and the dirty tiles of the bitmap index -- so after each apply every path that reads any
 of them is run and compared with the oracle (capi.eval_encoded, and for ksched_explain the reason rebuilt from single-predicate oracle
-masks) on the columns the exact-integer restatement (oracle_ref.apply_bindings_exact) gives.  Every mask word, fit-mask word, binding and
+masks) on the columns the exact-integer restatement gives (tests/admit_ref.apply_exact: by the apply's flags, oracle_ref.apply_bindings_exact
+or, for KSCHED_APPLY_WHILE_FIT, apply_while_fit_exact).  Every mask word, fit-mask word, binding and
 reason is compared.  The spread pick (KSCHED_PICK_SPREAD) is the one pick whose bindings depend on the VALUES of the columns and not only
 on which nodes are feasible: its expected bindings are tests/spread_ref.py on the oracle's mask and on the restated columns, so a column
 left stale by an apply on some stream shows as a few wrong bindings.  A case prints "ok <case>" as its last line when all its checks passed.
@@ -14,6 +15,13 @@ left stale by an apply on some stream shows as a few wrong bindings.  A case pri
 The sequence of a case (snapshots, rounds, which pick's bindings an apply takes, the input conditions) is walk_single, which takes the
 device as three callables: tests/test_apply_paths_host.py walks it with the oracle and the restatements alone and asserts the same
 input conditions without a GPU.
+
+KSCHED_APPLY_WHILE_FIT has a device pipeline of its own (keys, the merge sort, a wave per node, the dirty tiles re-indexed) that writes the
+same three places, so it stands in every case: the admit round that ends every node count of walk_single (the whole matrix after it; floors
+on deferrals, on pods admitted behind a deferred one and on what the two other rules would have left: admit_round_conditions); in
+case_sizes behind two applies and two updates with no host wait, once outgrowing the admit scratch behind a queued admit, on odd steps with
+negative requests (sizes_step); in case_large first, 600 000 pods with segments of more than 10 000 (large_plan).  sizes_step and
+large_plan need no device and assert their input conditions before anything runs on one; tests/test_apply_paths_host.py calls them too.
 """
 from __future__ import annotations
 
@@ -26,7 +34,8 @@ import torch
 from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator,
                                              KschedError, _lib, synth, unpack_mask)
 from oracle import capi
-from oracle.oracle_ref import apply_bindings_exact
+from oracle.oracle_ref import apply_bindings_exact  # (the two other rules on an admit round's inputs: admit_round_conditions)
+from tests.admit_ref import admitted_behind_deferred, apply_exact, longest_segment
 from tests.spread_ref import spread_pick_blocks
 from tests.test_gpu_apply_bindings import random_bindings
 from tests.uniform_ref import uniform_pick_blocks
@@ -311,14 +320,17 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
     return out_b
 
 
-def apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, what):
-    """one apply on `ev` against the restatement: columns, statuses, the index (== a fresh ksched_set_nodes on `ref`; (0, 0) unindexed)"""
+def apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, what, expect=None):
+    """one apply on `ev` against the restatement (apply_exact by its flags; `expect`: its result where the caller has it already):
+    columns, statuses, the index (== a fresh ksched_set_nodes on `ref`; (0, 0) unindexed; what it was where no column moved)"""
     P = len(b)
+    # (first: flags without a restatement never reach the device)
+    ncpu, nmem, want = expect if expect is not None else apply_exact(cpu, mem, b, S["rc"][:P], S["rm"][:P], ok, flags)
+    ck0 = ev.index_checksum()
     st = torch.full((P,), -7, dtype=torch.int32, device=DEV)
     ev.apply_bindings_device(t(b, np.int32), t(S["rc"][:P], np.int64), t(S["rm"][:P], np.int64), None if ok is None else t(ok, np.uint8),
                              flags, st)
     torch.cuda.synchronize()
-    ncpu, nmem, want = apply_bindings_exact(cpu, mem, b, S["rc"][:P], S["rm"][:P], ok, flags)
     assert np.array_equal(st.cpu().numpy(), want), f"{what}: statuses"
     got = ev.read_nodes()
     assert np.array_equal(got[0], ncpu) and np.array_equal(got[1], nmem), f"{what}: columns"
@@ -327,6 +339,8 @@ def apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, what):
     assert ck == ref.index_checksum(), f"{what}: index checksum"
     if not S["indexed"]:
         assert ck == (0, 0), f"{what}: an unindexed snapshot has an index checksum {ck}"
+    if np.array_equal(ncpu, cpu) and np.array_equal(nmem, mem):  # an apply that admits nobody leaves the index as it was
+        assert ck == ck0, f"{what}: the index checksum moved although no column did"
     return ncpu, nmem, want
 
 
@@ -340,17 +354,54 @@ FORMS = [("real", 0, False), ("random", FPN, True), ("real", REL, True), ("rando
 PICKS = ("spread", "sampled", "uniform")
 
 
+def admit_round_conditions(N, src, b, ok, st, cpu0, mem0, cpu, mem, rc, rm, stale, what):
+    """the input conditions of the WHILE_FIT round of walk_single at N nodes, from the restatement alone (bindings b, ok or None, restated
+    statuses st, the columns before and after): prints the counts, then asserts the floors -- an admit round that admits everything, or
+    defers nothing behind which a pod is admitted, or leaves what another rule leaves, compares nothing that is the admission rule's own.
+    A node count without conditions of its own is refused: give it some."""
+    counts = np.bincount(st, minlength=6)
+    longest, behind = longest_segment(b, N, ok), admitted_behind_deferred(b, st)
+    plain = apply_bindings_exact(cpu0, mem0, b, rc, rm, ok, 0)
+    first = apply_bindings_exact(cpu0, mem0, b, rc, rm, ok, FPN)
+    not_plain = not (np.array_equal(plain[0], cpu) and np.array_equal(plain[1], mem))
+    not_first = not (np.array_equal(first[0], cpu) and np.array_equal(first[1], mem))
+    unchanged = np.array_equal(cpu, cpu0) and np.array_equal(mem, mem0)
+    print(f"{what}: statuses (applied, unbound, not ok, deferred, overflow, bad node) = {counts.tolist()}, longest segment {longest}, "
+          f"{behind} admitted behind a deferred pod of their node, columns as after flags=0: {not not_plain}, as after FIRST_PER_NODE: {not not_first}"
+          + ("" if stale is None else f", the columns from before this admit move {stale} spread bindings (d = 5)"))
+    n_app, n_def = int(counts[_lib.APPLY_APPLIED]), int(counts[_lib.APPLY_DEFERRED])
+    eligible = int(((b >= 0) & (b < N) & (True if ok is None else ok != 0)).sum())
+    if N == 1:  # random: one segment across sort runs and 25 chunks, onto a node the earlier rounds exhausted
+        assert src == "random" and longest > 1024, f"{what}: longest segment {longest}"
+        assert n_def == eligible == longest and n_app == 0, f"{what}: {n_def} of {eligible} eligible pods deferred, {n_app} admitted"
+        assert unchanged, f"{what}: the restated columns moved"
+    elif N == 63:  # real
+        assert src == "real" and n_def >= 40 and behind >= 15 and not_plain and not_first and stale >= 1, what
+    elif N == 1025:  # random
+        assert src == "random" and all(counts[s] > 0 for s in range(6) if s != _lib.APPLY_OVERFLOW), f"{what}: {counts.tolist()}"
+        assert longest > 64 and n_def >= 150 and behind >= 15 and not_plain and not_first, what
+    elif N == 4097:  # real
+        assert src == "real" and n_app >= 1000 and stale >= 1, what
+    elif N == 50_000:  # random
+        assert src == "random" and n_def >= 10 and not_plain, what
+    else:
+        raise AssertionError(f"{what}: no input conditions are stated for an admit round at {N} nodes")
+
+
 def walk_single(spec, begin, matrix, apply):
     """case_single's sequence with the device behind three callables: begin(S, cpu, mem, what) loads the snapshot; matrix(S, cpu, mem,
     what, rng, hand_on=, input_condition=) checks every path and -> the bindings of the pick `hand_on` names; apply(S, cpu, mem, b, ok,
     flags, what) -> (cpu, mem, statuses) after the apply.  Per node count: the matrix, then rounds of [apply (the previous evaluation's
-    bindings or random ones) -> the matrix].
+    bindings or random ones) -> the matrix], then the admit round: one more [apply with WHILE_FIT -> the matrix].
     Real bindings come from the spread, the sampled and the uniform pick in turn over the case's real applies (the rounds with i + r
     even): the uniform pick binds more pods and does not favour the lowest feasible nodes, the spread pick's bindings are the ones whose
     apply moves the columns its own next evaluation ranks by.  Asserted here, so with or without a device: each of the three hands on
     in both classes of node counts (below 1025, and from 1025 on, where the input conditions hold); and at every node count from 1025
     on, summed over its applies of real bindings, the d = 5 spread restatement after the apply differs between the columns after and the
-    columns before it for at least one pod (stale_spread_bindings) -- a stale column cannot pass."""
+    columns before it for at least one pod (stale_spread_bindings) -- a stale column cannot pass.
+    The admit round takes real bindings without ok at odd i (from PICKS[i % 3]: a hand-on outside the turn above, which it does not
+    move) and random ones with ok at even i; every round before it draws, binds and applies what it did without it.  Its conditions
+    are admit_round_conditions."""
     kind, rounds = spec["kind"], spec.get("rounds", 2)
     reals = 0
     handed = {}
@@ -360,10 +411,13 @@ def walk_single(spec, begin, matrix, apply):
         cpu, mem = S["cpu"], S["mem"]
         begin(S, cpu, mem, f"{kind} N={N}")
         rng = np.random.default_rng(N)
+        admit_real = i % 2 == 1
 
         def hand_on(r):  # the pick that hands its bindings to round r; None when that round applies random ones (or does not exist)
             nonlocal reals
-            if r >= rounds or FORMS[(i + r) % len(FORMS)][0] != "real":
+            if r == rounds:  # the admit round: not one of the case's real applies
+                return PICKS[i % len(PICKS)] if admit_real else None
+            if r > rounds or FORMS[(i + r) % len(FORMS)][0] != "real":
                 return None
             reals += 1
             handed.setdefault(N >= 1025, []).append(PICKS[(reals - 1) % len(PICKS)])
@@ -388,6 +442,15 @@ def walk_single(spec, begin, matrix, apply):
             bind = matrix(S, cpu, mem, what, rng, hand_on=hand_on(r + 1))
         assert applied > 0, f"{kind} N={N}: no pod was applied"
         assert stale > 0 or N < 1025, f"{kind} N={N}: no spread binding depends on what this node count's applies changed"
+        # the admit round
+        src = "real" if admit_real else "random"
+        b, ok = (bind, None) if admit_real else random_bindings(rng, N, P)
+        what = f"{kind} N={N} admit round ({src} bindings, flags={_lib.APPLY_WHILE_FIT}, ok={not admit_real})"
+        cpu0, mem0 = cpu, mem
+        cpu, mem, st = apply(S, cpu, mem, b, ok, _lib.APPLY_WHILE_FIT, what)
+        admit_round_conditions(N, src, b, ok, st, cpu0, mem0, cpu, mem, S["rc"][:P], S["rm"][:P],
+                               stale_spread_bindings(S, cpu, mem, cpu0, mem0) if admit_real else None, what)
+        matrix(S, cpu, mem, what, rng, hand_on=None)
     for big, picks in handed.items():  # (a class with fewer real applies than picks cannot see them all: the committed spec has 3 and 5, asserted
         # by tests/test_apply_paths_host.py on what is returned here)
         assert len(picks) < len(PICKS) or set(picks) == set(PICKS), f"{kind}: real bindings came from {picks} (node counts from 1025 on: {big})"
@@ -419,38 +482,96 @@ def case_single(spec):
     ref.close()
 
 
+SIZES_PODS, SIZES_BIG = 3000, 4  # pods per batch of case_sizes; the second admit at 4097 nodes has SIZES_BIG times as many
+
+
+def sizes_step(step, N):
+    """what step `step` of case_sizes (N nodes) enqueues, and what the restatements make of it, without a device:
+    -> dict(S, applies=[(bindings, ok or None, flags, req_cpu, req_mem, restated statuses)] in order, updates={k: (idx, cpu, mem)} -- update
+    k goes behind apply k -- and cpu / mem, the restated columns after all of it).  Applies 0 and 1 and update 0 are what they were before
+    the admits came (the same draws in the same order); update 1 sets up to 50 of the nodes the third batch binds; apply 2 is that batch
+    with WHILE_FIT (ok on even steps; on odd steps a twentieth of its pods carry negative requests, so what is left of a node grows
+    inside a chunk of the walk and the shrink-only shortcut must stay off); at 4097 nodes apply 3 is a WHILE_FIT batch of SIZES_BIG x SIZES_PODS pods -- past the 25 % headroom
+    the admit scratch got with apply 2, so both of its ping-pong sets are reallocated behind a queued admit.
+    Asserted here, from the restatement: every WHILE_FIT apply admits a pod (but on one node, which the second update may leave with
+    nothing), at 300 nodes and at 1 it defers 100 pods or more, on the odd steps a pod or more is admitted only into what a pod before
+    it gave back, and the big one has APPLIED, DEFERRED, UNBOUND and BAD_NODE."""
+    P, WF = SIZES_PODS, _lib.APPLY_WHILE_FIT
+    S = snapshot("taints", N, P, 0xC0 + step)
+    cpu, mem = S["cpu"], S["mem"]
+    rng = np.random.default_rng(step)
+
+    def some_of(b):  # up to 50 of the nodes `b` binds, and new values for them
+        touched = np.unique(b[(b >= 0) & (b < N)])
+        idx = rng.choice(touched, min(len(touched), 50), replace=False).astype(np.uint32) if len(touched) else np.zeros(0, np.uint32)
+        return idx, rng.integers(-1000, 64_000, idx.size).astype(np.int64), rng.integers(0, 1 << 40, idx.size).astype(np.int64)
+
+    b1, ok1 = random_bindings(rng, N, P)
+    b2, ok2 = random_bindings(rng, N, P)
+    updates = {0: some_of(b1)}
+    f1, f2 = (FPN, 0) if step % 2 == 0 else (0, FPN | REL)
+    b3, ok3 = random_bindings(rng, N, P)
+    updates[1] = some_of(b3)
+    rc3, rm3 = S["rc"], S["rm"]
+    if step % 2:  # odd steps: a twentieth of the third batch's pods give back what they name (negative requests: R grows inside a chunk)
+        back = rng.random(P) < 0.05
+        rc3, rm3 = np.where(back, -rc3, rc3), np.where(back, -rm3, rm3)
+    batches = [(b1, ok1, f1, S["rc"], S["rm"]), (b2, None, f2, S["rc"], S["rm"]), (b3, ok3 if step % 2 == 0 else None, WF, rc3, rm3)]
+    if N == 4097:
+        b4, ok4 = random_bindings(rng, N, SIZES_BIG * P)
+        batches.append((b4, ok4, WF, np.tile(S["rc"], SIZES_BIG), np.tile(S["rm"], SIZES_BIG)))
+    applies, what = [], f"step {step} N={N}"
+    for k, (b, ok, flags, rc, rm) in enumerate(batches):
+        cpu0, mem0 = cpu, mem
+        cpu, mem, w = apply_exact(cpu, mem, b, rc, rm, ok, flags)
+        applies.append((b, ok, flags, rc, rm, w))
+        counts = np.bincount(w, minlength=6)
+        if flags == WF:
+            print(f"{what}: admit of {len(b)} pods (ok={ok is not None}): statuses (applied, unbound, not ok, deferred, overflow, bad node) = "
+                  f"{counts.tolist()}, longest segment {longest_segment(b, N, ok)}")
+            assert counts[_lib.APPLY_APPLIED] >= 1 or N == 1, f"{what}: admit {k} admits nobody"
+            assert counts[_lib.APPLY_DEFERRED] >= 100 or N not in (300, 1), f"{what}: admit {k} defers {counts[_lib.APPLY_DEFERRED]}"
+            if (rc < 0).any():  # pods admitted only because a pod before them gave back: deferred once the negative requests are zeroed
+                grown = int(((w == _lib.APPLY_APPLIED) & (rc >= 0) & (apply_exact(cpu0, mem0, b, np.maximum(rc, 0), np.maximum(rm, 0), ok, flags)[2]
+                                                                      == _lib.APPLY_DEFERRED)).sum())
+                print(f"{what}: {int((rc < 0).sum())} pods give back, {grown} pods are admitted into what was given back")
+                assert grown >= 1, f"{what}: no admission depends on a negative request"
+            if k == 3:
+                assert all(counts[s] > 0 for s in (_lib.APPLY_APPLIED, _lib.APPLY_DEFERRED, _lib.APPLY_UNBOUND, _lib.APPLY_BAD_NODE)), f"{what}: {counts.tolist()}"
+        else:
+            assert counts[_lib.APPLY_APPLIED] >= 1, what
+        if k in updates and updates[k][0].size:
+            cpu[updates[k][0]], mem[updates[k][0]] = updates[k][1], updates[k][2]
+    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem)
+
+
 def case_sizes(spec):
     """one ctx through snapshots of 50 000 -> 300 -> 4097 -> 1 -> 60 000 nodes (the last one past the apply scratch's size): after each
-    ksched_set_nodes an apply, an update of nodes in the tiles it touched and a second apply, enqueued with no host wait in between;
-    then the columns, the statuses, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused evaluation
-    with the sampled pick in its waves form"""
+    ksched_set_nodes what sizes_step lists -- an apply, an update of nodes in the tiles it touched, a second apply, a second update, an
+    apply with WHILE_FIT (at 4097 nodes a second, four times as long, straight behind it) -- enqueued with no host wait in between; then
+    the statuses of every apply, the columns, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused
+    evaluation with the sampled pick in its waves form"""
+    plans = [sizes_step(step, N) for step, N in enumerate(spec["nodes"])]  # (every input condition, before anything runs on the device)
+    assert sum(len(q["applies"]) == 4 for q in plans) == 1, "no step reallocates the admit scratch"
     ev, ref = Evaluator(0), Evaluator(0)
     seen = set()
-    for step, N in enumerate(spec["nodes"]):
-        P = 3000
-        S = snapshot("taints", N, P, 0xC0 + step)
-        cpu, mem = S["cpu"], S["mem"]
-        set_nodes(ev, S, cpu, mem)
-        rng = np.random.default_rng(step)
-        b1, ok1 = random_bindings(rng, N, P)
-        b2, ok2 = random_bindings(rng, N, P)
-        touched = np.unique(b1[(b1 >= 0) & (b1 < N)])
-        idx = rng.choice(touched, min(len(touched), 50), replace=False).astype(np.uint32) if len(touched) else np.zeros(0, np.uint32)
-        ucpu, umem = rng.integers(-1000, 64_000, idx.size).astype(np.int64), rng.integers(0, 1 << 40, idx.size).astype(np.int64)
-        f1, f2 = (FPN, 0) if step % 2 == 0 else (0, FPN | REL)
-        st1, st2 = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
-        rc_t, rm_t = t(S["rc"], np.int64), t(S["rm"], np.int64)
-        ev.apply_bindings_device(t(b1, np.int32), rc_t, rm_t, t(ok1, np.uint8), f1, st1)
-        if idx.size:
-            ev.update_nodes(idx, ucpu, umem)
-        ev.apply_bindings_device(t(b2, np.int32), rc_t, rm_t, None, f2, st2)
+    for step, (N, q) in enumerate(zip(spec["nodes"], plans)):
+        S = q["S"]
+        set_nodes(ev, S, S["cpu"], S["mem"])
+        sts, keep = [], []
+        for k, (b, ok, flags, rc, rm, _) in enumerate(q["applies"]):
+            st = torch.full((len(b),), -7, dtype=torch.int32, device=DEV)
+            args = (t(b, np.int32), t(rc, np.int64), t(rm, np.int64), None if ok is None else t(ok, np.uint8))
+            keep.append(args)  # (inputs stay alive until the host has waited)
+            ev.apply_bindings_device(*args, flags, st)
+            sts.append(st)
+            if k in q["updates"] and q["updates"][k][0].size:
+                ev.update_nodes(*q["updates"][k])
         torch.cuda.synchronize()
         what = f"step {step} N={N}"
-        cpu, mem, w1 = apply_bindings_exact(cpu, mem, b1, S["rc"], S["rm"], ok1, f1)
-        cpu[idx], mem[idx] = ucpu, umem
-        cpu, mem, w2 = apply_bindings_exact(cpu, mem, b2, S["rc"], S["rm"], None, f2)
-        assert np.array_equal(st1.cpu().numpy(), w1) and np.array_equal(st2.cpu().numpy(), w2), f"{what}: statuses"
-        assert (w1 == _lib.APPLY_APPLIED).any() and (w2 == _lib.APPLY_APPLIED).any(), what
+        for k, (st, a) in enumerate(zip(sts, q["applies"])):
+            assert np.array_equal(st.cpu().numpy(), a[5]), f"{what}: statuses of apply {k} (flags={a[2]})"
+        cpu, mem = q["cpu"], q["mem"]
         got = ev.read_nodes()
         assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem), f"{what}: columns"
         set_nodes(ref, S, cpu, mem)
@@ -483,23 +604,53 @@ def large_batch(rng, N, P, far):
     return b, ok
 
 
-def case_large(spec):
-    """one apply of P >= 600 000 pods (more than one stride of the pod kernels' grid, 2048 x 256 threads) for every flag set"""
-    N, P = 5000, spec["pods"]
-    far = 2048 * 256 + 1000
+LARGE_NODES, LARGE_FAR = 5000, 2048 * 256 + 1000
+
+
+def large_plan(P):
+    """the applies of case_large and what the restatements make of them, without a device: -> (S, [(flags, bindings, ok or None, (cpu, mem,
+    statuses) restated)]).  First, on the fresh snapshot while the 16 hot nodes (64 .. 79) still have room, a WHILE_FIT batch of its own
+    generator -- so the four batches behind it are what they were before it came -- then flags 0, FIRST_PER_NODE, RELEASE and both, each
+    from the columns the one before left.  Asserted here: the admit's longest segment is past 10 000 pods, 64 or more pods past
+    LARGE_FAR are admitted, 1000 or more deferred, and on 8 or more of the hot nodes a pod is admitted behind a deferred one; of the
+    other four, what case_large always asserted."""
+    N, far = LARGE_NODES, LARGE_FAR
     S = snapshot("taints", N, P, 0x1A)
-    ev, ref = Evaluator(0), Evaluator(0)
     cpu, mem = S["cpu"], S["mem"]
-    set_nodes(ev, S, cpu, mem)
+    plan = []
+    b, ok = large_batch(np.random.default_rng([6, 0xAD]), N, P, far)
+    cpu, mem, want = exp = apply_exact(cpu, mem, b, S["rc"], S["rm"], ok, _lib.APPLY_WHILE_FIT)
+    plan.append((_lib.APPLY_WHILE_FIT, b, ok, exp))
+    where, counts = set(), np.bincount(want, minlength=6)
+    behind, longest, late = admitted_behind_deferred(b, want, where), longest_segment(b, N, ok), int((want[far:] == _lib.APPLY_APPLIED).sum())
+    hot = sorted(x for x in where if 64 <= x < 80)
+    print(f"P={P} admit: statuses (applied, unbound, not ok, deferred, overflow, bad node) = {counts.tolist()}, longest segment {longest}, "
+          f"{late} pods past pod {far} admitted, {behind} admitted behind a deferred pod of their node on {len(where)} nodes, hot ones among them: {hot}")
+    assert longest > 10_000 and late >= 64 and counts[_lib.APPLY_DEFERRED] >= 1000 and len(hot) >= 8, "the admit of the large case"
     rng = np.random.default_rng(6)
     for flags in (0, FPN, REL, FPN | REL):
         b, ok = large_batch(rng, N, P, far)
-        cpu, mem, want = apply_and_check(ev, ref, S, cpu, mem, b, ok if flags != REL else None, flags, f"P={P} flags={flags}")
+        ok = ok if flags != REL else None
+        cpu, mem, want = exp = apply_exact(cpu, mem, b, S["rc"], S["rm"], ok, flags)
+        plan.append((flags, b, ok, exp))
         assert (want[far:] == _lib.APPLY_APPLIED).sum() >= 64, flags
         if flags & FPN:
             for node in range(64):
-                elig = np.nonzero((b == node) & ((ok != 0) if flags != REL else True))[0]
+                elig = np.nonzero((b == node) & ((ok != 0) if ok is not None else True))[0]
                 assert len(elig) and elig[0] >= far and want[elig[0]] == _lib.APPLY_APPLIED, (flags, node)
+    return S, plan
+
+
+def case_large(spec):
+    """one apply of P >= 600 000 pods (more than one stride of the pod kernels' grid, 2048 x 256 threads; ten merge passes of the admit's
+    sort) for WHILE_FIT and then every other flag set: large_plan"""
+    P = spec["pods"]
+    S, plan = large_plan(P)  # (every input condition, before anything runs on the device)
+    ev, ref = Evaluator(0), Evaluator(0)
+    cpu, mem = S["cpu"], S["mem"]
+    set_nodes(ev, S, cpu, mem)
+    for flags, b, ok, exp in plan:
+        cpu, mem, _ = apply_and_check(ev, ref, S, cpu, mem, b, ok, flags, f"P={P} flags={flags}", expect=exp)
     ev.close()
     ref.close()
 

@@ -1,10 +1,11 @@
 """tests/admit_ref.py (KSCHED_APPLY_WHILE_FIT restated) against answers worked by hand from the header's contract, and against the two
 older rules' restatement (oracle_ref.apply_bindings_exact) where the three must agree.  No GPU."""
 import numpy as np
+import pytest
 
-from oracle.oracle_ref import APPLY_FIRST_PER_NODE, apply_bindings_exact
-from tests.admit_ref import (APPLIED, BAD_NODE, DEFERRED, I64_MAX, I64_MIN, NOT_OK, OVERFLOW, UNBOUND, admitted_behind_deferred,
-                             apply_while_fit_exact, longest_segment)
+from oracle.oracle_ref import APPLY_FIRST_PER_NODE, APPLY_RELEASE, apply_bindings_exact
+from tests.admit_ref import (APPLIED, BAD_NODE, DEFERRED, I64_MAX, I64_MIN, NOT_OK, OVERFLOW, UNBOUND, WHILE_FIT, admitted_behind_deferred,
+                             apply_exact, apply_while_fit_exact, longest_segment)
 
 A, D, O = APPLIED, DEFERRED, OVERFLOW
 
@@ -36,6 +37,8 @@ def test_skip_not_stop():
     c, m, st = run([10], [100], [0, 0, 0], [5, 9, 3], [1, 1, 1])
     assert st == [A, D, A] and c == [2] and m == [98]
     assert admitted_behind_deferred([0, 0, 0], st) == 1
+    where = set()
+    assert admitted_behind_deferred([1, 0, 1, 0, 1, 2, 2], [A, D, D, A, A, A, D], where) == 2 and where == {0, 1}
 
 
 def test_exact_fill():
@@ -113,3 +116,39 @@ def test_with_one_fitting_pod_per_node_it_is_first_per_node():
     for g, w in zip(got, want):
         assert np.array_equal(g, w)
     assert set(want[2].tolist()) == {APPLIED, UNBOUND, NOT_OK, BAD_NODE}
+
+
+def tight_case():
+    """three pods onto one node of which the middle one does not fit: the three rules leave three different columns"""
+    return (np.array([10], dtype=np.int64), np.array([100], dtype=np.int64), np.array([0, 0, 0], dtype=np.int32),
+            np.array([5, 9, 3], dtype=np.int64), np.array([1, 1, 1], dtype=np.int64), np.array([1, 1, 1], dtype=np.uint8))
+
+
+def test_apply_exact_picks_the_rule_by_the_flags():
+    args = tight_case()
+    c, m, st = apply_exact(*args, WHILE_FIT)
+    assert c.tolist() == [2] and m.tolist() == [98] and st.tolist() == [A, D, A]
+    for g, w in zip(apply_exact(*args, WHILE_FIT), apply_while_fit_exact(*args)):
+        assert np.array_equal(g, w)
+    left = {WHILE_FIT: 2}
+    for flags in (0, APPLY_FIRST_PER_NODE, APPLY_RELEASE, APPLY_FIRST_PER_NODE | APPLY_RELEASE):
+        got, want = apply_exact(*args, flags), apply_bindings_exact(*args, flags)
+        for g, w in zip(got, want):
+            assert np.array_equal(g, w) and g.dtype == w.dtype
+        left[flags] = int(got[0][0])
+    assert left == {WHILE_FIT: 2, 0: -7, APPLY_FIRST_PER_NODE: 5, APPLY_RELEASE: 27, APPLY_FIRST_PER_NODE | APPLY_RELEASE: 15}  # no two rules alike
+    assert apply_exact(*args[:5], None, WHILE_FIT)[2].tolist() == [A, D, A]  # ok=None passes through
+
+
+@pytest.mark.parametrize("flags", [WHILE_FIT | APPLY_FIRST_PER_NODE, WHILE_FIT | APPLY_RELEASE, WHILE_FIT | 3, 0x04, 0x10, 0x0C, 1 << 31, -1])
+def test_apply_exact_refuses_every_other_flag_set(flags):
+    with pytest.raises(ValueError):
+        apply_exact(*tight_case(), flags)
+
+
+@pytest.mark.parametrize("flags", [WHILE_FIT, WHILE_FIT | APPLY_FIRST_PER_NODE, WHILE_FIT | APPLY_RELEASE, 0x04, 0x10, 1 << 31])
+def test_the_summed_restatement_refuses_flags_it_does_not_restate(flags):
+    """it used to ignore them: flags = 0x08 gave the flags = 0 rule, which agrees with the admission rule wherever everything fits"""
+    with pytest.raises(ValueError):
+        apply_bindings_exact(*tight_case(), flags)
+    assert apply_bindings_exact(*tight_case(), flags & 3)[2].shape == (3,)  # the same call without the foreign bits is restated

@@ -4,19 +4,21 @@ in place of the device, over the specs the GPU tests pass.  The walks assert wha
 apply at 1025 nodes or more, the d = 5 spread restatement binds 35 % of the pods or more to another node than their candidate 0 (and the
 uniform legs' condition holds); (b) at every such node count the columns from before an apply of real bindings would change at least one
 spread binding, summed over its rounds; and the sampled, the uniform and the spread pick each hand their bindings on.  A change of the
-shapes, the seeds or the rotation that would let the GPU legs pass with stale columns fails here first."""
+shapes, the seeds or the rotation that would let the GPU legs pass with stale columns fails here first.  Likewise the admit legs
+(KSCHED_APPLY_WHILE_FIT): the admit round of every node count with admit_round_conditions' floors, the sizes and the large case's plans
+(sizes_step, large_plan) and the pipe's admit -- an admit that defers nobody where a floor says it must fails here, not on a GPU."""
 import numpy as np
 import pytest
 
-from oracle.oracle_ref import apply_bindings_exact
 from tests import apply_paths_worker as W
-from tests.test_gpu_apply_paths import SINGLE
+from tests.admit_ref import apply_exact
+from tests.test_gpu_apply_paths import LARGE, NODES, SINGLE, SIZES
 from tests.test_gpu_apply_sharded import PATHS_NODES
 
 
 def exact_apply(S, cpu, mem, b, ok, flags, what):
     P = len(b)
-    return apply_bindings_exact(cpu, mem, b, S["rc"][:P], S["rm"][:P], ok, flags)
+    return apply_exact(cpu, mem, b, S["rc"][:P], S["rm"][:P], ok, flags)
 
 
 def restated(S, cpu, mem, what, rng, **kw):
@@ -30,6 +32,34 @@ def test_single_ctx_matrix_inputs(kind, capsys):
     out = capsys.readouterr().out
     print(out)
     assert out.count("the spread pick (d = 5) binds") >= 3 and out.count("would change") >= 8
+    # the admit round of every node count, with the floors walk_single sets on it (admit_round_conditions), printed in words of its own
+    assert [out.count(f"{kind} N={N} admit round (") > 0 for N in NODES] == [True] * len(NODES)
+    assert out.count("statuses (applied, unbound, not ok, deferred, overflow, bad node)") == len(NODES)
+    assert out.count("the columns from before this admit move") == 2  # the two on real bindings
+
+
+def test_sizes_case_inputs(capsys):
+    """tests/apply_paths_worker.py case_sizes without a device: every WHILE_FIT apply of the committed spec meets sizes_step's floors, and
+    exactly one step has the admit that outgrows the admit scratch"""
+    plans = [W.sizes_step(step, N) for step, N in enumerate(SIZES["nodes"])]
+    assert [len(q["applies"]) for q in plans] == [4 if N == 4097 else 3 for N in SIZES["nodes"]]
+    big = plans[SIZES["nodes"].index(4097)]["applies"]
+    assert len(big[3][0]) > len(big[2][0]) + len(big[2][0]) // 4 and all(a[2] == 0x08 for a in big[2:])  # past the 25 % headroom
+    assert all((q["updates"][0][0].size, q["updates"][1][0].size) == (min(50, q["S"]["N"]),) * 2 for q in plans)
+    out = capsys.readouterr().out
+    print(out)
+    assert out.count(": admit of ") == len(SIZES["nodes"]) + 1
+
+
+def test_large_case_inputs(capsys):
+    """case_large without a device: the 600 000-pod admit meets large_plan's floors, and the four applies behind it still meet theirs on
+    the columns it leaves"""
+    S, plan = W.large_plan(LARGE["pods"])
+    assert [f for f, *_ in plan] == [0x08, 0, W.FPN, W.REL, W.FPN | W.REL] and LARGE["pods"] > W.LARGE_FAR + 64
+    assert all(len(b) == LARGE["pods"] for _, b, _, _ in plan)
+    out = capsys.readouterr().out
+    print(out)
+    assert "admit: statuses" in out
 
 
 @pytest.mark.parametrize("n", [1, 2, 3])
@@ -56,7 +86,7 @@ def test_replicated_matrix_inputs(n, capsys):
     assert {W.PICKS[(ki + m) % 3] for ki in (0, 1) for m in (1, 2, 3)} == set(W.PICKS)
 
 
-@pytest.mark.parametrize("change", ["negated", "permuted", "apply"])
+@pytest.mark.parametrize("change", ["negated", "permuted", "apply", "admit"])
 def test_pipe_snapshot_change_inputs(change):
     """tests/test_gpu_spread_pick.py::test_pipe_submits_around_a_snapshot_change can tell the old snapshot from the new one"""
     from tests.test_gpu_spread_pick import assert_old_and_new_can_be_told_apart

@@ -13,6 +13,12 @@ ksched_eval_device beside a mask, ksched_pick with d = 64, d = 1 against the res
 sampled, the uniform and the spread pick in turn.  Two input conditions keep the spread legs from passing vacuously (walk_single; asserted
 without a GPU by tests/test_apply_paths_host.py): before any apply 35 % of the pods or more bind to another node than their candidate 0,
 and at every node count from 1025 on the columns from before an apply of real bindings would change at least one spread binding.
+Admission in pod order (KSCHED_APPLY_WHILE_FIT) stands in all six children, each expectation tests/admit_ref.py's: one more round
+[admit -> the whole matrix] at every node count of the four walks, on real bindings at 63 and 4097 nodes and on random ones at 1, 1025
+and 50 000; in the sizes case an admit behind two applies and two updates with no host wait, at 4097 nodes a second one that outgrows the
+admit scratch; in the large case an admit of 600 000 pods before the four other flag sets.  Their input conditions (deferrals, pods
+admitted behind a deferred one, columns unlike what flags = 0 and FIRST_PER_NODE leave) are asserted from the restatement in the
+worker before the device is compared, and without a GPU by tests/test_apply_paths_host.py.
 """
 import json
 import os
@@ -24,7 +30,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NODES = [1, 63, 1025, 4097, 50_000]
-SINGLE = {"nodes": NODES, "pods": 2000, "pods_big": 600, "rounds": 3}  # (tests/test_apply_paths_host.py walks the same spec without a GPU)
+SINGLE = {"nodes": NODES, "pods": 2000, "pods_big": 600, "rounds": 3}  # (tests/test_apply_paths_host.py walks the same specs without a GPU)
+SIZES = {"nodes": [50_000, 300, 4097, 1, 60_000]}
+LARGE = {"pods": 600_000}
 
 
 def run(case, spec, timeout=300):
@@ -39,17 +47,24 @@ def run(case, spec, timeout=300):
 @pytest.mark.parametrize("kind", ["taints", "many-keys", "list-key", "unindexed"])
 def test_every_path_after_an_apply(built, kind):
     """per node count: the matrix, then three rounds of [apply -> the matrix]; the applies rotate over plain, FIRST_PER_NODE, RELEASE and
-    both, with and without ok, on the previous evaluation's device bindings and on random ones"""
+    both, with and without ok, on the previous evaluation's device bindings and on random ones; then the admit round, [apply with
+    WHILE_FIT -> the matrix], on real bindings at 63 and 4097 nodes and on random ones at the others"""
     out = run("single", dict(SINGLE, kind=kind))
     assert "'spread'" in out.rsplit("picks reached", 1)[-1], "the spread pick is not among the picks reached"
+    for N in NODES:
+        assert f"{kind} N={N} admit round (" in out, f"no admit round at {N} nodes"
 
 
 def test_snapshot_sizes_and_updates_between_applies_on_one_ctx(built):
     """50 000 -> 300 -> 4097 -> 1 -> 60 000 nodes on one ctx: the apply scratch is kept while the snapshot shrinks and regrows, then
-    reallocated; updates of the applied tiles between two applies, no host wait"""
-    run("sizes", {"nodes": [50_000, 300, 4097, 1, 60_000]})
+    reallocated; per snapshot an apply, an update of the applied tiles, an apply, an update, an apply with WHILE_FIT and at 4097 nodes a
+    second one of four times the pods (the admit scratch reallocated behind a queued admit), no host wait"""
+    out = run("sizes", SIZES)
+    assert out.count(": admit of ") == len(SIZES["nodes"]) + 1
 
 
 def test_a_batch_longer_than_one_stride_of_the_pod_kernels(built):
-    """600 000 pods (the pod passes launch at most 2048 x 256 threads): some nodes' first eligible pod lies past pod 524 288"""
-    run("large", {"pods": 600_000}, timeout=600)
+    """600 000 pods (the pod passes launch at most 2048 x 256 threads): some nodes' first eligible pod lies past pod 524 288; WHILE_FIT
+    first (segments of more than 10 000 pods with admits and deferrals mixed, ten merge passes), then the four other flag sets"""
+    out = run("large", LARGE, timeout=600)
+    assert f"P={LARGE['pods']} admit:" in out

@@ -10,7 +10,7 @@ import pytest
 
 from kube_scheduler_rs_reference_amd import FIT, PICK_BESTFIT, PICK_SAMPLED, SEL, SEL_NEVER, TAINT, Evaluator, KschedError, _lib, synth
 from oracle import capi
-from oracle.oracle_ref import apply_bindings_exact
+from tests.admit_ref import apply_exact
 
 pytestmark = pytest.mark.gpu
 
@@ -208,9 +208,12 @@ def test_replanned_layout_equals_the_oracle(ev, kind, base):
     W.check_matrix(ev, dict(S2, lab=np.ascontiguousarray(lab3)), cpu, mem, set(), kind + " + in-layout", rng, reduced=True)
 
 
-def test_interleaved_with_update_nodes_and_apply_bindings(ev):
-    """label updates between ksched_update_nodes and ksched_apply_bindings_device; best fit after a label-only change (its rows rebuilt
-    without the sorts) equals the oracle"""
+@pytest.mark.parametrize("rule", [0, _lib.APPLY_WHILE_FIT], ids=["all", "while-fit"])
+def test_interleaved_with_update_nodes_and_apply_bindings(ev, rule):
+    """label updates between ksched_update_nodes and ksched_apply_bindings_device (every bound pod, or APPLY_WHILE_FIT: the expected columns
+    are tests/admit_ref.apply_exact's by that rule); best fit after a label-only change (its rows rebuilt without the sorts) equals the
+    oracle.  The admitted batch is one of which the restatement defers a pod or more -- the sampled pick's bindings as they are (restated:
+    6, 9 and 7 of some 1100 bound pods, two pods drawn onto a node with room for one), or twice over should they all fit"""
     import torch
     c = synth.make_cluster(3000, 5000, n_keys=8, n_taints=16, seed=0xB1)
     ev.set_kernel("auto")
@@ -243,11 +246,22 @@ def test_interleaved_with_update_nodes_and_apply_bindings(ev):
         cpu[u] -= rng.integers(0, 1000, u.size)
         ev.update_nodes(u, cpu[u], mem[u])
         check(f"round {rnd}: after ksched_update_nodes")
-        b = torch.from_numpy(want.astype(np.int32)).to(dev)
-        rc_t, rm_t = torch.from_numpy(c.req_cpu).to(dev), torch.from_numpy(c.req_mem).to(dev)
-        ev.apply_bindings_device(b, rc_t, rm_t)
-        cpu, mem, _ = apply_bindings_exact(cpu, mem, want, c.req_cpu, c.req_mem)
+        batch = want.astype(np.int32), c.req_cpu, c.req_mem
+        restated = apply_exact(cpu, mem, *batch, None, rule)
+        if rule == _lib.APPLY_WHILE_FIT and not (restated[2] == _lib.APPLY_DEFERRED).any():
+            batch = tuple(np.concatenate([a, a]) for a in batch)
+            restated = apply_exact(cpu, mem, *batch, None, rule)
+        n_def = int((restated[2] == _lib.APPLY_DEFERRED).sum())
+        print(f"round {rnd}: flags={rule}, {len(batch[0])} pods, {n_def} deferred")
+        assert (n_def >= 1) == (rule == _lib.APPLY_WHILE_FIT), f"round {rnd}: {n_def} pods deferred"
+        b, rc_t, rm_t = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in batch)
+        st = torch.full((len(batch[0]),), -7, dtype=torch.int32, device=dev)
+        ev.apply_bindings_device(b, rc_t, rm_t, None, rule, st)
+        cpu, mem, want_st = restated
         torch.cuda.synchronize()
+        assert np.array_equal(st.cpu().numpy(), want_st), f"round {rnd}: statuses of the apply"
+        got = ev.read_nodes()
+        assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem), f"round {rnd}: columns after the apply"
         idx, rows, rows_t = in_layout_rows(rng, lab, tnt, rng.integers(0, c.N, 17).astype(np.uint32))
         ev.update_node_labels(idx, rows, rows_t)
         lab, tnt = apply_rows(lab, tnt, idx, rows, rows_t)

@@ -12,6 +12,7 @@ from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PI
                                              unpack_mask)
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact
+from tests.admit_ref import apply_while_fit_exact
 from tests.spread_ref import best_of, spread_candidates, spread_candidates_listed, spread_pick
 from tests.test_gpu_uniform_pick import dev_of, mask_np, oracle_mask, pitched_mask, pod_tensors, to_dev
 from tests.uniform_ref import uniform_pick
@@ -487,6 +488,8 @@ def changing_snapshot(change):
                   column fits no pod), so the mask stays and only the ranking turns over
       "permuted"  ksched_update_nodes: the (cpu, mem) pairs of the drawn nodes permuted among them; the fit term on, so the mask moves too
       "apply"     ksched_apply_bindings_device of the old snapshot's own spread bindings (back: the same bindings with APPLY_RELEASE)
+      "admit"     the same bindings with APPLY_WHILE_FIT (tests/admit_ref.py): a pod that no longer fits what the pods before it left of
+                  its node is DEFERRED (`new` carries the statuses as `status`); back: APPLY_RELEASE with ok = (status == APPLIED)
     Computed once per change and shared."""
     k = case(TWO_PASS)
     if ("changing", change) not in k:
@@ -507,12 +510,22 @@ def changing_snapshot(change):
         elif change == "permuted":
             src = idx[np.random.default_rng(0x9E12).permutation(idx.size)]
             cpu[idx], mem[idx] = old["cpu"][src], old["mem"][src]
-        else:
+        elif change == "apply":
             cpu, mem, st = apply_bindings_exact(cpu, mem, old["want"], c.req_cpu, c.req_mem, None, 0)
             assert (st == _lib.APPLY_APPLIED).sum() == (old["want"] >= 0).sum() > 0
             back = apply_bindings_exact(cpu, mem, old["want"], c.req_cpu, c.req_mem, None, _lib.APPLY_RELEASE)
             assert np.array_equal(back[0], old["cpu"]) and np.array_equal(back[1], old["mem"])
+        elif change == "admit":
+            cpu, mem, st = apply_while_fit_exact(cpu, mem, old["want"], c.req_cpu, c.req_mem, None)
+            assert (st == _lib.APPLY_APPLIED).sum() + (st == _lib.APPLY_DEFERRED).sum() == (old["want"] >= 0).sum() and (st == _lib.APPLY_APPLIED).any()
+            back = apply_bindings_exact(cpu, mem, old["want"], c.req_cpu, c.req_mem, (st == _lib.APPLY_APPLIED).astype(np.uint8), _lib.APPLY_RELEASE)
+            assert np.array_equal(back[0], old["cpu"]) and np.array_equal(back[1], old["mem"])
+            assert np.array_equal(back[2] == _lib.APPLY_APPLIED, st == _lib.APPLY_APPLIED)  # the release takes back the admitted pods, and only them
+        else:
+            raise ValueError(change)
         new = dict(state(cpu, mem), idx=idx)
+        if change == "admit":
+            new["status"] = st
         k[("changing", change)] = (flags, [old, new])
     return k[("changing", change)]
 
@@ -522,19 +535,24 @@ def assert_old_and_new_can_be_told_apart(change):
     changes a quarter or more of the restated bindings.  An apply is what slot 0's own bindings make it: 900 pods' requests taken from 8200
     nodes change only the pods whose candidates include a node another pod was bound to.  Restated: 13.0 % of the bindings differ between
     the two snapshots (the mask moves with the fit term), and on the new mask the old columns change 15 of 900 -- thin discrimination, so a
-    floor of 10 is asserted: the case cannot shrink to a single pod unnoticed"""
+    floor of 10 is asserted: the case cannot shrink to a single pod unnoticed.  An admit of the same bindings keeps those two floors; how
+    many pods it defers is printed and no floor is set on it: restated, 0 of the 825 bound pods (every binding is of a node the pod fits, and
+    two pods seldom share one), so this admit leaves what the apply leaves and the leg is about where the admit's own kernels, its statuses
+    and the release by them run among the pipe's streams, not about deferral (profiles/admit_standing_checks.txt)"""
     flags, (old, new) = changing_snapshot(change)
     moved = float((old["want"] != new["want"]).mean())
     stale = int((best_of(new["cand"], old["mem"], old["cpu"]) != new["want"]).sum())  # on the new mask: the old columns against the new
     print(f"{change}: {100 * moved:.1f} % of the restated bindings differ between the two snapshots; on the new mask the old columns change {stale}")
-    if change == "apply":
+    if change == "admit":
+        print(f"admit: {int((new['status'] == _lib.APPLY_DEFERRED).sum())} of {int((old['want'] >= 0).sum())} bound pods are deferred")
+    if change in ("apply", "admit"):
         assert moved >= 0.10 and stale >= 10
     else:
         assert moved >= 0.25 and stale >= 0.25 * old["want"].size
     assert (change == "negated") == np.array_equal(old["feas"], new["feas"])
 
 
-@pytest.mark.parametrize("change", ["negated", "permuted", "apply"])
+@pytest.mark.parametrize("change", ["negated", "permuted", "apply", "admit"])
 @pytest.mark.parametrize("mode", [0, 2, 3])
 def test_pipe_submits_around_a_snapshot_change(ev, mode, change):
     """Two submits of the same pods and draws (900 x 8200, d = 5: a two-pass row) into slots 0 and 1 with a snapshot change enqueued between
@@ -542,7 +560,8 @@ def test_pipe_submits_around_a_snapshot_change(ev, mode, change):
     the NEW one.  The slot's pick stream is kept busy for some milliseconds first, so the change is enqueued while slot 0's pick has not
     run.  The change: ksched_update_nodes, or ksched_apply_bindings_device of slot 0's own bindings on a stream ordered behind slot 0 with
     pipe.wait(0, stream=...).  A second round on the same slots takes the change back (the update with the old values; the same bindings
-    with APPLY_RELEASE): slot 0 is reused on the new snapshot, slot 1 on the old one again."""
+    with APPLY_RELEASE): slot 0 is reused on the new snapshot, slot 1 on the old one again.  "admit" is the apply with APPLY_WHILE_FIT and
+    its statuses written; its way back releases the pods it admitted, ok = (status == APPLIED) computed on the side stream, no host wait."""
     import torch
     k = case(TWO_PASS)
     c, d = k["c"], 5
@@ -559,6 +578,7 @@ def test_pipe_submits_around_a_snapshot_change(ev, mode, change):
         masks = [ev.alloc_mask(c.P, pitched=True) for _ in range(2)]
         outs = [fresh(ev, c.P) for _ in range(2)]
         applied = fresh(ev, c.P)  # the bindings the apply took, kept for the release
+        status, landed = fresh(ev, c.P), torch.zeros(c.P, dtype=torch.uint8, device=dev_of(ev))  # of the admit, and which pods it admitted
         torch.cuda.synchronize()
         for rnd in range(2):
             before, after = states[rnd % 2], states[(rnd + 1) % 2]
@@ -575,6 +595,17 @@ def test_pipe_submits_around_a_snapshot_change(ev, mode, change):
                     with torch.cuda.stream(side):
                         applied.copy_(outs[0])
                 ev.apply_bindings_device(outs[0] if rnd == 0 else applied, cpu_t, mem_t, None, _lib.APPLY_RELEASE if rnd else 0, stream=side)
+            elif change == "admit":
+                pipe.wait(0, stream=side)
+                with torch.cuda.stream(side):
+                    if rnd == 0:
+                        applied.copy_(outs[0])
+                    else:
+                        landed.copy_(status == _lib.APPLY_APPLIED)
+                if rnd == 0:
+                    ev.apply_bindings_device(outs[0], cpu_t, mem_t, None, _lib.APPLY_WHILE_FIT, status_out=status, stream=side)
+                else:
+                    ev.apply_bindings_device(applied, cpu_t, mem_t, landed, _lib.APPLY_RELEASE, stream=side)
             else:
                 ev.update_nodes(idx, after["cpu"][idx], after["mem"][idx])
             pipe.submit(1, cpu_t, mem_t, sel, tol, smp, flags | PICK_SPREAD, masks[1], outs[1])
@@ -592,6 +623,8 @@ def test_pipe_submits_around_a_snapshot_change(ev, mode, change):
                 f"{what}: slot 1, enqueued after the change ({int((got1 != after['want']).sum())} bindings differ, {int((got1 == before['want']).sum())} of {c.P} are the old snapshot's)"
             got_cpu, got_mem = ev.read_nodes()
             assert np.array_equal(got_cpu, after["cpu"]) and np.array_equal(got_mem, after["mem"]), f"{what}: the columns"
+            if change == "admit" and rnd == 0:
+                assert np.array_equal(status.cpu().numpy(), after["status"]), f"{what}: the admit's statuses"
     finally:
         torch.cuda.synchronize()
         pipe.close()

@@ -14,7 +14,9 @@ import pytest
 import torch
 
 from kube_scheduler_rs_reference_amd import FIT, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth
+from oracle import capi
 from tests import summary_ref as ref
+from tests.admit_ref import apply_exact
 
 pytestmark = pytest.mark.gpu
 
@@ -292,10 +294,13 @@ def test_selector_and_taint_are_told_apart_where_two_masks_cannot(ev):
     assert got[pod, 2] < c.N - got[pod, 0]
 
 
-def test_after_snapshot_changes(ev):
-    """apply_bindings_device (shrinks `available`), update_nodes, update_node_labels (labels and taints), then summarise: equal to the
-    restatement on the accumulated columns and to a fresh ctx given those columns; a summary enqueued before an update on the same
-    stream sees the old snapshot"""
+@pytest.mark.parametrize("rule", [0, _lib.APPLY_WHILE_FIT], ids=["all", "while-fit"])
+def test_after_snapshot_changes(ev, rule):
+    """apply_bindings_device (shrinks `available`: every bound pod, or APPLY_WHILE_FIT), update_nodes, update_node_labels (labels and
+    taints), then summarise: equal to the restatement on the accumulated columns -- tests/admit_ref.apply_exact's for the apply, on the
+    oracle's sampled bindings, which the device's must equal -- and to a fresh ctx given those columns; a summary enqueued before an update
+    on the same stream sees the old snapshot.  The admitted batch is one of which the restatement defers a pod or more: the bindings as
+    they are (restated: 1 of 774 bound pods) or, should they all fit, twice over (87 of 1548)"""
     c = synth.make_config("C5", P=2000, N=4300)
     flags = FIT | SEL | TAINT
     ev.set_nodes(**c.node_columns())
@@ -304,13 +309,30 @@ def test_after_snapshot_changes(ev):
     # 1. bind the batch's sampled picks and apply them on the device
     bind = torch.full((c.P,), -1, dtype=torch.int32, device="cuda:0")
     smp = torch.from_numpy(c.samples.view(np.int32)).to("cuda:0")
+    want_bind = capi.eval_encoded(c.avail_cpu, c.avail_mem, lab, tnt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, c.samples,
+                                  flags | _lib.PICK_SAMPLED, want_mask=False)[2].astype(np.int32)
+    batch, twice = (want_bind, c.req_cpu, c.req_mem), False
+    restated = apply_exact(c.avail_cpu, c.avail_mem, *batch, None, rule)
+    if rule == _lib.APPLY_WHILE_FIT and not (restated[2] == _lib.APPLY_DEFERRED).any():
+        batch, twice = tuple(np.concatenate([a, a]) for a in batch), True
+        restated = apply_exact(c.avail_cpu, c.avail_mem, *batch, None, rule)
+    n_def = int((restated[2] == _lib.APPLY_DEFERRED).sum())
+    print(f"flags={rule}: {len(batch[0])} pods, {n_def} deferred")
+    assert (n_def >= 1) == (rule == _lib.APPLY_WHILE_FIT), f"{n_def} pods deferred"
     ev.eval_device(cpu, mem, sel, tol, smp, flags | _lib.PICK_SAMPLED, out_binding=bind)
     before = ev.summarize_device(cpu, mem, sel, tol, flags=flags)  # enqueued BEFORE the apply: the old snapshot
-    ev.apply_bindings_device(bind, cpu, mem)
+    st = torch.full((len(batch[0]),), -7, dtype=torch.int32, device="cuda:0")
+    if twice:
+        ev.apply_bindings_device(torch.cat([bind, bind]), torch.cat([cpu, cpu]), torch.cat([mem, mem]), None, rule, st)
+    else:
+        ev.apply_bindings_device(bind, cpu, mem, None, rule, st)
     after = ev.summarize_device(cpu, mem, sel, tol, flags=flags)
     torch.cuda.synchronize()
     assert np.array_equal(before.cpu().numpy().view(np.uint32), ref.cluster_expected(c, flags))
+    assert np.array_equal(bind.cpu().numpy(), want_bind) and np.array_equal(st.cpu().numpy(), restated[2])
     acpu, amem = ev.read_nodes()
+    assert np.array_equal(acpu, restated[0]) and np.array_equal(amem, restated[1])
+    acpu, amem = restated[0], restated[1]
     assert (acpu <= c.avail_cpu).all() and (acpu < c.avail_cpu).any()
     want = ref.expected_counts(acpu, amem, lab, tnt, c.req_cpu, c.req_mem, c.pod_sel, c.pod_tol, flags)
     assert np.array_equal(after.cpu().numpy().view(np.uint32), want)
