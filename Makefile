@@ -44,6 +44,7 @@ SPREAD_PICK_TEST := tests/cpp/spread_pick_tests
 BESTFIT_LAYOUT_TEST := tests/cpp/bestfit_layout_tests
 PIPE_PLAN_TEST := tests/cpp/pipe_plan_tests
 APPLY_ADMIT_TEST := tests/cpp/apply_admit_tests
+STREAM_ORDER_TEST := tests/cpp/stream_order_tests
 
 PMC_CALIB := tools/pmc_calib
 
@@ -71,7 +72,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
 # (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -102,6 +103,9 @@ $(PIPE_PLAN_TEST): tests/cpp/pipe_plan_tests.cpp $(CSRC)/pipe_plan.hpp include/k
 # host-only check of KSCHED_APPLY_WHILE_FIT's chunk walk (csrc/apply_admit.hpp: a 64-lane emulation of k_apply_admit against the serial rule; no GPU, no HIP header): tests/test_admit_host.py runs it
 $(APPLY_ADMIT_TEST): tests/cpp/apply_admit_tests.cpp $(CSRC)/apply_admit.hpp
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -pthread -o $@ tests/cpp/apply_admit_tests.cpp
+# host-only check of the ctx's stream ordering (csrc/stream_order.hpp: every stream wait, over a happens-before model of every sequence of up to five calls, against the rules as they were, and the steady states call by call; no GPU, no HIP header): tests/test_stream_order_host.py runs it
+$(STREAM_ORDER_TEST): tests/cpp/stream_order_tests.cpp $(CSRC)/stream_order.hpp
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/stream_order_tests.cpp
 $(LIB_HOST): $(HOST_SRCS) $(HOST_HDRS) $(LIB_HIP)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRCS) -L$(PKG) -lksched_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 # C++ tests of the host mirror (tests/cpp/host_tests.cpp; driven by tests/test_host_mirror.py)
@@ -157,4 +161,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

@@ -33,6 +33,7 @@
 #include "mask_alloc.hpp"
 #include "pipe_plan.hpp"
 #include "snapshot_change.hpp"
+#include "stream_order.hpp"
 #include "tile_index.hpp"
 
 using namespace ksched;
@@ -110,6 +111,14 @@ struct BestfitIndex {
     bool stale() const { return order_stale || rows_stale; }
 };
 
+// what the ctx keeps per stream evaluations are enqueued on: the registry is stream_order.hpp's, one entry and one lookup per stream
+struct StreamRes {
+    hipEvent_t ev = nullptr;  // recorded on the stream when a snapshot change has to wait for what it holds (the ctx's own stream: none)
+    // per-pod accumulators of the tile-test pick (kernels_fused.hpp PICK == 2): all zero between launches (the kernel zeroes what it
+    // used); one buffer per stream, so that launches on different streams may overlap
+    DevBuf<uint64_t> pick_acc;
+};
+
 }  // namespace
 
 struct ksched_ctx {
@@ -149,32 +158,11 @@ struct ksched_ctx {
     size_t h_stage_cap = 0;
     hipEvent_t ev_stage = nullptr;  // the last copy out of h_stage
     DevBuf<uint8_t> d_stage;
-    // Ordering between the snapshot (built / patched on `stream`) and evaluations on the caller's streams, without a device
-    // synchronize: every stream an evaluation was enqueued on is remembered with an event; a snapshot change first makes
-    // `stream` wait for what those streams hold (evaluations already enqueued read the snapshot as it was), and an evaluation
-    // enqueued afterwards makes its stream wait for the change (ev_build).
-    struct UserStream {
-        hipStream_t s;
-        hipEvent_t ev;
-        uint64_t gen;  // snapshot generation this stream has waited for
-    };
-    std::vector<UserStream> user_streams;
-    hipEvent_t ev_build = nullptr;
-    uint64_t build_gen = 0;
-    // Where a snapshot change is enqueued (snapshot_begin decides, the build / patch code uses it, snapshot_end records ev_build
-    // there).  With exactly ONE caller stream known -- one scheduler loop on one stream, the common case -- the change goes onto
-    // that stream itself: ordered behind the evaluations already there and ahead of the next ones by the stream, with no event
-    // and no cross-stream wait at all (each costs ~5 us; on some hardware queues ~180 us, tools/stream_probe.py).  Otherwise:
-    // the ctx's own stream and the events described above.  KSCHED_OPT_SNAPSHOT_STREAM = 1 keeps every change on the ctx's stream.
-    hipStream_t change_stream = nullptr;
-    uint64_t own_gen = 0;  // snapshot generation the ctx's own stream is ordered behind
-    bool opt_own_stream = false;
-    // The ctx-owned device scratch that evaluations on the caller's streams use (the best-fit hand-over, scratch_mask, trace) belongs to one
-    // stream at a time: when another stream is about to use it, that stream first waits for what the previous one holds
-    // (scratch_enter; an event recorded at that moment, nothing on the common one-stream path).
-    hipStream_t scratch_stream = nullptr;
-    bool scratch_owned = false, scratch_ev_pending = false;
-    hipEvent_t ev_scratch = nullptr;
+    // Every stream wait of the ctx is decided by stream_order.hpp (which stream carries a snapshot change, who waits for whom); the helpers
+    // under "stream ordering" below execute its answers with these events and the per-stream ones in StreamRes.
+    StreamOrder<StreamRes> order;
+    hipEvent_t ev_build = nullptr;    // behind every snapshot change, on the stream that carried it
+    hipEvent_t ev_scratch = nullptr;  // the scratch owner's last use, when the ctx-owned scratch changes hands
 
     // scratch for the host-pointer path
     DevBuf<int64_t> pcpu, pmem;
@@ -198,13 +186,6 @@ struct ksched_ctx {
     bool opt_pick_from_mask = false;
     int opt_fused_pick = 1;       // KSCHED_OPT_FUSED_PICK: 0 = the pick is its own launch, 1 = it rides in the fused mask launch (the form is chosen
                                   // by the request), 2 = ... only as waves of the fill, 3 = ... only as tile tests
-    // per-pod accumulators of the tile-test pick (kernels_fused.hpp PICK == 2): all zero between launches (the kernel zeroes what it
-    // used); one buffer per stream evaluations are enqueued on, so that launches on different streams may overlap
-    struct PickAcc {
-        hipStream_t s;
-        DevBuf<uint64_t> buf;
-    };
-    std::vector<PickAcc> pick_acc;
     int opt_pipe_mode = 0;        // KSCHED_OPT_PIPE_MODE: 0 split (mask stream / pick stream), m >= 1 alternate (whole steps, stream = slot % max(2, m))
     int opt_round_order = 0;      // KSCHED_OPT_ROUND_ORDER: 0 interleaved wave-major (default), 1 blocked, 2 interleaved chunk-major
     uint32_t opt_mask_probe = 6;  // KSCHED_OPT_MASK_PROBE: candidates of ksched_mask_alloc's probe-and-keep path
@@ -302,115 +283,100 @@ int timing_slot(ksched_ctx *c, size_t *slot) {
     return KSCHED_OK;
 }
 
-// ---- stream ordering (see ksched_ctx::user_streams) ---------------------------------------------------------------
+// ---- stream ordering: the executors of stream_order.hpp's answers (ksched_ctx::order) -------------------------------------------
+// Each asks the header, issues exactly the HIP calls the answer names and tells it what went through; the decisions, and the
+// reasons for them, are in the header.
 
-// `s`, whose generation is `gen`, waits for the latest snapshot change if it is behind
-int stream_catch_up(ksched_ctx *c, hipStream_t s, uint64_t &gen) {
-    if (gen != c->build_gen) {
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_build, 0));
-        gen = c->build_gen;
-    }
+inline hipStream_t hip_stream_of(StreamKey s) { return (hipStream_t) const_cast<void *>(s); }
+// where the snapshot change in progress is enqueued (snapshot_begin decides, the build / patch code uses it, snapshot_end records ev_build there)
+inline hipStream_t change_stream(const ksched_ctx *c) { return hip_stream_of(c->order.change_stream()); }
+
+// `s` waits for the latest snapshot change (ev_build) and has then met it
+int stream_wait_build(ksched_ctx *c, hipStream_t s) {
+    HIPCHK(c, hipStreamWaitEvent(s, c->ev_build, 0));
+    c->order.met(s);
     return KSCHED_OK;
 }
 
-// `s` has met the latest snapshot change (it carried the change, or has just been made to wait for it); a stream the ctx does not know
-// has no generation to keep
-void stream_met(ksched_ctx *c, hipStream_t s) {
-    if (s == c->stream) c->own_gen = c->build_gen;
-    for (auto &u : c->user_streams)
-        if (u.s == s) u.gen = c->build_gen;
-}
-
-// remember `s` as a stream evaluations are enqueued on; make it wait for the latest snapshot change if it has not yet
+// an evaluation is about to be enqueued on `s`: remembered for the next snapshot change, behind the latest one
 int stream_enter(ksched_ctx *c, hipStream_t s) {
-    // the ctx's own stream: in order by itself unless the latest change went onto a caller's stream
-    if (s == c->stream) return stream_catch_up(c, s, c->own_gen);
-    ksched_ctx::UserStream *u = nullptr;
-    for (auto &x : c->user_streams)
-        if (x.s == s) u = &x;
-    if (!u) {
-        ksched_ctx::UserStream n{s, nullptr, 0};
-        HIPCHK(c, hipEventCreateWithFlags(&n.ev, hipEventDisableTiming));
-        c->user_streams.push_back(n);
-        u = &c->user_streams.back();
+    const EnterPlan pl = c->order.plan_enter(s);
+    if (pl.is_new) {
+        StreamRes r;
+        HIPCHK(c, hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+        c->order.add(s, std::move(r));
     }
-    return stream_catch_up(c, s, u->gen);
+    return pl.wait_build ? stream_wait_build(c, s) : KSCHED_OK;
 }
 
 // `s` is about to enqueue work that uses the ctx-owned scratch buffers
 int scratch_enter(ksched_ctx *c, hipStream_t s) {
-    if (c->scratch_owned && c->scratch_stream != s) {
-        HIPCHK(c, hipEventRecord(c->ev_scratch, c->scratch_stream));
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_scratch, 0));
-    } else if (!c->scratch_owned && c->scratch_ev_pending) {
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_scratch, 0));
-    }
-    c->scratch_stream = s;
-    c->scratch_owned = true;
-    c->scratch_ev_pending = false;
+    const ScratchPlan pl = c->order.plan_scratch(s);
+    if (pl.step == ScratchStep::kRecordOwnerAndWait) HIPCHK(c, hipEventRecord(c->ev_scratch, hip_stream_of(pl.owner)));
+    if (pl.step != ScratchStep::kNothing) HIPCHK(c, hipStreamWaitEvent(s, c->ev_scratch, 0));
+    c->order.scratch_taken(s);
     return KSCHED_OK;
 }
 
 void stream_forget(ksched_ctx *c, hipStream_t s) {
-    for (size_t i = 0; i < c->pick_acc.size(); ++i)
-        if (c->pick_acc[i].s == s) {  // (its launches are ordered before whatever the caller does to the stream next: freeing is safe after a sync there;
-                                      // hipFree synchronises the device itself)
-            c->pick_acc.erase(c->pick_acc.begin() + (std::ptrdiff_t)i);
-            break;
-        }
-    if (c->scratch_owned && c->scratch_stream == s) {  // its last use of the scratch buffers stays ordered: as an event
-        c->scratch_ev_pending = hipEventRecord(c->ev_scratch, s) == hipSuccess;
-        if (!c->scratch_ev_pending) (void)hipGetLastError();
-        c->scratch_owned = false;
-        c->scratch_stream = nullptr;
+    // (its launches are ordered before whatever the caller does to the stream next: freeing is safe after a sync there; hipFree
+    // synchronises the device itself)
+    if (StreamRes *r = c->order.res(s)) r->pick_acc.release();
+    bool recorded = false;
+    if (c->order.plan_forget(s).record_scratch) {
+        recorded = hipEventRecord(c->ev_scratch, s) == hipSuccess;
+        if (!recorded) (void)hipGetLastError();
     }
-    for (size_t i = 0; i < c->user_streams.size(); ++i)
-        if (c->user_streams[i].s == s) {
-            (void)hipEventDestroy(c->user_streams[i].ev);
-            c->user_streams.erase(c->user_streams.begin() + (std::ptrdiff_t)i);
-            return;
-        }
+    StreamRes gone;
+    if (c->order.forget(s, recorded, &gone)) (void)hipEventDestroy(gone.ev);
 }
 
-// Before the snapshot changes: choose the stream that carries the change (ksched_ctx::change_stream).  One caller stream known: that
-// stream (it is behind its own evaluations by itself).  Otherwise the ctx's stream, which first waits for everything already enqueued
-// on the remembered streams.
+// Before the snapshot changes: the stream that carries the change (ksched_ctx::order.change_stream()) and what it first waits for
 int snapshot_begin(ksched_ctx *c) {
-    c->change_stream = c->stream;
-    if (c->user_streams.size() == 1 && !c->opt_own_stream) {
-        auto &u = c->user_streams[0];
-        const hipError_t q = hipStreamQuery(u.s);  // host-side probe: a stream the caller destroyed without telling is not used
-        if (q == hipSuccess || q == hipErrorNotReady) {
-            // (an earlier change may have gone onto the ctx's stream, and this stream not have met it yet)
-            if (int rc = stream_catch_up(c, u.s, u.gen)) return rc;
-            c->change_stream = u.s;
-            return KSCHED_OK;
-        }
-        (void)hipGetLastError();  // fall through: the loop below forgets the stream
+    StreamOrder<StreamRes> &o = c->order;
+    const ProbePlan pr = o.plan_probe();
+    bool alive = false;
+    if (pr.probe) {  // host-side
+        const hipError_t q = hipStreamQuery(hip_stream_of(pr.stream));
+        alive = q == hipSuccess || q == hipErrorNotReady;
+        if (!alive) (void)hipGetLastError();
     }
-    // an earlier change may have gone onto a caller's stream: this one is ordered behind it
-    if (int rc = stream_catch_up(c, c->stream, c->own_gen)) return rc;
-    for (size_t i = 0; i < c->user_streams.size();) {
-        auto &u = c->user_streams[i];
-        if (hipEventRecord(u.ev, u.s) != hipSuccess) {  // the caller destroyed that stream: forget it
+    const BeginPlan pl = o.begin(alive);
+    const hipStream_t s = hip_stream_of(pl.carrier);
+    if (pl.carrier_waits_build)
+        if (int rc = stream_wait_build(c, s)) return rc;
+    if (!pl.record_callers) return KSCHED_OK;
+    for (size_t i = 0; i < o.callers();) {
+        if (hipEventRecord(o.caller_res(i).ev, hip_stream_of(o.caller(i))) != hipSuccess) {  // the caller destroyed that stream
             (void)hipGetLastError();
-            (void)hipEventDestroy(u.ev);
-            c->user_streams.erase(c->user_streams.begin() + (std::ptrdiff_t)i);
+            const StreamRes gone = o.drop(i);
+            (void)hipEventDestroy(gone.ev);
             continue;
         }
-        HIPCHK(c, hipStreamWaitEvent(c->stream, u.ev, 0));
+        HIPCHK(c, hipStreamWaitEvent(s, o.caller_res(i).ev, 0));
         ++i;
     }
     return KSCHED_OK;
 }
 
-// after the change has been enqueued on change_stream: ev_build marks it for every other stream
+// after the change has been enqueued on the change stream: ev_build marks it for every other stream
 int snapshot_end(ksched_ctx *c) {
-    HIPCHK(c, hipEventRecord(c->ev_build, c->change_stream));
-    ++c->build_gen;
-    stream_met(c, c->change_stream);  // the stream that carries the change is behind it by itself
+    HIPCHK(c, hipEventRecord(c->ev_build, hip_stream_of(c->order.change_stream())));
+    c->order.committed();
     return KSCHED_OK;
 }
+
+// An apply whose caller stream is `hs`, behind snapshot_begin: the change also waits for what `hs` holds ...
+int apply_order_begin(ksched_ctx *c, hipStream_t hs) {
+    if (!c->order.plan_apply(hs).change_waits_hs) return KSCHED_OK;
+    if (!c->ev_apply) HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_apply, hs));
+    HIPCHK(c, hipStreamWaitEvent(hip_stream_of(c->order.change_stream()), c->ev_apply, 0));
+    return KSCHED_OK;
+}
+
+// ... and behind snapshot_end, `hs` waits for the change (the caller reads status_out there)
+int apply_order_end(ksched_ctx *c, hipStream_t hs) { return c->order.plan_apply(hs).hs_waits_change ? stream_wait_build(c, hs) : KSCHED_OK; }
 
 // Every change of the node snapshot, in three calls: begin -> stage, fill, upload (a change that brings data) ->
 // the caller's kernels on change_stream -> commit.  A change can stop halfway, by an error return or a throw: once armed, the ctx
@@ -451,7 +417,7 @@ struct SnapshotChange {
     // the pinned block's first `dev_bytes` bytes -> the device block, one copy on the change stream; ev_stage: the last copy out of the
     // pinned block (the caller's own copies out of it come before this call)
     int upload(size_t dev_bytes) {
-        const hipStream_t s = c->change_stream;
+        const hipStream_t s = change_stream(c);
         if (dev_bytes) HIPCHK(c, hipMemcpyAsync(c->d_stage.ptr, c->h_stage, dev_bytes, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipEventRecord(c->ev_stage, s));
         return KSCHED_OK;
@@ -482,7 +448,7 @@ int launch_build_fit(ksched_ctx *c, const uint32_t *d_tile_list, uint32_t count,
     a.n = l.n;
     a.rows = l.rows;
     a.row_cpu = l.row_cpu;
-    hipLaunchKernelGGL(k_build_tile_fit, dim3(d_tile_list ? count : l.tiles, 2), dim3(1024), 0, c->change_stream, a);
+    hipLaunchKernelGGL(k_build_tile_fit, dim3(d_tile_list ? count : l.tiles, 2), dim3(1024), 0, change_stream(c), a);
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
@@ -498,7 +464,7 @@ int launch_build_lists(ksched_ctx *c, const uint32_t *d_tile_list = nullptr, uin
     a.n = l.n;
     a.nlist = l.nlist;
     for (uint32_t j = 0; j < l.nlist; ++j) a.list_col[j] = l.list_col[j];
-    hipLaunchKernelGGL(k_build_tile_list, dim3(d_tile_list ? count : l.tiles, l.nlist), dim3(1024), 0, c->change_stream, a);
+    hipLaunchKernelGGL(k_build_tile_list, dim3(d_tile_list ? count : l.tiles, l.nlist), dim3(1024), 0, change_stream(c), a);
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
@@ -521,7 +487,7 @@ int launch_build_named(ksched_ctx *c, const uint32_t *d_tile_list = nullptr, uin
     a.named_rows = l.row_cpu;
     const uint32_t lds = l.row_cpu * 128u;
     HIPCHK(c, hipFuncSetAttribute((const void *)k_build_tile_named, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_build_tile_named, dim3(d_tile_list ? count : l.tiles), dim3(1024), lds, c->change_stream, a);
+    hipLaunchKernelGGL(k_build_tile_named, dim3(d_tile_list ? count : l.tiles), dim3(1024), lds, change_stream(c), a);
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
 }
@@ -551,7 +517,7 @@ void fill_pod_operands(A &a, const ksched_ctx *c, const EvalRequest &r) {
 int bestfit_sort(ksched_ctx *c, const int64_t *k0, const int64_t *k1, int64_t *dst_k0, uint32_t *dst_idx) {
     BestfitIndex &bi = c->bestfit;
     const uint32_t n = c->n, passes = bi.order.merge_passes;
-    const hipStream_t s = c->change_stream;
+    const hipStream_t s = change_stream(c);
     if (n > (1u << 31)) {  // (the merge passes index records with 32 bits; no snapshot of that size fits a GPU's memory anyway)
         c->last_error = "best-fit structures: more than 2^31 nodes";
         return KSCHED_E_INVAL;
@@ -594,7 +560,7 @@ int build_bestfit(ksched_ctx *c) {
     BestfitIndex &bi = c->bestfit;
     const uint32_t n = c->n;
     bi.rows_built = false;
-    hipStream_t s = c->change_stream;
+    hipStream_t s = change_stream(c);
     const BfOrderLayout &o = bi.order = bf_order_layout(n);
     HIPCHK(c, bi.by_cpu.reserve(n));
     HIPCHK(c, bi.cpurank.reserve(n));
@@ -649,7 +615,7 @@ inline bool bf_rows_expected(const ksched_ctx *c) { return c->idx.built && c->n 
 int build_bestfit_rows(ksched_ctx *c) {
     BestfitIndex &bi = c->bestfit;
     const uint32_t n = c->n;
-    hipStream_t s = c->change_stream;
+    hipStream_t s = change_stream(c);
     bi.rows_built = false;
     if (!bf_rows_expected(c)) return KSCHED_OK;  // (list keys have no rows: pods that constrain one are picked from the key's sorted lists, k_pick_bestfit_listed)
     const IndexedLayout &l = c->idx.lay;
@@ -893,7 +859,7 @@ int index_reserve(ksched_ctx *c, const IndexPlan &p, uint8_t *h_meta) {
     hipError_t e = indexed_reserve(c->idx, p.l);
     if (e != hipSuccess) return fail_hip(c, e, "indexed_reserve");
     memcpy(h_meta, p.meta, kPlanMetaBytes);
-    HIPCHK(c, hipMemcpyAsync(c->idx.d_lab_meta, h_meta, kPlanMetaBytes, hipMemcpyHostToDevice, c->change_stream));
+    HIPCHK(c, hipMemcpyAsync(c->idx.d_lab_meta, h_meta, kPlanMetaBytes, hipMemcpyHostToDevice, change_stream(c)));
     return KSCHED_OK;
 }
 
@@ -908,7 +874,7 @@ int index_build(ksched_ctx *c, const IndexPlan &p, bool host, const int64_t *cpu
     }
     c->idx.lay = p.l;
     if (host && c->opt_index_build == 1) {
-        hipError_t e = indexed_build_host(c->idx, p.l, cpu, mem, lab, taints, c->change_stream);
+        hipError_t e = indexed_build_host(c->idx, p.l, cpu, mem, lab, taints, change_stream(c));
         if (e != hipSuccess) return fail_hip(c, e, "indexed_build_host");
     } else {
         if (int rc = launch_build_named(c)) return rc;
@@ -1066,22 +1032,20 @@ int launch_select(ksched_ctx *c, const EvalRequest &r) {
     return KSCHED_OK;
 }
 
-// the accumulators of the tile-test pick for launches on `s` (ksched_ctx::pick_acc): one buffer per stream, all zero between launches
+// the accumulators of the tile-test pick for launches on `s` (StreamRes::pick_acc): one buffer per stream, all zero between launches
 int pick_acc_for(ksched_ctx *c, uint32_t p, hipStream_t s, uint64_t **out) {
-    ksched_ctx::PickAcc *pa = nullptr;
-    for (auto &x : c->pick_acc)
-        if (x.s == s) pa = &x;
-    if (!pa) {
-        c->pick_acc.emplace_back();
-        pa = &c->pick_acc.back();
-        pa->s = s;
+    StreamRes *sr = c->order.res(s);
+    if (!sr) {  // (every evaluation goes through stream_enter first)
+        c->last_error = "the tile-test pick's stream has not been entered";
+        return KSCHED_E_STATE;
     }
+    DevBuf<uint64_t> &buf = sr->pick_acc;
     const size_t units = ((size_t)p + 7) / 8 + 8;  // one word per unit of eight pods (+ slack: the lanes past a batch's last unit compute an address, never use it)
-    if (pa->buf.cap < units) {  // (re)allocated: zero once; from then on the kernel leaves every word it used at zero
-        HIPCHK(c, pa->buf.reserve(units));
-        HIPCHK(c, hipMemsetAsync(pa->buf.ptr, 0, units * 8, s));
+    if (buf.cap < units) {  // (re)allocated: zero once; from then on the kernel leaves every word it used at zero
+        HIPCHK(c, buf.reserve(units));
+        HIPCHK(c, hipMemsetAsync(buf.ptr, 0, units * 8, s));
     }
-    *out = pa->buf.ptr;
+    *out = buf.ptr;
     return KSCHED_OK;
 }
 
@@ -1354,7 +1318,7 @@ int ksched_create(ksched_ctx **out, int device_id) try {
         delete c;
         return KSCHED_E_HIP;
     }
-    c->change_stream = c->stream;
+    c->order.set_own_stream(c->stream);
     *out = c;
     return KSCHED_OK;
 } KSCHED_ABI_CATCH(nullptr)
@@ -1365,7 +1329,7 @@ void ksched_destroy(ksched_ctx *c) try {
         DeviceGuard g(c->device);
         (void)hipDeviceSynchronize();
         if (c->h_stage) (void)hipHostFree(c->h_stage);
-        for (auto &u : c->user_streams) (void)hipEventDestroy(u.ev);
+        for (size_t i = 0; i < c->order.callers(); ++i) (void)hipEventDestroy(c->order.caller_res(i).ev);
         if (c->ev_build) (void)hipEventDestroy(c->ev_build);
         if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
         if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
@@ -1428,7 +1392,7 @@ int ksched_set_option(ksched_ctx *c, int option, int64_t value) try {
             return KSCHED_OK;
         case KSCHED_OPT_SNAPSHOT_STREAM:
             if (value != 0 && value != 1) return KSCHED_E_INVAL;
-            c->opt_own_stream = value == 1;
+            c->order.set_opt_own_stream(value == 1);
             return KSCHED_OK;
         case KSCHED_OPT_FUSED_PICK:
             if (value < 0 || value > 3) return KSCHED_E_INVAL;
@@ -1507,7 +1471,7 @@ int ksched_set_nodes(ksched_ctx *c, uint32_t n, const int64_t *cpu, const int64_
     HIPCHK(c, c->nlab.reserve((size_t)n * n_keys));
     HIPCHK(c, c->ntaint.reserve(n));
     HIPCHK(c, c->bestfit.reserve_for(n));
-    hipStream_t s = c->change_stream;  // (snapshot_begin chose it)
+    hipStream_t s = change_stream(c);  // (snapshot_begin chose it)
     // the per-tile bitmap index: layout on the host (it fixes kernel arguments and LDS sizes), contents on the device
     IndexPlan plan;
     index_plan(c, n, n_keys, lab_max, all_taints, plan);
@@ -1589,7 +1553,7 @@ int ksched_update_node_labels(ksched_ctx *c, uint32_t count, const uint32_t *nod
         if (int rc = index_reserve(c, plan, h + o_meta)) return rc;
     if (int rc = chg.upload(b_dev)) return rc;
     if (taints && !c->have_taints) {  // taints on a snapshot set without them: every other node has none
-        HIPCHK(c, hipMemsetAsync(c->ntaint.ptr, 0, (size_t)n * 8, c->change_stream));
+        HIPCHK(c, hipMemsetAsync(c->ntaint.ptr, 0, (size_t)n * 8, change_stream(c)));
         c->have_taints = true;
     }
     PatchLabelsArgs pa{};
@@ -1603,7 +1567,7 @@ int ksched_update_node_labels(ksched_ctx *c, uint32_t count, const uint32_t *nod
     pa.count = m;
     pa.n = n;
     pa.nkeys = nkeys;
-    hipLaunchKernelGGL(k_patch_labels, dim3((m + 255u) / 256u), dim3(256), 0, c->change_stream, pa);
+    hipLaunchKernelGGL(k_patch_labels, dim3((m + 255u) / 256u), dim3(256), 0, change_stream(c), pa);
     HIPCHK(c, hipGetLastError());
     if (holds) {
         // only the touched 1024-node tiles are re-indexed: their named rows and list slots (the fit part reads `available` only)
@@ -1672,7 +1636,7 @@ int ksched_update_nodes(ksched_ctx *c, uint32_t count, const uint32_t *node_inde
         for (size_t j = 0; j < tiles.size(); ++j) pa.tiles_in[j] = tiles[j];
         d_tiles = pa.tile_out;
     }
-    hipLaunchKernelGGL(k_patch_nodes, dim3((m + 255u) / 256u), dim3(256), 0, c->change_stream, pa);
+    hipLaunchKernelGGL(k_patch_nodes, dim3((m + 255u) / 256u), dim3(256), 0, change_stream(c), pa);
     HIPCHK(c, hipGetLastError());
     if (c->idx.built) {
         // only the touched 1024-node tiles are re-indexed (fit rows, search trees, cnt tables); label and taint rows are untouched
@@ -2648,12 +2612,8 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
     if (x.admit)
         if (int rc = admit_scratch_ready(c, x.count)) return rc;
     if (int rc = x.chg.begin(c)) return rc;
-    const hipStream_t s = c->change_stream;
-    if (s != x.hs) {
-        if (!c->ev_apply) HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_apply, x.hs));
-        HIPCHK(c, hipStreamWaitEvent(s, c->ev_apply, 0));
-    }
+    const hipStream_t s = change_stream(c);
+    if (int rc = apply_order_begin(c, x.hs)) return rc;
     if (int rc = apply_scratch_ready(c, s)) return rc;
     const uint32_t n = c->n;
     ApplyArgs &a = x.a;
@@ -2711,7 +2671,7 @@ int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const in
 // two sets; the keys start in set 1, so every pass reads one set and writes the other.  x.w.k0 / x.w.idx: where the last pass landed.
 int apply_admit_sort(ApplyCall &x) {
     ksched_ctx *c = x.c;
-    const hipStream_t s = c->change_stream;
+    const hipStream_t s = change_stream(c);
     AdmitArgs &w = x.w;
     const uint32_t p = w.p;
     if (p == 0) return KSCHED_OK;
@@ -2748,7 +2708,7 @@ int apply_admit_sort(ApplyCall &x) {
 // accumulate pass
 int apply_accumulate(ApplyCall &x) {
     ksched_ctx *c = x.c;
-    const hipStream_t s = c->change_stream;
+    const hipStream_t s = change_stream(c);
     if (x.q && x.a.first_per_node && x.a.n > 0) {
         hipLaunchKernelGGL(k_apply_claim_merge, dim3(std::min<uint32_t>((x.a.n + 255u) / 256u, 1024u)), dim3(256), 0, s, x.a);
         HIPCHK(c, hipGetLastError());
@@ -2764,7 +2724,7 @@ int apply_accumulate(ApplyCall &x) {
 // (the caller reads status_out there) and has then met this generation
 int apply_finish(ApplyCall &x) {
     ksched_ctx *c = x.c;
-    const hipStream_t s = c->change_stream;
+    const hipStream_t s = change_stream(c);
     if (x.a.tiles > 0) {
         if (x.admit) {  // a wave per node, four to a block
             if (x.w.p > 0) hipLaunchKernelGGL(k_apply_admit, dim3((x.w.n + 3u) / 4u), dim3(256), 0, s, x.w);
@@ -2781,11 +2741,7 @@ int apply_finish(ApplyCall &x) {
         }
     }
     if (int rc = x.chg.commit(Stale::kAvailable)) return rc;
-    if (s != x.hs) {
-        HIPCHK(c, hipStreamWaitEvent(x.hs, c->ev_build, 0));
-        stream_met(c, x.hs);
-    }
-    return KSCHED_OK;
+    return apply_order_end(c, x.hs);
 }
 
 // one grouped all-gather, on the ranks' change streams, of every rank's claims (or sums) into its apply_gath
@@ -2797,7 +2753,7 @@ int apply_allgather(ApplyCall *v, int k, bool claims, size_t count, const char *
         comms[i] = v[i].q;
         send[i] = claims ? (const void *)v[i].c->apply_claim.ptr : (const void *)v[i].c->apply_acc.ptr;
         recv[i] = v[i].c->apply_gath.ptr;
-        streams[i] = v[i].c->change_stream;
+        streams[i] = change_stream(v[i].c);
     }
     return group_allgather(comms.data(), k, send.data(), recv.data(), count, ncclUint32, streams.data(), what);
 }
