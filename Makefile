@@ -45,6 +45,8 @@ BESTFIT_LAYOUT_TEST := tests/cpp/bestfit_layout_tests
 PIPE_PLAN_TEST := tests/cpp/pipe_plan_tests
 APPLY_ADMIT_TEST := tests/cpp/apply_admit_tests
 STREAM_ORDER_TEST := tests/cpp/stream_order_tests
+MERGE_SORT_PLAN_TEST := tests/cpp/merge_sort_plan_tests
+APPLY_PLAN_TEST := tests/cpp/apply_plan_tests
 
 PMC_CALIB := tools/pmc_calib
 
@@ -72,7 +74,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
 # (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -80,7 +82,7 @@ $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 $(INDEX_TEST): tests/cpp/index_tests.cpp $(CSRC)/tile_index.hpp
 	$(CXX) -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/cpp/index_tests.cpp
 # host-only check of the evaluation plan (csrc/eval_plan.hpp: which kernels a request runs; no GPU, no HIP header): tests/test_eval_plan_host.py runs it
-$(PLAN_TEST): tests/cpp/plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp include/ksched.h
+$(PLAN_TEST): tests/cpp/plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/plan_tests.cpp
 # host-only check of a tile-kernel launch's description (csrc/tile_launch.hpp: LDS carve-up, launch geometry, argument fill, predicate dispatch; no GPU, no HIP runtime call): tests/test_tile_launch_host.py runs it
 $(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/tile_index.hpp $(CSRC)/eval_request.hpp include/ksched.h
@@ -89,13 +91,13 @@ $(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/
 $(CHANGE_TEST): tests/cpp/snapshot_change_tests.cpp $(CSRC)/snapshot_change.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/snapshot_change_tests.cpp
 # host-only check of the plan of a KSCHED_PICK_UNIFORM request (csrc/eval_plan.hpp; no GPU, no HIP header): tests/test_uniform_plan_host.py runs it
-$(UNIFORM_PLAN_TEST): tests/cpp/uniform_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp include/ksched.h
+$(UNIFORM_PLAN_TEST): tests/cpp/uniform_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/uniform_plan_tests.cpp
 # host-only check of the plan of a KSCHED_PICK_SPREAD request (csrc/eval_plan.hpp; no GPU, no HIP header): tests/test_spread_plan_host.py runs it
-$(SPREAD_PLAN_TEST): tests/cpp/spread_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp include/ksched.h
+$(SPREAD_PLAN_TEST): tests/cpp/spread_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/spread_plan_tests.cpp
 # host-only check of the numbers the best-fit structures and launches are sized by (csrc/bestfit_layout.hpp: order, row and hand-over layouts, counter rotation, debug bits; no GPU, no HIP header): tests/test_bestfit_layout_host.py runs it
-$(BESTFIT_LAYOUT_TEST): tests/cpp/bestfit_layout_tests.cpp $(CSRC)/bestfit_layout.hpp
+$(BESTFIT_LAYOUT_TEST): tests/cpp/bestfit_layout_tests.cpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/bestfit_layout_tests.cpp
 # host-only check of a pipe submit's plan (csrc/pipe_plan.hpp: streams, event waits, the slot's next state, over a happens-before model of every sequence of four submits; no GPU, no HIP header): tests/test_pipe_plan_host.py runs it
 $(PIPE_PLAN_TEST): tests/cpp/pipe_plan_tests.cpp $(CSRC)/pipe_plan.hpp include/ksched.h
@@ -106,6 +108,12 @@ $(APPLY_ADMIT_TEST): tests/cpp/apply_admit_tests.cpp $(CSRC)/apply_admit.hpp
 # host-only check of the ctx's stream ordering (csrc/stream_order.hpp: every stream wait, over a happens-before model of every sequence of up to five calls, against the rules as they were, and the steady states call by call; no GPU, no HIP header): tests/test_stream_order_host.py runs it
 $(STREAM_ORDER_TEST): tests/cpp/stream_order_tests.cpp $(CSRC)/stream_order.hpp
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/stream_order_tests.cpp
+# host-only check of the device merge sort's plan (csrc/merge_sort_plan.hpp: passes, grids and buffers of every step, executed on the CPU with the stale set poisoned, and step by step against the two drivers as they were; no GPU, no HIP header): tests/test_merge_sort_plan_host.py runs it
+$(MERGE_SORT_PLAN_TEST): tests/cpp/merge_sort_plan_tests.cpp $(CSRC)/merge_sort_plan.hpp
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/merge_sort_plan_tests.cpp
+# host-only check of an apply call's plan (csrc/apply_plan.hpp: flag verdict, scratch step, passes and grids per rank, collectives, against the five functions as they were; no GPU, no HIP header): tests/test_apply_plan_host.py runs it
+$(APPLY_PLAN_TEST): tests/cpp/apply_plan_tests.cpp $(CSRC)/apply_plan.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/apply_plan_tests.cpp
 $(LIB_HOST): $(HOST_SRCS) $(HOST_HDRS) $(LIB_HIP)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRCS) -L$(PKG) -lksched_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 # C++ tests of the host mirror (tests/cpp/host_tests.cpp; driven by tests/test_host_mirror.py)
@@ -161,4 +169,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

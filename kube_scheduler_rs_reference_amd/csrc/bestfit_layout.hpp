@@ -12,6 +12,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "merge_sort_plan.hpp"
+
 namespace ksched {
 
 // The first stage appends the pods it hands over to kBfSublists lists, wave w to list w % kBfSublists: ONE list with one counter made
@@ -35,7 +37,7 @@ struct BfOrderLayout {
     uint32_t n1 = 0, n2 = 0;  // entries of s1, s2
     bool sampled = false;     // the sampled searches apply: three rounds of 64 cover the array
     uint32_t nlev = 0, lvl_off[kBfMaxLevels] = {}, lvl_half = 0;
-    uint32_t merge_passes = 0;  // merge passes of each sort behind the runs of 1024 (kernels_build.hpp: k_sort_runs + k_merge_pass)
+    uint32_t merge_passes = 0;  // merge passes of each sort behind the runs of 1024 (merge_sort_plan.hpp)
 
     size_t sample_elems() const { return 2 * (size_t)(n1 + n2); }
     size_t level_elems() const { return 2 * (size_t)lvl_half + 8; }
@@ -58,7 +60,7 @@ inline BfOrderLayout bf_order_layout(uint32_t n) {
         off += (nk + 7u) & ~7u;  // every level starts on a 64-byte boundary and may be read in whole blocks of eight
     }
     l.lvl_half = off;
-    for (uint64_t run = 1024; run < n; run <<= 1) ++l.merge_passes;
+    l.merge_passes = merge_passes(n);
     return l;
 }
 

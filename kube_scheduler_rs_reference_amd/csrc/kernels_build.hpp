@@ -738,6 +738,8 @@ __global__ __launch_bounds__(256) void k_bf_levels(const BfLevelsArgs a) {
 // run is its index in its own run plus the number of records of the sibling run that come before it (one binary search per record;
 // the order being total, both sides count strictly smaller records).  ceil(log2(n / 1024)) passes, each a launch of n independent
 // threads; the structures are rebuilt lazily, by the first PICK_BESTFIT request after the snapshot changed (n = 50 000: 6 passes).
+// Which pass reads and writes which of the two buffer sets, the grids and the pass count are merge_sort_plan.hpp's (host-tested);
+// launch_merge_sort (ksched_api.hip) fills a SortArgs per step of that plan, for the best-fit orders and for KSCHED_APPLY_WHILE_FIT.
 // (Rounds 1 - 3 called rocPRIM's radix sort here: the one place a library did device work.)
 struct SortArgs {
     const int64_t *k0_in, *k1_in;  // k1_in == nullptr: the records have no second key

@@ -20,6 +20,7 @@
 #include <vector>
 
 
+#include "apply_plan.hpp"
 #include "bestfit_layout.hpp"
 #include "comm_rccl.hpp"
 #include "eval_plan.hpp"
@@ -31,6 +32,7 @@
 #include "kernels_summary.hpp"
 #include "kernels_pick_spread.hpp"  // (uses kernels_pick_uniform.hpp's helpers)
 #include "mask_alloc.hpp"
+#include "merge_sort_plan.hpp"
 #include "pipe_plan.hpp"
 #include "snapshot_change.hpp"
 #include "stream_order.hpp"
@@ -40,6 +42,7 @@ using namespace ksched;
 
 static_assert(kListBytes == 6144u && kTileNodes == 1024, "k_pick_bestfit_listed (kernels_direct.hpp) addresses the tile lists with these sizes");
 static_assert(kChangeTileNodes == (uint32_t)kTileNodes, "snapshot_change.hpp lists the tiles an update touches");
+static_assert(kApplyTileNodes == (uint32_t)kTileNodes && kApplyIdleClaim == kApplyUnclaimed, "apply_plan.hpp sizes the commit by the tile and bounds the global pod indexes by the idle claim");
 static_assert(sizeof(BestfitRowsArgs::lvl_off) == 4 * kBfMaxLevels && sizeof(BfLevelsArgs::lvl_off) == 4 * kBfMaxLevels, "bestfit_layout.hpp sizes the level arrays the kernels carry");
 
 namespace {
@@ -71,6 +74,23 @@ struct DevBuf {
     }
 };
 
+// the two ping-pong sets of one device merge sort (merge_sort_plan.hpp names them kSet0 / kSet1; launch_merge_sort walks a plan over
+// them).  Best fit and the apply each own one, with their own sizes and growth rules.
+struct SortScratch {
+    DevBuf<int64_t> k0[2], k1[2];
+    DevBuf<uint32_t> idx[2];
+    bool holds(size_t n) const { return n <= k0[0].cap && n <= k0[1].cap && n <= idx[0].cap && n <= idx[1].cap; }
+    hipError_t reserve(size_t n, bool second_key) {
+        hipError_t e = hipSuccess;
+        for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+            e = k0[b].reserve(n);
+            if (e == hipSuccess && second_key) e = k1[b].reserve(n);
+            if (e == hipSuccess) e = idx[b].reserve(n);
+        }
+        return e;
+    }
+};
+
 // ---- the best-fit index: buffers and state ("the best-fit pick" below builds it and launches over it) -------------------------
 // Everything a PICK_BESTFIT request reads beyond the snapshot's columns, sized by bestfit_layout.hpp.  Built lazily, by the first
 // PICK_BESTFIT request after the snapshot changed: order_stale = the order (and with it everything) is stale, rows_stale = only the
@@ -83,8 +103,7 @@ struct BestfitIndex {
     DevBuf<int64_t> samples;             // sample arrays of bf_mem and cpu_sorted (BfOrderLayout)
     DevBuf<int64_t> levels;              // 8-ary level arrays of bf_mem / cpu_sorted (k_pick_bestfit_lanes)
     DevBuf<uint64_t> rows;               // [rows][Wbf] bitmaps over best-fit positions (k_pick_bestfit_rows); built with the tile index's row numbering
-    DevBuf<int64_t> srt_k0[2], srt_k1[2];  // ping-pong sets of the orders' merge sort (kernels_build.hpp)
-    DevBuf<uint32_t> srt_idx[2];
+    SortScratch sort;                    // the orders' merge sort (bestfit_sort), n records with both keys
     DevBuf<uint32_t> handover;           // the two-stage pick's hand-over (BfHandoverLayout): counter sets in rotation, the listed mask, the sub-lists' 64-byte records
     DevBuf<uint64_t> trace;              // KSCHED_OPT_DEBUG bit 20: per-wave time stamps of the two stages (tools/bestfit_ab.py --trace)
     BfOrderLayout order;  // as of the latest build_bestfit
@@ -109,6 +128,45 @@ struct BestfitIndex {
         if (what == Stale::kEverything) rows_built = false;
     }
     bool stale() const { return order_stale || rows_stale; }
+};
+
+// ---- the apply's state (ksched_apply_bindings_device and its sharded forms, "applying a batch's bindings" below) ---------------
+// The per-node scratch, idle between calls and sized by plan_apply_scratch (apply_plan.hpp), the receive buffer of the sharded
+// forms, and the sort scratch of KSCHED_APPLY_WHILE_FIT.
+struct ApplyState {
+    DevBuf<uint64_t> acc;    // [scratch.n][4] split sums, idle 0
+    DevBuf<uint32_t> claim;  // [scratch.n] lowest eligible pod index, idle 0xFFFFFFFF
+    DevBuf<uint8_t> ovf;     // [scratch.n]
+    DevBuf<uint32_t> dirty;  // [tiles of scratch.n + 1] dirty-tile generations, initially 0
+    DevBuf<uint64_t> gath;   // ksched_apply_bindings_sharded*: every rank's acc [nranks][n][4] (or claims [nranks][n] uint32)
+    ApplyScratch scratch;    // nodes the scratch holds in its idle state, and the generation of the latest call
+    SortScratch admit_sort;  // KSCHED_APPLY_WHILE_FIT: the (node, pod) merge sort, no second key, grown on demand
+    hipEvent_t ev = nullptr;  // the caller's stream, when the change rides another one (apply_order_begin)
+
+    // a change that stopped halfway (SnapshotChange): the scratch may not be idle
+    void invalidate() { scratch.invalidate(); }
+    // the scratch in its idle state for n nodes, and the next generation; the (re)allocation and its memsets run once per snapshot
+    // size, on `s`.  A failure leaves the scratch unknown.
+    hipError_t ready(uint32_t n, hipStream_t s) {
+        const ApplyScratchStep st = plan_apply_scratch(scratch, n);
+        if (st.allocate) {
+            scratch.invalidate();
+            hipError_t e = acc.reserve(st.acc_elems);
+            if (e == hipSuccess) e = claim.reserve(st.claim_elems);
+            if (e == hipSuccess) e = ovf.reserve(st.ovf_elems);
+            if (e == hipSuccess) e = dirty.reserve(st.dirty_elems);
+            if (e == hipSuccess) e = hipMemsetAsync(acc.ptr, 0, st.acc_bytes, s);
+            if (e == hipSuccess) e = hipMemsetAsync(claim.ptr, 0xFF, st.claim_bytes, s);
+            if (e == hipSuccess) e = hipMemsetAsync(dirty.ptr, 0, st.dirty_bytes, s);
+            if (e != hipSuccess) return e;
+        }
+        scratch = st.next;
+        return hipSuccess;
+    }
+    // the admit's two sets for the plan's rows, regrown to its capacity when they do not hold them
+    hipError_t reserve_admit(const ApplyRankPlan &pl) {
+        return admit_sort.holds(pl.admit_rows) ? hipSuccess : admit_sort.reserve(pl.admit_cap, false);
+    }
 };
 
 // what the ctx keeps per stream evaluations are enqueued on: the registry is stream_order.hpp's, one entry and one lookup per stream
@@ -141,17 +199,7 @@ struct ksched_ctx {
     // update whose ids and bits stay within them keeps the layout
     uint32_t plan_lab_max[KSCHED_MAX_KEYS] = {};
     uint64_t plan_taints = 0;
-    // ksched_apply_bindings_device (kernels_build.hpp "ksched_apply_bindings_device"): per-node scratch, idle between calls
-    DevBuf<uint64_t> apply_acc;   // [apply_n][4] split sums, idle 0
-    DevBuf<uint32_t> apply_claim; // [apply_n] lowest eligible pod index, idle 0xFFFFFFFF
-    DevBuf<uint8_t> apply_ovf;    // [apply_n]
-    DevBuf<uint32_t> apply_dirty; // [tiles of apply_n + 1] dirty-tile generations, initially 0
-    DevBuf<uint64_t> apply_gath;  // ksched_apply_bindings_sharded*: every rank's acc [nranks][n][4] (or claims [nranks][n] uint32)
-    uint32_t apply_n = 0;         // nodes the scratch holds in its idle state (0 = not yet, or a failed call left it unknown)
-    uint32_t apply_gen = 0;       // generation of the latest call
-    DevBuf<int64_t> admit_k0[2];  // KSCHED_APPLY_WHILE_FIT: ping-pong sets of the (node, pod) merge sort, [p] each, grown on demand
-    DevBuf<uint32_t> admit_idx[2];
-    hipEvent_t ev_apply = nullptr;  // the caller's stream, when the change rides another one
+    ApplyState apply;  // ksched_apply_bindings_device and its sharded forms: per-node scratch, receive buffer, the admit's sort scratch
     std::string index_reason;  // why the snapshot has no bitmap index (the fused kernel is then not applicable)
     // host -> device staging for the snapshot calls: pinned, so the copies are asynchronous on the change stream
     uint8_t *h_stage = nullptr;
@@ -369,9 +417,9 @@ int snapshot_end(ksched_ctx *c) {
 // An apply whose caller stream is `hs`, behind snapshot_begin: the change also waits for what `hs` holds ...
 int apply_order_begin(ksched_ctx *c, hipStream_t hs) {
     if (!c->order.plan_apply(hs).change_waits_hs) return KSCHED_OK;
-    if (!c->ev_apply) HIPCHK(c, hipEventCreateWithFlags(&c->ev_apply, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_apply, hs));
-    HIPCHK(c, hipStreamWaitEvent(hip_stream_of(c->order.change_stream()), c->ev_apply, 0));
+    if (!c->apply.ev) HIPCHK(c, hipEventCreateWithFlags(&c->apply.ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->apply.ev, hs));
+    HIPCHK(c, hipStreamWaitEvent(hip_stream_of(c->order.change_stream()), c->apply.ev, 0));
     return KSCHED_OK;
 }
 
@@ -387,7 +435,7 @@ struct SnapshotChange {
     ~SnapshotChange() {
         if (c && !done) {
             c->have_nodes = false;
-            c->apply_n = 0;
+            c->apply.invalidate();
         }
     }
     // (ksched_set_nodes alone is armed from the start, SnapshotChange chg{c}: whatever stops it, the old snapshot is gone)
@@ -511,43 +559,48 @@ void fill_pod_operands(A &a, const ksched_ctx *c, const EvalRequest &r) {
 
 // ---- the best-fit pick: build and launches over the BestfitIndex (sized by bestfit_layout.hpp) ---------------------------------
 
-// one order by the merge sort of kernels_build.hpp: ascending (k0, k1, node) -- k1 may be null -- of the snapshot's n nodes; runs of
-// 1024 sorted in LDS, then merged by ranking, ping-pong between two sets of (k0, k1, idx) arrays; the last pass lands in dst_k0 /
-// dst_idx, the arrays the pick kernels read
-int bestfit_sort(ksched_ctx *c, const int64_t *k0, const int64_t *k1, int64_t *dst_k0, uint32_t *dst_idx) {
-    BestfitIndex &bi = c->bestfit;
-    const uint32_t n = c->n, passes = bi.order.merge_passes;
+// One device merge sort (kernels_build.hpp: k_sort_runs, k_merge_pass), as merge_sort_plan.hpp planned it, on the change stream.  The
+// plan names every step's buffers; `io` carries the caller's columns and destination arrays (SortInto::kDest), the sets are `sc`'s.
+int launch_merge_sort(ksched_ctx *c, const SortPlan &pl, const SortScratch &sc, SortBuffers io) {
     const hipStream_t s = change_stream(c);
-    if (n > (1u << 31)) {  // (the merge passes index records with 32 bits; no snapshot of that size fits a GPU's memory anyway)
+    for (int b = 0; b < 2; ++b) {
+        io.set_k0[b] = sc.k0[b].ptr;
+        io.set_k1[b] = sc.k1[b].ptr;
+        io.set_idx[b] = sc.idx[b].ptr;
+    }
+    for (uint32_t i = 0; i < pl.nsteps; ++i) {
+        const SortStep &st = pl.steps[i];
+        const SortPtrs ptr = sort_step_ptrs(pl, st, io);
+        SortArgs q{};
+        q.n = pl.n;
+        q.run = st.run;
+        q.k0_in = ptr.k0_in;
+        q.k1_in = ptr.k1_in;
+        q.idx_in = ptr.idx_in;
+        q.k0_out = ptr.k0_out;
+        q.k1_out = ptr.k1_out;
+        q.idx_out = ptr.idx_out;
+        if (st.kernel == SortKernel::kRuns) hipLaunchKernelGGL(k_sort_runs, dim3(st.grid), dim3(kSortRun), 0, s, q);
+        else hipLaunchKernelGGL(k_merge_pass, dim3(st.grid), dim3(256), 0, s, q);
+        HIPCHK(c, hipGetLastError());
+    }
+    return KSCHED_OK;
+}
+
+// one order of the snapshot's n nodes: ascending (k0, k1, node) -- k1 may be null -- from the columns into dst_k0 / dst_idx, the arrays
+// the pick kernels read (nobody reads the second key of the final order: it stays in the scratch)
+int bestfit_sort(ksched_ctx *c, const int64_t *k0, const int64_t *k1, int64_t *dst_k0, uint32_t *dst_idx) {
+    const SortPlan pl = plan_merge_sort(c->n, k1 != nullptr, SortInto::kDest);
+    if (pl.refused) {  // (no snapshot of that size fits a GPU's memory anyway)
         c->last_error = "best-fit structures: more than 2^31 nodes";
         return KSCHED_E_INVAL;
     }
-    // buffer of pass i's output: the destination arrays for the last one, the ping-pong sets before it
-    auto out_of = [&](uint32_t i, SortArgs &q) {  // i = 0: k_sort_runs, i = 1 .. passes: merge passes
-        q.k0_out = i == passes ? dst_k0 : bi.srt_k0[i & 1].ptr;
-        q.k1_out = k1 ? bi.srt_k1[i & 1].ptr : nullptr;  // (nobody reads the second key of the final order)
-        q.idx_out = i == passes ? dst_idx : bi.srt_idx[i & 1].ptr;
-    };
-    SortArgs q{};  // (no idx_in, run 0: the runs are sorted from the columns)
-    q.n = n;
-    q.k0_in = k0;
-    q.k1_in = k1;
-    out_of(0, q);
-    hipLaunchKernelGGL(k_sort_runs, dim3((n + 1023u) / 1024u), dim3(1024), 0, s, q);
-    HIPCHK(c, hipGetLastError());
-    for (uint32_t i = 1; i <= passes; ++i) {
-        SortArgs m{};
-        m.n = n;
-        m.run = 1024u << (i - 1u);
-        m.k0_in = q.k0_out;
-        m.k1_in = q.k1_out;
-        m.idx_in = q.idx_out;
-        out_of(i, m);
-        hipLaunchKernelGGL(k_merge_pass, dim3((n + 255u) / 256u), dim3(256), 0, s, m);
-        HIPCHK(c, hipGetLastError());
-        q = m;
-    }
-    return KSCHED_OK;
+    SortBuffers io;
+    io.col_k0 = k0;
+    io.col_k1 = k1;
+    io.dst_k0 = dst_k0;
+    io.dst_idx = dst_idx;
+    return launch_merge_sort(c, pl, c->bestfit.sort, io);
 }
 
 // Best-fit candidate order of the snapshot, ascending (avail_mem, avail_cpu, node), its inverse, the node
@@ -565,11 +618,7 @@ int build_bestfit(ksched_ctx *c) {
     HIPCHK(c, bi.by_cpu.reserve(n));
     HIPCHK(c, bi.cpurank.reserve(n));
     HIPCHK(c, bi.samples.reserve(o.sample_elems()));
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(c, bi.srt_k0[b].reserve(n));
-        HIPCHK(c, bi.srt_k1[b].reserve(n));
-        HIPCHK(c, bi.srt_idx[b].reserve(n));
-    }
+    HIPCHK(c, bi.sort.reserve(n, true));
     // order 1: ascending (cpu, node) -> cpu_sorted (the sorted cpu column), by_cpu (node with cpu rank r)
     if (int rc = bestfit_sort(c, c->ncpu.ptr, nullptr, bi.cpu_sorted.ptr, bi.by_cpu.ptr)) return rc;
     // order 2: ascending (mem, cpu, node) -> bf_mem, bf_order
@@ -1333,7 +1382,7 @@ void ksched_destroy(ksched_ctx *c) try {
         if (c->ev_build) (void)hipEventDestroy(c->ev_build);
         if (c->ev_stage) (void)hipEventDestroy(c->ev_stage);
         if (c->ev_scratch) (void)hipEventDestroy(c->ev_scratch);
-        if (c->ev_apply) (void)hipEventDestroy(c->ev_apply);
+        if (c->apply.ev) (void)hipEventDestroy(c->apply.ev);
         indexed_release(c->idx);
         {  // masks the caller never handed back (ksched_mask_alloc)
             MaskRegistry &reg = mask_registry();
@@ -2522,13 +2571,12 @@ int ksched_allgather_bindings_local(ksched_comm *const *comms, int n, const int3
 }  // extern "C"
 
 // ---- applying a batch's bindings (kernels_build.hpp "ksched_apply_bindings_device") ------------------------------------------------
-// One ApplyCall per rank: claim (FIRST_PER_NODE) -> accumulate of the rank's rows -> commit -> re-index of the dirty tiles -> status of
-// the rank's rows.  The single-ctx call is one rank without a communicator.  With one, each rank passes its own rows of a row-sharded
-// batch, the claims and the partial sums are all-gathered between the phases, and the commit merges them.  Everything of one rank rides
-// its ctx's change stream; the all-gathers are enqueued there too.  The runner takes each phase through every rank before the
-// collective that joins them, so the one-process form issues the per-device calls of a collective together in one group.
-// KSCHED_APPLY_WHILE_FIT (single ctx only) keeps the bracket -- apply_begin orders the change, apply_finish re-indexes and commits --
-// and runs keys -> sort by (node, pod) -> admit in place of accumulate -> commit -> status (apply_admit_sort, k_apply_admit).
+// Request, plan, launchers: apply_plan.hpp decides what a call does -- the flag verdict, the scratch step, per
+// rank the passes of each phase with their grids, per call the all-gathers -- and the functions here execute it.  One ApplyCall per
+// rank; the single-ctx call is one rank without a communicator.  With one, each rank passes its own rows of a row-sharded batch, the
+// claims and the partial sums are all-gathered between the phases, and the commit merges them.  Everything of one rank rides its
+// ctx's change stream; the all-gathers are enqueued there too.  The runner takes each phase through every rank before the collective
+// that joins them, so the one-process form issues the per-device calls of a collective together in one group.
 namespace {
 
 struct ApplyCall {
@@ -2536,250 +2584,173 @@ struct ApplyCall {
     ksched_comm *q = nullptr;  // nullptr: the single-ctx call (no collectives)
     hipStream_t hs = nullptr;  // the caller's stream
     uint32_t count = 0;        // the rank's rows
+    ApplyRankPlan plan;
     ApplyArgs a{};
-    bool admit = false;        // KSCHED_APPLY_WHILE_FIT (single-ctx only): keys, sort and admit in place of accumulate, commit and status
-    AdmitArgs w{};
+    AdmitArgs w{};             // KSCHED_APPLY_WHILE_FIT: what keys and admit take, of `a`
     SnapshotChange chg;        // done when every rank's change has been committed (apply_run)
 };
 
-dim3 pod_grid(uint32_t p) { return dim3(std::min<uint32_t>((p + 255u) / 256u, 2048u)); }
-
-// the apply scratch in its idle state for the ctx's node count, and the next generation; the (re)allocation and its memsets run once per
-// snapshot size, on `s`
-int apply_scratch_ready(ksched_ctx *c, hipStream_t s) {
-    const uint32_t n = c->n;
-    if (c->apply_n == 0 || n > c->apply_n) {  // (an empty snapshot needs the scratch too: the accumulate pass writes dirty[0])
-        c->apply_n = 0;
-        const uint32_t cap = std::max<uint32_t>(n, 1024u), cap_tiles = (cap + kTileNodes - 1) / kTileNodes;
-        HIPCHK(c, c->apply_acc.reserve((size_t)cap * 4));
-        HIPCHK(c, c->apply_claim.reserve(cap));
-        HIPCHK(c, c->apply_ovf.reserve(cap));
-        HIPCHK(c, c->apply_dirty.reserve(cap_tiles + 1u));
-        HIPCHK(c, hipMemsetAsync(c->apply_acc.ptr, 0, (size_t)cap * 32, s));
-        HIPCHK(c, hipMemsetAsync(c->apply_claim.ptr, 0xFF, (size_t)cap * 4, s));
-        HIPCHK(c, hipMemsetAsync(c->apply_dirty.ptr, 0, (size_t)(cap_tiles + 1u) * 4, s));
-        c->apply_n = cap;
-        c->apply_gen = 0;
-    }
-    if (++c->apply_gen == 0) c->apply_gen = 1;  // (0 is the initial value of every tile's entry)
-    return KSCHED_OK;
-}
-
-// flags every entry point refuses: unknown bits, and WHILE_FIT with another admission rule or with RELEASE (nothing is admitted there)
-int apply_flags_check(uint32_t flags) {
-    if (flags & ~(KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE | KSCHED_APPLY_WHILE_FIT)) return KSCHED_E_INVAL;
-    if ((flags & KSCHED_APPLY_WHILE_FIT) && (flags & (KSCHED_APPLY_FIRST_PER_NODE | KSCHED_APPLY_RELEASE))) return KSCHED_E_INVAL;
-    return KSCHED_OK;
-}
-
-// KSCHED_APPLY_WHILE_FIT: the sort's two buffer sets for p records, grown on demand (apply_begin calls this BEFORE the change begins:
-// a failed allocation leaves the snapshot as it was)
-int admit_scratch_ready(ksched_ctx *c, uint32_t p) {
-    if (p > (1u << 31)) {  // (the merge passes index records with 32 bits, as bestfit_sort)
-        c->last_error = "ksched_apply_bindings_device: KSCHED_APPLY_WHILE_FIT with more than 2^31 pods";
-        return KSCHED_E_INVAL;
-    }
-    if (p <= c->admit_k0[0].cap && p <= c->admit_k0[1].cap && p <= c->admit_idx[0].cap && p <= c->admit_idx[1].cap) return KSCHED_OK;
-    const size_t cap = std::max<size_t>((size_t)p + p / 4, 1024);
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, c->admit_k0[i].reserve(cap));
-        HIPCHK(c, c->admit_idx[i].reserve(cap));
-    }
-    return KSCHED_OK;
+// the admit's arguments from the call's filled ApplyArgs (keys, k0 and idx follow the sort: apply_launch)
+AdmitArgs admit_args_of(const ApplyArgs &a) {
+    AdmitArgs w{};
+    w.bindings = a.bindings;
+    w.req_cpu = a.req_cpu;
+    w.req_mem = a.req_mem;
+    w.ok = a.ok;
+    w.status = a.status;
+    w.dirty = a.dirty;
+    w.ncpu = a.ncpu;
+    w.nmem = a.nmem;
+    w.nrec = a.nrec;
+    w.p = a.p;
+    w.n = a.n;
+    w.tiles = a.tiles;
+    w.gen = a.gen;
+    return w;
 }
 
 // argument checks of one rank of a sharded call that need no lock and no device
 int sharded_check(ksched_ctx *c, ksched_comm *q, uint32_t count, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu,
                   const int64_t *req_mem, uint32_t flags) {
     if (!c || !q || !q->comm) return KSCHED_E_INVAL;
-    if (int rc = apply_flags_check(flags)) return rc;
-    // (admission needs every rank's requests per node, in pod order; the per-node exchange of claims and sums cannot carry that)
-    if (flags & KSCHED_APPLY_WHILE_FIT) return KSCHED_E_UNSUPPORTED;
+    if (int rc = apply_flags_verdict(flags, true)) return rc;
     if (count > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
-    if ((uint64_t)row_lo + count > (uint64_t)kApplyUnclaimed) return KSCHED_E_INVAL;  // global pod indexes stay below the idle claim
+    if (!apply_rows_in_range(row_lo, count)) return KSCHED_E_INVAL;
     if (q->device != c->device) return KSCHED_E_INVAL;
     return KSCHED_OK;
 }
 
-// phase 1 (the ctx's mutex held, its device current): order the change, ready the scratch, claim the rank's rows.  Evaluations already
-// enqueued read the snapshot as it was (snapshot_begin); the change also waits for what the caller's stream holds (the evaluation that
-// wrote `bindings`, typically).
-int apply_begin(ApplyCall &x, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
-                const uint8_t *ok, uint32_t flags, int32_t *status_out) {
+// the plan's launches of one phase, in order, on the change stream (the ctx's mutex held, its device current)
+int apply_launch(ApplyCall &x, int phase) {
     ksched_ctx *c = x.c;
-    fault_point(c);  // (nothing has changed yet)
-    x.admit = (flags & KSCHED_APPLY_WHILE_FIT) != 0u;
-    if (x.admit)
-        if (int rc = admit_scratch_ready(c, x.count)) return rc;
-    if (int rc = x.chg.begin(c)) return rc;
     const hipStream_t s = change_stream(c);
+    SortScratch &sc = c->apply.admit_sort;
+    for (const ApplyLaunch *l = x.plan.begin(phase); l != x.plan.end(phase); ++l) {
+        const dim3 grid(l->grid), block(apply_pass_block(l->pass));
+        switch (l->pass) {
+        case ApplyPass::kClaim: hipLaunchKernelGGL(k_apply_claim, grid, block, 0, s, x.a); break;
+        case ApplyPass::kClaimMerge: hipLaunchKernelGGL(k_apply_claim_merge, grid, block, 0, s, x.a); break;
+        case ApplyPass::kAccumulate: hipLaunchKernelGGL(k_apply_accumulate, grid, block, 0, s, x.a); break;
+        case ApplyPass::kKeys:  // into set 1, where a SortInto::kScratch plan reads them
+            x.w.keys = sc.k0[1].ptr;
+            hipLaunchKernelGGL(k_apply_keys, grid, block, 0, s, x.w);
+            break;
+        case ApplyPass::kSort: {  // (no second key, idx = position = the pod index); the admit reads where the last pass landed
+            if (int rc = launch_merge_sort(c, x.plan.sort, sc, SortBuffers{})) return rc;
+            const int b = x.plan.sort.landing == SortBuf::kSet1;
+            x.w.k0 = sc.k0[b].ptr;
+            x.w.idx = sc.idx[b].ptr;
+            continue;
+        }
+        case ApplyPass::kCommitLocal: hipLaunchKernelGGL(k_apply_commit, grid, block, 0, s, x.a); break;
+        case ApplyPass::kCommitGathered: hipLaunchKernelGGL(k_apply_commit_gathered, grid, block, 0, s, x.a); break;
+        case ApplyPass::kCommitAdmit: hipLaunchKernelGGL(k_apply_admit, grid, block, 0, s, x.w); break;
+        case ApplyPass::kReindex:
+            if (int rc = launch_build_fit(c, nullptr, 0, c->apply.dirty.ptr)) return rc;
+            continue;
+        case ApplyPass::kStatus: hipLaunchKernelGGL(k_apply_status, grid, block, 0, s, x.a); break;
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    return KSCHED_OK;
+}
+
+// phase 0 (the ctx's mutex held, its device current): plan the rank, order the change, ready the scratch, fill the arguments, claim the
+// rank's rows.  Evaluations already enqueued read the snapshot as it was (snapshot_begin); the change also waits for what the caller's
+// stream holds (the evaluation that wrote `bindings`, typically).
+int apply_begin(ApplyCall &x, const ApplyFacts &f, uint32_t row_lo, const int32_t *bindings, const int64_t *req_cpu,
+                const int64_t *req_mem, const uint8_t *ok, int32_t *status_out) {
+    ksched_ctx *c = x.c;
+    ApplyState &st = c->apply;
+    fault_point(c);  // (nothing has changed yet)
+    x.plan = plan_apply_rank(f, ApplyRankFacts{x.count, status_out != nullptr, c->idx.built});
+    if (x.plan.refused) {  // (the merge passes index records with 32 bits, as bestfit_sort)
+        c->last_error = "ksched_apply_bindings_device: KSCHED_APPLY_WHILE_FIT with more than 2^31 pods";
+        return KSCHED_E_INVAL;
+    }
+    if (x.plan.admit) HIPCHK(c, st.reserve_admit(x.plan));  // (BEFORE the change begins: a failed allocation leaves the snapshot as it was)
+    if (int rc = x.chg.begin(c)) return rc;
     if (int rc = apply_order_begin(c, x.hs)) return rc;
-    if (int rc = apply_scratch_ready(c, s)) return rc;
-    const uint32_t n = c->n;
+    HIPCHK(c, st.ready(c->n, change_stream(c)));
     ApplyArgs &a = x.a;
     a.bindings = bindings;
     a.req_cpu = req_cpu;
     a.req_mem = req_mem;
     a.ok = ok;
     a.status = status_out;
-    a.acc = c->apply_acc.ptr;
-    a.claim = c->apply_claim.ptr;
-    a.ovf = c->apply_ovf.ptr;
-    a.dirty = c->apply_dirty.ptr;
+    a.acc = st.acc.ptr;
+    a.claim = st.claim.ptr;
+    a.ovf = st.ovf.ptr;
+    a.dirty = st.dirty.ptr;
     a.ncpu = c->ncpu.ptr;
     a.nmem = c->nmem.ptr;
     a.nrec = c->nrec.ptr;
     a.p = x.count;
-    a.n = n;
-    a.tiles = (n + kTileNodes - 1) / kTileNodes;
-    a.gen = c->apply_gen;
-    a.first_per_node = (flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
-    a.release = (flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
+    a.n = c->n;
+    a.tiles = x.plan.tiles;
+    a.gen = st.scratch.gen;
+    a.first_per_node = (f.flags & KSCHED_APPLY_FIRST_PER_NODE) ? 1u : 0u;
+    a.release = (f.flags & KSCHED_APPLY_RELEASE) ? 1u : 0u;
     if (x.q) {
-        HIPCHK(c, c->apply_gath.reserve((size_t)x.q->nranks * n * 4));
+        HIPCHK(c, st.gath.reserve(x.plan.gather_elems));
         a.row_lo = row_lo;
         a.sharded = 1;
-        a.gathered = c->apply_gath.ptr;
+        a.gathered = st.gath.ptr;
         a.nranks = (uint32_t)x.q->nranks;
         a.rank = (uint32_t)x.q->rank;
     }
-    if (a.first_per_node && a.p > 0 && n > 0) {
-        hipLaunchKernelGGL(k_apply_claim, pod_grid(a.p), dim3(256), 0, s, a);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (x.admit) {
-        AdmitArgs &w = x.w;
-        w.bindings = bindings;
-        w.req_cpu = req_cpu;
-        w.req_mem = req_mem;
-        w.ok = ok;
-        w.status = status_out;
-        w.dirty = a.dirty;
-        w.ncpu = a.ncpu;
-        w.nmem = a.nmem;
-        w.nrec = a.nrec;
-        w.p = a.p;
-        w.n = n;
-        w.tiles = a.tiles;
-        w.gen = a.gen;
-    }
-    return KSCHED_OK;
+    if (x.plan.admit) x.w = admit_args_of(a);
+    return apply_launch(x, 0);
 }
 
-// phase 2 of KSCHED_APPLY_WHILE_FIT, in place of the accumulate pass: the pods' sort keys (and the ineligible pods' statuses), then
-// the records (node, pod index) sorted as bestfit_sort sorts -- runs of 1024 in LDS, merged by ranking, ping-pong between the ctx's
-// two sets; the keys start in set 1, so every pass reads one set and writes the other.  x.w.k0 / x.w.idx: where the last pass landed.
-int apply_admit_sort(ApplyCall &x) {
-    ksched_ctx *c = x.c;
-    const hipStream_t s = change_stream(c);
-    AdmitArgs &w = x.w;
-    const uint32_t p = w.p;
-    if (p == 0) return KSCHED_OK;
-    w.keys = c->admit_k0[1].ptr;
-    hipLaunchKernelGGL(k_apply_keys, pod_grid(p), dim3(256), 0, s, w);
-    HIPCHK(c, hipGetLastError());
-    if (w.n == 0) return KSCHED_OK;  // (every pod is UNBOUND or BAD_NODE: final)
-    SortArgs q{};  // (no second key, no idx_in: idx = position = the pod index)
-    q.n = p;
-    q.k0_in = w.keys;
-    q.k0_out = c->admit_k0[0].ptr;
-    q.idx_out = c->admit_idx[0].ptr;
-    hipLaunchKernelGGL(k_sort_runs, dim3((p + 1023u) / 1024u), dim3(1024), 0, s, q);
-    HIPCHK(c, hipGetLastError());
-    uint32_t set = 0;
-    for (uint64_t run = 1024; run < p; run <<= 1) {
-        SortArgs m{};
-        m.n = p;
-        m.run = (uint32_t)run;
-        m.k0_in = c->admit_k0[set].ptr;
-        m.idx_in = c->admit_idx[set].ptr;
-        set ^= 1u;
-        m.k0_out = c->admit_k0[set].ptr;
-        m.idx_out = c->admit_idx[set].ptr;
-        hipLaunchKernelGGL(k_merge_pass, dim3((p + 255u) / 256u), dim3(256), 0, s, m);
-        HIPCHK(c, hipGetLastError());
-    }
-    w.k0 = c->admit_k0[set].ptr;
-    w.idx = c->admit_idx[set].ptr;
-    return KSCHED_OK;
-}
-
-// phase 2: with a communicator and FIRST_PER_NODE (after the claims' all-gather), the batch's claim per node; then the rank's
-// accumulate pass
-int apply_accumulate(ApplyCall &x) {
-    ksched_ctx *c = x.c;
-    const hipStream_t s = change_stream(c);
-    if (x.q && x.a.first_per_node && x.a.n > 0) {
-        hipLaunchKernelGGL(k_apply_claim_merge, dim3(std::min<uint32_t>((x.a.n + 255u) / 256u, 1024u)), dim3(256), 0, s, x.a);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (x.a.p > 0) {
-        hipLaunchKernelGGL(k_apply_accumulate, pod_grid(x.a.p), dim3(256), 0, s, x.a);
-        HIPCHK(c, hipGetLastError());
-    }
-    return KSCHED_OK;
-}
-
-// phase 3 (with a communicator, after the partial sums' all-gather): commit, re-index, status; the caller's stream waits for the change
+// phase 2 (with a communicator, after the partial sums' all-gather): commit, re-index, status; the caller's stream waits for the change
 // (the caller reads status_out there) and has then met this generation
 int apply_finish(ApplyCall &x) {
-    ksched_ctx *c = x.c;
-    const hipStream_t s = change_stream(c);
-    if (x.a.tiles > 0) {
-        if (x.admit) {  // a wave per node, four to a block
-            if (x.w.p > 0) hipLaunchKernelGGL(k_apply_admit, dim3((x.w.n + 3u) / 4u), dim3(256), 0, s, x.w);
-        } else if (x.q) hipLaunchKernelGGL(k_apply_commit_gathered, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
-        else hipLaunchKernelGGL(k_apply_commit, dim3(x.a.tiles), dim3(kTileNodes), 0, s, x.a);
-        HIPCHK(c, hipGetLastError());
-        if (c->idx.built) {
-            // only the dirty tiles are re-indexed: every tile's block reads its generation and the clean ones exit
-            if (int rc = launch_build_fit(c, nullptr, 0, c->apply_dirty.ptr)) return rc;
-        }
-        if (!x.admit && x.a.status && x.a.p > 0) {  // (every status but OVERFLOW is final after the accumulate pass; with no node, all of them)
-            hipLaunchKernelGGL(k_apply_status, pod_grid(x.a.p), dim3(256), 0, s, x.a);
-            HIPCHK(c, hipGetLastError());
-        }
-    }
+    if (int rc = apply_launch(x, 2)) return rc;
     if (int rc = x.chg.commit(Stale::kAvailable)) return rc;
-    return apply_order_end(c, x.hs);
+    return apply_order_end(x.c, x.hs);
 }
 
-// one grouped all-gather, on the ranks' change streams, of every rank's claims (or sums) into its apply_gath
+// one grouped all-gather, on the ranks' change streams, of every rank's claims (or sums) into its receive buffer
 int apply_allgather(ApplyCall *v, int k, bool claims, size_t count, const char *what) {
     std::vector<ksched_comm *> comms(k);
     std::vector<const void *> send(k);
     std::vector<void *> recv(k), streams(k);
     for (int i = 0; i < k; ++i) {
         comms[i] = v[i].q;
-        send[i] = claims ? (const void *)v[i].c->apply_claim.ptr : (const void *)v[i].c->apply_acc.ptr;
-        recv[i] = v[i].c->apply_gath.ptr;
+        send[i] = claims ? (const void *)v[i].c->apply.claim.ptr : (const void *)v[i].c->apply.acc.ptr;
+        recv[i] = v[i].c->apply.gath.ptr;
         streams[i] = change_stream(v[i].c);
     }
     return group_allgather(comms.data(), k, send.data(), recv.data(), count, ncclUint32, streams.data(), what);
 }
 
-// the whole call over the k ranks of `v` (their mutexes held): the phases of every rank, and between them the collectives when the
-// ranks have a communicator.  Any failure leaves every ctx that entered the call invalidated (ApplyCall::chg).
+// the whole call over the k ranks of `v` (their mutexes held): the phases of every rank, and between them the collectives the plan
+// names.  Any failure leaves every ctx that entered the call invalidated (ApplyCall::chg).
 int apply_run(ApplyCall *v, int k, const uint32_t *row_lo, const int32_t *const *bindings, const int64_t *const *req_cpu,
               const int64_t *const *req_mem, const uint8_t *const *ok, uint32_t flags, int32_t *const *status_out) {
+    ApplyFacts f;
+    f.flags = flags;
+    f.comm = v[0].q != nullptr;
+    f.nranks = f.comm ? (uint32_t)v[0].q->nranks : 1u;
+    f.n = v[0].c->n;  // (replicas of one snapshot)
+    const ApplyGathers gathers = plan_apply_gathers(f);
     for (int i = 0; i < k; ++i) {
         DeviceGuard g(v[i].c->device);
         if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = apply_begin(v[i], row_lo[i], bindings[i], req_cpu[i], req_mem[i], ok ? ok[i] : nullptr, flags,
+        if (int rc = apply_begin(v[i], f, row_lo[i], bindings[i], req_cpu[i], req_mem[i], ok ? ok[i] : nullptr,
                                  status_out ? status_out[i] : nullptr))
             return rc;
     }
-    const uint32_t n = v[0].a.n;
-    const bool comm = v[0].q != nullptr;
-    if (comm && (flags & KSCHED_APPLY_FIRST_PER_NODE) && n > 0)
-        if (int rc = apply_allgather(v, k, true, n, "ncclAllGather (claims)")) return rc;
+    if (gathers.claims_words)
+        if (int rc = apply_allgather(v, k, true, gathers.claims_words, "ncclAllGather (claims)")) return rc;
     for (int i = 0; i < k; ++i) {
         DeviceGuard g(v[i].c->device);
         if (!g.ok) return KSCHED_E_HIP;
-        if (int rc = v[i].admit ? apply_admit_sort(v[i]) : apply_accumulate(v[i])) return rc;
+        if (int rc = apply_launch(v[i], 1)) return rc;
     }
-    if (comm && n > 0)  // the split sums as 32-bit words: 8 per node
-        if (int rc = apply_allgather(v, k, false, (size_t)n * 8, "ncclAllGather (sums)")) return rc;
+    if (gathers.sums_words)  // the split sums as 32-bit words: 8 per node
+        if (int rc = apply_allgather(v, k, false, gathers.sums_words, "ncclAllGather (sums)")) return rc;
     int rc = KSCHED_OK;
     for (int i = 0; i < k && !rc; ++i) {
         DeviceGuard g(v[i].c->device);
@@ -2797,7 +2768,7 @@ extern "C" {
 int ksched_apply_bindings_device(ksched_ctx *c, uint32_t p, const int32_t *bindings, const int64_t *req_cpu, const int64_t *req_mem,
                                  const uint8_t *ok, uint32_t flags, int32_t *status_out, void *hip_stream) try {
     if (!c) return KSCHED_E_INVAL;
-    if (int rc = apply_flags_check(flags)) return rc;
+    if (int rc = apply_flags_verdict(flags, false)) return rc;
     if (p > 0 && (!bindings || !req_cpu || !req_mem)) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;

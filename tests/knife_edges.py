@@ -367,6 +367,54 @@ def bestfit_window(n: int, shape: str) -> Case:
     return c
 
 
+BF_ORDER_NODES = (1024, 2048, 2049, 4097)  # one run of the orders' merge sort, exactly two, two and a record, four and a record (three passes)
+
+
+def bestfit_orders(n: int) -> Case:
+    """A snapshot on which all three levels of the best-fit order and every merge of its sort decide something: avail_mem descends in node
+    index, every value shared by the three nodes of a triple (the sorted runs of 1024 nodes come out in reverse, so each merge moves every
+    record); avail_cpu descends inside a triple, (c + 1, c, c): the second and third node tie in both and the node index decides.  Two label
+    keys, so that the snapshot has a bitmap index.  200 pods ask for exactly a triple's memory and for its c (-> the tied pair's first node),
+    c + 1 (-> the triple's first node) or c + 2 (-> on to a triple further down the order)."""
+    rng = np.random.default_rng(n)
+    T = (n + 2) // 3
+    t = np.arange(n) // 3
+    c = 2 * rng.integers(0, 40, T)
+    c[0] = 1000  # (the last triple of the order takes whatever fits nowhere else)
+    mem = (5000 + (T - 1 - t)).astype(np.int64)
+    cpu = (c[t] + (np.arange(n) % 3 == 0)).astype(np.int64)
+    labels = np.stack([1 + np.arange(n) % 3, 1 + np.arange(n) % 5]).astype(np.uint32)
+    P = 200
+    tj = np.round(np.arange(P) * (T - 1) / (P - 1)).astype(np.int64)
+    rc = c[tj] + np.array([0, 1, 0, 2])[np.arange(P) % 4]
+    rm = 5000 + (T - 1 - tj)
+    k = Case(f"bestfit_orders-{n}", cpu, mem, i64(rc), i64(rm), labels=labels, flags=FIT)
+    k.cond = bestfit_orders_conditions(k)
+    return k
+
+
+def bestfit_orders_conditions(c: Case) -> dict:
+    n = c.N
+    win = bestfit(c, feasible(c, FIT))
+    bound = win[win >= 0]
+    order = bestfit_order(c)
+    h = np.arange(0, n - 2, 3)  # the first node of every full triple
+    sharers = np.unique(c.mem, return_counts=True, return_inverse=True)
+    return {
+        "distinct_nodes_bound": int(np.unique(bound).size),
+        "unbound": int((win < 0).sum()),
+        "bound_below_1024": int((bound < 1024).sum()),
+        "bound_in_last_1024": int((bound >= n - 1024).sum()),
+        "mem_descends_in_index": bool((np.diff(c.mem) <= 0).all()),
+        "nodes_sharing_their_mem_with_two_others": int((sharers[2][sharers[1]] == 3).sum()),
+        "full_triples": int(h.size),
+        "triples_cpu_descending_with_a_tied_pair": int(((c.cpu[h] > c.cpu[h + 1]) & (c.cpu[h + 1] == c.cpu[h + 2])).sum()),
+        "label_keys": int(c.labels.shape[0]),
+        "order_is_not_index_order": int((order != np.arange(n)).sum()),
+        "winners_by_place_in_triple": np.bincount(bound % 3, minlength=3).tolist(),
+    }
+
+
 def bestfit_window_conditions(c: Case) -> dict:
     n, q = c.N, bf_q(c.N)
     win = bestfit(c, feasible(c, FIT))

@@ -163,7 +163,7 @@ def test_a_herd_on_one_node(ev, ref):
     assert want[:100].tolist() == [APPLIED] * 100 and (want[100:] == DEFERRED).all() and cpu.tolist() == [5, 0, 5]
 
 
-@pytest.mark.parametrize("P", [1, 1023, 1024, 1025, 2049])
+@pytest.mark.parametrize("P", [1, 1023, 1024, 1025, 2048, 2049, 4097])
 def test_sort_run_and_merge_boundaries_in_descending_node_order(ev, ref, P):
     """two pods per node, the batch in descending node order (the sort turns all of it round), ineligible pods interleaved; every node has
     room for one of its two pods"""

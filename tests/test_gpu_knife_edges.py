@@ -30,6 +30,8 @@ def case(name, *args):
     if name == "bestfit_window":
         c = ke.bestfit_window(*args)
         return {"set": c, "swapped": ke.swap_window_cpu(c)}
+    if name == "bestfit_orders":
+        return {"set": ke.bestfit_orders(*args)}
     if name == "selector_ids":
         c = ke.selector_ids()
         return {"set": c, "relabelled": ke.relabel(c)}
@@ -190,6 +192,26 @@ def test_bestfit_window(evaluator, n, shape):
             assert ev.last_pick == "from-mask" and ev.last_kernel == "direct", (ev.last_pick, ev.last_kernel)
             same_rows(r.binding, want["bestfit"], f"{c.name}: from the mask")
             ev.set_option(_lib.OPT_PICK_FROM_MASK, 0)
+
+
+# ---- bestfit_orders: the orders' merge sort at one run, two runs, two runs and a record, three passes ----------------------------------
+@pytest.mark.parametrize("n", ke.BF_ORDER_NODES)
+def test_bestfit_orders(evaluator, n):
+    ev = evaluator
+    c = load(ev, "bestfit_orders", "set", n)
+    want = expected(c, FIT)
+    for stages in (1, 2):
+        ev.set_option(_lib.OPT_BESTFIT_STAGES, stages)
+        r = evaluate(ev, c, FIT | PICK_BESTFIT, want_mask=False)
+        assert ev.last_pick == "bestfit-rows", ev.last_pick
+        same_rows(r.binding, want["bestfit"], f"{c.name} stages {stages}: bindings only")
+    ev.set_option(_lib.OPT_BESTFIT_STAGES, 0)  # the mask-reading best fit behind the direct kernel
+    ev.set_option(_lib.OPT_PICK_FROM_MASK, 1)
+    ev.set_kernel("direct")
+    r = evaluate(ev, c, FIT | PICK_BESTFIT)
+    assert ev.last_pick == "from-mask" and ev.last_kernel == "direct", (ev.last_pick, ev.last_kernel)
+    same_rows(r.binding, want["bestfit"], f"{c.name}: from the mask")
+    same_rows(r.feasible, want["feasible"], f"{c.name}: the mask")
 
 
 # ---- selector_ids: label ids with bit 31 set, the ends of the list keys' searches ---------------------------------------------------------

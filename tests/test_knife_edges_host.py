@@ -104,6 +104,25 @@ def test_bestfit_window_conditions_and_reference(n, shape):
     pin_against_the_oracle(c2, [ke.FIT])
 
 
+@pytest.mark.parametrize("n", ke.BF_ORDER_NODES)
+def test_bestfit_orders_conditions_and_reference(n):
+    c = ke.bestfit_orders(n)
+    k = c.cond
+    print(c.name, k)
+    assert c.N == n and c.P == 200 and k["label_keys"] == 2
+    assert k["distinct_nodes_bound"] >= 150 and k["unbound"] == 0
+    assert k["bound_below_1024"] >= 1 and k["bound_in_last_1024"] >= 1
+    # memory descends in node index, every value shared by three nodes (the last one by n % 3 when that is not 0) ...
+    assert k["mem_descends_in_index"] and k["nodes_sharing_their_mem_with_two_others"] == n - n % 3 and k["full_triples"] == n // 3
+    # ... cpu descends inside every triple, whose last two nodes tie in both columns
+    assert k["triples_cpu_descending_with_a_tied_pair"] == n // 3
+    assert k["order_is_not_index_order"] >= n - 3
+    # winners are first nodes of a triple (cpu decided) and first nodes of a tied pair (the index decided), never the pair's second node
+    w = k["winners_by_place_in_triple"]
+    assert w[0] >= 40 and w[1] >= 40 and w[2] == 0, w
+    pin_against_the_oracle(c, [ke.FIT])
+
+
 def test_selector_ids_conditions_and_reference():
     c = ke.selector_ids()
     k = c.cond
