@@ -146,7 +146,8 @@ SAN_SRCS := tests/cpp/host_tests.cpp $(HOST_SRCS)
 SAN_FLAGS := -O1 -g -std=c++17 -fPIC -Wall -Wextra -Iinclude -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -fno-omit-frame-pointer
 SAN_LINK := -Ltests/cpp/hooks -lksched_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../../tests/cpp/hooks' -Wl,-rpath,/opt/rocm/lib -lpthread -ldl
 SAN_OBJ_SRCS := tests/cpp/objects_eval.cpp $(HOST_SRCS)
-sanitize: $(SAN_DIR)/host_tests_asan $(SAN_DIR)/host_tests_tsan $(SAN_DIR)/objects_eval_asan $(SAN_DIR)/objects_eval_tsan
+SAN_NODE_SRCS := tests/cpp/node_events_tests.cpp $(HOST_SRCS)
+sanitize: $(SAN_DIR)/host_tests_asan $(SAN_DIR)/host_tests_tsan $(SAN_DIR)/objects_eval_asan $(SAN_DIR)/objects_eval_tsan $(SAN_DIR)/node_events_tests_asan
 $(SAN_DIR)/asan/%.o: %.cpp $(HOST_HDRS)
 	mkdir -p $(dir $@)
 	$(CXX) $(SAN_FLAGS) -fsanitize=address,undefined -c -o $@ $<
@@ -159,6 +160,9 @@ $(SAN_DIR)/objects_eval_asan: $(SAN_OBJ_SRCS:%.cpp=$(SAN_DIR)/asan/%.o) $(LIB_HI
 	$(CXX) -fsanitize=address,undefined -o $@ $(SAN_OBJ_SRCS:%.cpp=$(SAN_DIR)/asan/%.o) $(SAN_LINK)
 $(SAN_DIR)/objects_eval_tsan: $(SAN_OBJ_SRCS:%.cpp=$(SAN_DIR)/tsan/%.o) $(LIB_HIP_TEST)
 	$(CXX) -fsanitize=thread -o $@ $(SAN_OBJ_SRCS:%.cpp=$(SAN_DIR)/tsan/%.o) $(SAN_LINK)
+# the node-event sequences and the seeded walk (node_events_tests cpu / walk: encode-only, no device call) under AddressSanitizer + UBSan
+$(SAN_DIR)/node_events_tests_asan: $(SAN_NODE_SRCS:%.cpp=$(SAN_DIR)/asan/%.o) $(LIB_HIP_TEST)
+	$(CXX) -fsanitize=address,undefined -o $@ $(SAN_NODE_SRCS:%.cpp=$(SAN_DIR)/asan/%.o) $(SAN_LINK)
 $(SAN_DIR)/host_tests_asan: $(SAN_SRCS:%.cpp=$(SAN_DIR)/asan/%.o) $(LIB_HIP_TEST)
 	$(CXX) -fsanitize=address,undefined -o $@ $(SAN_SRCS:%.cpp=$(SAN_DIR)/asan/%.o) $(SAN_LINK)
 $(SAN_DIR)/host_tests_tsan: $(SAN_SRCS:%.cpp=$(SAN_DIR)/tsan/%.o) $(LIB_HIP_TEST)

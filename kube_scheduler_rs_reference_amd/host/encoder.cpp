@@ -88,6 +88,103 @@ bool toleration_matches(const corev1::Toleration &t, const TaintId &x) {
     return op == "Equal" && t.value.value_or("") == value;
 }
 
+// what the predicates read of one node: allocatable (src/predicates.rs:27-32), labels (:45-61), the counted taints (extension E2)
+Snapshot::NodeState Snapshot::read_node(const corev1::Node &node, const std::string &name, bool with_resources) {
+    NodeState r;
+    if (with_resources && node.status && node.status->allocatable) {  // (a node without allocatable offers nothing)
+        const auto &al = *node.status->allocatable;
+        auto cpu = al.find("cpu"), mem = al.find("memory");
+        if (cpu == al.end() || mem == al.end())
+            throw EncodeError("node " + name + ": allocatable lacks cpu or memory (reference panics, src/predicates.rs:29-31)");
+        try {
+            r.avail_cpu = r.alloc_cpu = ParsedQuantity::try_from(cpu->second).nanos();
+            r.avail_mem = r.alloc_mem = ParsedQuantity::try_from(mem->second).nanos();
+        } catch (const QuantityError &e) {
+            throw EncodeError("node " + name + ": invalid node spec: " + e.what());
+        }
+    }
+    if (node.metadata.labels) {
+        r.labels = *node.metadata.labels;
+        r.has_labels = true;
+    }
+    if (node.spec && node.spec->taints)
+        for (const auto &t : *node.spec->taints)  // PreferNoSchedule never filters
+            if (t.effect == "NoSchedule" || t.effect == "NoExecute") r.taints.emplace_back(t.key, t.value.value_or(""), t.effect);
+    return r;
+}
+
+void Snapshot::list_node(PodLister *client, const std::string &name, uint32_t canonical, NodeState &node, CountedTable &counted) {
+    ++client->list_calls;
+    for (const auto &p : client->list_pods_on_node(name)) {
+        try {
+            const PodResources r = total_pod_resources(p);
+            node.avail_cpu -= r.cpu.nanos();
+            node.avail_mem -= r.memory.nanos();
+            counted[full_name(p.metadata)] = Counted{canonical, r.cpu.nanos(), r.memory.nanos()};  // observe_pods() starts from the LISTs
+        } catch (const QuantityError &e) {
+            throw EncodeError("pod " + full_name(p.metadata) + ": invalid pod spec: " + e.what());
+        }
+    }
+}
+
+std::pair<__int128, __int128> Snapshot::choose_units(const std::vector<__int128> &cpu, const std::vector<__int128> &mem, const std::vector<std::string> &names,
+                                                     const std::vector<uint32_t> *diagnose, const UnitWording &w) {
+    // the unit of each resource column: the coarsest one in which every node's `available` is a whole int64 number (encoder.hpp)
+    const __int128 cpu_unit = choose_unit(cpu, kCpuUnits), mem_unit = choose_unit(mem, kMemUnits);
+    if (cpu_unit && mem_unit) return {cpu_unit, mem_unit};
+    for (size_t k = 0, count = !w.node ? 0 : diagnose ? diagnose->size() : cpu.size(); k < count; ++k) {
+        const size_t i = diagnose ? (*diagnose)[k] : k;
+        if (!choose_unit(std::vector<__int128>{cpu[i]}, kCpuUnits) || !choose_unit(std::vector<__int128>{mem[i]}, kMemUnits))
+            throw EncodeError("node " + names[i] + w.node);
+    }
+    throw EncodeError(w.common);
+}
+
+Snapshot::NodeSet Snapshot::encode_node_set(std::vector<std::string> names, std::vector<NodeState> nodes, std::vector<uint32_t> store_of_canonical,
+                                            CountedTable counted, const UnitWording &w) const {
+    const uint32_t n = (uint32_t)nodes.size();
+    NodeSet s;
+    std::vector<__int128> cpu(n), mem(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        cpu[i] = nodes[i].avail_cpu;
+        mem[i] = nodes[i].avail_mem;
+        s.any_counted_taint = s.any_counted_taint || !nodes[i].taints.empty();
+    }
+    std::tie(s.cpu_unit, s.mem_unit) = choose_units(cpu, mem, names, nullptr, w);
+    s.cols.n = n;
+    s.cols.avail_cpu_milli.resize(n);
+    s.cols.avail_mem_bytes.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        s.cols.avail_cpu_milli[i] = (int64_t)(cpu[i] / s.cpu_unit);
+        s.cols.avail_mem_bytes[i] = (int64_t)(mem[i] / s.mem_unit);
+    }
+    s.cols.taints.assign(n, 0);
+    if (taints_enabled_) intern_taints_into(nodes, s.taint_ids, s.cols.taints);  // "more than 64": the extension stays on across rebuilds
+    s.canonical_of_store.resize(n);
+    for (uint32_t i = 0; i < n; ++i) s.canonical_of_store[store_of_canonical[i]] = i;
+    s.cols.names = std::move(names);
+    s.nodes = std::move(nodes);
+    s.store_of_canonical = std::move(store_of_canonical);
+    s.counted = std::move(counted);
+    return s;
+}
+
+// (nothing here throws an EncodeError about the INPUT; a failing device call is remembered, see upload())
+void Snapshot::commit_node_set(NodeSet &&s) {
+    s.cols.keys = std::move(cols_.keys);  // keep the label columns that were in use
+    cols_ = std::move(s.cols);
+    nodes_ = std::move(s.nodes);
+    counted_ = std::move(s.counted);
+    store_of_canonical_ = std::move(s.store_of_canonical);
+    canonical_of_store_ = std::move(s.canonical_of_store);
+    cpu_unit_ = s.cpu_unit;
+    mem_unit_ = s.mem_unit;
+    any_counted_taint_ = s.any_counted_taint;
+    if (taints_enabled_) taint_ids_ = std::move(s.taint_ids);
+    encode_labels();
+    upload();
+}
+
 void Snapshot::rebuild(const std::vector<corev1::Node> &nodes, PodLister *client, bool with_resources) {
     // Everything is staged in locals and committed at the end: an EncodeError (a node or a LISTed pod that cannot be encoded, more
     // than 64 distinct taints with the extension on) leaves the snapshot -- host bookkeeping AND device -- exactly as it was.
@@ -97,122 +194,40 @@ void Snapshot::rebuild(const std::vector<corev1::Node> &nodes, PodLister *client
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
         return corev1::name_any(nodes[a].metadata) < corev1::name_any(nodes[b].metadata);
     });
-    std::vector<uint32_t> canonical_of_store(n, 0u);
-    for (uint32_t i = 0; i < n; ++i) canonical_of_store[order[i]] = i;
-    NodeColumns c;
+    std::vector<std::string> names(n);
+    std::vector<NodeState> states(n);
     CountedTable counted;
-    std::vector<__int128> cpu_nanos(n, 0), mem_nanos(n, 0), alloc_cpu(n, 0), alloc_mem(n, 0);
-    c.n = n;
-    c.names.resize(n);
-    c.avail_cpu_milli.resize(n);
-    c.avail_mem_bytes.resize(n);
-    c.taints.assign(n, 0);
-    std::vector<corev1::StringMap> labels(n);
-    std::vector<bool> has_labels(n, false);
-    std::vector<std::vector<TaintId>> taints_raw(n);
-    bool any_taint = false;
     for (uint32_t i = 0; i < n; ++i) {
-        const corev1::Node &node = nodes[order[i]];
-        c.names[i] = corev1::name_any(node.metadata);
-        // src/predicates.rs:27-32
-        PodResources avail;
-        if (with_resources && node.status && node.status->allocatable) {
-            const auto &al = *node.status->allocatable;
-            auto cpu = al.find("cpu"), mem = al.find("memory");
-            if (cpu == al.end() || mem == al.end())
-                throw EncodeError("node " + c.names[i] + ": allocatable lacks cpu or memory (reference panics, src/predicates.rs:29-31)");
-            try {
-                avail.cpu = ParsedQuantity::try_from(cpu->second);
-                avail.memory = ParsedQuantity::try_from(mem->second);
-            } catch (const QuantityError &e) {
-                throw EncodeError("node " + c.names[i] + ": invalid node spec: " + e.what());
-            }
-        }
-        alloc_cpu[i] = avail.cpu.nanos();
-        alloc_mem[i] = avail.memory.nanos();
-        // src/predicates.rs:34-38: every pod the LIST returns is subtracted, any phase
-        if (with_resources && client) {
-            ++client->list_calls;
-            for (const auto &p : client->list_pods_on_node(c.names[i])) {
-                try {
-                    const PodResources r = total_pod_resources(p);
-                    avail -= r;
-                    counted[full_name(p.metadata)] = Counted{i, r.cpu.nanos(), r.memory.nanos()};  // observe_pods() starts from the LISTs
-                } catch (const QuantityError &e) {
-                    throw EncodeError("pod " + full_name(p.metadata) + ": invalid pod spec: " + e.what());
-                }
-            }
-        }
-        cpu_nanos[i] = avail.cpu.nanos();
-        mem_nanos[i] = avail.memory.nanos();
-        if (node.metadata.labels) {
-            labels[i] = *node.metadata.labels;
-            has_labels[i] = true;
-        }
-        if (node.spec && node.spec->taints) {
-            for (const auto &t : *node.spec->taints) {
-                if (t.effect != "NoSchedule" && t.effect != "NoExecute") continue;  // PreferNoSchedule never filters
-                taints_raw[i].emplace_back(t.key, t.value.value_or(""), t.effect);
-                any_taint = true;
-            }
-        }
+        names[i] = corev1::name_any(nodes[order[i]].metadata);
+        states[i] = read_node(nodes[order[i]], names[i], with_resources);
+        if (with_resources && client) list_node(client, names[i], i, states[i], counted);
     }
-    // the unit of each resource column: the coarsest one in which every node's `available` is a whole int64 number (encoder.hpp)
-    const __int128 cpu_unit = choose_unit(cpu_nanos, kCpuUnits), mem_unit = choose_unit(mem_nanos, kMemUnits);
-    if (!cpu_unit || !mem_unit) {
-        for (uint32_t i = 0; i < n; ++i) {
-            const std::vector<__int128> one_c{cpu_nanos[i]}, one_m{mem_nanos[i]};
-            if (!choose_unit(one_c, kCpuUnits) || !choose_unit(one_m, kMemUnits))
-                throw EncodeError("node " + c.names[i] + ": outside the exact integer domain: available does not fit int64 in any unit fine enough to hold it");
-        }
-        throw EncodeError("the nodes' available values do not fit int64 in one common unit (one node needs nano-units, another is too large for them)");
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-        c.avail_cpu_milli[i] = (int64_t)(cpu_nanos[i] / cpu_unit);
-        c.avail_mem_bytes[i] = (int64_t)(mem_nanos[i] / mem_unit);
-    }
-    std::map<TaintId, uint32_t> ids;
-    if (taints_enabled_) intern_taints_into(taints_raw, ids, c.taints);  // throws BEFORE anything is committed; the extension stays on across rebuilds
-    // ---- commit (nothing below throws an EncodeError about the INPUT; a failing device call is remembered, see upload()) ----
-    c.keys = cols_.keys;  // keep the label columns that were in use
-    cols_ = std::move(c);
-    avail_cpu_nanos_ = std::move(cpu_nanos);
-    avail_mem_nanos_ = std::move(mem_nanos);
-    alloc_cpu_nanos_ = std::move(alloc_cpu);
-    alloc_mem_nanos_ = std::move(alloc_mem);
-    cpu_unit_ = cpu_unit;
-    mem_unit_ = mem_unit;
-    counted_ = std::move(counted);
-    store_of_canonical_ = std::move(order);
-    canonical_of_store_ = std::move(canonical_of_store);
-    node_labels_ = std::move(labels);
-    node_has_labels_ = std::move(has_labels);
-    node_taints_raw_ = std::move(taints_raw);
-    any_counted_taint_ = any_taint;
-    if (taints_enabled_) taint_ids_ = std::move(ids);
-    encode_labels();
-    upload();
+    commit_node_set(encode_node_set(std::move(names), std::move(states), std::move(order), std::move(counted),
+                                    {": outside the exact integer domain: available does not fit int64 in any unit fine enough to hold it",
+                                     "the nodes' available values do not fit int64 in one common unit (one node needs nano-units, another is too large for them)"}));
 }
 
 // Extension E2: (key, value, effect) triples -> bit positions, at most 64 per snapshot.
-void Snapshot::intern_taints_into(const std::vector<std::vector<TaintId>> &raw, std::map<TaintId, uint32_t> &ids, std::vector<uint64_t> &column) {
+uint32_t Snapshot::taint_bit(std::map<TaintId, uint32_t> &ids, const TaintId &taint) {
+    auto it = ids.find(taint);
+    if (it == ids.end()) {
+        if (ids.size() >= 64) throw EncodeError("taint extension: more than 64 distinct NoSchedule/NoExecute taints in one snapshot");
+        it = ids.emplace(taint, (uint32_t)ids.size()).first;
+    }
+    return it->second;
+}
+
+void Snapshot::intern_taints_into(const std::vector<NodeState> &nodes, std::map<TaintId, uint32_t> &ids, std::vector<uint64_t> &column) {
     ids.clear();
-    column.assign(raw.size(), 0ull);
-    for (size_t i = 0; i < raw.size(); ++i)
-        for (const TaintId &id : raw[i]) {
-            auto it = ids.find(id);
-            if (it == ids.end()) {
-                if (ids.size() >= 64) throw EncodeError("taint extension: more than 64 distinct NoSchedule/NoExecute taints in one snapshot");
-                it = ids.emplace(id, (uint32_t)ids.size()).first;
-            }
-            column[i] |= 1ull << it->second;
-        }
+    column.assign(nodes.size(), 0ull);
+    for (size_t i = 0; i < nodes.size(); ++i)
+        for (const TaintId &id : nodes[i].taints) column[i] |= 1ull << taint_bit(ids, id);
 }
 
 void Snapshot::intern_taints() {
     std::map<TaintId, uint32_t> ids;
     std::vector<uint64_t> column;
-    intern_taints_into(node_taints_raw_, ids, column);  // (throws before anything changes)
+    intern_taints_into(nodes_, ids, column);  // (throws before anything changes)
     taint_ids_ = std::move(ids);
     cols_.taints = std::move(column);
 }
@@ -232,8 +247,8 @@ void Snapshot::encode_labels() {
     for (uint32_t k = 0; k < cols_.n_keys; ++k) {
         auto &dict = value_ids_[k];
         for (uint32_t i = 0; i < n; ++i) {
-            auto it = node_labels_[i].find(cols_.keys[k]);
-            if (it == node_labels_[i].end()) continue;  // 0 = key absent on this node
+            auto it = nodes_[i].labels.find(cols_.keys[k]);
+            if (it == nodes_[i].labels.end()) continue;  // 0 = key absent on this node
             auto [d, fresh] = dict.emplace(it->second, (uint32_t)dict.size() + 1u);
             (void)fresh;
             cols_.label_val_ids[(size_t)k * n + i] = d->second;  // "" is a value like any other: non-zero id
@@ -269,7 +284,7 @@ size_t Snapshot::apply_pod_events(const std::vector<std::pair<const corev1::Pod 
             throw EncodeError("pod " + full_name(pod->metadata) + ": invalid pod spec: " + e.what());
         }
         auto it = fresh_of.find((uint32_t)idx);
-        if (it == fresh_of.end()) it = fresh_of.emplace((uint32_t)idx, std::make_pair(avail_cpu_nanos_[(size_t)idx], avail_mem_nanos_[(size_t)idx])).first;
+        if (it == fresh_of.end()) it = fresh_of.emplace((uint32_t)idx, std::make_pair(nodes_[(size_t)idx].avail_cpu, nodes_[(size_t)idx].avail_mem)).first;
         it->second.first += bound ? -dc : dc;
         it->second.second += bound ? -dm : dm;
         ++applied;
@@ -297,36 +312,34 @@ void Snapshot::store_available(const std::vector<uint32_t> &nodes, const std::ve
         // (a coarser unit may have become possible again; it is only looked for by the next rebuild -- the comparison is exact in any unit)
         commit();
         for (size_t i = 0; i < nodes.size(); ++i) {
-            avail_cpu_nanos_[nodes[i]] = fresh[i].first;
-            avail_mem_nanos_[nodes[i]] = fresh[i].second;
+            nodes_[nodes[i]].avail_cpu = fresh[i].first;
+            nodes_[nodes[i]].avail_mem = fresh[i].second;
             cols_.avail_cpu_milli[nodes[i]] = (int64_t)(fresh[i].first / cpu_unit_);
             cols_.avail_mem_bytes[nodes[i]] = (int64_t)(fresh[i].second / mem_unit_);
         }
         push_rows(nodes);
         return;
     }
-    std::vector<__int128> cpu_all = avail_cpu_nanos_, mem_all = avail_mem_nanos_;
+    std::vector<__int128> cpu_all(cols_.n), mem_all(cols_.n);
+    for (uint32_t i = 0; i < cols_.n; ++i) {
+        cpu_all[i] = nodes_[i].avail_cpu;
+        mem_all[i] = nodes_[i].avail_mem;
+    }
     for (size_t i = 0; i < nodes.size(); ++i) {
         cpu_all[nodes[i]] = fresh[i].first;
         mem_all[nodes[i]] = fresh[i].second;
     }
-    const __int128 cpu_unit = choose_unit(cpu_all, kCpuUnits), mem_unit = choose_unit(mem_all, kMemUnits);
-    if (!cpu_unit || !mem_unit) {
-        for (size_t i = 0; i < nodes.size(); ++i) {
-            const std::vector<__int128> one_c{fresh[i].first}, one_m{fresh[i].second};
-            if (!choose_unit(one_c, kCpuUnits) || !choose_unit(one_m, kMemUnits))
-                throw EncodeError("node " + cols_.names[nodes[i]] + ": available leaves the int64 domain (in the unit its fineness needs)");
-        }
-        throw EncodeError("the nodes' available values do not fit int64 in one common unit after this change");
-    }
+    const auto [cpu_unit, mem_unit] = choose_units(cpu_all, mem_all, cols_.names, &nodes,
+                                                   {": available leaves the int64 domain (in the unit its fineness needs)",
+                                                    "the nodes' available values do not fit int64 in one common unit after this change"});
     commit();
-    avail_cpu_nanos_ = std::move(cpu_all);
-    avail_mem_nanos_ = std::move(mem_all);
     cpu_unit_ = cpu_unit;
     mem_unit_ = mem_unit;
     for (uint32_t i = 0; i < cols_.n; ++i) {
-        cols_.avail_cpu_milli[i] = (int64_t)(avail_cpu_nanos_[i] / cpu_unit_);
-        cols_.avail_mem_bytes[i] = (int64_t)(avail_mem_nanos_[i] / mem_unit_);
+        nodes_[i].avail_cpu = cpu_all[i];
+        nodes_[i].avail_mem = mem_all[i];
+        cols_.avail_cpu_milli[i] = (int64_t)(cpu_all[i] / cpu_unit_);
+        cols_.avail_mem_bytes[i] = (int64_t)(mem_all[i] / mem_unit_);
     }
     upload();  // every row changed its scale: the whole snapshot goes up (pods are encoded against the new unit from now on)
 }
@@ -521,7 +534,7 @@ std::shared_ptr<Snapshot::StagedUpdate> Snapshot::stage_impl(const std::vector<O
     auto add = [&](uint32_t node, const std::pair<__int128, __int128> &d) {
         if (d.first == 0 && d.second == 0) return;
         S.touched.push_back(node);
-        S.fresh.emplace_back(avail_cpu_nanos_[node] + d.first, avail_mem_nanos_[node] + d.second);
+        S.fresh.emplace_back(nodes_[node].avail_cpu + d.first, nodes_[node].avail_mem + d.second);
     };
     if (dense) {
         std::sort(nodes.begin(), nodes.end());
@@ -703,230 +716,140 @@ PodColumns Snapshot::encode_pods(const std::vector<const corev1::Pod *> &pods, c
 }
 
 // ---- node watch events (observe_nodes) ------------------------------------------------------------------------------------------
-namespace {
-// what the predicates read of one node: allocatable (src/predicates.rs:27-32), labels (:45-61), the counted taints (extension E2)
-struct NodeRead {
-    __int128 alloc_cpu = 0, alloc_mem = 0;
-    bool has_labels = false;
-    corev1::StringMap labels;
-    std::vector<TaintId> taints;
-};
-NodeRead read_node(const corev1::Node &node, const std::string &name) {
-    NodeRead r;
-    if (node.status && node.status->allocatable) {  // (as rebuild: a node without allocatable offers nothing)
-        const auto &al = *node.status->allocatable;
-        auto cpu = al.find("cpu"), mem = al.find("memory");
-        if (cpu == al.end() || mem == al.end())
-            throw EncodeError("node " + name + ": allocatable lacks cpu or memory (reference panics, src/predicates.rs:29-31)");
-        try {
-            r.alloc_cpu = ParsedQuantity::try_from(cpu->second).nanos();
-            r.alloc_mem = ParsedQuantity::try_from(mem->second).nanos();
-        } catch (const QuantityError &e) {
-            throw EncodeError("node " + name + ": invalid node spec: " + e.what());
-        }
-    }
-    if (node.metadata.labels) {
-        r.labels = *node.metadata.labels;
-        r.has_labels = true;
-    }
-    if (node.spec && node.spec->taints)
-        for (const auto &t : *node.spec->taints)
-            if (t.effect == "NoSchedule" || t.effect == "NoExecute") r.taints.emplace_back(t.key, t.value.value_or(""), t.effect);
-    return r;
-}
-}  // namespace
-
-size_t Snapshot::observe_nodes(const std::vector<std::pair<NodeEvent, const corev1::Node *>> &events, PodLister *client) {
-    const uint32_t n = cols_.n;
-    bool structural = false;  // a node joins or leaves: the canonical order changes
+size_t Snapshot::observe_nodes(const NodeEvents &events, PodLister *client) {
     for (const auto &[kind, node] : events) {
-        const int idx = index_of(corev1::name_any(node->metadata));
-        if ((kind == NodeEvent::Applied && idx < 0) || (kind == NodeEvent::Deleted && idx >= 0)) structural = true;
+        const bool known = index_of(corev1::name_any(node->metadata)) >= 0;
+        if (kind == NodeEvent::Applied ? !known : known) return observe_node_set(events, client);  // a node joins or leaves: the canonical order changes
     }
-    // ---- the nodes of this snapshot only: a diff, applied as row updates --------------------------------------------------------
-    if (!structural) {
-        std::map<uint32_t, NodeRead> now;  // canonical index -> the node as it is now (events taken in order)
-        size_t changed = 0;
-        auto taints_of = [&](uint32_t i) -> const std::vector<TaintId> & { auto it = now.find(i); return it == now.end() ? node_taints_raw_[i] : it->second.taints; };
-        for (const auto &[kind, node] : events) {
-            if (kind != NodeEvent::Applied) continue;  // (a Deleted event names no node of the snapshot here)
-            const std::string name = corev1::name_any(node->metadata);
-            const uint32_t i = (uint32_t)index_of(name);
-            NodeRead r = read_node(*node, name);
-            auto it = now.find(i);
-            const bool same_res = it != now.end() ? (r.alloc_cpu == it->second.alloc_cpu && r.alloc_mem == it->second.alloc_mem)
-                                                   : (r.alloc_cpu == alloc_cpu_nanos_[i] && r.alloc_mem == alloc_mem_nanos_[i]);
-            const bool same_lab = it != now.end() ? (r.has_labels == it->second.has_labels && r.labels == it->second.labels)
-                                                   : (r.has_labels == node_has_labels_[i] && r.labels == node_labels_[i]);
-            const bool same_taints = !taints_enabled_ || r.taints == taints_of(i);
-            if (!(same_res && same_lab && same_taints)) ++changed;
-            if (it != now.end()) it->second = std::move(r);
-            else if (!(same_res && same_lab && r.taints == node_taints_raw_[i])) now.emplace(i, std::move(r));
-        }
-        if (now.empty()) return changed;
-        // everything the change needs, computed before anything is committed
-        std::vector<uint32_t> res_nodes, lab_nodes;
-        std::vector<std::pair<__int128, __int128>> res_fresh;
-        std::map<TaintId, uint32_t> ids = taint_ids_;
-        std::vector<std::map<std::string, uint32_t>> fresh_values(cols_.n_keys);  // values new to a column -> their ids
-        std::map<uint32_t, std::vector<uint32_t>> lab_rows;                         // node -> its new ids of every column
-        std::map<uint32_t, uint64_t> taint_rows;
-        for (const auto &[i, r] : now) {
-            if (r.alloc_cpu != alloc_cpu_nanos_[i] || r.alloc_mem != alloc_mem_nanos_[i]) {
-                res_nodes.push_back(i);
-                res_fresh.emplace_back(avail_cpu_nanos_[i] + (r.alloc_cpu - alloc_cpu_nanos_[i]), avail_mem_nanos_[i] + (r.alloc_mem - alloc_mem_nanos_[i]));
-            }
-            bool dev = false;
-            std::vector<uint32_t> row(cols_.n_keys, 0u);
-            for (uint32_t k = 0; k < cols_.n_keys; ++k) {
-                auto v = r.labels.find(cols_.keys[k]);
-                if (v != r.labels.end()) {
-                    auto known = value_ids_[k].find(v->second);
-                    if (known != value_ids_[k].end()) {
-                        row[k] = known->second;
-                    } else {
-                        auto [f, _] = fresh_values[k].emplace(v->second, (uint32_t)(value_ids_[k].size() + fresh_values[k].size() + 1u));
-                        row[k] = f->second;
-                    }
-                }
-                dev = dev || row[k] != cols_.label_val_ids[(size_t)k * n + i];
-            }
-            uint64_t bits = 0;
-            if (taints_enabled_) {
-                for (const TaintId &t : r.taints) {
-                    auto it = ids.find(t);
-                    if (it == ids.end()) {
-                        if (ids.size() >= 64) throw EncodeError("taint extension: more than 64 distinct NoSchedule/NoExecute taints in one snapshot");
-                        it = ids.emplace(t, (uint32_t)ids.size()).first;
-                    }
-                    bits |= 1ull << it->second;
-                }
-                dev = dev || bits != cols_.taints[i];
-            }
-            if (dev) {
-                lab_nodes.push_back(i);
-                lab_rows[i] = std::move(row);
-                taint_rows[i] = bits;
-            }
-        }
-        auto commit = [&] {
-            for (uint32_t k = 0; k < cols_.n_keys; ++k) value_ids_[k].insert(fresh_values[k].begin(), fresh_values[k].end());
-            if (taints_enabled_) taint_ids_ = ids;
-            for (auto &[i, r] : now) {
-                alloc_cpu_nanos_[i] = r.alloc_cpu;
-                alloc_mem_nanos_[i] = r.alloc_mem;
-                node_labels_[i] = std::move(r.labels);
-                node_has_labels_[i] = r.has_labels;
-                node_taints_raw_[i] = std::move(r.taints);
-            }
-            for (const auto &[i, row] : lab_rows) {
-                for (uint32_t k = 0; k < cols_.n_keys; ++k) cols_.label_val_ids[(size_t)k * n + i] = row[k];
-                if (taints_enabled_) cols_.taints[i] = taint_rows[i];
-            }
-            any_counted_taint_ = std::any_of(node_taints_raw_.begin(), node_taints_raw_.end(), [](const std::vector<TaintId> &t) { return !t.empty(); });
-        };
-        if (!res_nodes.empty()) store_available(res_nodes, res_fresh, commit);  // (validates, commits, pushes the rows)
-        else commit();
-        if (!lab_nodes.empty()) push_labels(lab_nodes);
-        else if (changed && res_nodes.empty()) ++generation_;  // (a label no column holds yet: nothing on the device, but the snapshot moved)
-        return changed;
+    return observe_known_nodes(events);
+}
+
+// The nodes of this snapshot only: a diff, applied as row updates.
+size_t Snapshot::observe_known_nodes(const NodeEvents &events) {
+    const uint32_t n = cols_.n;
+    std::map<uint32_t, NodeState> now;  // canonical index -> the node as it is now (events taken in order)
+    size_t changed = 0;
+    for (const auto &[kind, node] : events) {
+        if (kind != NodeEvent::Applied) continue;  // (a Deleted event names no node of the snapshot here)
+        const std::string name = corev1::name_any(node->metadata);
+        const uint32_t i = (uint32_t)index_of(name);
+        NodeState r = read_node(*node, name, true);
+        auto it = now.find(i);
+        const NodeState &was = it != now.end() ? it->second : nodes_[i];
+        const bool same = r.alloc_cpu == was.alloc_cpu && r.alloc_mem == was.alloc_mem && r.has_labels == was.has_labels && r.labels == was.labels;
+        if (!(same && (!taints_enabled_ || r.taints == was.taints))) ++changed;
+        if (it != now.end()) it->second = std::move(r);
+        else if (!(same && r.taints == was.taints)) now.emplace(i, std::move(r));
     }
-    // ---- a node joins or leaves: re-encode from the nodes and the counted pods (Rust's Snapshot::build_from_counted) ---------------
-    struct Rec {
-        NodeRead r;
-        __int128 avail_cpu = 0, avail_mem = 0;
-        int old = -1;  // canonical index in the snapshot as it is, -1 = joins now
+    if (now.empty()) return changed;
+    // everything the change needs, computed before anything is committed
+    std::vector<uint32_t> res_nodes, lab_nodes;
+    std::vector<std::pair<__int128, __int128>> res_fresh;
+    std::map<TaintId, uint32_t> ids = taint_ids_;
+    std::vector<std::map<std::string, uint32_t>> fresh_values(cols_.n_keys);  // values new to a column -> their ids
+    std::map<uint32_t, std::vector<uint32_t>> lab_rows;                         // node -> its new ids of every column
+    std::map<uint32_t, uint64_t> taint_rows;
+    for (auto &[i, r] : now) {
+        r.avail_cpu = nodes_[i].avail_cpu + (r.alloc_cpu - nodes_[i].alloc_cpu);  // `available` moves by new - old, exactly
+        r.avail_mem = nodes_[i].avail_mem + (r.alloc_mem - nodes_[i].alloc_mem);
+        if (r.alloc_cpu != nodes_[i].alloc_cpu || r.alloc_mem != nodes_[i].alloc_mem) {
+            res_nodes.push_back(i);
+            res_fresh.emplace_back(r.avail_cpu, r.avail_mem);
+        }
+        bool dev = false;
+        std::vector<uint32_t> row(cols_.n_keys, 0u);
+        for (uint32_t k = 0; k < cols_.n_keys; ++k) {
+            auto v = r.labels.find(cols_.keys[k]);
+            if (v != r.labels.end()) {
+                auto known = value_ids_[k].find(v->second);
+                if (known != value_ids_[k].end()) {
+                    row[k] = known->second;
+                } else {  // (appended after the ids in use; a re-encode numbers them again from scratch)
+                    auto [f, _] = fresh_values[k].emplace(v->second, (uint32_t)(value_ids_[k].size() + fresh_values[k].size() + 1u));
+                    row[k] = f->second;
+                }
+            }
+            dev = dev || row[k] != cols_.label_val_ids[(size_t)k * n + i];
+        }
+        uint64_t bits = 0;
+        if (taints_enabled_) {
+            for (const TaintId &t : r.taints) bits |= 1ull << taint_bit(ids, t);
+            dev = dev || bits != cols_.taints[i];
+        }
+        if (dev) {
+            lab_nodes.push_back(i);
+            lab_rows[i] = std::move(row);
+            taint_rows[i] = bits;
+        }
+    }
+    auto commit = [&] {
+        for (uint32_t k = 0; k < cols_.n_keys; ++k) value_ids_[k].insert(fresh_values[k].begin(), fresh_values[k].end());
+        if (taints_enabled_) taint_ids_ = ids;
+        for (auto &[i, r] : now) nodes_[i] = std::move(r);
+        for (const auto &[i, row] : lab_rows) {
+            for (uint32_t k = 0; k < cols_.n_keys; ++k) cols_.label_val_ids[(size_t)k * n + i] = row[k];
+            if (taints_enabled_) cols_.taints[i] = taint_rows[i];
+        }
+        any_counted_taint_ = std::any_of(nodes_.begin(), nodes_.end(), [](const NodeState &x) { return !x.taints.empty(); });
     };
-    std::map<std::string, Rec> recs;  // the nodes as they will be, in canonical order (ascending name, as rebuild sorts)
+    if (!res_nodes.empty()) store_available(res_nodes, res_fresh, commit);  // (validates, commits, pushes the rows)
+    else commit();
+    if (!lab_nodes.empty()) push_labels(lab_nodes);
+    else if (changed && res_nodes.empty()) ++generation_;  // (a label no column holds yet: nothing on the device, but the snapshot moved)
+    return changed;
+}
+
+// A node joins or leaves: the node set as it will be, then one re-encode from the nodes and the counted pods (Rust's Snapshot::build_from_counted).
+size_t Snapshot::observe_node_set(const NodeEvents &events, PodLister *client) {
+    const uint32_t n = cols_.n;
+    std::map<std::string, NodeState> next;  // the nodes as they will be, in canonical order (ascending name, as rebuild sorts)
+    std::set<std::string> joins;            // those of them the snapshot does not hold yet: only their pods are LISTed
+    std::vector<std::string> store(n);      // the node store's order, kept as the reflector's writer keeps it
     for (uint32_t i = 0; i < n; ++i) {
-        Rec x;
-        x.r.alloc_cpu = alloc_cpu_nanos_[i];
-        x.r.alloc_mem = alloc_mem_nanos_[i];
-        x.r.has_labels = node_has_labels_[i];
-        x.r.labels = node_labels_[i];
-        x.r.taints = node_taints_raw_[i];
-        x.avail_cpu = avail_cpu_nanos_[i];
-        x.avail_mem = avail_mem_nanos_[i];
-        x.old = (int)i;
-        recs.emplace(cols_.names[i], std::move(x));
+        next.emplace(cols_.names[i], nodes_[i]);
+        store[store_of_canonical_[i]] = cols_.names[i];
     }
-    std::vector<std::string> store(n);  // the node store's order, kept as the reflector's writer keeps it
-    for (uint32_t i = 0; i < n; ++i) store[store_of_canonical_[i]] = cols_.names[i];
     size_t changed = 0;
     for (const auto &[kind, node] : events) {
         const std::string name = corev1::name_any(node->metadata);
-        auto it = recs.find(name);
+        auto it = next.find(name);
         if (kind == NodeEvent::Deleted) {
-            if (it == recs.end()) continue;
-            recs.erase(it);
+            if (it == next.end()) continue;
+            next.erase(it);
+            joins.erase(name);
             store.erase(std::find(store.begin(), store.end(), name));
             ++changed;
             continue;
         }
-        NodeRead r = read_node(*node, name);
-        if (it == recs.end()) {
-            Rec x;
-            x.r = std::move(r);
-            recs.emplace(name, std::move(x));
+        NodeState r = read_node(*node, name, true);
+        if (it == next.end()) {
+            next.emplace(name, std::move(r));
+            joins.insert(name);
             store.push_back(name);
             ++changed;
             continue;
         }
-        Rec &x = it->second;
-        if (!(r.alloc_cpu == x.r.alloc_cpu && r.alloc_mem == x.r.alloc_mem && r.has_labels == x.r.has_labels && r.labels == x.r.labels &&
-              (!taints_enabled_ || r.taints == x.r.taints)))
+        const NodeState &was = it->second;
+        if (!(r.alloc_cpu == was.alloc_cpu && r.alloc_mem == was.alloc_mem && r.has_labels == was.has_labels && r.labels == was.labels &&
+              (!taints_enabled_ || r.taints == was.taints)))
             ++changed;
-        x.avail_cpu += r.alloc_cpu - x.r.alloc_cpu;  // (a joining node's `available` is computed from its LIST below)
-        x.avail_mem += r.alloc_mem - x.r.alloc_mem;
-        x.r = std::move(r);
+        r.avail_cpu = was.avail_cpu + (r.alloc_cpu - was.alloc_cpu);  // (a joining node's `available` is its allocatable until its LIST below)
+        r.avail_mem = was.avail_mem + (r.alloc_mem - was.alloc_mem);
+        it->second = std::move(r);
     }
-    const uint32_t m = (uint32_t)recs.size();
+    const uint32_t m = (uint32_t)next.size();
     std::vector<int> new_of_old(n, -1);
-    NodeColumns c;
-    c.n = m;
-    c.names.reserve(m);
-    c.avail_cpu_milli.resize(m);
-    c.avail_mem_bytes.resize(m);
-    c.taints.assign(m, 0);
-    std::vector<__int128> cpu_nanos(m), mem_nanos(m), alloc_cpu(m), alloc_mem(m);
-    std::vector<corev1::StringMap> labels(m);
-    std::vector<bool> has_labels(m, false);
-    std::vector<std::vector<TaintId>> taints_raw(m);
+    std::vector<std::string> names;
+    std::vector<NodeState> states;
     CountedTable counted;
-    bool any_taint = false;
-    {
-        uint32_t j = 0;
-        for (auto &[name, x] : recs) {
-            c.names.push_back(name);
-            if (x.old >= 0) {
-                new_of_old[(size_t)x.old] = (int)j;
-            } else {  // joins: only its pods are LISTed
-                x.avail_cpu = x.r.alloc_cpu;
-                x.avail_mem = x.r.alloc_mem;
-                if (client) {
-                    ++client->list_calls;
-                    for (const auto &p : client->list_pods_on_node(name)) {
-                        try {
-                            const PodResources pr = total_pod_resources(p);
-                            x.avail_cpu -= pr.cpu.nanos();
-                            x.avail_mem -= pr.memory.nanos();
-                            counted[full_name(p.metadata)] = Counted{j, pr.cpu.nanos(), pr.memory.nanos()};
-                        } catch (const QuantityError &e) {
-                            throw EncodeError("pod " + full_name(p.metadata) + ": invalid pod spec: " + e.what());
-                        }
-                    }
-                }
-            }
-            cpu_nanos[j] = x.avail_cpu;
-            mem_nanos[j] = x.avail_mem;
-            alloc_cpu[j] = x.r.alloc_cpu;
-            alloc_mem[j] = x.r.alloc_mem;
-            has_labels[j] = x.r.has_labels;
-            labels[j] = x.r.labels;
-            taints_raw[j] = x.r.taints;
-            any_taint = any_taint || !x.r.taints.empty();
-            ++j;
-        }
+    names.reserve(m);
+    states.reserve(m);
+    for (auto &[name, x] : next) {
+        const uint32_t j = (uint32_t)names.size();
+        if (!joins.count(name)) new_of_old[(size_t)index_of(name)] = (int)j;
+        else if (client) list_node(client, name, j, x, counted);
+        names.push_back(name);
+        states.push_back(std::move(x));
     }
     for (const auto &sh : counted_.shard)  // the counted pods of the nodes that stay, remapped; those of deleted nodes are dropped
         for (const auto &[key, ct] : sh) {
@@ -934,39 +857,10 @@ size_t Snapshot::observe_nodes(const std::vector<std::pair<NodeEvent, const core
             if (j >= 0 && counted.shard[CountedTable::shard_of(CountedTable::hash_of(key))].count(key) == 0)
                 counted[key] = Counted{(uint32_t)j, ct.cpu_nanos, ct.mem_nanos};
         }
-    const __int128 cpu_unit = choose_unit(cpu_nanos, kCpuUnits), mem_unit = choose_unit(mem_nanos, kMemUnits);
-    if (!cpu_unit || !mem_unit) throw EncodeError("observe_nodes: the nodes' available values do not fit int64 in one common unit");
-    for (uint32_t j = 0; j < m; ++j) {
-        c.avail_cpu_milli[j] = (int64_t)(cpu_nanos[j] / cpu_unit);
-        c.avail_mem_bytes[j] = (int64_t)(mem_nanos[j] / mem_unit);
-    }
-    std::map<TaintId, uint32_t> ids;
-    if (taints_enabled_) intern_taints_into(taints_raw, ids, c.taints);  // (throws before anything is committed)
-    std::vector<uint32_t> canonical_of_store(m), store_of_canonical(m);
-    for (uint32_t s = 0; s < m; ++s) {
-        const uint32_t j = (uint32_t)std::distance(c.names.begin(), std::lower_bound(c.names.begin(), c.names.end(), store[s]));
-        canonical_of_store[s] = j;
-        store_of_canonical[j] = s;
-    }
-    // ---- commit ----
-    c.keys = cols_.keys;
-    cols_ = std::move(c);
-    avail_cpu_nanos_ = std::move(cpu_nanos);
-    avail_mem_nanos_ = std::move(mem_nanos);
-    alloc_cpu_nanos_ = std::move(alloc_cpu);
-    alloc_mem_nanos_ = std::move(alloc_mem);
-    cpu_unit_ = cpu_unit;
-    mem_unit_ = mem_unit;
-    counted_ = std::move(counted);
-    store_of_canonical_ = std::move(store_of_canonical);
-    canonical_of_store_ = std::move(canonical_of_store);
-    node_labels_ = std::move(labels);
-    node_has_labels_ = std::move(has_labels);
-    node_taints_raw_ = std::move(taints_raw);
-    any_counted_taint_ = any_taint;
-    if (taints_enabled_) taint_ids_ = std::move(ids);
-    encode_labels();
-    upload();
+    std::vector<uint32_t> store_of_canonical(m);
+    for (uint32_t s = 0; s < m; ++s) store_of_canonical[(size_t)std::distance(names.begin(), std::lower_bound(names.begin(), names.end(), store[s]))] = s;
+    commit_node_set(encode_node_set(std::move(names), std::move(states), std::move(store_of_canonical), std::move(counted),
+                                    {nullptr, "observe_nodes: the nodes' available values do not fit int64 in one common unit"}));
     return changed;
 }
 

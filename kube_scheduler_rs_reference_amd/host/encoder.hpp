@@ -203,6 +203,16 @@ public:
     bool device_stale() const { return device_stale_; }
 
 private:
+    // Everything the snapshot knows of one node, exactly; nodes_ holds one per node in canonical order, and the columns are encoded from it.
+    struct NodeState {
+        __int128 alloc_cpu = 0, alloc_mem = 0;  // allocatable in nano-units (observe_nodes diffs it)
+        __int128 avail_cpu = 0, avail_mem = 0;  // the exact values behind the two resource columns
+        bool has_labels = false;                // labels is None / Some (an empty map either way when None)
+        corev1::StringMap labels;
+        std::vector<TaintId> taints;            // the counted (NoSchedule / NoExecute) taints, un-interned: recorded with the extension off too
+    };
+    // The only code that reads a corev1::Node: available = allocatable (nothing LISTed yet).  with_resources = false leaves both at 0.
+    static NodeState read_node(const corev1::Node &node, const std::string &name, bool with_resources);
     void encode_labels();
     void upload();
 
@@ -210,20 +220,25 @@ private:
     std::vector<std::shared_ptr<DeviceEvaluator>> devs_;  // every device the snapshot is replicated to
     std::unique_ptr<ShardedContext> sharded_;
     NodeColumns cols_;
+    std::vector<NodeState> nodes_;                           // canonical order, cols_.n of them
     std::vector<uint32_t> store_of_canonical_, canonical_of_store_;
-    std::vector<corev1::StringMap> node_labels_;            // canonical order; empty map when labels is None
-    std::vector<bool> node_has_labels_;
     std::vector<std::map<std::string, uint32_t>> value_ids_;  // per column: value string -> id (1..)
     std::map<TaintId, uint32_t> taint_ids_;                 // NoSchedule / NoExecute taints -> bit (filled by enable_taints)
-    std::vector<std::vector<TaintId>> node_taints_raw_;     // canonical order: the node's counted taints, un-interned
     bool any_counted_taint_ = false, taints_enabled_ = false, device_stale_ = false;
     void intern_taints();
-    static void intern_taints_into(const std::vector<std::vector<TaintId>> &raw, std::map<TaintId, uint32_t> &ids, std::vector<uint64_t> &column);
+    static uint32_t taint_bit(std::map<TaintId, uint32_t> &ids, const TaintId &taint);  // its bit, a new one if need be; throws at the 65th
+    static void intern_taints_into(const std::vector<NodeState> &nodes, std::map<TaintId, uint32_t> &ids, std::vector<uint64_t> &column);
     uint64_t generation_ = 0;
-    std::vector<__int128> avail_cpu_nanos_, avail_mem_nanos_;  // canonical order: the exact values behind the two resource columns
-    std::vector<__int128> alloc_cpu_nanos_, alloc_mem_nanos_;  // canonical order: the nodes' exact allocatable (observe_nodes diffs it)
     void push_labels(const std::vector<uint32_t> &nodes);      // label ids / taints of these nodes -> ksched_update_node_labels
     __int128 cpu_unit_ = 1000000, mem_unit_ = 1000000000;      // nano-units per column unit (see cpu_unit_nanos())
+    // The units in which every one of these `available` values is a whole int64 number.  When there are none: EncodeError, in the caller's
+    // words -- "node <name>" + w.node for the first of `diagnose` (nullptr: every node) that no unit holds on its own (w.node = nullptr: no such
+    // diagnosis), else w.common.
+    struct UnitWording {
+        const char *node, *common;
+    };
+    static std::pair<__int128, __int128> choose_units(const std::vector<__int128> &cpu, const std::vector<__int128> &mem, const std::vector<std::string> &names,
+                                                      const std::vector<uint32_t> *diagnose, const UnitWording &w);
     // new exact `available` values of some nodes -> columns (+ a new unit when one of them needs it) -> device.  Validates before it
     // changes anything (strong guarantee); `commit` runs between validation and the device call (the callers' own bookkeeping).
     void store_available(const std::vector<uint32_t> &nodes, const std::vector<std::pair<__int128, __int128>> &fresh, const std::function<void()> &commit);
@@ -246,6 +261,27 @@ private:
         Counted &operator[](const std::string &key) { return shard[shard_of(hash_of(key))][key]; }
     };
     CountedTable counted_;
+    // A changed node set (rebuild, a node joining or leaving), in two steps: encode_node_set works out everything the snapshot holds per node
+    // set -- units, resource columns, taint ids and column (extension on), both order maps -- from the states in canonical order, the store
+    // order and the counted pods, and throws before anything of the snapshot is touched; commit_node_set swaps it in (keeping the label
+    // columns in use), re-encodes the labels and uploads.
+    struct NodeSet {
+        NodeColumns cols;
+        std::vector<NodeState> nodes;
+        CountedTable counted;
+        std::vector<uint32_t> store_of_canonical, canonical_of_store;
+        std::map<TaintId, uint32_t> taint_ids;
+        __int128 cpu_unit = 0, mem_unit = 0;
+        bool any_counted_taint = false;
+    };
+    NodeSet encode_node_set(std::vector<std::string> names, std::vector<NodeState> nodes, std::vector<uint32_t> store_of_canonical, CountedTable counted,
+                            const UnitWording &w) const;
+    void commit_node_set(NodeSet &&set);
+    // One LIST: every pod it returns is subtracted from the node's `available` (any phase, src/predicates.rs:34-38) and counted against `canonical`.
+    static void list_node(PodLister *client, const std::string &name, uint32_t canonical, NodeState &node, CountedTable &counted);
+    using NodeEvents = std::vector<std::pair<NodeEvent, const corev1::Node *>>;
+    size_t observe_known_nodes(const NodeEvents &events);                  // no node joins or leaves: a diff, applied as row updates
+    size_t observe_node_set(const NodeEvents &events, PodLister *client);  // one does: the new node set is encoded and committed
     void push_rows(const std::vector<uint32_t> &touched);
     // one event of observe_pods / observe_bound: the pod, and the node it runs on now (nullptr = none: deleted / unbound)
     struct Observed {

@@ -3,9 +3,18 @@
 //   node_events_tests cpu   event sequences on an encode-only snapshot: after each, the decoded snapshot (available, label values,
 //                           taints per node) equals a rebuild from scratch over the final node set; LIST, generation and
 //                           strong-guarantee accounting
-//   node_events_tests gpu   objects -> events -> reconcile_batch equals reconcile_batch over a snapshot built from scratch
+//   node_events_tests walk [--seed S] [--steps N] [--dump]
+//                           a seeded walk of drawn steps (default: seeds 1, 2 and 3, 2000 steps each) on an encode-only snapshot, the same
+//                           checks after every step, a floor under the count of every kind of step; --dump prints every observable
+//                           after every step (to compare two builds of the host library line by line)
+//   node_events_tests time  rebuild of 5000 nodes with 20 LISTed pods each, then one Added event and one label change on it (ms, encode-only)
+//   node_events_tests gpu   objects -> events -> reconcile_batch equals reconcile_batch over a snapshot built from scratch, and a walk of
+//                           200 steps after every tenth of which the device holds what the host columns say
 //                           (run it with KSCHED_SHARDED=1 for the one-device sharded path)
+#include <algorithm>
+#include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <set>
@@ -140,11 +149,12 @@ static bool same(const Decoded &a, const Decoded &b) {
 
 static const std::set<std::string> kKeys = {"zone", "disk"};
 
-// the snapshot a rebuild from scratch over `nodes` gives (encode-only)
-static Decoded fresh(const std::vector<corev1::Node> &nodes, const std::vector<corev1::Pod> &pods) {
+// the snapshot a rebuild from scratch over `nodes` gives (encode-only), with these label columns and the taint extension on or off
+static Decoded fresh(const std::vector<corev1::Node> &nodes, const std::vector<corev1::Pod> &pods, const std::set<std::string> &keys = kKeys,
+                     bool taints = true) {
     Snapshot s(Snapshot::kEncodeOnly);
-    s.ensure_keys(kKeys);
-    s.enable_taints();
+    s.ensure_keys(keys);
+    if (taints) s.enable_taints();
     StaticPodLister l;
     l.pods = pods;
     s.rebuild(nodes, &l);
@@ -244,6 +254,502 @@ static void cpu_tests() {
     });
 }
 
+// ---- the seeded walk -----------------------------------------------------------------------------------------------------
+// About 2000 drawn steps per seed over one snapshot; after every step the decoded snapshot equals a rebuild from scratch over the
+// node and pod set as it is then, the store maps hold, and a step that threw has left every observable as it was.  Only the public
+// interface of Snapshot and Context is used, so the same source runs against an older host library: `--dump` prints every
+// observable after every step, and two libraries that behave alike print the same lines.
+struct Rng {  // splitmix64: the same draws whatever the program is linked against
+    uint64_t s;
+    uint64_t next() {
+        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    }
+    uint32_t below(uint32_t n) { return (uint32_t)(next() % n); }
+    bool chance(uint32_t percent) { return below(100) < percent; }
+    template <class T>
+    const T &of(const std::vector<T> &v) { return v[below((uint32_t)v.size())]; }
+};
+
+enum Kind {
+    kLabelKnown, kLabelNew, kKeyRemoved, kTaintNewBit, kTaintRemoved, kAllocatable, kHeartbeat, kAddedWithPods, kDeletedWithPods, kMixedBatch,
+    kPodEvents, kFinerUnit, kEvictKeys, kEnableTaints, kErrNoMemory, kErrQuantity, kErrListedPod, kErr65thTaint, kKinds
+};
+// the draw weights (percent).  Every kind has a floor of 20 counted steps per seed: the rarest, at 3 %, is expected 60 times in 2000 steps
+// (the two that need the taint extension, which goes on after two fifths of the walk, 36 and 60 times in the 1200 steps that are left).
+static const struct {
+    const char *name;
+    uint32_t weight;
+} kKind[kKinds] = {{"a label value changed to a known value", 6}, {"a label changed to a new value", 6}, {"a key removed", 5},
+                   {"a taint added that needs a new bit", 7}, {"a taint removed", 5}, {"an allocatable change", 6}, {"a heartbeat that changes nothing", 5},
+                   {"an Added node with LISTed pods", 7}, {"a Deleted node that has counted pods", 6}, {"a batch mixing Added, Deleted and Modified", 5},
+                   {"pod events between node events", 17}, {"a request that forces a finer unit", 5}, {"ensure_keys evicting columns", 3},
+                   {"enable_taints late in the walk", 3}, {"EncodeError: allocatable without memory", 3}, {"EncodeError: an unparsable quantity", 3},
+                   {"EncodeError: a LISTed pod that does not parse", 3}, {"EncodeError: a 65th taint", 5}};
+
+struct NodeModel {
+    std::string cpu, mem;
+    std::map<std::string, std::string> labels;
+    std::vector<std::pair<std::string, std::string>> taints;  // key, effect
+    corev1::Node object(const std::string &name) const { return node(name, cpu.c_str(), mem.c_str(), labels, taints); }
+};
+
+static std::string observables(const Snapshot &s) {
+    const NodeColumns &c = s.columns();
+    std::string o = "names=";
+    auto num = [&](__int128 v) { o += std::to_string((long long)v) + ","; };
+    for (const auto &x : c.names) o += x + ",";
+    o += " cpu=";
+    for (int64_t v : c.avail_cpu_milli) num(v);
+    o += " mem=";
+    for (int64_t v : c.avail_mem_bytes) num(v);
+    o += " keys=";
+    for (const auto &x : c.keys) o += x + ",";
+    o += " label_val_ids=";
+    for (uint32_t v : c.label_val_ids) num(v);
+    o += " taints=";
+    for (uint64_t v : c.taints) o += std::to_string(v) + ",";
+    o += " units=";
+    num(s.cpu_unit_nanos());
+    num(s.mem_unit_nanos());
+    o += " taint_ids=";
+    for (const auto &[id, bit] : s.taint_ids()) o += std::get<0>(id) + "/" + std::get<1>(id) + "/" + std::get<2>(id) + ":" + std::to_string(bit) + ",";
+    o += " store_of_canonical=";
+    for (uint32_t i = 0; i < s.n(); ++i) num(s.store_index(i));
+    o += " canonical_of_store=";
+    for (uint32_t i = 0; i < s.n(); ++i) num(s.canonical_index(i));
+    o += " generation=" + std::to_string(s.generation()) + " counted_pods=" + std::to_string(s.counted_pods()) + " has_taints=" + std::to_string(s.has_taints());
+    return o;
+}
+
+static const std::vector<std::string> kCpus = {"2", "4", "6", "8", "3500m", "16"}, kMems = {"4Gi", "8Gi", "9Gi", "16Gi", "32Gi"},
+                                      kPodCpus = {"100m", "250m", "500m", "1", "1500m"}, kPodMems = {"64Mi", "128Mi", "256Mi", "1Gi"},
+                                      kZones = {"z1", "z2", "z3", "z4"}, kDisks = {"ssd", "hdd", "nvme"};
+static std::pair<std::string, std::string> pool_taint(uint32_t i) { return {"t" + std::to_string(i), (i % 2) ? "NoExecute" : "NoSchedule"}; }
+constexpr uint32_t kTaintPool = 60, kMaxNodes = 40, kMinNodes = 12, kNamePool = 60, kFillerKeys = 17;
+
+struct Walk {
+    Rng rng;
+    Context ctx;
+    std::shared_ptr<StaticPodLister> lister = std::make_shared<StaticPodLister>();
+    std::map<std::string, NodeModel> nodes;   // the node store, by name
+    std::map<std::string, corev1::Pod> pods;  // the API server's pods, by name (lister->pods holds the same)
+    size_t count[kKinds] = {};
+    uint64_t serial = 0;
+    uint32_t step_no = 0, late = 0;
+    bool dump = false, keep_layout = false;
+
+    explicit Walk(uint64_t seed) : rng{seed} {}
+
+    NodeModel random_model() {
+        NodeModel m{rng.of(kCpus), rng.of(kMems), {}, {}};
+        if (rng.chance(80)) m.labels["zone"] = rng.of(kZones);
+        if (rng.chance(60)) m.labels["disk"] = rng.of(kDisks);
+        if (rng.chance(30)) m.labels["rack"] = "r" + std::to_string(rng.below(3));
+        for (uint32_t t = rng.below(3); t > 0; --t) {
+            const auto x = pool_taint(rng.below(kTaintPool));
+            if (std::find(m.taints.begin(), m.taints.end(), x) == m.taints.end()) m.taints.push_back(x);
+        }
+        return m;
+    }
+    static std::string node_name(uint32_t i) { return (i < 10 ? "n0" : "n") + std::to_string(i); }
+    std::string free_name() {
+        for (;;) {
+            const std::string name = node_name(rng.below(kNamePool));
+            if (!nodes.count(name)) return name;
+        }
+    }
+    void serve(const std::map<std::string, corev1::Pod> &from) {
+        lister->pods.clear();
+        for (const auto &[name, p] : from) lister->pods.push_back(p);
+    }
+    // nodes a step that takes a label value or a taint AWAY leaves alone on a device: the only carrier of a column's largest id or of the
+    // highest taint bit.  ksched_update_node_labels keeps the index layout planned for the maxima it has seen (include/ksched.h), and only an
+    // index of the same layout is the same bits as a fresh ctx's; with these nodes left alone the maxima in use never fall between two uploads.
+    std::set<std::string> layout_carriers() const {
+        std::set<std::string> out;
+        const NodeColumns &c = ctx.snapshot->columns();
+        auto sole = [&](auto value_of) {
+            uint64_t top = 0;
+            uint32_t carriers = 0, who = 0;
+            for (uint32_t i = 0; i < c.n; ++i) {
+                const uint64_t v = value_of(i);
+                if (v > top) top = v, carriers = 0;
+                if (v == top && top) ++carriers, who = i;
+            }
+            if (carriers == 1) out.insert(c.names[who]);
+        };
+        for (uint32_t k = 0; k < c.n_keys; ++k) sole([&](uint32_t i) { return (uint64_t)c.label_val_ids[(size_t)k * c.n + i]; });
+        sole([&](uint32_t i) { return c.taints[i] ? 64u - (uint64_t)__builtin_clzll(c.taints[i]) : 0u; });
+        return out;
+    }
+    // a node of the store for which `ok` holds ("" = none); `taking_away`: see layout_carriers
+    std::string pick_node(const std::function<bool(const std::string &, const NodeModel &)> &ok, bool taking_away = false) {
+        const std::set<std::string> keep = (keep_layout && taking_away) ? layout_carriers() : std::set<std::string>{};
+        std::vector<std::string> names;
+        for (const auto &[name, m] : nodes)
+            if (!keep.count(name) && ok(name, m)) names.push_back(name);
+        return names.empty() ? std::string() : rng.of(names);
+    }
+    std::string any_node() { return pick_node([](const std::string &, const NodeModel &) { return true; }); }
+
+    void start(bool on_device) {
+        ctx.warn = nullptr;
+        ctx.client = lister;
+        const uint32_t n0 = on_device ? kMaxNodes : 25 + rng.below(16);
+        std::vector<std::string> order;
+        while (nodes.size() < n0) {
+            const std::string name = free_name();
+            nodes[name] = random_model();
+            order.push_back(name);  // (the store's order is the order of the draws, not the canonical one)
+        }
+        for (const auto &name : order) ctx.node_store.push_back(nodes[name].object(name));
+        for (uint32_t i = 0; i < 2 * n0; ++i) {
+            const std::string name = "p" + std::to_string(serial++);
+            pods[name] = pod(name, rng.of(kPodCpus).c_str(), rng.of(kPodMems).c_str(), rng.of(order).c_str());
+        }
+        serve(pods);
+        if (on_device) {
+            ctx.refresh_snapshot();
+        } else {
+            ctx.snapshot = std::make_shared<Snapshot>(Snapshot::kEncodeOnly);
+            ctx.snapshot->rebuild(ctx.node_store, lister.get());
+        }
+        ctx.snapshot->ensure_keys(kKeys);
+    }
+
+    Kind draw() {
+        if (step_no == late) return kEnableTaints;
+        for (;;) {
+            uint32_t r = rng.below(100);
+            uint32_t k = 0;
+            while (r >= kKind[k].weight) r -= kKind[k++].weight;
+            if ((k == kEnableTaints || k == kErr65thTaint) && step_no < late) continue;
+            if (k == kAddedWithPods && nodes.size() >= kMaxNodes) k = kDeletedWithPods;
+            if (k == kDeletedWithPods && nodes.size() <= kMinNodes) k = kAddedWithPods;
+            return (Kind)k;
+        }
+    }
+
+    void step() {
+        const Kind kind = draw();
+        Snapshot &snap = *ctx.snapshot;
+        std::map<std::string, NodeModel> nodes_next = nodes;
+        std::map<std::string, corev1::Pod> pods_next = pods;
+        std::vector<std::pair<NodeEvent, corev1::Node>> ev;  // a node step: its events ...
+        std::function<size_t()> call;                        // ... any other step: what it calls
+        std::vector<corev1::Pod> objs;                       // (the pods a pod step's events point at)
+        std::vector<std::string> bound_to;
+        bool counted = true, expect_throw = false;
+        uint64_t lists_of_a_throw = 0;  // LISTs a step issues before it throws
+        auto applied = [&](const std::string &name, const NodeModel &m) {
+            ev.emplace_back(NodeEvent::Applied, m.object(name));
+            nodes_next[name] = m;
+        };
+        auto deleted = [&](const std::string &name) {
+            ev.emplace_back(NodeEvent::Deleted, node(name, "1", "1"));
+            nodes_next.erase(name);
+        };
+        auto heartbeat = [&] {
+            const std::string name = any_node();
+            applied(name, nodes.at(name));
+        };
+        auto new_pod_on = [&](const std::string &node_name) {
+            const std::string name = "p" + std::to_string(serial++);
+            pods_next[name] = pod(name, rng.of(kPodCpus).c_str(), rng.of(kPodMems).c_str(), node_name.c_str());
+        };
+        auto has_pods = [&](const std::string &node_name) {
+            for (const auto &[name, p] : pods)
+                if (p.spec->node_name && *p.spec->node_name == node_name) return true;
+            return false;
+        };
+        auto change_allocatable = [&](NodeModel &m) {
+            const std::string cpu = m.cpu, mem = m.mem;
+            while (m.cpu == cpu && m.mem == mem) {
+                if (rng.chance(60)) m.cpu = rng.of(kCpus);
+                if (rng.chance(60)) m.mem = rng.of(kMems);
+            }
+        };
+        switch (kind) {
+        case kLabelKnown: {
+            counted = false;
+            const std::string name = pick_node([](const std::string &, const NodeModel &) { return true; }, true);
+            for (const char *key : {rng.chance(50) ? "zone" : "disk", "zone", "disk"}) {
+                if (name.empty() || counted) break;
+                std::vector<std::string> values;  // what other nodes carry for this key
+                for (const auto &[other, m] : nodes) {
+                    auto v = m.labels.find(key);
+                    auto mine = nodes.at(name).labels.find(key);
+                    if (other != name && v != m.labels.end() && (mine == nodes.at(name).labels.end() || mine->second != v->second) &&
+                        std::find(values.begin(), values.end(), v->second) == values.end())
+                        values.push_back(v->second);
+                }
+                if (values.empty()) continue;
+                NodeModel m = nodes.at(name);
+                m.labels[key] = rng.of(values);
+                applied(name, m);
+                counted = true;
+            }
+            if (!counted) heartbeat();
+            break;
+        }
+        case kLabelNew: {
+            const std::string name = any_node();
+            NodeModel m = nodes.at(name);
+            m.labels[rng.chance(50) ? "zone" : "disk"] = "v" + std::to_string(serial++);
+            applied(name, m);
+            break;
+        }
+        case kKeyRemoved: {
+            const std::string name = pick_node([](const std::string &, const NodeModel &m) { return m.labels.count("zone") || m.labels.count("disk"); }, true);
+            if ((counted = !name.empty())) {
+                NodeModel m = nodes.at(name);
+                if (rng.chance(15)) m.labels.clear();  // (labels: None)
+                else m.labels.erase(m.labels.count("zone") && (!m.labels.count("disk") || rng.chance(50)) ? "zone" : "disk");
+                applied(name, m);
+            } else {
+                heartbeat();
+            }
+            break;
+        }
+        case kTaintNewBit: {
+            const std::string name = pick_node([](const std::string &, const NodeModel &m) { return m.taints.size() < 3; });
+            if (name.empty()) {
+                counted = false;
+                heartbeat();
+                break;
+            }
+            NodeModel m = nodes.at(name);
+            auto on_node = [&](uint32_t i) { return std::find(m.taints.begin(), m.taints.end(), pool_taint(i)) != m.taints.end(); };
+            auto has_bit = [&](uint32_t i) { return snap.taint_ids().count(TaintId(pool_taint(i).first, "", pool_taint(i).second)) != 0; };
+            uint32_t pick = rng.below(kTaintPool);
+            for (uint32_t j = 0; j < kTaintPool && (on_node(pick) || has_bit(pick)); ++j) pick = (pick + 1) % kTaintPool;
+            while (on_node(pick)) pick = (pick + 1) % kTaintPool;
+            counted = snap.taints_enabled() && !has_bit(pick);
+            m.taints.push_back(pool_taint(pick));
+            applied(name, m);
+            break;
+        }
+        case kTaintRemoved: {
+            const std::string name = pick_node([](const std::string &, const NodeModel &m) { return !m.taints.empty(); }, true);
+            if ((counted = !name.empty())) {
+                NodeModel m = nodes.at(name);
+                m.taints.erase(m.taints.begin() + rng.below((uint32_t)m.taints.size()));
+                applied(name, m);
+            } else {
+                heartbeat();
+            }
+            break;
+        }
+        case kAllocatable: {
+            const std::string name = any_node();
+            NodeModel m = nodes.at(name);
+            change_allocatable(m);
+            applied(name, m);
+            break;
+        }
+        case kHeartbeat:
+            heartbeat();
+            break;
+        case kAddedWithPods: {
+            const std::string name = free_name();
+            for (uint32_t k = 1 + rng.below(3); k > 0; --k) new_pod_on(name);  // (bound to a node outside the snapshot: counted nowhere until it joins)
+            applied(name, random_model());
+            break;
+        }
+        case kDeletedWithPods: {
+            std::string name = pick_node([&](const std::string &n, const NodeModel &) { return has_pods(n); });
+            if ((counted = !name.empty())) deleted(name);
+            else deleted(any_node());
+            break;
+        }
+        case kMixedBatch: {
+            const std::string a = any_node(), b = free_name();
+            const std::string c = pick_node([&](const std::string &n, const NodeModel &) { return n != a; });
+            NodeModel ma = nodes.at(a), mb = random_model();
+            change_allocatable(ma);
+            applied(a, ma);
+            if (rng.chance(50)) new_pod_on(b);
+            applied(b, mb);
+            deleted(c);
+            if (rng.chance(50)) {
+                mb.labels["zone"] = rng.of(kZones);
+                change_allocatable(mb);
+                applied(b, mb);
+            }
+            break;
+        }
+        case kPodEvents: {
+            const uint32_t how = rng.below(3);
+            const uint32_t want = 1 + rng.below(3);
+            std::set<std::string> used;
+            std::vector<Snapshot::PodEvent> kinds;
+            for (uint32_t k = 0; k < want; ++k) {
+                if (how == 2) {  // observe_bound: the pod object carries no nodeName
+                    const std::string name = "p" + std::to_string(serial++);
+                    objs.push_back(pod(name, rng.of(kPodCpus).c_str(), rng.of(kPodMems).c_str()));
+                    bound_to.push_back(any_node());
+                    pods_next[name] = pod(name, objs.back().spec->containers[0].resources->requests->at("cpu").c_str(),
+                                          objs.back().spec->containers[0].resources->requests->at("memory").c_str(), bound_to.back().c_str());
+                    continue;
+                }
+                const bool del = !pods_next.empty() && (how == 1 || pods_next.size() > 150);
+                if (del) {  // a Deleted event; a pod with a fine request goes first, so that the units get coarse again
+                    std::vector<std::string> names, fine;
+                    for (const auto &[name, p] : pods_next)
+                        if (!used.count(name)) (name[0] == 'f' ? fine : names).push_back(name);
+                    if (names.empty() && fine.empty()) break;
+                    const std::string name = (!fine.empty() && (names.empty() || rng.chance(60))) ? rng.of(fine) : rng.of(names);
+                    used.insert(name);
+                    objs.push_back(pods_next.at(name));
+                    kinds.push_back(Snapshot::PodEvent::Deleted);
+                    pods_next.erase(name);
+                    continue;
+                }
+                std::string name = "p" + std::to_string(serial++);
+                if (!pods.empty() && rng.chance(50)) {  // a pod the server has: it moves, or its requests change
+                    auto it = pods.begin();
+                    std::advance(it, rng.below((uint32_t)pods.size()));
+                    if (!used.count(it->first) && pods_next.count(it->first) && it->first[0] != 'f') name = it->first;
+                }
+                used.insert(name);
+                const uint32_t where = rng.below(10);
+                const std::string on = where == 0 ? free_name() : any_node();  // (sometimes a node outside the snapshot, or none at all)
+                objs.push_back(pod(name, rng.of(kPodCpus).c_str(), rng.of(kPodMems).c_str(), where == 1 ? nullptr : on.c_str()));
+                kinds.push_back(Snapshot::PodEvent::Applied);
+                pods_next[name] = objs.back();
+            }
+            if (how == 2) {
+                call = [&] {
+                    std::vector<std::pair<const corev1::Pod *, const std::string *>> b;
+                    for (size_t i = 0; i < objs.size(); ++i) b.emplace_back(&objs[i], &bound_to[i]);
+                    return snap.observe_bound(b);
+                };
+            } else {
+                call = [&, kinds] {
+                    std::vector<std::pair<Snapshot::PodEvent, const corev1::Pod *>> e;
+                    for (size_t i = 0; i < objs.size(); ++i) e.emplace_back(kinds[i], &objs[i]);
+                    return snap.observe_pods(e);
+                };
+            }
+            break;
+        }
+        case kFinerUnit: {
+            const std::string name = "f" + std::to_string(serial++);
+            const bool cpu = rng.chance(50);
+            objs.push_back(pod(name, cpu ? "100u" : "100m", cpu ? "64Mi" : "100m", any_node().c_str()));  // ("100m" of memory: milli-bytes)
+            pods_next[name] = objs.back();
+            call = [&] { return snap.observe_pods({{Snapshot::PodEvent::Applied, &objs[0]}}); };
+            break;
+        }
+        case kEvictKeys: {
+            std::set<std::string> keys = kKeys;
+            for (uint32_t i = 0; i < kFillerKeys; ++i) keys.insert("e" + std::to_string(serial) + "_" + std::to_string(i));
+            ++serial;
+            counted = snap.columns().keys.size() + kFillerKeys > KSCHED_MAX_KEYS;  // (the batch's keys do not fit beside the ones in use)
+            call = [&snap, keys] {
+                snap.ensure_keys(keys);
+                return (size_t)0;
+            };
+            break;
+        }
+        case kEnableTaints:
+            call = [&snap] {
+                snap.enable_taints();
+                return (size_t)0;
+            };
+            break;
+        case kErrNoMemory:
+        case kErrQuantity:
+        case kErrListedPod:
+        case kErr65thTaint: {
+            expect_throw = true;
+            const bool known = kind != kErrListedPod && rng.chance(50);  // through the diff of known nodes, or through the join of a new one
+            const std::string name = known ? any_node() : free_name();
+            NodeModel m = known ? nodes.at(name) : random_model();
+            lists_of_a_throw = (kind == kErrListedPod || (kind == kErr65thTaint && !known)) ? 1 : 0;  // (a joining node is LISTed before the taints are interned)
+            if (kind == kErrNoMemory) {
+                ev.emplace_back(NodeEvent::Applied, node(name, "6", nullptr));
+            } else if (kind == kErrQuantity) {
+                ev.emplace_back(NodeEvent::Applied, rng.chance(50) ? node(name, "abc", "8Gi") : node(name, "4", "lots"));
+            } else if (kind == kErrListedPod) {
+                pods_next["bad"] = pod("bad", "bogus", "1Gi", name.c_str());
+                ev.emplace_back(NodeEvent::Applied, m.object(name));
+            } else {
+                if (!snap.taints_enabled()) std::printf("    the taint extension is off at step %u\n", step_no), ++g_fail;
+                m.taints.clear();
+                for (int i = 0; i < 70; ++i) m.taints.emplace_back("x" + std::to_string(i), "NoSchedule");
+                ev.emplace_back(NodeEvent::Applied, m.object(name));
+            }
+            break;
+        }
+        default:
+            break;
+        }
+        serve(pods_next);
+        const int failed_before = g_fail;
+        const std::string before = observables(snap);
+        const uint64_t lists = lister->list_calls, gen = snap.generation();
+        const __int128 cpu_unit = snap.cpu_unit_nanos(), mem_unit = snap.mem_unit_nanos();
+        const bool taints_were_on = snap.taints_enabled();
+        std::string outcome;
+        bool threw = false;
+        size_t returned = 0;
+        try {
+            if (call) {
+                returned = call();
+            } else {
+                std::vector<std::pair<NodeEvent, const corev1::Node *>> e;
+                for (const auto &[k, n] : ev) e.emplace_back(k, &n);
+                returned = ctx.observe_nodes(e);
+            }
+            outcome = "returned " + std::to_string(returned);
+        } catch (const EncodeError &e) {
+            threw = true;
+            outcome = std::string("threw ") + e.what();
+        }
+        CHECK(threw == expect_throw);
+        if (threw) {  // the strong guarantee: every observable as before the step (a LIST issued before the throw was a LIST all the same)
+            CHECK(observables(snap) == before);
+            CHECK(lister->list_calls == lists + lists_of_a_throw);
+            serve(pods);
+        } else {
+            nodes = std::move(nodes_next);
+            pods = std::move(pods_next);
+        }
+        if (kind == kHeartbeat) CHECK(returned == 0 && snap.generation() == gen && observables(snap) == before);
+        if (kind == kAddedWithPods) CHECK(lister->list_calls == lists + 1);
+        if (kind == kEnableTaints) CHECK(snap.taints_enabled() && (!taints_were_on || observables(snap) == before));  // the first call switches the extension on, every later one changes nothing
+        if (kind == kFinerUnit) counted = snap.cpu_unit_nanos() < cpu_unit || snap.mem_unit_nanos() < mem_unit;
+        CHECK(ctx.node_store.size() == nodes.size());
+        const std::set<std::string> keys(snap.columns().keys.begin(), snap.columns().keys.end());
+        CHECK(same(decode(snap, ctx.node_store), fresh(ctx.node_store, lister->pods, keys, snap.taints_enabled())));
+        check_store_maps(ctx);
+        if (counted) ++count[kind];
+        if (g_fail != failed_before) std::printf("    at step %u (%s): %s\n", step_no, kKind[kind].name, outcome.c_str());
+        if (dump) std::printf("step %u | %s | %s | list_calls=%llu %s\n", step_no, kKind[kind].name, outcome.c_str(), (unsigned long long)lister->list_calls, observables(snap).c_str());
+        ++step_no;
+    }
+};
+
+static void walk_tests(const std::vector<uint64_t> &seeds, uint32_t steps, bool dump) {
+    for (const uint64_t seed : seeds) {
+        run(("walk, seed " + std::to_string(seed)).c_str(), [&] {
+            Walk w(seed);
+            w.dump = dump;
+            w.late = steps * 2 / 5;
+            w.start(false);
+            while (w.step_no < steps) w.step();
+            for (int k = 0; k < kKinds; ++k) {
+                std::printf("    %5zu  %s\n", w.count[k], kKind[k].name);
+                CHECK(w.count[k] >= 20);
+            }
+        });
+    }
+}
+
 // ---- GPU: objects -> events -> reconcile_batch, against a snapshot built from scratch ------------------------------------------
 struct RecordingSink : BindingSink {
     std::vector<std::pair<std::string, std::string>> posts;
@@ -311,14 +817,91 @@ static void gpu_tests() {
         CHECK(bound_n > 50 && bound_n < pp.size());
         std::printf("    %zu of %zu pods bound, the same nodes through both snapshots\n", bound_n, pp.size());
     });
+    run("a walk of 200 steps: the device holds what the host columns say", [&] {
+        Walk w(11);
+        w.keep_layout = true;
+        w.late = 80;
+        w.start(true);
+        DeviceEvaluator ref(w.ctx.device);  // a fresh ctx, given the host columns at every check
+        size_t checks = 0;
+        while (w.step_no < 200) {
+            w.step();
+            if (w.step_no % 10) continue;
+            Snapshot &s = *w.ctx.snapshot;
+            const NodeColumns &c = s.columns();
+            CHECK(s.device_count() == 1);  // (device() is every device: KSCHED_SHARDED=1 shards over the one)
+            DeviceEvaluator &d = s.device();
+            std::vector<int64_t> cpu(c.n), mem(c.n);
+            d.check(ksched_read_nodes(d.handle(), 0, c.n, cpu.data(), mem.data()), "ksched_read_nodes");
+            CHECK(cpu == c.avail_cpu_milli && mem == c.avail_mem_bytes);
+            uint64_t got[2] = {}, want[2] = {};
+            d.check(ksched_index_checksum(d.handle(), got), "ksched_index_checksum");
+            const bool with_taints = s.taints_enabled() && !s.taint_ids().empty();
+            ref.check(ksched_set_nodes(ref.handle(), c.n, c.avail_cpu_milli.data(), c.avail_mem_bytes.data(), c.n_keys ? c.label_val_ids.data() : nullptr,
+                                       c.n_keys, with_taints ? c.taints.data() : nullptr),
+                      "ksched_set_nodes");
+            ref.check(ksched_index_checksum(ref.handle(), want), "ksched_index_checksum");
+            CHECK(got[0] == want[0] && got[1] == want[1]);
+            checks += got[0] != 0;
+        }
+        CHECK(checks >= 10);  // (an indexed snapshot at most of the checks: the comparison is not one of zeros)
+        std::printf("    %u steps, %zu checks of an indexed snapshot\n", w.step_no, checks);
+    });
+}
+
+// ---- timing of what the batch loop's figure does not hold: the snapshot build and a node joining (encode-only, no device) -------------
+struct ByNodeLister : PodLister {
+    std::map<std::string, std::vector<corev1::Pod>> by_node;
+    std::vector<corev1::Pod> list_pods_on_node(const std::string &node_name) override { return by_node[node_name]; }
+};
+
+static void time_tests() {
+    ByNodeLister l;
+    std::vector<corev1::Node> nodes;
+    const char *zones[] = {"z1", "z2", "z3", "z4"};
+    for (int i = 0; i < 5000; ++i) {
+        const std::string nm = "n" + std::to_string(100000 + i);
+        nodes.push_back(node(nm, "64", "256Gi", {{"zone", zones[i % 4]}, {"disk", (i % 2) ? "ssd" : "hdd"}}, {{"t" + std::to_string(i % 8), "NoSchedule"}}));
+        for (int j = 0; j < 20; ++j) l.by_node[nm].push_back(pod("p" + std::to_string(i) + "_" + std::to_string(j), "250m", "512Mi", nm.c_str()));
+    }
+    const corev1::Node joins = node("n200000", "64", "256Gi", {{"zone", "z1"}});
+    for (int j = 0; j < 20; ++j) l.by_node["n200000"].push_back(pod("pj_" + std::to_string(j), "250m", "512Mi", "n200000"));
+    corev1::Node relabelled = nodes[2500];
+    (*relabelled.metadata.labels)["zone"] = "z2";
+    auto ms = [](const std::function<void()> &f) {
+        const auto t0 = std::chrono::steady_clock::now();
+        f();
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    for (int rep = 0; rep < 5; ++rep) {
+        Snapshot s(Snapshot::kEncodeOnly);
+        s.ensure_keys(kKeys);
+        s.enable_taints();
+        const double rebuild = ms([&] { s.rebuild(nodes, &l); });
+        const double label = ms([&] { CHECK(s.observe_nodes({{NodeEvent::Applied, &relabelled}}, &l) == 1); });
+        const double added = ms([&] { CHECK(s.observe_nodes({{NodeEvent::Applied, &joins}}, &l) == 1); });
+        CHECK(s.n() == 5001 && s.counted_pods() == 5001 * 20);
+        std::printf("run %d: rebuild %.2f ms, one label change %.4f ms, one Added event %.2f ms\n", rep, rebuild, label, added);
+    }
 }
 
 int main(int argc, char **argv) {
     const std::string mode = argc > 1 ? argv[1] : "cpu";
+    std::vector<uint64_t> seeds = {1, 2, 3};
+    uint32_t steps = 2000;
+    bool dump = false;
+    for (int i = 2; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--dump") dump = true;
+        else if (a == "--seed" && i + 1 < argc) seeds = {std::strtoull(argv[++i], nullptr, 10)};
+        else if (a == "--steps" && i + 1 < argc) steps = (uint32_t)std::strtoul(argv[++i], nullptr, 10);
+    }
     if (mode == "cpu") cpu_tests();
+    else if (mode == "walk") walk_tests(seeds, steps, dump);
+    else if (mode == "time") time_tests();
     else if (mode == "gpu") gpu_tests();
     else {
-        std::printf("usage: node_events_tests cpu|gpu\n");
+        std::printf("usage: node_events_tests cpu|walk [--seed S] [--steps N] [--dump]|time|gpu\n");
         return 2;
     }
     std::printf("%d failed check(s)\n", g_fail);
