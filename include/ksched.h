@@ -22,6 +22,7 @@
  *   (extension E2, BASELINE.json config 5)               KSCHED_TAINT
  *   (extension E3: the batch holds every pod's whole row)  KSCHED_PICK_UNIFORM
  *   (extension E4: ... and the nodes' available resources)  KSCHED_PICK_SPREAD
+ *   (extension E5: E4 towards the fullest node)            KSCHED_PICK_PACK
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -125,6 +126,34 @@ extern "C" {
  * have no effect on it; ksched_pipe_submit takes its split route with events, and a slot's mask is not overwritten before the slot's spread
  * pick has read it.  ksched_last_pick: "spread". */
 #define KSCHED_PICK_SPREAD 0x80u
+/* KSCHED_PICK_PACK (extension E5): the tightest of d uniformly drawn feasible nodes -- the spread pick towards the fullest node instead of
+ * the emptiest, for a caller that consolidates load; -1 only when the pod has none.  At most one KSCHED_PICK_* flag per call.  Added in
+ * ABI 7 without a version change and without a new symbol: detect it by this constant and by KSCHED_E_INVAL from an older library.
+ *   draws      : d = attempts, 1 <= d <= KSCHED_MAX_ATTEMPTS.  ALL d entries of the pod's row are read as 32-bit draws:
+ *                u_j = samples[pod * attempts + j].  A draw is a number, not a node index.
+ *   candidates : c = set bits of the pod's feasible row over nodes [0, n).  c == 0: binding -1.  Otherwise k_j = (uint64(u_j) * c) >> 32 and
+ *                v_j is the index of the pod's k_j-th set bit (0-based, ascending node index) -- exactly KSCHED_PICK_UNIFORM's rule, once per
+ *                draw.  Candidates may repeat.
+ *   result     : the candidate with the SMALLEST signed 64-bit (avail_mem[v], avail_cpu[v]), compared lexicographically, memory first.
+ *                This is best fit's key: for a fixed pod the residual orders as `available` does.  Ties go to the lowest node index.  The
+ *                result does not depend on the order of the draws.  No request column is read: ksched_pick_device needs no req_mem_bytes.
+ *   available  : the snapshot as an evaluation enqueued at that point sees it: a ksched_set_nodes, ksched_update_nodes or
+ *                ksched_apply_bindings_device enqueued before the call is visible, a change enqueued after it is not -- also when the call
+ *                is ksched_pick_device on a stream of its own.
+ *   exact      : integers and comparisons only -- same inputs, same bits, on every run.  Negative `available` is legal and compares as
+ *                signed.  d = 1 gives, bit for bit, the bindings of KSCHED_PICK_UNIFORM for the same column 0.
+ *   ignored    : bits at or beyond n in a row's last word and the words [W, pitch) are never counted and never chosen -- also in the masks a
+ *                caller hands to ksched_pick_device / ksched_pick.
+ *   n == 0 gives -1 for every pod; p == 0 is a no-op.
+ * Accepted, with identical results, by ksched_eval, ksched_eval_begin / ksched_eval_end, ksched_eval_device, ksched_eval_device_pitched,
+ * ksched_pick_device, ksched_pick and ksched_pipe_submit (ksched_summarize* takes no pick flag).  Errors as for KSCHED_PICK_SPREAD:
+ * KSCHED_E_INVAL for two pick flags at once, out_binding == NULL, samples == NULL with p > 0, attempts == 0 or above the maximum;
+ * KSCHED_E_STATE exactly where the uniform pick returns it.  The plan is the spread pick's too: the pick always reads the mask, behind the
+ * mask kernel; a request without out_feasible evaluates into the ctx's scratch mask; KSCHED_OPT_PICK_FROM_MASK / KSCHED_OPT_FUSED_PICK
+ * have no effect on it; ksched_pipe_submit takes its split route with events, and a slot's mask is not overwritten before the slot's pack
+ * pick has read it.  The best-fit order is neither needed nor rebuilt: after a snapshot change a pack request costs what it cost before.
+ * ksched_last_pick: "pack". */
+#define KSCHED_PICK_PACK 0x100u
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0
@@ -194,7 +223,7 @@ extern "C" {
  * the previous one's blocks still store -- as far as the chip has room for them: KSCHED_OPT_GRID_CUS).  Same results either way;
  * in every mode, and across a change of mode, a slot's mask kernel runs behind the slot's previous mask kernel, its pick behind the
  * slot's previous pick, and a slot's mask is not overwritten by a later submit before the slot's previous pick, where that pick
- * reads the mask (the uniform and the spread pick always do), has run.  ksched_pipe_wait / ksched_pipe_wait_mask order a consumer behind the slot's work, ksched_pipe_slot_stream names its stream. */
+ * reads the mask (the uniform, the spread and the pack pick always do), has run.  ksched_pipe_wait / ksched_pipe_wait_mask order a consumer behind the slot's work, ksched_pipe_slot_stream names its stream. */
 #define KSCHED_OPT_PIPE_MODE 11
 #define KSCHED_PIPE_MAX_STREAMS 8u
 /* KSCHED_OPT_GRID_CUS: how many of the chip's 256 compute units ONE fused mask launch may occupy (0, the default, = all of them;
@@ -364,7 +393,7 @@ uint32_t ksched_num_keys(const ksched_ctx *ctx);
  *   samples       : [p][attempts] node indices or NULL       -- only read with KSCHED_PICK_SAMPLED
  *                   an index >= n is treated as an infeasible draw
  *                   (with KSCHED_PICK_UNIFORM: 32-bit draws, of which entry 0 of every row is read;
- *                   with KSCHED_PICK_SPREAD: 32-bit draws, all `attempts` of every row are read)
+ *                   with KSCHED_PICK_SPREAD or KSCHED_PICK_PACK: 32-bit draws, all `attempts` of every row are read)
  *   out_feasible  : [p][W] or NULL
  *   out_fit       : [p][W] or NULL; requires KSCHED_WANT_FIT_MASK
  *   out_binding   : [p] or NULL; requires one of the KSCHED_PICK_* flags; -1 = no node
@@ -474,8 +503,9 @@ int ksched_mask_probe_report(ksched_ctx *ctx, double *out_us, uint32_t cap);
  * run the mask kernel of batch i + 1 and the pick of batch i on different HIP streams (the two do not depend on each
  * other; the mask of batch i must stay untouched until its pick has run).
  *   flags        : exactly one of KSCHED_PICK_SAMPLED (select_node_for_pod, src/main.rs:51-71: `samples`, `attempts`),
- *                  KSCHED_PICK_BESTFIT (extension E1), KSCHED_PICK_UNIFORM (extension E3: `samples`, `attempts`) and
- *                  KSCHED_PICK_SPREAD (extension E4: `samples`, `attempts`; it reads the snapshot's available columns);
+ *                  KSCHED_PICK_BESTFIT (extension E1), KSCHED_PICK_UNIFORM (extension E3: `samples`, `attempts`),
+ *                  KSCHED_PICK_SPREAD (extension E4: `samples`, `attempts`; it reads the snapshot's available columns) and
+ *                  KSCHED_PICK_PACK (extension E5: as E4);
  *                  KSCHED_FIT tells the best-fit pick that the mask includes the resource fit (then `req_mem_bytes` [p]
  *                  is read to skip candidates that cannot fit)
  *   feasible     : [p] rows, mask_pitch_words apart, as written by ksched_eval_device_pitched
@@ -667,7 +697,7 @@ int ksched_index_checksum(ksched_ctx *ctx, uint64_t *out /* [2] */);
 const char *ksched_last_kernel(const ksched_ctx *ctx);
 /* how the pick of the last ksched_eval* ran: "fused-tile" / "fused" (it rode in the fused mask launch as tile tests / as waves of
  * the fill, KSCHED_OPT_FUSED_PICK), "select" (its own launch testing the drawn candidates), "bestfit-rows", "from-mask"
- * (KSCHED_OPT_PICK_FROM_MASK / no bitmap index), "uniform" (KSCHED_PICK_UNIFORM), "spread" (KSCHED_PICK_SPREAD), "none" */
+ * (KSCHED_OPT_PICK_FROM_MASK / no bitmap index), "uniform" (KSCHED_PICK_UNIFORM), "spread" (KSCHED_PICK_SPREAD), "pack" (KSCHED_PICK_PACK), "none" */
 const char *ksched_last_pick(const ksched_ctx *ctx);
 
 #ifdef __cplusplus

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 
-DRAWS = L.PICK_SAMPLED | L.PICK_UNIFORM | L.PICK_SPREAD  # the picks that read `samples`
+DRAWS = L.PICK_SAMPLED | L.PICK_UNIFORM | L.PICK_SPREAD | L.PICK_PACK  # the picks that read `samples`
 
 # element kinds of the C ABI: the torch dtypes that may stand for them (int64 stands in for uint64, int32 for uint32, bool for uint8)
 KINDS = {"i64": ("int64",), "u64": ("int64", "uint64"), "i32": ("int32",), "u32": ("int32", "uint32"), "u8": ("uint8", "bool")}
@@ -85,7 +85,7 @@ def _vp(address: Optional[int]):
 
 def draws(samples, name: str, flags: int, p: int, device: Optional[int] = None):
     """(address, attempts, what the address points into): `samples` is read exactly when flags carry PICK_SAMPLED (node indices),
-    PICK_UNIFORM (32-bit draws, column 0) or PICK_SPREAD (32-bit draws, every column) and must then be a contiguous [p, attempts >= 1] uint32 array (device None: whatever numpy
+    PICK_UNIFORM (32-bit draws, column 0) or PICK_SPREAD / PICK_PACK (32-bit draws, every column) and must then be a contiguous [p, attempts >= 1] uint32 array (device None: whatever numpy
     converts) or CUDA tensor on cuda:`device`; a wrong shape would be an out-of-bounds read.  Without such a flag attempts is 0 and
     nothing reads it, whatever its shape."""
     if device is None:
@@ -93,7 +93,7 @@ def draws(samples, name: str, flags: int, p: int, device: Optional[int] = None):
     attempts = 0
     if flags & DRAWS:
         if samples is None or len(samples.shape) != 2 or int(samples.shape[0]) != p or int(samples.shape[1]) < 1:
-            raise ValueError(f"{name}: expected a contiguous [{p}, attempts >= 1] array with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM / KSCHED_PICK_SPREAD, "
+            raise ValueError(f"{name}: expected a contiguous [{p}, attempts >= 1] array with KSCHED_PICK_SAMPLED / KSCHED_PICK_UNIFORM / KSCHED_PICK_SPREAD / KSCHED_PICK_PACK, "
                              f"got {None if samples is None else tuple(samples.shape)}")
         attempts = int(samples.shape[1])
     return host_ptr(samples) if device is None else _vp(device_ptr(samples, name, "u32", None, device)), attempts, samples

@@ -17,9 +17,9 @@ namespace ksched {
 // Does the pick read the feasibility mask?  By default it does not (sampled: the drawn candidates are tested from the columns;
 // best fit: bitmaps kept in best-fit order); it does with KSCHED_OPT_PICK_FROM_MASK, and a best-fit pick does when the snapshot
 // has no best-fit rows (`bf_rows`: they exist, or will once ensure_bestfit has run).  The uniform pick (KSCHED_PICK_UNIFORM) always does:
-// it counts and ranks the row's set bits; so does the spread pick (KSCHED_PICK_SPREAD), once per draw.
+// it counts and ranks the row's set bits; so do the spread pick (KSCHED_PICK_SPREAD) and the pack pick (KSCHED_PICK_PACK), once per draw.
 inline bool pick_reads_mask(uint32_t flags, bool opt_pick_from_mask, bool bf_rows) {
-    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD)) return true;
+    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)) return true;
     return (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) && (opt_pick_from_mask || ((flags & KSCHED_PICK_BESTFIT) && !bf_rows));
 }
 
@@ -51,6 +51,7 @@ enum class SampledPick { kNone, kOwnLaunch, kRidesFill, kRidesTiles, kFromMask }
 enum class BestfitPick { kNone, kRowsOneStage, kRowsTwoStages, kRowsTwoStagesListed, kFromMask };
 enum class UniformPick { kNone, kFromMask };  // k_pick_uniform behind the mask kernel: the only form
 enum class SpreadPick { kNone, kFromMask };   // k_pick_spread behind the mask kernel: the only form
+enum class PackPick { kNone, kFromMask };     // k_pick_pack behind the mask kernel: the only form
 enum class PlanError { kNone, kFusedNotApplicable, kTilePickNotApplicable, kListKeysTooManyNodes };
 
 struct EvalPlan {
@@ -62,13 +63,14 @@ struct EvalPlan {
     BestfitPick bestfit = BestfitPick::kNone;
     UniformPick uniform = UniformPick::kNone;
     SpreadPick spread = SpreadPick::kNone;
+    PackPick pack = PackPick::kNone;
     const char *last_kernel = nullptr;  // ksched_last_kernel after the launch; nullptr = no mask kernel runs, it stays what it was
     const char *last_pick = "none";     // ksched_last_pick
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
     // a pick launch follows the mask kernel and reads what it wrote
-    bool pick_from_mask() const { return sampled == SampledPick::kFromMask || bestfit == BestfitPick::kFromMask || uniform == UniformPick::kFromMask || spread == SpreadPick::kFromMask; }
+    bool pick_from_mask() const { return sampled == SampledPick::kFromMask || bestfit == BestfitPick::kFromMask || uniform == UniformPick::kFromMask || spread == SpreadPick::kFromMask || pack == PackPick::kFromMask; }
 };
 
 inline EvalPlan plan_unsupported(PlanError why) {
@@ -90,7 +92,8 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     // The uniform pick counts and ranks the set bits of the pod's whole row: the mask kernel always runs (into the ctx's scratch mask when
     // the caller gave none), the pick is its own launch behind it, and neither KSCHED_OPT_PICK_FROM_MASK nor KSCHED_OPT_FUSED_PICK applies.
     // The spread pick (KSCHED_PICK_SPREAD) does the same once per draw and compares the candidates: the same plan, its own kernel.
-    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD)) {
+    // The pack pick (KSCHED_PICK_PACK) is the spread pick with the comparison turned round: the same plan again.
+    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)) {
         if (kern == KSCHED_KERNEL_FUSED && !can_fused) return plan_unsupported(PlanError::kFusedNotApplicable);
         plan.scratch_mask = !f.have_feas;
         plan.mask = kern == KSCHED_KERNEL_FUSED ? MaskKernel::kFused : MaskKernel::kDirect;
@@ -98,6 +101,11 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
         if (flags & KSCHED_PICK_SPREAD) {
             plan.spread = SpreadPick::kFromMask;
             plan.last_pick = "spread";
+            return plan;
+        }
+        if (flags & KSCHED_PICK_PACK) {
+            plan.pack = PackPick::kFromMask;
+            plan.last_pick = "pack";
             return plan;
         }
         plan.uniform = UniformPick::kFromMask;

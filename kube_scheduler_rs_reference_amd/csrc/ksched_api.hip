@@ -31,6 +31,7 @@
 #include "kernels_pick_uniform.hpp"
 #include "kernels_summary.hpp"
 #include "kernels_pick_spread.hpp"  // (uses kernels_pick_uniform.hpp's helpers)
+#include "kernels_pick_pack.hpp"    // (k_pick_spread's body with the comparison turned round)
 #include "mask_alloc.hpp"
 #include "merge_sort_plan.hpp"
 #include "pipe_plan.hpp"
@@ -1039,6 +1040,9 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
     } else if (r.flags & KSCHED_PICK_SPREAD) {  // (c->n > 0 likewise; the stream_enter above puts the columns it reads behind the latest snapshot change)
         hipLaunchKernelGGL(k_pick_spread, dim3((r.p + kSpreadWaves - 1) / kSpreadWaves), dim3(64 * kSpreadWaves), 0, s, feas, r.samples,
                            (const int64_t *)c->nmem.ptr, (const int64_t *)c->ncpu.ptr, r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
+    } else if (r.flags & KSCHED_PICK_PACK) {  // (c->n > 0 and the columns behind the latest snapshot change, as for the spread pick; no best-fit order involved)
+        hipLaunchKernelGGL(k_pick_pack, dim3((r.p + kPackWaves - 1) / kPackWaves), dim3(64 * kPackWaves), 0, s, feas, r.samples,
+                           (const int64_t *)c->nmem.ptr, (const int64_t *)c->ncpu.ptr, r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
     }
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
@@ -1229,7 +1233,7 @@ int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
     if (c->n == 0) {
         // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
         // yields None on every attempt, src/main.rs:56,70)
-        if ((pick_s || pick_b || (r.flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD))) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
+        if ((pick_s || pick_b || (r.flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK))) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
         return KSCHED_OK;
     }
     fault_point(c);
@@ -1284,9 +1288,9 @@ int stage_batch(ksched_ctx *c, uint32_t p, const HostBatch &h, hipStream_t s) {
 }
 
 // the pick flags: at most one per call
-constexpr uint32_t kPickFlags = KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD;
-// the picks that read `samples`: node indices (sampled), 32-bit draws (uniform: entry 0 of every row; spread: all `attempts` of them)
-constexpr uint32_t kDrawPicks = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD;
+constexpr uint32_t kPickFlags = KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK;
+// the picks that read `samples`: node indices (sampled), 32-bit draws (uniform: entry 0 of every row; spread and pack: all `attempts` of them)
+constexpr uint32_t kDrawPicks = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK;
 inline bool at_most_one_pick(uint32_t flags) {
     const uint32_t pick = flags & kPickFlags;
     return (pick & (pick - 1u)) == 0;
@@ -1894,7 +1898,7 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
     if (!c) return KSCHED_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    // (pick_s: the pick reads draws -- sampled, uniform or spread)
+    // (pick_s: the pick reads draws -- sampled, uniform, spread or pack)
     const bool pick_s = flags & kDrawPicks, pick_b = flags & KSCHED_PICK_BESTFIT;
     if (int rc = check_pick_args(c->n, p, feasible, req_mem_bytes, samples, attempts, flags, out_binding)) return rc;
     if (p == 0) return KSCHED_OK;
@@ -1938,7 +1942,7 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
     const size_t W = c->W;
     const size_t pitch = ksched_mask_pitch(c->n);
     const bool pick = flags & kPickFlags;
-    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled, uniform or spread pick
+    HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled, uniform, spread or pack pick
     b.pcpu = h.pcpu;
     b.pmem = h.pmem;
     if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride;
@@ -1956,7 +1960,7 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
 
     if (int rc = stage_batch(c, p, b, s)) return rc;
     uint64_t *d_feas = nullptr, *d_fit = nullptr;
-    // a mask is needed when the caller wants it, or when the pick reads it (uniform and spread; best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
+    // a mask is needed when the caller wants it, or when the pick reads it (uniform, spread and pack; best fit; sampled only with KSCHED_OPT_PICK_FROM_MASK)
     if (out_feas || pick_reads_mask(flags, c->opt_pick_from_mask, bf_rows_expected(c))) {
         HIPCHK(c, c->feas.reserve((size_t)p * pitch));
         d_feas = c->feas.ptr;

@@ -15,7 +15,7 @@
 //   3. its pick, if it reads the mask, runs after its own mask kernel;
 //   4. its pick runs after the slot's previous pick (both write the slot's bindings).
 //
-// The rules.  By default the pick does not read the mask (eval_plan.hpp, pick_reads_mask), so in the steady state the streams need
+// The rules.  By default the pick does not read the mask (eval_plan.hpp, pick_reads_mask: the uniform, spread and pack picks always do), so in the steady state the streams need
 // no event at all: mask kernels of successive batches on one stream and picks on another, or a slot's whole evaluation on the same
 // stream every time.  Events order a slot only where its previous use ran elsewhere, or where a pick reads the mask.
 //

@@ -460,7 +460,7 @@ class PipelinedScheduler:
             if self._alternate:
                 # The slot's all-gather is pre-bound to stream (k mod 2) and relies on the pick having gone onto that very stream.
                 # ksched_pipe_submit falls back to its split mode when the pick reads the mask (KSCHED_OPT_PICK_FROM_MASK, a best-fit
-                # pick without the bitmap index, KSCHED_PICK_UNIFORM and KSCHED_PICK_SPREAD always) and deals slots over more streams when KSCHED_OPT_PIPE_MODE > 2: the pick is then
+                # pick without the bitmap index, KSCHED_PICK_UNIFORM, KSCHED_PICK_SPREAD and KSCHED_PICK_PACK always) and deals slots over more streams when KSCHED_OPT_PIPE_MODE > 2: the pick is then
                 # somewhere else.  Asked after EVERY submit (one C call; the option can change between two steps: ADVICE r5).
                 used = self.pipe.slot_stream_handle(k)
                 if used != self._stream2_handles[k & 1]:

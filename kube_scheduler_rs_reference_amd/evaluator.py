@@ -22,7 +22,7 @@ def mask_words(n_nodes: int) -> int:
     return (int(n_nodes) + 63) // 64
 
 
-_PICKS = L.PICK_SAMPLED | L.PICK_BESTFIT | L.PICK_UNIFORM | L.PICK_SPREAD  # at most one per call
+_PICKS = L.PICK_SAMPLED | L.PICK_BESTFIT | L.PICK_UNIFORM | L.PICK_SPREAD | L.PICK_PACK  # at most one per call
 _ptr = M.host_ptr
 
 
@@ -132,7 +132,7 @@ class Evaluator:
 
     @property
     def last_pick(self) -> str:
-        """How the latest evaluation's pick ran: "fused-tile" / "fused" (inside the mask launch), "select", "bestfit-rows", "from-mask", "uniform", "spread", "none"."""
+        """How the latest evaluation's pick ran: "fused-tile" / "fused" (inside the mask launch), "select", "bestfit-rows", "from-mask", "uniform", "spread", "pack", "none"."""
         return self._lib.ksched_last_pick(self._h).decode()
 
     @property
@@ -199,7 +199,8 @@ class Evaluator:
              want_mask: bool = True, out: "EvalResult | None" = None) -> EvalResult:
         """flags: predicates, at most one of PICK_SAMPLED (samples [p][attempts] node indices), PICK_BESTFIT and PICK_UNIFORM (samples [p][attempts]
         32-bit draws of which column 0 is read: uniformly among the pod's feasible nodes) and PICK_SPREAD (samples [p][d] 32-bit draws, all read:
-        the least loaded -- available memory, then cpu, then the lowest index -- of d uniformly drawn feasible nodes), WANT_FIT_MASK.
+        the least loaded -- available memory, then cpu, then the lowest index -- of d uniformly drawn feasible nodes) and PICK_PACK
+        (the same draws: the tightest -- the smallest available memory, then cpu, then the lowest index -- of them), WANT_FIT_MASK.
         `out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4)."""
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
@@ -225,7 +226,7 @@ class Evaluator:
                     flags: int = L.FIT, out_feasible=None, out_fit=None, out_binding=None, stream=None):
         """All arguments are torch CUDA tensors on this evaluator's device (int64 stands in for
         uint64, int32 for uint32).  Work is enqueued on `stream` (default: torch's current stream).  `samples` [p, attempts] is read with
-        PICK_SAMPLED (node indices), with PICK_UNIFORM (32-bit draws, column 0) and with PICK_SPREAD (32-bit draws, every column)."""
+        PICK_SAMPLED (node indices), with PICK_UNIFORM (32-bit draws, column 0) and with PICK_SPREAD / PICK_PACK (32-bit draws, every column)."""
         calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                              [out_feasible], out_fit, [out_binding], stream)
         self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
@@ -262,7 +263,7 @@ class Evaluator:
     def pick_device(self, feasible, flags: int, out_binding, req_mem_bytes=None, samples=None, stream=None):
         """The pick alone (ksched_pick_device) from a [p, W] device mask written by eval_device: torch CUDA tensors,
         enqueued on `stream` (default: torch's current stream).  flags: PICK_SAMPLED (+ samples [p, attempts]),
-        PICK_UNIFORM (+ samples [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD (+ samples [p, d]: 32-bit draws, all read; the nodes'
+        PICK_UNIFORM (+ samples [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD / PICK_PACK (+ samples [p, d]: 32-bit draws, all read; the nodes'
         available columns as this stream sees them at this point) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask
         includes the resource fit)."""
         import torch
@@ -279,7 +280,7 @@ class Evaluator:
     def pick(self, feasible: np.ndarray, flags: int, req_mem_bytes=None, samples=None) -> np.ndarray:
         """The pick alone from HOST masks (ksched_pick): `feasible` = [p, W] uint64 rows as `eval` returns them (or as a caller has combined
         them: ANDed masks of a selector evaluated in key groups).  flags: PICK_SAMPLED (+ samples [p, attempts]), PICK_UNIFORM (+ samples
-        [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD (+ samples [p, d]: 32-bit draws, all read) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
+        [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD / PICK_PACK (+ samples [p, d]: 32-bit draws, all read; no req_mem_bytes needed) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
         f = M.host_array(feasible, "feasible", "u64", (None, self.W))
         b = M.host_batch(self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=f.shape[0])
         out = np.empty((b.p,), dtype=np.int32)
@@ -421,7 +422,7 @@ class Pipe:
 
     def submit(self, slot: int, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags: int, mask, binding):
         """torch CUDA tensors (see Evaluator.eval_device); `mask` is a [p, W] (possibly pitched) view, `binding` int32 [p].  flags carry one
-        of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM, PICK_SPREAD (the uniform and the spread pick read the mask: their slot runs in the split mode, ordered by events)."""
+        of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM, PICK_SPREAD, PICK_PACK (the uniform, the spread and the pack pick read the mask: their slot runs in the split mode, ordered by events)."""
         b, per_slot = self._marshal((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags, [mask], [binding])
         self.ev._check(self._lib.ksched_pipe_submit(self._h, slot, *b[:8], *per_slot[0]), "ksched_pipe_submit")
 

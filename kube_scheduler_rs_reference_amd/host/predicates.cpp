@@ -179,8 +179,8 @@ std::vector<corev1::Pod> split_wide_pod(const corev1::Pod &pod) {
     return out;
 }
 
-// the picks that read `samples`: [p][attempts] node indices (sampled), 32-bit draws of which entry 0 is read (uniform) or all are (spread)
-constexpr uint32_t kPicksWithDraws = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD;
+// the picks that read `samples`: [p][attempts] node indices (sampled), 32-bit draws of which entry 0 is read (uniform) or all are (spread, pack)
+constexpr uint32_t kPicksWithDraws = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK;
 
 // A pod whose selector has more keys than one call takes (row `i` of `out`): one device evaluation per key group against that group's
 // label columns, the groups' feasible masks ANDed (does_node_selector_match is a conjunction over the keys, src/predicates.rs:48-53;
@@ -258,7 +258,7 @@ BatchValidity check_node_validity_batch(const std::vector<const corev1::Pod *> &
     out.n = snap.n();
     out.W = snap.mask_words();
     out.flags = KSCHED_FIT | KSCHED_SEL | ((taints && snap.has_taints()) ? KSCHED_TAINT : 0u);
-    const uint32_t pick = pick_flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD);
+    const uint32_t pick = pick_flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK);
     if (!want_masks && !pick) throw EncodeError("check_node_validity_batch: nothing asked for (no masks, no pick)");
     if (want_masks) {
         out.feasible.assign((size_t)out.p * out.W, 0ull);

@@ -63,7 +63,7 @@ struct BatchValidity {
 
 // check_node_validity for every (pod, node) pair.  `pick_flags` may add KSCHED_PICK_SAMPLED (with
 // `samples`, [p][attempts] canonical node indices), KSCHED_PICK_UNIFORM (with `samples`, [p][attempts] 32-bit draws of which
-// entry 0 of every row is read), KSCHED_PICK_SPREAD (with `samples`, [p][attempts] 32-bit draws, all read) or KSCHED_PICK_BESTFIT; `taints` adds extension E2.
+// entry 0 of every row is read), KSCHED_PICK_SPREAD or KSCHED_PICK_PACK (with `samples`, [p][attempts] 32-bit draws, all read) or KSCHED_PICK_BESTFIT; `taints` adds extension E2.
 // want_masks = false (with a pick): bindings only -- `feasible` / `fit` stay empty, no mask kernel runs and nothing but the bindings
 // comes back from the device (the reference's reconcile needs the chosen node, not the matrix: src/main.rs:53-66).
 // `samples_ready`: called (once or more) right before the first device call that reads `samples` -- a caller that is still filling the

@@ -62,22 +62,26 @@ BatchSelection select_nodes_for_pods(const std::vector<const corev1::Pod *> &pod
     // (refused before anything is evaluated or drawn)
     if (ctx.pick_spread && ctx.pick_uniform) throw EncodeError("select_nodes_for_pods: Context::pick_spread and Context::pick_uniform are both set (one pick per batch)");
     if (ctx.pick_spread > KSCHED_MAX_ATTEMPTS) throw EncodeError("select_nodes_for_pods: Context::pick_spread is above KSCHED_MAX_ATTEMPTS");
+    if (ctx.pick_pack && (ctx.pick_uniform || ctx.pick_spread)) throw EncodeError("select_nodes_for_pods: Context::pick_pack is set together with Context::pick_uniform or Context::pick_spread (one pick per batch)");
+    if (ctx.pick_pack > KSCHED_MAX_ATTEMPTS) throw EncodeError("select_nodes_for_pods: Context::pick_pack is above KSCHED_MAX_ATTEMPTS");
     if (!ctx.snapshot) ctx.refresh_snapshot();
     Snapshot &snap = *ctx.snapshot;
     const uint32_t p = (uint32_t)pods.size(), n = snap.n();
     BatchSelection out;
     out.node_store_index.assign(p, -1);
-    if (ctx.pick_uniform || ctx.pick_spread) {
+    if (ctx.pick_uniform || ctx.pick_spread || ctx.pick_pack) {
         // extension E3: one 32-bit draw per pod, in pod order; the device ranks it among the pod's feasible nodes (KSCHED_PICK_UNIFORM).
         // extension E4: d = pick_spread draws per pod, in pod order and draw-major within a pod; the device ranks each and keeps the least
         // loaded of the d candidates (KSCHED_PICK_SPREAD).
+        // extension E5: d = pick_pack draws per pod, taken the same way; the device keeps the tightest of the d candidates (KSCHED_PICK_PACK).
         // No draw is ever rejected: `rejected` stays empty.  The masks ride along when the caller asked for the rejected draws' reasons.
         if (n == 0 || p == 0 || ctx.node_store.size() == 0) return out;
-        const uint32_t d = ctx.pick_spread ? ctx.pick_spread : 1u;
-        PhaseClock clock(ctx.pick_spread ? "select (spread)" : "select (uniform)");
+        const uint32_t d = ctx.pick_pack ? ctx.pick_pack : ctx.pick_spread ? ctx.pick_spread : 1u;
+        const uint32_t pick_flag = ctx.pick_pack ? KSCHED_PICK_PACK : ctx.pick_spread ? KSCHED_PICK_SPREAD : KSCHED_PICK_UNIFORM;
+        PhaseClock clock(ctx.pick_pack ? "select (pack)" : ctx.pick_spread ? "select (spread)" : "select (uniform)");
         std::vector<uint32_t> draws((size_t)p * d);
         for (uint32_t &u : draws) u = (uint32_t)chooser.choose(size_t(1) << 32).value_or(0);
-        out.validity = predicates::check_node_validity_batch(pods, ctx, /*taints=*/false, ctx.pick_spread ? KSCHED_PICK_SPREAD : KSCHED_PICK_UNIFORM, &draws, d,
+        out.validity = predicates::check_node_validity_batch(pods, ctx, /*taints=*/false, pick_flag, &draws, d,
                                                              /*want_masks=*/want_rejected);
         out.samples = std::move(draws);
         clock.lap("draws + check_node_validity_batch");
@@ -155,7 +159,7 @@ std::vector<std::vector<RejectedCandidate>> explain_rejected(const std::vector<c
     const uint32_t p = (uint32_t)pods.size();
     std::vector<std::vector<RejectedCandidate>> out(p);
     if (!ctx.snapshot || p == 0 || sel.samples.size() != (size_t)p * ATTEMPTS || sel.validity.binding.size() != p) return out;
-    if (ctx.pick_uniform || ctx.pick_spread) return out;  // (those draws are numbers, not node indices, and none of them is rejected)
+    if (ctx.pick_uniform || ctx.pick_spread || ctx.pick_pack) return out;  // (those draws are numbers, not node indices, and none of them is rejected)
     Snapshot &snap = *ctx.snapshot;
     const uint32_t n = snap.n();
     std::vector<std::pair<uint32_t, uint32_t>> pairs;

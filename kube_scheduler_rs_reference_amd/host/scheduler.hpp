@@ -69,12 +69,15 @@ std::optional<corev1::Node> select_node_for_pod(const corev1::Pod &pod, Context 
 // With Context::pick_spread = d > 0 (extension E4) the device keeps the least loaded of d such candidates (KSCHED_PICK_SPREAD): d draws per
 // pod, in pod order and draw-major within a pod, handed over as a [p][d] table; the largest (available memory, available cpu) wins, the
 // lowest node index among equals.  No rejected draws either.  Together with pick_uniform: EncodeError before anything is evaluated.
+// With Context::pick_pack = d > 0 (extension E5) the device keeps the tightest of d such candidates (KSCHED_PICK_PACK): the same [p][d] table
+// of draws, the smallest (available memory, available cpu) wins, the lowest node index among equals.  No rejected draws either.  Together
+// with pick_uniform or pick_spread: EncodeError before anything is evaluated.
 struct BatchSelection {
     std::vector<int32_t> node_store_index;             // [p] index into ctx.node_store or -1
     std::vector<std::vector<RejectedCandidate>> rejected;  // [p] candidates tried and refused, in order (filled on request)
     predicates::BatchValidity validity;                // the bindings; with want_rejected also both masks (canonical node order): without it no mask is computed or copied
     std::vector<uint32_t> samples;                     // [p][ATTEMPTS] the draws as canonical node indices (n = "no draw": empty store)
-                                                       // (Context::pick_uniform: [p][1] 32-bit draws, Context::pick_spread: [p][d]; empty when the store is)
+                                                       // (Context::pick_uniform: [p][1] 32-bit draws, Context::pick_spread / pick_pack: [p][d]; empty when the store is)
 };
 BatchSelection select_nodes_for_pods(const std::vector<const corev1::Pod *> &pods, Context &ctx, NodeChooser &chooser,
                                      bool want_rejected = false);

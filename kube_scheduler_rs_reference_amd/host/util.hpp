@@ -86,6 +86,13 @@ struct Context {
     // 0: nothing changes, draw for draw.
     uint32_t pick_spread = 0;
 
+    // Opt-in (0 = off, the default; extension E5): select_nodes_for_pods picks THE TIGHTEST OF d = pick_pack UNIFORMLY DRAWN FEASIBLE NODES
+    // on the device (KSCHED_PICK_PACK; 1 <= d <= KSCHED_MAX_ATTEMPTS): pick_spread's draws -- d per pod, chooser.choose(2^32), in pod order
+    // and draw-major within a pod -- with the comparison turned round: the smallest (available memory, available cpu) wins, the lowest node
+    // index among equals.  Not together with pick_uniform or pick_spread: refused before anything is evaluated.  Outside the parity claim.
+    // 0: nothing changes, draw for draw.
+    uint32_t pick_pack = 0;
+
     // (Re)build `snapshot` from node_store and one LIST per node.
     void refresh_snapshot();
     // Keep node_store and the snapshot current from node watch events, the way the reflector's writer does: an Applied node already in

@@ -39,6 +39,7 @@ pub const KSCHED_PICK_SAMPLED: u32 = 0x08;
 pub const KSCHED_PICK_BESTFIT: u32 = 0x10;
 pub const KSCHED_PICK_UNIFORM: u32 = 0x40;
 pub const KSCHED_PICK_SPREAD: u32 = 0x80;
+pub const KSCHED_PICK_PACK: u32 = 0x100;
 pub const KSCHED_WANT_FIT_MASK: u32 = 0x20;
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
@@ -290,6 +291,7 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_PICK_BESTFIT", KSCHED_PICK_BESTFIT as i64),
         ("KSCHED_PICK_UNIFORM", KSCHED_PICK_UNIFORM as i64),
         ("KSCHED_PICK_SPREAD", KSCHED_PICK_SPREAD as i64),
+        ("KSCHED_PICK_PACK", KSCHED_PICK_PACK as i64),
         ("KSCHED_WANT_FIT_MASK", KSCHED_WANT_FIT_MASK as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),

@@ -1,0 +1,473 @@
+"""KSCHED_PICK_PACK (extension E5) on the GPU, bit for bit against three answers:
+ (a) tests/pack_ref.py (the numpy restatement, pinned by tests/test_pack_restatement.py) on the oracle's feasibility mask -- or, for the
+     caller-made rows, on the rows themselves -- and the snapshot's columns;
+ (b) the device's own KSCHED_PICK_SPREAD on a second ctx whose snapshot holds the bitwise complement of both columns, through
+     ksched_pick_device on the same mask and draws (~x reverses the order of int64 exactly and both picks break ties to the lowest node);
+ (c) where the draws name every feasible node of every pod, the device's KSCHED_PICK_BESTFIT on small positive columns.
+Shapes are the smallest at which k_pick_pack takes each of its paths: rows of one word, around a lane's two words, the last register-path
+row (W = 128), the first chunked row (W = 129), three chunks with a ragged last word; pod counts that are no multiple of the four waves of
+a block; d = 1 (the uniform pick), 2, 3, 5 and 64 (every lane holds a candidate)."""
+import ctypes as C
+import dataclasses
+
+import numpy as np
+import pytest
+
+from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_PACK, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM, SEL, TAINT, Evaluator,
+                                             KschedError, _lib, synth)
+from tests import uniform_rows as R
+from tests.admit_ref import apply_while_fit_exact
+from tests.pack_ref import pack_pick, pack_pick_listed
+from tests.spread_ref import spread_candidates_listed
+from tests.test_gpu_uniform_pick import dev_of, mask_np, oracle_mask, pod_tensors, to_dev
+from tests.uniform_ref import uniform_pick
+
+pytestmark = pytest.mark.gpu
+
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+ROW_NODES = [1, 63, 64, 65, 8192, 8193, 16500]  # W = 1, 1, 1, 2, 128 (the last register-path row), 129 (the first chunked row), 258
+DS = [1, 2, 3, 5, 64]
+PODS = 37
+GUARD = 8
+
+
+@pytest.fixture
+def ev(evaluator):
+    evaluator.set_kernel("auto")
+    yield evaluator
+    evaluator.set_kernel("auto")
+    evaluator.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+@pytest.fixture(scope="module")
+def twin(built):
+    """the second ctx of answer (b): it holds the complemented columns and runs the spread pick"""
+    with Evaluator(0) as e:
+        yield e
+
+
+def fresh(ev, p, extra=0):
+    import torch
+    return torch.full((p + extra,), -7, dtype=torch.int32, device=dev_of(ev))
+
+
+def u_lo(j, c):
+    """the smallest draw whose k is j among c feasible nodes: ceil(j * 2^32 / c)"""
+    return -((-j << 32) // c)
+
+
+def u_hi(j, c):
+    """the largest draw whose k is j"""
+    return u_lo(j + 1, c) - 1
+
+
+# ---- 1. caller-made rows ------------------------------------------------------------------------------------------------------
+def tied_columns(n, rng):
+    """few distinct values, negatives among them: ties on (mem, cpu), ties on mem alone; both ends of int64 in either column"""
+    mem = rng.integers(-2, 3, n).astype(np.int64) << 30
+    cpu = rng.integers(-2, 2, n).astype(np.int64) * 500
+    at = rng.integers(0, n, 6)
+    mem[at[0]], mem[at[1]] = I64_MIN, I64_MAX
+    cpu[at[2]], cpu[at[3]] = I64_MIN, I64_MAX
+    mem[at[4]], cpu[at[4]] = I64_MIN, I64_MAX
+    mem[at[5]], cpu[at[5]] = I64_MIN, I64_MIN
+    return mem, cpu
+
+
+def chunk_edge_ranks(pos):
+    """the set-bit numbers of the first and the last set bit of every chunk of the row, descending: neighbours in this list sit on both sides
+    of a chunk boundary"""
+    chunk = pos // R.CHUNK_NODES
+    edge = np.ones(pos.size, bool)
+    edge[1:-1] = (chunk[1:-1] != chunk[:-2]) | (chunk[1:-1] != chunk[2:])
+    return np.nonzero(edge)[0][::-1]
+
+
+def rows_and_draws(n, d, rng):
+    """-> valid [PODS, W] uint64 (no bit at or beyond n), draws [PODS, d] uint32, edge {pod: the candidates its draws were built to name}"""
+    bits = np.zeros((PODS, n), bool)
+    for i in range(PODS):
+        bits[i] = rng.random(n) < (0.5, 0.02, 0.3, 0.9)[i % 4]
+    bits[0, [0, n - 1]] = True
+    bits[1] = False                           # c = 0
+    bits[2] = False
+    bits[2, n - 1] = True                     # c = 1: the row's last valid bit
+    bits[3] = True                            # c = n
+    bits[8] = True
+    draws = rng.integers(0, 1 << 32, size=(PODS, d), dtype=np.uint64)
+    draws[4] = draws[4, 0]                    # all d draws equal
+    draws[5] = 0
+    draws[6] = 0xFFFFFFFF
+    draws[7] = np.where(np.arange(d) % 2, 0, 0xFFFFFFFF)
+    edge = {}
+    for i in (0, 8):                          # a half-full row and a full one: draws on the first and the last set bit of every chunk
+        pos = np.nonzero(bits[i])[0]
+        ranks = chunk_edge_ranks(pos)
+        js = [int(ranks[(t + d) % ranks.size]) for t in range(d)]
+        draws[i] = [u_hi(j, pos.size) if t % 2 else u_lo(j, pos.size) for t, j in enumerate(js)]
+        edge[i] = pos[js]
+    valid = np.packbits(np.pad(bits, ((0, 0), (0, R.words(n) * 64 - n))), axis=1, bitorder="little").view(np.uint64)
+    return np.ascontiguousarray(valid), draws.astype(np.uint32), edge
+
+
+@pytest.mark.parametrize("n", ROW_NODES)
+def test_caller_made_rows_with_all_padding_set(ev, twin, n):
+    """ksched_pick_device over rows `pitch` words apart whose padding bits and padding words are all ones, p = 1, 5 and 37 pods, and
+    ksched_pick over the packed host rows: (a) and (b)"""
+    import torch
+    rng = np.random.default_rng([0xE5, n])
+    W = R.words(n)
+    mem, cpu = tied_columns(n, rng)
+    ev.set_nodes(cpu, mem)
+    twin.set_nodes(~cpu, ~mem)
+    assert ev.W == W and twin.W == W
+    dev = dev_of(ev)
+    for d in DS:
+        valid, draws, edge = rows_and_draws(n, d, rng)
+        want = pack_pick(valid, draws, n, mem, cpu)
+        assert np.array_equal(want, pack_pick_listed(valid, draws, n, mem, cpu))
+        assert want[1] == -1 and want[2] == n - 1 and (want[[0, 3, 8]] >= 0).all()
+        for i, cand in edge.items():  # the rows whose draws were built: the expected binding from their candidates directly
+            assert want[i] == min(cand.tolist(), key=lambda v: (int(mem[v]), int(cpu[v]), v)), (n, d, i)
+        if d == 1:
+            assert np.array_equal(want, uniform_pick(valid, draws[:, 0], n))
+        smp = torch.from_numpy(draws.view(np.int32)).to(dev)
+        for p in (1, 5, PODS):
+            for pitch in (W, W + 3):
+                what = f"n = {n}, d = {d}, p = {p}, pitch {pitch}"
+                host = R.padded(valid[:p], n, pitch, True)
+                m = torch.from_numpy(host.view(np.int64)).to(dev)[:, :W]
+                assert m.stride(0) == pitch
+                buf, buf2 = fresh(ev, p, GUARD), fresh(ev, p, GUARD)
+                ev.pick_device(m, PICK_PACK, buf[:p], samples=smp[:p])
+                twin.pick_device(m, PICK_SPREAD, buf2[:p], samples=smp[:p])
+                torch.cuda.synchronize()
+                got, got2 = buf.cpu().numpy(), buf2.cpu().numpy()
+                assert np.array_equal(got[:p], want[:p]), f"{what}: pods {np.nonzero(got[:p] != want[:p])[0][:5]} differ from the restatement"
+                assert (got[p:] == -7).all(), f"{what}: wrote past the bindings"
+                assert np.array_equal(got[:p], got2[:p]), f"{what}: differs from the spread pick on the complemented columns"
+        assert np.array_equal(ev.pick(R.padded(valid, n, W, True), PICK_PACK, samples=draws), want), f"n = {n}, d = {d}: ksched_pick"
+
+
+@pytest.mark.parametrize("n", [65, 8192, 8193, 16500])
+def test_draws_that_name_every_feasible_node_give_the_best_fit_pick(ev, n):
+    """(c): every pod has 1 <= c <= d feasible nodes and draws u_j = ceil(j * 2^32 / c), j < c, padded with u_0: the candidates are exactly
+    the feasible set, so the tightest of them is best fit's node.  Small positive columns (no residual overflows); the best-fit pick runs
+    without KSCHED_FIT, so it excludes no candidate and no pod."""
+    import torch
+    rng = np.random.default_rng([0xE5C, n])
+    W = R.words(n)
+    mem = rng.integers(1, 4, n).astype(np.int64) << 30
+    cpu = rng.integers(1, 4, n).astype(np.int64) * 500
+    ev.set_nodes(cpu, mem)
+    dev = dev_of(ev)
+    for d in DS:
+        bits = np.zeros((PODS, n), bool)
+        draws = np.zeros((PODS, d), np.uint32)
+        for i in range(PODS):
+            c = int(rng.integers(1, d + 1)) if i else d
+            nodes = rng.choice(n, c, replace=False)
+            if i % 3 == 0 and c >= 2 and n > R.CHUNK_NODES:
+                nodes[:2] = R.CHUNK_NODES - 1, R.CHUNK_NODES  # both sides of the first chunk boundary
+                nodes = np.unique(nodes)
+                c = nodes.size
+            bits[i, nodes] = True
+            draws[i, :c] = [u_lo(j, c) for j in range(c)]
+            draws[i, c:] = draws[i, 0]
+        valid = np.ascontiguousarray(np.packbits(np.pad(bits, ((0, 0), (0, W * 64 - n))), axis=1, bitorder="little").view(np.uint64))
+        cand = spread_candidates_listed(valid, draws, n)
+        for i in range(PODS):
+            assert set(cand[i].tolist()) == set(np.nonzero(bits[i])[0].tolist())  # the input condition: the candidates are the feasible set
+        want = pack_pick(valid, draws, n, mem, cpu)
+        assert (want >= 0).all()
+        m = torch.from_numpy(valid.view(np.int64)).to(dev)
+        smp = torch.from_numpy(draws.view(np.int32)).to(dev)
+        got, bf = fresh(ev, PODS), fresh(ev, PODS)
+        ev.pick_device(m, PICK_PACK, got, samples=smp)
+        ev.pick_device(m, PICK_BESTFIT, bf)
+        torch.cuda.synchronize()
+        assert np.array_equal(got.cpu().numpy(), want), f"n = {n}, d = {d}: the restatement"
+        assert np.array_equal(got.cpu().numpy(), bf.cpu().numpy()), f"n = {n}, d = {d}: the best-fit pick"
+
+
+# ---- 2. every entry point -----------------------------------------------------------------------------------------------------
+MID = (500, 2600, 8, 16, 55)
+CHUNKED = (300, 8200, 8, 16, 11)  # W = 129
+_CASES = {}
+
+
+def case(spec, d):
+    """the cluster, its predicate flags, the oracle's mask, [P, d] draws and the restatement's bindings: computed once, read-only"""
+    if (spec, d) not in _CASES:
+        P, N, n_keys, n_taints, seed = spec
+        c = synth.make_cluster(P, N, n_keys=n_keys, n_taints=n_taints, seed=seed)
+        flags = FIT | (SEL if n_keys else 0) | (TAINT if n_taints else 0)
+        feas = oracle_mask(c, flags)
+        draws = np.random.default_rng([seed, d]).integers(0, 1 << 32, size=(P, d), dtype=np.uint64).astype(np.uint32)
+        want = pack_pick_listed(feas, draws, N, c.avail_mem, c.avail_cpu)
+        for a in (feas, draws, want):
+            a.setflags(write=False)
+        _CASES[(spec, d)] = dict(c=c, flags=flags, feas=feas, draws=draws, want=want)
+    return _CASES[(spec, d)]
+
+
+@pytest.mark.parametrize("spec,kernel,d", [(MID, "auto", 3), (MID, "direct", 5), (MID, "fused", 64), (CHUNKED, "auto", 1), (CHUNKED, "auto", 5)],
+                         ids=lambda v: v if isinstance(v, str) else str(v) if isinstance(v, int) else f"{v[0]}x{v[1]}")
+def test_identical_bindings_from_every_entry_point(ev, twin, spec, kernel, d):
+    import torch
+    k = case(spec, d)
+    c, flags, feas, draws, want = k["c"], k["flags"] | PICK_PACK, k["feas"], k["draws"], k["want"]
+    if d >= 3:  # the input condition: the test cannot pass vacuously
+        first = uniform_pick(feas, draws[:, 0], c.N)
+        assert ((want >= 0) & (want != first)).mean() >= 0.3 and (want < 0).mean() >= 0.01
+    ev.set_kernel(kernel)
+    ev.set_nodes(**c.node_columns())
+    twin.set_nodes(~c.avail_cpu, ~c.avail_mem)
+    cpu, mem, sel, tol = pod_tensors(ev, c)
+    smp = to_dev(ev, draws, np.int32)
+    last_kernel = {"auto": ("fused", "direct"), "direct": ("direct",), "fused": ("fused",)}[kernel]
+    # ksched_eval_device_pitched: the mask pitched (rows on cache-line boundaries)
+    m = ev.alloc_mask(c.P, pitched=True)
+    b = fresh(ev, c.P)
+    ev.eval_device(cpu, mem, sel, tol, smp, flags, out_feasible=m, out_binding=b)
+    torch.cuda.synchronize()
+    assert ev.last_pick == "pack" and ev.last_kernel in last_kernel
+    assert np.array_equal(mask_np(m), feas), "pitched mask"
+    assert np.array_equal(b.cpu().numpy(), want), "ksched_eval_device_pitched"
+    # ksched_eval_device itself: the mask packed
+    m2 = torch.full((c.P, ev.W), 0x5A5A5A5A, dtype=torch.int64, device=dev_of(ev))
+    b2 = fresh(ev, c.P)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = ev._lib.ksched_eval_device(ev._h, c.P, ptr(cpu), ptr(mem), ptr(sel), ptr(tol), ptr(smp), d, flags, ptr(m2), None, ptr(b2),
+                                    C.c_void_p(torch.cuda.current_stream(ev.device).cuda_stream))
+    assert rc == _lib.OK
+    torch.cuda.synchronize()
+    assert np.array_equal(mask_np(m2), feas), "packed mask"
+    assert np.array_equal(b2.cpu().numpy(), want), "ksched_eval_device"
+    # without out_feasible: the mask kernel writes the ctx's scratch mask
+    b3 = fresh(ev, c.P)
+    ev.eval_device(cpu, mem, sel, tol, smp, flags, out_binding=b3)
+    torch.cuda.synchronize()
+    assert ev.last_pick == "pack"
+    assert np.array_equal(b3.cpu().numpy(), want), "ksched_eval_device, bindings only"
+    # host pointers: ksched_eval with and without the mask
+    pc = c.pod_columns()
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags)
+    assert np.array_equal(r.feasible, feas) and np.array_equal(r.binding, want), "ksched_eval"
+    r = ev.eval(pc["req_cpu_milli"], pc["req_mem_bytes"], pc["sel_val_ids"], pc["tolerations"], draws, flags, want_mask=False)
+    assert r.feasible is None and np.array_equal(r.binding, want), "ksched_eval, bindings only"
+    # ksched_eval_begin / ksched_eval_end: three row shards on this one ctx, one after the other
+    rc_c, rm_c = np.ascontiguousarray(pc["req_cpu_milli"]), np.ascontiguousarray(pc["req_mem_bytes"])
+    sel_c, tol_c = np.ascontiguousarray(pc["sel_val_ids"]), np.ascontiguousarray(pc["tolerations"])
+    smp_c = np.ascontiguousarray(draws)
+    feas_s, bind_s = np.zeros((c.P, ev.W), np.uint64), np.full(c.P, 777, np.int32)
+    lo_, hi_, cpr_ = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    for rank in range(3):
+        ev._lib.ksched_shard_bounds(c.P, 3, rank, C.byref(lo_), C.byref(hi_), C.byref(cpr_))
+        lo, hi, cpr = lo_.value, hi_.value, cpr_.value
+        dev_b, stream = C.c_void_p(), C.c_void_p()
+        rc = ev._lib.ksched_eval_begin(ev._h, hi - lo, C.c_void_p(rc_c.ctypes.data + 8 * lo), C.c_void_p(rm_c.ctypes.data + 8 * lo),
+                                       C.c_void_p(sel_c.ctypes.data + 4 * lo), c.P, C.c_void_p(tol_c.ctypes.data + 8 * lo),
+                                       C.c_void_p(smp_c.ctypes.data + 4 * d * lo), d, flags, C.c_void_p(feas_s.ctypes.data + 8 * ev.W * lo), None, cpr,
+                                       C.byref(dev_b), C.byref(stream))
+        assert rc == _lib.OK, ev._lib.ksched_last_error(ev._h)
+        part = np.full(cpr, 555, np.int32)
+        assert ev._lib.ksched_eval_end(ev._h, dev_b, cpr, part.ctypes.data_as(C.c_void_p)) == _lib.OK
+        bind_s[lo:hi] = part[:hi - lo]
+        assert (part[hi - lo:] == -1).all()
+    assert np.array_equal(feas_s, feas) and np.array_equal(bind_s, want), "ksched_eval_begin / ksched_eval_end"
+    # the pick alone from the oracle's mask: ksched_pick_device (no req_mem_bytes), ksched_pick, and answer (b)
+    om = to_dev(ev, feas, np.int64)
+    b4, b5 = fresh(ev, c.P), fresh(ev, c.P)
+    ev.pick_device(om, PICK_PACK, b4, samples=smp)
+    twin.pick_device(om, PICK_SPREAD, b5, samples=smp)
+    torch.cuda.synchronize()
+    assert np.array_equal(b4.cpu().numpy(), want), "ksched_pick_device"
+    assert np.array_equal(b5.cpu().numpy(), want), "the spread pick on the complemented columns"
+    assert np.array_equal(ev.pick(feas, PICK_PACK, samples=draws), want), "ksched_pick"
+    # ksched_pipe_submit: depth 2, five submits of different slices of the batch, every slot reused, no host wait in between
+    size, step, submits = c.P // 2, c.P // 8, 5
+    cols = [pod_tensors(ev, c, i * step, i * step + size) + (to_dev(ev, draws[i * step:i * step + size], np.int32),) for i in range(submits)]
+    torch.cuda.synchronize()
+    for mode in (0, 2):
+        ev.set_option(_lib.OPT_PIPE_MODE, mode)
+        pipe = ev.pipe(2)
+        try:
+            masks = [ev.alloc_mask(size, pitched=True) for _ in range(2)]
+            outs = [fresh(ev, size) for _ in range(2)]
+            copies = torch.full((submits, size), -7, dtype=torch.int32, device=dev_of(ev))
+            torch.cuda.synchronize()
+            for i in range(submits):
+                slot = i % 2
+                pipe.submit(slot, *cols[i], flags, masks[slot], outs[slot])
+                with torch.cuda.stream(pipe.slot_stream(slot)):
+                    copies[i].copy_(outs[slot])
+            for slot in range(2):
+                pipe.wait(slot, host=True)
+                pipe.wait_mask(slot, host=True)
+            torch.cuda.synchronize()
+            got = copies.cpu().numpy()
+            for i in range(submits):
+                assert np.array_equal(got[i], want[i * step:i * step + size]), f"pipe mode {mode}: bindings of submit {i} (slot {i % 2})"
+            for slot, i in ((1, 3), (0, 4)):
+                assert np.array_equal(mask_np(masks[slot]), feas[i * step:i * step + size]), f"pipe mode {mode}: final mask of slot {slot}"
+        finally:
+            pipe.close()
+            ev.set_option(_lib.OPT_PIPE_MODE, 0)
+
+
+def test_no_nodes_and_no_pods(ev):
+    import torch
+    z5 = np.zeros(5, np.int64)
+    ev.set_nodes(np.zeros(0, np.int64), np.zeros(0, np.int64))
+    r = ev.eval(z5, z5, samples=np.full((5, 3), 0xFFFFFFFF, np.uint32), flags=FIT | PICK_PACK)
+    assert r.feasible.shape == (5, 0) and (r.binding == -1).all()
+    b = fresh(ev, 5)
+    smp = to_dev(ev, np.zeros((5, 3), np.uint32), np.int32)
+    ev.eval_device(to_dev(ev, z5, np.int64), to_dev(ev, z5, np.int64), None, None, smp, FIT | PICK_PACK, out_binding=b)
+    torch.cuda.synchronize()
+    assert (b.cpu().numpy() == -1).all()
+    b.fill_(-7)
+    ev.pick_device(torch.empty((5, 0), dtype=torch.int64, device=dev_of(ev)), PICK_PACK, b, samples=smp)
+    torch.cuda.synchronize()
+    assert (b.cpu().numpy() == -1).all()
+    assert (ev.pick(np.zeros((5, 0), np.uint64), PICK_PACK, samples=np.zeros((5, 3), np.uint32)) == -1).all()
+    # no pods: KSCHED_OK, nothing written
+    ev.set_nodes(np.ones(10, np.int64), np.ones(10, np.int64))
+    lib, h = ev._lib, ev._h
+    guard = fresh(ev, 4)
+    gp = C.c_void_p(guard.data_ptr())
+    host_guard = np.full(4, -7, np.int32)
+    hp = host_guard.ctypes.data_as(C.c_void_p)
+    assert lib.ksched_eval_device(h, 0, None, None, None, None, None, 2, FIT | PICK_PACK, None, None, gp, None) == _lib.OK
+    assert lib.ksched_pick_device(h, 0, None, 1, None, None, 2, PICK_PACK, gp, None) == _lib.OK
+    assert lib.ksched_eval(h, 0, None, None, None, None, None, 2, FIT | PICK_PACK, None, None, hp) == _lib.OK
+    assert lib.ksched_pick(h, 0, None, None, None, 2, PICK_PACK, hp) == _lib.OK
+    torch.cuda.synchronize()
+    assert (guard.cpu().numpy() == -7).all() and (host_guard == -7).all()
+
+
+def test_argument_errors(ev):
+    import torch
+    ev.set_nodes(np.ones(10, np.int64), np.arange(10, dtype=np.int64))
+    lib, h = ev._lib, ev._h
+    z = np.zeros(4, np.int64)
+    smp = np.zeros((4, 64), np.uint32)
+    mask = np.zeros((4, 1), np.uint64)
+    out = np.full(4, -7, np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    d_z, d_smp, d_mask = to_dev(ev, z, np.int64), to_dev(ev, smp, np.int32), to_dev(ev, mask, np.int64)
+    d_out = fresh(ev, 4)
+    dp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    pipe = ev.pipe(1)
+    # (flags, samples given, attempts, binding given): exactly the spread pick's errors
+    bad = [(PICK_PACK | PICK_SAMPLED, True, 5, True), (PICK_PACK | PICK_BESTFIT, True, 5, True), (PICK_PACK | PICK_UNIFORM, True, 5, True),
+           (PICK_PACK | PICK_SPREAD, True, 5, True), (PICK_PACK, False, 5, True), (PICK_PACK, True, 0, True), (PICK_PACK, True, 65, True),
+           (PICK_PACK, True, 5, False)]
+    for flags, have_smp, attempts, have_out in bad:
+        what = (hex(flags), have_smp, attempts, have_out)
+        assert lib.ksched_eval(h, 4, p(z), p(z), None, None, p(smp) if have_smp else None, attempts, FIT | flags, None, None,
+                               p(out) if have_out else None) == _lib.E_INVAL, what
+        assert lib.ksched_eval_device(h, 4, dp(d_z), dp(d_z), None, None, dp(d_smp) if have_smp else None, attempts, FIT | flags, None, None,
+                                      dp(d_out) if have_out else None, None) == _lib.E_INVAL, what
+        assert lib.ksched_pick_device(h, 4, dp(d_mask), 1, None, dp(d_smp) if have_smp else None, attempts, flags,
+                                      dp(d_out) if have_out else None, None) == _lib.E_INVAL, what
+        assert lib.ksched_pick(h, 4, p(mask), None, p(smp) if have_smp else None, attempts, flags, p(out) if have_out else None) == _lib.E_INVAL, what
+        assert lib.ksched_pipe_submit(pipe._h, 0, 4, dp(d_z), dp(d_z), None, None, dp(d_smp) if have_smp else None, attempts, FIT | flags,
+                                      dp(d_mask), 1, dp(d_out) if have_out else None) == _lib.E_INVAL, what
+    pipe.close()
+    torch.cuda.synchronize()
+    assert (out == -7).all() and (d_out.cpu().numpy() == -7).all()
+    # the summaries take no pick flag
+    with pytest.raises(KschedError) as e:
+        ev.summarize(z, z, flags=FIT | PICK_PACK)
+    assert e.value.code == _lib.E_INVAL
+    # KSCHED_E_STATE where the uniform pick returns it: a ctx without a snapshot
+    with Evaluator(ev.device) as bare:
+        for flag in (PICK_UNIFORM, PICK_PACK):
+            assert bare._lib.ksched_eval(bare._h, 4, p(z), p(z), None, None, p(smp), 5, FIT | flag, None, None, p(out)) == _lib.E_STATE
+            assert bare._lib.ksched_pick(bare._h, 4, p(mask), None, p(smp), 5, flag, p(out)) == _lib.E_STATE
+            assert bare._lib.ksched_pick_device(bare._h, 4, dp(d_mask), 1, None, dp(d_smp), 5, flag, dp(d_out), None) == _lib.E_STATE
+    assert (out == -7).all()
+    # and a valid call still works on this ctx: every node fits a zero request; memory grows with the index, so the tightest of (0, 0, ...) is node 0
+    r = ev.eval(z, z, samples=smp[:, :5], flags=FIT | PICK_PACK)
+    assert (r.binding == 0).all()
+    full = np.full((4, 2), 0xFFFFFFFF, np.uint32)
+    assert (ev.eval(z, z, samples=full, flags=FIT | PICK_PACK).binding == 9).all()  # candidates 9 and 9
+    full[:, 1] = 0x80000000
+    assert (ev.eval(z, z, samples=full, flags=FIT | PICK_PACK).binding == 5).all()  # candidates 9 and 5: 5 has less memory
+
+
+# ---- 3. the live loop ---------------------------------------------------------------------------------------------------------
+def test_live_loop_of_evaluate_and_apply_while_fit_on_a_ctx_that_never_ran_best_fit(ev):
+    """Four rounds of [evaluate with PICK_PACK -> ksched_apply_bindings_device(APPLY_WHILE_FIT) -> ksched_read_nodes] on a fresh ctx that has
+    seen ksched_update_nodes and ksched_update_node_labels and never a best-fit request: every round's mask is the oracle's and its
+    bindings the restatement's on the columns as they stood before the round.  Round 2 is ksched_pick_device on a second stream, enqueued
+    right behind round 1's apply with no host wait in between: it sees the columns the apply leaves."""
+    import torch
+    P, N, d = 600, 130, 3
+    c = synth.make_cluster(P, N, n_keys=8, n_taints=16, seed=7)
+    flags = FIT | SEL | TAINT
+    rng = np.random.default_rng(0xE51)
+    with Evaluator(ev.device) as live:
+        live.set_nodes(**c.node_columns())
+        # a snapshot change of each kind before the first request: ten nodes' columns halved, two nodes' labels and taints swapped
+        cpu, mem = c.avail_cpu.copy(), c.avail_mem.copy()
+        idx = np.arange(10, dtype=np.uint32)
+        cpu[idx], mem[idx] = cpu[idx] // 2, mem[idx] // 2
+        live.update_nodes(idx, cpu[idx], mem[idx])
+        labels, taints = c.node_labels.copy(), c.node_taints.copy()
+        labels[:, [20, 21]], taints[[20, 21]] = labels[:, [21, 20]], taints[[21, 20]]
+        live.update_node_labels(np.array([20, 21], np.uint32), np.ascontiguousarray(labels[:, [20, 21]]), np.ascontiguousarray(taints[[20, 21]]))
+        c = dataclasses.replace(c, node_labels=labels, node_taints=taints)
+        cpu_t, mem_t, sel, tol = pod_tensors(live, c)
+        status = fresh(live, P)
+        second = torch.cuda.Stream(device=dev_of(live))
+        tables = [rng.integers(0, 1 << 32, size=(P, d), dtype=np.uint64).astype(np.uint32) for _ in range(4)]
+
+        def restate(rnd, cpu, mem):
+            feas = oracle_mask(c, flags, cpu, mem)
+            return feas, pack_pick_listed(feas, tables[rnd], N, mem, cpu)
+
+        try:
+            before = None  # the columns one round earlier
+            b = None
+            for rnd in range(4):
+                if rnd != 2:
+                    got_cpu, got_mem = live.read_nodes()
+                    assert np.array_equal(got_cpu, cpu) and np.array_equal(got_mem, mem), f"round {rnd}: the columns read back"
+                    feas, want = restate(rnd, cpu, mem)
+                    m = live.alloc_mask(P, pitched=True)
+                    b = fresh(live, P)
+                    live.eval_device(cpu_t, mem_t, sel, tol, to_dev(live, tables[rnd], np.int32), flags | PICK_PACK, out_feasible=m, out_binding=b)
+                    torch.cuda.synchronize()
+                    assert live.last_pick == "pack"
+                    assert np.array_equal(mask_np(m), feas), f"round {rnd}: the mask"
+                assert np.array_equal(b.cpu().numpy(), want), f"round {rnd}: the bindings"
+                if before is not None:  # the input condition: the columns of a round earlier give other bindings
+                    stale = int((pack_pick_listed(feas, tables[rnd], N, before[1], before[0]) != want).sum())
+                    print(f"round {rnd}: {int((want >= 0).sum())} of {P} pods bound; the columns of the round before change {stale} bindings")
+                    assert stale >= 5
+                new_cpu, new_mem, st = apply_while_fit_exact(cpu, mem, want, c.req_cpu, c.req_mem, None)
+                assert (st == _lib.APPLY_APPLIED).sum() >= 50
+                if rnd == 1:
+                    # round 2's mask and draws go to the device first; then the apply and, with no host wait, the pick on the second stream
+                    feas2, want2 = restate(2, new_cpu, new_mem)
+                    m2, smp2, b2 = to_dev(live, feas2, np.int64), to_dev(live, tables[2], np.int32), fresh(live, P)
+                    torch.cuda.synchronize()
+                live.apply_bindings_device(b, cpu_t, mem_t, None, _lib.APPLY_WHILE_FIT, status_out=status)
+                if rnd == 1:
+                    live.pick_device(m2, PICK_PACK, b2, samples=smp2, stream=second)
+                torch.cuda.synchronize()
+                assert np.array_equal(status.cpu().numpy(), st), f"round {rnd}: the statuses of the apply"
+                before = (cpu, mem)
+                cpu, mem = new_cpu, new_mem
+                if rnd == 1:
+                    b, feas, want = b2, feas2, want2
+                    got_cpu, got_mem = live.read_nodes()
+                    assert np.array_equal(got_cpu, cpu) and np.array_equal(got_mem, mem), "round 2: the columns read back"
+            got_cpu, got_mem = live.read_nodes()
+            assert np.array_equal(got_cpu, cpu) and np.array_equal(got_mem, mem), "the columns after the last apply"
+        finally:
+            torch.cuda.synchronize()
+            live.forget_stream(second)
