@@ -37,11 +37,9 @@ LAUNCH_TEST := tests/cpp/tile_launch_tests
 CHANGE_TEST := tests/cpp/snapshot_change_tests
 NODE_EVENTS_TEST := tests/cpp/node_events_tests
 SUMMARY_TEST := tests/cpp/summary_tests
-UNIFORM_PLAN_TEST := tests/cpp/uniform_plan_tests
+RANKED_PLAN_TEST := tests/cpp/ranked_plan_tests
 UNIFORM_PICK_TEST := tests/cpp/uniform_pick_tests
-SPREAD_PLAN_TEST := tests/cpp/spread_plan_tests
 SPREAD_PICK_TEST := tests/cpp/spread_pick_tests
-PACK_PLAN_TEST := tests/cpp/pack_plan_tests
 PACK_PICK_TEST := tests/cpp/pack_pick_tests
 BESTFIT_LAYOUT_TEST := tests/cpp/bestfit_layout_tests
 PIPE_PLAN_TEST := tests/cpp/pipe_plan_tests
@@ -76,7 +74,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
 # (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(PACK_PLAN_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -92,15 +90,9 @@ $(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/
 # host-only check of the pure parts of a snapshot change (csrc/snapshot_change.hpp: kept rows, layout decision, staging offsets, what is stale; no GPU, no HIP header): tests/test_snapshot_change_host.py runs it
 $(CHANGE_TEST): tests/cpp/snapshot_change_tests.cpp $(CSRC)/snapshot_change.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/snapshot_change_tests.cpp
-# host-only check of the plan of a KSCHED_PICK_UNIFORM request (csrc/eval_plan.hpp; no GPU, no HIP header): tests/test_uniform_plan_host.py runs it
-$(UNIFORM_PLAN_TEST): tests/cpp/uniform_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
-	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/uniform_plan_tests.cpp
-# host-only check of the plan of a KSCHED_PICK_SPREAD request (csrc/eval_plan.hpp; no GPU, no HIP header): tests/test_spread_plan_host.py runs it
-$(SPREAD_PLAN_TEST): tests/cpp/spread_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
-	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/spread_plan_tests.cpp
-# host-only check of the plan of a KSCHED_PICK_PACK request (csrc/eval_plan.hpp, csrc/pipe_plan.hpp; no GPU, no HIP header): tests/test_pack_plan_host.py runs it
-$(PACK_PLAN_TEST): tests/cpp/pack_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/pipe_plan.hpp $(CSRC)/bestfit_layout.hpp include/ksched.h
-	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/pack_plan_tests.cpp
+# host-only check of the plan of a ranked-pick request, KSCHED_PICK_UNIFORM / _SPREAD / _PACK (csrc/eval_plan.hpp, csrc/pipe_plan.hpp; no GPU, no HIP header): tests/test_ranked_plan_host.py runs it
+$(RANKED_PLAN_TEST): tests/cpp/ranked_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/pipe_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/ranked_plan_tests.cpp
 # host-only check of the numbers the best-fit structures and launches are sized by (csrc/bestfit_layout.hpp: order, row and hand-over layouts, counter rotation, debug bits; no GPU, no HIP header): tests/test_bestfit_layout_host.py runs it
 $(BESTFIT_LAYOUT_TEST): tests/cpp/bestfit_layout_tests.cpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/bestfit_layout_tests.cpp
@@ -182,4 +174,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(UNIFORM_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PLAN_TEST) $(SPREAD_PICK_TEST) $(PACK_PLAN_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB)

@@ -154,6 +154,14 @@ extern "C" {
  * pick has read it.  The best-fit order is neither needed nor rebuilt: after a snapshot change a pack request costs what it cost before.
  * ksched_last_pick: "pack". */
 #define KSCHED_PICK_PACK 0x100u
+/* The pick flags as sets, derived from the flags above (no new value; a flag list is spelled here and nowhere else):
+ *   KSCHED_PICK_ANY    : every pick flag -- a call carries at most one of them;
+ *   KSCHED_PICK_DRAWS  : the picks that read `samples` (sampled: node indices; the ranked picks: 32-bit draws);
+ *   KSCHED_PICK_RANKED : the ranked picks -- uniform, spread and pack rank a 32-bit draw among the pod's feasible nodes, so they always
+ *                        read the mask, behind the mask kernel. */
+#define KSCHED_PICK_RANKED (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)
+#define KSCHED_PICK_DRAWS (KSCHED_PICK_SAMPLED | KSCHED_PICK_RANKED)
+#define KSCHED_PICK_ANY (KSCHED_PICK_BESTFIT | KSCHED_PICK_DRAWS)
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0

@@ -38,6 +38,9 @@ WANT_FIT_MASK = 0x20
 PICK_UNIFORM = 0x40  # extension E3: uniformly among the pod's feasible nodes, one 32-bit draw per pod (samples[:, 0])
 PICK_SPREAD = 0x80  # extension E4: the least loaded (available memory, then cpu) of samples.shape[1] uniformly drawn feasible nodes
 PICK_PACK = 0x100  # extension E5: the tightest (smallest available memory, then cpu) of samples.shape[1] uniformly drawn feasible nodes
+PICK_RANKED = PICK_UNIFORM | PICK_SPREAD | PICK_PACK  # the picks that rank 32-bit draws among a pod's feasible nodes: they always read the mask
+PICK_DRAWS = PICK_SAMPLED | PICK_RANKED  # the picks that read `samples`
+PICK_ANY = PICK_BESTFIT | PICK_DRAWS  # every pick flag: at most one per call
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib as L
 
-DRAWS = L.PICK_SAMPLED | L.PICK_UNIFORM | L.PICK_SPREAD | L.PICK_PACK  # the picks that read `samples`
+DRAWS = L.PICK_DRAWS  # the picks that read `samples`
 
 # element kinds of the C ABI: the torch dtypes that may stand for them (int64 stands in for uint64, int32 for uint32, bool for uint8)
 KINDS = {"i64": ("int64",), "u64": ("int64", "uint64"), "i32": ("int32",), "u32": ("int32", "uint32"), "u8": ("uint8", "bool")}

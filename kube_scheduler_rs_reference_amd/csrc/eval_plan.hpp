@@ -16,10 +16,10 @@ namespace ksched {
 
 // Does the pick read the feasibility mask?  By default it does not (sampled: the drawn candidates are tested from the columns;
 // best fit: bitmaps kept in best-fit order); it does with KSCHED_OPT_PICK_FROM_MASK, and a best-fit pick does when the snapshot
-// has no best-fit rows (`bf_rows`: they exist, or will once ensure_bestfit has run).  The uniform pick (KSCHED_PICK_UNIFORM) always does:
-// it counts and ranks the row's set bits; so do the spread pick (KSCHED_PICK_SPREAD) and the pack pick (KSCHED_PICK_PACK), once per draw.
+// has no best-fit rows (`bf_rows`: they exist, or will once ensure_bestfit has run).  The ranked picks (KSCHED_PICK_RANKED) always do:
+// the uniform pick counts and ranks the row's set bits; the spread and the pack pick do so once per draw.
 inline bool pick_reads_mask(uint32_t flags, bool opt_pick_from_mask, bool bf_rows) {
-    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)) return true;
+    if (flags & KSCHED_PICK_RANKED) return true;
     return (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT)) && (opt_pick_from_mask || ((flags & KSCHED_PICK_BESTFIT) && !bf_rows));
 }
 
@@ -49,9 +49,7 @@ struct EvalFacts {
 enum class MaskKernel { kNone, kFused, kDirect };
 enum class SampledPick { kNone, kOwnLaunch, kRidesFill, kRidesTiles, kFromMask };
 enum class BestfitPick { kNone, kRowsOneStage, kRowsTwoStages, kRowsTwoStagesListed, kFromMask };
-enum class UniformPick { kNone, kFromMask };  // k_pick_uniform behind the mask kernel: the only form
-enum class SpreadPick { kNone, kFromMask };   // k_pick_spread behind the mask kernel: the only form
-enum class PackPick { kNone, kFromMask };     // k_pick_pack behind the mask kernel: the only form
+enum class RankedPick { kNone, kUniform, kSpread, kPack };  // k_pick_uniform / k_pick_spread / k_pick_pack behind the mask kernel: the only form
 enum class PlanError { kNone, kFusedNotApplicable, kTilePickNotApplicable, kListKeysTooManyNodes };
 
 struct EvalPlan {
@@ -61,16 +59,14 @@ struct EvalPlan {
     bool scratch_mask = false;  // the mask kernel writes the feasible mask into the ctx's scratch one (the caller gave none)
     SampledPick sampled = SampledPick::kNone;
     BestfitPick bestfit = BestfitPick::kNone;
-    UniformPick uniform = UniformPick::kNone;
-    SpreadPick spread = SpreadPick::kNone;
-    PackPick pack = PackPick::kNone;
+    RankedPick ranked = RankedPick::kNone;
     const char *last_kernel = nullptr;  // ksched_last_kernel after the launch; nullptr = no mask kernel runs, it stays what it was
     const char *last_pick = "none";     // ksched_last_pick
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
     // a pick launch follows the mask kernel and reads what it wrote
-    bool pick_from_mask() const { return sampled == SampledPick::kFromMask || bestfit == BestfitPick::kFromMask || uniform == UniformPick::kFromMask || spread == SpreadPick::kFromMask || pack == PackPick::kFromMask; }
+    bool pick_from_mask() const { return sampled == SampledPick::kFromMask || bestfit == BestfitPick::kFromMask || ranked != RankedPick::kNone; }
 };
 
 inline EvalPlan plan_unsupported(PlanError why) {
@@ -78,6 +74,22 @@ inline EvalPlan plan_unsupported(PlanError why) {
     e.error = KSCHED_E_UNSUPPORTED;
     e.why = why;
     return e;
+}
+
+// The ranked picks, member by member: the flag, the plan's name for it and ksched_last_pick.  (A call carries one pick flag; the
+// first row whose flag is set answers.)
+struct RankedMember {
+    uint32_t flag;
+    RankedPick pick;
+    const char *name;
+};
+constexpr RankedMember kRankedMembers[] = {{KSCHED_PICK_SPREAD, RankedPick::kSpread, "spread"},
+                                           {KSCHED_PICK_PACK, RankedPick::kPack, "pack"},
+                                           {KSCHED_PICK_UNIFORM, RankedPick::kUniform, "uniform"}};
+inline const RankedMember *ranked_member(uint32_t flags) {
+    for (const RankedMember &m : kRankedMembers)
+        if (flags & m.flag) return &m;
+    return nullptr;
 }
 
 inline EvalPlan plan_eval(const EvalFacts &f) {
@@ -89,27 +101,17 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     const bool want_mask = f.have_feas || f.have_fit;
     const bool can_fused = f.fused_applicable;
     const int kern = choose_kernel(f.opt_kernel, can_fused);
-    // The uniform pick counts and ranks the set bits of the pod's whole row: the mask kernel always runs (into the ctx's scratch mask when
-    // the caller gave none), the pick is its own launch behind it, and neither KSCHED_OPT_PICK_FROM_MASK nor KSCHED_OPT_FUSED_PICK applies.
-    // The spread pick (KSCHED_PICK_SPREAD) does the same once per draw and compares the candidates: the same plan, its own kernel.
-    // The pack pick (KSCHED_PICK_PACK) is the spread pick with the comparison turned round: the same plan again.
-    if (flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)) {
+    // The ranked picks (KSCHED_PICK_RANKED) count and rank the set bits of the pod's whole row -- the uniform pick once, the spread and the
+    // pack pick once per draw, comparing the candidates: the mask kernel always runs (into the ctx's scratch mask when the caller gave
+    // none), the pick is its own launch behind it, and neither KSCHED_OPT_PICK_FROM_MASK nor KSCHED_OPT_FUSED_PICK applies.  One plan for
+    // the family; a member has its own kernel and its own name.
+    if (const RankedMember *m = ranked_member(flags)) {
         if (kern == KSCHED_KERNEL_FUSED && !can_fused) return plan_unsupported(PlanError::kFusedNotApplicable);
         plan.scratch_mask = !f.have_feas;
         plan.mask = kern == KSCHED_KERNEL_FUSED ? MaskKernel::kFused : MaskKernel::kDirect;
         plan.last_kernel = kern == KSCHED_KERNEL_FUSED ? "fused" : "direct";
-        if (flags & KSCHED_PICK_SPREAD) {
-            plan.spread = SpreadPick::kFromMask;
-            plan.last_pick = "spread";
-            return plan;
-        }
-        if (flags & KSCHED_PICK_PACK) {
-            plan.pack = PackPick::kFromMask;
-            plan.last_pick = "pack";
-            return plan;
-        }
-        plan.uniform = UniformPick::kFromMask;
-        plan.last_pick = "uniform";
+        plan.ranked = m->pick;
+        plan.last_pick = m->name;
         return plan;
     }
     // The sampled pick tests only the drawn candidates, from the node records: it does not need the mask.  When a mask is

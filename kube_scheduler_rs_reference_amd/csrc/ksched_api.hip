@@ -1034,15 +1034,18 @@ int launch_pick(ksched_ctx *c, const EvalRequest &r, const uint64_t *feas) {
         const BestfitIndex &bi = c->bestfit;  // (the order and its inverse: no rows)
         hipLaunchKernelGGL(k_pick_bestfit, dim3((r.p + 3) / 4), dim3(256), 0, s, feas, bi.bf_order.ptr, bi.bf_rank.ptr, bi.bf_mem.ptr, r.pmem,
                            r.out_binding, r.p, c->n, c->W, r.pitch, r.fit() ? 1u : 0u);
-    } else if (r.flags & KSCHED_PICK_UNIFORM) {  // (every caller has c->n > 0 here: an empty snapshot's bindings are a memset)
-        hipLaunchKernelGGL(k_pick_uniform, dim3((r.p + kUniformWaves - 1) / kUniformWaves), dim3(64 * kUniformWaves), 0, s, feas, r.samples,
-                           r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
-    } else if (r.flags & KSCHED_PICK_SPREAD) {  // (c->n > 0 likewise; the stream_enter above puts the columns it reads behind the latest snapshot change)
-        hipLaunchKernelGGL(k_pick_spread, dim3((r.p + kSpreadWaves - 1) / kSpreadWaves), dim3(64 * kSpreadWaves), 0, s, feas, r.samples,
-                           (const int64_t *)c->nmem.ptr, (const int64_t *)c->ncpu.ptr, r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
-    } else if (r.flags & KSCHED_PICK_PACK) {  // (c->n > 0 and the columns behind the latest snapshot change, as for the spread pick; no best-fit order involved)
-        hipLaunchKernelGGL(k_pick_pack, dim3((r.p + kPackWaves - 1) / kPackWaves), dim3(64 * kPackWaves), 0, s, feas, r.samples,
-                           (const int64_t *)c->nmem.ptr, (const int64_t *)c->ncpu.ptr, r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
+    } else if (const RankedMember *m = ranked_member(r.flags)) {  // (every caller has c->n > 0 here: an empty snapshot's bindings are a memset)
+        if (m->pick == RankedPick::kUniform) {
+            hipLaunchKernelGGL(k_pick_uniform, dim3((r.p + kUniformWaves - 1) / kUniformWaves), dim3(64 * kUniformWaves), 0, s, feas, r.samples,
+                               r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
+        } else {
+            // the members that read the available columns, one launch shape (the stream_enter above puts the columns behind the latest
+            // snapshot change; no best-fit order involved).  Two kernels on purpose: kernels_pick_pack.hpp.
+            static_assert(kSpreadWaves == kPackWaves, "k_pick_spread and k_pick_pack are launched with one geometry");
+            const auto kernel = m->pick == RankedPick::kSpread ? k_pick_spread : k_pick_pack;
+            hipLaunchKernelGGL(kernel, dim3((r.p + kSpreadWaves - 1) / kSpreadWaves), dim3(64 * kSpreadWaves), 0, s, feas, r.samples,
+                               (const int64_t *)c->nmem.ptr, (const int64_t *)c->ncpu.ptr, r.out_binding, r.p, c->n, c->W, r.pitch, r.attempts);
+        }
     }
     HIPCHK(c, hipGetLastError());
     return KSCHED_OK;
@@ -1225,7 +1228,7 @@ int fail_plan(ksched_ctx *c, const EvalPlan &plan) {
 }
 
 int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
-    const bool pick_s = r.flags & KSCHED_PICK_SAMPLED, pick_b = r.flags & KSCHED_PICK_BESTFIT;
+    const bool pick_b = r.flags & KSCHED_PICK_BESTFIT;
     if (r.p == 0) return KSCHED_OK;
     if (pick_b && c->n > 0)
         if (int rcb = ensure_bestfit(c)) return rcb;  // lazily (re)built after a snapshot change, on the change stream
@@ -1233,7 +1236,7 @@ int eval_on_device(ksched_ctx *c, const EvalRequest &r) {
     if (c->n == 0) {
         // no nodes: empty mask rows, no binding possible (reference: choose() on an empty store
         // yields None on every attempt, src/main.rs:56,70)
-        if ((pick_s || pick_b || (r.flags & (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK))) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
+        if ((r.flags & KSCHED_PICK_ANY) && r.out_binding) HIPCHK(c, hipMemsetAsync(r.out_binding, 0xFF, (size_t)r.p * sizeof(int32_t), r.stream));
         return KSCHED_OK;
     }
     fault_point(c);
@@ -1287,39 +1290,37 @@ int stage_batch(ksched_ctx *c, uint32_t p, const HostBatch &h, hipStream_t s) {
     return KSCHED_OK;
 }
 
-// the pick flags: at most one per call
-constexpr uint32_t kPickFlags = KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK;
-// the picks that read `samples`: node indices (sampled), 32-bit draws (uniform: entry 0 of every row; spread and pack: all `attempts` of them)
-constexpr uint32_t kDrawPicks = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK;
+// the pick flags (KSCHED_PICK_ANY): at most one per call.  KSCHED_PICK_DRAWS are the picks that read `samples`: node indices (sampled),
+// 32-bit draws (uniform: entry 0 of every row; spread and pack: all `attempts` of them)
 inline bool at_most_one_pick(uint32_t flags) {
-    const uint32_t pick = flags & kPickFlags;
+    const uint32_t pick = flags & KSCHED_PICK_ANY;
     return (pick & (pick - 1u)) == 0;
 }
 
 // the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed)
 int check_eval_args(const EvalRequest &r) {
     const uint32_t flags = r.flags;
-    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | kPickFlags | KSCHED_WANT_FIT_MASK;
+    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK;
     if (flags & ~known) return KSCHED_E_INVAL;
     if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
-    if (flags & kDrawPicks) {
+    if (flags & KSCHED_PICK_DRAWS) {
         if (!r.out_binding || r.attempts == 0 || r.attempts > KSCHED_MAX_ATTEMPTS) return KSCHED_E_INVAL;
         if (r.p > 0 && !r.samples) return KSCHED_E_INVAL;
     }
     if ((flags & KSCHED_PICK_BESTFIT) && !r.out_binding) return KSCHED_E_INVAL;
     if ((flags & KSCHED_WANT_FIT_MASK) && !r.out_fit) return KSCHED_E_INVAL;
     if (!(flags & KSCHED_WANT_FIT_MASK) && r.out_fit) return KSCHED_E_INVAL;
-    if (!(flags & kPickFlags) && !r.out_feas && !r.out_fit) return KSCHED_E_INVAL;
+    if (!(flags & KSCHED_PICK_ANY) && !r.out_feas && !r.out_fit) return KSCHED_E_INVAL;
     return KSCHED_OK;
 }
 
 // the arguments of a pick from the caller's masks (ksched_pick, ksched_pick_device) over a snapshot of n nodes
 int check_pick_args(uint32_t n, uint32_t p, const uint64_t *feasible, const int64_t *req_mem_bytes, const uint32_t *samples, uint32_t attempts,
                     uint32_t flags, const int32_t *out_binding) {
-    if (!(flags & kPickFlags) || !at_most_one_pick(flags) || (flags & ~(kPickFlags | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
+    if (!(flags & KSCHED_PICK_ANY) || !at_most_one_pick(flags) || (flags & ~(KSCHED_PICK_ANY | KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT))) return KSCHED_E_INVAL;
     if (!out_binding || (p > 0 && n > 0 && !feasible)) return KSCHED_E_INVAL;
-    if ((flags & kDrawPicks) && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
+    if ((flags & KSCHED_PICK_DRAWS) && (attempts == 0 || attempts > KSCHED_MAX_ATTEMPTS || (p > 0 && !samples))) return KSCHED_E_INVAL;
     if ((flags & KSCHED_PICK_BESTFIT) && (flags & KSCHED_FIT) && p > 0 && !req_mem_bytes) return KSCHED_E_INVAL;
     return KSCHED_OK;
 }
@@ -1819,7 +1820,7 @@ int ksched_pipe_submit(ksched_pipe *q, uint32_t slot, uint32_t p, const int64_t 
     ksched_ctx *c = q->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
-    const uint32_t pick = flags & kPickFlags;
+    const uint32_t pick = flags & KSCHED_PICK_ANY;
     if (!pick || (flags & KSCHED_WANT_FIT_MASK) || !mask) return KSCHED_E_INVAL;
     EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, mask, nullptr, binding, mask_pitch_words, nullptr};  // (the stream: the plan's)
     int rc = check_eval_args(r);
@@ -1899,7 +1900,7 @@ int ksched_pick(ksched_ctx *c, uint32_t p, const uint64_t *feasible, const int64
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
     // (pick_s: the pick reads draws -- sampled, uniform, spread or pack)
-    const bool pick_s = flags & kDrawPicks, pick_b = flags & KSCHED_PICK_BESTFIT;
+    const bool pick_s = flags & KSCHED_PICK_DRAWS, pick_b = flags & KSCHED_PICK_BESTFIT;
     if (int rc = check_pick_args(c->n, p, feasible, req_mem_bytes, samples, attempts, flags, out_binding)) return rc;
     if (p == 0) return KSCHED_OK;
     if (c->n == 0) {  // choose() on an empty store yields None on every attempt (src/main.rs:56,70)
@@ -1941,13 +1942,13 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
     uint64_t *const out_feas = h.out_feas, *const out_fit = h.out_fit;
     const size_t W = c->W;
     const size_t pitch = ksched_mask_pitch(c->n);
-    const bool pick = flags & kPickFlags;
+    const bool pick = flags & KSCHED_PICK_ANY;
     HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled, uniform, spread or pack pick
     b.pcpu = h.pcpu;
     b.pmem = h.pmem;
     if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride;
     if (h.taint_flag()) b.ptol = h.ptol;
-    if (flags & kDrawPicks) b.samples = h.samples, b.attempts = h.attempts;
+    if (flags & KSCHED_PICK_DRAWS) b.samples = h.samples, b.attempts = h.attempts;
     int32_t *d_bind = nullptr;
     if (pick) {
         const size_t cap = std::max<size_t>(capacity, p);
@@ -2021,7 +2022,7 @@ int ksched_eval_begin(ksched_ctx *c, uint32_t p, const int64_t *pcpu, const int6
     if (psel && sel_stride < p) return KSCHED_E_INVAL;
     int32_t sentinel = 0;  // (the bindings stay on the device: check_eval_args only wants to know that a pick has somewhere to go)
     const EvalRequest h{p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit,
-                        (flags & kPickFlags) ? &sentinel : nullptr, 0, c->stream};
+                        (flags & KSCHED_PICK_ANY) ? &sentinel : nullptr, 0, c->stream};
     int rc = check_eval_args(h);
     if (rc) return rc;
     DeviceGuard g(c->device);

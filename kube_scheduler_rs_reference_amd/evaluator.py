@@ -22,7 +22,7 @@ def mask_words(n_nodes: int) -> int:
     return (int(n_nodes) + 63) // 64
 
 
-_PICKS = L.PICK_SAMPLED | L.PICK_BESTFIT | L.PICK_UNIFORM | L.PICK_SPREAD | L.PICK_PACK  # at most one per call
+_PICKS = L.PICK_ANY  # at most one per call
 _ptr = M.host_ptr
 
 

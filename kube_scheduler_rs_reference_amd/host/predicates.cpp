@@ -179,9 +179,6 @@ std::vector<corev1::Pod> split_wide_pod(const corev1::Pod &pod) {
     return out;
 }
 
-// the picks that read `samples`: [p][attempts] node indices (sampled), 32-bit draws of which entry 0 is read (uniform) or all are (spread, pack)
-constexpr uint32_t kPicksWithDraws = KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK;
-
 // A pod whose selector has more keys than one call takes (row `i` of `out`): one device evaluation per key group against that group's
 // label columns, the groups' feasible masks ANDed (does_node_selector_match is a conjunction over the keys, src/predicates.rs:48-53;
 // the fit mask is the same in every group), and the pick made by the device from the combined mask (ksched_pick).  On the first
@@ -207,7 +204,7 @@ void eval_wide_pod(Snapshot &snap, const corev1::Pod &pod, size_t i, uint32_t pi
     }
     if (pick && samples_ready) (*samples_ready)();
     if (pick)
-        dev.check(ksched_pick(dev.handle(), 1, feas.data(), &req_mem, (pick & kPicksWithDraws) ? samples->data() + i * attempts : nullptr, attempts,
+        dev.check(ksched_pick(dev.handle(), 1, feas.data(), &req_mem, (pick & KSCHED_PICK_DRAWS) ? samples->data() + i * attempts : nullptr, attempts,
                               pick | (out.flags & (KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT)), out.binding.data() + i),
                   "ksched_pick");
 }
@@ -231,7 +228,7 @@ void eval_range(Snapshot &snap, const std::vector<const corev1::Pod *> &pods, si
     if (ShardedContext *sh = snap.sharded()) {
         // several devices (or KSCHED_SHARDED): the range's rows are cut over them, each device evaluates its rows against its
         // replica of the snapshot, the bindings meet in one RCCL all-gather (sharded.hpp); masks land in this range's rows directly
-        sh->eval(pc, (pick & kPicksWithDraws) ? samples->data() + lo * attempts : nullptr, attempts, flags, out.W,
+        sh->eval(pc, (pick & KSCHED_PICK_DRAWS) ? samples->data() + lo * attempts : nullptr, attempts, flags, out.W,
                  want_masks ? out.feasible.data() + lo * out.W : nullptr, want_masks ? out.fit.data() + lo * out.W : nullptr,
                  pick ? out.binding.data() + lo : nullptr);
         return;
@@ -239,7 +236,7 @@ void eval_range(Snapshot &snap, const std::vector<const corev1::Pod *> &pods, si
     DeviceEvaluator &dev = snap.device();
     dev.check(ksched_eval(dev.handle(), pc.p, pc.req_cpu_milli.data(), pc.req_mem_bytes.data(),
                           pc.n_keys ? pc.sel_val_ids.data() : nullptr, (out.flags & KSCHED_TAINT) ? pc.tolerations.data() : nullptr,
-                          (pick & kPicksWithDraws) ? samples->data() + lo * attempts : nullptr, attempts,
+                          (pick & KSCHED_PICK_DRAWS) ? samples->data() + lo * attempts : nullptr, attempts,
                           flags, want_masks ? out.feasible.data() + lo * out.W : nullptr,
                           want_masks ? out.fit.data() + lo * out.W : nullptr, pick ? out.binding.data() + lo : nullptr),
               "ksched_eval");
@@ -258,7 +255,7 @@ BatchValidity check_node_validity_batch(const std::vector<const corev1::Pod *> &
     out.n = snap.n();
     out.W = snap.mask_words();
     out.flags = KSCHED_FIT | KSCHED_SEL | ((taints && snap.has_taints()) ? KSCHED_TAINT : 0u);
-    const uint32_t pick = pick_flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK);
+    const uint32_t pick = pick_flags & KSCHED_PICK_ANY;
     if (!want_masks && !pick) throw EncodeError("check_node_validity_batch: nothing asked for (no masks, no pick)");
     if (want_masks) {
         out.feasible.assign((size_t)out.p * out.W, 0ull);
@@ -266,7 +263,7 @@ BatchValidity check_node_validity_batch(const std::vector<const corev1::Pod *> &
     }
     if (pick) out.binding.assign(out.p, -1);
     if (out.p == 0 || out.n == 0) return out;  // no pods, or an empty store: nothing is feasible
-    if ((pick & kPicksWithDraws) && (!samples || samples->size() != (size_t)out.p * attempts))
+    if ((pick & KSCHED_PICK_DRAWS) && (!samples || samples->size() != (size_t)out.p * attempts))
         throw EncodeError("check_node_validity_batch: samples must hold p * attempts indices");
     // (key_ranges: consecutive pod ranges within the device's budget of label columns per call; a pod with more keys than that is
     // evaluated group by group and ANDed -- no input the reference schedules is refused)

@@ -58,30 +58,48 @@ std::optional<corev1::Node> select_node_for_pod(const corev1::Pod &pod, Context 
     return node;  // :70
 }
 
+namespace {
+
+// Which ranked pick (KSCHED_PICK_RANKED) the Context asks for: the flag, the draws per pod and the phase clock's label; flag 0 = none, the
+// sampled pick of the reference.  `refusal` is set for a Context that no batch is evaluated with.
+struct RankedChoice {
+    uint32_t flag = 0, d = 0;
+    const char *label = nullptr, *refusal = nullptr;
+};
+
+RankedChoice ranked_choice(const Context &ctx) {
+    RankedChoice c;
+    if (ctx.pick_spread && ctx.pick_uniform) c.refusal = "select_nodes_for_pods: Context::pick_spread and Context::pick_uniform are both set (one pick per batch)";
+    else if (ctx.pick_spread > KSCHED_MAX_ATTEMPTS) c.refusal = "select_nodes_for_pods: Context::pick_spread is above KSCHED_MAX_ATTEMPTS";
+    else if (ctx.pick_pack && (ctx.pick_uniform || ctx.pick_spread)) c.refusal = "select_nodes_for_pods: Context::pick_pack is set together with Context::pick_uniform or Context::pick_spread (one pick per batch)";
+    else if (ctx.pick_pack > KSCHED_MAX_ATTEMPTS) c.refusal = "select_nodes_for_pods: Context::pick_pack is above KSCHED_MAX_ATTEMPTS";
+    // extension E5: d = pick_pack draws per pod; the device keeps the tightest of the d candidates (KSCHED_PICK_PACK).
+    if (ctx.pick_pack) c.flag = KSCHED_PICK_PACK, c.d = ctx.pick_pack, c.label = "select (pack)";
+    // extension E4: d = pick_spread draws per pod; the device keeps the least loaded of the d candidates (KSCHED_PICK_SPREAD).
+    else if (ctx.pick_spread) c.flag = KSCHED_PICK_SPREAD, c.d = ctx.pick_spread, c.label = "select (spread)";
+    // extension E3: one draw per pod; the device ranks it among the pod's feasible nodes (KSCHED_PICK_UNIFORM).
+    else if (ctx.pick_uniform) c.flag = KSCHED_PICK_UNIFORM, c.d = 1u, c.label = "select (uniform)";
+    return c;
+}
+
+}  // namespace
+
 BatchSelection select_nodes_for_pods(const std::vector<const corev1::Pod *> &pods, Context &ctx, NodeChooser &chooser, bool want_rejected) {
-    // (refused before anything is evaluated or drawn)
-    if (ctx.pick_spread && ctx.pick_uniform) throw EncodeError("select_nodes_for_pods: Context::pick_spread and Context::pick_uniform are both set (one pick per batch)");
-    if (ctx.pick_spread > KSCHED_MAX_ATTEMPTS) throw EncodeError("select_nodes_for_pods: Context::pick_spread is above KSCHED_MAX_ATTEMPTS");
-    if (ctx.pick_pack && (ctx.pick_uniform || ctx.pick_spread)) throw EncodeError("select_nodes_for_pods: Context::pick_pack is set together with Context::pick_uniform or Context::pick_spread (one pick per batch)");
-    if (ctx.pick_pack > KSCHED_MAX_ATTEMPTS) throw EncodeError("select_nodes_for_pods: Context::pick_pack is above KSCHED_MAX_ATTEMPTS");
+    const RankedChoice ranked = ranked_choice(ctx);
+    if (ranked.refusal) throw EncodeError(ranked.refusal);  // (refused before anything is evaluated or drawn)
     if (!ctx.snapshot) ctx.refresh_snapshot();
     Snapshot &snap = *ctx.snapshot;
     const uint32_t p = (uint32_t)pods.size(), n = snap.n();
     BatchSelection out;
     out.node_store_index.assign(p, -1);
-    if (ctx.pick_uniform || ctx.pick_spread || ctx.pick_pack) {
-        // extension E3: one 32-bit draw per pod, in pod order; the device ranks it among the pod's feasible nodes (KSCHED_PICK_UNIFORM).
-        // extension E4: d = pick_spread draws per pod, in pod order and draw-major within a pod; the device ranks each and keeps the least
-        // loaded of the d candidates (KSCHED_PICK_SPREAD).
-        // extension E5: d = pick_pack draws per pod, taken the same way; the device keeps the tightest of the d candidates (KSCHED_PICK_PACK).
+    if (ranked.flag) {
+        // d 32-bit draws per pod, in pod order and draw-major within a pod; the device ranks each among the pod's feasible nodes.
         // No draw is ever rejected: `rejected` stays empty.  The masks ride along when the caller asked for the rejected draws' reasons.
         if (n == 0 || p == 0 || ctx.node_store.size() == 0) return out;
-        const uint32_t d = ctx.pick_pack ? ctx.pick_pack : ctx.pick_spread ? ctx.pick_spread : 1u;
-        const uint32_t pick_flag = ctx.pick_pack ? KSCHED_PICK_PACK : ctx.pick_spread ? KSCHED_PICK_SPREAD : KSCHED_PICK_UNIFORM;
-        PhaseClock clock(ctx.pick_pack ? "select (pack)" : ctx.pick_spread ? "select (spread)" : "select (uniform)");
-        std::vector<uint32_t> draws((size_t)p * d);
+        PhaseClock clock(ranked.label);
+        std::vector<uint32_t> draws((size_t)p * ranked.d);
         for (uint32_t &u : draws) u = (uint32_t)chooser.choose(size_t(1) << 32).value_or(0);
-        out.validity = predicates::check_node_validity_batch(pods, ctx, /*taints=*/false, pick_flag, &draws, d,
+        out.validity = predicates::check_node_validity_batch(pods, ctx, /*taints=*/false, ranked.flag, &draws, ranked.d,
                                                              /*want_masks=*/want_rejected);
         out.samples = std::move(draws);
         clock.lap("draws + check_node_validity_batch");
@@ -159,7 +177,7 @@ std::vector<std::vector<RejectedCandidate>> explain_rejected(const std::vector<c
     const uint32_t p = (uint32_t)pods.size();
     std::vector<std::vector<RejectedCandidate>> out(p);
     if (!ctx.snapshot || p == 0 || sel.samples.size() != (size_t)p * ATTEMPTS || sel.validity.binding.size() != p) return out;
-    if (ctx.pick_uniform || ctx.pick_spread || ctx.pick_pack) return out;  // (those draws are numbers, not node indices, and none of them is rejected)
+    if (ranked_choice(ctx).flag) return out;  // (those draws are numbers, not node indices, and none of them is rejected)
     Snapshot &snap = *ctx.snapshot;
     const uint32_t n = snap.n();
     std::vector<std::pair<uint32_t, uint32_t>> pairs;

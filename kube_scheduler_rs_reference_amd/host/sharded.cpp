@@ -73,7 +73,7 @@ ShardedContext::~ShardedContext() {
 void ShardedContext::eval(const PodColumns &pc, const uint32_t *samples, uint32_t attempts, uint32_t flags, uint32_t W, uint64_t *out_feasible,
                           uint64_t *out_fit, int32_t *out_binding) {
     const uint32_t n = size(), p = pc.p;
-    const bool pick = flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_BESTFIT | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK);
+    const bool pick = flags & KSCHED_PICK_ANY;
     if (pick && !out_binding) throw EncodeError("ShardedContext::eval: a pick needs out_binding");
     if (p == 0) return;
     const uint32_t cpr = shard_bounds(p, n, 0).count_per_rank;
@@ -89,7 +89,7 @@ void ShardedContext::eval(const PodColumns &pc, const uint32_t *samples, uint32_
         const int rc = ksched_eval_begin(devs_[r]->handle(), rows, pc.req_cpu_milli.data() + lo, pc.req_mem_bytes.data() + lo,
                                          pc.n_keys ? pc.sel_val_ids.data() + lo : nullptr, p,  // rows [lo, hi) of the [n_keys][p] array
                                          (flags & KSCHED_TAINT) && !pc.tolerations.empty() ? pc.tolerations.data() + lo : nullptr,
-                                         (flags & (KSCHED_PICK_SAMPLED | KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)) ? samples + (size_t)lo * attempts : nullptr, attempts, flags,
+                                         (flags & KSCHED_PICK_DRAWS) ? samples + (size_t)lo * attempts : nullptr, attempts, flags,
                                          out_feasible ? out_feasible + (size_t)lo * W : nullptr, out_fit ? out_fit + (size_t)lo * W : nullptr, cpr, &local[r],
                                          &streams[r]);
         ++touched;

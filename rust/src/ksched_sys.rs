@@ -40,6 +40,9 @@ pub const KSCHED_PICK_BESTFIT: u32 = 0x10;
 pub const KSCHED_PICK_UNIFORM: u32 = 0x40;
 pub const KSCHED_PICK_SPREAD: u32 = 0x80;
 pub const KSCHED_PICK_PACK: u32 = 0x100;
+pub const KSCHED_PICK_RANKED: u32 = KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK; // rank 32-bit draws among the feasible nodes: always read the mask
+pub const KSCHED_PICK_DRAWS: u32 = KSCHED_PICK_SAMPLED | KSCHED_PICK_RANKED; // the picks that read `samples`
+pub const KSCHED_PICK_ANY: u32 = KSCHED_PICK_BESTFIT | KSCHED_PICK_DRAWS; // every pick flag: at most one per call
 pub const KSCHED_WANT_FIT_MASK: u32 = 0x20;
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
@@ -292,6 +295,9 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_PICK_UNIFORM", KSCHED_PICK_UNIFORM as i64),
         ("KSCHED_PICK_SPREAD", KSCHED_PICK_SPREAD as i64),
         ("KSCHED_PICK_PACK", KSCHED_PICK_PACK as i64),
+        ("KSCHED_PICK_RANKED", KSCHED_PICK_RANKED as i64),
+        ("KSCHED_PICK_DRAWS", KSCHED_PICK_DRAWS as i64),
+        ("KSCHED_PICK_ANY", KSCHED_PICK_ANY as i64),
         ("KSCHED_WANT_FIT_MASK", KSCHED_WANT_FIT_MASK as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),

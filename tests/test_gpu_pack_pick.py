@@ -18,8 +18,8 @@ from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_PACK, PICK_
 from tests import uniform_rows as R
 from tests.admit_ref import apply_while_fit_exact
 from tests.pack_ref import pack_pick, pack_pick_listed
+from tests.pick_helpers import dev_of, fresh, mask_np, oracle_mask, pod_tensors, to_dev, u_hi, u_lo
 from tests.spread_ref import spread_candidates_listed
-from tests.test_gpu_uniform_pick import dev_of, mask_np, oracle_mask, pod_tensors, to_dev
 from tests.uniform_ref import uniform_pick
 
 pytestmark = pytest.mark.gpu
@@ -44,21 +44,6 @@ def twin(built):
     """the second ctx of answer (b): it holds the complemented columns and runs the spread pick"""
     with Evaluator(0) as e:
         yield e
-
-
-def fresh(ev, p, extra=0):
-    import torch
-    return torch.full((p + extra,), -7, dtype=torch.int32, device=dev_of(ev))
-
-
-def u_lo(j, c):
-    """the smallest draw whose k is j among c feasible nodes: ceil(j * 2^32 / c)"""
-    return -((-j << 32) // c)
-
-
-def u_hi(j, c):
-    """the largest draw whose k is j"""
-    return u_lo(j + 1, c) - 1
 
 
 # ---- 1. caller-made rows ------------------------------------------------------------------------------------------------------

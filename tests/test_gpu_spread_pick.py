@@ -13,8 +13,8 @@ from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PI
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact
 from tests.admit_ref import apply_while_fit_exact
+from tests.pick_helpers import dev_of, fresh, mask_np, oracle_mask, pitched_mask, pod_tensors, to_dev
 from tests.spread_ref import best_of, spread_candidates, spread_candidates_listed, spread_pick
-from tests.test_gpu_uniform_pick import dev_of, mask_np, oracle_mask, pitched_mask, pod_tensors, to_dev
 from tests.uniform_ref import uniform_pick
 
 pytestmark = pytest.mark.gpu
@@ -55,11 +55,6 @@ def want_of(k, d):
 
 def table(k, d, lo=0, hi=None):
     return np.ascontiguousarray(k["draws"][lo:hi, :d])
-
-
-def fresh(ev, p, extra=0):
-    import torch
-    return torch.full((p + extra,), -7, dtype=torch.int32, device=dev_of(ev))
 
 
 @pytest.fixture

@@ -11,6 +11,7 @@ import pytest
 from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_UNIFORM, SEL, TAINT, KschedError, _lib, synth,
                                              unpack_mask)
 from oracle import capi
+from tests.pick_helpers import dev_of, mask_np, oracle_mask, pitched_mask, pod_tensors, to_dev
 from tests.uniform_ref import uniform_pick
 
 pytestmark = pytest.mark.gpu
@@ -33,41 +34,6 @@ def case(spec):
         draws.setflags(write=False)
         _CASES[spec] = dict(c=c, flags=flags, feas=feas, draws=draws, want=uniform_pick(feas, draws[:, 0], N))
     return _CASES[spec]
-
-
-def oracle_mask(c, flags, cpu=None, mem=None):
-    feas, _, _ = capi.eval_encoded(c.avail_cpu if cpu is None else cpu, c.avail_mem if mem is None else mem,
-                                   c.node_labels if c.n_keys else None, c.node_taints if c.n_taints else None, c.req_cpu, c.req_mem,
-                                   np.ascontiguousarray(c.pod_sel) if c.n_keys else None, c.pod_tol if c.n_taints else None, None, flags)
-    return feas
-
-
-def dev_of(ev):
-    import torch
-    return torch.device("cuda", ev.device)
-
-
-def to_dev(ev, a, dt):
-    import torch
-    return torch.from_numpy(np.array(a, order="C").view(dt)).to(dev_of(ev))  # (a copy: the shared cases are read-only)
-
-
-def pod_tensors(ev, c, lo=0, hi=None):
-    hi = c.P if hi is None else hi
-    return (to_dev(ev, c.req_cpu[lo:hi], np.int64), to_dev(ev, c.req_mem[lo:hi], np.int64),
-            to_dev(ev, c.pod_sel[:, lo:hi], np.int32) if c.n_keys else None, to_dev(ev, c.pod_tol[lo:hi], np.int64) if c.n_taints else None)
-
-
-def pitched_mask(ev, p, pitch, fill=0x5A):
-    """a [p, W] view with rows `pitch` words apart over a buffer filled with a sentinel"""
-    import torch
-    buf = torch.empty((max(p, 1), max(pitch, 1)), dtype=torch.int64, device=dev_of(ev))
-    buf.untyped_storage().fill_(fill)
-    return buf[:p, :ev.W]
-
-
-def mask_np(m):
-    return m.contiguous().cpu().numpy().view(np.uint64)
 
 
 @pytest.fixture
