@@ -23,6 +23,8 @@
  *   (extension E3: the batch holds every pod's whole row)  KSCHED_PICK_UNIFORM
  *   (extension E4: ... and the nodes' available resources)  KSCHED_PICK_SPREAD
  *   (extension E5: E4 towards the fullest node)            KSCHED_PICK_PACK
+ *   (extension E6: boolean expressions over evaluations,   KSCHED_COMBINE_AND / _OR / _ANDNOT
+ *     combined in the caller's mask on the device)
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -162,6 +164,44 @@ extern "C" {
 #define KSCHED_PICK_RANKED (KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | KSCHED_PICK_PACK)
 #define KSCHED_PICK_DRAWS (KSCHED_PICK_SAMPLED | KSCHED_PICK_RANKED)
 #define KSCHED_PICK_ANY (KSCHED_PICK_BESTFIT | KSCHED_PICK_DRAWS)
+/* KSCHED_COMBINE_AND / _OR / _ANDNOT (extension E6): fold this call's evaluation into the mask the caller already holds, on the device.
+ * One call of the evaluator answers one conjunction (fit AND nodeSelector AND taints, at most KSCHED_MAX_KEYS label columns); with these
+ * flags any boolean expression over evaluations -- a selector with more keys than one call takes, a nodeAffinity term with In {a, b} or
+ * NotIn {v}, several nodeSelectorTerms (which Kubernetes ORs), "not on a node that already carries X" -- stays in HBM, and the existing
+ * picks finish it.  At most one KSCHED_COMBINE_* flag per call.  Added in ABI 7 without a version change and without a new symbol: detect
+ * them by these constants and by KSCHED_E_INVAL from an older library.  (0x1000 is not a flag: callers probe with it for KSCHED_E_INVAL.)
+ *   meaning    : feasible(this call) is, bit for bit, what the same call WITHOUT the combine flag would have written: the predicates
+ *                selected in `flags` against the current snapshot, predicates not selected treated as true.  out_feasible is read AND
+ *                written: it is the caller's mask from earlier calls, and becomes out_feasible OP feasible(this call).  Per pod row the
+ *                words [0, W) are combined; bits at or beyond n in the row's last word come out ZERO, whatever the old mask held there;
+ *                the words [W, pitch) are never read, and are left untouched or written as zero (the existing rule for padding).
+ *   exact      : integer logic only -- same inputs, same bits, on every run.
+ *   accepted   : by ksched_eval_device and ksched_eval_device_pitched.  NOT by the host-pointer forms ksched_eval and ksched_eval_begin (a
+ *                host mask would first have to travel to the device, which is what the flags exist to avoid), nor by ksched_pipe_submit,
+ *                ksched_pick* or ksched_summarize*: all of these answer KSCHED_E_INVAL with nothing enqueued and nothing written.
+ *   errors     : KSCHED_E_INVAL with nothing enqueued for two combine flags at once, for out_feasible == NULL, and for KSCHED_WANT_FIT_MASK
+ *                or out_fit together with a combine flag.  Everything else follows the plain evaluation: KSCHED_E_STATE before
+ *                ksched_set_nodes, p == 0 is a no-op, n == 0 leaves the mask alone (and gives -1 for every pod of a pick).
+ *   with a pick: a pick flag in the same call runs BEHIND the combine and reads the COMBINED mask: the bindings are exactly those of
+ *                ksched_pick_device on that mask with the pick flag alone and no predicate flag.  In particular the best-fit pick is not
+ *                told that the mask includes the resource fit -- under OR and AND-NOT it need not --, so req_mem_bytes is not used to skip
+ *                candidates.  KSCHED_OPT_PICK_FROM_MASK and KSCHED_OPT_FUSED_PICK have no effect on a combining call.  ksched_last_pick:
+ *                "from-mask" for the sampled and the best-fit pick, the member's name for the ranked picks, "none" without a pick;
+ *                ksched_last_kernel: the mask kernel's name, as for a plain call.
+ *   ordering   : that of a plain ksched_eval_device on `hip_stream`: a set, update or apply enqueued before the call is visible, one
+ *                enqueued after it is not.  The call evaluates into the ctx's scratch mask and holds it under the same rule as a ranked pick
+ *                without out_feasible: calls on several streams are ordered against each other by the library.
+ *   timing     : KSCHED_OPT_TIMING keeps bracketing the mask kernel only.
+ * Recipe -- zone In {a, b} AND disk NotIn {hdd} AND fit, then the spread pick, in four calls on one stream and one mask M:
+ *     ksched_eval_device(.., sel: zone = a,   KSCHED_SEL,                                            M, ..)   M  = [zone = a]
+ *     ksched_eval_device(.., sel: zone = b,   KSCHED_SEL | KSCHED_COMBINE_OR,                        M, ..)   M |= [zone = b]
+ *     ksched_eval_device(.., sel: disk = hdd, KSCHED_SEL | KSCHED_COMBINE_ANDNOT,                    M, ..)   M &= ~[disk = hdd]
+ *     ksched_eval_device(.., no selector,     KSCHED_FIT | KSCHED_COMBINE_AND | KSCHED_PICK_SPREAD,  M, .., out_binding, ..)
+ * (a node WITHOUT the disk label passes NotIn, as in Kubernetes: it does not carry disk = hdd.) */
+#define KSCHED_COMBINE_AND 0x200u    /* out_feasible = out_feasible &  feasible(this call) */
+#define KSCHED_COMBINE_OR 0x400u     /* out_feasible = out_feasible |  feasible(this call) */
+#define KSCHED_COMBINE_ANDNOT 0x800u /* out_feasible = out_feasible & ~feasible(this call) */
+#define KSCHED_COMBINE_ANY (KSCHED_COMBINE_AND | KSCHED_COMBINE_OR | KSCHED_COMBINE_ANDNOT)
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0

@@ -41,6 +41,11 @@ PICK_PACK = 0x100  # extension E5: the tightest (smallest available memory, then
 PICK_RANKED = PICK_UNIFORM | PICK_SPREAD | PICK_PACK  # the picks that rank 32-bit draws among a pod's feasible nodes: they always read the mask
 PICK_DRAWS = PICK_SAMPLED | PICK_RANKED  # the picks that read `samples`
 PICK_ANY = PICK_BESTFIT | PICK_DRAWS  # every pick flag: at most one per call
+# extension E6 (ksched_eval_device* only): fold this call's evaluation into the caller's out_feasible on the device; at most one per call
+COMBINE_AND = 0x200  # out_feasible = out_feasible & feasible(this call)
+COMBINE_OR = 0x400  # out_feasible = out_feasible | feasible(this call)
+COMBINE_ANDNOT = 0x800  # out_feasible = out_feasible & ~feasible(this call)
+COMBINE_ANY = COMBINE_AND | COMBINE_OR | COMBINE_ANDNOT
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

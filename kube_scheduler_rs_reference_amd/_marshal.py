@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib as L
 
 DRAWS = L.PICK_DRAWS  # the picks that read `samples`
+COMBINE = L.COMBINE_ANY  # the flags that fold a call's evaluation into the caller's mask (extension E6)
 
 # element kinds of the C ABI: the torch dtypes that may stand for them (int64 stands in for uint64, int32 for uint32, bool for uint8)
 KINDS = {"i64": ("int64",), "u64": ("int64", "uint64"), "i32": ("int32",), "u32": ("int32", "uint32"), "u8": ("uint8", "bool")}
@@ -97,6 +98,24 @@ def draws(samples, name: str, flags: int, p: int, device: Optional[int] = None):
                              f"got {None if samples is None else tuple(samples.shape)}")
         attempts = int(samples.shape[1])
     return host_ptr(samples) if device is None else _vp(device_ptr(samples, name, "u32", None, device)), attempts, samples
+
+
+def combine(flags: int, where: str, accepted: bool, out_feasible=None, out_fit=None) -> None:
+    """The one rule of COMBINE_AND / COMBINE_OR / COMBINE_ANDNOT (include/ksched.h, extension E6), before any library call: only
+    `eval_device` / `bind_eval_device` accept them (accepted=True) -- a host mask would first have to travel to the device, a pipe slot's
+    mask belongs to the slot --, at most one per call, `out_feasible` is required (it is read and written: the caller's mask from earlier
+    calls) and WANT_FIT_MASK / `out_fit` are excluded (a combining call writes one mask).  ValueError naming the argument."""
+    c = int(flags) & COMBINE
+    if not c:
+        return
+    if not accepted:
+        raise ValueError(f"flags: {where} takes no COMBINE_AND / COMBINE_OR / COMBINE_ANDNOT (the mask is combined on the device: Evaluator.eval_device)")
+    if c & (c - 1):
+        raise ValueError(f"flags: at most one of COMBINE_AND / COMBINE_OR / COMBINE_ANDNOT per call, got {c:#x}")
+    if out_feasible is None:
+        raise ValueError("out_feasible: a COMBINE_* flag needs the mask it combines into")
+    if out_fit is not None or int(flags) & L.WANT_FIT_MASK:
+        raise ValueError("out_fit: a COMBINE_* flag excludes WANT_FIT_MASK / out_fit")
 
 
 class Batch(NamedTuple):

@@ -11,6 +11,7 @@
 
 #include "../../include/ksched.h"
 #include "bestfit_layout.hpp"
+#include "mask_combine.hpp"
 
 namespace ksched {
 
@@ -44,6 +45,7 @@ struct EvalFacts {
     bool opt_pick_from_mask = false;
     uint32_t opt_grid_cus = 0;
     uint32_t debug = 0;  // KSCHED_OPT_DEBUG (bit 0x400: best fit in one stage)
+    CombineOp combine = CombineOp::kNone;  // combine_op(flags) of a combining call (extension E6, mask_combine.hpp); the caller gave out_feasible and no out_fit
 };
 
 enum class MaskKernel { kNone, kFused, kDirect };
@@ -56,10 +58,11 @@ struct EvalPlan {
     int error = KSCHED_OK;  // KSCHED_E_UNSUPPORTED: nothing is enqueued, `why` names the message
     PlanError why = PlanError::kNone;
     MaskKernel mask = MaskKernel::kNone;
-    bool scratch_mask = false;  // the mask kernel writes the feasible mask into the ctx's scratch one (the caller gave none)
+    bool scratch_mask = false;  // the mask kernel writes the feasible mask into the ctx's scratch one (the caller gave none, or the call combines into the caller's)
     SampledPick sampled = SampledPick::kNone;
     BestfitPick bestfit = BestfitPick::kNone;
     RankedPick ranked = RankedPick::kNone;
+    CombineOp combine = CombineOp::kNone;  // not kNone: k_mask_combine folds the scratch mask into the caller's mask, between the mask kernel and the pick
     const char *last_kernel = nullptr;  // ksched_last_kernel after the launch; nullptr = no mask kernel runs, it stays what it was
     const char *last_pick = "none";     // ksched_last_pick
 
@@ -101,6 +104,26 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     const bool want_mask = f.have_feas || f.have_fit;
     const bool can_fused = f.fused_applicable;
     const int kern = choose_kernel(f.opt_kernel, can_fused);
+    // A combining call (extension E6) is a mask-only evaluation into the ctx's scratch mask -- although the caller gave a mask: that one
+    // is the combine's left operand --, then the combine, then the pick from the COMBINED mask.  So the mask kernel is chosen as for a
+    // mask-only request, nothing rides in it (a riding pick would test the call's own predicates, not the combined mask), and the sampled
+    // and the best-fit pick read the mask, whatever KSCHED_OPT_PICK_FROM_MASK / KSCHED_OPT_FUSED_PICK say; the ranked picks always did.
+    if (f.combine != CombineOp::kNone) {
+        if (kern == KSCHED_KERNEL_FUSED && !can_fused) return plan_unsupported(PlanError::kFusedNotApplicable);
+        plan.combine = f.combine;
+        plan.scratch_mask = true;
+        plan.mask = kern == KSCHED_KERNEL_FUSED ? MaskKernel::kFused : MaskKernel::kDirect;
+        plan.last_kernel = kern == KSCHED_KERNEL_FUSED ? "fused" : "direct";
+        if (const RankedMember *m = ranked_member(flags)) {
+            plan.ranked = m->pick;
+            plan.last_pick = m->name;
+        } else if (pick_s || pick_b) {
+            if (pick_s) plan.sampled = SampledPick::kFromMask;
+            else plan.bestfit = BestfitPick::kFromMask;
+            plan.last_pick = "from-mask";
+        }
+        return plan;
+    }
     // The ranked picks (KSCHED_PICK_RANKED) count and rank the set bits of the pod's whole row -- the uniform pick once, the spread and the
     // pack pick once per draw, comparing the candidates: the mask kernel always runs (into the ctx's scratch mask when the caller gave
     // none), the pick is its own launch behind it, and neither KSCHED_OPT_PICK_FROM_MASK nor KSCHED_OPT_FUSED_PICK applies.  One plan for

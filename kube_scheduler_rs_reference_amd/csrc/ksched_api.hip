@@ -32,6 +32,7 @@
 #include "kernels_summary.hpp"
 #include "kernels_pick_spread.hpp"  // (uses kernels_pick_uniform.hpp's helpers)
 #include "kernels_pick_pack.hpp"    // (k_pick_spread's body with the comparison turned round)
+#include "kernels_combine.hpp"      // (extension E6: the scratch mask folded into the caller's mask)
 #include "mask_alloc.hpp"
 #include "merge_sort_plan.hpp"
 #include "pipe_plan.hpp"
@@ -1136,7 +1137,7 @@ int fail_fused_not_applicable(ksched_ctx *c) {
     return KSCHED_E_UNSUPPORTED;
 }
 
-// the mask kernel of the plan -- with the riding pick, if one rides -- and the pick that reads the mask, if one does
+// the mask kernel of the plan -- with the riding pick, if one rides --, the combine of a combining call, and the pick that reads the mask, if one does
 int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
     const hipStream_t s = r.stream;
     const bool fused = plan.mask == MaskKernel::kFused;
@@ -1182,8 +1183,15 @@ int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
     }
     c->last_kernel = plan.last_kernel;
     if (int trc = timing_end(c, s, t)) return trc;
+    if (plan.combine == CombineOp::kNone) return plan.pick_from_mask() ? launch_pick(c, r, feas) : KSCHED_OK;
+    // a combining call: the scratch mask holds feasible(this call); fold it into the caller's mask, then pick from that mask alone -- the
+    // pick is told nothing about the predicates (best fit must not skip candidates by req_mem: under OR and AND-NOT the combined mask
+    // need not include the fit)
+    if (hipError_t e = run_mask_combine(plan.combine, r.out_feas, feas, r.p, c->n, c->W, r.pitch, s); e != hipSuccess) return fail_hip(c, e, "run_mask_combine");
     if (!plan.pick_from_mask()) return KSCHED_OK;
-    return launch_pick(c, r, feas);
+    EvalRequest pick = r;
+    pick.flags = r.flags & KSCHED_PICK_ANY;
+    return launch_pick(c, pick, r.out_feas);
 }
 
 // what plan_eval decides by, read off the ctx and the request
@@ -1211,6 +1219,7 @@ EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
     f.opt_pick_from_mask = c->opt_pick_from_mask;
     f.opt_grid_cus = c->opt_grid_cus;
     f.debug = c->opt_debug;
+    f.combine = combine_op(r.flags);
     return f;
 }
 
@@ -1297,11 +1306,13 @@ inline bool at_most_one_pick(uint32_t flags) {
     return (pick & (pick - 1u)) == 0;
 }
 
-// the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed)
-int check_eval_args(const EvalRequest &r) {
+// the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed).
+// combine_accepted: the entry point takes the KSCHED_COMBINE_* flags (the two device-pointer evaluations; mask_combine.hpp has the rules)
+int check_eval_args(const EvalRequest &r, bool combine_accepted = false) {
     const uint32_t flags = r.flags;
-    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK;
+    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK | KSCHED_COMBINE_ANY;
     if (flags & ~known) return KSCHED_E_INVAL;
+    if (int rcc = check_combine_args(flags, combine_accepted, r.out_feas != nullptr, r.out_fit != nullptr)) return rcc;
     if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
     if (flags & KSCHED_PICK_DRAWS) {
@@ -1723,7 +1734,7 @@ int ksched_eval_device_pitched(ksched_ctx *c, uint32_t p, const int64_t *pcpu, c
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->have_nodes) return KSCHED_E_STATE;
     const EvalRequest r{p, pcpu, pmem, psel, ptol, samples, attempts, flags, out_feas, out_fit, out_binding, mask_pitch_words, (hipStream_t)hip_stream};
-    int rc = check_eval_args(r);
+    int rc = check_eval_args(r, /*combine_accepted=*/true);
     if (rc) return rc;
     if (mask_pitch_words < c->W) return KSCHED_E_INVAL;
     DeviceGuard g(c->device);

@@ -202,7 +202,9 @@ class Evaluator:
         the least loaded -- available memory, then cpu, then the lowest index -- of d uniformly drawn feasible nodes) and PICK_PACK
         (the same draws: the tightest -- the smallest available memory, then cpu, then the lowest index -- of them), WANT_FIT_MASK.
         `out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
-        after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4)."""
+        after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4).
+        The COMBINE_* flags are refused here (ValueError): masks are combined on the device, by eval_device."""
+        M.combine(flags, "Evaluator.eval", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
         p, W = b.p, self.W
         res = EvalResult()
@@ -226,7 +228,12 @@ class Evaluator:
                     flags: int = L.FIT, out_feasible=None, out_fit=None, out_binding=None, stream=None):
         """All arguments are torch CUDA tensors on this evaluator's device (int64 stands in for
         uint64, int32 for uint32).  Work is enqueued on `stream` (default: torch's current stream).  `samples` [p, attempts] is read with
-        PICK_SAMPLED (node indices), with PICK_UNIFORM (32-bit draws, column 0) and with PICK_SPREAD / PICK_PACK (32-bit draws, every column)."""
+        PICK_SAMPLED (node indices), with PICK_UNIFORM (32-bit draws, column 0) and with PICK_SPREAD / PICK_PACK (32-bit draws, every column).
+        With one of COMBINE_AND / COMBINE_OR / COMBINE_ANDNOT (extension E6) `out_feasible` is read AND written: it holds the caller's mask
+        from earlier calls and becomes out_feasible & / | / & ~ feasible(this call), on the device -- words [0, W) of every row, bits at or
+        beyond n of the last word zero afterwards.  A pick flag in the same call picks from the COMBINED mask (as pick_device on it with the
+        pick flag alone).  Needs `out_feasible`; excludes WANT_FIT_MASK / `out_fit`.  So `zone In {a, b} and disk NotIn {hdd} and fit` is
+        four calls on one mask: SEL (zone = a), SEL | COMBINE_OR (zone = b), SEL | COMBINE_ANDNOT (disk = hdd), FIT | COMBINE_AND | a pick."""
         calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                              [out_feasible], out_fit, [out_binding], stream)
         self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
@@ -235,6 +242,8 @@ class Evaluator:
         """calls[i][m] = the checked argument tuple of ksched_eval_device_pitched that writes bindings outs[i] and mask masks[m], and
         what those addresses point into."""
         import torch
+        for m in masks:
+            M.combine(flags, "Evaluator.eval_device", accepted=True, out_feasible=m, out_fit=out_fit)
         b = M.device_batch(self.device, self.n_keys, *cols, flags)
         (*pm, pr), pitch = M.mask_rows(b.p, self.W, self.device, *[("out_feasible", m) for m in masks], ("out_fit", out_fit))
         po = [M.device_ptr(o, "out_binding", "i32", (b.p,), self.device) for o in outs]
@@ -248,7 +257,8 @@ class Evaluator:
         """Pre-marshal eval_device for a steady-state loop whose inputs stay in place: validates once and returns run(i, m=0)
         that enqueues the evaluation writing out_bindings[i] (and, when `out_feasible` is a LIST of equally shaped masks, the
         mask out_feasible[m]: a loop can rotate its output over several buffers).  Saves the per-call tensor checks and pointer
-        conversions (tens of microseconds of Python per step)."""
+        conversions (tens of microseconds of Python per step).  The COMBINE_* flags as in eval_device: every mask of the list is then
+        one that run(i, m) reads and writes."""
         masks = list(out_feasible) if isinstance(out_feasible, (list, tuple)) else [out_feasible]
         calls, keep = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                                 masks, out_fit, list(out_bindings) or [None], stream)
@@ -413,6 +423,7 @@ class Pipe:
     def _marshal(self, cols, flags, masks, bindings):
         """(the batch, [(mask, pitch, binding) per slot]) as ksched_pipe_submit takes them, checked"""
         ev = self.ev
+        M.combine(flags, "Pipe.submit", accepted=False)
         b = M.device_batch(ev.device, ev.n_keys, *cols, flags)
         per_slot = []
         for m, o in zip(masks, bindings):
@@ -422,7 +433,8 @@ class Pipe:
 
     def submit(self, slot: int, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags: int, mask, binding):
         """torch CUDA tensors (see Evaluator.eval_device); `mask` is a [p, W] (possibly pitched) view, `binding` int32 [p].  flags carry one
-        of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM, PICK_SPREAD, PICK_PACK (the uniform, the spread and the pack pick read the mask: their slot runs in the split mode, ordered by events)."""
+        of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM, PICK_SPREAD, PICK_PACK (the uniform, the spread and the pack pick read the mask: their slot runs in the split mode, ordered by events).
+        The COMBINE_* flags are refused (ValueError): a slot's mask belongs to the slot; combine with Evaluator.eval_device."""
         b, per_slot = self._marshal((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags, [mask], [binding])
         self.ev._check(self._lib.ksched_pipe_submit(self._h, slot, *b[:8], *per_slot[0]), "ksched_pipe_submit")
 

@@ -44,6 +44,10 @@ pub const KSCHED_PICK_RANKED: u32 = KSCHED_PICK_UNIFORM | KSCHED_PICK_SPREAD | K
 pub const KSCHED_PICK_DRAWS: u32 = KSCHED_PICK_SAMPLED | KSCHED_PICK_RANKED; // the picks that read `samples`
 pub const KSCHED_PICK_ANY: u32 = KSCHED_PICK_BESTFIT | KSCHED_PICK_DRAWS; // every pick flag: at most one per call
 pub const KSCHED_WANT_FIT_MASK: u32 = 0x20;
+pub const KSCHED_COMBINE_AND: u32 = 0x200; // extension E6, ksched_eval_device*: out_feasible = out_feasible & feasible(this call)
+pub const KSCHED_COMBINE_OR: u32 = 0x400; // out_feasible = out_feasible | feasible(this call)
+pub const KSCHED_COMBINE_ANDNOT: u32 = 0x800; // out_feasible = out_feasible & !feasible(this call)
+pub const KSCHED_COMBINE_ANY: u32 = KSCHED_COMBINE_AND | KSCHED_COMBINE_OR | KSCHED_COMBINE_ANDNOT; // at most one per call
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
 pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
@@ -299,6 +303,10 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_PICK_DRAWS", KSCHED_PICK_DRAWS as i64),
         ("KSCHED_PICK_ANY", KSCHED_PICK_ANY as i64),
         ("KSCHED_WANT_FIT_MASK", KSCHED_WANT_FIT_MASK as i64),
+        ("KSCHED_COMBINE_AND", KSCHED_COMBINE_AND as i64),
+        ("KSCHED_COMBINE_OR", KSCHED_COMBINE_OR as i64),
+        ("KSCHED_COMBINE_ANDNOT", KSCHED_COMBINE_ANDNOT as i64),
+        ("KSCHED_COMBINE_ANY", KSCHED_COMBINE_ANY as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
         ("KSCHED_APPLY_WHILE_FIT", KSCHED_APPLY_WHILE_FIT as i64),
