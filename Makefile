@@ -6,7 +6,8 @@
 #   make host       -> kube_scheduler_rs_reference_amd/libksched_host.so    g++, links libksched_hip.so; + tests/cpp/host_tests
 #   make oracle     -> oracle/liboracle.so                                  gcc, test infrastructure only
 #   make tools      -> tools/pmc_calib                                      hipcc: calibration kernels for the HBM counters
-#                      tools/libmask_combine_bench.so                       hipcc: k_mask_combine alone, for tools/mask_combine_cost.py
+#                      tools/libmask_combine_bench.so                       hipcc: k_mask_combine and k_mask_combine_soft alone, for tools/mask_combine_cost.py
+#                                                                           and tools/mask_combine_soft_cost.py
 #   make sanitize   -> build/san/host_tests_{asan,tsan}                     the host mirror + its C++ tests under AddressSanitizer + UBSan, and under ThreadSanitizer
 #                      (CPU sanitizers over HOST code only; `tools/sanitize.sh` runs them: the CPU half here, the device half on a GPU box)
 #   make test-lib   -> tests/cpp/hooks/libksched_hip.so                     the SAME object code + tests/cpp/test_hooks.cpp: the only build in which
@@ -49,6 +50,7 @@ STREAM_ORDER_TEST := tests/cpp/stream_order_tests
 MERGE_SORT_PLAN_TEST := tests/cpp/merge_sort_plan_tests
 APPLY_PLAN_TEST := tests/cpp/apply_plan_tests
 COMBINE_PLAN_TEST := tests/cpp/combine_plan_tests
+SOFT_PLAN_TEST := tests/cpp/soft_plan_tests
 
 PMC_CALIB := tools/pmc_calib
 COMBINE_BENCH := tools/libmask_combine_bench.so
@@ -64,9 +66,9 @@ tools: $(PMC_CALIB) $(COMBINE_BENCH)
 $(PMC_CALIB): tools/pmc_calib.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -o $@ tools/pmc_calib.hip
 
-# k_mask_combine alone and its yardstick (a device-to-device copy) as two C functions, for tools/mask_combine_cost.py: the library's own
-# launch path, compiled from the same header with the same flags
-$(COMBINE_BENCH): tools/mask_combine_bench.hip $(CSRC)/kernels_combine.hpp $(CSRC)/mask_combine.hpp include/ksched.h
+# k_mask_combine alone, its yardstick (a device-to-device copy) and k_mask_combine_soft alone as three C functions, for
+# tools/mask_combine_cost.py and tools/mask_combine_soft_cost.py: the library's own launch paths, compiled from the same headers with the same flags
+$(COMBINE_BENCH): tools/mask_combine_bench.hip $(CSRC)/kernels_combine.hpp $(CSRC)/mask_combine.hpp $(CSRC)/kernels_combine_soft.hpp $(CSRC)/mask_combine_soft.hpp include/ksched.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ tools/mask_combine_bench.hip
 
 lib: $(LIB_HIP)
@@ -82,7 +84,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
 # (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(SOFT_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -122,6 +124,9 @@ $(APPLY_PLAN_TEST): tests/cpp/apply_plan_tests.cpp $(CSRC)/apply_plan.hpp $(CSRC
 # host-only check of a combining evaluation's rules (csrc/mask_combine.hpp: the op of a flag word, the argument rules, the valid-bits word, the access width, the launch geometry executed on the CPU; csrc/eval_plan.hpp: the plan with an op, and without one against plan_eval as it was; no GPU, no HIP header): tests/test_combine_plan_host.py runs it
 $(COMBINE_PLAN_TEST): tests/cpp/combine_plan_tests.cpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/combine_plan_tests.cpp
+# host-only check of a soft combining evaluation's rules, KSCHED_COMBINE_SOFT (csrc/mask_combine_soft.hpp: which flag words and entry points carry the modifier, the row rule, the launch geometry executed on the CPU at each side of every switch; csrc/eval_plan.hpp: the plan with the bit against the plain combining plan; no GPU, no HIP header): tests/test_soft_plan_host.py runs it
+$(SOFT_PLAN_TEST): tests/cpp/soft_plan_tests.cpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/soft_plan_tests.cpp
 $(LIB_HOST): $(HOST_SRCS) $(HOST_HDRS) $(LIB_HIP)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRCS) -L$(PKG) -lksched_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 # C++ tests of the host mirror (tests/cpp/host_tests.cpp; driven by tests/test_host_mirror.py)
@@ -185,4 +190,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB) $(COMBINE_BENCH)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(SOFT_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB) $(COMBINE_BENCH)

@@ -25,6 +25,8 @@
  *   (extension E5: E4 towards the fullest node)            KSCHED_PICK_PACK
  *   (extension E6: boolean expressions over evaluations,   KSCHED_COMBINE_AND / _OR / _ANDNOT
  *     combined in the caller's mask on the device)
+ *   (extension E7: soft constraints -- combine only where   KSCHED_COMBINE_SOFT
+ *     the pod keeps a node)
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -202,6 +204,40 @@ extern "C" {
 #define KSCHED_COMBINE_OR 0x400u     /* out_feasible = out_feasible |  feasible(this call) */
 #define KSCHED_COMBINE_ANDNOT 0x800u /* out_feasible = out_feasible & ~feasible(this call) */
 #define KSCHED_COMBINE_ANY (KSCHED_COMBINE_AND | KSCHED_COMBINE_OR | KSCHED_COMBINE_ANDNOT)
+/* KSCHED_COMBINE_SOFT (extension E7): a SOFT constraint -- narrow the pod's feasible set by this call's evaluation, unless that would leave
+ * it empty.  A modifier of KSCHED_COMBINE_AND or KSCHED_COMBINE_ANDNOT in ksched_eval_device and ksched_eval_device_pitched; not a member of
+ * KSCHED_COMBINE_ANY, which stays "the ops".  It is what a preferred node-affinity term, a PreferNoSchedule taint and any rule "prefer X,
+ * but never leave the pod unbound for it" mean; the decision is per pod row and needs the whole row, so no sequence of AND / OR / AND-NOT
+ * gives it.  Added in ABI 7 without a version change and without a new symbol: detect it by this constant and by KSCHED_E_INVAL from an
+ * older library.
+ *   meaning    : per pod row, with new = feasible(this call), bit for bit what the call writes without any combine flag, and old' = the
+ *                caller's row over the words [0, W) with the bits at or beyond n in the last word cleared:
+ *                    r = old' & new (KSCHED_COMBINE_AND)    or    r = old' & ~new (KSCHED_COMBINE_ANDNOT);
+ *                if r has at least one set bit the row becomes r (the preference narrows), otherwise it becomes old' (the preference is
+ *                dropped for this pod).  So a row that was empty stays empty; a non-empty row never becomes empty; a row whose only set
+ *                bits were at or beyond n counts as empty and comes out all zero; bits at or beyond n come out zero in every case.  The
+ *                words [W, pitch) are never read, and are left untouched or written as zero.
+ *   exact      : integer logic only -- same inputs, same bits, on every run.
+ *   errors     : KSCHED_E_INVAL with nothing enqueued and nothing written for KSCHED_COMBINE_SOFT without a combine op; with
+ *                KSCHED_COMBINE_OR (OR cannot empty a row, so the modifier would mean nothing); for every refusal of a combining call (two
+ *                ops, out_feasible == NULL, KSCHED_WANT_FIT_MASK or out_fit); and for the flag at ksched_eval, ksched_eval_begin,
+ *                ksched_pipe_submit, ksched_pick* and ksched_summarize*.
+ *   otherwise  : the combining call's contract, unchanged: ordering on `hip_stream`; the evaluation goes into the ctx's scratch mask, held
+ *                as by any combining call; a pick flag in the same call runs BEHIND the combine and reads the combined mask, with the
+ *                bindings of ksched_pick_device on that mask with the pick flag alone; ksched_last_pick and ksched_last_kernel as for a
+ *                combining call; KSCHED_OPT_TIMING brackets the mask kernel only; p == 0 is a no-op, n == 0 leaves the mask alone,
+ *                KSCHED_E_STATE before ksched_set_nodes.
+ * Recipes, beside the one above.  M is the pod batch's HARD mask, built as today; every soft call is one TIER:
+ *   preferred node affinity (preferredDuringSchedulingIgnoredDuringExecution), the term's selector ids in sel_val_ids:
+ *     ksched_eval_device(.., sel: the preferred term, KSCHED_SEL | KSCHED_COMBINE_AND | KSCHED_COMBINE_SOFT,    M, ..)   affinity
+ *     ksched_eval_device(.., sel: the avoided term,   KSCHED_SEL | KSCHED_COMBINE_ANDNOT | KSCHED_COMBINE_SOFT, M, ..)   anti-affinity
+ *     the last call carries the pick flag, or ksched_pick_device(M) follows.
+ *   PreferNoSchedule taints: keep the soft taints as further bits of the one taint set.
+ *     the hard call passes  tolerations | soft_bits  (a soft taint never filters):          KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT, M
+ *     the soft call passes the pod's real tolerations:   KSCHED_TAINT | KSCHED_COMBINE_AND | KSCHED_COMBINE_SOFT, M
+ * Several tiers, applied most important first, are LEXICOGRAPHIC: a later tier only chooses among what the earlier ones left, and the order
+ * of the calls matters.  Kubernetes' weighted sum of preferred terms is not reproduced. */
+#define KSCHED_COMBINE_SOFT 0x2000u /* with KSCHED_COMBINE_AND / _ANDNOT: keep the row as it was where the op would empty it */
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0

@@ -46,6 +46,8 @@ COMBINE_AND = 0x200  # out_feasible = out_feasible & feasible(this call)
 COMBINE_OR = 0x400  # out_feasible = out_feasible | feasible(this call)
 COMBINE_ANDNOT = 0x800  # out_feasible = out_feasible & ~feasible(this call)
 COMBINE_ANY = COMBINE_AND | COMBINE_OR | COMBINE_ANDNOT
+# extension E7: a modifier of COMBINE_AND / COMBINE_ANDNOT (not a member of COMBINE_ANY): a row the op would empty keeps what it held
+COMBINE_SOFT = 0x2000
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

@@ -118,6 +118,19 @@ def combine(flags: int, where: str, accepted: bool, out_feasible=None, out_fit=N
         raise ValueError("out_fit: a COMBINE_* flag excludes WANT_FIT_MASK / out_fit")
 
 
+def soft(flags: int, where: str, accepted: bool) -> None:
+    """The rules of COMBINE_SOFT (include/ksched.h, extension E7) that `combine` does not already state, before any library call: only
+    `eval_device` / `bind_eval_device` accept the modifier (accepted=True), and only together with COMBINE_AND or COMBINE_ANDNOT -- it
+    modifies an op, and COMBINE_OR cannot empty a row.  Everything a combining call needs (`combine`) it needs too.  ValueError naming the
+    argument; a word without the modifier passes."""
+    if not int(flags) & L.COMBINE_SOFT:
+        return
+    if not accepted:
+        raise ValueError(f"flags: {where} takes no COMBINE_SOFT (the mask is combined on the device: Evaluator.eval_device)")
+    if int(flags) & COMBINE not in (L.COMBINE_AND, L.COMBINE_ANDNOT):
+        raise ValueError(f"flags: COMBINE_SOFT modifies COMBINE_AND or COMBINE_ANDNOT, got {int(flags) & COMBINE:#x} beside it")
+
+
 class Batch(NamedTuple):
     """One pod batch as the C ABI takes it; [:8] is the argument run every evaluation entry point shares."""
     p: int

@@ -46,6 +46,7 @@ struct EvalFacts {
     uint32_t opt_grid_cus = 0;
     uint32_t debug = 0;  // KSCHED_OPT_DEBUG (bit 0x400: best fit in one stage)
     CombineOp combine = CombineOp::kNone;  // combine_op(flags) of a combining call (extension E6, mask_combine.hpp); the caller gave out_feasible and no out_fit
+    bool soft = false;  // combine_soft(flags) (extension E7, mask_combine_soft.hpp): with kAnd or kAndNot only
 };
 
 enum class MaskKernel { kNone, kFused, kDirect };
@@ -65,6 +66,7 @@ struct EvalPlan {
     CombineOp combine = CombineOp::kNone;  // not kNone: k_mask_combine folds the scratch mask into the caller's mask, between the mask kernel and the pick
     const char *last_kernel = nullptr;  // ksched_last_kernel after the launch; nullptr = no mask kernel runs, it stays what it was
     const char *last_pick = "none";     // ksched_last_pick
+    bool soft = false;  // with a combine: k_mask_combine_soft in k_mask_combine's place -- a row the fold would empty keeps what it held
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
@@ -111,6 +113,7 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     if (f.combine != CombineOp::kNone) {
         if (kern == KSCHED_KERNEL_FUSED && !can_fused) return plan_unsupported(PlanError::kFusedNotApplicable);
         plan.combine = f.combine;
+        plan.soft = f.soft;
         plan.scratch_mask = true;
         plan.mask = kern == KSCHED_KERNEL_FUSED ? MaskKernel::kFused : MaskKernel::kDirect;
         plan.last_kernel = kern == KSCHED_KERNEL_FUSED ? "fused" : "direct";

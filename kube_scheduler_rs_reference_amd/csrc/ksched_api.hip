@@ -33,6 +33,7 @@
 #include "kernels_pick_spread.hpp"  // (uses kernels_pick_uniform.hpp's helpers)
 #include "kernels_pick_pack.hpp"    // (k_pick_spread's body with the comparison turned round)
 #include "kernels_combine.hpp"      // (extension E6: the scratch mask folded into the caller's mask)
+#include "kernels_combine_soft.hpp" // (extension E7: ... row by row, unless that would leave the row empty)
 #include "mask_alloc.hpp"
 #include "merge_sort_plan.hpp"
 #include "pipe_plan.hpp"
@@ -1187,7 +1188,12 @@ int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
     // a combining call: the scratch mask holds feasible(this call); fold it into the caller's mask, then pick from that mask alone -- the
     // pick is told nothing about the predicates (best fit must not skip candidates by req_mem: under OR and AND-NOT the combined mask
     // need not include the fit)
-    if (hipError_t e = run_mask_combine(plan.combine, r.out_feas, feas, r.p, c->n, c->W, r.pitch, s); e != hipSuccess) return fail_hip(c, e, "run_mask_combine");
+    // (KSCHED_COMBINE_SOFT, extension E7: the same fold, dropped for the rows it would empty)
+    if (plan.soft) {
+        if (hipError_t e = run_mask_combine_soft(plan.combine, r.out_feas, feas, r.p, c->n, c->W, r.pitch, s); e != hipSuccess) return fail_hip(c, e, "run_mask_combine_soft");
+    } else if (hipError_t e = run_mask_combine(plan.combine, r.out_feas, feas, r.p, c->n, c->W, r.pitch, s); e != hipSuccess) {
+        return fail_hip(c, e, "run_mask_combine");
+    }
     if (!plan.pick_from_mask()) return KSCHED_OK;
     EvalRequest pick = r;
     pick.flags = r.flags & KSCHED_PICK_ANY;
@@ -1220,6 +1226,7 @@ EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
     f.opt_grid_cus = c->opt_grid_cus;
     f.debug = c->opt_debug;
     f.combine = combine_op(r.flags);
+    f.soft = combine_soft(r.flags);
     return f;
 }
 
@@ -1307,12 +1314,13 @@ inline bool at_most_one_pick(uint32_t flags) {
 }
 
 // the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed).
-// combine_accepted: the entry point takes the KSCHED_COMBINE_* flags (the two device-pointer evaluations; mask_combine.hpp has the rules)
+// combine_accepted: the entry point takes the KSCHED_COMBINE_* flags (the two device-pointer evaluations; mask_combine.hpp and
+// mask_combine_soft.hpp have the rules)
 int check_eval_args(const EvalRequest &r, bool combine_accepted = false) {
     const uint32_t flags = r.flags;
-    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK | KSCHED_COMBINE_ANY;
+    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK | KSCHED_COMBINE_ANY | KSCHED_COMBINE_SOFT;
     if (flags & ~known) return KSCHED_E_INVAL;
-    if (int rcc = check_combine_args(flags, combine_accepted, r.out_feas != nullptr, r.out_fit != nullptr)) return rcc;
+    if (int rcc = check_soft_args(flags, combine_accepted, r.out_feas != nullptr, r.out_fit != nullptr)) return rcc;
     if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
     if (flags & KSCHED_PICK_DRAWS) {

@@ -4,7 +4,7 @@
 //
 // Host-only on purpose, like eval_plan.hpp, apply_plan.hpp and merge_sort_plan.hpp: no HIP include, no ksched_ctx, so that plain g++
 // compiles it and tests/cpp/combine_plan_tests.cpp pins every rule at its boundary without a GPU.  check_eval_args (ksched_api.hip) asks
-// check_combine_args for every evaluation entry point, the accepting and the refusing ones alike; plan_eval (eval_plan.hpp) carries the op
+// check_combine_args (through mask_combine_soft.hpp's check_soft_args) for every evaluation entry point, the accepting and the refusing ones alike; plan_eval (eval_plan.hpp) carries the op
 // from EvalFacts to EvalPlan; launch_mask launches k_mask_combine (kernels_combine.hpp) with what plan_combine_launch says and takes no
 // decision of its own.
 #pragma once

@@ -205,6 +205,7 @@ class Evaluator:
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4).
         The COMBINE_* flags are refused here (ValueError): masks are combined on the device, by eval_device."""
         M.combine(flags, "Evaluator.eval", accepted=False)
+        M.soft(flags, "Evaluator.eval", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
         p, W = b.p, self.W
         res = EvalResult()
@@ -233,7 +234,11 @@ class Evaluator:
         from earlier calls and becomes out_feasible & / | / & ~ feasible(this call), on the device -- words [0, W) of every row, bits at or
         beyond n of the last word zero afterwards.  A pick flag in the same call picks from the COMBINED mask (as pick_device on it with the
         pick flag alone).  Needs `out_feasible`; excludes WANT_FIT_MASK / `out_fit`.  So `zone In {a, b} and disk NotIn {hdd} and fit` is
-        four calls on one mask: SEL (zone = a), SEL | COMBINE_OR (zone = b), SEL | COMBINE_ANDNOT (disk = hdd), FIT | COMBINE_AND | a pick."""
+        four calls on one mask: SEL (zone = a), SEL | COMBINE_OR (zone = b), SEL | COMBINE_ANDNOT (disk = hdd), FIT | COMBINE_AND | a pick.
+        COMBINE_SOFT (extension E7) beside COMBINE_AND or COMBINE_ANDNOT makes the call a soft constraint: per pod row the mask narrows to
+        out_feasible & feasible(this call) (or & ~) only where that leaves the pod a node; a row it would empty keeps what it held (bits at
+        or beyond n zero either way).  A preferred affinity term is SEL | COMBINE_AND | COMBINE_SOFT on the hard mask; tiers applied most
+        important first are lexicographic."""
         calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                              [out_feasible], out_fit, [out_binding], stream)
         self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
@@ -244,6 +249,7 @@ class Evaluator:
         import torch
         for m in masks:
             M.combine(flags, "Evaluator.eval_device", accepted=True, out_feasible=m, out_fit=out_fit)
+        M.soft(flags, "Evaluator.eval_device", accepted=True)
         b = M.device_batch(self.device, self.n_keys, *cols, flags)
         (*pm, pr), pitch = M.mask_rows(b.p, self.W, self.device, *[("out_feasible", m) for m in masks], ("out_fit", out_fit))
         po = [M.device_ptr(o, "out_binding", "i32", (b.p,), self.device) for o in outs]
@@ -424,6 +430,7 @@ class Pipe:
         """(the batch, [(mask, pitch, binding) per slot]) as ksched_pipe_submit takes them, checked"""
         ev = self.ev
         M.combine(flags, "Pipe.submit", accepted=False)
+        M.soft(flags, "Pipe.submit", accepted=False)
         b = M.device_batch(ev.device, ev.n_keys, *cols, flags)
         per_slot = []
         for m, o in zip(masks, bindings):
@@ -434,7 +441,7 @@ class Pipe:
     def submit(self, slot: int, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags: int, mask, binding):
         """torch CUDA tensors (see Evaluator.eval_device); `mask` is a [p, W] (possibly pitched) view, `binding` int32 [p].  flags carry one
         of PICK_SAMPLED, PICK_BESTFIT, PICK_UNIFORM, PICK_SPREAD, PICK_PACK (the uniform, the spread and the pack pick read the mask: their slot runs in the split mode, ordered by events).
-        The COMBINE_* flags are refused (ValueError): a slot's mask belongs to the slot; combine with Evaluator.eval_device."""
+        The COMBINE_* flags, COMBINE_SOFT included, are refused (ValueError): a slot's mask belongs to the slot; combine with Evaluator.eval_device."""
         b, per_slot = self._marshal((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags, [mask], [binding])
         self.ev._check(self._lib.ksched_pipe_submit(self._h, slot, *b[:8], *per_slot[0]), "ksched_pipe_submit")
 

@@ -48,6 +48,7 @@ pub const KSCHED_COMBINE_AND: u32 = 0x200; // extension E6, ksched_eval_device*:
 pub const KSCHED_COMBINE_OR: u32 = 0x400; // out_feasible = out_feasible | feasible(this call)
 pub const KSCHED_COMBINE_ANDNOT: u32 = 0x800; // out_feasible = out_feasible & !feasible(this call)
 pub const KSCHED_COMBINE_ANY: u32 = KSCHED_COMBINE_AND | KSCHED_COMBINE_OR | KSCHED_COMBINE_ANDNOT; // at most one per call
+pub const KSCHED_COMBINE_SOFT: u32 = 0x2000; // extension E7, with KSCHED_COMBINE_AND / _ANDNOT: a row the op would empty keeps what it held
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
 pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
@@ -307,6 +308,7 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_COMBINE_OR", KSCHED_COMBINE_OR as i64),
         ("KSCHED_COMBINE_ANDNOT", KSCHED_COMBINE_ANDNOT as i64),
         ("KSCHED_COMBINE_ANY", KSCHED_COMBINE_ANY as i64),
+        ("KSCHED_COMBINE_SOFT", KSCHED_COMBINE_SOFT as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
         ("KSCHED_APPLY_WHILE_FIT", KSCHED_APPLY_WHILE_FIT as i64),

@@ -10,7 +10,8 @@ it changes with any edit, host code included.  Exit status 0: identical; 1: they
 
 When the files differ the functions are compared one by one as well, by name, with the function's ordinal masked in its local labels
 (.LBB<n>_<block>, .Lfunc_end<n>, "Header=BB<n>_<block>" comments): a change that ADDS a kernel moves the ordinals of the functions
-emitted after it and nothing else of them.  The last line then names the functions added, removed and changed; exit status 2 when none
+emitted after it and nothing else of them -- except the blanks in front of a label's trailing comment, which the assembly printer pads to a
+column and which therefore move when an ordinal gains a digit (.LBB99_4 -> .LBB100_4); they are squeezed to one.  The last line then names the functions added, removed and changed; exit status 2 when none
 was removed or changed (every function of REV is in the work tree with the same instructions), 1 otherwise.
 
 What it is for: a refactor of the host side (the dispatch, the ABI functions) must leave every kernel as it was; with this
@@ -50,7 +51,8 @@ def functions(lines):
         elif "; -- End function" in ln:
             cur = None
         elif cur is not None:
-            cur.append(re.sub(r"(\.LBB|\bBB|\.Lfunc_begin|\.Lfunc_end|\.Ltmp)\d+(?=_|\b)", r"\1N", ln))
+            ln = re.sub(r"(\.LBB|\bBB|\.Lfunc_begin|\.Lfunc_end|\.Ltmp)\d+(?=_|\b)", r"\1N", ln)
+            cur.append(re.sub(r"^(\.LBBN_\d+:)[ \t]+;", r"\1 ;", ln))
     return out
 
 
