@@ -22,6 +22,16 @@ on deferrals, on pods admitted behind a deferred one and on what the two other r
 case_sizes behind two applies and two updates with no host wait, once outgrowing the admit scratch behind a queued admit, on odd steps with
 negative requests (sizes_step); in case_large first, 600 000 pods with segments of more than 10 000 (large_plan).  sizes_step and
 large_plan need no device and assert their input conditions before anything runs on one; tests/test_apply_paths_host.py calls them too.
+
+The pack pick (KSCHED_PICK_PACK) reads the same two columns as the spread pick through a kernel of its own (k_pick_pack): check_matrix
+runs it wherever it runs the spread pick, on the same draws, against tests/pack_ref.py, and walk_single counts the pack bindings a stale
+column would change (stale_pack_bindings) beside the spread ones.  The combining calls (KSCHED_COMBINE_AND / _OR / _ANDNOT and
+KSCHED_COMBINE_SOFT) evaluate into the ctx's scratch mask and fold it into the caller's: check_matrix runs them per predicate set and
+kernel choice as chains of ksched_eval_device calls on one mask, compared after every link with tests/combine_ref.py / tests/soft_ref.py
+on the oracle's masks -- two hard chains and a soft chain whose last link carries each pick in turn (soft_chain_restated,
+last_link_binding) -- and case_sizes enqueues the soft chain with PICK_PACK behind its queued applies and updates, no host wait, while
+the scratch mask shrinks in need to one node and regrows.  Their input conditions (assert_pack_input_condition,
+assert_chain_input_conditions) are asserted from the restatements, so also without a GPU.  No expected value comes from the device.
 """
 from __future__ import annotations
 
@@ -31,11 +41,14 @@ import sys
 import numpy as np
 import torch
 
-from kube_scheduler_rs_reference_amd import (FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator,
-                                             KschedError, _lib, synth, unpack_mask)
+from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, PICK_BESTFIT, PICK_PACK, PICK_SAMPLED, PICK_SPREAD,
+                                             PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth, unpack_mask)
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact  # (the two other rules on an admit round's inputs: admit_round_conditions)
+from tests import combine_ref, soft_ref
 from tests.admit_ref import admitted_behind_deferred, apply_exact, longest_segment
+from tests.knife_edges import sampled as sampled_from_bits  # ksched_pick's rule for PICK_SAMPLED on a [p, n] table of bits
+from tests.pack_ref import pack_pick_listed
 from tests.spread_ref import spread_pick_blocks
 from tests.test_gpu_apply_bindings import random_bindings
 from tests.uniform_ref import uniform_pick_blocks
@@ -154,6 +167,102 @@ def stale_spread_bindings(S, cpu, mem, cpu_before, mem_before):
     return int((spread_restated(S, feas, cpu, mem, 5) != spread_restated(S, feas, cpu_before, mem_before, 5)).sum())
 
 
+def pack_restated(S, feas, cpu, mem, d, cells=1 << 24):
+    """KSCHED_PICK_PACK restated (tests/pack_ref.py, the listed route, in blocks of pods) for the first d columns of the snapshot's draw
+    table -- the spread legs' table: with the same candidates the two picks differ only in the ranking"""
+    draws, N = S["smpS"][:, :d], S["N"]
+    step = max(1, cells // max(N, 1))
+    return np.concatenate([pack_pick_listed(feas[lo:lo + step], draws[lo:lo + step], N, mem, cpu) for lo in range(0, feas.shape[0], step)])
+
+
+def assert_pack_input_condition(S, feas, bind_k5, bind_p5, what):
+    """the pack legs cannot pass vacuously: 35 % of the pods or more are bound by the d = 5 restatement to another node than their candidate
+    0 (an evaluation that ranked nothing fails), and 35 % or more to another node than the spread restatement binds them to (one that
+    ranked the other way fails)"""
+    cand0 = uniform_pick_blocks(feas, S["smpS"][:, 0], S["N"])
+    other, unlike = float(((bind_k5 >= 0) & (bind_k5 != cand0)).mean()), float((bind_k5 != bind_p5).mean())
+    msg = (f"{what}: the pack pick (d = 5) binds {100 * other:.1f} % of the pods to another node than their candidate 0, "
+           f"{100 * unlike:.1f} % to another node than the spread pick")
+    print(msg)
+    assert other >= 0.35 and unlike >= 0.35, msg
+
+
+PACK_LEG_DRAWS = (5, 2, 64)  # the d of the matrix's pack legs
+
+
+def stale_pack_bindings(S, cpu, mem, cpu_before, mem_before):
+    """stale_spread_bindings for the pack restatement (k_pick_pack reads the same two columns through loads of its own), per d of the
+    matrix's pack legs: -> {d: the number of pods bound differently on the columns from before the apply}"""
+    feas = oracle_mask(S, cpu, mem, S["preds"][0])
+    return {d: int((pack_restated(S, feas, cpu, mem, d) != pack_restated(S, feas, cpu_before, mem_before, d)).sum()) for d in PACK_LEG_DRAWS}
+
+
+# ---- the combining calls (KSCHED_COMBINE_AND / _OR / _ANDNOT, KSCHED_COMBINE_SOFT): what a chain must leave, from the restatements alone
+ROLLS = (1, 2)  # how many pods the selector table is rolled by for soft tier 1 and tier 2: pod i prefers what pod i + k selects
+LAST_LINKS = ("pack", "spread", "uniform", "sampled", "bestfit")  # the pick in a soft chain's last link, in turn over the chains of a process
+_chains = [0]  # soft chains run so far in this process
+
+
+def rolled_sel(S, k):
+    return np.ascontiguousarray(np.roll(S["sel"], k, axis=1))
+
+
+def last_link_binding(S, mask, cpu, mem, pick):
+    """what a pick in a combining call binds: ksched_pick's rule on the COMBINED mask with the pick flag alone (include/ksched.h, "with a
+    pick") -- the ranked picks' restatements with d = 5 (the uniform pick on its own draws); the sampled pick the first of the pod's five
+    samples whose bit is set; best fit, not told that the mask includes the fit, the set bit with the smallest (avail_mem, avail_cpu,
+    node): for one pod the residual orders as `available` does"""
+    N = S["N"]
+    if pick == "pack":
+        return pack_restated(S, mask, cpu, mem, 5)
+    if pick == "spread":
+        return spread_restated(S, mask, cpu, mem, 5)
+    if pick == "uniform":
+        return uniform_pick_blocks(mask, S["smpU"][:, 0], N)
+    bits = unpack_mask(mask, N)
+    if pick == "sampled":
+        return sampled_from_bits(bits, S["smp5"])
+    assert pick == "bestfit", pick
+    order = np.lexsort((np.arange(N), cpu, mem))  # ascending (mem, cpu, node)
+    f = bits[:, order]
+    return np.where(f.any(axis=1), order[f.argmax(axis=1)], -1).astype(np.int32)
+
+
+def soft_chain_restated(S, cpu, mem, feas):
+    """the soft chain on the hard mask `feas`: tier 1 = SEL | COMBINE_AND | COMBINE_SOFT with the selector table rolled by ROLLS[0] pods,
+    tier 2 = SEL | COMBINE_ANDNOT | COMBINE_SOFT with it rolled by ROLLS[1].  -> dict(sel=(the two tables), t1, t2 = tests/soft_ref.py on the
+    oracle's SEL-only masks of the rolled tables, dec=(soft_ref.decisions of either tier))"""
+    N = S["N"]
+    sels = tuple(rolled_sel(S, k) for k in ROLLS)
+    m1, m2 = (capi.eval_encoded(cpu, mem, S["lab"], None, S["rc"], S["rm"], s, None, None, SEL)[0] for s in sels)
+    t1 = soft_ref.soft_combine(feas, m1, COMBINE_AND, N)
+    t2 = soft_ref.soft_combine(t1, m2, COMBINE_ANDNOT, N)
+    return dict(sel=sels, t1=t1, t2=t2, dec=(soft_ref.decisions(feas, m1, COMBINE_AND, N), soft_ref.decisions(t1, m2, COMBINE_ANDNOT, N)))
+
+
+def assert_chain_input_conditions(S, feas, fit, cpu, mem, soft, what):
+    """the combining legs cannot pass vacuously: either soft tier narrows 20 % of the rows or more, is dropped for 10 % or more, finds 1 %
+    or more empty and changes 10 % or more; the pack pick on the tier-2 mask binds 15 % of the pods or more differently from the pack pick
+    on the hard mask (a pick in the last link that read the scratch mask or the hard mask fails); and, with `fit` (None: a soft chain
+    alone), in the hard chain (b) 30 % of the rows or more of fit & ~feas have a set bit (an AND-NOT that complemented the wrong operand,
+    or did nothing, fails)"""
+    for tier, (old, new, dec) in enumerate(((feas, soft["t1"], soft["dec"][0]), (soft["t1"], soft["t2"], soft["dec"][1])), 1):
+        nar, dro, emp = (float((dec == k).mean()) for k in (soft_ref.NARROWED, soft_ref.DROPPED, soft_ref.EMPTY))
+        chg = float((old != new).any(axis=1).mean())
+        msg = (f"{what}: soft tier {tier} (the selectors of pod i + {ROLLS[tier - 1]}) narrows {100 * nar:.1f} % of the rows, is dropped for "
+               f"{100 * dro:.1f} %, finds {100 * emp:.1f} % empty and changes {100 * chg:.1f} %")
+        print(msg)
+        assert nar >= 0.20 and dro >= 0.10 and emp >= 0.01 and chg >= 0.10, msg
+    moved = float((pack_restated(S, soft["t2"], cpu, mem, 5) != pack_restated(S, feas, cpu, mem, 5)).mean())
+    msg = f"{what}: the pack pick (d = 5) on the tier-2 mask binds {100 * moved:.1f} % of the pods differently from the hard mask's"
+    rejected = 1.0
+    if fit is not None:
+        rejected = float(combine_ref.combine(fit, feas, COMBINE_ANDNOT, S["N"]).any(axis=1).mean())
+        msg += f"; {100 * rejected:.1f} % of the rows of fit & ~feasible have a set bit"
+    print(msg)
+    assert moved >= 0.15 and rejected >= 0.30, msg
+
+
 def explain_pairs(rng, P, N, n_pairs=4000):
     return rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
 
@@ -168,7 +277,10 @@ def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sample
             feas = oracle_mask(S, cpu, mem, preds)
         if input_condition:
             assert_input_condition(feas, S["N"], w)
-            assert_spread_input_condition(S, feas, spread_restated(S, feas, cpu, mem, 5), w)
+            bind_p5 = spread_restated(S, feas, cpu, mem, 5)
+            assert_spread_input_condition(S, feas, bind_p5, w)
+            assert_pack_input_condition(S, feas, pack_restated(S, feas, cpu, mem, 5), bind_p5, w)
+            assert_chain_input_conditions(S, feas, oracle_mask(S, cpu, mem, FIT), cpu, mem, soft_chain_restated(S, cpu, mem, feas), w)
         if k == 0 and hand_on == "sampled":
             out_b = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"] if preds & TAINT else None, S["rc"], S["rm"], S["sel"],
                                       S["tol"] if preds & TAINT else None, S["smp5"], preds | PICK_SAMPLED, want_mask=False)[2]
@@ -189,6 +301,13 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
     d = 5 beside the mask on every kernel choice; d = 2, bindings only, through host and device pointers; ksched_eval_device with d = 5
     beside a mask (last_pick == "spread" in both forms); ksched_pick from the oracle's host mask with d = 64; and once per matrix d = 1,
     which must be the restatement's uniform pick for column 0 of the same draws.
+    The pack legs mirror them one for one (tests/pack_ref.py, the same draws, last_pick == "pack").
+    The combining calls, per predicate set and kernel choice, on ksched_eval_device into a mask filled with ones (padding bits too),
+    packed under one kernel choice and pitched under the next, the mask compared after every link: (a) FIT, then the other predicates
+    with COMBINE_AND == the oracle's mask; (b) FIT, the predicates with COMBINE_ANDNOT == combine_ref (fit & ~feasible), the predicates
+    with COMBINE_OR == the oracle's fit mask again; and the soft chain of soft_chain_restated on the hard mask, whose last link carries a
+    pick (LAST_LINKS in turn; names "chain-<pick>" go into `seen`) compared with last_link_binding on the expected tier-2 mask and cpu / mem.
+    The new legs compare; they hand nothing on.
     -> the device bindings, under the first predicate set, of the pick `hand_on` names: "sampled", "uniform" or "spread" (a real
     evaluation's bindings for the next apply); None with hand_on=None"""
     P, N = S["P"], S["N"]
@@ -205,9 +324,58 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
         # KSCHED_PICK_SPREAD restated, on the oracle's mask and the columns this matrix was called with
         bind_p5, bind_p2, bind_p64 = (spread_restated(S, feas, cpu, mem, d) for d in (5, 2, 64))
         smpS5, smpS2 = np.ascontiguousarray(S["smpS"][:, :5]), np.ascontiguousarray(S["smpS"][:, :2])
+        # KSCHED_PICK_PACK restated likewise, and the soft chain on the oracle's mask
+        bind_k5, bind_k2, bind_k64 = (pack_restated(S, feas, cpu, mem, d) for d in (5, 2, 64))
+        soft = soft_chain_restated(S, cpu, mem, feas)
         if input_condition:
             assert_input_condition(feas, N, w)
             assert_spread_input_condition(S, feas, bind_p5, w)
+            assert_pack_input_condition(S, feas, bind_k5, bind_p5, w)
+            assert_chain_input_conditions(S, feas, fit, cpu, mem, soft, w)
+        rc_t, rm_t, sel_t = t(rc, np.int64), t(rm, np.int64), t(sel, np.int32)
+        tol_t = t(tol, np.int64) if tol is not None else None
+        soft_sel_t = [t(x, np.int32) for x in soft["sel"]]
+        link_smp = {"pack": (PICK_PACK, t(smpS5, np.int32)), "spread": (PICK_SPREAD, t(smpS5, np.int32)), "uniform": (PICK_UNIFORM, t(S["smpU"], np.int32)),
+                    "sampled": (PICK_SAMPLED, t(S["smp5"], np.int32)), "bestfit": (PICK_BESTFIT, None)}
+
+        def link(M, flags, want, label, sel_=None, smp=None, out=None):
+            """one link of a chain into M, the mask compared at once"""
+            ev.eval_device(rc_t, rm_t, (sel_t if sel_ is None else sel_) if flags & SEL else None, tol_t if flags & TAINT else None, smp, flags,
+                           out_feasible=M, out_binding=out)
+            name = ev.last_pick
+            torch.cuda.synchronize()
+            got = M.contiguous().cpu().numpy().view(np.uint64)
+            assert np.array_equal(got, want), f"{w} {label}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ (kernel {ev.last_kernel})"
+            return name
+
+        def chains(k, n_kernel):
+            """the two hard chains and the soft chain under the kernel choice set"""
+            def ones():
+                M = ev.alloc_mask(P, pitched=n_kernel % 2 == 1)
+                M.fill_(-1)
+                return M
+            lay = "pitched" if n_kernel % 2 else "packed"
+            M = ones()
+            link(M, FIT, fit, f"{k} {lay} chain (a) FIT")
+            link(M, (preds & ~FIT) | COMBINE_AND, feas, f"{k} {lay} chain (a) AND")
+            M = ones()
+            link(M, FIT, fit, f"{k} {lay} chain (b) FIT")
+            link(M, preds | COMBINE_ANDNOT, combine_ref.combine(fit, feas, COMBINE_ANDNOT, N), f"{k} {lay} chain (b) AND-NOT")
+            link(M, preds | COMBINE_OR, fit, f"{k} {lay} chain (b) OR")
+            assert ev.last_pick == "none", f"{w} {k}: a combining call without a pick ran one: {ev.last_pick}"
+            pick = LAST_LINKS[_chains[0] % len(LAST_LINKS)]
+            _chains[0] += 1
+            flag, smp = link_smp[pick]
+            M, out = ones(), torch.full((P + 4,), -7, dtype=torch.int32, device=DEV)
+            link(M, preds, feas, f"{k} {lay} soft chain, hard mask")
+            link(M, SEL | COMBINE_AND | COMBINE_SOFT, soft["t1"], f"{k} {lay} soft chain, tier 1", soft_sel_t[0])
+            name = link(M, SEL | COMBINE_ANDNOT | COMBINE_SOFT | flag, soft["t2"], f"{k} {lay} soft chain, tier 2 with the {pick} pick", soft_sel_t[1], smp, out[:P])
+            assert name == {"pack": "pack", "spread": "spread", "uniform": "uniform"}.get(pick, "from-mask"), f"{w} {k}: the {pick} pick of a combining call ran as {name}"
+            b = out.cpu().numpy()
+            want_b = last_link_binding(S, soft["t2"], cpu, mem, pick)
+            assert np.array_equal(b[:P], want_b), f"{w} {k} {lay} soft chain: {int((b[:P] != want_b).sum())} bindings of the {pick} pick in the last link differ"
+            assert (b[P:] == -7).all(), f"{w} {k} soft chain: the pick wrote past the batch"
+            seen.add(f"chain-{pick}")
 
         def run(flags, smp=None, want_mask=True, expect_b=None, label=""):
             r = ev.eval(rc, rm, sel, tol, smp, flags, want_mask=want_mask)
@@ -220,7 +388,7 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
             seen.add(ev.last_pick)
 
         kernels = ("auto", "direct") if reduced else ("fused", "direct", "auto")
-        for kernel in kernels:
+        for n_kernel, kernel in enumerate(kernels):
             ev.set_kernel(kernel)
             if kernel == "fused" and not S["indexed"]:
                 try:
@@ -248,22 +416,25 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
             run(preds | PICK_UNIFORM, S["smpU"], expect_b=bind_u, label=f"{k} uniform")
             run(preds | PICK_SPREAD, smpS5, expect_b=bind_p5, label=f"{k} spread d=5")
             assert ev.last_pick == "spread", f"{w} {k}: a spread pick beside the mask ran as {ev.last_pick}"
+            run(preds | PICK_PACK, smpS5, expect_b=bind_k5, label=f"{k} pack d=5")
+            assert ev.last_pick == "pack", f"{w} {k}: a pack pick beside the mask ran as {ev.last_pick}"
+            chains(k, n_kernel)
         ev.set_kernel("auto")
         # bindings only: the sampled pick is its own launch ("select"), best fit reads no mask
         run(preds | PICK_SAMPLED, S["smp5"], want_mask=False, expect_b=bind_s, label="sampled, bindings only")
         run(preds | PICK_BESTFIT, want_mask=False, expect_b=bind_b, label="best fit, bindings only")
         run(preds | PICK_UNIFORM, S["smpU"], want_mask=False, expect_b=bind_u, label="uniform, bindings only")  # the mask goes to the ctx's scratch
         run(preds | PICK_SPREAD, smpS2, want_mask=False, expect_b=bind_p2, label="spread d=2, bindings only")  # likewise
+        run(preds | PICK_PACK, smpS2, want_mask=False, expect_b=bind_k2, label="pack d=2, bindings only")  # likewise
         if n_set == 0:  # d = 1 is the uniform pick: the restatement's own (uniform_ref), for column 0 of the spread draws
             run(preds | PICK_SPREAD, np.ascontiguousarray(S["smpS"][:, :1]), expect_b=uniform_pick_blocks(feas, S["smpS"][:, 0], N), label="spread d=1")
+            run(preds | PICK_PACK, np.ascontiguousarray(S["smpS"][:, :1]), expect_b=uniform_pick_blocks(feas, S["smpS"][:, 0], N), label="pack d=1")
         if not reduced:  # the mask-reading picks
             ev.set_option(_lib.OPT_PICK_FROM_MASK, 1)
             run(preds | PICK_SAMPLED, S["smp5"], expect_b=bind_s, label="sampled from the mask")
             run(preds | PICK_BESTFIT, expect_b=bind_b, label="best fit from the mask")
             ev.set_option(_lib.OPT_PICK_FROM_MASK, 0)
         # device buffers, with and without a mask
-        rc_t, rm_t, sel_t = t(rc, np.int64), t(rm, np.int64), t(sel, np.int32)
-        tol_t = t(tol, np.int64) if tol is not None else None
         smp_t = t(S["smp5"], np.int32)
         m = torch.empty((P, ev.W), dtype=torch.int64, device=DEV)
         bs, bs0, bb = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(3))
@@ -295,9 +466,19 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
         seen.add(ev.last_pick)
         torch.cuda.synchronize()
         assert np.array_equal(mp.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask beside the spread pick"
+        mk = torch.empty((P, ev.W), dtype=torch.int64, device=DEV)
+        bk, bk0 = (torch.full((P,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smps5_t, preds | PICK_PACK, out_feasible=mk, out_binding=bk)
+        assert ev.last_pick == "pack", f"{w}: a pack pick beside the mask ran as {ev.last_pick}"
+        ev.eval_device(rc_t, rm_t, sel_t, tol_t, smps2_t, preds | PICK_PACK, out_binding=bk0)
+        assert ev.last_pick == "pack", f"{w}: a bindings-only pack pick ran as {ev.last_pick}"
+        seen.add(ev.last_pick)
+        torch.cuda.synchronize()
+        assert np.array_equal(mk.cpu().numpy().view(np.uint64), feas), f"{w}: eval_device mask beside the pack pick"
         for got, want, lbl in ((bs, bind_s, "sampled"), (bs0, bind_s, "sampled, bindings only"), (bb, bind_b, "best fit"),
                                (bu, bind_u, "uniform"), (bu0, bind_u, "uniform, bindings only"),
-                               (bp, bind_p5, "spread d=5"), (bp0, bind_p2, "spread d=2, bindings only")):
+                               (bp, bind_p5, "spread d=5"), (bp0, bind_p2, "spread d=2, bindings only"),
+                               (bk, bind_k5, "pack d=5"), (bk0, bind_k2, "pack d=2, bindings only")):
             assert np.array_equal(got.cpu().numpy(), want), f"{w}: eval_device {lbl} bindings"
         if out_b is None and hand_on is not None:
             out_b = {"sampled": bs, "uniform": bu, "spread": bp}[hand_on].cpu().numpy()
@@ -307,6 +488,7 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
             f"{w}: ksched_pick best fit"
         assert np.array_equal(ev.pick(feas, PICK_UNIFORM, samples=S["smpU"]), bind_u), f"{w}: ksched_pick uniform"
         assert np.array_equal(ev.pick(feas, PICK_SPREAD, samples=S["smpS"]), bind_p64), f"{w}: ksched_pick spread d=64"
+        assert np.array_equal(ev.pick(feas, PICK_PACK, samples=S["smpS"]), bind_k64), f"{w}: ksched_pick pack d=64"
         # per-pair reasons
         n_pairs = 4000
         # `rng` is drawn from HERE ONLY in this function, once per predicate set: restated_matrix, the walk without a device, advances it by
@@ -398,7 +580,8 @@ def walk_single(spec, begin, matrix, apply):
     apply moves the columns its own next evaluation ranks by.  Asserted here, so with or without a device: each of the three hands on
     in both classes of node counts (below 1025, and from 1025 on, where the input conditions hold); and at every node count from 1025
     on, summed over its applies of real bindings, the d = 5 spread restatement after the apply differs between the columns after and the
-    columns before it for at least one pod (stale_spread_bindings) -- a stale column cannot pass.
+    columns before it for at least one pod (stale_spread_bindings) -- a stale column cannot pass; the same count is printed and asserted
+    for the pack restatement (stale_pack_bindings), whose kernel reads the columns through loads of its own.
     The admit round takes real bindings without ok at odd i (from PICKS[i % 3]: a hand-on outside the turn above, which it does not
     move) and random ones with ok at even i; every round before it draws, binds and applies what it did without it.  Its conditions
     are admit_round_conditions."""
@@ -424,7 +607,7 @@ def walk_single(spec, begin, matrix, apply):
             return handed[N >= 1025][-1]
 
         bind = matrix(S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on(0), input_condition=N >= 1025)
-        applied = stale = 0
+        applied = stale = stale_pack = 0
         for r in range(rounds):
             src, flags, use_ok = FORMS[(i + r) % len(FORMS)]
             if src == "random":
@@ -436,12 +619,15 @@ def walk_single(spec, begin, matrix, apply):
             cpu, mem, st = apply(S, cpu, mem, b, ok if use_ok else None, flags, what)
             applied += int((st == _lib.APPLY_APPLIED).sum())
             if src == "real":
-                k = stale_spread_bindings(S, cpu, mem, cpu0, mem0)
-                print(f"{what}: the columns from before this apply would change {k} of {P} spread bindings (d = 5)")
+                k, kp = stale_spread_bindings(S, cpu, mem, cpu0, mem0), stale_pack_bindings(S, cpu, mem, cpu0, mem0)
+                print(f"{what}: the columns from before this apply would change {k} of {P} spread bindings (d = 5) and, for d = "
+                      f"{', '.join(map(str, kp))}, {', '.join(map(str, kp.values()))} pack bindings")
                 stale += k
+                stale_pack += sum(kp.values())
             bind = matrix(S, cpu, mem, what, rng, hand_on=hand_on(r + 1))
         assert applied > 0, f"{kind} N={N}: no pod was applied"
         assert stale > 0 or N < 1025, f"{kind} N={N}: no spread binding depends on what this node count's applies changed"
+        assert stale_pack > 0 or N < 1025, f"{kind} N={N}: no pack binding depends on what this node count's applies changed"
         # the admit round
         src = "real" if admit_real else "random"
         b, ok = (bind, None) if admit_real else random_bindings(rng, N, P)
@@ -475,13 +661,14 @@ def case_single(spec):
     want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask", "uniform", "spread"},
             "many-keys": {"select", "fused", "bestfit-rows", "from-mask", "uniform", "spread"},
             "list-key": {"select", "bestfit-rows", "from-mask", "uniform", "spread"},
-            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind]
+            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind] | {"pack"} | {f"chain-{p}" for p in LAST_LINKS}
     assert want <= seen, f"{kind}: picks reached {sorted(seen)}, missing {sorted(want - seen)}"
     print(f"{kind}: picks reached {sorted(seen)}")
     ev.close()
     ref.close()
 
 
+SIZES_PREDS = FIT | SEL | TAINT  # what case_sizes evaluates with
 SIZES_PODS, SIZES_BIG = 3000, 4  # pods per batch of case_sizes; the second admit at 4097 nodes has SIZES_BIG times as many
 
 
@@ -495,7 +682,10 @@ def sizes_step(step, N):
     the admit scratch got with apply 2, so both of its ping-pong sets are reallocated behind a queued admit.
     Asserted here, from the restatement: every WHILE_FIT apply admits a pod (but on one node, which the second update may leave with
     nothing), at 300 nodes and at 1 it defers 100 pods or more, on the odd steps a pod or more is admitted only into what a pod before
-    it gave back, and the big one has APPLIED, DEFERRED, UNBOUND and BAD_NODE."""
+    it gave back, and the big one has APPLIED, DEFERRED, UNBOUND and BAD_NODE.
+    chain: what the soft chain of check_matrix leaves on the columns after all of it -- sel (the rolled selector tables), links (the mask
+    after the hard call, tier 1 and tier 2) and bind (tests/pack_ref.py, d = 5, on the tier-2 mask and those columns); from 1025 nodes on
+    with assert_chain_input_conditions' floors on the tiers and on the bindings the tiers move."""
     P, WF = SIZES_PODS, _lib.APPLY_WHILE_FIT
     S = snapshot("taints", N, P, 0xC0 + step)
     cpu, mem = S["cpu"], S["mem"]
@@ -542,14 +732,21 @@ def sizes_step(step, N):
             assert counts[_lib.APPLY_APPLIED] >= 1, what
         if k in updates and updates[k][0].size:
             cpu[updates[k][0]], mem[updates[k][0]] = updates[k][1], updates[k][2]
-    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem)
+    # the soft chain behind all of it (case_sizes enqueues it with no host wait): the hard mask, two soft tiers, PICK_PACK in the last link
+    feas = oracle_mask(S, cpu, mem, SIZES_PREDS)
+    soft = soft_chain_restated(S, cpu, mem, feas)
+    if N >= 1025:
+        assert_chain_input_conditions(S, feas, None, cpu, mem, soft, f"{what} chain")
+    chain = dict(sel=soft["sel"], links=(feas, soft["t1"], soft["t2"]), bind=pack_restated(S, soft["t2"], cpu, mem, 5))
+    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem, chain=chain)
 
 
 def case_sizes(spec):
     """one ctx through snapshots of 50 000 -> 300 -> 4097 -> 1 -> 60 000 nodes (the last one past the apply scratch's size): after each
     ksched_set_nodes what sizes_step lists -- an apply, an update of nodes in the tiles it touched, a second apply, a second update, an
-    apply with WHILE_FIT (at 4097 nodes a second, four times as long, straight behind it) -- enqueued with no host wait in between; then
-    the statuses of every apply, the columns, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused
+    apply with WHILE_FIT (at 4097 nodes a second, four times as long, straight behind it) -- and behind those the soft chain of
+    check_matrix with PICK_PACK in its last link (the mask copied on the stream after every link), enqueued with no host wait in between;
+    then the chain's masks and bindings against sizes_step's, the statuses of every apply, the columns, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused
     evaluation with the sampled pick in its waves form"""
     plans = [sizes_step(step, N) for step, N in enumerate(spec["nodes"])]  # (every input condition, before anything runs on the device)
     assert sum(len(q["applies"]) == 4 for q in plans) == 1, "no step reallocates the admit scratch"
@@ -559,6 +756,14 @@ def case_sizes(spec):
         S = q["S"]
         set_nodes(ev, S, S["cpu"], S["mem"])
         sts, keep = [], []
+        # the chain's operands and outputs, on the device before anything is enqueued (packed rows on even steps, pitched on odd ones)
+        P = S["P"]
+        M = ev.alloc_mask(P, pitched=step % 2 == 1)
+        out = torch.full((P + 4,), -7, dtype=torch.int32, device=DEV)
+        pods = (t(S["rc"], np.int64), t(S["rm"], np.int64))
+        sels = [t(x, np.int32) for x in (S["sel"],) + q["chain"]["sel"]]
+        tol_t, smp_t = t(S["tol"], np.int64), t(np.ascontiguousarray(S["smpS"][:, :5]), np.int32)
+        torch.cuda.synchronize()
         for k, (b, ok, flags, rc, rm, _) in enumerate(q["applies"]):
             st = torch.full((len(b),), -7, dtype=torch.int32, device=DEV)
             args = (t(b, np.int32), t(rc, np.int64), t(rm, np.int64), None if ok is None else t(ok, np.uint8))
@@ -567,8 +772,24 @@ def case_sizes(spec):
             sts.append(st)
             if k in q["updates"] and q["updates"][k][0].size:
                 ev.update_nodes(*q["updates"][k])
+        # straight behind the last admit (and update), no host wait: the ctx's scratch mask, which every combining call evaluates into, has
+        # to fit this snapshot by then -- it shrinks in need down to one node and regrows to 60 000 behind queued work
+        M.fill_(-1)
+        ev.eval_device(*pods, sels[0], tol_t, None, SIZES_PREDS, out_feasible=M)
+        links = [M.clone()]
+        ev.eval_device(*pods, sels[1], None, None, SEL | COMBINE_AND | COMBINE_SOFT, out_feasible=M)
+        links.append(M.clone())
+        ev.eval_device(*pods, sels[2], None, smp_t, SEL | COMBINE_ANDNOT | COMBINE_SOFT | PICK_PACK, out_feasible=M, out_binding=out[:P])
+        assert ev.last_pick == "pack", ev.last_pick
+        links.append(M)
         torch.cuda.synchronize()
         what = f"step {step} N={N}"
+        for name, got, want in zip(("the hard mask", "tier 1", "tier 2"), links, q["chain"]["links"]):
+            got = got.contiguous().cpu().numpy().view(np.uint64)
+            assert np.array_equal(got, want), f"{what}: the chain behind the queued changes, {name}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"
+        b = out.cpu().numpy()
+        assert np.array_equal(b[:P], q["chain"]["bind"]) and (b[P:] == -7).all(), \
+            f"{what}: the chain's pack bindings: {int((b[:P] != q['chain']['bind']).sum())} differ"
         for k, (st, a) in enumerate(zip(sts, q["applies"])):
             assert np.array_equal(st.cpu().numpy(), a[5]), f"{what}: statuses of apply {k} (flags={a[2]})"
         cpu, mem = q["cpu"], q["mem"]
@@ -576,7 +797,7 @@ def case_sizes(spec):
         assert np.array_equal(got[0], cpu) and np.array_equal(got[1], mem), f"{what}: columns"
         set_nodes(ref, S, cpu, mem)
         assert ev.index_checksum() == ref.index_checksum(), f"{what}: index checksum"
-        preds = FIT | SEL | TAINT
+        preds = SIZES_PREDS
         feas, _, bind = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"], S["rc"], S["rm"], S["sel"], S["tol"], S["smp5"], preds | PICK_SAMPLED)
         for kernel, fp in (("direct", 1), ("fused", 2)):
             ev.set_kernel(kernel)

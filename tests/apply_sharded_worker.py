@@ -429,7 +429,9 @@ def case_paths(spec):
     """after each sharded apply every replica runs the reduced evaluation matrix of tests/apply_paths_worker.py against the oracle on the
     restated columns: the "select" pick, the riding pick in its waves form, ksched_explain, the direct kernel and (list key) best fit from
     the key's lists -- the paths that read the node records the gathered commit writes -- and the uniform and the spread pick; the spread
-    pick ranks by the columns that commit has just written on every replica (walk_paths)"""
+    pick ranks by the columns that commit has just written on every replica (walk_paths); and check_matrix's pack legs (the pack pick reads
+    the same columns through a kernel of its own) and combining chains (KSCHED_COMBINE_*, KSCHED_COMBINE_SOFT: each evaluates into the
+    replica's scratch mask), against tests/pack_ref.py, tests/combine_ref.py and tests/soft_ref.py"""
     from tests.apply_paths_worker import check_matrix
     n = spec["n"]
     seen = set()
@@ -449,7 +451,9 @@ def case_paths(spec):
 
     k = walk_paths(spec, begin, lambda q, S, cpu, mem, what, rng, **kw: check_matrix(R[0].evs[q], S, cpu, mem, seen, what, rng, reduced=True, **kw),
                    apply, lambda: R[0].close())
-    assert {"select", "fused", "bestfit-rows", "uniform", "spread"} <= seen, f"picks reached {sorted(seen)}"
+    from tests.apply_paths_worker import LAST_LINKS
+    # (check_matrix's pack legs and combining chains run on every replica too: the soft chain's last link takes each pick in turn)
+    assert {"select", "fused", "bestfit-rows", "uniform", "spread", "pack"} | {f"chain-{p}" for p in LAST_LINKS} <= seen, f"picks reached {sorted(seen)}"
     print(f"{k} sharded applies, picks reached {sorted(seen)}")
 
 

@@ -1,4 +1,4 @@
-"""The input conditions of the spread legs in tests/apply_paths_worker.py, without a GPU: the worker's own sequences (walk_single, and
+"""The input conditions of the spread, the pack and the combining legs in tests/apply_paths_worker.py, without a GPU: the worker's own sequences (walk_single, and
 walk_paths of tests/apply_sharded_worker.py) walked with the oracle, tests/uniform_ref.py, tests/spread_ref.py and the exact-integer apply
 in place of the device, over the specs the GPU tests pass.  The walks assert what the GPU cases assert of their inputs: (a) before any
 apply at 1025 nodes or more, the d = 5 spread restatement binds 35 % of the pods or more to another node than their candidate 0 (and the
@@ -6,7 +6,12 @@ uniform legs' condition holds); (b) at every such node count the columns from be
 spread binding, summed over its rounds; and the sampled, the uniform and the spread pick each hand their bindings on.  A change of the
 shapes, the seeds or the rotation that would let the GPU legs pass with stale columns fails here first.  Likewise the admit legs
 (KSCHED_APPLY_WHILE_FIT): the admit round of every node count with admit_round_conditions' floors, the sizes and the large case's plans
-(sizes_step, large_plan) and the pipe's admit -- an admit that defers nobody where a floor says it must fails here, not on a GPU."""
+(sizes_step, large_plan) and the pipe's admit -- an admit that defers nobody where a floor says it must fails here, not on a GPU.
+Likewise the pack legs (KSCHED_PICK_PACK) and the combining chains (KSCHED_COMBINE_*, KSCHED_COMBINE_SOFT): at 1025 nodes or more the d = 5
+pack restatement binds 35 % of the pods or more to another node than their candidate 0 and than the spread restatement; either soft tier
+narrows 20 %, is dropped for 10 %, finds 1 % empty and changes 10 % of the rows or more; the pack pick on the tier-2 mask differs from the
+hard mask's for 15 % of the pods or more; fit & ~feasible has a set bit in 30 % of the rows or more; a stale column would change a pack
+binding of the matrix's legs; and the sizes plan's chain meets the same floors at its three large snapshots."""
 import numpy as np
 import pytest
 
@@ -32,6 +37,14 @@ def test_single_ctx_matrix_inputs(kind, capsys):
     out = capsys.readouterr().out
     print(out)
     assert out.count("the spread pick (d = 5) binds") >= 3 and out.count("would change") >= 8
+    # the pack and the combining legs' conditions, per predicate set of the three node counts from 1025 on: asserted by restated_matrix
+    # (assert_pack_input_condition, assert_chain_input_conditions), printed in words of their own; and the stale-column count of the pack
+    # restatement beside the spread one's, asserted by walk_single
+    sets = 3 * len(W.snapshot(kind, 63, 8, 1)["preds"])
+    assert out.count("the pack pick (d = 5) binds") == sets and out.count("to another node than the spread pick") == sets
+    assert [out.count(f"soft tier {tier} (") for tier in (1, 2)] == [sets, sets]
+    assert out.count("on the tier-2 mask binds") == sets and out.count("of the rows of fit & ~feasible have a set bit") == sets
+    assert out.count("pack bindings") == out.count("would change")
     # the admit round of every node count, with the floors walk_single sets on it (admit_round_conditions), printed in words of its own
     assert [out.count(f"{kind} N={N} admit round (") > 0 for N in NODES] == [True] * len(NODES)
     assert out.count("statuses (applied, unbound, not ok, deferred, overflow, bad node)") == len(NODES)
@@ -49,6 +62,14 @@ def test_sizes_case_inputs(capsys):
     out = capsys.readouterr().out
     print(out)
     assert out.count(": admit of ") == len(SIZES["nodes"]) + 1
+    # the soft chain behind the queued changes: expected masks and bindings for every step, the floors where a floor can hold
+    big_steps = sum(N >= 1025 for N in SIZES["nodes"])
+    assert big_steps == 3 and [out.count(f"chain: soft tier {tier} (") for tier in (1, 2)] == [big_steps, big_steps]
+    assert out.count("chain: the pack pick (d = 5) on the tier-2 mask binds") == big_steps
+    for q in plans:
+        S, c = q["S"], q["chain"]
+        assert [m.shape for m in c["links"]] == [(S["P"], (S["N"] + 63) // 64)] * 3 and c["bind"].shape == (S["P"],)
+        assert ((c["bind"] >= 0) == c["links"][2].any(axis=1)).all() and (c["links"][2].any(axis=1) == c["links"][0].any(axis=1)).all()
 
 
 def test_large_case_inputs(capsys):
@@ -80,6 +101,9 @@ def test_replicated_matrix_inputs(n, capsys):
     out = capsys.readouterr().out
     print(out)
     assert k == 12 and out.count("would change") == 6
+    sets = 2 * (2 + 1)  # the two node counts from 1025 on, the taints snapshot's two predicate sets and the list-key snapshot's one
+    assert out.count("the pack pick (d = 5) binds") == out.count("the spread pick (d = 5) binds") == sets
+    assert out.count("soft tier 1 (") == out.count("soft tier 2 (") == out.count("on the tier-2 mask binds") == out.count("the pack pick (d = 5) binds")
     assert {p for big, p in handed if big} == set(W.PICKS), handed  # at 1025 nodes or more: all three within one run
     # (below 1025 a run has two snapshots: the three picks over the runs with n = 1, 2, 3)
     assert len({p for big, p in handed if not big}) == 2, handed

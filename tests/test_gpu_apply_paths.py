@@ -19,6 +19,16 @@ and 50 000; in the sizes case an admit behind two applies and two updates with n
 admit scratch; in the large case an admit of 600 000 pods before the four other flag sets.  Their input conditions (deferrals, pods
 admitted behind a deferred one, columns unlike what flags = 0 and FIRST_PER_NODE leave) are asserted from the restatement in the
 worker before the device is compared, and without a GPU by tests/test_apply_paths_host.py.
+The pack pick (KSCHED_PICK_PACK) has the spread pick's legs one for one, against tests/pack_ref.py on the same draws: it reads the same two
+columns through a kernel of its own, so its stale-column count is printed and asserted beside the spread pick's.  The combining calls
+(KSCHED_COMBINE_AND / _OR / _ANDNOT, KSCHED_COMBINE_SOFT) run per predicate set and kernel choice as chains of ksched_eval_device calls on
+one mask, packed under one kernel choice and pitched under the next, filled with ones beforehand and compared after every link with
+tests/combine_ref.py / tests/soft_ref.py on the oracle's masks: FIT then the other predicates with AND (== the one call); FIT, AND-NOT, OR
+(== the fit mask again); and a soft chain -- the hard mask, two soft tiers on the selector table rolled by one and by two pods -- whose last
+link carries the pack, spread, uniform, sampled and best-fit pick in turn.  So every combining call evaluates into the ctx's scratch mask
+after an apply, on list-key, ten-key and unindexed snapshots; the sizes case enqueues the soft chain with PICK_PACK behind its queued
+applies and updates with no host wait, while that scratch mask shrinks in need to one node and regrows to 60 000.  Floors on what the tiers
+narrow, drop, find empty and change, on the bindings they move and on fit & ~feasible are asserted from the restatements first.
 """
 import json
 import os
@@ -50,7 +60,11 @@ def test_every_path_after_an_apply(built, kind):
     both, with and without ok, on the previous evaluation's device bindings and on random ones; then the admit round, [apply with
     WHILE_FIT -> the matrix], on real bindings at 63 and 4097 nodes and on random ones at the others"""
     out = run("single", dict(SINGLE, kind=kind))
-    assert "'spread'" in out.rsplit("picks reached", 1)[-1], "the spread pick is not among the picks reached"
+    reached = out.rsplit("picks reached", 1)[-1]
+    assert "'spread'" in reached, "the spread pick is not among the picks reached"
+    assert "'pack'" in reached, "the pack pick is not among the picks reached"
+    for pick in ("pack", "spread", "uniform", "sampled", "bestfit"):
+        assert f"'chain-{pick}'" in reached, f"no soft chain carried the {pick} pick in its last link"
     for N in NODES:
         assert f"{kind} N={N} admit round (" in out, f"no admit round at {N} nodes"
 
@@ -61,6 +75,7 @@ def test_snapshot_sizes_and_updates_between_applies_on_one_ctx(built):
     second one of four times the pods (the admit scratch reallocated behind a queued admit), no host wait"""
     out = run("sizes", SIZES)
     assert out.count(": admit of ") == len(SIZES["nodes"]) + 1
+    assert out.count("chain: the pack pick (d = 5) on the tier-2 mask binds") == 3  # the chain's floors, at the three snapshots from 1025 nodes on
 
 
 def test_a_batch_longer_than_one_stride_of_the_pod_kernels(built):

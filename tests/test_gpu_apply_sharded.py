@@ -2,7 +2,10 @@
 ctx's ksched_apply_bindings_device over the concatenated rows ends (columns, index checksum, statuses).
 
 n > 1 ranks run as n ctxs on the one GPU in ONE child process (tests/apply_sharded_worker.py) against the test build of the library with
-the RCCL stand-in; n = 1 runs the shipped library over the real RCCL.  Only the per-process test starts two children at once."""
+the RCCL stand-in; n = 1 runs the shipped library over the real RCCL.  Only the per-process test starts two children at once.
+The "paths" case runs tests/apply_paths_worker.check_matrix in its reduced form on every replica after each sharded apply: with it the
+pack pick's legs (tests/pack_ref.py on the columns the gathered commit wrote) and the combining chains (KSCHED_COMBINE_AND / _OR / _ANDNOT
+and KSCHED_COMBINE_SOFT against tests/combine_ref.py / tests/soft_ref.py, a pick in the soft chain's last link)."""
 import json
 import os
 import subprocess

@@ -4,8 +4,12 @@ and on-device applies of the previous evaluation's bindings between evaluations,
 oracle; and at every step the uniform pick against tests/uniform_ref.py on the oracle's mask, and the spread pick (d of 1, 2, 3, 5, 8, 33,
 64; both kernels, with and without the mask) against tests/spread_ref.py on the oracle's mask and on the columns the step's updates and
 applies must have left -- the one pick that goes wrong, for a few pods, when a column is stale.  With the hooks the spread pick also goes
-through the multi-device sequence, a sharded apply of its gathered bindings and the sequence again on the replicas' columns.  (240 s runs of
-the same tool: profiles/uniform_pick_standing_checks.txt, profiles/spread_pick_standing_checks.txt.)"""
+through the multi-device sequence, a sharded apply of its gathered bindings and the sequence again on the replicas' columns.  Likewise at
+every step the pack pick (the same draws and d; tests/pack_ref.py) and one combining chain of 2 to 4 ksched_eval_device calls on one mask --
+random predicate subsets and ops, KSCHED_COMBINE_SOFT at random, odd pitches and bases with sentinel words around the view, a random pick
+in the last link -- against tests/combine_ref.py / tests/soft_ref.py on the oracle's per-link masks; with the hooks the pack pick takes the
+spread pick's multi-device route and the chain runs on every replica after the sharded apply.  (240 s runs of the same tool:
+profiles/uniform_pick_standing_checks.txt, profiles/spread_pick_standing_checks.txt, profiles/combine_pack_standing_checks.txt.)"""
 import os
 import re
 import subprocess
@@ -27,6 +31,12 @@ def assert_new_tallies(out):
     assert tally(out, "uniform") > 0, "no evaluation ran the uniform pick"
     assert tally(out, "uniform-ranked") > 0, "no uniform pick chose among two or more feasible nodes"
     assert tally(out, "labels") > 0, "no case updated node labels between evaluations"
+    assert tally(out, "pack") > 0, "no evaluation ran the pack pick"
+    assert tally(out, "pack-ranked") > 0, "no pack pick bound a pod to another node than its candidate 0"
+    assert tally(out, "combine") > 0, "no combining chain ran"
+    assert tally(out, "soft-narrowed") > 0, "no soft link narrowed a row"
+    assert tally(out, "soft-dropped") > 0, "no soft link was dropped for a row"
+    assert tally(out, "soft-empty") > 0, "no soft link met an empty row"
 
 
 def test_fuzz_parity_short(built):
@@ -56,3 +66,5 @@ def test_fuzz_parity_short_with_the_multi_device_sequence(built):
     assert re.search(r"'gathered-over-\d': [1-9]", r.stdout), "no sampled or best-fit case went through the multi-device sequence"
     assert re.search(r"'uniform-gathered-over-\d': [1-9]", r.stdout), "no uniform pick went through the multi-device sequence"
     assert re.search(r"'spread-gathered-over-\d': [1-9]", r.stdout), "no spread pick went through the multi-device sequence"
+    assert re.search(r"'pack-gathered-over-\d': [1-9]", r.stdout), "no pack pick went through the multi-device sequence"
+    assert tally(r.stdout, "combine-on-replicas") > 0, "no combining chain ran on the replicas after a sharded apply"

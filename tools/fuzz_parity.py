@@ -12,6 +12,14 @@ mask -- against tests/spread_ref.py on the oracle's mask AND on the step's resta
 apply has just written, so a column left stale shows as a few wrong bindings; through ksched_pick, the row shards and the multi-device sequence too,
 the latter followed by a sharded apply of the gathered bindings over the same replicas and a second sequence on the columns that apply left (no
 ksched_set_nodes in between); the wide cases take k_pick_spread's two-pass form, with draws that arrive out of chunk order,
+the pack pick (KSCHED_PICK_PACK) at every step of every case too -- the same table of draws, d drawn from the same list, both kernels, with and without
+the mask -- against tests/pack_ref.py on the oracle's mask and the step's restated columns; with the hooks through the spread pick's multi-device
+route (the sequence, a sharded apply of the gathered bindings, the sequence again),
+one combining chain at every step (KSCHED_COMBINE_AND / _OR / _ANDNOT, KSCHED_COMBINE_SOFT at random on AND and AND-NOT): 2 to 4 calls of
+ksched_eval_device on one mask, each with a random non-empty predicate subset, into a view at pitch W, W + 1 or ksched_mask_pitch(n) that starts at
+an even or an odd word of a buffer of sentinel words, the mask copied on the stream after every link, a random pick or none in the last link --
+against tests/combine_ref.py / tests/soft_ref.py on the oracle's per-link masks and the pick restatements on the final mask; with the hooks the same
+chain on every replica after the pack pick's sharded apply, on the columns it left,
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
 ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts; about one apply in four with KSCHED_APPLY_WHILE_FIT, against
 tests/admit_ref.py -- the sharded entry point must then refuse with KSCHED_E_UNSUPPORTED and leave every replica as it was; tallies
@@ -22,14 +30,16 @@ ksched_comm_create_local, ksched_eval_begin on every replica, ksched_gather_buff
 A case's decisions come from three generators seeded from the case seed: `r` draws what the tool has always drawn, in the same order (a
 case that keeps its node count is the case an older log names by that seed), `r2` every decision added with the uniform pick (the uniform legs,
 the wider snapshots, the label updates), in its order, and `r3` every decision added since (the spread legs): a seed names the case it named
-before the spread legs, with those legs added.
+before the spread legs, with those legs added; `r4` every decision of the pack legs and the combining chains, likewise.
 The summary's tallies: pick launches by name ('uniform': evaluations whose last_pick was "uniform"; 'uniform-ranked': those in which some
 pod had two or more feasible nodes, so the rank arithmetic ran), 'labels' (label updates), 'apply', 'host-masks', 'sharded-halves',
 'gathered-over-n' (and their 'uniform-' and 'spread-' twins), 'summarize'; 'spread': evaluations whose last_pick was "spread" (one per
 ksched_eval; a multi-device sequence counts as one, whatever the number of replicas, as it does for 'uniform');
 'spread-ranked': those in which some pod was bound to another node than its candidate 0; 'spread-tied': those in which some pod's winner was
 decided by cpu or by the node index (two distinct candidates with the same, largest memory); 'spread-gathered-moved': second sequences in which
-the columns from before the gathered apply would have given some pod another binding.
+the columns from before the gathered apply would have given some pod another binding; 'pack', 'pack-ranked', 'pack-gathered-over-N' and
+'pack-gathered-moved' as their spread twins; 'combine': chains run on `ev`; 'soft-narrowed', 'soft-dropped', 'soft-empty': chains in which a
+soft link narrowed a row, was dropped for one, met an empty one; 'combine-on-replicas': cases whose chain ran on every replica.
 usage: python tools/fuzz_parity.py [seconds] [seed]       prints one line per failure and a summary; exit code 1 on any failure"""
 import os, sys, time
 import numpy as np
@@ -43,6 +53,10 @@ from tests.admit_ref import apply_while_fit_exact  # KSCHED_APPLY_WHILE_FIT rest
 from tests.test_gpu_node_labels import apply_rows  # the columns after ksched_update_node_labels: a node listed twice takes its last row
 from tests.uniform_ref import uniform_pick  # KSCHED_PICK_UNIFORM restated
 from tests.spread_ref import best_of, spread_candidates_listed  # KSCHED_PICK_SPREAD restated: every draw's candidate, the best of them
+from tests.pack_ref import tightest_of  # KSCHED_PICK_PACK restated: the tightest of the same candidates
+from tests import combine_ref, soft_ref  # KSCHED_COMBINE_AND / _OR / _ANDNOT and KSCHED_COMBINE_SOFT restated
+from tests.knife_edges import sampled as sampled_from_bits  # ksched_pick's rule for PICK_SAMPLED on a [p, n] table of bits
+from tests.test_gpu_combine_soft import old_mask_for  # an old mask whose neighbouring rows narrow, are dropped, are empty and are random
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -80,6 +94,127 @@ def spread_restated(mask, draws, n, mem, cpu, cells=1 << 24):
             top = m == m.max(axis=1, keepdims=True)
             tied = bool((np.where(top, v, n).min(axis=1) != np.where(top, v, -1).max(axis=1)).any())
     return np.concatenate(out), ranked, tied
+
+
+def pack_restated(mask, draws, n, mem, cpu, cells=1 << 24):
+    """tests/pack_ref.py in blocks of pods -> (the bindings, whether some pod is bound to another node than its candidate 0, False)"""
+    step = max(1, cells // max(int(n), 1))
+    out, ranked = [], False
+    for lo in range(0, mask.shape[0], step):
+        cand = spread_candidates_listed(mask[lo:lo + step], draws[lo:lo + step], n)
+        b = tightest_of(cand, mem, cpu)
+        out.append(b)
+        ranked = ranked or bool(((b >= 0) & (b != cand[:, 0])).any())
+    return np.concatenate(out), ranked, False
+
+
+CHAIN_PODS = 2000  # a combining chain takes the batch's first pods, at most so many (the oracle runs once per link)
+SENTINEL, GUARD_ROWS = 0x5A5A5A5A5A5A5A5A, 2
+
+
+def draw_chain(g, N, P, K, nt):
+    """one combining chain of 2 to 4 links: per link a non-empty predicate subset, an op and (on AND and AND-NOT, at random)
+    KSCHED_COMBINE_SOFT; the view's pitch (W, W + 1 or ksched_mask_pitch(n)) and whether it starts at an even or an odd word of its
+    buffer; the pick of the last link, or none; the kernel choice"""
+    W = (N + 63) // 64
+    avail = [L.FIT] + ([L.SEL] if K else []) + ([L.TAINT] if nt else [])
+    links = []
+    for _ in range(int(g.integers(2, 5))):
+        sub = 0
+        while not sub:
+            sub = sum(f for f in avail if g.random() < 0.5)
+        op = int(g.choice(combine_ref.OPS))
+        links.append((sub, op, soft_ref.SOFT if op != combine_ref.OR and g.random() < 0.5 else 0))
+    return dict(links=links, pitch=int(g.choice([W, W + 1, int(ev._lib.ksched_mask_pitch(N))])), offset=int(g.integers(0, 2)),
+                pick=int(g.choice([0, L.PICK_SAMPLED, L.PICK_BESTFIT, L.PICK_UNIFORM, L.PICK_SPREAD, L.PICK_PACK])),
+                kernel=str(g.choice(["auto", "direct"])), seed=int(g.integers(0, 1 << 31)))
+
+
+def run_chain(e, cs, where, spec, cpu, mem, lab, taints, N, P, K, nt, rc, rm, sel, tol, smp, smp_u, smp_s):
+    """the chain `spec` on evaluator `e`, whose snapshot should hold cpu / mem: every link a ksched_eval_device into one [p, W] view with
+    sentinel words around it, the mask copied on the stream after every link.  Expected: tests/combine_ref.py / tests/soft_ref.py on the
+    oracle's per-link masks (on cpu / mem), from an old mask whose rows narrow, are dropped and are empty under the first link
+    (old_mask_for), and for the last link's pick the restatement of ksched_pick's rule on the final mask.  -> the number of failures"""
+    import torch
+    dev = torch.device("cuda:0")
+    p, W = min(P, CHAIN_PODS), (N + 63) // 64
+    pitch, offset, pick = spec["pitch"], spec["offset"], spec["pick"]
+    if pick == L.PICK_BESTFIT and any(a.size and (int(a.min()) < -(1 << 61) or int(a.max()) > (1 << 61)) for a in (cpu, mem, rc, rm)):
+        pick = L.PICK_PACK  # (best fit ranks by the residual, which orders as `available` only while the subtraction stays inside int64)
+    rc_p, rm_p = np.ascontiguousarray(rc[:p]), np.ascontiguousarray(rm[:p])
+    sel_p = np.ascontiguousarray(sel[:, :p]) if K else None
+    tol_p = np.ascontiguousarray(tol[:p]) if nt else None
+    new = [capi.eval_encoded(cpu, mem, lab, taints if (sub & L.TAINT) else None, rc_p, rm_p, sel_p, tol_p if (sub & L.TAINT) else None, None, sub)[0]
+           for sub, _, _ in spec["links"]]
+    op0 = spec["links"][0][1]
+    old = old_mask_for(new[0], combine_ref.AND if op0 == combine_ref.OR else op0, N, np.random.default_rng(spec["seed"]))
+    want, cur, seen_dec = [], old, set()
+    for (sub, op, soft), m in zip(spec["links"], new):
+        if soft:
+            seen_dec.update(np.unique(soft_ref.decisions(cur, m, op, N)).tolist())
+            cur = soft_ref.soft_combine(cur, m, op, N)
+        else:
+            cur = combine_ref.combine(cur, m, op, N)
+        want.append(cur)
+    draws = {L.PICK_SAMPLED: smp, L.PICK_UNIFORM: smp_u, L.PICK_SPREAD: smp_s, L.PICK_PACK: smp_s}.get(pick)
+    draws = None if draws is None else np.ascontiguousarray(draws[:p])
+    if pick == L.PICK_UNIFORM:
+        want_b = uniform_pick_blocks(cur, draws[:, 0], N)
+    elif pick == L.PICK_SPREAD:
+        want_b = spread_restated(cur, draws, N, mem, cpu)[0]
+    elif pick == L.PICK_PACK:
+        want_b = pack_restated(cur, draws, N, mem, cpu)[0]
+    elif pick:
+        from kube_scheduler_rs_reference_amd.evaluator import unpack_mask
+        bits = unpack_mask(cur, N)
+        if pick == L.PICK_SAMPLED:
+            want_b = sampled_from_bits(bits, draws)
+        else:  # best fit, not told that the mask includes the fit: the set bit with the smallest (avail_mem, avail_cpu, node)
+            order = np.lexsort((np.arange(N), cpu, mem))
+            f = bits[:, order]
+            want_b = np.where(f.any(axis=1), order[f.argmax(axis=1)], -1).astype(np.int32)
+    rows = p + GUARD_ROWS
+    host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
+    host[offset:offset + rows * pitch].reshape(rows, pitch)[:p, :W] = old
+    buf = torch.from_numpy(host.view(np.int64)).to(dev)
+    view = buf[offset:offset + rows * pitch].view(rows, pitch)[:p, :W]
+    td = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+    rc_t, rm_t, sel_t, tol_t, smp_t = td(rc_p, np.int64), td(rm_p, np.int64), td(sel_p, np.int32), td(tol_p, np.int64), td(draws, np.int32)
+    out = torch.full((p + 4,), -7, dtype=torch.int32, device=dev)
+    e.set_kernel(spec["kernel"])
+    copies = []
+    for i, (sub, op, soft) in enumerate(spec["links"]):
+        last = i == len(spec["links"]) - 1
+        e.eval_device(rc_t, rm_t, sel_t if (sub & L.SEL) else None, tol_t if (sub & L.TAINT) else None, smp_t if last and pick else None,
+                      sub | op | soft | (pick if last else 0), out_feasible=view, out_binding=out[:p] if last and pick else None)
+        copies.append(buf.clone())
+    torch.cuda.synchronize()
+    e.set_kernel("auto")
+    bad = 0
+    what = (f"case seed {cs} {where}: N={N} p={p} K={K} nt={nt} links={[(hex(a), combine_ref.NAMES[b] + ('-soft' if c else '')) for a, b, c in spec['links']]} "
+            f"pitch={pitch} offset={offset} pick={pick:#x} kernel={spec['kernel']}")
+    for i, (c, w) in enumerate(zip(copies, want)):
+        got = c.cpu().numpy().view(np.uint64)
+        body = got[offset:offset + rows * pitch].reshape(rows, pitch)
+        pad = body[:p, W:]
+        if not np.array_equal(body[:p, :W], w):
+            bad += 1
+            print(f"FAIL combine {what}: the mask after link {i} ({int((body[:p, :W] != w).any(axis=1).sum())} rows differ)", flush=True)
+            break
+        if not (((pad == SENTINEL) | (pad == 0)).all() and (body[p:] == SENTINEL).all() and (got[:offset] == SENTINEL).all() and got[-1] == SENTINEL):
+            bad += 1
+            print(f"FAIL combine {what}: link {i} wrote outside words [0, W) of the view's rows", flush=True)
+            break
+    if pick:
+        b = out.cpu().numpy()
+        if not (np.array_equal(b[:p], want_b) and (b[p:] == -7).all()):
+            bad += 1
+            print(f"FAIL combine {what}: the last link's pick ({int((b[:p] != want_b).sum())} bindings differ)", flush=True)
+    picks["combine"] = picks.get("combine", 0) + 1
+    for k, name in ((soft_ref.NARROWED, "soft-narrowed"), (soft_ref.DROPPED, "soft-dropped"), (soft_ref.EMPTY, "soft-empty")):
+        if k in seen_dec:
+            picks[name] = picks.get(name, 0) + 1
+    return bad
 
 
 def clique(n_sh):
@@ -306,16 +441,21 @@ def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, fla
     return bad, {e.last_pick for e in ran}
 
 
-def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, ranked, tied):
+def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, ranked, tied,
+                    name="spread", restate=None, chain=None):
     """the multi-device sequence with the spread pick, twice: on freshly set replicas; then -- after ksched_apply_bindings_sharded_local of
     the gathered bindings over the same replicas, ragged cuts, no ksched_set_nodes -- on the columns that apply left on every replica: the
     oracle's mask and the restatement on the exact-integer apply of those bindings.  A replica whose columns the gathered commit left behind
-    ranks its rows by old values.  Every replica's pick must run as "spread".  `ev`, cpu and mem are not touched.  -> the number of failures"""
+    ranks its rows by old values.  Every replica's pick must run as "spread".  `ev`, cpu and mem are not touched.  -> the number of failures.
+    name="pack", restate=pack_restated: the same for the pack pick (flags carry PICK_PACK).  chain=(spec, smp, smp_u, smp_s): after the
+    sharded apply and the second sequence that combining chain runs on every replica, against the columns the apply left."""
     import torch
+    restate = restate or spread_restated
+    tag, pick_flag = name + "-", {"spread": L.PICK_SPREAD, "pack": L.PICK_PACK}[name]
     n_sh = int(g.choice([2, 3, 4]))
     for e in clique(n_sh)[0]:
         e.set_nodes(cpu, mem, lab, taints)
-    bad, names = gathered_sequence(g, cs, "spread-", cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, n_sh=n_sh)
+    bad, names = gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, n_sh=n_sh)
     tally = [(names, ranked, tied)]
     af = int(g.choice([0, L.APPLY_FIRST_PER_NODE])) | (L.APPLY_RELEASE if g.random() < 0.2 else 0)
     ncpu, nmem, want_st = apply_bindings_exact(cpu, mem, want[2], rc, rm, None, af)
@@ -324,25 +464,30 @@ def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc,
     bt, rct, rmt = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (want[2], rc, rm))
     cut = [0] + sorted(int(x) for x in g.integers(0, P + 1, n_sh - 1)) + [P]
     sts = sharded_apply(reps, comms, cut, bt, rct, rmt, None, af, wait=False)  # no host wait before the replicas evaluate again
-    picks[f"spread-gathered-apply-over-{n_sh}"] = picks.get(f"spread-gathered-apply-over-{n_sh}", 0) + 1
-    want2 = capi.eval_encoded(ncpu, nmem, lab, taints if (preds & L.TAINT) else None, rc, rm, sel, tol if (preds & L.TAINT) else None, None, flags & ~L.PICK_SPREAD)
-    b2, ranked2, tied2 = spread_restated(want2[0], smp, N, nmem, ncpu)
-    bad2, names2 = gathered_sequence(g, cs, "spread-", ncpu, nmem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, (want2[0], want2[1], b2), n_sh=n_sh)
+    picks[f"{tag}gathered-apply-over-{n_sh}"] = picks.get(f"{tag}gathered-apply-over-{n_sh}", 0) + 1
+    want2 = capi.eval_encoded(ncpu, nmem, lab, taints if (preds & L.TAINT) else None, rc, rm, sel, tol if (preds & L.TAINT) else None, None, flags & ~pick_flag)
+    b2, ranked2, tied2 = restate(want2[0], smp, N, nmem, ncpu)
+    bad2, names2 = gathered_sequence(g, cs, tag, ncpu, nmem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, (want2[0], want2[1], b2), n_sh=n_sh)
     tally.append((names2, ranked2, tied2))
     torch.cuda.synchronize()
     if not np.array_equal(np.concatenate([s_.cpu().numpy() for s_ in sts]), want_st):
         bad += 1
-        print(f"FAIL spread gathered apply case seed {cs}: N={N} P={P} flags={af} cuts={cut}: statuses", flush=True)
-    if not np.array_equal(b2, spread_restated(want2[0], smp, N, mem, cpu)[0]):  # (the old columns would show)
-        picks["spread-gathered-moved"] = picks.get("spread-gathered-moved", 0) + 1
+        print(f"FAIL {name} gathered apply case seed {cs}: N={N} P={P} flags={af} cuts={cut}: statuses", flush=True)
+    if not np.array_equal(b2, restate(want2[0], smp, N, mem, cpu)[0]):  # (the old columns would show)
+        picks[f"{tag}gathered-moved"] = picks.get(f"{tag}gathered-moved", 0) + 1
     for nm, rk, td in tally:
-        if nm == {"spread"}:
-            picks["spread"] = picks.get("spread", 0) + len(nm)
-            picks["spread-ranked"] = picks.get("spread-ranked", 0) + int(rk) * len(nm)
-            picks["spread-tied"] = picks.get("spread-tied", 0) + int(td) * len(nm)
+        if nm == {name}:
+            picks[name] = picks.get(name, 0) + len(nm)
+            picks[f"{tag}ranked"] = picks.get(f"{tag}ranked", 0) + int(rk) * len(nm)
+            if name == "spread":
+                picks["spread-tied"] = picks.get("spread-tied", 0) + int(td) * len(nm)
         else:
             bad += 1
-            print(f"FAIL spread multi-device sequence case seed {cs}: N={N} P={P} d={d}: the replicas' picks ran as {sorted(nm)}", flush=True)
+            print(f"FAIL {name} multi-device sequence case seed {cs}: N={N} P={P} d={d}: the replicas' picks ran as {sorted(nm)}", flush=True)
+    if chain is not None:  # the step's combining chain on every replica, on the columns the sharded apply left there
+        for q, e in enumerate(reps):
+            bad += run_chain(e, cs, f"replica {q} of {n_sh} after a sharded apply", chain[0], ncpu, nmem, lab, taints, N, P, K, nt, rc, rm, sel, tol, *chain[1:])
+        picks["combine-on-replicas"] = picks.get("combine-on-replicas", 0) + 1
     return bad + bad2
 
 
@@ -356,6 +501,7 @@ while time.time() < t_end:
     r = np.random.default_rng(cs)
     r2 = np.random.default_rng([cs, 0x0E3])  # every decision added after the sequence of `r` was fixed (see the docstring)
     r3 = np.random.default_rng([cs, 0x5E4])  # every decision added after the sequence of `r2` was fixed: the spread legs
+    r4 = np.random.default_rng([cs, 0xC0B])  # every decision added after the sequence of `r3` was fixed: the pack legs and the combining chains
     wide = int(r2.choice([8192, 8193, 12_500])) if r2.random() < 0.1 else 0  # rows of more than 128 words: k_pick_uniform's two-pass form (8192: the longest one-pass row)
     N = int(r.choice([1, 2, 63, 64, 65, 300, 1023, 1024, 1025, 2500, 4097, 6000]))
     P = int(r.choice([1, 7, 64, 65, 500, 1500, 3000]))
@@ -513,6 +659,29 @@ while time.time() < t_end:
                     else:  # a KSCHED_PICK_SPREAD request has one launch form
                         fails += 1
                         print(f"FAIL spread case seed {cs}: N={N} P={P} K={K} flags={fl_s:#x} d={d_s} kernel={kernel} mask={want_mask} step={step}: the pick ran as {ev.last_pick!r}", flush=True)
+            # the pack pick on the same snapshot and the same table of draws, d drawn anew from the spread pick's list: both kernels, with and
+            # without the mask -- against tests/pack_ref.py on the oracle's mask and on cpu / mem as the updates and applies above left them
+            d_k = int(r4.choice([1, 2, 3, 5, 8, 33, 64]))
+            smp_k = np.ascontiguousarray(smp_s64[:, :d_k])
+            want_k, ranked_k, _ = pack_restated(want[0], smp_k, N, mem, cpu)
+            fl_k = preds | L.PICK_PACK
+            for kernel in ("auto", "direct"):
+                ev.set_kernel(kernel)
+                for want_mask in (True, False):
+                    got = ev.eval(rc, rm, sel if K else None, tol if (preds & L.TAINT) else None, smp_k, fl_k, want_mask=want_mask)
+                    if not ((not want_mask or np.array_equal(got.feasible, want[0])) and np.array_equal(got.binding, want_k)):
+                        fails += 1
+                        print(f"FAIL pack case seed {cs}: N={N} P={P} K={K} cards={cards} nt={nt} flags={fl_k:#x} d={d_k} kernel={kernel}/{ev.last_kernel} pick={ev.last_pick} mask={want_mask} step={step}"
+                              f" ({int((got.binding != want_k).sum())} bindings differ)", flush=True)
+                    if ev.last_pick == "pack":
+                        picks["pack"] = picks.get("pack", 0) + 1
+                        picks["pack-ranked"] = picks.get("pack-ranked", 0) + int(ranked_k)
+                    else:  # a KSCHED_PICK_PACK request has one launch form
+                        fails += 1
+                        print(f"FAIL pack case seed {cs}: N={N} P={P} K={K} flags={fl_k:#x} d={d_k} kernel={kernel} mask={want_mask} step={step}: the pick ran as {ev.last_pick!r}", flush=True)
+            # one combining chain on the same snapshot (draw_chain, run_chain)
+            chain = draw_chain(r4, N, P, K, nt)
+            fails += run_chain(ev, cs, f"step {step}", chain, cpu, mem, lab, taints, N, P, K, nt, rc, rm, sel, tol, smp, smp_u, smp_s)
         ev.set_kernel("auto")
         want3_u = (want[0], want[1], want_u)
         want3_s = (want[0], want[1], want_s)
@@ -527,6 +696,9 @@ while time.time() < t_end:
             fails += shard_halves(r3, cs, "spread-", N, P, K, nt, preds, fl_s, rc, rm, sel, tol, smp_s, d_s, want3_s)
         if HOOKS and r3.random() < 0.35:
             fails += spread_gathered(r3, cs, cpu, mem, lab, taints, N, P, K, nt, preds, fl_s, rc, rm, sel, tol, smp_s, d_s, want3_s, ranked_s, tied_s)
+        if HOOKS and r4.random() < 0.5:  # the pack pick through the multi-device sequence and a sharded apply of its gathered bindings; then the chain on every replica
+            fails += spread_gathered(r4, cs, cpu, mem, lab, taints, N, P, K, nt, preds, fl_k, rc, rm, sel, tol, smp_k, d_k, (want[0], want[1], want_k), ranked_k, False,
+                                     name="pack", restate=pack_restated, chain=(chain, smp, smp_u, smp_s))
         if r2.random() < 0.4:  # ksched_pick with the uniform pick: the oracle's mask, and that mask thinned by random words -- the restatement on either
             thin_u = want[0] & r2.integers(0, 1 << 63, want[0].shape, dtype=np.uint64)
             if not (np.array_equal(ev.pick(want[0], L.PICK_UNIFORM, samples=smp_u), want_u) and
