@@ -27,6 +27,7 @@
  *     combined in the caller's mask on the device)
  *   (extension E7: soft constraints -- combine only where   KSCHED_COMBINE_SOFT
  *     the pod keeps a node)
+ *   (extension E8: the selector operators Exists, Gt, Lt)   KSCHED_SELOP_EXISTS / _GT / _LT
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -238,6 +239,57 @@ extern "C" {
  * Several tiers, applied most important first, are LEXICOGRAPHIC: a later tier only chooses among what the earlier ones left, and the order
  * of the calls matters.  Kubernetes' weighted sum of preferred terms is not reproduced. */
 #define KSCHED_COMBINE_SOFT 0x2000u /* with KSCHED_COMBINE_AND / _ANDNOT: keep the row as it was where the op would empty it */
+/* KSCHED_SELOP_EXISTS / _GT / _LT (extension E8): the selector operators that are not equality.  A plain KSCHED_SEL call answers, per
+ * (pod, key), "the node's value id equals this id"; In, NotIn and ORed nodeSelectorTerms are built from such calls (E6).  Exists /
+ * DoesNotExist ("the node carries key k, whatever the value") and Gt / Lt on a numeric label are no sequence of equality calls: an OPERATOR
+ * CALL -- an evaluation whose flag word carries exactly one KSCHED_SELOP_* flag -- answers one such term, as a mask that the combining
+ * calls, the soft modifier and the picks consume like any other.  Added in ABI 7 without a version change and without a new symbol: detect
+ * them by these constants and by KSCHED_E_INVAL from an older library.
+ *   meaning    : per pod and per key k, with e = sel_val_ids[k*p + pod] and v = label_val_ids[k][node] of the current snapshot:
+ *                    e == 0                 the pod does not constrain key k: passes, under every operator;
+ *                    e == KSCHED_SEL_NEVER  never passes, under every operator -- an encoder's one way to say "this expression can match
+ *                                           nothing" (Gt against a non-integer, say);
+ *                    any other e            EXISTS: v != 0;    GT: v != 0 && v > e;    LT: v != 0 && v < e.
+ *                The compares are UNSIGNED 32-bit on the ids.  A node without the key (v == 0) fails every constrained key under every
+ *                operator: Kubernetes' rule for Gt / Lt on a missing label (a bare v < e would let absent nodes through).  Under EXISTS
+ *                the entry's value is not looked at beyond "constrained": any id from 1 to 0xFFFFFFFE says "must carry the key".  The row
+ *                is the AND over all keys, over nodes [0, n); bits at or beyond n in the last word are zero; the words [W, pitch) are left
+ *                untouched or written as zero.  sel_val_ids == NULL, or a snapshot without keys: no pod constrains anything and every
+ *                node passes, as for plain KSCHED_SEL.
+ *   ids        : the library compares ids, exactly.  ORDERING the ids of a numeric key is the caller's interning: id = value + 1, say, or
+ *                the rank of the value among the key's values -- any map that is monotonic over the values of that key and keeps 0 for
+ *                "absent".  The bound of a Gt / Lt expression is interned by the same map (it need not be a value some node carries).
+ *   exact      : integer logic only -- same inputs, same bits, on every run.
+ *   flags      : KSCHED_SEL is required.  Allowed beside it: ONE KSCHED_SELOP_* flag; optionally one KSCHED_COMBINE_* op, with or without
+ *                KSCHED_COMBINE_SOFT, under E6 / E7's own rules; optionally one KSCHED_PICK_* flag.  req_cpu_milli / req_mem_bytes stay
+ *                required as in every evaluation and are not read.
+ *   errors     : KSCHED_E_INVAL with nothing enqueued and nothing written for two operator flags; for an operator flag without KSCHED_SEL;
+ *                and for KSCHED_FIT, KSCHED_TAINT, KSCHED_WANT_FIT_MASK or out_fit in the same call -- fit and taints come from another call
+ *                and are combined in, as in the recipe below.  Every refusal of a plain or a combining call stays what it is.
+ *   accepted   : by ksched_eval and ksched_eval_begin / ksched_eval_end (without a combine flag, as today) and by ksched_eval_device and
+ *                ksched_eval_device_pitched (with or without one).  NOT by ksched_pipe_submit, ksched_pick, ksched_pick_device,
+ *                ksched_summarize* or ksched_explain: KSCHED_E_INVAL with nothing enqueued.
+ *   with a pick: a pick flag in the same call runs BEHIND the mask -- behind the combine, if there is one -- and reads that mask: the
+ *                bindings are exactly those of ksched_pick_device on it with the pick flag alone; best fit is told nothing about the fit.
+ *                KSCHED_OPT_PICK_FROM_MASK and KSCHED_OPT_FUSED_PICK have no effect (the combining call's rule).  ksched_last_pick:
+ *                "from-mask" for the sampled and the best-fit pick, the member's name for the ranked picks, "none" without a pick.
+ *   options    : KSCHED_OPT_KERNEL has no effect on an operator call: the operator kernel is the only form, works on every snapshot,
+ *                indexed or not, and never reads the bitmap index.  ksched_last_kernel: "selop".  KSCHED_OPT_TIMING brackets the operator
+ *                kernel with stream events, as it does the direct kernel.
+ *   otherwise  : the plain evaluation's contract: p == 0 is a no-op, n == 0 leaves the mask alone (and gives -1 for every pod of a pick),
+ *                KSCHED_E_STATE before ksched_set_nodes; ordering is that of a plain ksched_eval_device on `hip_stream` -- a
+ *                ksched_update_node_labels or ksched_set_nodes enqueued before the call is visible to it, one enqueued after it is not --,
+ *                and a combining operator call holds the ctx's scratch mask as any combining call does.
+ * Recipe -- gpu Exists AND cores Gt 16 AND zone NotIn {z3} AND fit, then the spread pick, in four calls on one stream and one mask M:
+ *     ksched_eval_device(.., sel: gpu = 1 (any non-zero), KSCHED_SEL | KSCHED_SELOP_EXISTS,                      M, ..)   M  = [gpu Exists]
+ *     ksched_eval_device(.., sel: cores = id(16),         KSCHED_SEL | KSCHED_SELOP_GT | KSCHED_COMBINE_AND,     M, ..)   M &= [cores > 16]
+ *     ksched_eval_device(.., sel: zone = z3,              KSCHED_SEL | KSCHED_COMBINE_ANDNOT,                    M, ..)   M &= ~[zone = z3]
+ *     ksched_eval_device(.., no selector,                 KSCHED_FIT | KSCHED_COMBINE_AND | KSCHED_PICK_SPREAD,  M, .., out_binding, ..)
+ * DoesNotExist is KSCHED_SEL | KSCHED_SELOP_EXISTS | KSCHED_COMBINE_ANDNOT; a preferred expression adds KSCHED_COMBINE_SOFT. */
+#define KSCHED_SELOP_EXISTS 0x4000u /* a constrained key passes where the node carries the key at all */
+#define KSCHED_SELOP_GT 0x8000u     /* ... where the node carries the key and its id > the pod's entry */
+#define KSCHED_SELOP_LT 0x10000u    /* ... where the node carries the key and its id < the pod's entry */
+#define KSCHED_SELOP_ANY (KSCHED_SELOP_EXISTS | KSCHED_SELOP_GT | KSCHED_SELOP_LT)
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0

@@ -48,6 +48,11 @@ COMBINE_ANDNOT = 0x800  # out_feasible = out_feasible & ~feasible(this call)
 COMBINE_ANY = COMBINE_AND | COMBINE_OR | COMBINE_ANDNOT
 # extension E7: a modifier of COMBINE_AND / COMBINE_ANDNOT (not a member of COMBINE_ANY): a row the op would empty keeps what it held
 COMBINE_SOFT = 0x2000
+# extension E8: the selector operators -- with SEL alone (no FIT / TAINT / WANT_FIT_MASK), at most one per call; ids compare as unsigned 32-bit
+SELOP_EXISTS = 0x4000  # a constrained key passes where the node carries the key at all
+SELOP_GT = 0x8000  # ... where the node carries the key and its id > the pod's entry
+SELOP_LT = 0x10000  # ... where the node carries the key and its id < the pod's entry
+SELOP_ANY = SELOP_EXISTS | SELOP_GT | SELOP_LT
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

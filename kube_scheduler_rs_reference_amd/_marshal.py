@@ -131,6 +131,27 @@ def soft(flags: int, where: str, accepted: bool) -> None:
         raise ValueError(f"flags: COMBINE_SOFT modifies COMBINE_AND or COMBINE_ANDNOT, got {int(flags) & COMBINE:#x} beside it")
 
 
+def selop(flags: int, where: str, accepted: bool, out_fit=None) -> None:
+    """The one rule of SELOP_EXISTS / SELOP_GT / SELOP_LT (include/ksched.h, extension E8), before any library call: the evaluations accept
+    them (accepted=True: `eval`, `eval_device`, `bind_eval_device`), the pipe, the picks, the summaries and `explain` do not; at most one
+    per call; SEL is required -- the operator is a reading of the selector entries --; FIT, TAINT and WANT_FIT_MASK / `out_fit` are
+    excluded: the call answers the selector term alone, fit and taints are combined in from another call.  ValueError naming the
+    argument; a word without an operator flag passes."""
+    o = int(flags) & L.SELOP_ANY
+    if not o:
+        return
+    if not accepted:
+        raise ValueError(f"flags: {where} takes no SELOP_EXISTS / SELOP_GT / SELOP_LT (an operator call is an evaluation: Evaluator.eval, Evaluator.eval_device)")
+    if o & (o - 1):
+        raise ValueError(f"flags: at most one of SELOP_EXISTS / SELOP_GT / SELOP_LT per call, got {o:#x}")
+    if not int(flags) & L.SEL:
+        raise ValueError("flags: a SELOP_* flag needs SEL (it says how the selector entries are read)")
+    if int(flags) & (L.FIT | L.TAINT):
+        raise ValueError("flags: a SELOP_* flag excludes FIT and TAINT (combine them in from another call: COMBINE_AND)")
+    if out_fit is not None or int(flags) & L.WANT_FIT_MASK:
+        raise ValueError("out_fit: a SELOP_* flag excludes WANT_FIT_MASK / out_fit")
+
+
 class Batch(NamedTuple):
     """One pod batch as the C ABI takes it; [:8] is the argument run every evaluation entry point shares."""
     p: int

@@ -12,6 +12,7 @@
 #include "../../include/ksched.h"
 #include "bestfit_layout.hpp"
 #include "mask_combine.hpp"
+#include "sel_ops.hpp"
 
 namespace ksched {
 
@@ -47,9 +48,10 @@ struct EvalFacts {
     uint32_t debug = 0;  // KSCHED_OPT_DEBUG (bit 0x400: best fit in one stage)
     CombineOp combine = CombineOp::kNone;  // combine_op(flags) of a combining call (extension E6, mask_combine.hpp); the caller gave out_feasible and no out_fit
     bool soft = false;  // combine_soft(flags) (extension E7, mask_combine_soft.hpp): with kAnd or kAndNot only
+    SelOp selop = SelOp::kNone;  // sel_op(flags) of an operator call (extension E8, sel_ops.hpp): KSCHED_SEL alone beside it, no out_fit
 };
 
-enum class MaskKernel { kNone, kFused, kDirect };
+enum class MaskKernel { kNone, kFused, kDirect, kSelOp };
 enum class SampledPick { kNone, kOwnLaunch, kRidesFill, kRidesTiles, kFromMask };
 enum class BestfitPick { kNone, kRowsOneStage, kRowsTwoStages, kRowsTwoStagesListed, kFromMask };
 enum class RankedPick { kNone, kUniform, kSpread, kPack };  // k_pick_uniform / k_pick_spread / k_pick_pack behind the mask kernel: the only form
@@ -67,6 +69,7 @@ struct EvalPlan {
     const char *last_kernel = nullptr;  // ksched_last_kernel after the launch; nullptr = no mask kernel runs, it stays what it was
     const char *last_pick = "none";     // ksched_last_pick
     bool soft = false;  // with a combine: k_mask_combine_soft in k_mask_combine's place -- a row the fold would empty keeps what it held
+    SelOp selop = SelOp::kNone;  // with mask == kSelOp: the operator k_eval_selop answers
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
@@ -106,6 +109,28 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     const bool want_mask = f.have_feas || f.have_fit;
     const bool can_fused = f.fused_applicable;
     const int kern = choose_kernel(f.opt_kernel, can_fused);
+    // An operator call (extension E8) answers the selector term alone, by the operator kernel: the only form, whatever KSCHED_OPT_KERNEL
+    // says and whether or not the snapshot has a bitmap index -- so no plan of it is unsupported.  Nothing rides in that kernel and no pick
+    // has structures for the operators: a pick runs behind the mask (behind the combine, if the call combines) and reads it, as in a
+    // combining call, whatever KSCHED_OPT_PICK_FROM_MASK / KSCHED_OPT_FUSED_PICK say.  The mask goes into the ctx's scratch mask when the
+    // call combines (the caller's is the combine's left operand) or the caller gave none.
+    if (f.selop != SelOp::kNone) {
+        plan.selop = f.selop;
+        plan.mask = MaskKernel::kSelOp;
+        plan.last_kernel = "selop";
+        plan.combine = f.combine;
+        plan.soft = f.combine != CombineOp::kNone && f.soft;
+        plan.scratch_mask = f.combine != CombineOp::kNone || !f.have_feas;
+        if (const RankedMember *m = ranked_member(flags)) {
+            plan.ranked = m->pick;
+            plan.last_pick = m->name;
+        } else if (pick_s || pick_b) {
+            if (pick_s) plan.sampled = SampledPick::kFromMask;
+            else plan.bestfit = BestfitPick::kFromMask;
+            plan.last_pick = "from-mask";
+        }
+        return plan;
+    }
     // A combining call (extension E6) is a mask-only evaluation into the ctx's scratch mask -- although the caller gave a mask: that one
     // is the combine's left operand --, then the combine, then the pick from the COMBINED mask.  So the mask kernel is chosen as for a
     // mask-only request, nothing rides in it (a riding pick would test the call's own predicates, not the combined mask), and the sampled

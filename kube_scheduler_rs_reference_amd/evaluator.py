@@ -203,9 +203,11 @@ class Evaluator:
         (the same draws: the tightest -- the smallest available memory, then cpu, then the lowest index -- of them), WANT_FIT_MASK.
         `out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4).
-        The COMBINE_* flags are refused here (ValueError): masks are combined on the device, by eval_device."""
+        The COMBINE_* flags are refused here (ValueError): masks are combined on the device, by eval_device.
+        SEL with one of SELOP_EXISTS / SELOP_GT / SELOP_LT (extension E8) is an operator call, as in eval_device."""
         M.combine(flags, "Evaluator.eval", accepted=False)
         M.soft(flags, "Evaluator.eval", accepted=False)
+        M.selop(flags, "Evaluator.eval", accepted=True)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
         p, W = b.p, self.W
         res = EvalResult()
@@ -238,7 +240,12 @@ class Evaluator:
         COMBINE_SOFT (extension E7) beside COMBINE_AND or COMBINE_ANDNOT makes the call a soft constraint: per pod row the mask narrows to
         out_feasible & feasible(this call) (or & ~) only where that leaves the pod a node; a row it would empty keeps what it held (bits at
         or beyond n zero either way).  A preferred affinity term is SEL | COMBINE_AND | COMBINE_SOFT on the hard mask; tiers applied most
-        important first are lexicographic."""
+        important first are lexicographic.
+        SEL with one of SELOP_EXISTS / SELOP_GT / SELOP_LT (extension E8) is an OPERATOR call: a constrained key (entry neither 0 nor
+        SEL_NEVER) passes where the node carries the key at all / carries it with an id above / below the entry, ids compared as unsigned
+        32-bit numbers (ordering a numeric key's ids is the caller's interning); a node without the key fails.  No FIT, TAINT or
+        WANT_FIT_MASK beside it; a COMBINE_* op (with or without COMBINE_SOFT) and a pick may be: `gpu Exists and cores Gt 16 and fit` is
+        SEL | SELOP_EXISTS, then SEL | SELOP_GT | COMBINE_AND, then FIT | COMBINE_AND | a pick; DoesNotExist is SELOP_EXISTS with COMBINE_ANDNOT."""
         calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                              [out_feasible], out_fit, [out_binding], stream)
         self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
@@ -250,6 +257,7 @@ class Evaluator:
         for m in masks:
             M.combine(flags, "Evaluator.eval_device", accepted=True, out_feasible=m, out_fit=out_fit)
         M.soft(flags, "Evaluator.eval_device", accepted=True)
+        M.selop(flags, "Evaluator.eval_device", accepted=True, out_fit=out_fit)
         b = M.device_batch(self.device, self.n_keys, *cols, flags)
         (*pm, pr), pitch = M.mask_rows(b.p, self.W, self.device, *[("out_feasible", m) for m in masks], ("out_fit", out_fit))
         po = [M.device_ptr(o, "out_binding", "i32", (b.p,), self.device) for o in outs]
@@ -283,6 +291,7 @@ class Evaluator:
         available columns as this stream sees them at this point) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask
         includes the resource fit)."""
         import torch
+        M.selop(flags, "Evaluator.pick_device", accepted=False)
         if feasible is None or len(feasible.shape) != 2:
             raise ValueError(f"feasible must be a [p, {self.W}] CUDA mask with unit column stride")
         b = M.device_batch(self.device, self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=feasible.shape[0])
@@ -297,6 +306,7 @@ class Evaluator:
         """The pick alone from HOST masks (ksched_pick): `feasible` = [p, W] uint64 rows as `eval` returns them (or as a caller has combined
         them: ANDed masks of a selector evaluated in key groups).  flags: PICK_SAMPLED (+ samples [p, attempts]), PICK_UNIFORM (+ samples
         [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD / PICK_PACK (+ samples [p, d]: 32-bit draws, all read; no req_mem_bytes needed) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
+        M.selop(flags, "Evaluator.pick", accepted=False)
         f = M.host_array(feasible, "feasible", "u64", (None, self.W))
         b = M.host_batch(self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=f.shape[0])
         out = np.empty((b.p,), dtype=np.int32)
@@ -334,6 +344,7 @@ class Evaluator:
     # -- reasons -------------------------------------------------------------------------------------
     def explain(self, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, pair_pod, pair_node, flags: int) -> np.ndarray:
         """ksched_explain: REASON_* of check_node_validity for the listed (pod, node) pairs, decided on the device."""
+        M.selop(flags, "Evaluator.explain", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         pp = M.host_array(pair_pod, "pair_pod", "u32", (None,))
         pn = M.host_array(pair_node, "pair_node", "u32", pp.shape)
@@ -345,6 +356,7 @@ class Evaluator:
     def summarize(self, req_cpu_milli, req_mem_bytes, sel_val_ids=None, tolerations=None, flags: int = L.FIT) -> np.ndarray:
         """ksched_summarize: per pod the number of nodes check_node_validity accepts / rejects by reason, [p, SUMMARY_WORDS] uint32
         (column r = REASON_*; column 0 = feasible nodes; every row adds up to the node count)."""
+        M.selop(flags, "Evaluator.summarize", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         out = np.empty((b.p, L.SUMMARY_WORDS), dtype=np.uint32)
         rc = self._lib.ksched_summarize(self._h, *b[:5], int(flags), _ptr(out))
@@ -356,6 +368,7 @@ class Evaluator:
         (default: torch's current stream), the host does not wait.  `out`: a contiguous [p, SUMMARY_WORDS] int32/uint32 tensor
         (allocated when None; it need not be zeroed).  Returns it."""
         import torch
+        M.selop(flags, "Evaluator.summarize_device", accepted=False)
         b = M.device_batch(self.device, self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         if out is None:
             out = torch.empty((b.p, L.SUMMARY_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
@@ -431,6 +444,7 @@ class Pipe:
         ev = self.ev
         M.combine(flags, "Pipe.submit", accepted=False)
         M.soft(flags, "Pipe.submit", accepted=False)
+        M.selop(flags, "Pipe.submit", accepted=False)
         b = M.device_batch(ev.device, ev.n_keys, *cols, flags)
         per_slot = []
         for m, o in zip(masks, bindings):

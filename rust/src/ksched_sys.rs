@@ -49,6 +49,10 @@ pub const KSCHED_COMBINE_OR: u32 = 0x400; // out_feasible = out_feasible | feasi
 pub const KSCHED_COMBINE_ANDNOT: u32 = 0x800; // out_feasible = out_feasible & !feasible(this call)
 pub const KSCHED_COMBINE_ANY: u32 = KSCHED_COMBINE_AND | KSCHED_COMBINE_OR | KSCHED_COMBINE_ANDNOT; // at most one per call
 pub const KSCHED_COMBINE_SOFT: u32 = 0x2000; // extension E7, with KSCHED_COMBINE_AND / _ANDNOT: a row the op would empty keeps what it held
+pub const KSCHED_SELOP_EXISTS: u32 = 0x4000; // extension E8, with KSCHED_SEL alone: a constrained key passes where the node carries the key at all
+pub const KSCHED_SELOP_GT: u32 = 0x8000; // ... where the node carries the key and its id > the pod's entry (unsigned 32-bit)
+pub const KSCHED_SELOP_LT: u32 = 0x10000; // ... where the node carries the key and its id < the pod's entry
+pub const KSCHED_SELOP_ANY: u32 = KSCHED_SELOP_EXISTS | KSCHED_SELOP_GT | KSCHED_SELOP_LT; // at most one per call
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
 pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
@@ -309,6 +313,10 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_COMBINE_ANDNOT", KSCHED_COMBINE_ANDNOT as i64),
         ("KSCHED_COMBINE_ANY", KSCHED_COMBINE_ANY as i64),
         ("KSCHED_COMBINE_SOFT", KSCHED_COMBINE_SOFT as i64),
+        ("KSCHED_SELOP_EXISTS", KSCHED_SELOP_EXISTS as i64),
+        ("KSCHED_SELOP_GT", KSCHED_SELOP_GT as i64),
+        ("KSCHED_SELOP_LT", KSCHED_SELOP_LT as i64),
+        ("KSCHED_SELOP_ANY", KSCHED_SELOP_ANY as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
         ("KSCHED_APPLY_WHILE_FIT", KSCHED_APPLY_WHILE_FIT as i64),
