@@ -28,6 +28,7 @@
  *   (extension E7: soft constraints -- combine only where   KSCHED_COMBINE_SOFT
  *     the pod keeps a node)
  *   (extension E8: the selector operators Exists, Gt, Lt)   KSCHED_SELOP_EXISTS / _GT / _LT
+ *   (extension E9: a selector operator per pod and key)     KSCHED_SELOP_TAGGED, KSCHED_SELTAG_*
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -290,6 +291,65 @@ extern "C" {
 #define KSCHED_SELOP_GT 0x8000u     /* ... where the node carries the key and its id > the pod's entry */
 #define KSCHED_SELOP_LT 0x10000u    /* ... where the node carries the key and its id < the pod's entry */
 #define KSCHED_SELOP_ANY (KSCHED_SELOP_EXISTS | KSCHED_SELOP_GT | KSCHED_SELOP_LT)
+/* KSCHED_SELOP_TAGGED (extension E9): a selector operator per pod and key.  Under a KSCHED_SELOP_* flag above the operator belongs to the
+ * CALL: every constrained entry of every pod is read under it, so a batch in which pod A says `cores Gt 16`, pod B `gpu Exists` and pod C
+ * `zone = a` takes one evaluation per operator over the whole pods x nodes rectangle plus the combines, and a negated expression (NotIn,
+ * DoesNotExist) takes a call of its own.  Under KSCHED_SELOP_TAGGED the operator is part of the selector ENTRY, and ONE call answers a whole
+ * conjunctive matchExpressions term for every pod of a heterogeneous batch: In {one value}, NotIn {one value}, Exists, DoesNotExist, Gt and
+ * Lt, mixed across keys.  A modifier of KSCHED_SEL in an evaluation; NOT a member of KSCHED_SELOP_ANY (as KSCHED_COMBINE_SOFT is none of
+ * KSCHED_COMBINE_ANY).  Added in ABI 7 without a version change and without a new symbol: detect it by this constant and by
+ * KSCHED_E_INVAL from an older library.
+ *   entry      : e = sel_val_ids[k*p + pod] is read as tag = e >> KSCHED_SELTAG_SHIFT (3 bits), id = e & KSCHED_SELTAG_ID_MASK (29 bits).
+ *   meaning    : per pod and per key k, with v = label_val_ids[k][node], the node's FULL 32-bit id of the current snapshot (v == 0: the
+ *                node does not carry the key):
+ *                    e == 0                    passes everywhere: the pod does not constrain key k;
+ *                    tag KSCHED_SELTAG_EQ      v == id               (so id >= 1; an absent node fails) -- In {one value};
+ *                    tag KSCHED_SELTAG_NE      v != id               (an absent node PASSES: Kubernetes' NotIn);
+ *                    tag KSCHED_SELTAG_EXISTS  v != 0                (the id field is not looked at);
+ *                    tag KSCHED_SELTAG_ABSENT  v == 0                (DoesNotExist; the id field is not looked at);
+ *                    tag KSCHED_SELTAG_GT      v != 0 && v > id;
+ *                    tag KSCHED_SELTAG_LT      v != 0 && v < id      (id 0 or 1: no node);
+ *                    tag 6 or 7                nowhere, whatever the id field holds.
+ *                KSCHED_SEL_NEVER (0xFFFFFFFF) is tag 7: it keeps its meaning without a special case.  An entry with tag EQ and id 0 IS the
+ *                unconstrained entry 0.  The compares are UNSIGNED 32-bit between the node's WHOLE id and the 29-bit id field: a snapshot
+ *                may hold ids at or above 2^29 -- they never equal an entry's id, they pass NE, and they pass GT for every bound --, an
+ *                entry cannot name them.  That is the one limit of a tagged call: interned ids must stay below 2^29.
+ *                The row is the AND over all keys, over nodes [0, n); bits at or beyond n in the last word are zero -- under NE and ABSENT
+ *                too, the first rules of this library that an all-zero padding lane would pass; the words [W, pitch) are left untouched
+ *                or written as zero.  sel_val_ids == NULL, or a snapshot without keys: every node passes.
+ *   exact      : integer logic only -- same inputs, same bits, on every run.
+ *   flags      : KSCHED_SEL is required.  Allowed beside the two: optionally one KSCHED_COMBINE_* op, with or without KSCHED_COMBINE_SOFT,
+ *                at the two device-pointer evaluations, under E6 / E7's own rules; optionally one KSCHED_PICK_* flag.  req_cpu_milli /
+ *                req_mem_bytes stay required as in every evaluation and are not read.
+ *   errors     : KSCHED_E_INVAL with nothing enqueued and nothing written for the flag beside any KSCHED_SELOP_EXISTS / _GT / _LT; without
+ *                KSCHED_SEL; and for KSCHED_FIT, KSCHED_TAINT, KSCHED_WANT_FIT_MASK or out_fit in the same call -- fit and taints come from
+ *                another call and are combined in.  Every refusal of a plain or a combining call stays what it is.
+ *   accepted   : by ksched_eval and ksched_eval_begin / ksched_eval_end (without a combine flag, as today) and by ksched_eval_device and
+ *                ksched_eval_device_pitched (with or without one).  NOT by ksched_pipe_submit, ksched_pick, ksched_pick_device,
+ *                ksched_summarize* or ksched_explain: KSCHED_E_INVAL with nothing enqueued and nothing written.
+ *   with a pick: a pick flag in the same call runs BEHIND the mask -- behind the combine, if there is one -- and reads that mask: the
+ *                bindings are exactly those of ksched_pick_device on it with the pick flag alone (an operator call's rule, E8).
+ *   options    : KSCHED_OPT_KERNEL has no effect: the tagged kernel is the only form, works on every snapshot, indexed or not, and never
+ *                reads the bitmap index.  ksched_last_kernel: "seltag".  KSCHED_OPT_TIMING brackets the kernel with stream events.
+ *   otherwise  : an operator call's contract (E8): p == 0 is a no-op, n == 0 leaves the mask alone (and gives -1 for every pod of a pick),
+ *                KSCHED_E_STATE before ksched_set_nodes; ordering against ksched_update_node_labels / ksched_set_nodes is that of a plain
+ *                evaluation on `hip_stream`; a combining tagged call holds the ctx's scratch mask as any combining call does.
+ * Recipes:
+ *   - gpu Exists AND cores Gt 16 AND zone NotIn {z3} is ONE row -- gpu: EXISTS, cores: GT id(16), zone: NE z3 -- and ONE call,
+ *         ksched_eval_device(.., sel: that row per pod, KSCHED_SEL | KSCHED_SELOP_TAGGED,                        M, ..)   M  = [the term]
+ *         ksched_eval_device(.., no selector,           KSCHED_FIT | KSCHED_COMBINE_AND | KSCHED_PICK_SPREAD,    M, .., out_binding, ..)
+ *     where E8's recipe above takes three calls for the term, each over every pod.
+ *   - In {a, b} stays two calls under KSCHED_COMBINE_OR (an entry holds one id).
+ *   - A range on one key (Gt 4 AND Lt 16) is two calls under KSCHED_COMBINE_AND: a key has one entry per pod per call. */
+#define KSCHED_SELOP_TAGGED 0x40000u /* with KSCHED_SEL alone: every selector entry carries its own operator, tag << 29 | id */
+#define KSCHED_SELTAG_SHIFT 29u
+#define KSCHED_SELTAG_ID_MASK 0x1FFFFFFFu
+#define KSCHED_SELTAG_EQ 0u     /* v == id */
+#define KSCHED_SELTAG_NE 1u     /* v != id; an absent node passes */
+#define KSCHED_SELTAG_EXISTS 2u /* v != 0 */
+#define KSCHED_SELTAG_ABSENT 3u /* v == 0 */
+#define KSCHED_SELTAG_GT 4u     /* v != 0 && v > id */
+#define KSCHED_SELTAG_LT 5u     /* v != 0 && v < id */
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0

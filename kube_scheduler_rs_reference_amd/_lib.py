@@ -53,6 +53,17 @@ SELOP_EXISTS = 0x4000  # a constrained key passes where the node carries the key
 SELOP_GT = 0x8000  # ... where the node carries the key and its id > the pod's entry
 SELOP_LT = 0x10000  # ... where the node carries the key and its id < the pod's entry
 SELOP_ANY = SELOP_EXISTS | SELOP_GT | SELOP_LT
+# extension E9: a modifier of SEL (not a member of SELOP_ANY, and never beside one): every selector entry carries its own operator,
+# entry = tag << SELTAG_SHIFT | id, compared against the node's whole 32-bit id; entry 0 stays "unconstrained", SEL_NEVER is tag 7
+SELOP_TAGGED = 0x40000
+SELTAG_SHIFT = 29
+SELTAG_ID_MASK = 0x1FFFFFFF
+SELTAG_EQ = 0  # v == id (In {one value}); with id 0 it IS the unconstrained entry
+SELTAG_NE = 1  # v != id; a node without the key passes (NotIn {one value})
+SELTAG_EXISTS = 2  # v != 0; the id field is not looked at
+SELTAG_ABSENT = 3  # v == 0 (DoesNotExist); the id field is not looked at
+SELTAG_GT = 4  # v != 0 and v > id
+SELTAG_LT = 5  # v != 0 and v < id
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

@@ -152,6 +152,26 @@ def selop(flags: int, where: str, accepted: bool, out_fit=None) -> None:
         raise ValueError("out_fit: a SELOP_* flag excludes WANT_FIT_MASK / out_fit")
 
 
+def seltag(flags: int, where: str, accepted: bool, out_fit=None) -> None:
+    """The one rule of SELOP_TAGGED (include/ksched.h, extension E9), before any library call: the evaluations accept it (accepted=True:
+    `eval`, `eval_device`, `bind_eval_device`), the pipe, the picks, the summaries and `explain` do not; no SELOP_EXISTS / SELOP_GT /
+    SELOP_LT beside it -- the operator is the entry's or the call's, not both --; SEL is required; FIT, TAINT and WANT_FIT_MASK /
+    `out_fit` are excluded: the call answers the selector term alone, fit and taints are combined in from another call.  ValueError
+    naming the argument; a word without the flag passes."""
+    if not int(flags) & L.SELOP_TAGGED:
+        return
+    if not accepted:
+        raise ValueError(f"flags: {where} takes no SELOP_TAGGED (a tagged call is an evaluation: Evaluator.eval, Evaluator.eval_device)")
+    if int(flags) & L.SELOP_ANY:
+        raise ValueError(f"flags: SELOP_TAGGED excludes SELOP_EXISTS / SELOP_GT / SELOP_LT, got {int(flags) & L.SELOP_ANY:#x} beside it")
+    if not int(flags) & L.SEL:
+        raise ValueError("flags: SELOP_TAGGED needs SEL (it says how the selector entries are read)")
+    if int(flags) & (L.FIT | L.TAINT):
+        raise ValueError("flags: SELOP_TAGGED excludes FIT and TAINT (combine them in from another call: COMBINE_AND)")
+    if out_fit is not None or int(flags) & L.WANT_FIT_MASK:
+        raise ValueError("out_fit: SELOP_TAGGED excludes WANT_FIT_MASK / out_fit")
+
+
 class Batch(NamedTuple):
     """One pod batch as the C ABI takes it; [:8] is the argument run every evaluation entry point shares."""
     p: int

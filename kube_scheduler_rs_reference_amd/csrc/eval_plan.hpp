@@ -13,6 +13,7 @@
 #include "bestfit_layout.hpp"
 #include "mask_combine.hpp"
 #include "sel_ops.hpp"
+#include "sel_tags.hpp"
 
 namespace ksched {
 
@@ -49,9 +50,10 @@ struct EvalFacts {
     CombineOp combine = CombineOp::kNone;  // combine_op(flags) of a combining call (extension E6, mask_combine.hpp); the caller gave out_feasible and no out_fit
     bool soft = false;  // combine_soft(flags) (extension E7, mask_combine_soft.hpp): with kAnd or kAndNot only
     SelOp selop = SelOp::kNone;  // sel_op(flags) of an operator call (extension E8, sel_ops.hpp): KSCHED_SEL alone beside it, no out_fit
+    bool seltag = false;  // sel_tagged(flags) of a tagged call (extension E9, sel_tags.hpp): KSCHED_SEL alone beside it, no operator flag, no out_fit
 };
 
-enum class MaskKernel { kNone, kFused, kDirect, kSelOp };
+enum class MaskKernel { kNone, kFused, kDirect, kSelOp, kSelTag };
 enum class SampledPick { kNone, kOwnLaunch, kRidesFill, kRidesTiles, kFromMask };
 enum class BestfitPick { kNone, kRowsOneStage, kRowsTwoStages, kRowsTwoStagesListed, kFromMask };
 enum class RankedPick { kNone, kUniform, kSpread, kPack };  // k_pick_uniform / k_pick_spread / k_pick_pack behind the mask kernel: the only form
@@ -70,6 +72,7 @@ struct EvalPlan {
     const char *last_pick = "none";     // ksched_last_pick
     bool soft = false;  // with a combine: k_mask_combine_soft in k_mask_combine's place -- a row the fold would empty keeps what it held
     SelOp selop = SelOp::kNone;  // with mask == kSelOp: the operator k_eval_selop answers
+    bool seltag = false;  // mask == kSelTag: k_eval_seltag reads the operator out of every selector entry
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
@@ -114,10 +117,18 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     // has structures for the operators: a pick runs behind the mask (behind the combine, if the call combines) and reads it, as in a
     // combining call, whatever KSCHED_OPT_PICK_FROM_MASK / KSCHED_OPT_FUSED_PICK say.  The mask goes into the ctx's scratch mask when the
     // call combines (the caller's is the combine's left operand) or the caller gave none.
-    if (f.selop != SelOp::kNone) {
-        plan.selop = f.selop;
-        plan.mask = MaskKernel::kSelOp;
-        plan.last_kernel = "selop";
+    // A tagged call (extension E9) is planned the same way, with the tagged kernel in the operator kernel's place; it carries no operator
+    // (check_seltag_args), so an operator decides first only where a caller of plan_eval gives both.
+    if (f.selop != SelOp::kNone || f.seltag) {
+        if (f.selop != SelOp::kNone) {
+            plan.selop = f.selop;
+            plan.mask = MaskKernel::kSelOp;
+            plan.last_kernel = "selop";
+        } else {
+            plan.seltag = true;
+            plan.mask = MaskKernel::kSelTag;
+            plan.last_kernel = "seltag";
+        }
         plan.combine = f.combine;
         plan.soft = f.combine != CombineOp::kNone && f.soft;
         plan.scratch_mask = f.combine != CombineOp::kNone || !f.have_feas;

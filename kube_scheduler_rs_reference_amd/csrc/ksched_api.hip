@@ -35,6 +35,7 @@
 #include "kernels_combine.hpp"      // (extension E6: the scratch mask folded into the caller's mask)
 #include "kernels_combine_soft.hpp" // (extension E7: ... row by row, unless that would leave the row empty)
 #include "kernels_selop.hpp"        // (extension E8: the mask of an operator call -- Exists, Gt, Lt)
+#include "kernels_seltag.hpp"       // (extension E9: the mask of a tagged call -- the operator per pod and key)
 #include "mask_alloc.hpp"
 #include "merge_sort_plan.hpp"
 #include "pipe_plan.hpp"
@@ -1183,6 +1184,9 @@ int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
     } else if (plan.mask == MaskKernel::kSelOp) {  // (extension E8: the selector term alone, under the plan's operator, from the label columns)
         if (hipError_t e = run_selop(plan.selop, c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, s); e != hipSuccess)
             return fail_hip(c, e, "run_selop");
+    } else if (plan.mask == MaskKernel::kSelTag) {  // (extension E9: the selector term alone, the operator read out of every entry, from the label columns)
+        if (hipError_t e = run_seltag(c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, s); e != hipSuccess)
+            return fail_hip(c, e, "run_seltag");
     } else if (int rc = run_direct(c, r, feas)) {
         return rc;
     }
@@ -1232,6 +1236,7 @@ EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
     f.combine = combine_op(r.flags);
     f.soft = combine_soft(r.flags);
     f.selop = sel_op(r.flags);
+    f.seltag = sel_tagged(r.flags);
     return f;
 }
 
@@ -1321,13 +1326,15 @@ inline bool at_most_one_pick(uint32_t flags) {
 // the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed).
 // combine_accepted: the entry point takes the KSCHED_COMBINE_* flags (the two device-pointer evaluations; mask_combine.hpp and
 // mask_combine_soft.hpp have the rules).  selop_accepted: it takes the KSCHED_SELOP_* flags (every evaluation but ksched_pipe_submit;
-// sel_ops.hpp has the rules)
+// sel_ops.hpp has the rules) and, with them, KSCHED_SELOP_TAGGED (sel_tags.hpp has the rules)
 int check_eval_args(const EvalRequest &r, bool combine_accepted = false, bool selop_accepted = true) {
     const uint32_t flags = r.flags;
-    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK | KSCHED_COMBINE_ANY | KSCHED_COMBINE_SOFT | KSCHED_SELOP_ANY;
+    const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK | KSCHED_COMBINE_ANY | KSCHED_COMBINE_SOFT | KSCHED_SELOP_ANY |
+                           KSCHED_SELOP_TAGGED;
     if (flags & ~known) return KSCHED_E_INVAL;
     if (int rcc = check_soft_args(flags, combine_accepted, r.out_feas != nullptr, r.out_fit != nullptr)) return rcc;
     if (int rco = check_selop_args(flags, selop_accepted, r.out_fit != nullptr)) return rco;
+    if (int rct = check_seltag_args(flags, selop_accepted, r.out_fit != nullptr)) return rct;
     if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
     if (flags & KSCHED_PICK_DRAWS) {

@@ -204,10 +204,12 @@ class Evaluator:
         `out`: an EvalResult of an earlier call with the same shapes whose arrays are written again instead of fresh ones -- a caller that evaluates batch
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4).
         The COMBINE_* flags are refused here (ValueError): masks are combined on the device, by eval_device.
-        SEL with one of SELOP_EXISTS / SELOP_GT / SELOP_LT (extension E8) is an operator call, as in eval_device."""
+        SEL with one of SELOP_EXISTS / SELOP_GT / SELOP_LT (extension E8) is an operator call, as in eval_device; SEL | SELOP_TAGGED
+        (extension E9) a tagged call, as there."""
         M.combine(flags, "Evaluator.eval", accepted=False)
         M.soft(flags, "Evaluator.eval", accepted=False)
         M.selop(flags, "Evaluator.eval", accepted=True)
+        M.seltag(flags, "Evaluator.eval", accepted=True)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
         p, W = b.p, self.W
         res = EvalResult()
@@ -245,7 +247,12 @@ class Evaluator:
         SEL_NEVER) passes where the node carries the key at all / carries it with an id above / below the entry, ids compared as unsigned
         32-bit numbers (ordering a numeric key's ids is the caller's interning); a node without the key fails.  No FIT, TAINT or
         WANT_FIT_MASK beside it; a COMBINE_* op (with or without COMBINE_SOFT) and a pick may be: `gpu Exists and cores Gt 16 and fit` is
-        SEL | SELOP_EXISTS, then SEL | SELOP_GT | COMBINE_AND, then FIT | COMBINE_AND | a pick; DoesNotExist is SELOP_EXISTS with COMBINE_ANDNOT."""
+        SEL | SELOP_EXISTS, then SEL | SELOP_GT | COMBINE_AND, then FIT | COMBINE_AND | a pick; DoesNotExist is SELOP_EXISTS with COMBINE_ANDNOT.
+        SEL | SELOP_TAGGED (extension E9) is a TAGGED call: every entry of sel_val_ids carries its own operator, `seltag(tag, id)` =
+        tag << SELTAG_SHIFT | id with tag SELTAG_EQ / _NE / _EXISTS / _ABSENT / _GT / _LT, compared against the node's whole 32-bit id (entry
+        0: unconstrained; SEL_NEVER: nothing; NE and ABSENT pass a node without the key), so one call answers a whole conjunctive
+        matchExpressions term per pod: `gpu Exists and cores Gt 16 and zone NotIn {z3}` is one row.  No SELOP_EXISTS / _GT / _LT, FIT, TAINT
+        or WANT_FIT_MASK beside it; a COMBINE_* op (with or without COMBINE_SOFT) and a pick may be.  Interned ids must stay below 2^29."""
         calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                              [out_feasible], out_fit, [out_binding], stream)
         self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
@@ -258,6 +265,7 @@ class Evaluator:
             M.combine(flags, "Evaluator.eval_device", accepted=True, out_feasible=m, out_fit=out_fit)
         M.soft(flags, "Evaluator.eval_device", accepted=True)
         M.selop(flags, "Evaluator.eval_device", accepted=True, out_fit=out_fit)
+        M.seltag(flags, "Evaluator.eval_device", accepted=True, out_fit=out_fit)
         b = M.device_batch(self.device, self.n_keys, *cols, flags)
         (*pm, pr), pitch = M.mask_rows(b.p, self.W, self.device, *[("out_feasible", m) for m in masks], ("out_fit", out_fit))
         po = [M.device_ptr(o, "out_binding", "i32", (b.p,), self.device) for o in outs]
@@ -292,6 +300,7 @@ class Evaluator:
         includes the resource fit)."""
         import torch
         M.selop(flags, "Evaluator.pick_device", accepted=False)
+        M.seltag(flags, "Evaluator.pick_device", accepted=False)
         if feasible is None or len(feasible.shape) != 2:
             raise ValueError(f"feasible must be a [p, {self.W}] CUDA mask with unit column stride")
         b = M.device_batch(self.device, self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=feasible.shape[0])
@@ -307,6 +316,7 @@ class Evaluator:
         them: ANDed masks of a selector evaluated in key groups).  flags: PICK_SAMPLED (+ samples [p, attempts]), PICK_UNIFORM (+ samples
         [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD / PICK_PACK (+ samples [p, d]: 32-bit draws, all read; no req_mem_bytes needed) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
         M.selop(flags, "Evaluator.pick", accepted=False)
+        M.seltag(flags, "Evaluator.pick", accepted=False)
         f = M.host_array(feasible, "feasible", "u64", (None, self.W))
         b = M.host_batch(self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=f.shape[0])
         out = np.empty((b.p,), dtype=np.int32)
@@ -345,6 +355,7 @@ class Evaluator:
     def explain(self, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, pair_pod, pair_node, flags: int) -> np.ndarray:
         """ksched_explain: REASON_* of check_node_validity for the listed (pod, node) pairs, decided on the device."""
         M.selop(flags, "Evaluator.explain", accepted=False)
+        M.seltag(flags, "Evaluator.explain", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         pp = M.host_array(pair_pod, "pair_pod", "u32", (None,))
         pn = M.host_array(pair_node, "pair_node", "u32", pp.shape)
@@ -357,6 +368,7 @@ class Evaluator:
         """ksched_summarize: per pod the number of nodes check_node_validity accepts / rejects by reason, [p, SUMMARY_WORDS] uint32
         (column r = REASON_*; column 0 = feasible nodes; every row adds up to the node count)."""
         M.selop(flags, "Evaluator.summarize", accepted=False)
+        M.seltag(flags, "Evaluator.summarize", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         out = np.empty((b.p, L.SUMMARY_WORDS), dtype=np.uint32)
         rc = self._lib.ksched_summarize(self._h, *b[:5], int(flags), _ptr(out))
@@ -369,6 +381,7 @@ class Evaluator:
         (allocated when None; it need not be zeroed).  Returns it."""
         import torch
         M.selop(flags, "Evaluator.summarize_device", accepted=False)
+        M.seltag(flags, "Evaluator.summarize_device", accepted=False)
         b = M.device_batch(self.device, self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         if out is None:
             out = torch.empty((b.p, L.SUMMARY_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
@@ -445,6 +458,7 @@ class Pipe:
         M.combine(flags, "Pipe.submit", accepted=False)
         M.soft(flags, "Pipe.submit", accepted=False)
         M.selop(flags, "Pipe.submit", accepted=False)
+        M.seltag(flags, "Pipe.submit", accepted=False)
         b = M.device_batch(ev.device, ev.n_keys, *cols, flags)
         per_slot = []
         for m, o in zip(masks, bindings):
@@ -511,3 +525,23 @@ def pack_mask(bits: np.ndarray) -> np.ndarray:
     padded = np.zeros((p, W * 64), dtype=np.uint8)
     padded[:, :n] = bits
     return np.packbits(padded, axis=1, bitorder="little").view(np.uint64).reshape(p, W)
+
+
+# ---- tagged selector entries (extension E9; numpy, no predicate logic here) ----------------------------
+def seltag(tag, ids) -> np.ndarray:
+    """Tagged selector entries for a SEL | SELOP_TAGGED call: `tag << SELTAG_SHIFT | id`, elementwise over `tag` and `ids` (scalars or
+    arrays, broadcast against each other), as a uint32 array of the broadcast shape.  tag: SELTAG_EQ (In {one value}), SELTAG_NE
+    (NotIn {one value}: a node without the key passes), SELTAG_EXISTS, SELTAG_ABSENT (the id is not looked at), SELTAG_GT, SELTAG_LT.
+    ValueError for a tag above SELTAG_LT or an id above SELTAG_ID_MASK (interned ids must stay below 2^29 in a tagged call) or below 0.
+    SELTAG_EQ with id 0 IS the unconstrained entry 0: the pod does not constrain that key.  "Matches nothing" is SEL_NEVER, as ever."""
+    t = np.asarray(tag)
+    i = np.asarray(ids)
+    if t.dtype.kind not in "iu" or i.dtype.kind not in "iu":
+        raise ValueError(f"seltag: tag and ids must be integers, got {t.dtype} and {i.dtype}")
+    t = t.astype(np.int64) if t.dtype != np.uint64 else t
+    i = i.astype(np.int64) if i.dtype != np.uint64 else i
+    if t.size and (t.min() < 0 or t.max() > L.SELTAG_LT):
+        raise ValueError(f"tag: expected SELTAG_EQ ({L.SELTAG_EQ}) ... SELTAG_LT ({L.SELTAG_LT}), got {int(t.min())} ... {int(t.max())}")
+    if i.size and (i.min() < 0 or i.max() > L.SELTAG_ID_MASK):
+        raise ValueError(f"ids: a tagged entry holds ids 0 ... {L.SELTAG_ID_MASK:#x}, got {int(i.min())} ... {int(i.max())}")
+    return ((t.astype(np.uint64) << np.uint64(L.SELTAG_SHIFT)) | i.astype(np.uint64)).astype(np.uint32)

@@ -53,6 +53,15 @@ pub const KSCHED_SELOP_EXISTS: u32 = 0x4000; // extension E8, with KSCHED_SEL al
 pub const KSCHED_SELOP_GT: u32 = 0x8000; // ... where the node carries the key and its id > the pod's entry (unsigned 32-bit)
 pub const KSCHED_SELOP_LT: u32 = 0x10000; // ... where the node carries the key and its id < the pod's entry
 pub const KSCHED_SELOP_ANY: u32 = KSCHED_SELOP_EXISTS | KSCHED_SELOP_GT | KSCHED_SELOP_LT; // at most one per call
+pub const KSCHED_SELOP_TAGGED: u32 = 0x40000; // extension E9, with KSCHED_SEL alone (no KSCHED_SELOP_ANY member beside it): every selector entry carries its own operator
+pub const KSCHED_SELTAG_SHIFT: u32 = 29; // entry = tag << KSCHED_SELTAG_SHIFT | id; compared against the node's whole 32-bit id
+pub const KSCHED_SELTAG_ID_MASK: u32 = 0x1FFFFFFF; // interned ids of a tagged call stay below 2^29
+pub const KSCHED_SELTAG_EQ: u32 = 0; // v == id (In {one value}); entry 0 is "unconstrained"
+pub const KSCHED_SELTAG_NE: u32 = 1; // v != id; a node without the key passes (NotIn {one value})
+pub const KSCHED_SELTAG_EXISTS: u32 = 2; // v != 0
+pub const KSCHED_SELTAG_ABSENT: u32 = 3; // v == 0 (DoesNotExist)
+pub const KSCHED_SELTAG_GT: u32 = 4; // v != 0 && v > id
+pub const KSCHED_SELTAG_LT: u32 = 5; // v != 0 && v < id; tags 6 and 7 (KSCHED_SEL_NEVER) pass nowhere
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
 pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
@@ -317,6 +326,15 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_SELOP_GT", KSCHED_SELOP_GT as i64),
         ("KSCHED_SELOP_LT", KSCHED_SELOP_LT as i64),
         ("KSCHED_SELOP_ANY", KSCHED_SELOP_ANY as i64),
+        ("KSCHED_SELOP_TAGGED", KSCHED_SELOP_TAGGED as i64),
+        ("KSCHED_SELTAG_SHIFT", KSCHED_SELTAG_SHIFT as i64),
+        ("KSCHED_SELTAG_ID_MASK", KSCHED_SELTAG_ID_MASK as i64),
+        ("KSCHED_SELTAG_EQ", KSCHED_SELTAG_EQ as i64),
+        ("KSCHED_SELTAG_NE", KSCHED_SELTAG_NE as i64),
+        ("KSCHED_SELTAG_EXISTS", KSCHED_SELTAG_EXISTS as i64),
+        ("KSCHED_SELTAG_ABSENT", KSCHED_SELTAG_ABSENT as i64),
+        ("KSCHED_SELTAG_GT", KSCHED_SELTAG_GT as i64),
+        ("KSCHED_SELTAG_LT", KSCHED_SELTAG_LT as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
         ("KSCHED_APPLY_WHILE_FIT", KSCHED_APPLY_WHILE_FIT as i64),
