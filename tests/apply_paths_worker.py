@@ -32,6 +32,20 @@ on the oracle's masks -- two hard chains and a soft chain whose last link carrie
 last_link_binding) -- and case_sizes enqueues the soft chain with PICK_PACK behind its queued applies and updates, no host wait, while
 the scratch mask shrinks in need to one node and regrows.  Their input conditions (assert_pack_input_condition,
 assert_chain_input_conditions) are asserted from the restatements, so also without a GPU.  No expected value comes from the device.
+
+The operator and the tagged selector calls (KSCHED_SELOP_EXISTS / _GT / _LT -> k_eval_selop, KSCHED_SELOP_TAGGED -> k_eval_seltag) answer the
+selector term alone from the label columns, and a pick inside one reads the columns and node records an apply has just written.
+snapshot() carries a tagged copy of the selector table (S["tsel"]: every id entry under one of the six tags, drawn uniformly by a generator
+of its own).  check_matrix runs, once per predicate set with SEL and in its reduced form too: the bare masks of the three operators on
+S["sel"] and of the tagged call on S["tsel"] through ksched_eval, against tests/selop_ref.py and tests/seltag_ref.py (selector_masks);
+S["sel"] under the tagged call against the oracle's SEL-only mask; and chain (c) of selector_chain_restated on one mask filled with ones --
+the other predicates, the tagged call with AND, EXISTS with AND-NOT, GT with OR, LT of the table rolled by one pod with the soft AND --
+compared after every link, its last link carrying each pick in turn ("selchain-<pick>" in `seen`) against last_link_binding on the
+expected mask and the restated columns.  The ten-key and the nine-key (list-key) snapshots take both key passes of either kernel.
+case_sizes enqueues chain (c) with PICK_SPREAD behind its soft chain with no host wait: 3000 pods at 50 000 and 60 000 nodes are the only
+standing operator calls with two pod tiles per block.  Their input conditions (assert_selector_input_conditions: rows neither full nor
+empty, pods constrained through negated tags only, all tags present, pods constraining keys of both passes, what every link changes) are
+asserted from the references, so also without a GPU; the new legs draw nothing from `rng`.
 """
 from __future__ import annotations
 
@@ -42,10 +56,11 @@ import numpy as np
 import torch
 
 from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, PICK_BESTFIT, PICK_PACK, PICK_SAMPLED, PICK_SPREAD,
-                                             PICK_UNIFORM, SEL, SEL_NEVER, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth, unpack_mask)
+                                             PICK_UNIFORM, SEL, SEL_NEVER, SELOP_EXISTS, SELOP_GT, SELOP_LT, SELOP_TAGGED, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth,
+                                             unpack_mask)
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact  # (the two other rules on an admit round's inputs: admit_round_conditions)
-from tests import combine_ref, soft_ref
+from tests import combine_ref, selop_ref, seltag_ref, soft_ref
 from tests.admit_ref import admitted_behind_deferred, apply_exact, longest_segment
 from tests.knife_edges import sampled as sampled_from_bits  # ksched_pick's rule for PICK_SAMPLED on a [p, n] table of bits
 from tests.pack_ref import pack_pick_listed
@@ -102,13 +117,25 @@ def snapshot(kind, N, P, seed):
         preds = [FIT | SEL]
     else:
         raise ValueError(kind)
+    # the tagged call reads 29-bit ids (and the tag in an entry's top three bits): the largest id of these snapshots is 63 000, at 60 000 nodes
+    assert int(lab.max(initial=0)) < 1 << 29 and int(sel[sel != SEL_NEVER].max(initial=0)) < 1 << 29, f"{kind} N={N}: an id at or above 2^29"
     return dict(kind=kind, N=N, P=P, cpu=c.avail_cpu.copy(), mem=c.avail_mem.copy(), lab=np.ascontiguousarray(lab), tnt=tnt,
                 rc=c.req_cpu, rm=c.req_mem, sel=np.ascontiguousarray(sel), tol=tol, preds=preds, indexed=kind != "unindexed",
                 smp5=rng.integers(0, N + 2, (P, 5)).astype(np.uint32), smp3=rng.integers(0, N, (P, 3)).astype(np.uint32),
                 # full-range 32-bit draws for the uniform pick, from a generator of their own: every other value is what it was without them
                 smpU=np.random.default_rng([seed, 0x55]).integers(0, 1 << 32, (P, 5), dtype=np.uint64).astype(np.uint32),
                 # and for the spread pick: 64 columns, of which a leg reads the first d
-                smpS=np.random.default_rng([seed, 0x5E]).integers(0, 1 << 32, (P, 64), dtype=np.uint64).astype(np.uint32))
+                smpS=np.random.default_rng([seed, 0x5E]).integers(0, 1 << 32, (P, 64), dtype=np.uint64).astype(np.uint32),
+                # and for the tagged call (KSCHED_SELOP_TAGGED): the selector table with a tag per entry, likewise from a generator of its own
+                tsel=tagged_table(np.ascontiguousarray(sel), np.random.default_rng([seed, 0xE9])))
+
+
+def tagged_table(sel, g):
+    """`sel` as a table of tagged entries (tests/seltag_ref.entry): every entry that constrains its key with an id -- neither 0 nor
+    SEL_NEVER -- gets one of the six tags, drawn uniformly from `g`; 0 stays "not constrained", SEL_NEVER stays what it is (tag 7)"""
+    tags = g.integers(0, len(seltag_ref.TAGS), sel.shape)
+    named = (sel != 0) & (sel != SEL_NEVER)
+    return np.ascontiguousarray(np.where(named, seltag_ref.entry(tags, sel), sel).astype(np.uint32))
 
 
 def set_nodes(ev, S, cpu, mem):
@@ -263,6 +290,111 @@ def assert_chain_input_conditions(S, feas, fit, cpu, mem, soft, what):
     assert moved >= 0.15 and rejected >= 0.30, msg
 
 
+# ---- the operator and the tagged selector calls (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED): the bare masks and chain (c), from
+# tests/selop_ref.py and tests/seltag_ref.py on the label columns and from the oracle's FIT / TAINT mask on the restated columns
+assert (SELOP_EXISTS, SELOP_GT, SELOP_LT, SELOP_TAGGED) == (selop_ref.EXISTS, selop_ref.GT, selop_ref.LT, seltag_ref.TAGGED)
+SELOPS = ((SELOP_EXISTS, "exists"), (SELOP_GT, "gt"), (SELOP_LT, "lt"))
+_selchains = [0]  # selector chains run so far in this process: the last link's pick and the mask's layout go by it
+_POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+
+
+def row_popcounts(m):
+    """set bits per row of packed rows"""
+    return _POP8[np.ascontiguousarray(m).view(np.uint8)].sum(axis=1, dtype=np.int64)
+
+
+def _in_pod_blocks(fn, entries, n, cells=1 << 25):
+    """fn(entries [keys][pods]) -> packed rows, in blocks of pods: the restatements hold [pods, n] tables, and the sizes case has 3000 x 60 000"""
+    step = max(1, cells // max(int(n), 1))
+    return np.concatenate([fn(np.ascontiguousarray(entries[:, lo:lo + step])) for lo in range(0, entries.shape[1], step)])
+
+
+def selector_masks(S):
+    """the expected bare masks of the snapshot's operator and tagged calls: {SELOP_EXISTS, SELOP_GT, SELOP_LT: tests/selop_ref.py on
+    S["sel"]; "tagged": tests/seltag_ref.py on S["tsel"]; "lt-rolled": SELOP_LT on rolled_sel(S, ROLLS[0]), the operand of chain (c)'s last
+    link}.  They depend on the label columns and the two tables alone, which no apply and no update of cpu / mem moves: computed once and
+    kept beside the three arrays they were computed from -- a caller that hands on a copy of S with other labels or another table (dict(S,
+    lab=...), as tests/test_gpu_node_labels.py does after a label update) gets masks of its own; read-only from then on"""
+    lab, sel, tsel, N = S["lab"], S["sel"], S["tsel"], S["N"]
+    kept = S.get("_selector_masks")
+    if kept is None or kept[0] is not lab or kept[1] is not sel or kept[2] is not tsel:
+        assert int(lab.max(initial=0)) < 1 << 29 and int(sel[sel != SEL_NEVER].max(initial=0)) < 1 << 29, "an id at or above 2^29"
+        m = {op: _in_pod_blocks(lambda e, op=op: selop_ref.selop_mask(lab, e, op), sel, N) for op, _ in SELOPS}
+        m["tagged"] = _in_pod_blocks(lambda e: seltag_ref.seltag_mask(lab, e), tsel, N)
+        m["lt-rolled"] = _in_pod_blocks(lambda e: selop_ref.selop_mask(lab, e, SELOP_LT), rolled_sel(S, ROLLS[0]), N)
+        for a in m.values():
+            a.setflags(write=False)
+        S["_selector_masks"] = kept = (lab, sel, tsel, m)
+    return kept[3]
+
+
+def selector_chain_restated(S, cpu, mem, preds):
+    """chain (c) on the columns cpu / mem: -> dict(first = the flags of link 1, links = the mask after each of the five links):
+      1  preds & ~SEL (FIT alone where that is empty), plain: the oracle's mask;
+      2  SEL | SELOP_TAGGED | COMBINE_AND with S["tsel"];
+      3  SEL | SELOP_EXISTS | COMBINE_ANDNOT with S["sel"] -- DoesNotExist;
+      4  SEL | SELOP_GT | COMBINE_OR;
+      5  SEL | SELOP_LT | COMBINE_AND | COMBINE_SOFT with the table rolled by ROLLS[0] pods (pod i prefers what lies below the ids pod
+         i + 1 names), the link that carries a pick
+    -- tests/combine_ref.py / tests/soft_ref.py on selector_masks.  Link 5 on S["sel"] itself could change no row: what link 4 ORs in lies
+    above the pod's ids and what link 3 left lacks a constrained key, so the AND with "below the same ids" is empty for every constrained
+    pod and the soft tier is dropped (0.0 % of the rows changed on every committed seed).  With another pod's entries it narrows, is
+    dropped and changes rows like the soft tiers of the other chains."""
+    N, m = S["N"], selector_masks(S)
+    first = (preds & ~SEL) or FIT
+    l1 = oracle_mask(S, cpu, mem, first)
+    l2 = combine_ref.combine(l1, m["tagged"], COMBINE_AND, N)
+    l3 = combine_ref.combine(l2, m[SELOP_EXISTS], COMBINE_ANDNOT, N)
+    l4 = combine_ref.combine(l3, m[SELOP_GT], COMBINE_OR, N)
+    l5 = soft_ref.soft_combine(l4, m["lt-rolled"], COMBINE_AND, N)
+    return dict(first=first, links=(l1, l2, l3, l4, l5))
+
+
+def assert_selector_input_conditions(S, chain, what):
+    """the operator and the tagged legs cannot pass vacuously -- conditions on the references, each printed in words of its own:
+    under each operator and under the tagged table half or more of the constrained rows (pods with a non-zero entry) are neither full nor
+    empty; a tenth or more of the pods are constrained through negated tags (NE / ABSENT) only -- the rows in which valid-bits applied on
+    the wrong side of the negation would set padding bits; all six tags and SEL_NEVER occur; on a snapshot of more than eight keys a tenth
+    or more of the pods constrain a key below 8 and a key at 8 or above, so both key passes shape the row; and every link of chain (c)
+    changes the mask of 5 % of the rows or more (link 1: against the all-valid rows)"""
+    N, m = S["N"], selector_masks(S)
+    sel, tsel = S["sel"], S["tsel"]
+    con = (sel != 0).any(axis=0)
+    assert np.array_equal(con, (tsel != 0).any(axis=0)) and con.any(), what
+
+    def mixed(mask):
+        cnt = row_popcounts(mask)[con]
+        return float(((cnt > 0) & (cnt < N)).mean())
+    shares = [mixed(m[op]) for op, _ in SELOPS] + [mixed(m["tagged"])]
+    msg = (f"{what}: of the constrained rows {', '.join(f'{100 * x:.1f} % ({name})' for x, name in zip(shares, ('exists', 'gt', 'lt', 'tagged')))} "
+           f"are neither full nor empty")
+    print(msg)
+    assert min(shares) >= 0.50, msg
+    tag = tsel >> np.uint32(seltag_ref.SHIFT)
+    named = (tsel != 0) & (tsel != SEL_NEVER)
+    negated = named & ((tag == seltag_ref.NE) | (tag == seltag_ref.ABSENT))
+    only = float(((tsel != 0).any(axis=0) & (negated == (tsel != 0)).all(axis=0)).mean())
+    by_tag = np.bincount(tag[named].astype(np.int64), minlength=8)
+    never = int((tsel == SEL_NEVER).sum())
+    msg = (f"{what}: the tagged table constrains {100 * only:.1f} % of the pods through NE / ABSENT entries only; entries by tag (eq, ne, exists, absent, gt, lt) = "
+           f"{by_tag[:6].tolist()}, SEL_NEVER {never}")
+    print(msg)
+    assert only >= 0.10 and (by_tag[:6] > 0).all() and by_tag[6:].sum() == 0 and never > 0, msg
+    if sel.shape[0] > 8:
+        both = float(((sel[:8] != 0).any(axis=0) & (sel[8:] != 0).any(axis=0)).mean())
+        msg = f"{what}: {100 * both:.1f} % of the pods constrain a key below 8 and a key at 8 or above"
+        print(msg)
+        assert both >= 0.10, msg
+    prev = selop_ref.selop_mask(S["lab"], None, SELOP_EXISTS, p=1)  # the all-valid row
+    changed = []
+    for cur in chain["links"]:
+        changed.append(float((cur != prev).any(axis=1).mean()))
+        prev = cur
+    msg = f"{what}: the selector chain's links change {', '.join(f'{100 * x:.1f}' for x in changed)} % of the rows"
+    print(msg)
+    assert min(changed) >= 0.05, msg
+
+
 def explain_pairs(rng, P, N, n_pairs=4000):
     return rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
 
@@ -281,6 +413,8 @@ def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sample
             assert_spread_input_condition(S, feas, bind_p5, w)
             assert_pack_input_condition(S, feas, pack_restated(S, feas, cpu, mem, 5), bind_p5, w)
             assert_chain_input_conditions(S, feas, oracle_mask(S, cpu, mem, FIT), cpu, mem, soft_chain_restated(S, cpu, mem, feas), w)
+            if preds & SEL:  # the operator and the tagged legs: the same expectations, from the references alone
+                assert_selector_input_conditions(S, selector_chain_restated(S, cpu, mem, preds), w)
         if k == 0 and hand_on == "sampled":
             out_b = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"] if preds & TAINT else None, S["rc"], S["rm"], S["sel"],
                                       S["tol"] if preds & TAINT else None, S["smp5"], preds | PICK_SAMPLED, want_mask=False)[2]
@@ -307,6 +441,13 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
     with COMBINE_AND == the oracle's mask; (b) FIT, the predicates with COMBINE_ANDNOT == combine_ref (fit & ~feasible), the predicates
     with COMBINE_OR == the oracle's fit mask again; and the soft chain of soft_chain_restated on the hard mask, whose last link carries a
     pick (LAST_LINKS in turn; names "chain-<pick>" go into `seen`) compared with last_link_binding on the expected tier-2 mask and cpu / mem.
+    The operator and the tagged selector calls (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED), once per predicate set that has SEL
+    (not per kernel choice: plan_eval ignores KSCHED_OPT_KERNEL for them; last_kernel "selop" / "seltag" is asserted), reduced or not:
+    (a) the bare masks through ksched_eval against selector_masks (tests/selop_ref.py on S["sel"], tests/seltag_ref.py on S["tsel"]);
+    (b) S["sel"] under SEL | SELOP_TAGGED == the oracle's SEL-only mask; (c) the chain of selector_chain_restated on one mask filled with
+    ones, packed in one predicate set and pitched in the next, compared after every link, whose last link -- LT under the soft AND --
+    carries a pick (LAST_LINKS in turn over the chains of a process; names "selchain-<pick>" go into `seen`) compared with
+    last_link_binding on the expected mask and cpu / mem, the words behind the batch untouched.
     The new legs compare; they hand nothing on.
     -> the device bindings, under the first predicate set, of the pick `hand_on` names: "sampled", "uniform" or "spread" (a real
     evaluation's bindings for the next apply); None with hand_on=None"""
@@ -419,6 +560,48 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
             run(preds | PICK_PACK, smpS5, expect_b=bind_k5, label=f"{k} pack d=5")
             assert ev.last_pick == "pack", f"{w} {k}: a pack pick beside the mask ran as {ev.last_pick}"
             chains(k, n_kernel)
+        if preds & SEL:
+            # the operator and the tagged calls, once per predicate set: plan_eval ignores KSCHED_OPT_KERNEL for them, so the choice stays
+            # whatever the loop above set last
+            sm, sc = selector_masks(S), selector_chain_restated(S, cpu, mem, preds)
+            if input_condition:
+                assert_selector_input_conditions(S, sc, w)
+            # (a) the bare masks through the host form
+            for op, name in SELOPS:
+                r = ev.eval(rc, rm, sel, None, None, SEL | op)
+                assert np.array_equal(r.feasible, sm[op]), f"{w} operator {name}: pods {np.nonzero((r.feasible != sm[op]).any(axis=1))[0][:5]} differ from selop_ref"
+                assert ev.last_kernel == "selop" and ev.last_pick == "none", f"{w} operator {name}: ran as {ev.last_kernel} / {ev.last_pick}"
+            r = ev.eval(rc, rm, S["tsel"], None, None, SEL | SELOP_TAGGED)
+            assert np.array_equal(r.feasible, sm["tagged"]), f"{w} tagged: pods {np.nonzero((r.feasible != sm['tagged']).any(axis=1))[0][:5]} differ from seltag_ref"
+            assert ev.last_kernel == "seltag" and ev.last_pick == "none", f"{w} tagged: ran as {ev.last_kernel} / {ev.last_pick}"
+            # (b) the plain table under the tagged call -- an untagged entry is tag EQ, SEL_NEVER is tag 7 -- is the oracle's SEL-only mask
+            r = ev.eval(rc, rm, sel, None, None, SEL | SELOP_TAGGED)
+            want_eq = oracle_mask(S, cpu, mem, SEL)
+            assert np.array_equal(r.feasible, want_eq), f"{w} the plain table under SELOP_TAGGED: pods {np.nonzero((r.feasible != want_eq).any(axis=1))[0][:5]} differ from the oracle"
+            assert ev.last_kernel == "seltag", f"{w} the plain table under SELOP_TAGGED: ran as {ev.last_kernel}"
+            # (c) the hard chain with a soft last link that carries a pick, on one mask filled with ones
+            n_chain = _selchains[0]
+            _selchains[0] += 1
+            pick, lay = LAST_LINKS[n_chain % len(LAST_LINKS)], "pitched" if n_chain % 2 else "packed"
+            flag, smp = link_smp[pick]
+            M, out = ev.alloc_mask(P, pitched=n_chain % 2 == 1), torch.full((P + 4,), -7, dtype=torch.int32, device=DEV)
+            M.fill_(-1)
+            c = f"{lay} selector chain"
+            link(M, sc["first"], sc["links"][0], f"{c}, link 1 ({sc['first']:#x})")
+            link(M, SEL | SELOP_TAGGED | COMBINE_AND, sc["links"][1], f"{c}, link 2 (tagged, AND)", t(S["tsel"], np.int32))
+            assert ev.last_kernel == "seltag", f"{w} {c}, link 2: ran as {ev.last_kernel}"
+            link(M, SEL | SELOP_EXISTS | COMBINE_ANDNOT, sc["links"][2], f"{c}, link 3 (EXISTS, AND-NOT)")
+            assert ev.last_kernel == "selop", f"{w} {c}, link 3: ran as {ev.last_kernel}"
+            link(M, SEL | SELOP_GT | COMBINE_OR, sc["links"][3], f"{c}, link 4 (GT, OR)")
+            assert ev.last_kernel == "selop" and ev.last_pick == "none", f"{w} {c}, link 4: ran as {ev.last_kernel} / {ev.last_pick}"
+            name = link(M, SEL | SELOP_LT | COMBINE_AND | COMBINE_SOFT | flag, sc["links"][4], f"{c}, link 5 (LT, soft AND) with the {pick} pick", soft_sel_t[0], smp, out[:P])
+            assert ev.last_kernel == "selop", f"{w} {c}, link 5: ran as {ev.last_kernel}"
+            assert name == {"pack": "pack", "spread": "spread", "uniform": "uniform"}.get(pick, "from-mask"), f"{w}: the {pick} pick of an operator call ran as {name}"
+            b = out.cpu().numpy()
+            want_b = last_link_binding(S, sc["links"][4], cpu, mem, pick)
+            assert np.array_equal(b[:P], want_b), f"{w} {c}: {int((b[:P] != want_b).sum())} bindings of the {pick} pick in the last link differ"
+            assert (b[P:] == -7).all(), f"{w} {c}: the pick wrote past the batch"
+            seen.add(f"selchain-{pick}")
         ev.set_kernel("auto")
         # bindings only: the sampled pick is its own launch ("select"), best fit reads no mask
         run(preds | PICK_SAMPLED, S["smp5"], want_mask=False, expect_b=bind_s, label="sampled, bindings only")
@@ -661,7 +844,7 @@ def case_single(spec):
     want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask", "uniform", "spread"},
             "many-keys": {"select", "fused", "bestfit-rows", "from-mask", "uniform", "spread"},
             "list-key": {"select", "bestfit-rows", "from-mask", "uniform", "spread"},
-            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind] | {"pack"} | {f"chain-{p}" for p in LAST_LINKS}
+            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind] | {"pack"} | {f"chain-{p}" for p in LAST_LINKS} | {f"selchain-{p}" for p in LAST_LINKS}
     assert want <= seen, f"{kind}: picks reached {sorted(seen)}, missing {sorted(want - seen)}"
     print(f"{kind}: picks reached {sorted(seen)}")
     ev.close()
@@ -685,7 +868,10 @@ def sizes_step(step, N):
     it gave back, and the big one has APPLIED, DEFERRED, UNBOUND and BAD_NODE.
     chain: what the soft chain of check_matrix leaves on the columns after all of it -- sel (the rolled selector tables), links (the mask
     after the hard call, tier 1 and tier 2) and bind (tests/pack_ref.py, d = 5, on the tier-2 mask and those columns); from 1025 nodes on
-    with assert_chain_input_conditions' floors on the tiers and on the bindings the tiers move."""
+    with assert_chain_input_conditions' floors on the tiers and on the bindings the tiers move.
+    selchain: what chain (c) of check_matrix (selector_chain_restated, with SIZES_PREDS) leaves on the same columns -- first (the flags of
+    link 1), links (the mask after each of the five links) and bind (tests/spread_ref.py, d = 5, on the last mask and those columns);
+    from 1025 nodes on with assert_selector_input_conditions' floors."""
     P, WF = SIZES_PODS, _lib.APPLY_WHILE_FIT
     S = snapshot("taints", N, P, 0xC0 + step)
     cpu, mem = S["cpu"], S["mem"]
@@ -738,15 +924,23 @@ def sizes_step(step, N):
     if N >= 1025:
         assert_chain_input_conditions(S, feas, None, cpu, mem, soft, f"{what} chain")
     chain = dict(sel=soft["sel"], links=(feas, soft["t1"], soft["t2"]), bind=pack_restated(S, soft["t2"], cpu, mem, 5))
-    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem, chain=chain)
+    # and chain (c) behind that: the operator and the tagged calls, PICK_SPREAD in the last link
+    sc = selector_chain_restated(S, cpu, mem, SIZES_PREDS)
+    if N >= 1025:
+        assert_selector_input_conditions(S, sc, f"{what} selchain")
+    selchain = dict(first=sc["first"], links=sc["links"], bind=spread_restated(S, sc["links"][4], cpu, mem, 5))
+    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem, chain=chain, selchain=selchain)
 
 
 def case_sizes(spec):
     """one ctx through snapshots of 50 000 -> 300 -> 4097 -> 1 -> 60 000 nodes (the last one past the apply scratch's size): after each
     ksched_set_nodes what sizes_step lists -- an apply, an update of nodes in the tiles it touched, a second apply, a second update, an
     apply with WHILE_FIT (at 4097 nodes a second, four times as long, straight behind it) -- and behind those the soft chain of
-    check_matrix with PICK_PACK in its last link (the mask copied on the stream after every link), enqueued with no host wait in between;
-    then the chain's masks and bindings against sizes_step's, the statuses of every apply, the columns, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused
+    check_matrix with PICK_PACK in its last link (the mask copied on the stream after every link) and, on a second mask, chain (c) -- the
+    tagged call and the three operators, PICK_SPREAD in its last link, copied likewise --, enqueued with no host wait in between: with
+    3000 pods at 50 000 and 60 000 nodes the only standing operator calls whose blocks walk two pod tiles (47 tiles in 24 block rows: the
+    last block leaves its second slot at `first >= p`), and the only ones behind which the scratch mask is resized under queued work;
+    then the chains' masks and bindings against sizes_step's, the statuses of every apply, the columns, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused
     evaluation with the sampled pick in its waves form"""
     plans = [sizes_step(step, N) for step, N in enumerate(spec["nodes"])]  # (every input condition, before anything runs on the device)
     assert sum(len(q["applies"]) == 4 for q in plans) == 1, "no step reallocates the admit scratch"
@@ -758,8 +952,9 @@ def case_sizes(spec):
         sts, keep = [], []
         # the chain's operands and outputs, on the device before anything is enqueued (packed rows on even steps, pitched on odd ones)
         P = S["P"]
-        M = ev.alloc_mask(P, pitched=step % 2 == 1)
-        out = torch.full((P + 4,), -7, dtype=torch.int32, device=DEV)
+        M, M2 = ev.alloc_mask(P, pitched=step % 2 == 1), ev.alloc_mask(P, pitched=step % 2 == 0)
+        out, out2 = (torch.full((P + 4,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        tsel_t = t(S["tsel"], np.int32)
         pods = (t(S["rc"], np.int64), t(S["rm"], np.int64))
         sels = [t(x, np.int32) for x in (S["sel"],) + q["chain"]["sel"]]
         tol_t, smp_t = t(S["tol"], np.int64), t(np.ascontiguousarray(S["smpS"][:, :5]), np.int32)
@@ -782,8 +977,29 @@ def case_sizes(spec):
         ev.eval_device(*pods, sels[2], None, smp_t, SEL | COMBINE_ANDNOT | COMBINE_SOFT | PICK_PACK, out_feasible=M, out_binding=out[:P])
         assert ev.last_pick == "pack", ev.last_pick
         links.append(M)
+        # chain (c) behind it, on the second mask (the other layout), still with no host wait
+        sc = q["selchain"]
+        M2.fill_(-1)
+        ev.eval_device(*pods, None, tol_t if sc["first"] & TAINT else None, None, sc["first"], out_feasible=M2)
+        links2 = [M2.clone()]
+        ev.eval_device(*pods, tsel_t, None, None, SEL | SELOP_TAGGED | COMBINE_AND, out_feasible=M2)
+        assert ev.last_kernel == "seltag", ev.last_kernel
+        links2.append(M2.clone())
+        ev.eval_device(*pods, sels[0], None, None, SEL | SELOP_EXISTS | COMBINE_ANDNOT, out_feasible=M2)
+        links2.append(M2.clone())
+        ev.eval_device(*pods, sels[0], None, None, SEL | SELOP_GT | COMBINE_OR, out_feasible=M2)
+        links2.append(M2.clone())
+        ev.eval_device(*pods, sels[1], None, smp_t, SEL | SELOP_LT | COMBINE_AND | COMBINE_SOFT | PICK_SPREAD, out_feasible=M2, out_binding=out2[:P])
+        assert ev.last_kernel == "selop" and ev.last_pick == "spread", (ev.last_kernel, ev.last_pick)
+        links2.append(M2)
         torch.cuda.synchronize()
         what = f"step {step} N={N}"
+        for k, (got, want) in enumerate(zip(links2, sc["links"]), 1):
+            got = got.contiguous().cpu().numpy().view(np.uint64)
+            assert np.array_equal(got, want), f"{what}: the selector chain behind the queued changes, link {k}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"
+        b = out2.cpu().numpy()
+        assert np.array_equal(b[:P], sc["bind"]) and (b[P:] == -7).all(), \
+            f"{what}: the selector chain's spread bindings: {int((b[:P] != sc['bind']).sum())} differ"
         for name, got, want in zip(("the hard mask", "tier 1", "tier 2"), links, q["chain"]["links"]):
             got = got.contiguous().cpu().numpy().view(np.uint64)
             assert np.array_equal(got, want), f"{what}: the chain behind the queued changes, {name}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"

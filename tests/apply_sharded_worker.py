@@ -431,7 +431,10 @@ def case_paths(spec):
     the key's lists -- the paths that read the node records the gathered commit writes -- and the uniform and the spread pick; the spread
     pick ranks by the columns that commit has just written on every replica (walk_paths); and check_matrix's pack legs (the pack pick reads
     the same columns through a kernel of its own) and combining chains (KSCHED_COMBINE_*, KSCHED_COMBINE_SOFT: each evaluates into the
-    replica's scratch mask), against tests/pack_ref.py, tests/combine_ref.py and tests/soft_ref.py"""
+    replica's scratch mask), against tests/pack_ref.py, tests/combine_ref.py and tests/soft_ref.py; and its operator and tagged selector
+    legs (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED): the bare masks, the plain table under the tagged call against the
+    oracle, and the selector chain whose last link's pick reads the columns the gathered commit has just written, against
+    tests/selop_ref.py and tests/seltag_ref.py -- all five picks of that link are reached in every run (asserted)"""
     from tests.apply_paths_worker import check_matrix
     n = spec["n"]
     seen = set()
@@ -452,8 +455,10 @@ def case_paths(spec):
     k = walk_paths(spec, begin, lambda q, S, cpu, mem, what, rng, **kw: check_matrix(R[0].evs[q], S, cpu, mem, seen, what, rng, reduced=True, **kw),
                    apply, lambda: R[0].close())
     from tests.apply_paths_worker import LAST_LINKS
-    # (check_matrix's pack legs and combining chains run on every replica too: the soft chain's last link takes each pick in turn)
-    assert {"select", "fused", "bestfit-rows", "uniform", "spread", "pack"} | {f"chain-{p}" for p in LAST_LINKS} <= seen, f"picks reached {sorted(seen)}"
+    # (check_matrix's pack legs, combining chains and selector chains run on every replica too: the soft chain's and the selector chain's
+    # last link take each pick in turn)
+    assert {"select", "fused", "bestfit-rows", "uniform", "spread", "pack"} | {f"chain-{p}" for p in LAST_LINKS} | {f"selchain-{p}" for p in LAST_LINKS} <= seen, \
+        f"picks reached {sorted(seen)}"
     print(f"{k} sharded applies, picks reached {sorted(seen)}")
 
 

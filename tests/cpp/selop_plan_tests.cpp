@@ -233,6 +233,19 @@ static void the_launch() {
     CHECK(l.gx == 1 && l.pod_tiles == (1u << 26) && l.gy == 2048 && l.pod_tiles_per_block == (1u << 15));
     l = plan_selop_launch(1000, 1u << 26, 8);  // the most nodes: one block row
     CHECK(l.gx == (1u << 22) && l.gy == 1 && l.pod_tiles == 16 && l.pod_tiles_per_block == 16);
+    // the geometry the standing legs rely on (tests/apply_paths_worker.py case_sizes, tests/test_gpu_selop.py): 3000 pods over 50 000 and
+    // 60 000 nodes -- 47 tiles, two a block, 24 block rows: 48 slots, so the last block breaks at `first >= p` --; 130 pods over 1024
+    // column blocks; and a walk's 2000 pods over 4097 nodes with ten keys, which stays at one tile a block and takes two passes
+    l = plan_selop_launch(3000, 782, 8);
+    CHECK(l.gx == 49 && l.pod_tiles == 47 && l.pod_tiles_per_block == 2 && l.gy == 24 && l.passes == 1);
+    l = plan_selop_launch(3000, 938, 8);
+    CHECK(l.gx == 59 && l.pod_tiles == 47 && l.pod_tiles_per_block == 2 && l.gy == 24 && l.passes == 1);
+    l = plan_selop_launch(130, 16384, 2);
+    CHECK(l.gx == 1024 && l.pod_tiles == 3 && l.gy == 2 && l.pod_tiles_per_block == 2 && l.passes == 1);
+    l = plan_selop_launch(2000, 65, 10);
+    CHECK(l.gx == 5 && l.pod_tiles == 32 && l.gy == 32 && l.pod_tiles_per_block == 1 && l.passes == 2);
+    walk(3000, 782, 784, 8);
+    walk(130, 16384, 16384, 2);
     l = plan_selop_launch(0, 5, 8);
     CHECK(l.gx == 0 && l.gy == 0 && l.passes == 0);  // nothing to launch
     l = plan_selop_launch(5, 0, 8);

@@ -11,7 +11,12 @@ Likewise the pack legs (KSCHED_PICK_PACK) and the combining chains (KSCHED_COMBI
 pack restatement binds 35 % of the pods or more to another node than their candidate 0 and than the spread restatement; either soft tier
 narrows 20 %, is dropped for 10 %, finds 1 % empty and changes 10 % of the rows or more; the pack pick on the tier-2 mask differs from the
 hard mask's for 15 % of the pods or more; fit & ~feasible has a set bit in 30 % of the rows or more; a stale column would change a pack
-binding of the matrix's legs; and the sizes plan's chain meets the same floors at its three large snapshots."""
+binding of the matrix's legs; and the sizes plan's chain meets the same floors at its three large snapshots.
+Likewise the operator and the tagged selector legs (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED; assert_selector_input_conditions, on
+tests/selop_ref.py and tests/seltag_ref.py alone): at 1025 nodes or more, under each operator and under the tagged table half of the
+constrained rows or more are neither full nor empty; a tenth of the pods or more are constrained through NE / ABSENT entries only; all six
+tags and SEL_NEVER occur; on the nine- and ten-key snapshots a tenth of the pods or more constrain a key below 8 and a key at 8 or above;
+every link of the selector chain changes 5 % of the rows or more -- in the single walks, the sizes plan and the replicated walk."""
 import numpy as np
 import pytest
 
@@ -45,6 +50,9 @@ def test_single_ctx_matrix_inputs(kind, capsys):
     assert [out.count(f"soft tier {tier} (") for tier in (1, 2)] == [sets, sets]
     assert out.count("on the tier-2 mask binds") == sets and out.count("of the rows of fit & ~feasible have a set bit") == sets
     assert out.count("pack bindings") == out.count("would change")
+    # the operator and the tagged legs' conditions, per predicate set of the same node counts (every predicate set has SEL)
+    assert out.count("are neither full nor empty") == out.count("through NE / ABSENT entries only") == out.count("the selector chain's links change") == sets
+    assert out.count("constrain a key below 8 and a key at 8 or above") == (sets if kind in ("many-keys", "list-key") else 0)
     # the admit round of every node count, with the floors walk_single sets on it (admit_round_conditions), printed in words of its own
     assert [out.count(f"{kind} N={N} admit round (") > 0 for N in NODES] == [True] * len(NODES)
     assert out.count("statuses (applied, unbound, not ok, deferred, overflow, bad node)") == len(NODES)
@@ -66,10 +74,16 @@ def test_sizes_case_inputs(capsys):
     big_steps = sum(N >= 1025 for N in SIZES["nodes"])
     assert big_steps == 3 and [out.count(f"chain: soft tier {tier} (") for tier in (1, 2)] == [big_steps, big_steps]
     assert out.count("chain: the pack pick (d = 5) on the tier-2 mask binds") == big_steps
+    # the selector chain behind it: the floors at the same three snapshots, expected masks and spread bindings for every step
+    assert out.count("selchain: of the constrained rows") == out.count("selchain: the tagged table constrains") == big_steps
+    assert out.count("selchain: the selector chain's links change") == big_steps
     for q in plans:
         S, c = q["S"], q["chain"]
         assert [m.shape for m in c["links"]] == [(S["P"], (S["N"] + 63) // 64)] * 3 and c["bind"].shape == (S["P"],)
         assert ((c["bind"] >= 0) == c["links"][2].any(axis=1)).all() and (c["links"][2].any(axis=1) == c["links"][0].any(axis=1)).all()
+        sc = q["selchain"]
+        assert sc["first"] == W.FIT | W.TAINT and [m.shape for m in sc["links"]] == [(S["P"], (S["N"] + 63) // 64)] * 5 and sc["bind"].shape == (S["P"],)
+        assert ((sc["bind"] >= 0) == sc["links"][4].any(axis=1)).all() and (sc["links"][4].any(axis=1) == sc["links"][3].any(axis=1)).all()  # the last link is soft
 
 
 def test_large_case_inputs(capsys):
@@ -104,6 +118,8 @@ def test_replicated_matrix_inputs(n, capsys):
     sets = 2 * (2 + 1)  # the two node counts from 1025 on, the taints snapshot's two predicate sets and the list-key snapshot's one
     assert out.count("the pack pick (d = 5) binds") == out.count("the spread pick (d = 5) binds") == sets
     assert out.count("soft tier 1 (") == out.count("soft tier 2 (") == out.count("on the tier-2 mask binds") == out.count("the pack pick (d = 5) binds")
+    assert out.count("are neither full nor empty") == out.count("through NE / ABSENT entries only") == out.count("the selector chain's links change") == sets
+    assert out.count("constrain a key below 8 and a key at 8 or above") == 2  # the list-key snapshot's nine keys, at either node count
     assert {p for big, p in handed if big} == set(W.PICKS), handed  # at 1025 nodes or more: all three within one run
     # (below 1025 a run has two snapshots: the three picks over the runs with n = 1, 2, 3)
     assert len({p for big, p in handed if not big}) == 2, handed

@@ -29,6 +29,16 @@ link carries the pack, spread, uniform, sampled and best-fit pick in turn.  So e
 after an apply, on list-key, ten-key and unindexed snapshots; the sizes case enqueues the soft chain with PICK_PACK behind its queued
 applies and updates with no host wait, while that scratch mask shrinks in need to one node and regrows to 60 000.  Floors on what the tiers
 narrow, drop, find empty and change, on the bindings they move and on fit & ~feasible are asserted from the restatements first.
+The operator and the tagged selector calls (KSCHED_SELOP_EXISTS / _GT / _LT -> k_eval_selop, KSCHED_SELOP_TAGGED -> k_eval_seltag) run once
+per predicate set in every matrix, so after every apply and on every kind of snapshot: the bare masks through ksched_eval against
+tests/selop_ref.py on the selector table and tests/seltag_ref.py on a tagged copy of it (every id entry under one of the six tags, drawn
+uniformly); the plain table under the tagged call against the oracle's SEL-only mask; and a chain on one mask filled with ones -- the other
+predicates, the tagged call with AND, EXISTS with AND-NOT, GT with OR, LT with the soft AND -- compared after every link, whose last link
+carries the pack, spread, uniform, sampled and best-fit pick in turn, compared with the pick's restatement on the expected mask and the
+restated columns.  The ten-key and the list-key snapshot take the kernels' second key pass.  The sizes case enqueues the chain with
+PICK_SPREAD behind the soft chain, still with no host wait: with 3000 pods at 50 000 and 60 000 nodes its operator kernels walk two pod
+tiles per block.  Floors on the rows that are neither full nor empty, on the pods constrained through negated tags only, on the pods that
+constrain keys of both passes and on what every link changes are asserted from the references first.
 """
 import json
 import os
@@ -65,6 +75,7 @@ def test_every_path_after_an_apply(built, kind):
     assert "'pack'" in reached, "the pack pick is not among the picks reached"
     for pick in ("pack", "spread", "uniform", "sampled", "bestfit"):
         assert f"'chain-{pick}'" in reached, f"no soft chain carried the {pick} pick in its last link"
+        assert f"'selchain-{pick}'" in reached, f"no selector chain carried the {pick} pick in its last link"
     for N in NODES:
         assert f"{kind} N={N} admit round (" in out, f"no admit round at {N} nodes"
 
@@ -76,6 +87,7 @@ def test_snapshot_sizes_and_updates_between_applies_on_one_ctx(built):
     out = run("sizes", SIZES)
     assert out.count(": admit of ") == len(SIZES["nodes"]) + 1
     assert out.count("chain: the pack pick (d = 5) on the tier-2 mask binds") == 3  # the chain's floors, at the three snapshots from 1025 nodes on
+    assert out.count("selchain: the selector chain's links change") == 3  # and the selector chain's, at the same three
 
 
 def test_a_batch_longer_than_one_stride_of_the_pod_kernels(built):

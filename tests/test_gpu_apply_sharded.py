@@ -5,7 +5,11 @@ n > 1 ranks run as n ctxs on the one GPU in ONE child process (tests/apply_shard
 the RCCL stand-in; n = 1 runs the shipped library over the real RCCL.  Only the per-process test starts two children at once.
 The "paths" case runs tests/apply_paths_worker.check_matrix in its reduced form on every replica after each sharded apply: with it the
 pack pick's legs (tests/pack_ref.py on the columns the gathered commit wrote) and the combining chains (KSCHED_COMBINE_AND / _OR / _ANDNOT
-and KSCHED_COMBINE_SOFT against tests/combine_ref.py / tests/soft_ref.py, a pick in the soft chain's last link)."""
+and KSCHED_COMBINE_SOFT against tests/combine_ref.py / tests/soft_ref.py, a pick in the soft chain's last link), and the operator and
+tagged selector calls (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED): their bare masks against tests/selop_ref.py /
+tests/seltag_ref.py, the plain table under the tagged call against the oracle, and a chain of them on one mask whose last link carries
+each of the five picks in turn on the columns the gathered commit wrote -- the first operator and tagged calls on a replica after a
+sharded apply."""
 import json
 import os
 import subprocess
@@ -67,7 +71,10 @@ def test_every_replica_evaluates_right_after_a_sharded_apply(built, n):
     every replica, against the oracle (the spread pick: tests/spread_ref.py on the columns the gathered commit must have left on that
     replica); n = 1 over the real RCCL"""
     out = run("paths", {"n": n, "nodes": PATHS_NODES}, hooks=n > 1, timeout=900)
-    assert "'spread'" in out.rsplit("picks reached", 1)[-1], "the spread pick is not among the picks reached"
+    reached = out.rsplit("picks reached", 1)[-1]
+    assert "'spread'" in reached, "the spread pick is not among the picks reached"
+    for pick in ("pack", "spread", "uniform", "sampled", "bestfit"):
+        assert f"'selchain-{pick}'" in reached, f"no selector chain carried the {pick} pick in its last link"
 
 
 def test_shards_longer_than_one_stride_of_the_pod_kernels(built):

@@ -8,8 +8,15 @@ through the multi-device sequence, a sharded apply of its gathered bindings and 
 every step the pack pick (the same draws and d; tests/pack_ref.py) and one combining chain of 2 to 4 ksched_eval_device calls on one mask --
 random predicate subsets and ops, KSCHED_COMBINE_SOFT at random, odd pitches and bases with sentinel words around the view, a random pick
 in the last link -- against tests/combine_ref.py / tests/soft_ref.py on the oracle's per-link masks; with the hooks the pack pick takes the
-spread pick's multi-device route and the chain runs on every replica after the sharded apply.  (240 s runs of the same tool:
-profiles/uniform_pick_standing_checks.txt, profiles/spread_pick_standing_checks.txt, profiles/combine_pack_standing_checks.txt.)"""
+spread pick's multi-device route and the chain runs on every replica after the sharded apply.  And at every step one operator call
+(KSCHED_SELOP_EXISTS / _GT / _LT at random) and one tagged call (KSCHED_SELOP_TAGGED: all six tags, now and then tags 6 and 7, ids at and
+beside the nodes' ids and 0, 1, 0x1FFFFFFF) against tests/selop_ref.py / tests/seltag_ref.py on the labels as the step's updates left them --
+into a sentinel-surrounded view at an odd pitch or base, about half of them as one more link on the step's combining chain, with a random
+pick -- and both through ksched_eval_begin / _end over 1 to 5 row shards (sel_stride > p); with the hooks both run on every replica after
+the sharded apply.  Asserted here: the tallies 'selop', 'seltag', 'seltag-negated-padding' (a pod constrained through NE / ABSENT only, in
+rows with padding bits) and 'selop-sharded-halves' in both runs, 'selop-on-replicas' with the hooks; 'selop-two-pass' and
+'selop-two-tiles' are recorded from a long run.  (240 s runs of the same tool: profiles/uniform_pick_standing_checks.txt,
+profiles/spread_pick_standing_checks.txt, profiles/combine_pack_standing_checks.txt, profiles/selop_seltag_standing_checks.txt.)"""
 import os
 import re
 import subprocess
@@ -37,6 +44,10 @@ def assert_new_tallies(out):
     assert tally(out, "soft-narrowed") > 0, "no soft link narrowed a row"
     assert tally(out, "soft-dropped") > 0, "no soft link was dropped for a row"
     assert tally(out, "soft-empty") > 0, "no soft link met an empty row"
+    assert tally(out, "selop") > 0, "no operator call ran"
+    assert tally(out, "seltag") > 0, "no tagged call ran"
+    assert tally(out, "seltag-negated-padding") > 0, "no tagged call had a pod constrained through NE / ABSENT only in rows with padding bits"
+    assert tally(out, "selop-sharded-halves") > 0, "no operator or tagged call went through ksched_eval_begin / _end over row shards"
 
 
 def test_fuzz_parity_short(built):
@@ -68,3 +79,4 @@ def test_fuzz_parity_short_with_the_multi_device_sequence(built):
     assert re.search(r"'spread-gathered-over-\d': [1-9]", r.stdout), "no spread pick went through the multi-device sequence"
     assert re.search(r"'pack-gathered-over-\d': [1-9]", r.stdout), "no pack pick went through the multi-device sequence"
     assert tally(r.stdout, "combine-on-replicas") > 0, "no combining chain ran on the replicas after a sharded apply"
+    assert tally(r.stdout, "selop-on-replicas") > 0, "no operator and tagged call ran on the replicas after a sharded apply"

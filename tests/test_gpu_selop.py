@@ -217,6 +217,45 @@ def test_mask_parity(ev, n, keys):
                 assert ev.last_kernel == "selop" and ev.last_pick == "none"
 
 
+def test_a_block_that_walks_more_than_one_pod_tile(ev):
+    """1024 column blocks leave two block rows for three pod tiles: the first block row walks two tiles, the second one (whose second slot
+    lies past p: the `first >= p` break) -- the smallest shape at which k_eval_selop's tile loop takes a second turn.  Every pod's entries
+    are its own, so a block that computed its first tile again, or stored a tile's rows a tile too low, gives rows that differ"""
+    n, keys, p = 16 * 64 * 1024 - 37, 2, 130
+    W = (n + 63) // 64
+    gx = (W + 15) // 16
+    want_rows = (2048 + gx - 1) // gx
+    tiles = (p + 63) // 64
+    assert gx == 1024 and want_rows == 2 < tiles == 3, "pod_tiles_per_block == 2"
+    rng = np.random.default_rng([0xE8, n, keys, p])
+    lab = IDS[rng.integers(0, IDS.size, size=(keys, n))]
+    lab[:, rng.random(n) < 0.5] = 0  # (so that EXISTS rows are neither full nor empty too)
+    lab[1] = np.where(rng.random(n) < 0.7, lab[1], IDS[rng.integers(0, IDS.size, size=n)])
+    sel = np.zeros((keys, p), dtype=np.uint32)
+    for pod in range(p):  # kind by pod: key 0, key 1, both, and now and then NEVER or nothing -- with a period of 7, so no tile repeats another
+        kind = pod % 7
+        if kind in (0, 2, 4, 5):
+            sel[0, pod] = IDS[rng.integers(1, IDS.size)]
+        if kind in (1, 2, 5, 6):
+            sel[1, pod] = IDS[rng.integers(1, IDS.size)]
+        if kind == 6 and pod % 3 == 0:
+            sel[0, pod] = SEL_NEVER
+    sel[:, 3] = 0
+    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), lab)
+    assert ev.W == W
+    cols = (zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, sel, np.int32))
+    pitch = W + 3
+    for op, name in zip(OPS, OP_IDS):
+        want = selop_ref.selop_mask(lab, sel, op)
+        assert want.shape == (p, W) and not (want[:, -1] & ~np.uint64(combine_ref.valid_bits_word(n))).any()
+        assert row_kinds(want, n)[2] >= p // 4, f"{name}: rows that are neither full nor empty"
+        # what a block that walked tile 0 twice would leave in the rows of tile 1, and one that skipped to tile 2 in those of tile 1
+        assert (want[64:128] != want[0:64]).any(axis=1).sum() >= 32 and (want[64:66] != want[128:130]).any(), f"{name}: the tiles' rows differ"
+        got = eval_into_view(ev, cols, SEL | op, n, p, pitch, 1)
+        assert np.array_equal(got, want), f"{name}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ from selop_ref"
+        assert ev.last_kernel == "selop" and ev.last_pick == "none"
+
+
 def test_no_selectors_and_no_keys_pass_every_node(ev):
     n, p = 65, 3
     lab = IDS[np.random.default_rng(0xE80).integers(0, IDS.size, size=(2, n))]

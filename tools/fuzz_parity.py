@@ -20,6 +20,14 @@ ksched_eval_device on one mask, each with a random non-empty predicate subset, i
 an even or an odd word of a buffer of sentinel words, the mask copied on the stream after every link, a random pick or none in the last link --
 against tests/combine_ref.py / tests/soft_ref.py on the oracle's per-link masks and the pick restatements on the final mask; with the hooks the same
 chain on every replica after the pack pick's sharded apply, on the columns it left,
+one operator call (KSCHED_SELOP_EXISTS / _GT / _LT at random, on the step's selector table) and one tagged call (KSCHED_SELOP_TAGGED, on a table of
+its own: all six tags, now and then tag 6 or 7, ids drawn from the nodes' ids, those ids + / - 1, and 0, 1 and 0x1FFFFFFF) at every step, over the
+batch's first 200 pods -- each into a view with sentinel words around it at pitch W, W + 1 or ksched_mask_pitch(n), about half of them as one more
+link on the final mask of the step's combining chain (a random op, KSCHED_COMBINE_SOFT at random), with a random pick or none -- against
+tests/selop_ref.py / tests/seltag_ref.py on the labels as the step's updates left them (apply_rows), tests/combine_ref.py / tests/soft_ref.py and the
+pick restatements on the resulting mask and the step's columns; both also through ksched_eval_begin / _end over 1 to 5 row shards with the uniform
+pick (sel_stride > p); where the whole batch gives a block of the operator kernel two pod tiles to walk, one more operator call over all its
+pods, compared on 1024 rows or fewer; with the hooks both calls on every replica after the pack pick's sharded apply,
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
 ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts; about one apply in four with KSCHED_APPLY_WHILE_FIT, against
 tests/admit_ref.py -- the sharded entry point must then refuse with KSCHED_E_UNSUPPORTED and leave every replica as it was; tallies
@@ -30,7 +38,8 @@ ksched_comm_create_local, ksched_eval_begin on every replica, ksched_gather_buff
 A case's decisions come from three generators seeded from the case seed: `r` draws what the tool has always drawn, in the same order (a
 case that keeps its node count is the case an older log names by that seed), `r2` every decision added with the uniform pick (the uniform legs,
 the wider snapshots, the label updates), in its order, and `r3` every decision added since (the spread legs): a seed names the case it named
-before the spread legs, with those legs added; `r4` every decision of the pack legs and the combining chains, likewise.
+before the spread legs, with those legs added; `r4` every decision of the pack legs and the combining chains, likewise; `r5` every decision of
+the operator and the tagged calls, likewise.
 The summary's tallies: pick launches by name ('uniform': evaluations whose last_pick was "uniform"; 'uniform-ranked': those in which some
 pod had two or more feasible nodes, so the rank arithmetic ran), 'labels' (label updates), 'apply', 'host-masks', 'sharded-halves',
 'gathered-over-n' (and their 'uniform-' and 'spread-' twins), 'summarize'; 'spread': evaluations whose last_pick was "spread" (one per
@@ -39,7 +48,11 @@ ksched_eval; a multi-device sequence counts as one, whatever the number of repli
 decided by cpu or by the node index (two distinct candidates with the same, largest memory); 'spread-gathered-moved': second sequences in which
 the columns from before the gathered apply would have given some pod another binding; 'pack', 'pack-ranked', 'pack-gathered-over-N' and
 'pack-gathered-moved' as their spread twins; 'combine': chains run on `ev`; 'soft-narrowed', 'soft-dropped', 'soft-empty': chains in which a
-soft link narrowed a row, was dropped for one, met an empty one; 'combine-on-replicas': cases whose chain ran on every replica.
+soft link narrowed a row, was dropped for one, met an empty one; 'combine-on-replicas': cases whose chain ran on every replica;
+'selop', 'seltag': operator and tagged calls run on `ev` through ksched_eval_device; 'seltag-negated-padding': tagged calls with a pod constrained
+through NE / ABSENT entries only on a node count that is no multiple of 64 (valid-bits applied before the negation would set padding bits);
+'selop-two-pass': operator calls on more than eight keys; 'selop-two-tiles': operator calls over a whole batch whose blocks walk two pod tiles or
+more; 'selop-sharded-halves': operator and tagged calls through the two halves; 'selop-on-replicas': cases whose two calls ran on every replica.
 usage: python tools/fuzz_parity.py [seconds] [seed]       prints one line per failure and a summary; exit code 1 on any failure"""
 import os, sys, time
 import numpy as np
@@ -55,6 +68,7 @@ from tests.uniform_ref import uniform_pick  # KSCHED_PICK_UNIFORM restated
 from tests.spread_ref import best_of, spread_candidates_listed  # KSCHED_PICK_SPREAD restated: every draw's candidate, the best of them
 from tests.pack_ref import tightest_of  # KSCHED_PICK_PACK restated: the tightest of the same candidates
 from tests import combine_ref, soft_ref  # KSCHED_COMBINE_AND / _OR / _ANDNOT and KSCHED_COMBINE_SOFT restated
+from tests import selop_ref, seltag_ref  # KSCHED_SELOP_EXISTS / _GT / _LT and KSCHED_SELOP_TAGGED restated
 from tests.knife_edges import sampled as sampled_from_bits  # ksched_pick's rule for PICK_SAMPLED on a [p, n] table of bits
 from tests.test_gpu_combine_soft import old_mask_for  # an old mask whose neighbouring rows narrow, are dropped, are empty and are random
 
@@ -108,6 +122,27 @@ def pack_restated(mask, draws, n, mem, cpu, cells=1 << 24):
     return np.concatenate(out), ranked, False
 
 
+def pick_on_mask(pick, cur, draws, N, cpu, mem):
+    """what a pick in a combining (or an operator, or a tagged) call binds: ksched_pick's rule on the resulting mask `cur` with the pick
+    flag alone; None without a pick"""
+    if pick == L.PICK_UNIFORM:
+        return uniform_pick_blocks(cur, draws[:, 0], N)
+    if pick == L.PICK_SPREAD:
+        return spread_restated(cur, draws, N, mem, cpu)[0]
+    if pick == L.PICK_PACK:
+        return pack_restated(cur, draws, N, mem, cpu)[0]
+    if not pick:
+        return None
+    from kube_scheduler_rs_reference_amd.evaluator import unpack_mask
+    bits = unpack_mask(cur, N)
+    if pick == L.PICK_SAMPLED:
+        return sampled_from_bits(bits, draws)
+    # best fit, not told that the mask includes the fit: the set bit with the smallest (avail_mem, avail_cpu, node)
+    order = np.lexsort((np.arange(N), cpu, mem))
+    f = bits[:, order]
+    return np.where(f.any(axis=1), order[f.argmax(axis=1)], -1).astype(np.int32)
+
+
 CHAIN_PODS = 2000  # a combining chain takes the batch's first pods, at most so many (the oracle runs once per link)
 SENTINEL, GUARD_ROWS = 0x5A5A5A5A5A5A5A5A, 2
 
@@ -158,21 +193,8 @@ def run_chain(e, cs, where, spec, cpu, mem, lab, taints, N, P, K, nt, rc, rm, se
         want.append(cur)
     draws = {L.PICK_SAMPLED: smp, L.PICK_UNIFORM: smp_u, L.PICK_SPREAD: smp_s, L.PICK_PACK: smp_s}.get(pick)
     draws = None if draws is None else np.ascontiguousarray(draws[:p])
-    if pick == L.PICK_UNIFORM:
-        want_b = uniform_pick_blocks(cur, draws[:, 0], N)
-    elif pick == L.PICK_SPREAD:
-        want_b = spread_restated(cur, draws, N, mem, cpu)[0]
-    elif pick == L.PICK_PACK:
-        want_b = pack_restated(cur, draws, N, mem, cpu)[0]
-    elif pick:
-        from kube_scheduler_rs_reference_amd.evaluator import unpack_mask
-        bits = unpack_mask(cur, N)
-        if pick == L.PICK_SAMPLED:
-            want_b = sampled_from_bits(bits, draws)
-        else:  # best fit, not told that the mask includes the fit: the set bit with the smallest (avail_mem, avail_cpu, node)
-            order = np.lexsort((np.arange(N), cpu, mem))
-            f = bits[:, order]
-            want_b = np.where(f.any(axis=1), order[f.argmax(axis=1)], -1).astype(np.int32)
+    want_b = pick_on_mask(pick, cur, draws, N, cpu, mem)
+    spec["final"] = cur  # (the step's selector calls combine into it)
     rows = p + GUARD_ROWS
     host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
     host[offset:offset + rows * pitch].reshape(rows, pitch)[:p, :W] = old
@@ -214,6 +236,171 @@ def run_chain(e, cs, where, spec, cpu, mem, lab, taints, N, P, K, nt, rc, rm, se
     for k, name in ((soft_ref.NARROWED, "soft-narrowed"), (soft_ref.DROPPED, "soft-dropped"), (soft_ref.EMPTY, "soft-empty")):
         if k in seen_dec:
             picks[name] = picks.get(name, 0) + 1
+    return bad
+
+
+SELOP_FLAGS = (L.SELOP_EXISTS, L.SELOP_GT, L.SELOP_LT)
+SELCALL_PODS = 200  # an operator / tagged call takes the batch's first pods, at most so many (the restatements' time)
+assert SELOP_FLAGS == selop_ref.OPS and L.SELOP_TAGGED == seltag_ref.TAGGED
+
+
+def in_pod_blocks(fn, entries, n, cells=1 << 25):
+    """fn(entries [K][pods]) -> packed rows, in blocks of pods (the restatements hold [pods, n] tables)"""
+    step = max(1, cells // max(int(n), 1))
+    return np.concatenate([fn(np.ascontiguousarray(entries[:, lo:lo + step])) for lo in range(0, entries.shape[1], step)])
+
+
+def draw_selcalls(g, lab, N, P, K):
+    """the step's operator call and tagged call (generator r5): the operator; the tagged table [K][P] -- per entry constrained with a
+    probability drawn per step, all six tags, now and then tag 6 or 7, the id one of the key's node ids, such an id + / - 1, or 0, 1 or
+    0x1FFFFFFF --; per call the view's pitch (W, W + 1 or ksched_mask_pitch(n)) and its even or odd start, whether it runs as a link on the
+    step's combining chain (about half: then with a random op, KSCHED_COMBINE_SOFT at random on AND and AND-NOT) and the pick or none;
+    the shard count of the two halves; and, where the whole batch would give a block of the operator kernel more than one pod tile to walk
+    (plan_selop_launch: ceil(P / 64) > ceil(2048 / ceil(W / 16)) -- here 40 000 pods or more on 2500 nodes or more), the rows of one more
+    operator call over all P pods that are compared: the first and the last 256 and 512 random ones"""
+    W = (N + 63) // 64
+    tsel = None
+    if K:
+        pk = float(g.choice([0.05, 0.3, 0.9]))
+        near = lab[np.arange(K)[:, None], g.integers(0, N, (K, P))].astype(np.int64) + g.integers(-1, 2, (K, P))
+        ident = np.where(g.random((K, P)) < 0.8, near, g.choice(np.array([0, 1, seltag_ref.ID_MASK]), (K, P))) & seltag_ref.ID_MASK
+        tags = np.where(g.random((K, P)) < 0.03, g.integers(6, 8, (K, P)), g.integers(0, 6, (K, P)))
+        tsel = np.ascontiguousarray(np.where(g.random((K, P)) < pk, seltag_ref.entry(tags, ident), 0).astype(np.uint32))
+
+    gx = (W + 15) // 16
+    whole = None
+    if (P + 63) // 64 > (2048 + gx - 1) // gx:
+        whole = np.unique(np.concatenate([np.arange(min(P, 256)), np.arange(max(P - 256, 0), P), g.integers(0, P, 512)]))
+
+    def call():
+        op = int(g.choice(combine_ref.OPS))
+        return dict(pitch=int(g.choice([W, W + 1, int(ev._lib.ksched_mask_pitch(N))])), offset=int(g.integers(0, 2)), link=bool(g.random() < 0.5), comb=op,
+                    soft=soft_ref.SOFT if op != combine_ref.OR and g.random() < 0.5 else 0,
+                    pick=int(g.choice([0, L.PICK_SAMPLED, L.PICK_BESTFIT, L.PICK_UNIFORM, L.PICK_SPREAD, L.PICK_PACK])))
+    return dict(op=int(g.choice(SELOP_FLAGS)), tsel=tsel, calls=(call(), call()), whole=whole, shards=int(g.choice([1, 2, 3, 5])))
+
+
+def selcall_masks(spec, lab, sel, N, P, K):
+    """the expected bare masks of the step's two calls on the labels `lab` (the updated ones after a label update): -> (p, the operator
+    call's mask [p, W] from tests/selop_ref.py on sel, the tagged call's from tests/seltag_ref.py on spec's table -- None without keys)"""
+    p = min(P, SELCALL_PODS)
+    if not K:
+        return p, selop_ref.selop_mask(np.zeros((0, N), np.uint32), None, spec["op"], p=p), None
+    return (p, in_pod_blocks(lambda e: selop_ref.selop_mask(lab, e, spec["op"]), sel[:, :p], N),
+            in_pod_blocks(lambda e: seltag_ref.seltag_mask(lab, e), spec["tsel"][:, :p], N))
+
+
+def run_selcalls(e, cs, where, spec, masks, chain_final, cpu, mem, N, P, K, rc, rm, sel, smp, smp_u, smp_s, tally=True):
+    """the step's operator call and tagged call on evaluator `e` (whose labels should be the ones `masks` was computed on, whose columns
+    cpu / mem): each a ksched_eval_device into a [p, W] view with sentinel words around it -- plain, or as one more link on the final
+    mask of the step's combining chain (the first p rows of `chain_final`) -- with the call's pick.  Expected: `masks` (selcall_masks), combined by
+    tests/combine_ref.py / tests/soft_ref.py, and the pick restated on the resulting mask.  -> the number of failures"""
+    import torch
+    dev = torch.device("cuda:0")
+    p, want_op, want_tag = masks
+    W = (N + 63) // 64
+    td = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+    rc_t, rm_t = td(rc[:p], np.int64), td(rm[:p], np.int64)
+    bad = 0
+    for name, kernel, flags, entries, new, c in (("operator", "selop", L.SEL | spec["op"], sel, want_op, spec["calls"][0]),
+                                                 ("tagged", "seltag", L.SEL | L.SELOP_TAGGED, spec["tsel"], want_tag, spec["calls"][1])):
+        if new is None:
+            continue
+        pitch, offset, pick = c["pitch"], c["offset"], c["pick"]
+        link = c["link"] and chain_final is not None and chain_final.shape[0] >= p
+        old = np.ascontiguousarray(chain_final[:p]) if link else None
+        if pick == L.PICK_BESTFIT and any(a.size and (int(a.min()) < -(1 << 61) or int(a.max()) > (1 << 61)) for a in (cpu, mem)):
+            pick = L.PICK_PACK  # (as in run_chain)
+        comb = (c["comb"] | c["soft"]) if link else 0
+        if link:
+            want = soft_ref.soft_combine(old, new, c["comb"], N) if c["soft"] else combine_ref.combine(old, new, c["comb"], N)
+        else:
+            want = new
+        draws = {L.PICK_SAMPLED: smp, L.PICK_UNIFORM: smp_u, L.PICK_SPREAD: smp_s, L.PICK_PACK: smp_s}.get(pick)
+        draws = None if draws is None else np.ascontiguousarray(draws[:p])
+        want_b = pick_on_mask(pick, want, draws, N, cpu, mem)
+        rows = p + GUARD_ROWS
+        host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
+        if link:
+            host[offset:offset + rows * pitch].reshape(rows, pitch)[:p, :W] = old
+        buf = torch.from_numpy(host.view(np.int64)).to(dev)
+        view = buf[offset:offset + rows * pitch].view(rows, pitch)[:p, :W]
+        out = torch.full((p + 4,), -7, dtype=torch.int32, device=dev)
+        e.eval_device(rc_t, rm_t, td(entries[:, :p], np.int32) if K else None, None, td(draws, np.int32) if pick else None, flags | comb | pick,
+                      out_feasible=view, out_binding=out[:p] if pick else None)
+        ran = e.last_kernel
+        torch.cuda.synchronize()
+        what = (f"case seed {cs} {where}: N={N} p={p} K={K} flags={flags | comb | pick:#x} pitch={pitch} offset={offset}" +
+                (" on the step's chain" if link else ""))
+        got = buf.cpu().numpy().view(np.uint64)
+        body = got[offset:offset + rows * pitch].reshape(rows, pitch)
+        pad = body[:p, W:]
+        if ran != kernel:
+            bad += 1
+            print(f"FAIL {name} call {what}: ran as {ran!r}", flush=True)
+        if not np.array_equal(body[:p, :W], want):
+            bad += 1
+            print(f"FAIL {name} call {what}: the mask ({int((body[:p, :W] != want).any(axis=1).sum())} rows differ)", flush=True)
+        elif not (((pad == SENTINEL) | (pad == 0)).all() and (body[p:] == SENTINEL).all() and (got[:offset] == SENTINEL).all() and got[-1] == SENTINEL):
+            bad += 1
+            print(f"FAIL {name} call {what}: wrote outside words [0, W) of the view's rows", flush=True)
+        if pick:
+            b = out.cpu().numpy()
+            if not (np.array_equal(b[:p], want_b) and (b[p:] == -7).all()):
+                bad += 1
+                print(f"FAIL {name} call {what}: the pick ({int((b[:p] != want_b).sum())} bindings differ)", flush=True)
+        if not tally:
+            continue
+        picks[kernel] = picks.get(kernel, 0) + 1
+        if kernel == "selop":
+            if K > 8:
+                picks["selop-two-pass"] = picks.get("selop-two-pass", 0) + 1
+        elif N % 64:  # a pod constrained through NE / ABSENT entries only, in rows whose last word has padding bits
+            ent = entries[:, :p]
+            tag = ent >> np.uint32(seltag_ref.SHIFT)
+            neg = (ent != 0) & ((tag == seltag_ref.NE) | (tag == seltag_ref.ABSENT))
+            if ((ent != 0).any(axis=0) & (neg == (ent != 0)).all(axis=0)).any():
+                picks["seltag-negated-padding"] = picks.get("seltag-negated-padding", 0) + 1
+    return bad
+
+
+def run_selop_whole(e, cs, where, spec, lab, sel, N, P, K, rc, rm):
+    """one more operator call over ALL P pods of a batch long enough for two pod tiles per block (spec["whole"]: the rows compared, against
+    tests/selop_ref.py on those rows' entries), into a view at pitch W + 1 with sentinel words behind every row and behind the last one.
+    -> the number of failures"""
+    import torch
+    dev = torch.device("cuda:0")
+    rows, W = spec["whole"], (N + 63) // 64
+    pitch = W + 1
+    want = selop_ref.selop_mask(lab, np.ascontiguousarray(sel[:, rows]), spec["op"]) if K else selop_ref.selop_mask(np.zeros((0, N), np.uint32), None, spec["op"], p=rows.size)
+    buf = torch.full(((P + GUARD_ROWS) * pitch,), SENTINEL, dtype=torch.int64, device=dev)
+    view = buf.view(P + GUARD_ROWS, pitch)[:P, :W]
+    td = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+    e.eval_device(td(rc, np.int64), td(rm, np.int64), td(sel, np.int32) if K else None, None, None, L.SEL | spec["op"], out_feasible=view)
+    ran = e.last_kernel
+    torch.cuda.synchronize()
+    body = buf.cpu().numpy().view(np.uint64).reshape(P + GUARD_ROWS, pitch)
+    bad = 0
+    if ran != "selop" or not np.array_equal(body[rows, :W], want) or not (body[:, W:] == SENTINEL).all() or not (body[P:] == SENTINEL).all():
+        bad += 1
+        print(f"FAIL operator call over the whole batch case seed {cs} {where}: N={N} P={P} K={K} flags={L.SEL | spec['op']:#x} kernel={ran} "
+              f"({int((body[rows, :W] != want).any(axis=1).sum())} of {rows.size} compared rows differ)", flush=True)
+    picks["selop"] = picks.get("selop", 0) + 1
+    picks["selop-two-tiles"] = picks.get("selop-two-tiles", 0) + 1
+    return bad
+
+
+def selcall_halves(cs, spec, masks, N, K, rc, rm, sel, smp_u, att_u):
+    """both calls through ksched_eval_begin / _end over spec's 1 to 5 row shards of the first p pods (shard_halves: the selector columns
+    addressed inside the whole array, so sel_stride > p on every real shard), with the uniform pick so that the second half has bindings
+    to hand back.  -> the number of failures"""
+    p, want_op, want_tag = masks
+    bad = 0
+    for flags, entries, want in ((L.SEL | spec["op"], sel, want_op), (L.SEL | L.SELOP_TAGGED, spec["tsel"], want_tag)):
+        ent = np.ascontiguousarray(entries[:, :p])
+        draws = np.ascontiguousarray(smp_u[:p])
+        bad += shard_halves(None, cs, "selop-", N, p, K, 0, L.SEL, flags | L.PICK_UNIFORM, rc[:p], rm[:p], ent, None, draws, att_u,
+                            (want, None, uniform_pick_blocks(want, draws[:, 0], N)), n_sh=spec["shards"])
     return bad
 
 
@@ -330,14 +517,15 @@ def row_popcounts(m):
     return np.unpackbits(np.ascontiguousarray(m).view(np.uint8), axis=1).sum(axis=1)
 
 
-def shard_halves(g, cs, tag, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, attempts, want):
+def shard_halves(g, cs, tag, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, attempts, want, n_sh=None):
     """the host-side row shard (include/ksched.h "one host thread, several devices"): the batch cut into 1 .. 5 shards with
     ksched_shard_bounds, every shard through ksched_eval_begin (selector columns addressed inside the whole batch's array with its
     stride, the draws `smp` [P, attempts] at 4 * attempts * lo bytes, bindings padded to ceil(P / n) with -1) + ksched_eval_end, merged
-    like an all-gathered table -- on this one evaluator, shard after shard.  `g` draws the shard count.  -> the number of failures"""
+    like an all-gathered table -- on this one evaluator, shard after shard.  `g` draws the shard count (n_sh given: that many, and `g` is
+    not asked).  -> the number of failures"""
     bad = 0
     import ctypes as C
-    n_sh = int(g.choice([1, 2, 3, 5]))
+    n_sh = int(g.choice([1, 2, 3, 5])) if n_sh is None else n_sh
     W = ev.W
     lo_, hi_, cpr_ = C.c_uint32(), C.c_uint32(), C.c_uint32()
     rc_c, rm_c = np.ascontiguousarray(rc), np.ascontiguousarray(rm)
@@ -442,13 +630,14 @@ def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, fla
 
 
 def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, ranked, tied,
-                    name="spread", restate=None, chain=None):
+                    name="spread", restate=None, chain=None, after=None):
     """the multi-device sequence with the spread pick, twice: on freshly set replicas; then -- after ksched_apply_bindings_sharded_local of
     the gathered bindings over the same replicas, ragged cuts, no ksched_set_nodes -- on the columns that apply left on every replica: the
     oracle's mask and the restatement on the exact-integer apply of those bindings.  A replica whose columns the gathered commit left behind
     ranks its rows by old values.  Every replica's pick must run as "spread".  `ev`, cpu and mem are not touched.  -> the number of failures.
     name="pack", restate=pack_restated: the same for the pack pick (flags carry PICK_PACK).  chain=(spec, smp, smp_u, smp_s): after the
-    sharded apply and the second sequence that combining chain runs on every replica, against the columns the apply left."""
+    sharded apply and the second sequence that combining chain runs on every replica, against the columns the apply left; behind it
+    after(e, where, ncpu, nmem) -> failures: the step's operator and tagged calls on that replica, on the same columns."""
     import torch
     restate = restate or spread_restated
     tag, pick_flag = name + "-", {"spread": L.PICK_SPREAD, "pack": L.PICK_PACK}[name]
@@ -487,7 +676,11 @@ def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc,
     if chain is not None:  # the step's combining chain on every replica, on the columns the sharded apply left there
         for q, e in enumerate(reps):
             bad += run_chain(e, cs, f"replica {q} of {n_sh} after a sharded apply", chain[0], ncpu, nmem, lab, taints, N, P, K, nt, rc, rm, sel, tol, *chain[1:])
+            if after is not None:
+                bad += after(e, f"replica {q} of {n_sh} after a sharded apply", ncpu, nmem)
         picks["combine-on-replicas"] = picks.get("combine-on-replicas", 0) + 1
+        if after is not None:
+            picks["selop-on-replicas"] = picks.get("selop-on-replicas", 0) + 1
     return bad + bad2
 
 
@@ -502,6 +695,7 @@ while time.time() < t_end:
     r2 = np.random.default_rng([cs, 0x0E3])  # every decision added after the sequence of `r` was fixed (see the docstring)
     r3 = np.random.default_rng([cs, 0x5E4])  # every decision added after the sequence of `r2` was fixed: the spread legs
     r4 = np.random.default_rng([cs, 0xC0B])  # every decision added after the sequence of `r3` was fixed: the pack legs and the combining chains
+    r5 = np.random.default_rng([cs, 0xE95])  # every decision added after the sequence of `r4` was fixed: the operator and the tagged selector calls
     wide = int(r2.choice([8192, 8193, 12_500])) if r2.random() < 0.1 else 0  # rows of more than 128 words: k_pick_uniform's two-pass form (8192: the longest one-pass row)
     N = int(r.choice([1, 2, 63, 64, 65, 300, 1023, 1024, 1025, 2500, 4097, 6000]))
     P = int(r.choice([1, 7, 64, 65, 500, 1500, 3000]))
@@ -682,6 +876,15 @@ while time.time() < t_end:
             # one combining chain on the same snapshot (draw_chain, run_chain)
             chain = draw_chain(r4, N, P, K, nt)
             fails += run_chain(ev, cs, f"step {step}", chain, cpu, mem, lab, taints, N, P, K, nt, rc, rm, sel, tol, smp, smp_u, smp_s)
+            # one operator call and one tagged call on the same snapshot (draw_selcalls, run_selcalls), on the labels as the updates above left
+            # them; and both through the two halves of ksched_eval over row shards
+            selc = draw_selcalls(r5, lab, N, P, K)
+            selm = selcall_masks(selc, lab, sel, N, P, K)
+            fails += run_selcalls(ev, cs, f"step {step}", selc, selm, chain["final"], cpu, mem, N, P, K, rc, rm, sel, smp, smp_u, smp_s)
+            if K:
+                fails += selcall_halves(cs, selc, selm, N, K, rc, rm, sel, smp_u, att_u)
+            if selc["whole"] is not None:
+                fails += run_selop_whole(ev, cs, f"step {step}", selc, lab, sel, N, P, K, rc, rm)
         ev.set_kernel("auto")
         want3_u = (want[0], want[1], want_u)
         want3_s = (want[0], want[1], want_s)
@@ -698,7 +901,9 @@ while time.time() < t_end:
             fails += spread_gathered(r3, cs, cpu, mem, lab, taints, N, P, K, nt, preds, fl_s, rc, rm, sel, tol, smp_s, d_s, want3_s, ranked_s, tied_s)
         if HOOKS and r4.random() < 0.5:  # the pack pick through the multi-device sequence and a sharded apply of its gathered bindings; then the chain on every replica
             fails += spread_gathered(r4, cs, cpu, mem, lab, taints, N, P, K, nt, preds, fl_k, rc, rm, sel, tol, smp_k, d_k, (want[0], want[1], want_k), ranked_k, False,
-                                     name="pack", restate=pack_restated, chain=(chain, smp, smp_u, smp_s))
+                                     name="pack", restate=pack_restated, chain=(chain, smp, smp_u, smp_s),
+                                     after=lambda e, where, ncpu, nmem: run_selcalls(e, cs, where, selc, selm, chain["final"], ncpu, nmem, N, P, K, rc, rm, sel,
+                                                                                     smp, smp_u, smp_s, tally=False))
         if r2.random() < 0.4:  # ksched_pick with the uniform pick: the oracle's mask, and that mask thinned by random words -- the restatement on either
             thin_u = want[0] & r2.integers(0, 1 << 63, want[0].shape, dtype=np.uint64)
             if not (np.array_equal(ev.pick(want[0], L.PICK_UNIFORM, samples=smp_u), want_u) and
