@@ -53,6 +53,7 @@ COMBINE_PLAN_TEST := tests/cpp/combine_plan_tests
 SOFT_PLAN_TEST := tests/cpp/soft_plan_tests
 SELOP_PLAN_TEST := tests/cpp/selop_plan_tests
 SELTAG_PLAN_TEST := tests/cpp/seltag_plan_tests
+SELTERMS_PLAN_TEST := tests/cpp/selterms_plan_tests
 
 PMC_CALIB := tools/pmc_calib
 COMBINE_BENCH := tools/libmask_combine_bench.so
@@ -86,7 +87,7 @@ $(LIB_HIP_TEST): $(LIB_OBJ) tests/cpp/test_hooks.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-soname,libksched_hip.so -o $@ $(LIB_OBJ) tests/cpp/hooks/test_hooks.o
 
 # (the plain-g++ tests of csrc/ headers are built where their source is present: a tree that carries an older tests/ still builds everything else)
-host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(SOFT_PLAN_TEST) $(SELOP_PLAN_TEST) $(SELTAG_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
+host: $(LIB_HOST) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(foreach t,$(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(SOFT_PLAN_TEST) $(SELOP_PLAN_TEST) $(SELTAG_PLAN_TEST) $(SELTERMS_PLAN_TEST),$(if $(wildcard $(t).cpp),$(t))) $(OBJ_TOOL) $(FAKE_RCCL) $(LIB_HIP_TEST)
 # TEST-ONLY stand-in for librccl (n ranks on one GPU; loaded only with KSCHED_TEST_HOOKS=1 + KSCHED_RCCL_LIB, see csrc/comm_rccl.hpp)
 $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 	$(CXX) -O2 -std=c++17 -fPIC -Wall -Wextra -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o $@ tests/cpp/fake_rccl.cpp -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lrt -lpthread
@@ -94,7 +95,7 @@ $(FAKE_RCCL): tests/cpp/fake_rccl.cpp
 $(INDEX_TEST): tests/cpp/index_tests.cpp $(CSRC)/tile_index.hpp
 	$(CXX) -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -o $@ tests/cpp/index_tests.cpp
 # host-only check of the evaluation plan (csrc/eval_plan.hpp: which kernels a request runs; no GPU, no HIP header): tests/test_eval_plan_host.py runs it
-$(PLAN_TEST): tests/cpp/plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/mask_combine.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+$(PLAN_TEST): tests/cpp/plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_terms.hpp $(CSRC)/mask_combine.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/plan_tests.cpp
 # host-only check of a tile-kernel launch's description (csrc/tile_launch.hpp: LDS carve-up, launch geometry, argument fill, predicate dispatch; no GPU, no HIP runtime call): tests/test_tile_launch_host.py runs it
 $(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/tile_index.hpp $(CSRC)/eval_request.hpp include/ksched.h
@@ -103,7 +104,7 @@ $(LAUNCH_TEST): tests/cpp/tile_launch_tests.cpp $(CSRC)/tile_launch.hpp $(CSRC)/
 $(CHANGE_TEST): tests/cpp/snapshot_change_tests.cpp $(CSRC)/snapshot_change.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/snapshot_change_tests.cpp
 # host-only check of the plan of a ranked-pick request, KSCHED_PICK_UNIFORM / _SPREAD / _PACK (csrc/eval_plan.hpp, csrc/pipe_plan.hpp; no GPU, no HIP header): tests/test_ranked_plan_host.py runs it
-$(RANKED_PLAN_TEST): tests/cpp/ranked_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/mask_combine.hpp $(CSRC)/pipe_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+$(RANKED_PLAN_TEST): tests/cpp/ranked_plan_tests.cpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_terms.hpp $(CSRC)/mask_combine.hpp $(CSRC)/pipe_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/ranked_plan_tests.cpp
 # host-only check of the numbers the best-fit structures and launches are sized by (csrc/bestfit_layout.hpp: order, row and hand-over layouts, counter rotation, debug bits; no GPU, no HIP header): tests/test_bestfit_layout_host.py runs it
 $(BESTFIT_LAYOUT_TEST): tests/cpp/bestfit_layout_tests.cpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp
@@ -124,17 +125,20 @@ $(MERGE_SORT_PLAN_TEST): tests/cpp/merge_sort_plan_tests.cpp $(CSRC)/merge_sort_
 $(APPLY_PLAN_TEST): tests/cpp/apply_plan_tests.cpp $(CSRC)/apply_plan.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/apply_plan_tests.cpp
 # host-only check of a combining evaluation's rules (csrc/mask_combine.hpp: the op of a flag word, the argument rules, the valid-bits word, the access width, the launch geometry executed on the CPU; csrc/eval_plan.hpp: the plan with an op, and without one against plan_eval as it was; no GPU, no HIP header): tests/test_combine_plan_host.py runs it
-$(COMBINE_PLAN_TEST): tests/cpp/combine_plan_tests.cpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+$(COMBINE_PLAN_TEST): tests/cpp/combine_plan_tests.cpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_terms.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/combine_plan_tests.cpp
 # host-only check of a soft combining evaluation's rules, KSCHED_COMBINE_SOFT (csrc/mask_combine_soft.hpp: which flag words and entry points carry the modifier, the row rule, the launch geometry executed on the CPU at each side of every switch; csrc/eval_plan.hpp: the plan with the bit against the plain combining plan; no GPU, no HIP header): tests/test_soft_plan_host.py runs it
-$(SOFT_PLAN_TEST): tests/cpp/soft_plan_tests.cpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+$(SOFT_PLAN_TEST): tests/cpp/soft_plan_tests.cpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_terms.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/soft_plan_tests.cpp
 # host-only check of an operator call's rules, KSCHED_SELOP_EXISTS / _GT / _LT (csrc/sel_ops.hpp: the operator of a flag word, the argument rules, the rule for one pair and one row, the launch geometry walked on the CPU; csrc/eval_plan.hpp: the plan of an operator call, and without an operator against plan_eval as it was; no GPU, no HIP header): tests/test_selop_plan_host.py runs it
-$(SELOP_PLAN_TEST): tests/cpp/selop_plan_tests.cpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+$(SELOP_PLAN_TEST): tests/cpp/selop_plan_tests.cpp $(CSRC)/sel_ops.hpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_terms.hpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/selop_plan_tests.cpp
 # host-only check of a tagged call's rules, KSCHED_SELOP_TAGGED (csrc/sel_tags.hpp: the argument rules, the entry's tag and id, the rule for one pair and one row, the one compare form the kernel decodes every tag into, the launch geometry walked on the CPU; csrc/eval_plan.hpp: the plan of a tagged call, and without the flag against plan_eval as it was; no GPU, no HIP header): tests/test_seltag_plan_host.py runs it
-$(SELTAG_PLAN_TEST): tests/cpp/seltag_plan_tests.cpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_ops.hpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+$(SELTAG_PLAN_TEST): tests/cpp/seltag_plan_tests.cpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_terms.hpp $(CSRC)/sel_ops.hpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
 	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/seltag_plan_tests.cpp
+# host-only check of a tagged call's term count, KSCHED_SEL_TERMS (csrc/sel_terms.hpp: the count of a flag word, the argument rules, where an entry lies, one pod's row against seltag_row, the launch geometry walked on the CPU for both kernels; csrc/eval_plan.hpp: the plan with the field, and without it against plan_eval as it was; no GPU, no HIP header): tests/test_selterms_plan_host.py runs it
+$(SELTERMS_PLAN_TEST): tests/cpp/selterms_plan_tests.cpp $(CSRC)/sel_terms.hpp $(CSRC)/sel_tags.hpp $(CSRC)/sel_ops.hpp $(CSRC)/mask_combine_soft.hpp $(CSRC)/mask_combine.hpp $(CSRC)/eval_plan.hpp $(CSRC)/bestfit_layout.hpp $(CSRC)/merge_sort_plan.hpp include/ksched.h
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -o $@ tests/cpp/selterms_plan_tests.cpp
 $(LIB_HOST): $(HOST_SRCS) $(HOST_HDRS) $(LIB_HIP)
 	$(CXX) $(CXXFLAGS) -shared -o $@ $(HOST_SRCS) -L$(PKG) -lksched_hip -Wl,-rpath,'$$ORIGIN' -lpthread
 # C++ tests of the host mirror (tests/cpp/host_tests.cpp; driven by tests/test_host_mirror.py)
@@ -198,4 +202,4 @@ $(LIB_ORA): oracle/oracle.c oracle/oracle.h
 	$(CC) $(CFLAGS) -shared -o $@ oracle/oracle.c
 
 clean:
-	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(SOFT_PLAN_TEST) $(SELOP_PLAN_TEST) $(SELTAG_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB) $(COMBINE_BENCH)
+	rm -f $(LIB_OBJ) $(LIB_HIP_TEST) tests/cpp/hooks/test_hooks.o $(LIB_HIP) $(LIB_HOST) $(LIB_ORA) $(HOST_TEST) $(NODE_EVENTS_TEST) $(SUMMARY_TEST) $(INDEX_TEST) $(PLAN_TEST) $(LAUNCH_TEST) $(CHANGE_TEST) $(RANKED_PLAN_TEST) $(UNIFORM_PICK_TEST) $(SPREAD_PICK_TEST) $(PACK_PICK_TEST) $(BESTFIT_LAYOUT_TEST) $(PIPE_PLAN_TEST) $(APPLY_ADMIT_TEST) $(STREAM_ORDER_TEST) $(MERGE_SORT_PLAN_TEST) $(APPLY_PLAN_TEST) $(COMBINE_PLAN_TEST) $(SOFT_PLAN_TEST) $(SELOP_PLAN_TEST) $(SELTAG_PLAN_TEST) $(SELTERMS_PLAN_TEST) $(OBJ_TOOL) $(FAKE_RCCL) $(PMC_CALIB) $(COMBINE_BENCH)

@@ -29,6 +29,7 @@
  *     the pod keeps a node)
  *   (extension E8: the selector operators Exists, Gt, Lt)   KSCHED_SELOP_EXISTS / _GT / _LT
  *   (extension E9: a selector operator per pod and key)     KSCHED_SELOP_TAGGED, KSCHED_SELTAG_*
+ *   (extension E10: ORed selector terms in one tagged call)  KSCHED_SEL_TERMS(t), KSCHED_MAX_TERMS
  *
  * Conventions
  *   - plain C, no C++ or torch types; nothing ever unwinds across this boundary: every failure
@@ -339,7 +340,8 @@ extern "C" {
  *         ksched_eval_device(.., sel: that row per pod, KSCHED_SEL | KSCHED_SELOP_TAGGED,                        M, ..)   M  = [the term]
  *         ksched_eval_device(.., no selector,           KSCHED_FIT | KSCHED_COMBINE_AND | KSCHED_PICK_SPREAD,    M, .., out_binding, ..)
  *     where E8's recipe above takes three calls for the term, each over every pod.
- *   - In {a, b} stays two calls under KSCHED_COMBINE_OR (an entry holds one id).
+ *   - In {a, b} is two TERMS of one call under KSCHED_SEL_TERMS (extension E10, below); without the term field it stays two calls under
+ *     KSCHED_COMBINE_OR (an entry holds one id).
  *   - A range on one key (Gt 4 AND Lt 16) is two calls under KSCHED_COMBINE_AND: a key has one entry per pod per call. */
 #define KSCHED_SELOP_TAGGED 0x40000u /* with KSCHED_SEL alone: every selector entry carries its own operator, tag << 29 | id */
 #define KSCHED_SELTAG_SHIFT 29u
@@ -350,6 +352,52 @@ extern "C" {
 #define KSCHED_SELTAG_ABSENT 3u /* v == 0 */
 #define KSCHED_SELTAG_GT 4u     /* v != 0 && v > id */
 #define KSCHED_SELTAG_LT 5u     /* v != 0 && v < id */
+
+/* KSCHED_SEL_TERMS(t) (extension E10): ORed selector terms in one tagged call.  A tagged call (E9) answers ONE conjunctive matchExpressions
+ * term per pod.  Kubernetes' requiredDuringSchedulingIgnoredDuringExecution is a LIST of nodeSelectorTerms that are ORed, and `In {a, b, c}`
+ * is an OR as well; with E9 alone each further term or set member is a further tagged call over the whole pods x nodes rectangle under
+ * KSCHED_COMBINE_OR, into a second mask that is then ANDed into the caller's.  With a TERM COUNT t in bits 20 .. 23 of the flag word the call
+ * takes t tagged rows per pod and writes the OR of the t conjunctions, once.  A modifier of a tagged call, as KSCHED_SELOP_TAGGED is one of
+ * KSCHED_SEL.  Added in ABI 7 without a version change and without a new symbol: detect it by these constants and by KSCHED_E_INVAL from an
+ * older library.  Field 0 is "no term field": every call means what it means without E10.
+ *   layout     : sel_val_ids is [t][n_keys][p]: entry (term, k, pod) at ((term * n_keys) + k) * p + pod; at ksched_eval_begin column
+ *                (term, k) starts (term * n_keys + k) * sel_stride entries in.  An entry is E9's, unchanged: tag << 29 | id.  The host-pointer
+ *                forms copy t * n_keys * p entries.
+ *   meaning    : row(pod) = valid bits AND ( OR over term of ( AND over k of [E9's rule for entry (term, k, pod) and the node's id of key k] ) ).
+ *                Bits at or beyond n are zero; the words [W, pitch) are left untouched or written as zero.  A term whose entries are all 0
+ *                passes everywhere, so a pod without affinity is all zeros.  A term that must match nothing carries KSCHED_SEL_NEVER (or any
+ *                tag-6 / tag-7 entry) in any ONE key: the padding term of a pod with fewer than t terms, and Kubernetes' empty term.
+ *                sel_val_ids == NULL, or a snapshot without keys: every node passes.  t = 1 gives, bit for bit, the tagged call's mask.
+ *   exact      : integer logic only -- same inputs, same bits, on every run.
+ *   flags      : KSCHED_SEL | KSCHED_SELOP_TAGGED are required beside a non-zero field; everything else is a tagged call's contract, word for
+ *                word: optionally one KSCHED_COMBINE_* op, with or without KSCHED_COMBINE_SOFT, at the two device-pointer evaluations;
+ *                optionally one KSCHED_PICK_* flag, which runs behind the mask (behind the combine, if there is one) and reads it.
+ *   errors     : KSCHED_E_INVAL with nothing enqueued and nothing written for a non-zero field without KSCHED_SELOP_TAGGED (hence without
+ *                KSCHED_SEL, or beside KSCHED_SELOP_EXISTS / _GT / _LT), and for KSCHED_FIT, KSCHED_TAINT, KSCHED_WANT_FIT_MASK or out_fit
+ *                beside it.  Every refusal of a tagged, a plain or a combining call stays what it is.
+ *   accepted   : where a tagged call is: ksched_eval, ksched_eval_begin / ksched_eval_end, ksched_eval_device, ksched_eval_device_pitched.
+ *                NOT by ksched_pipe_submit, ksched_pick, ksched_pick_device, ksched_summarize* or ksched_explain: KSCHED_E_INVAL.
+ *   options    : KSCHED_OPT_KERNEL has no effect.  ksched_last_kernel: "selterms" whenever the field is non-zero, t = 1 included.
+ *                KSCHED_OPT_TIMING brackets the kernel with stream events.
+ *   otherwise  : a tagged call's contract (E9): p == 0 is a no-op, n == 0 leaves the mask alone (and gives -1 for every pod of a pick),
+ *                KSCHED_E_STATE before ksched_set_nodes, the ordering of a plain evaluation on `hip_stream`, the ctx's scratch mask held as
+ *                by any combining call.
+ *   what a row cannot say: one row holds ONE entry per key, so NotIn {a, b} (two NE entries on one key) and a range (Gt 4 AND Lt 16) stay
+ *                two calls under KSCHED_COMBINE_AND / _ANDNOT, as under E9.  In {a, b} AND In {x, y} on two keys is four terms (the product).
+ * Recipe -- (zone In {a, b} AND gpu Exists) OR (cores Gt 16), then fit and the spread pick, in TWO calls on one stream and one mask M:
+ *     three terms per pod, rows [3][n_keys][p]:   term 0: zone = EQ a, gpu = EXISTS;   term 1: zone = EQ b, gpu = EXISTS;   term 2: cores = GT id(16)
+ *     (a pod with fewer terms pads with a term holding KSCHED_SEL_NEVER in one key; a pod without affinity is all zeros)
+ *     ksched_eval_device(.., sel: those rows, KSCHED_SEL | KSCHED_SELOP_TAGGED | KSCHED_SEL_TERMS(3),              M, ..)   M  = [the affinity]
+ *     ksched_eval_device(.., no selector,     KSCHED_FIT | KSCHED_COMBINE_AND | KSCHED_PICK_SPREAD,                M, .., out_binding, ..)
+ *   where E9 takes three tagged calls, two of them under KSCHED_COMBINE_OR into a second mask, and a combine of the two masks.
+ *   Cost at 100 000 x 5 000, 8 keys (profiles/selterms_cost.txt): where EVERY pod carries T real terms the one call is NOT
+ *   cheaper than that sequence (1128 us against 1081 us at T = 2; 2137 against 2182 us at T = 4): both are bound by the scalar decode of the
+ *   constrained entries.  Where one pod in a hundred carries terms and the rest have no affinity it is (401 against 629 us at T = 2, 413
+ *   against 1298 us at T = 4): a pod whose row is complete after a term stops there.  What the call gives in both cases: one call, one mask. */
+#define KSCHED_SEL_TERMS_SHIFT 20u
+#define KSCHED_SEL_TERMS_MASK 0x00F00000u
+#define KSCHED_SEL_TERMS(t) ((uint32_t)(t) << KSCHED_SEL_TERMS_SHIFT) /* 1 <= t <= KSCHED_MAX_TERMS */
+#define KSCHED_MAX_TERMS 15u
 
 /* InvalidNodeReason, src/predicates.rs:14-18 (variant order kept); 0 = Ok(()) */
 #define KSCHED_REASON_OK 0

@@ -64,6 +64,19 @@ SELTAG_EXISTS = 2  # v != 0; the id field is not looked at
 SELTAG_ABSENT = 3  # v == 0 (DoesNotExist); the id field is not looked at
 SELTAG_GT = 4  # v != 0 and v > id
 SELTAG_LT = 5  # v != 0 and v < id
+# extension E10: a term count in bits 20 .. 23, a modifier of a tagged call (SEL | SELOP_TAGGED): sel_val_ids is [T][n_keys][p] and a pod's
+# row the OR over its T tagged rows -- a required nodeAffinity (ORed nodeSelectorTerms, In {a, b} as two terms) in one call and one mask
+SEL_TERMS_SHIFT = 20
+SEL_TERMS_MASK = 0x00F00000
+MAX_TERMS = 15
+
+
+def sel_terms(t: int) -> int:
+    """the flag field for T = t terms per pod, 1 <= t <= MAX_TERMS (KSCHED_SEL_TERMS(t)); ValueError outside"""
+    t = int(t)
+    if not 1 <= t <= MAX_TERMS:
+        raise ValueError(f"sel_terms: expected 1 ... {MAX_TERMS} terms, got {t}")
+    return t << SEL_TERMS_SHIFT
 
 APPLY_FIRST_PER_NODE = 0x01
 APPLY_RELEASE = 0x02

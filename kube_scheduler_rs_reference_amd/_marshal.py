@@ -172,6 +172,38 @@ def seltag(flags: int, where: str, accepted: bool, out_fit=None) -> None:
         raise ValueError("out_fit: SELOP_TAGGED excludes WANT_FIT_MASK / out_fit")
 
 
+def terms_of(flags: int) -> int:
+    """the term count of a flag word (extension E10): 0 = no term field"""
+    return (int(flags) & L.SEL_TERMS_MASK) >> L.SEL_TERMS_SHIFT
+
+
+def selterms(flags: int, where: str, accepted: bool, out_fit=None) -> None:
+    """The one rule of a term count, `sel_terms(t)` in the flag word (include/ksched.h, extension E10), before any library call: it modifies
+    a TAGGED call, so where SELOP_TAGGED is accepted (accepted=True: `eval`, `eval_device`, `bind_eval_device`) it needs SELOP_TAGGED --
+    hence SEL, and no SELOP_EXISTS / SELOP_GT / SELOP_LT -- and excludes FIT, TAINT and WANT_FIT_MASK / `out_fit` as a tagged call does;
+    the pipe, the picks, the summaries and `explain` do not take it.  ValueError naming the argument; a word without the field passes."""
+    t = terms_of(flags)
+    if not t:
+        return
+    if not accepted:
+        raise ValueError(f"flags: {where} takes no term count (sel_terms({t}) modifies a tagged call, an evaluation: Evaluator.eval, Evaluator.eval_device)")
+    if not int(flags) & L.SELOP_TAGGED:
+        raise ValueError(f"flags: a term count (sel_terms({t})) needs SEL | SELOP_TAGGED (it says how many tagged rows a pod has)")
+    seltag(flags, where, accepted, out_fit)
+
+
+def _sel_shapes(n_keys: int, p: int, flags: int):
+    """the shapes sel_val_ids may have: [n_keys, p]; with a term count T (extension E10) [T, n_keys, p] or [T * n_keys, p] -- the library
+    reads T * n_keys * p entries, so any other shape would be an out-of-bounds read"""
+    t = terms_of(flags)
+    return ((n_keys, p),) if not t else ((t, n_keys, p), (t * n_keys, p))
+
+
+def _sel_shape_error(name: str, got, shapes, flags: int) -> ValueError:
+    what = " or ".join(str(list(s)) for s in shapes)
+    return ValueError(f"{name}: expected shape {what}" + (f" with sel_terms({terms_of(flags)})" if terms_of(flags) else "") + f", got {list(got)}")
+
+
 class Batch(NamedTuple):
     """One pod batch as the C ABI takes it; [:8] is the argument run every evaluation entry point shares."""
     p: int
@@ -194,20 +226,31 @@ def _rows(req_cpu, name: str, p: Optional[int]) -> int:
 
 
 def device_batch(device: int, n_keys: int, req_cpu, req_mem, sel_val_ids, tolerations, samples, flags: int, p: Optional[int] = None) -> Batch:
-    """torch CUDA tensors on cuda:`device`: requests int64 [p], sel_val_ids int32/uint32 [n_keys, p], tolerations int64/uint64 [p],
-    samples int32/uint32 [p, attempts] (see draws); any of them may be None.  p = len(req_cpu) unless given (the pick alone)."""
+    """torch CUDA tensors on cuda:`device`: requests int64 [p], sel_val_ids int32/uint32 [n_keys, p] ([T, n_keys, p] or [T * n_keys, p]
+    where flags carry a term count T, extension E10), tolerations int64/uint64 [p], samples int32/uint32 [p, attempts] (see draws); any of
+    them may be None.  p = len(req_cpu) unless given (the pick alone)."""
     p = _rows(req_cpu, "req_cpu_milli", p)
     smp, attempts, _ = draws(samples, "samples", flags, p, device)
-    cols = ((req_cpu, "req_cpu_milli", "i64", (p,)), (req_mem, "req_mem_bytes", "i64", (p,)), (sel_val_ids, "sel_val_ids", "u32", (n_keys, p)),
+    sel_shape = (n_keys, p)
+    if sel_val_ids is not None and terms_of(flags):
+        shapes = _sel_shapes(n_keys, p, flags)
+        if tuple(sel_val_ids.shape) not in shapes:
+            raise _sel_shape_error("sel_val_ids", sel_val_ids.shape, shapes, flags)
+        sel_shape = tuple(sel_val_ids.shape)
+    cols = ((req_cpu, "req_cpu_milli", "i64", (p,)), (req_mem, "req_mem_bytes", "i64", (p,)), (sel_val_ids, "sel_val_ids", "u32", sel_shape),
             (tolerations, "tolerations", "u64", (p,)))
     return Batch(p, *[_vp(device_ptr(*col, device)) for col in cols], smp, attempts, int(flags), (req_cpu, req_mem, sel_val_ids, tolerations, samples))
 
 
 def host_batch(n_keys: int, req_cpu, req_mem, sel_val_ids, tolerations, samples, flags: int, p: Optional[int] = None) -> Batch:
-    """The same batch from host memory: whatever numpy converts, every column 1-D of length p, sel_val_ids [n_keys][p]."""
+    """The same batch from host memory: whatever numpy converts, every column 1-D of length p, sel_val_ids [n_keys][p] ([T][n_keys][p] or
+    [T * n_keys][p] where flags carry a term count T, extension E10)."""
     cpu = host_array(req_cpu, "req_cpu_milli", "i64")
     p = _rows(cpu, "req_cpu_milli", p)
     smp, attempts, samples = draws(samples, "samples", flags, p)
-    keep = (cpu, host_array(req_mem, "req_mem_bytes", "i64", (p,)), host_array(sel_val_ids, "sel_val_ids", "u32", (n_keys, p)),
+    sel = host_array(sel_val_ids, "sel_val_ids", "u32", None if terms_of(flags) else (n_keys, p))
+    if sel is not None and terms_of(flags) and tuple(sel.shape) not in _sel_shapes(n_keys, p, flags):
+        raise _sel_shape_error("sel_val_ids", sel.shape, _sel_shapes(n_keys, p, flags), flags)
+    keep = (cpu, host_array(req_mem, "req_mem_bytes", "i64", (p,)), sel,
             host_array(tolerations, "tolerations", "u64", (p,)))
     return Batch(p, *map(host_ptr, keep), smp, attempts, int(flags), keep + (samples,))

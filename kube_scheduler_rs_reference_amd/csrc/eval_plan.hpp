@@ -14,6 +14,7 @@
 #include "mask_combine.hpp"
 #include "sel_ops.hpp"
 #include "sel_tags.hpp"
+#include "sel_terms.hpp"
 
 namespace ksched {
 
@@ -51,9 +52,10 @@ struct EvalFacts {
     bool soft = false;  // combine_soft(flags) (extension E7, mask_combine_soft.hpp): with kAnd or kAndNot only
     SelOp selop = SelOp::kNone;  // sel_op(flags) of an operator call (extension E8, sel_ops.hpp): KSCHED_SEL alone beside it, no out_fit
     bool seltag = false;  // sel_tagged(flags) of a tagged call (extension E9, sel_tags.hpp): KSCHED_SEL alone beside it, no operator flag, no out_fit
+    uint32_t terms = 0;  // sel_terms(flags) (extension E10, sel_terms.hpp): not 0 only in a tagged call -- the pod's row is the OR of that many tagged rows
 };
 
-enum class MaskKernel { kNone, kFused, kDirect, kSelOp, kSelTag };
+enum class MaskKernel { kNone, kFused, kDirect, kSelOp, kSelTag, kSelTerms };
 enum class SampledPick { kNone, kOwnLaunch, kRidesFill, kRidesTiles, kFromMask };
 enum class BestfitPick { kNone, kRowsOneStage, kRowsTwoStages, kRowsTwoStagesListed, kFromMask };
 enum class RankedPick { kNone, kUniform, kSpread, kPack };  // k_pick_uniform / k_pick_spread / k_pick_pack behind the mask kernel: the only form
@@ -73,6 +75,7 @@ struct EvalPlan {
     bool soft = false;  // with a combine: k_mask_combine_soft in k_mask_combine's place -- a row the fold would empty keeps what it held
     SelOp selop = SelOp::kNone;  // with mask == kSelOp: the operator k_eval_selop answers
     bool seltag = false;  // mask == kSelTag: k_eval_seltag reads the operator out of every selector entry
+    uint32_t terms = 0;  // mask == kSelTerms: k_eval_selterms ORs that many tagged rows per pod (not 0, T = 1 included; `seltag` is set too)
 
     bool pick_rides() const { return sampled == SampledPick::kRidesFill || sampled == SampledPick::kRidesTiles; }
     bool bestfit_rows() const { return bestfit != BestfitPick::kNone && bestfit != BestfitPick::kFromMask; }
@@ -119,6 +122,8 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
     // call combines (the caller's is the combine's left operand) or the caller gave none.
     // A tagged call (extension E9) is planned the same way, with the tagged kernel in the operator kernel's place; it carries no operator
     // (check_seltag_args), so an operator decides first only where a caller of plan_eval gives both.
+    // A term count (extension E10) modifies a tagged call and nothing else (check_selterms_args): the terms kernel takes the tagged
+    // kernel's place whenever the count is not 0, one term included; everything around it is the tagged call's plan.
     if (f.selop != SelOp::kNone || f.seltag) {
         if (f.selop != SelOp::kNone) {
             plan.selop = f.selop;
@@ -126,8 +131,9 @@ inline EvalPlan plan_eval(const EvalFacts &f) {
             plan.last_kernel = "selop";
         } else {
             plan.seltag = true;
-            plan.mask = MaskKernel::kSelTag;
-            plan.last_kernel = "seltag";
+            plan.terms = f.terms;
+            plan.mask = f.terms ? MaskKernel::kSelTerms : MaskKernel::kSelTag;
+            plan.last_kernel = f.terms ? "selterms" : "seltag";
         }
         plan.combine = f.combine;
         plan.soft = f.combine != CombineOp::kNone && f.soft;

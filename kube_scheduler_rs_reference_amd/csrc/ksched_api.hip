@@ -36,6 +36,7 @@
 #include "kernels_combine_soft.hpp" // (extension E7: ... row by row, unless that would leave the row empty)
 #include "kernels_selop.hpp"        // (extension E8: the mask of an operator call -- Exists, Gt, Lt)
 #include "kernels_seltag.hpp"       // (extension E9: the mask of a tagged call -- the operator per pod and key)
+#include "kernels_selterms.hpp"     // (extension E10: ... with a term count -- the OR of several tagged rows per pod)
 #include "mask_alloc.hpp"
 #include "merge_sort_plan.hpp"
 #include "pipe_plan.hpp"
@@ -1187,6 +1188,9 @@ int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
     } else if (plan.mask == MaskKernel::kSelTag) {  // (extension E9: the selector term alone, the operator read out of every entry, from the label columns)
         if (hipError_t e = run_seltag(c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, s); e != hipSuccess)
             return fail_hip(c, e, "run_seltag");
+    } else if (plan.mask == MaskKernel::kSelTerms) {  // (extension E10: the OR over the plan's term count of such terms, entries [terms][nkeys][p])
+        if (hipError_t e = run_selterms(c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, plan.terms, s); e != hipSuccess)
+            return fail_hip(c, e, "run_selterms");
     } else if (int rc = run_direct(c, r, feas)) {
         return rc;
     }
@@ -1237,6 +1241,7 @@ EvalFacts eval_facts(const ksched_ctx *c, const EvalRequest &r) {
     f.soft = combine_soft(r.flags);
     f.selop = sel_op(r.flags);
     f.seltag = sel_tagged(r.flags);
+    f.terms = sel_terms(r.flags);
     return f;
 }
 
@@ -1284,6 +1289,7 @@ struct HostBatch {
     const int64_t *pcpu = nullptr, *pmem = nullptr;
     const uint32_t *psel = nullptr;  // [n_keys][sel_stride], of which the first p entries of every column are the batch's
     uint32_t sel_stride = 0;
+    uint32_t terms = 0;  // not 0 (extension E10): [terms][n_keys][sel_stride], selterms_columns columns in all
     const uint64_t *ptol = nullptr;
     const uint32_t *samples = nullptr;  // [p][attempts]
     uint32_t attempts = 0;
@@ -1299,11 +1305,12 @@ int stage_batch(ksched_ctx *c, uint32_t p, const HostBatch &h, hipStream_t s) {
         HIPCHK(c, hipMemcpyAsync(c->pmem.ptr, h.pmem, (size_t)p * 8, hipMemcpyHostToDevice, s));
     }
     if (h.psel) {
-        HIPCHK(c, c->psel.reserve((size_t)p * c->nkeys));
+        const size_t cols = selterms_columns(h.terms, c->nkeys);  // (n_keys without a term count)
+        HIPCHK(c, c->psel.reserve((size_t)p * cols));
         if (h.sel_stride == p)
-            HIPCHK(c, hipMemcpyAsync(c->psel.ptr, h.psel, (size_t)p * c->nkeys * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(c->psel.ptr, h.psel, (size_t)p * cols * 4, hipMemcpyHostToDevice, s));
         else  // rows [lo, lo + p) of a [n_keys][sel_stride] array: column k of the shard starts sel_stride entries after column k - 1's
-            HIPCHK(c, hipMemcpy2DAsync(c->psel.ptr, (size_t)p * 4, h.psel, (size_t)h.sel_stride * 4, (size_t)p * 4, c->nkeys, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpy2DAsync(c->psel.ptr, (size_t)p * 4, h.psel, (size_t)h.sel_stride * 4, (size_t)p * 4, cols, hipMemcpyHostToDevice, s));
     }
     if (h.ptol) {
         HIPCHK(c, c->ptol.reserve(p));
@@ -1326,15 +1333,16 @@ inline bool at_most_one_pick(uint32_t flags) {
 // the arguments of an evaluation call: the scalars, and which pointers are null (host or device pointers alike: none is followed).
 // combine_accepted: the entry point takes the KSCHED_COMBINE_* flags (the two device-pointer evaluations; mask_combine.hpp and
 // mask_combine_soft.hpp have the rules).  selop_accepted: it takes the KSCHED_SELOP_* flags (every evaluation but ksched_pipe_submit;
-// sel_ops.hpp has the rules) and, with them, KSCHED_SELOP_TAGGED (sel_tags.hpp has the rules)
+// sel_ops.hpp has the rules) and, with them, KSCHED_SELOP_TAGGED (sel_tags.hpp has the rules) and its term count (sel_terms.hpp)
 int check_eval_args(const EvalRequest &r, bool combine_accepted = false, bool selop_accepted = true) {
     const uint32_t flags = r.flags;
     const uint32_t known = KSCHED_FIT | KSCHED_SEL | KSCHED_TAINT | KSCHED_PICK_ANY | KSCHED_WANT_FIT_MASK | KSCHED_COMBINE_ANY | KSCHED_COMBINE_SOFT | KSCHED_SELOP_ANY |
-                           KSCHED_SELOP_TAGGED;
+                           KSCHED_SELOP_TAGGED | KSCHED_SEL_TERMS_MASK;
     if (flags & ~known) return KSCHED_E_INVAL;
     if (int rcc = check_soft_args(flags, combine_accepted, r.out_feas != nullptr, r.out_fit != nullptr)) return rcc;
     if (int rco = check_selop_args(flags, selop_accepted, r.out_fit != nullptr)) return rco;
     if (int rct = check_seltag_args(flags, selop_accepted, r.out_fit != nullptr)) return rct;
+    if (int rcm = check_selterms_args(flags, selop_accepted, r.out_fit != nullptr)) return rcm;
     if (!at_most_one_pick(flags)) return KSCHED_E_INVAL;
     if (r.p > 0 && (!r.pcpu || !r.pmem)) return KSCHED_E_INVAL;
     if (flags & KSCHED_PICK_DRAWS) {
@@ -1979,7 +1987,7 @@ int eval_begin_locked(ksched_ctx *c, const EvalRequest &h, uint32_t sel_stride, 
     HostBatch b;  // what is uploaded: the requests always, selectors and tolerations where their term is active, the draws of a sampled, uniform, spread or pack pick
     b.pcpu = h.pcpu;
     b.pmem = h.pmem;
-    if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride;
+    if (h.sel(c->nkeys)) b.psel = h.psel, b.sel_stride = sel_stride, b.terms = sel_terms(flags);
     if (h.taint_flag()) b.ptol = h.ptol;
     if (flags & KSCHED_PICK_DRAWS) b.samples = h.samples, b.attempts = h.attempts;
     int32_t *d_bind = nullptr;

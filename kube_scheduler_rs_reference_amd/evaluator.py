@@ -205,11 +205,12 @@ class Evaluator:
         after batch keeps its result buffers (a fresh 63 MB numpy array is first touched BY the copy: 6 ms per C3 mask instead of 1.4).
         The COMBINE_* flags are refused here (ValueError): masks are combined on the device, by eval_device.
         SEL with one of SELOP_EXISTS / SELOP_GT / SELOP_LT (extension E8) is an operator call, as in eval_device; SEL | SELOP_TAGGED
-        (extension E9) a tagged call, as there."""
+        (extension E9) a tagged call, as there, and with `sel_terms(T)` in the flags (extension E10) sel_val_ids is [T][n_keys][p]."""
         M.combine(flags, "Evaluator.eval", accepted=False)
         M.soft(flags, "Evaluator.eval", accepted=False)
         M.selop(flags, "Evaluator.eval", accepted=True)
         M.seltag(flags, "Evaluator.eval", accepted=True)
+        M.selterms(flags, "Evaluator.eval", accepted=True)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples, flags)
         p, W = b.p, self.W
         res = EvalResult()
@@ -252,7 +253,11 @@ class Evaluator:
         tag << SELTAG_SHIFT | id with tag SELTAG_EQ / _NE / _EXISTS / _ABSENT / _GT / _LT, compared against the node's whole 32-bit id (entry
         0: unconstrained; SEL_NEVER: nothing; NE and ABSENT pass a node without the key), so one call answers a whole conjunctive
         matchExpressions term per pod: `gpu Exists and cores Gt 16 and zone NotIn {z3}` is one row.  No SELOP_EXISTS / _GT / _LT, FIT, TAINT
-        or WANT_FIT_MASK beside it; a COMBINE_* op (with or without COMBINE_SOFT) and a pick may be.  Interned ids must stay below 2^29."""
+        or WANT_FIT_MASK beside it; a COMBINE_* op (with or without COMBINE_SOFT) and a pick may be.  Interned ids must stay below 2^29.
+        SEL | SELOP_TAGGED | sel_terms(T) (extension E10, 1 <= T <= MAX_TERMS) takes T tagged rows per pod, sel_val_ids [T, n_keys, p] (or
+        [T * n_keys, p]), and writes the OR of the T conjunctions: a required nodeAffinity -- ORed nodeSelectorTerms, `In {a, b}` as two
+        terms -- in one call and one mask.  An all-zero term passes everywhere; a term with SEL_NEVER in one key passes nowhere (the padding
+        of a pod with fewer terms).  `node_affinity_rows` builds such rows from matchExpressions.  Everything else is the tagged call's."""
         calls, _ = self._marshal_eval_device((req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, samples), flags,
                                              [out_feasible], out_fit, [out_binding], stream)
         self._check(self._lib.ksched_eval_device_pitched(*calls[0][0]), "ksched_eval_device_pitched")
@@ -266,6 +271,7 @@ class Evaluator:
         M.soft(flags, "Evaluator.eval_device", accepted=True)
         M.selop(flags, "Evaluator.eval_device", accepted=True, out_fit=out_fit)
         M.seltag(flags, "Evaluator.eval_device", accepted=True, out_fit=out_fit)
+        M.selterms(flags, "Evaluator.eval_device", accepted=True, out_fit=out_fit)
         b = M.device_batch(self.device, self.n_keys, *cols, flags)
         (*pm, pr), pitch = M.mask_rows(b.p, self.W, self.device, *[("out_feasible", m) for m in masks], ("out_fit", out_fit))
         po = [M.device_ptr(o, "out_binding", "i32", (b.p,), self.device) for o in outs]
@@ -301,6 +307,7 @@ class Evaluator:
         import torch
         M.selop(flags, "Evaluator.pick_device", accepted=False)
         M.seltag(flags, "Evaluator.pick_device", accepted=False)
+        M.selterms(flags, "Evaluator.pick_device", accepted=False)
         if feasible is None or len(feasible.shape) != 2:
             raise ValueError(f"feasible must be a [p, {self.W}] CUDA mask with unit column stride")
         b = M.device_batch(self.device, self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=feasible.shape[0])
@@ -317,6 +324,7 @@ class Evaluator:
         [p, attempts]: 32-bit draws, column 0 is read), PICK_SPREAD / PICK_PACK (+ samples [p, d]: 32-bit draws, all read; no req_mem_bytes needed) or PICK_BESTFIT (+ FIT and req_mem_bytes when the mask includes the resource fit)."""
         M.selop(flags, "Evaluator.pick", accepted=False)
         M.seltag(flags, "Evaluator.pick", accepted=False)
+        M.selterms(flags, "Evaluator.pick", accepted=False)
         f = M.host_array(feasible, "feasible", "u64", (None, self.W))
         b = M.host_batch(self.n_keys, None, req_mem_bytes, None, None, samples, flags, p=f.shape[0])
         out = np.empty((b.p,), dtype=np.int32)
@@ -356,6 +364,7 @@ class Evaluator:
         """ksched_explain: REASON_* of check_node_validity for the listed (pod, node) pairs, decided on the device."""
         M.selop(flags, "Evaluator.explain", accepted=False)
         M.seltag(flags, "Evaluator.explain", accepted=False)
+        M.selterms(flags, "Evaluator.explain", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         pp = M.host_array(pair_pod, "pair_pod", "u32", (None,))
         pn = M.host_array(pair_node, "pair_node", "u32", pp.shape)
@@ -369,6 +378,7 @@ class Evaluator:
         (column r = REASON_*; column 0 = feasible nodes; every row adds up to the node count)."""
         M.selop(flags, "Evaluator.summarize", accepted=False)
         M.seltag(flags, "Evaluator.summarize", accepted=False)
+        M.selterms(flags, "Evaluator.summarize", accepted=False)
         b = M.host_batch(self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         out = np.empty((b.p, L.SUMMARY_WORDS), dtype=np.uint32)
         rc = self._lib.ksched_summarize(self._h, *b[:5], int(flags), _ptr(out))
@@ -382,6 +392,7 @@ class Evaluator:
         import torch
         M.selop(flags, "Evaluator.summarize_device", accepted=False)
         M.seltag(flags, "Evaluator.summarize_device", accepted=False)
+        M.selterms(flags, "Evaluator.summarize_device", accepted=False)
         b = M.device_batch(self.device, self.n_keys, req_cpu_milli, req_mem_bytes, sel_val_ids, tolerations, None, 0)
         if out is None:
             out = torch.empty((b.p, L.SUMMARY_WORDS), dtype=torch.int32, device=torch.device("cuda", self.device))
@@ -459,6 +470,7 @@ class Pipe:
         M.soft(flags, "Pipe.submit", accepted=False)
         M.selop(flags, "Pipe.submit", accepted=False)
         M.seltag(flags, "Pipe.submit", accepted=False)
+        M.selterms(flags, "Pipe.submit", accepted=False)
         b = M.device_batch(ev.device, ev.n_keys, *cols, flags)
         per_slot = []
         for m, o in zip(masks, bindings):

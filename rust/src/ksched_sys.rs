@@ -62,6 +62,13 @@ pub const KSCHED_SELTAG_EXISTS: u32 = 2; // v != 0
 pub const KSCHED_SELTAG_ABSENT: u32 = 3; // v == 0 (DoesNotExist)
 pub const KSCHED_SELTAG_GT: u32 = 4; // v != 0 && v > id
 pub const KSCHED_SELTAG_LT: u32 = 5; // v != 0 && v < id; tags 6 and 7 (KSCHED_SEL_NEVER) pass nowhere
+pub const KSCHED_SEL_TERMS_SHIFT: u32 = 20; // extension E10, a modifier of a tagged call: a term count in bits 20 .. 23 of the flag word
+pub const KSCHED_SEL_TERMS_MASK: u32 = 0x00F00000; // 0: no term field; t: sel_val_ids is [t][n_keys][p], the pod's row the OR of its t tagged rows
+pub const KSCHED_MAX_TERMS: u32 = 15;
+/// KSCHED_SEL_TERMS(t): the flag field of a tagged call with `t` terms per pod, 1 <= t <= KSCHED_MAX_TERMS
+pub const fn ksched_sel_terms(t: u32) -> u32 {
+    t << KSCHED_SEL_TERMS_SHIFT
+}
 
 pub const KSCHED_APPLY_FIRST_PER_NODE: u32 = 0x01; // ksched_apply_bindings_device flags
 pub const KSCHED_APPLY_RELEASE: u32 = 0x02;
@@ -335,6 +342,9 @@ pub fn constant_table() -> Vec<(&'static str, i64)> {
         ("KSCHED_SELTAG_ABSENT", KSCHED_SELTAG_ABSENT as i64),
         ("KSCHED_SELTAG_GT", KSCHED_SELTAG_GT as i64),
         ("KSCHED_SELTAG_LT", KSCHED_SELTAG_LT as i64),
+        ("KSCHED_SEL_TERMS_SHIFT", KSCHED_SEL_TERMS_SHIFT as i64),
+        ("KSCHED_SEL_TERMS_MASK", KSCHED_SEL_TERMS_MASK as i64),
+        ("KSCHED_MAX_TERMS", KSCHED_MAX_TERMS as i64),
         ("KSCHED_APPLY_FIRST_PER_NODE", KSCHED_APPLY_FIRST_PER_NODE as i64),
         ("KSCHED_APPLY_RELEASE", KSCHED_APPLY_RELEASE as i64),
         ("KSCHED_APPLY_WHILE_FIT", KSCHED_APPLY_WHILE_FIT as i64),
