@@ -46,6 +46,20 @@ case_sizes enqueues chain (c) with PICK_SPREAD behind its soft chain with no hos
 standing operator calls with two pod tiles per block.  Their input conditions (assert_selector_input_conditions: rows neither full nor
 empty, pods constrained through negated tags only, all tags present, pods constraining keys of both passes, what every link changes) are
 asserted from the references, so also without a GPU; the new legs draw nothing from `rng`.
+
+The terms call (KSCHED_SEL_TERMS: SEL | SELOP_TAGGED | sel_terms(T) -> k_eval_selterms up to eight keys, k_eval_selterms_wide past them) reads the
+same label columns and carries picks the same way.  snapshot() carries S["terms"], a [3][keys][pods] table from a generator of its own
+(terms_table: term 0 is S["tsel"], terms 1 and 2 the tagged selectors of the one and two pods before, a term count of 1 .. 3 per pod with
+SEL_NEVER padding behind it, and for pod % 8 == 5 a zero term behind a real one).  check_matrix runs, once per predicate set with SEL and
+in its reduced form too: (d) the bare mask through ksched_eval against tests/selterms_ref.py; (e) S["tsel"] under sel_terms(1) against the
+tagged mask, run by the terms kernel; (f) S["sel"] as term 0 with padding behind it against the oracle's SEL-only mask; (g) the chain of
+terms_chain_restated on one mask filled with ones -- the other predicates, the terms call with AND, the table rolled by one pod with the
+soft AND -- compared after every link, its last link carrying each pick in turn ("termchain-<pick>" in `seen`).  The ten-key and the
+nine-key snapshots take the wide kernel's per-term reset and pass walk.  case_sizes enqueues chain (g) with PICK_PACK on a third mask behind
+chain (c): the standing terms call with two pod tiles per block.  Input conditions (assert_terms_input_conditions: rows neither empty nor
+full, rows in which the OR shows, rows completed by a term behind term 0, rows an and-of-ors kernel gets wrong, the term counts, what
+every link changes) are asserted from the references from 63 nodes on (terms_condition; the other legs' conditions start at 1025), so also
+without a GPU; these legs draw nothing from `rng` either.
 """
 from __future__ import annotations
 
@@ -56,11 +70,11 @@ import numpy as np
 import torch
 
 from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, PICK_BESTFIT, PICK_PACK, PICK_SAMPLED, PICK_SPREAD,
-                                             PICK_UNIFORM, SEL, SEL_NEVER, SELOP_EXISTS, SELOP_GT, SELOP_LT, SELOP_TAGGED, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, synth,
-                                             unpack_mask)
+                                             PICK_UNIFORM, SEL, SEL_NEVER, SELOP_EXISTS, SELOP_GT, SELOP_LT, SELOP_TAGGED, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, sel_terms,
+                                             synth, unpack_mask)
 from oracle import capi
 from oracle.oracle_ref import apply_bindings_exact  # (the two other rules on an admit round's inputs: admit_round_conditions)
-from tests import combine_ref, selop_ref, seltag_ref, soft_ref
+from tests import combine_ref, selop_ref, selterms_ref, seltag_ref, soft_ref
 from tests.admit_ref import admitted_behind_deferred, apply_exact, longest_segment
 from tests.knife_edges import sampled as sampled_from_bits  # ksched_pick's rule for PICK_SAMPLED on a [p, n] table of bits
 from tests.pack_ref import pack_pick_listed
@@ -119,6 +133,8 @@ def snapshot(kind, N, P, seed):
         raise ValueError(kind)
     # the tagged call reads 29-bit ids (and the tag in an entry's top three bits): the largest id of these snapshots is 63 000, at 60 000 nodes
     assert int(lab.max(initial=0)) < 1 << 29 and int(sel[sel != SEL_NEVER].max(initial=0)) < 1 << 29, f"{kind} N={N}: an id at or above 2^29"
+    tsel = tagged_table(np.ascontiguousarray(sel), np.random.default_rng([seed, 0xE9]))
+    terms, tcount = terms_table(np.ascontiguousarray(sel), tsel, np.random.default_rng([seed, 0xE10]))
     return dict(kind=kind, N=N, P=P, cpu=c.avail_cpu.copy(), mem=c.avail_mem.copy(), lab=np.ascontiguousarray(lab), tnt=tnt,
                 rc=c.req_cpu, rm=c.req_mem, sel=np.ascontiguousarray(sel), tol=tol, preds=preds, indexed=kind != "unindexed",
                 smp5=rng.integers(0, N + 2, (P, 5)).astype(np.uint32), smp3=rng.integers(0, N, (P, 3)).astype(np.uint32),
@@ -127,7 +143,9 @@ def snapshot(kind, N, P, seed):
                 # and for the spread pick: 64 columns, of which a leg reads the first d
                 smpS=np.random.default_rng([seed, 0x5E]).integers(0, 1 << 32, (P, 64), dtype=np.uint64).astype(np.uint32),
                 # and for the tagged call (KSCHED_SELOP_TAGGED): the selector table with a tag per entry, likewise from a generator of its own
-                tsel=tagged_table(np.ascontiguousarray(sel), np.random.default_rng([seed, 0xE9])))
+                tsel=tsel,
+                # and for the terms call (KSCHED_SEL_TERMS): TERMS tagged rows per pod and the pods' own term counts, likewise (terms_table)
+                terms=terms, tcount=tcount)
 
 
 def tagged_table(sel, g):
@@ -136,6 +154,30 @@ def tagged_table(sel, g):
     tags = g.integers(0, len(seltag_ref.TAGS), sel.shape)
     named = (sel != 0) & (sel != SEL_NEVER)
     return np.ascontiguousarray(np.where(named, seltag_ref.entry(tags, sel), sel).astype(np.uint32))
+
+
+TERMS = 3  # the term count T of the snapshot's terms table
+
+
+def terms_table(sel, tsel, g):
+    """-> (the [TERMS][keys][pods] table of the terms call (KSCHED_SEL_TERMS), the pods' own term counts c in 1 .. TERMS), every draw from
+    `g`: term 0 is `tsel`; term r (1, 2) is tagged_table of `sel` rolled by r pods -- pod i's further terms are what pods i - 1 and i - 2
+    select, under tags of their own --; every term at or behind the pod's c is the documented padding, all zeros with SEL_NEVER in one
+    drawn key (it passes nowhere); and for the pods with pod % 8 == 5 and c >= 2 term 1 is all zeros: a zero term that is not the first,
+    which completes the row behind a real term 0"""
+    K, P = sel.shape
+    terms = np.empty((TERMS, K, P), np.uint32)
+    terms[0] = tsel
+    for r in range(1, TERMS):
+        terms[r] = tagged_table(np.ascontiguousarray(np.roll(sel, r, axis=1)), g)
+    c = g.integers(1, TERMS + 1, P)
+    pad_key = g.integers(0, K, (TERMS, P))
+    for r in range(1, TERMS):
+        pods = np.nonzero(c <= r)[0]
+        terms[r][:, pods] = 0
+        terms[r][pad_key[r][pods], pods] = SEL_NEVER
+    terms[1][:, (np.arange(P) % 8 == 5) & (c >= 2)] = 0
+    return terms, c
 
 
 def set_nodes(ev, S, cpu, mem):
@@ -303,29 +345,43 @@ def row_popcounts(m):
     return _POP8[np.ascontiguousarray(m).view(np.uint8)].sum(axis=1, dtype=np.int64)
 
 
-def _in_pod_blocks(fn, entries, n, cells=1 << 25):
-    """fn(entries [keys][pods]) -> packed rows, in blocks of pods: the restatements hold [pods, n] tables, and the sizes case has 3000 x 60 000"""
+def _pod_blocks(fn, entries, n, cells=1 << 25):
+    """[fn(a block of entries [...][pods])] over blocks of pods: the restatements hold [pods, n] tables, and the sizes case has 3000 x 60 000"""
     step = max(1, cells // max(int(n), 1))
-    return np.concatenate([fn(np.ascontiguousarray(entries[:, lo:lo + step])) for lo in range(0, entries.shape[1], step)])
+    return [fn(np.ascontiguousarray(entries[..., lo:lo + step])) for lo in range(0, entries.shape[-1], step)]
+
+
+def _in_pod_blocks(fn, entries, n):
+    """fn(entries [keys][pods] or [terms][keys][pods]) -> packed rows, in blocks of pods"""
+    return np.concatenate(_pod_blocks(fn, entries, n))
 
 
 def selector_masks(S):
     """the expected bare masks of the snapshot's operator and tagged calls: {SELOP_EXISTS, SELOP_GT, SELOP_LT: tests/selop_ref.py on
     S["sel"]; "tagged": tests/seltag_ref.py on S["tsel"]; "lt-rolled": SELOP_LT on rolled_sel(S, ROLLS[0]), the operand of chain (c)'s last
-    link}.  They depend on the label columns and the two tables alone, which no apply and no update of cpu / mem moves: computed once and
-    kept beside the three arrays they were computed from -- a caller that hands on a copy of S with other labels or another table (dict(S,
+    link; "terms": tests/selterms_ref.py on S["terms"], "term-0" .. "term-2": its single terms' tagged masks, "terms-rolled": "terms" of the
+    table rolled by ROLLS[0] pods, the operand of chain (g)'s last link}.  They depend on the label columns and the three tables alone, which no apply and no update of cpu / mem moves: computed once and
+    kept beside the four arrays they were computed from -- a caller that hands on a copy of S with other labels or another table (dict(S,
     lab=...), as tests/test_gpu_node_labels.py does after a label update) gets masks of its own; read-only from then on"""
-    lab, sel, tsel, N = S["lab"], S["sel"], S["tsel"], S["N"]
+    lab, sel, tsel, terms, N = S["lab"], S["sel"], S["tsel"], S["terms"], S["N"]
     kept = S.get("_selector_masks")
-    if kept is None or kept[0] is not lab or kept[1] is not sel or kept[2] is not tsel:
+    if kept is None or kept[0] is not lab or kept[1] is not sel or kept[2] is not tsel or kept[3] is not terms:
         assert int(lab.max(initial=0)) < 1 << 29 and int(sel[sel != SEL_NEVER].max(initial=0)) < 1 << 29, "an id at or above 2^29"
         m = {op: _in_pod_blocks(lambda e, op=op: selop_ref.selop_mask(lab, e, op), sel, N) for op, _ in SELOPS}
         m["tagged"] = _in_pod_blocks(lambda e: seltag_ref.seltag_mask(lab, e), tsel, N)
         m["lt-rolled"] = _in_pod_blocks(lambda e: selop_ref.selop_mask(lab, e, SELOP_LT), rolled_sel(S, ROLLS[0]), N)
+        # the terms call (KSCHED_SEL_TERMS) on S["terms"]: tests/selterms_ref.py, and every single term's tagged mask beside it.  The table
+        # rolled by k pods has the same rows k pods further on (row i of the rolled table is computed from the entries of pod i - k), so
+        # chain (g)'s last operand is a roll of the rows
+        blocks = _pod_blocks(lambda e: selterms_ref.selterms_and_term_masks(lab, e), terms, N)  # (every term's [pods, n] table is computed once)
+        m["terms"] = np.concatenate([b[0] for b in blocks])
+        for r in range(terms.shape[0]):
+            m[f"term-{r}"] = np.concatenate([b[1][r] for b in blocks])
+        m["terms-rolled"] = np.roll(m["terms"], ROLLS[0], axis=0)
         for a in m.values():
             a.setflags(write=False)
-        S["_selector_masks"] = kept = (lab, sel, tsel, m)
-    return kept[3]
+        S["_selector_masks"] = kept = (lab, sel, tsel, terms, m)
+    return kept[4]
 
 
 def selector_chain_restated(S, cpu, mem, preds):
@@ -395,11 +451,86 @@ def assert_selector_input_conditions(S, chain, what):
     assert min(changed) >= 0.05, msg
 
 
+# ---- the terms call (KSCHED_SEL_TERMS: SEL | SELOP_TAGGED | sel_terms(T) -> k_eval_selterms, k_eval_selterms_wide past eight keys): the bare
+# masks and chain (g), from tests/selterms_ref.py on the label columns and from the oracle's FIT / TAINT mask on the restated columns
+TERMS_FLAGS = SEL | SELOP_TAGGED | sel_terms(TERMS)
+assert TERMS_FLAGS == SEL | seltag_ref.TAGGED | selterms_ref.field(TERMS)
+_termchains = [0]  # terms chains run so far in this process: the last link's pick and the mask's layout go by it
+
+
+def padded_plain_table(S):
+    """S["sel"] as term 0 of a TERMS-term table whose other terms are the documented padding (all zeros, SEL_NEVER in key r % keys): under
+    the terms call the oracle's SEL-only mask"""
+    sel = S["sel"]
+    tab = np.zeros((TERMS,) + sel.shape, np.uint32)
+    tab[0] = sel
+    for r in range(1, TERMS):
+        tab[r, r % sel.shape[0]] = SEL_NEVER
+    return tab
+
+
+def rolled_terms(S, k):
+    return np.ascontiguousarray(np.roll(S["terms"], k, axis=2))
+
+
+def terms_chain_restated(S, cpu, mem, preds):
+    """chain (g) on the columns cpu / mem: -> dict(first = the flags of link 1, links = the mask after each of the three links):
+      1  preds & ~SEL (FIT alone where that is empty), plain: the oracle's mask;
+      2  TERMS_FLAGS | COMBINE_AND with S["terms"];
+      3  TERMS_FLAGS | COMBINE_AND | COMBINE_SOFT with the table rolled by ROLLS[0] pods (pod i prefers what pod i - 1 requires), the link
+         that carries a pick
+    -- tests/combine_ref.py / tests/soft_ref.py on selector_masks"""
+    N, m = S["N"], selector_masks(S)
+    first = (preds & ~SEL) or FIT
+    l1 = oracle_mask(S, cpu, mem, first)
+    l2 = combine_ref.combine(l1, m["terms"], COMBINE_AND, N)
+    l3 = soft_ref.soft_combine(l2, m["terms-rolled"], COMBINE_AND, N)
+    return dict(first=first, links=(l1, l2, l3))
+
+
+def assert_terms_input_conditions(S, chain, what):
+    """the legs of the terms call cannot pass vacuously -- conditions on the references, each printed in words of its own: a quarter or more
+    of the rows of the expected mask are neither full nor empty; 5 % of the pods or more have a row that differs from every one of their
+    single-term rows (the OR shows: a kernel that kept one term's word fails); a tenth or more have a full row although term 0's row is
+    not full (the narrow kernel's early exit fires behind a later term -- or, for a wave whose columns a term does not complete, not at
+    all); on a snapshot of more than eight keys a fifth of the rows or more differ from selterms_ref.and_of_ors_mask, what a kernel
+    computes that ORs the terms pass by pass and ANDs the passes; each term count 1 .. TERMS occurs in a fifth of the pods or more; and
+    every link of chain (g) changes the mask of 5 % of the rows or more (link 1: against the all-valid rows)"""
+    N, P, m, terms = S["N"], S["P"], selector_masks(S), S["terms"]
+    cnt = row_popcounts(m["terms"])
+    mixed = float(((cnt > 0) & (cnt < N)).mean())
+    singles = [m[f"term-{r}"] for r in range(terms.shape[0])]
+    shows = float(np.stack([(m["terms"] != s).any(axis=1) for s in singles]).all(axis=0).mean())
+    late = float(((cnt == N) & (row_popcounts(singles[0]) < N)).mean())
+    msg = (f"{what}: of the rows of the terms call {100 * mixed:.1f} % are neither empty nor full, {100 * shows:.1f} % differ from every single term's row, "
+           f"{100 * late:.1f} % are full although term 0's row is not")
+    print(msg)
+    assert mixed >= 0.25 and shows >= 0.05 and late >= 0.10, msg
+    if terms.shape[1] > 8:
+        wrong = _in_pod_blocks(lambda e: selterms_ref.and_of_ors_mask(S["lab"], e, 8), terms, N)
+        differs = float((wrong != m["terms"]).any(axis=1).mean())
+        msg = f"{what}: the terms ORed pass by pass and the passes ANDed differ from the terms call in {100 * differs:.1f} % of the rows"
+        print(msg)
+        assert differs >= 0.20, msg
+    counts = np.bincount(S["tcount"], minlength=terms.shape[0] + 1)[1:] / P
+    msg = f"{what}: term counts 1 .. {terms.shape[0]} occur in {', '.join(f'{100 * x:.1f}' for x in counts)} % of the pods"
+    print(msg)
+    assert len(counts) == terms.shape[0] and counts.min() >= 0.20, msg
+    prev = selop_ref.selop_mask(S["lab"], None, SELOP_EXISTS, p=1)  # the all-valid row
+    changed = []
+    for cur in chain["links"]:
+        changed.append(float((cur != prev).any(axis=1).mean()))
+        prev = cur
+    msg = f"{what}: the terms chain's links change {', '.join(f'{100 * x:.1f}' for x in changed)} % of the rows"
+    print(msg)
+    assert min(changed) >= 0.05, msg
+
+
 def explain_pairs(rng, P, N, n_pairs=4000):
     return rng.integers(0, P, n_pairs).astype(np.uint32), rng.integers(0, N, n_pairs).astype(np.uint32)
 
 
-def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False):
+def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False, terms_condition=False):
     """check_matrix without a device: what it returns when every comparison holds -- the oracle's or the restatement's bindings of the
     `hand_on` pick under the first predicate set -- with the same input conditions asserted and the generator advanced alike"""
     out_b = None
@@ -415,6 +546,8 @@ def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sample
             assert_chain_input_conditions(S, feas, oracle_mask(S, cpu, mem, FIT), cpu, mem, soft_chain_restated(S, cpu, mem, feas), w)
             if preds & SEL:  # the operator and the tagged legs: the same expectations, from the references alone
                 assert_selector_input_conditions(S, selector_chain_restated(S, cpu, mem, preds), w)
+        if (input_condition or terms_condition) and preds & SEL:  # the terms call's floors hold from 63 nodes on
+            assert_terms_input_conditions(S, terms_chain_restated(S, cpu, mem, preds), w)
         if k == 0 and hand_on == "sampled":
             out_b = capi.eval_encoded(cpu, mem, S["lab"], S["tnt"] if preds & TAINT else None, S["rc"], S["rm"], S["sel"],
                                       S["tol"] if preds & TAINT else None, S["smp5"], preds | PICK_SAMPLED, want_mask=False)[2]
@@ -426,11 +559,12 @@ def restated_matrix(S, cpu, mem, seen, what, rng, reduced=False, hand_on="sample
     return out_b
 
 
-def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False):
+def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampled", input_condition=False, terms_condition=False):
     """every evaluation path of `ev` (whose snapshot should hold cpu / mem) against the oracle; the names of the picks that ran go into
     `seen`.  reduced: the kernels and options at their defaults, plus the direct kernel, the waves-form pick, bindings-only "select",
     best fit, the uniform pick, the spread pick, ksched_pick and ksched_explain.  input_condition: assert_input_condition and
-    assert_spread_input_condition on every predicate set's mask.
+    assert_spread_input_condition on every predicate set's mask.  terms_condition: assert_terms_input_conditions alone (the walks set it from
+    63 nodes on, where the terms call's floors hold already; the other conditions start at 1025).
     The spread legs, per predicate set, against tests/spread_ref.py on the oracle's mask and on cpu / mem (the columns after the apply):
     d = 5 beside the mask on every kernel choice; d = 2, bindings only, through host and device pointers; ksched_eval_device with d = 5
     beside a mask (last_pick == "spread" in both forms); ksched_pick from the oracle's host mask with d = 64; and once per matrix d = 1,
@@ -448,6 +582,13 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
     ones, packed in one predicate set and pitched in the next, compared after every link, whose last link -- LT under the soft AND --
     carries a pick (LAST_LINKS in turn over the chains of a process; names "selchain-<pick>" go into `seen`) compared with
     last_link_binding on the expected mask and cpu / mem, the words behind the batch untouched.
+    The terms call (KSCHED_SEL_TERMS), likewise once per predicate set with SEL, reduced or not (last_kernel "selterms" is asserted): (d) the
+    bare mask of S["terms"] under TERMS_FLAGS through ksched_eval against selector_masks' "terms" (tests/selterms_ref.py); (e) S["tsel"]
+    under sel_terms(1) == the tagged mask; (f) padded_plain_table == the oracle's SEL-only mask; (g) the chain of terms_chain_restated on
+    one mask filled with ones, packed in one predicate set and pitched in the next, compared after every link, whose last link -- the
+    table rolled by ROLLS[0] pods under the soft AND -- carries a pick (LAST_LINKS in turn, two on from the selector chain's; names
+    "termchain-<pick>" go into `seen`) compared with last_link_binding on the expected mask and cpu / mem, the words behind the batch
+    untouched.
     The new legs compare; they hand nothing on.
     -> the device bindings, under the first predicate set, of the pick `hand_on` names: "sampled", "uniform" or "spread" (a real
     evaluation's bindings for the next apply); None with hand_on=None"""
@@ -602,6 +743,43 @@ def check_matrix(ev, S, cpu, mem, seen, what, rng, reduced=False, hand_on="sampl
             assert np.array_equal(b[:P], want_b), f"{w} {c}: {int((b[:P] != want_b).sum())} bindings of the {pick} pick in the last link differ"
             assert (b[P:] == -7).all(), f"{w} {c}: the pick wrote past the batch"
             seen.add(f"selchain-{pick}")
+            # the terms call (KSCHED_SEL_TERMS), likewise once per predicate set
+            tc = terms_chain_restated(S, cpu, mem, preds)
+            if input_condition or terms_condition:
+                assert_terms_input_conditions(S, tc, w)
+            # (d) the bare mask through the host form
+            r = ev.eval(rc, rm, S["terms"], None, None, TERMS_FLAGS)
+            assert np.array_equal(r.feasible, sm["terms"]), f"{w} terms: pods {np.nonzero((r.feasible != sm['terms']).any(axis=1))[0][:5]} differ from selterms_ref"
+            assert ev.last_kernel == "selterms" and ev.last_pick == "none", f"{w} terms: ran as {ev.last_kernel} / {ev.last_pick}"
+            # (e) one term: S["tsel"] under sel_terms(1) is the tagged call's mask, through the terms kernel
+            r = ev.eval(rc, rm, S["tsel"], None, None, SEL | SELOP_TAGGED | sel_terms(1))
+            assert np.array_equal(r.feasible, sm["tagged"]), f"{w} one term: pods {np.nonzero((r.feasible != sm['tagged']).any(axis=1))[0][:5]} differ from seltag_ref"
+            assert ev.last_kernel == "selterms" and ev.last_pick == "none", f"{w} one term: ran as {ev.last_kernel} / {ev.last_pick}"
+            # (f) the plain table as term 0 and SEL_NEVER padding behind it is the oracle's SEL-only mask
+            r = ev.eval(rc, rm, padded_plain_table(S), None, None, TERMS_FLAGS)
+            assert np.array_equal(r.feasible, want_eq), f"{w} the plain table under sel_terms({TERMS}): pods {np.nonzero((r.feasible != want_eq).any(axis=1))[0][:5]} differ from the oracle"
+            assert ev.last_kernel == "selterms", f"{w} the plain table under sel_terms({TERMS}): ran as {ev.last_kernel}"
+            # (g) the other predicates, the terms call with AND, the rolled table's with the soft AND and a pick, on one mask filled with ones
+            n_chain = _termchains[0]
+            _termchains[0] += 1
+            # (two picks on: within one predicate set the terms chain carries another pick than the selector chain)
+            pick, lay = LAST_LINKS[(n_chain + 2) % len(LAST_LINKS)], "pitched" if n_chain % 2 else "packed"
+            flag, smp = link_smp[pick]
+            M, out = ev.alloc_mask(P, pitched=n_chain % 2 == 1), torch.full((P + 4,), -7, dtype=torch.int32, device=DEV)
+            M.fill_(-1)
+            c = f"{lay} terms chain"
+            link(M, tc["first"], tc["links"][0], f"{c}, link 1 ({tc['first']:#x})")
+            link(M, TERMS_FLAGS | COMBINE_AND, tc["links"][1], f"{c}, link 2 (terms, AND)", t(S["terms"], np.int32))
+            assert ev.last_kernel == "selterms" and ev.last_pick == "none", f"{w} {c}, link 2: ran as {ev.last_kernel} / {ev.last_pick}"
+            name = link(M, TERMS_FLAGS | COMBINE_AND | COMBINE_SOFT | flag, tc["links"][2], f"{c}, link 3 (rolled terms, soft AND) with the {pick} pick",
+                        t(rolled_terms(S, ROLLS[0]), np.int32), smp, out[:P])
+            assert ev.last_kernel == "selterms", f"{w} {c}, link 3: ran as {ev.last_kernel}"
+            assert name == {"pack": "pack", "spread": "spread", "uniform": "uniform"}.get(pick, "from-mask"), f"{w}: the {pick} pick of a terms call ran as {name}"
+            b = out.cpu().numpy()
+            want_b = last_link_binding(S, tc["links"][2], cpu, mem, pick)
+            assert np.array_equal(b[:P], want_b), f"{w} {c}: {int((b[:P] != want_b).sum())} bindings of the {pick} pick in the last link differ"
+            assert (b[P:] == -7).all(), f"{w} {c}: the pick wrote past the batch"
+            seen.add(f"termchain-{pick}")
         ev.set_kernel("auto")
         # bindings only: the sampled pick is its own launch ("select"), best fit reads no mask
         run(preds | PICK_SAMPLED, S["smp5"], want_mask=False, expect_b=bind_s, label="sampled, bindings only")
@@ -789,7 +967,7 @@ def walk_single(spec, begin, matrix, apply):
             handed.setdefault(N >= 1025, []).append(PICKS[(reals - 1) % len(PICKS)])
             return handed[N >= 1025][-1]
 
-        bind = matrix(S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on(0), input_condition=N >= 1025)
+        bind = matrix(S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on(0), input_condition=N >= 1025, terms_condition=N >= 63)
         applied = stale = stale_pack = 0
         for r in range(rounds):
             src, flags, use_ok = FORMS[(i + r) % len(FORMS)]
@@ -844,7 +1022,7 @@ def case_single(spec):
     want = {"taints": {"select", "fused", "fused-tile", "bestfit-rows", "from-mask", "uniform", "spread"},
             "many-keys": {"select", "fused", "bestfit-rows", "from-mask", "uniform", "spread"},
             "list-key": {"select", "bestfit-rows", "from-mask", "uniform", "spread"},
-            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind] | {"pack"} | {f"chain-{p}" for p in LAST_LINKS} | {f"selchain-{p}" for p in LAST_LINKS}
+            "unindexed": {"select", "from-mask", "uniform", "spread"}}[kind] | {"pack"} | {f"chain-{p}" for p in LAST_LINKS} | {f"selchain-{p}" for p in LAST_LINKS} | {f"termchain-{p}" for p in LAST_LINKS}
     assert want <= seen, f"{kind}: picks reached {sorted(seen)}, missing {sorted(want - seen)}"
     print(f"{kind}: picks reached {sorted(seen)}")
     ev.close()
@@ -871,7 +1049,10 @@ def sizes_step(step, N):
     with assert_chain_input_conditions' floors on the tiers and on the bindings the tiers move.
     selchain: what chain (c) of check_matrix (selector_chain_restated, with SIZES_PREDS) leaves on the same columns -- first (the flags of
     link 1), links (the mask after each of the five links) and bind (tests/spread_ref.py, d = 5, on the last mask and those columns);
-    from 1025 nodes on with assert_selector_input_conditions' floors."""
+    from 1025 nodes on with assert_selector_input_conditions' floors.
+    termchain: what chain (g) of check_matrix (terms_chain_restated, with SIZES_PREDS) leaves on the same columns -- first, links (the mask
+    after each of the three links) and bind (tests/pack_ref.py, d = 5, on the last mask and those columns); from 1025 nodes on with
+    assert_terms_input_conditions' floors."""
     P, WF = SIZES_PODS, _lib.APPLY_WHILE_FIT
     S = snapshot("taints", N, P, 0xC0 + step)
     cpu, mem = S["cpu"], S["mem"]
@@ -929,7 +1110,12 @@ def sizes_step(step, N):
     if N >= 1025:
         assert_selector_input_conditions(S, sc, f"{what} selchain")
     selchain = dict(first=sc["first"], links=sc["links"], bind=spread_restated(S, sc["links"][4], cpu, mem, 5))
-    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem, chain=chain, selchain=selchain)
+    # and chain (g) behind that: the terms call, PICK_PACK in the last link
+    tc = terms_chain_restated(S, cpu, mem, SIZES_PREDS)
+    if N >= 1025:
+        assert_terms_input_conditions(S, tc, f"{what} termchain")
+    termchain = dict(first=tc["first"], links=tc["links"], bind=pack_restated(S, tc["links"][2], cpu, mem, 5))
+    return dict(S=S, applies=applies, updates=updates, cpu=cpu, mem=mem, chain=chain, selchain=selchain, termchain=termchain)
 
 
 def case_sizes(spec):
@@ -937,7 +1123,10 @@ def case_sizes(spec):
     ksched_set_nodes what sizes_step lists -- an apply, an update of nodes in the tiles it touched, a second apply, a second update, an
     apply with WHILE_FIT (at 4097 nodes a second, four times as long, straight behind it) -- and behind those the soft chain of
     check_matrix with PICK_PACK in its last link (the mask copied on the stream after every link) and, on a second mask, chain (c) -- the
-    tagged call and the three operators, PICK_SPREAD in its last link, copied likewise --, enqueued with no host wait in between: with
+    tagged call and the three operators, PICK_SPREAD in its last link, copied likewise --, and on a third mask chain (g) -- the terms call
+    with AND, the rolled table's with the soft AND and PICK_PACK, copied likewise: with 3000 pods and three terms the standing terms call
+    whose blocks walk two pod tiles (plan_selterms_launch(3000, 782 / 938, 8, 3), pinned in tests/cpp/selterms_plan_tests.cpp) --,
+    enqueued with no host wait in between: with
     3000 pods at 50 000 and 60 000 nodes the only standing operator calls whose blocks walk two pod tiles (47 tiles in 24 block rows: the
     last block leaves its second slot at `first >= p`), and the only ones behind which the scratch mask is resized under queued work;
     then the chains' masks and bindings against sizes_step's, the statuses of every apply, the columns, the index (against a fresh ksched_set_nodes on a second ctx) and a direct and a fused
@@ -952,9 +1141,10 @@ def case_sizes(spec):
         sts, keep = [], []
         # the chain's operands and outputs, on the device before anything is enqueued (packed rows on even steps, pitched on odd ones)
         P = S["P"]
-        M, M2 = ev.alloc_mask(P, pitched=step % 2 == 1), ev.alloc_mask(P, pitched=step % 2 == 0)
-        out, out2 = (torch.full((P + 4,), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+        M, M2, M3 = ev.alloc_mask(P, pitched=step % 2 == 1), ev.alloc_mask(P, pitched=step % 2 == 0), ev.alloc_mask(P, pitched=step % 2 == 1)
+        out, out2, out3 = (torch.full((P + 4,), -7, dtype=torch.int32, device=DEV) for _ in range(3))
         tsel_t = t(S["tsel"], np.int32)
+        terms_t, terms_rolled_t = t(S["terms"], np.int32), t(rolled_terms(S, ROLLS[0]), np.int32)
         pods = (t(S["rc"], np.int64), t(S["rm"], np.int64))
         sels = [t(x, np.int32) for x in (S["sel"],) + q["chain"]["sel"]]
         tol_t, smp_t = t(S["tol"], np.int64), t(np.ascontiguousarray(S["smpS"][:, :5]), np.int32)
@@ -992,8 +1182,25 @@ def case_sizes(spec):
         ev.eval_device(*pods, sels[1], None, smp_t, SEL | SELOP_LT | COMBINE_AND | COMBINE_SOFT | PICK_SPREAD, out_feasible=M2, out_binding=out2[:P])
         assert ev.last_kernel == "selop" and ev.last_pick == "spread", (ev.last_kernel, ev.last_pick)
         links2.append(M2)
+        # chain (g) behind it, on the third mask, still with no host wait: the terms call evaluates into the same scratch mask
+        tc = q["termchain"]
+        M3.fill_(-1)
+        ev.eval_device(*pods, None, tol_t if tc["first"] & TAINT else None, None, tc["first"], out_feasible=M3)
+        links3 = [M3.clone()]
+        ev.eval_device(*pods, terms_t, None, None, TERMS_FLAGS | COMBINE_AND, out_feasible=M3)
+        assert ev.last_kernel == "selterms" and ev.last_pick == "none", (ev.last_kernel, ev.last_pick)
+        links3.append(M3.clone())
+        ev.eval_device(*pods, terms_rolled_t, None, smp_t, TERMS_FLAGS | COMBINE_AND | COMBINE_SOFT | PICK_PACK, out_feasible=M3, out_binding=out3[:P])
+        assert ev.last_kernel == "selterms" and ev.last_pick == "pack", (ev.last_kernel, ev.last_pick)
+        links3.append(M3)
         torch.cuda.synchronize()
         what = f"step {step} N={N}"
+        for k, (got, want) in enumerate(zip(links3, tc["links"]), 1):
+            got = got.contiguous().cpu().numpy().view(np.uint64)
+            assert np.array_equal(got, want), f"{what}: the terms chain behind the queued changes, link {k}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"
+        b = out3.cpu().numpy()
+        assert np.array_equal(b[:P], tc["bind"]) and (b[P:] == -7).all(), \
+            f"{what}: the terms chain's pack bindings: {int((b[:P] != tc['bind']).sum())} differ"
         for k, (got, want) in enumerate(zip(links2, sc["links"]), 1):
             got = got.contiguous().cpu().numpy().view(np.uint64)
             assert np.array_equal(got, want), f"{what}: the selector chain behind the queued changes, link {k}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"

@@ -396,7 +396,7 @@ def walk_paths(spec, begin, matrix, apply, end):
                 hand_on = ("sampled", "uniform")[(ki + n) % 2]
             else:
                 hand_on = PICKS[(ki + n) % len(PICKS)]
-            bind = matrix(0, S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on, input_condition=N >= 1025)
+            bind = matrix(0, S, cpu, mem, f"{kind} N={N} before any apply", rng, hand_on=hand_on, input_condition=N >= 1025, terms_condition=N >= 63)
             for r in range(2):
                 k += 1
                 flags, use_ok = (0, FPN, REL, FPN | REL)[k % 4], k % 3 != 0
@@ -434,7 +434,10 @@ def case_paths(spec):
     replica's scratch mask), against tests/pack_ref.py, tests/combine_ref.py and tests/soft_ref.py; and its operator and tagged selector
     legs (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED): the bare masks, the plain table under the tagged call against the
     oracle, and the selector chain whose last link's pick reads the columns the gathered commit has just written, against
-    tests/selop_ref.py and tests/seltag_ref.py -- all five picks of that link are reached in every run (asserted)"""
+    tests/selop_ref.py and tests/seltag_ref.py -- all five picks of that link are reached in every run (asserted); and its legs of the
+    terms call (KSCHED_SEL_TERMS): the bare mask of the three-term table against tests/selterms_ref.py, one term against the tagged mask,
+    the padded plain table against the oracle, and the terms chain whose soft last link carries each of the five picks in turn on the
+    columns the gathered commit has just written (likewise asserted)"""
     from tests.apply_paths_worker import check_matrix
     n = spec["n"]
     seen = set()
@@ -455,10 +458,12 @@ def case_paths(spec):
     k = walk_paths(spec, begin, lambda q, S, cpu, mem, what, rng, **kw: check_matrix(R[0].evs[q], S, cpu, mem, seen, what, rng, reduced=True, **kw),
                    apply, lambda: R[0].close())
     from tests.apply_paths_worker import LAST_LINKS
-    # (check_matrix's pack legs, combining chains and selector chains run on every replica too: the soft chain's and the selector chain's
-    # last link take each pick in turn)
-    assert {"select", "fused", "bestfit-rows", "uniform", "spread", "pack"} | {f"chain-{p}" for p in LAST_LINKS} | {f"selchain-{p}" for p in LAST_LINKS} <= seen, \
-        f"picks reached {sorted(seen)}"
+    # (check_matrix's pack legs, combining chains, selector chains and terms chains run on every replica too: the soft chain's, the selector
+    # chain's and the terms chain's last link take each pick in turn)
+    want = {"select", "fused", "bestfit-rows", "uniform", "spread", "pack"}
+    for chain in ("chain", "selchain", "termchain"):
+        want |= {f"{chain}-{p}" for p in LAST_LINKS}
+    assert want <= seen, f"picks reached {sorted(seen)}, missing {sorted(want - seen)}"
     print(f"{k} sharded applies, picks reached {sorted(seen)}")
 
 

@@ -249,6 +249,20 @@ static void the_launch() {
     CHECK(l.gx == 0 && l.gy == 0);  // nothing to launch
     l = plan_selterms_launch(5, 0, 8, 2);
     CHECK(l.gx == 0 && l.gy == 0);
+    // the geometry the standing legs rely on (tests/apply_paths_worker.py case_sizes and the walks): 3000 pods over 50 000 and 60 000 nodes
+    // with three terms -- 47 tiles, two a block, 24 block rows: 48 slots, so the last block breaks at `first >= p`; the narrow kernel --; a
+    // walk's 2000 pods over 4097 nodes with ten keys: the wide kernel, two key passes, one tile a block; and the sizes case's one-node step
+    l = plan_selterms_launch(3000, 782, 8, 3);
+    CHECK(l.gx == 49 && l.pod_tiles == 47 && l.pod_tiles_per_block == 2 && l.gy == 24 && l.key_passes == 1 && !l.wide && l.terms == 3);
+    l = plan_selterms_launch(3000, 938, 8, 3);
+    CHECK(l.gx == 59 && l.pod_tiles == 47 && l.pod_tiles_per_block == 2 && l.gy == 24 && l.key_passes == 1 && !l.wide && l.terms == 3);
+    l = plan_selterms_launch(2000, 65, 10, 3);
+    CHECK(l.gx == 5 && l.pod_tiles == 32 && l.gy == 32 && l.pod_tiles_per_block == 1 && l.key_passes == 2 && l.wide && l.terms == 3);
+    l = plan_selterms_launch(3000, 1, 8, 3);
+    CHECK(l.gx == 1 && l.pod_tiles == 47 && l.gy == 47 && l.pod_tiles_per_block == 1 && l.key_passes == 1 && !l.wide && l.terms == 3);
+    walk(3000, 782, 784, 8, 3);
+    walk(2000, 65, 65, 10, 3);
+    walk(3000, 1, 1, 8, 3);
     walk(2048u * 64u + 1u, 1, 1, 8, 2);  // one pod more than 2048 block rows of one tile: two tiles a block
     walk(3u * 2048u * 64u + 65u, 3, 4, 9, 3);
 }

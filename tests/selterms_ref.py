@@ -57,6 +57,18 @@ def selterms_mask(labels, entries, p: int = None) -> np.ndarray:
     return seltag_ref.pack(pass_bits(labels, entries))
 
 
+def selterms_and_term_masks(labels, entries):
+    """(selterms_mask(labels, entries), term_masks(labels, entries)) with every term's bits computed once: for callers that want the
+    single terms' rows beside the call's on large tables"""
+    labels = np.asarray(labels)
+    entries = as_terms(labels, entries)
+    bits = [seltag_ref.pass_bits(labels, e) for e in entries]
+    ok = np.zeros((entries.shape[2], labels.shape[1]), dtype=bool)
+    for b in bits:
+        ok |= b
+    return seltag_ref.pack(ok), [seltag_ref.pack(b) for b in bits]
+
+
 def and_of_ors_mask(labels, entries, keys_per_pass: int = 8) -> np.ndarray:
     """What a WRONG kernel computes that ORs the terms pass by pass (`keys_per_pass` keys at a time) and ANDs the passes' words: the formula
     the header's layout does NOT mean.  (A0 & A1) | (B0 & B1) against (A0 | B0) & (A1 | B1)."""

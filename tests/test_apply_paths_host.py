@@ -16,7 +16,11 @@ Likewise the operator and the tagged selector legs (KSCHED_SELOP_EXISTS / _GT / 
 tests/selop_ref.py and tests/seltag_ref.py alone): at 1025 nodes or more, under each operator and under the tagged table half of the
 constrained rows or more are neither full nor empty; a tenth of the pods or more are constrained through NE / ABSENT entries only; all six
 tags and SEL_NEVER occur; on the nine- and ten-key snapshots a tenth of the pods or more constrain a key below 8 and a key at 8 or above;
-every link of the selector chain changes 5 % of the rows or more -- in the single walks, the sizes plan and the replicated walk."""
+every link of the selector chain changes 5 % of the rows or more -- in the single walks, the sizes plan and the replicated walk.
+Likewise the legs of the terms call (KSCHED_SEL_TERMS; assert_terms_input_conditions, on tests/selterms_ref.py alone), from 63 nodes on: a
+quarter of the rows or more are neither empty nor full; 5 % or more differ from every single term's row; a tenth or more are full although
+term 0's row is not; on the nine- and ten-key snapshots a fifth or more differ from the and-of-ors formula; each term count occurs in a
+fifth of the pods or more; every link of the terms chain changes 5 % of the rows or more."""
 import numpy as np
 import pytest
 
@@ -53,6 +57,11 @@ def test_single_ctx_matrix_inputs(kind, capsys):
     # the operator and the tagged legs' conditions, per predicate set of the same node counts (every predicate set has SEL)
     assert out.count("are neither full nor empty") == out.count("through NE / ABSENT entries only") == out.count("the selector chain's links change") == sets
     assert out.count("constrain a key below 8 and a key at 8 or above") == (sets if kind in ("many-keys", "list-key") else 0)
+    # the terms call's conditions (assert_terms_input_conditions), per predicate set of the same node counts
+    # -- these from 63 nodes on: four node counts
+    tsets = sets // 3 * 4
+    assert out.count("of the rows of the terms call") == out.count("term counts 1 .. 3 occur in") == out.count("the terms chain's links change") == tsets
+    assert out.count("the terms ORed pass by pass and the passes ANDed differ") == (tsets if kind in ("many-keys", "list-key") else 0)
     # the admit round of every node count, with the floors walk_single sets on it (admit_round_conditions), printed in words of its own
     assert [out.count(f"{kind} N={N} admit round (") > 0 for N in NODES] == [True] * len(NODES)
     assert out.count("statuses (applied, unbound, not ok, deferred, overflow, bad node)") == len(NODES)
@@ -77,6 +86,9 @@ def test_sizes_case_inputs(capsys):
     # the selector chain behind it: the floors at the same three snapshots, expected masks and spread bindings for every step
     assert out.count("selchain: of the constrained rows") == out.count("selchain: the tagged table constrains") == big_steps
     assert out.count("selchain: the selector chain's links change") == big_steps
+    # and the terms chain behind that: the floors at the same three snapshots, expected masks and pack bindings for every step
+    assert out.count("termchain: of the rows of the terms call") == out.count("termchain: term counts 1 .. 3 occur in") == big_steps
+    assert out.count("termchain: the terms chain's links change") == big_steps
     for q in plans:
         S, c = q["S"], q["chain"]
         assert [m.shape for m in c["links"]] == [(S["P"], (S["N"] + 63) // 64)] * 3 and c["bind"].shape == (S["P"],)
@@ -84,6 +96,10 @@ def test_sizes_case_inputs(capsys):
         sc = q["selchain"]
         assert sc["first"] == W.FIT | W.TAINT and [m.shape for m in sc["links"]] == [(S["P"], (S["N"] + 63) // 64)] * 5 and sc["bind"].shape == (S["P"],)
         assert ((sc["bind"] >= 0) == sc["links"][4].any(axis=1)).all() and (sc["links"][4].any(axis=1) == sc["links"][3].any(axis=1)).all()  # the last link is soft
+        tc = q["termchain"]
+        assert tc["first"] == W.FIT | W.TAINT and [m.shape for m in tc["links"]] == [(S["P"], (S["N"] + 63) // 64)] * 3 and tc["bind"].shape == (S["P"],)
+        assert ((tc["bind"] >= 0) == tc["links"][2].any(axis=1)).all() and (tc["links"][2].any(axis=1) == tc["links"][1].any(axis=1)).all()  # the last link is soft
+        assert S["terms"].shape == (W.TERMS, S["sel"].shape[0], S["P"]) and np.array_equal(S["terms"][0], S["tsel"])
 
 
 def test_large_case_inputs(capsys):
@@ -120,6 +136,9 @@ def test_replicated_matrix_inputs(n, capsys):
     assert out.count("soft tier 1 (") == out.count("soft tier 2 (") == out.count("on the tier-2 mask binds") == out.count("the pack pick (d = 5) binds")
     assert out.count("are neither full nor empty") == out.count("through NE / ABSENT entries only") == out.count("the selector chain's links change") == sets
     assert out.count("constrain a key below 8 and a key at 8 or above") == 2  # the list-key snapshot's nine keys, at either node count
+    # (the terms call's floors from 63 nodes on: all three node counts)
+    assert out.count("of the rows of the terms call") == out.count("term counts 1 .. 3 occur in") == out.count("the terms chain's links change") == 3 * (2 + 1)
+    assert out.count("the terms ORed pass by pass and the passes ANDed differ") == 3  # the list-key snapshot's nine keys, at every node count
     assert {p for big, p in handed if big} == set(W.PICKS), handed  # at 1025 nodes or more: all three within one run
     # (below 1025 a run has two snapshots: the three picks over the runs with n = 1, 2, 3)
     assert len({p for big, p in handed if not big}) == 2, handed

@@ -39,6 +39,15 @@ restated columns.  The ten-key and the list-key snapshot take the kernels' secon
 PICK_SPREAD behind the soft chain, still with no host wait: with 3000 pods at 50 000 and 60 000 nodes its operator kernels walk two pod
 tiles per block.  Floors on the rows that are neither full nor empty, on the pods constrained through negated tags only, on the pods that
 constrain keys of both passes and on what every link changes are asserted from the references first.
+The terms call (KSCHED_SEL_TERMS: SEL | SELOP_TAGGED | sel_terms(T) -> k_eval_selterms, k_eval_selterms_wide past eight keys) runs beside them,
+once per predicate set in every matrix: the bare mask of a three-term table (the tagged table, the tagged selectors of the two pods before,
+per-pod term counts with SEL_NEVER padding, a zero term behind a real one) against tests/selterms_ref.py; the tagged table under
+sel_terms(1) against tests/seltag_ref.py; the plain table with padding behind it against the oracle's SEL-only mask; and a chain on one mask
+filled with ones -- the other predicates, the terms call with AND, the table rolled by one pod with the soft AND -- compared after every
+link, whose last link carries each of the five picks in turn.  The ten-key and the list-key snapshot take the wide kernel.  The sizes case
+enqueues that chain with PICK_PACK on a third mask behind the selector chain: the standing terms call with two pod tiles per block.  Floors
+on the rows that are neither empty nor full, that differ from every single term's row, that are full although term 0's is not, that an
+and-of-ors kernel would get wrong, on the term counts and on what every link changes are asserted from the references first.
 """
 import json
 import os
@@ -76,6 +85,7 @@ def test_every_path_after_an_apply(built, kind):
     for pick in ("pack", "spread", "uniform", "sampled", "bestfit"):
         assert f"'chain-{pick}'" in reached, f"no soft chain carried the {pick} pick in its last link"
         assert f"'selchain-{pick}'" in reached, f"no selector chain carried the {pick} pick in its last link"
+        assert f"'termchain-{pick}'" in reached, f"no terms chain carried the {pick} pick in its last link"
     for N in NODES:
         assert f"{kind} N={N} admit round (" in out, f"no admit round at {N} nodes"
 
@@ -88,6 +98,7 @@ def test_snapshot_sizes_and_updates_between_applies_on_one_ctx(built):
     assert out.count(": admit of ") == len(SIZES["nodes"]) + 1
     assert out.count("chain: the pack pick (d = 5) on the tier-2 mask binds") == 3  # the chain's floors, at the three snapshots from 1025 nodes on
     assert out.count("selchain: the selector chain's links change") == 3  # and the selector chain's, at the same three
+    assert out.count("termchain: the terms chain's links change") == 3  # and the terms chain's
 
 
 def test_a_batch_longer_than_one_stride_of_the_pod_kernels(built):

@@ -9,7 +9,8 @@ and KSCHED_COMBINE_SOFT against tests/combine_ref.py / tests/soft_ref.py, a pick
 tagged selector calls (KSCHED_SELOP_EXISTS / _GT / _LT, KSCHED_SELOP_TAGGED): their bare masks against tests/selop_ref.py /
 tests/seltag_ref.py, the plain table under the tagged call against the oracle, and a chain of them on one mask whose last link carries
 each of the five picks in turn on the columns the gathered commit wrote -- the first operator and tagged calls on a replica after a
-sharded apply."""
+sharded apply; and the terms call (KSCHED_SEL_TERMS) beside them: its bare mask against tests/selterms_ref.py, one term against the tagged
+mask, the padded plain table against the oracle and the terms chain with each of the five picks in its last link."""
 import json
 import os
 import subprocess
@@ -75,6 +76,7 @@ def test_every_replica_evaluates_right_after_a_sharded_apply(built, n):
     assert "'spread'" in reached, "the spread pick is not among the picks reached"
     for pick in ("pack", "spread", "uniform", "sampled", "bestfit"):
         assert f"'selchain-{pick}'" in reached, f"no selector chain carried the {pick} pick in its last link"
+        assert f"'termchain-{pick}'" in reached, f"no terms chain carried the {pick} pick in its last link"
 
 
 def test_shards_longer_than_one_stride_of_the_pod_kernels(built):

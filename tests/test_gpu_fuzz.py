@@ -15,8 +15,14 @@ into a sentinel-surrounded view at an odd pitch or base, about half of them as o
 pick -- and both through ksched_eval_begin / _end over 1 to 5 row shards (sel_stride > p); with the hooks both run on every replica after
 the sharded apply.  Asserted here: the tallies 'selop', 'seltag', 'seltag-negated-padding' (a pod constrained through NE / ABSENT only, in
 rows with padding bits) and 'selop-sharded-halves' in both runs, 'selop-on-replicas' with the hooks; 'selop-two-pass' and
-'selop-two-tiles' are recorded from a long run.  (240 s runs of the same tool: profiles/uniform_pick_standing_checks.txt,
-profiles/spread_pick_standing_checks.txt, profiles/combine_pack_standing_checks.txt, profiles/selop_seltag_standing_checks.txt.)"""
+'selop-two-tiles' are recorded from a long run.  And at every step with keys one terms call (KSCHED_SEL_TERMS: 1, 2, 3 or 15 terms per pod of such
+tagged entries, per-pod term counts with SEL_NEVER padding, now and then a zero term behind a real one) against tests/selterms_ref.py:
+the bare mask, the call under a drawn combine with a drawn pick, and the two halves over 1 to 5 row shards (column (t, k) at
+(t * n_keys + k) * sel_stride); with the hooks on every replica after the sharded apply.  Asserted here: 'selterms', 'selterms-late-full' (a
+pod whose row a term behind term 0 completes) and 'selterms-sharded-halves' in both runs, 'selterms-on-replicas' with the hooks;
+'selterms-wide' (more than eight keys) is recorded from a long run.  (240 s runs of the same tool: profiles/uniform_pick_standing_checks.txt,
+profiles/spread_pick_standing_checks.txt, profiles/combine_pack_standing_checks.txt, profiles/selop_seltag_standing_checks.txt,
+profiles/selterms_standing_checks.txt.)"""
 import os
 import re
 import subprocess
@@ -48,6 +54,9 @@ def assert_new_tallies(out):
     assert tally(out, "seltag") > 0, "no tagged call ran"
     assert tally(out, "seltag-negated-padding") > 0, "no tagged call had a pod constrained through NE / ABSENT only in rows with padding bits"
     assert tally(out, "selop-sharded-halves") > 0, "no operator or tagged call went through ksched_eval_begin / _end over row shards"
+    assert tally(out, "selterms") > 0, "no terms call ran"
+    assert tally(out, "selterms-late-full") > 0, "no terms call had a pod whose row is completed by a term behind term 0"
+    assert tally(out, "selterms-sharded-halves") > 0, "no terms call went through ksched_eval_begin / _end over row shards"
 
 
 def test_fuzz_parity_short(built):
@@ -80,3 +89,4 @@ def test_fuzz_parity_short_with_the_multi_device_sequence(built):
     assert re.search(r"'pack-gathered-over-\d': [1-9]", r.stdout), "no pack pick went through the multi-device sequence"
     assert tally(r.stdout, "combine-on-replicas") > 0, "no combining chain ran on the replicas after a sharded apply"
     assert tally(r.stdout, "selop-on-replicas") > 0, "no operator and tagged call ran on the replicas after a sharded apply"
+    assert tally(r.stdout, "selterms-on-replicas") > 0, "no terms call ran on the replicas after a sharded apply"

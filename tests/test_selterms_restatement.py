@@ -34,6 +34,17 @@ def test_two_terms_that_each_pass_a_different_node():
     assert [int(r[0]) for r in one[0]] == [0b0010, 0b0100] and [int(r[0]) for r in one[1]] == [0b1000, 0b0010]
 
 
+def test_the_mask_and_the_single_terms_in_one_pass_are_the_two_functions():
+    sel = np.array([[[E(EQ, 2), E(EQ, 1)], [0, E(EQ, 6)]],
+                    [[E(AB, 0), E(EQ, 2)], [0, 0]],
+                    [[0, 0], [NEVER, E(LT, 6)]]], dtype=np.uint32)  # pod 0: padding; pod 1: disk < 6 -> nodes 0 and 1
+    both, one = selterms_ref.selterms_and_term_masks(LAB, sel)
+    assert [int(r[0]) for r in both] == rows(sel) == [0b1010, 0b0111]
+    assert [[int(r[0]) for r in m] for m in one] == [[int(r[0]) for r in m] for m in selterms_ref.term_masks(LAB, sel)] == [[0b0010, 0b0100], [0b1000, 0b0010], [0, 0b0011]]
+    both2, one2 = selterms_ref.selterms_and_term_masks(LAB, sel.reshape(6, 2))  # the flat layout
+    assert np.array_equal(both2, both) and all(np.array_equal(a, b) for a, b in zip(one2, one))
+
+
 def test_an_all_zero_term_passes_everywhere_wherever_it_stands():
     assert rows([[[0], [0]], [[E(EQ, 2)], [0]], [[NEVER], [0]]]) == [0b1111]
     assert rows([[[E(EQ, 2)], [0]], [[0], [NEVER]], [[0], [0]]]) == [0b1111]

@@ -28,6 +28,11 @@ tests/selop_ref.py / tests/seltag_ref.py on the labels as the step's updates lef
 pick restatements on the resulting mask and the step's columns; both also through ksched_eval_begin / _end over 1 to 5 row shards with the uniform
 pick (sel_stride > p); where the whole batch gives a block of the operator kernel two pod tiles to walk, one more operator call over all its
 pods, compared on 1024 rows or fewer; with the hooks both calls on every replica after the pack pick's sharded apply,
+one terms call (KSCHED_SEL_TERMS: SEL | SELOP_TAGGED | sel_terms(T), T of 1, 2, 3, 15) at every step with keys, on a table [T][n_keys][p] of its
+own built like the tagged call's -- per-pod term counts with SEL_NEVER padding behind them, in a share of the pods a zero term behind a real
+one -- over the batch's first pods (200 at most, about 600 / T): the bare mask and the call as one more link on the step's chain under a drawn
+op (KSCHED_COMBINE_SOFT at random) with a drawn pick, against tests/selterms_ref.py on the labels as the step's updates left them; through
+ksched_eval_begin / _end over 1 to 5 row shards, column (t, k) at (t * n_keys + k) * sel_stride; with the hooks on every replica likewise,
 on-device applies of the previous evaluation's bindings between evaluations (ksched_apply_bindings_device; with the hooks on, now and then
 ksched_apply_bindings_sharded_local over 2 .. 4 replicas with ragged cuts; about one apply in four with KSCHED_APPLY_WHILE_FIT, against
 tests/admit_ref.py -- the sharded entry point must then refuse with KSCHED_E_UNSUPPORTED and leave every replica as it was; tallies
@@ -39,7 +44,7 @@ A case's decisions come from three generators seeded from the case seed: `r` dra
 case that keeps its node count is the case an older log names by that seed), `r2` every decision added with the uniform pick (the uniform legs,
 the wider snapshots, the label updates), in its order, and `r3` every decision added since (the spread legs): a seed names the case it named
 before the spread legs, with those legs added; `r4` every decision of the pack legs and the combining chains, likewise; `r5` every decision of
-the operator and the tagged calls, likewise.
+the operator and the tagged calls, likewise; `r6` every decision of the terms call, likewise.
 The summary's tallies: pick launches by name ('uniform': evaluations whose last_pick was "uniform"; 'uniform-ranked': those in which some
 pod had two or more feasible nodes, so the rank arithmetic ran), 'labels' (label updates), 'apply', 'host-masks', 'sharded-halves',
 'gathered-over-n' (and their 'uniform-' and 'spread-' twins), 'summarize'; 'spread': evaluations whose last_pick was "spread" (one per
@@ -52,7 +57,10 @@ soft link narrowed a row, was dropped for one, met an empty one; 'combine-on-rep
 'selop', 'seltag': operator and tagged calls run on `ev` through ksched_eval_device; 'seltag-negated-padding': tagged calls with a pod constrained
 through NE / ABSENT entries only on a node count that is no multiple of 64 (valid-bits applied before the negation would set padding bits);
 'selop-two-pass': operator calls on more than eight keys; 'selop-two-tiles': operator calls over a whole batch whose blocks walk two pod tiles or
-more; 'selop-sharded-halves': operator and tagged calls through the two halves; 'selop-on-replicas': cases whose two calls ran on every replica.
+more; 'selop-sharded-halves': operator and tagged calls through the two halves; 'selop-on-replicas': cases whose two calls ran on every replica;
+'selterms': terms calls run on `ev` through ksched_eval_device; 'selterms-wide': those on more than eight keys (k_eval_selterms_wide);
+'selterms-late-full': those with a pod whose row is full although term 0's row is not (a term behind term 0 completes it);
+'selterms-sharded-halves': terms calls through the two halves; 'selterms-on-replicas': cases whose terms call ran on every replica.
 usage: python tools/fuzz_parity.py [seconds] [seed]       prints one line per failure and a summary; exit code 1 on any failure"""
 import os, sys, time
 import numpy as np
@@ -69,6 +77,7 @@ from tests.spread_ref import best_of, spread_candidates_listed  # KSCHED_PICK_SP
 from tests.pack_ref import tightest_of  # KSCHED_PICK_PACK restated: the tightest of the same candidates
 from tests import combine_ref, soft_ref  # KSCHED_COMBINE_AND / _OR / _ANDNOT and KSCHED_COMBINE_SOFT restated
 from tests import selop_ref, seltag_ref  # KSCHED_SELOP_EXISTS / _GT / _LT and KSCHED_SELOP_TAGGED restated
+from tests import selterms_ref  # KSCHED_SEL_TERMS restated
 from tests.knife_edges import sampled as sampled_from_bits  # ksched_pick's rule for PICK_SAMPLED on a [p, n] table of bits
 from tests.test_gpu_combine_soft import old_mask_for  # an old mask whose neighbouring rows narrow, are dropped, are empty and are random
 
@@ -290,65 +299,74 @@ def selcall_masks(spec, lab, sel, N, P, K):
             in_pod_blocks(lambda e: seltag_ref.seltag_mask(lab, e), spec["tsel"][:, :p], N))
 
 
-def run_selcalls(e, cs, where, spec, masks, chain_final, cpu, mem, N, P, K, rc, rm, sel, smp, smp_u, smp_s, tally=True):
-    """the step's operator call and tagged call on evaluator `e` (whose labels should be the ones `masks` was computed on, whose columns
-    cpu / mem): each a ksched_eval_device into a [p, W] view with sentinel words around it -- plain, or as one more link on the final
-    mask of the step's combining chain (the first p rows of `chain_final`) -- with the call's pick.  Expected: `masks` (selcall_masks), combined by
-    tests/combine_ref.py / tests/soft_ref.py, and the pick restated on the resulting mask.  -> the number of failures"""
+def run_one_selcall(e, cs, where, name, kernel, flags, entries, new, c, p, chain_final, cpu, mem, N, K, rc, rm, smp, smp_u, smp_s):
+    """one selector call (operator, tagged or terms) on evaluator `e`: a ksched_eval_device of the first p pods of `entries` ([...][pods]) into
+    a [p, W] view with sentinel words around it -- plain, or as one more link on the final mask of the step's combining chain (the first p
+    rows of `chain_final`) -- with the call's pick (`c`: pitch, offset, link, comb, soft, pick).  Expected: `new`, the call's bare mask from
+    its restatement, combined by tests/combine_ref.py / tests/soft_ref.py, and the pick restated on the resulting mask; last_kernel must be
+    `kernel`.  -> the number of failures"""
     import torch
     dev = torch.device("cuda:0")
-    p, want_op, want_tag = masks
     W = (N + 63) // 64
     td = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
     rc_t, rm_t = td(rc[:p], np.int64), td(rm[:p], np.int64)
+    bad = 0
+    pitch, offset, pick = c["pitch"], c["offset"], c["pick"]
+    link = c["link"] and chain_final is not None and chain_final.shape[0] >= p
+    old = np.ascontiguousarray(chain_final[:p]) if link else None
+    if pick == L.PICK_BESTFIT and any(a.size and (int(a.min()) < -(1 << 61) or int(a.max()) > (1 << 61)) for a in (cpu, mem)):
+        pick = L.PICK_PACK  # (as in run_chain)
+    comb = (c["comb"] | c["soft"]) if link else 0
+    if link:
+        want = soft_ref.soft_combine(old, new, c["comb"], N) if c["soft"] else combine_ref.combine(old, new, c["comb"], N)
+    else:
+        want = new
+    draws = {L.PICK_SAMPLED: smp, L.PICK_UNIFORM: smp_u, L.PICK_SPREAD: smp_s, L.PICK_PACK: smp_s}.get(pick)
+    draws = None if draws is None else np.ascontiguousarray(draws[:p])
+    want_b = pick_on_mask(pick, want, draws, N, cpu, mem)
+    rows = p + GUARD_ROWS
+    host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
+    if link:
+        host[offset:offset + rows * pitch].reshape(rows, pitch)[:p, :W] = old
+    buf = torch.from_numpy(host.view(np.int64)).to(dev)
+    view = buf[offset:offset + rows * pitch].view(rows, pitch)[:p, :W]
+    out = torch.full((p + 4,), -7, dtype=torch.int32, device=dev)
+    e.eval_device(rc_t, rm_t, td(entries[..., :p], np.int32) if K else None, None, td(draws, np.int32) if pick else None, flags | comb | pick,
+                  out_feasible=view, out_binding=out[:p] if pick else None)
+    ran = e.last_kernel
+    torch.cuda.synchronize()
+    what = (f"case seed {cs} {where}: N={N} p={p} K={K} flags={flags | comb | pick:#x} pitch={pitch} offset={offset}" +
+            (" on the step's chain" if link else ""))
+    got = buf.cpu().numpy().view(np.uint64)
+    body = got[offset:offset + rows * pitch].reshape(rows, pitch)
+    pad = body[:p, W:]
+    if ran != kernel:
+        bad += 1
+        print(f"FAIL {name} call {what}: ran as {ran!r}", flush=True)
+    if not np.array_equal(body[:p, :W], want):
+        bad += 1
+        print(f"FAIL {name} call {what}: the mask ({int((body[:p, :W] != want).any(axis=1).sum())} rows differ)", flush=True)
+    elif not (((pad == SENTINEL) | (pad == 0)).all() and (body[p:] == SENTINEL).all() and (got[:offset] == SENTINEL).all() and got[-1] == SENTINEL):
+        bad += 1
+        print(f"FAIL {name} call {what}: wrote outside words [0, W) of the view's rows", flush=True)
+    if pick:
+        b = out.cpu().numpy()
+        if not (np.array_equal(b[:p], want_b) and (b[p:] == -7).all()):
+            bad += 1
+            print(f"FAIL {name} call {what}: the pick ({int((b[:p] != want_b).sum())} bindings differ)", flush=True)
+    return bad
+
+
+def run_selcalls(e, cs, where, spec, masks, chain_final, cpu, mem, N, P, K, rc, rm, sel, smp, smp_u, smp_s, tally=True):
+    """the step's operator call and tagged call on evaluator `e` (whose labels should be the ones `masks` was computed on, whose columns
+    cpu / mem): each through run_one_selcall, against `masks` (selcall_masks).  -> the number of failures"""
+    p, want_op, want_tag = masks
     bad = 0
     for name, kernel, flags, entries, new, c in (("operator", "selop", L.SEL | spec["op"], sel, want_op, spec["calls"][0]),
                                                  ("tagged", "seltag", L.SEL | L.SELOP_TAGGED, spec["tsel"], want_tag, spec["calls"][1])):
         if new is None:
             continue
-        pitch, offset, pick = c["pitch"], c["offset"], c["pick"]
-        link = c["link"] and chain_final is not None and chain_final.shape[0] >= p
-        old = np.ascontiguousarray(chain_final[:p]) if link else None
-        if pick == L.PICK_BESTFIT and any(a.size and (int(a.min()) < -(1 << 61) or int(a.max()) > (1 << 61)) for a in (cpu, mem)):
-            pick = L.PICK_PACK  # (as in run_chain)
-        comb = (c["comb"] | c["soft"]) if link else 0
-        if link:
-            want = soft_ref.soft_combine(old, new, c["comb"], N) if c["soft"] else combine_ref.combine(old, new, c["comb"], N)
-        else:
-            want = new
-        draws = {L.PICK_SAMPLED: smp, L.PICK_UNIFORM: smp_u, L.PICK_SPREAD: smp_s, L.PICK_PACK: smp_s}.get(pick)
-        draws = None if draws is None else np.ascontiguousarray(draws[:p])
-        want_b = pick_on_mask(pick, want, draws, N, cpu, mem)
-        rows = p + GUARD_ROWS
-        host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
-        if link:
-            host[offset:offset + rows * pitch].reshape(rows, pitch)[:p, :W] = old
-        buf = torch.from_numpy(host.view(np.int64)).to(dev)
-        view = buf[offset:offset + rows * pitch].view(rows, pitch)[:p, :W]
-        out = torch.full((p + 4,), -7, dtype=torch.int32, device=dev)
-        e.eval_device(rc_t, rm_t, td(entries[:, :p], np.int32) if K else None, None, td(draws, np.int32) if pick else None, flags | comb | pick,
-                      out_feasible=view, out_binding=out[:p] if pick else None)
-        ran = e.last_kernel
-        torch.cuda.synchronize()
-        what = (f"case seed {cs} {where}: N={N} p={p} K={K} flags={flags | comb | pick:#x} pitch={pitch} offset={offset}" +
-                (" on the step's chain" if link else ""))
-        got = buf.cpu().numpy().view(np.uint64)
-        body = got[offset:offset + rows * pitch].reshape(rows, pitch)
-        pad = body[:p, W:]
-        if ran != kernel:
-            bad += 1
-            print(f"FAIL {name} call {what}: ran as {ran!r}", flush=True)
-        if not np.array_equal(body[:p, :W], want):
-            bad += 1
-            print(f"FAIL {name} call {what}: the mask ({int((body[:p, :W] != want).any(axis=1).sum())} rows differ)", flush=True)
-        elif not (((pad == SENTINEL) | (pad == 0)).all() and (body[p:] == SENTINEL).all() and (got[:offset] == SENTINEL).all() and got[-1] == SENTINEL):
-            bad += 1
-            print(f"FAIL {name} call {what}: wrote outside words [0, W) of the view's rows", flush=True)
-        if pick:
-            b = out.cpu().numpy()
-            if not (np.array_equal(b[:p], want_b) and (b[p:] == -7).all()):
-                bad += 1
-                print(f"FAIL {name} call {what}: the pick ({int((b[:p] != want_b).sum())} bindings differ)", flush=True)
+        bad += run_one_selcall(e, cs, where, name, kernel, flags, entries, new, c, p, chain_final, cpu, mem, N, K, rc, rm, smp, smp_u, smp_s)
         if not tally:
             continue
         picks[kernel] = picks.get(kernel, 0) + 1
@@ -362,6 +380,80 @@ def run_selcalls(e, cs, where, spec, masks, chain_final, cpu, mem, N, P, K, rc, 
             if ((ent != 0).any(axis=0) & (neg == (ent != 0)).all(axis=0)).any():
                 picks["seltag-negated-padding"] = picks.get("seltag-negated-padding", 0) + 1
     return bad
+
+
+def draw_selterms(g, lab, N, P, K):
+    """the step's terms call (KSCHED_SEL_TERMS; generator r6), None without keys: the term count T of {1, 2, 3, 15}; the pods (the batch's
+    first ones, at most SELCALL_PODS and, for the restatement's time, about 600 / T, never fewer than 65 where the batch has them: a second
+    pod tile); the entries [T][K][p], built as draw_selcalls builds its tagged table -- constrained with a probability drawn per step, all six
+    tags, now and then tag 6 or 7, ids from beside the nodes' ids or 0, 1, 0x1FFFFFFF --; a term count c of 1 .. T per pod, every term at or
+    behind it the documented padding (all zeros, SEL_NEVER in one drawn key); in about a seventh of the pods with c >= 2 term 1 all zeros, a
+    zero term behind a real one; the decisions of the bare call and of the combining call (draw_selcalls' call()); the shard count of the
+    two halves"""
+    if not K:
+        return None
+    W = (N + 63) // 64
+    T = int(g.choice([1, 2, 3, selterms_ref.MAX_TERMS]))
+    p = min(P, SELCALL_PODS, max(65, 600 // T))
+    pk = float(g.choice([0.05, 0.3, 0.9]))
+    near = lab[np.arange(K)[None, :, None], g.integers(0, N, (T, K, p))].astype(np.int64) + g.integers(-1, 2, (T, K, p))
+    ident = np.where(g.random((T, K, p)) < 0.8, near, g.choice(np.array([0, 1, seltag_ref.ID_MASK]), (T, K, p))) & seltag_ref.ID_MASK
+    tags = np.where(g.random((T, K, p)) < 0.03, g.integers(6, 8, (T, K, p)), g.integers(0, 6, (T, K, p)))
+    ent = np.where(g.random((T, K, p)) < pk, seltag_ref.entry(tags, ident), 0).astype(np.uint32)
+    c = g.integers(1, T + 1, p)
+    pad_key = g.integers(0, K, (T, p))
+    for r in range(1, T):
+        pods = np.nonzero(c <= r)[0]
+        ent[r][:, pods] = 0
+        ent[r][pad_key[r][pods], pods] = L.SEL_NEVER
+    if T >= 2:
+        ent[1][:, (g.random(p) < 0.15) & (c >= 2)] = 0
+
+    def call(link):
+        op = int(g.choice(combine_ref.OPS))
+        return dict(pitch=int(g.choice([W, W + 1, int(ev._lib.ksched_mask_pitch(N))])), offset=int(g.integers(0, 2)), link=link, comb=op,
+                    soft=soft_ref.SOFT if op != combine_ref.OR and g.random() < 0.5 else 0,
+                    pick=int(g.choice([0, L.PICK_SAMPLED, L.PICK_BESTFIT, L.PICK_UNIFORM, L.PICK_SPREAD, L.PICK_PACK])) if link else 0)
+    return dict(T=T, p=p, ent=np.ascontiguousarray(ent), calls=(call(False), call(True)), shards=int(g.choice([1, 2, 3, 5])))
+
+
+def selterms_masks(spec, lab, N):
+    """the expected bare mask of the step's terms call on the labels `lab`, from tests/selterms_ref.py, and whether a pod's row is full
+    although term 0's row is not (a term behind term 0 completes it): -> (mask [p, W], late_full)"""
+    want = in_pod_blocks(lambda e: selterms_ref.selterms_mask(lab, e), spec["ent"], N)
+    first = in_pod_blocks(lambda e: seltag_ref.seltag_mask(lab, e), spec["ent"][0], N)
+    return want, bool(((row_popcounts(want) == N) & (row_popcounts(first) < N)).any())
+
+
+def run_selterms(e, cs, where, spec, masks, chain_final, cpu, mem, N, P, K, rc, rm, smp, smp_u, smp_s, tally=True):
+    """the step's terms call on evaluator `e`, twice through ksched_eval_device (run_one_selcall's views, sentinels and comparisons): the bare
+    mask, and as one more link on the final mask of the step's combining chain under the drawn op (KSCHED_COMBINE_SOFT at random) with the
+    drawn pick in it.  -> the number of failures"""
+    want, late = masks
+    flags = L.SEL | L.SELOP_TAGGED | L.sel_terms(spec["T"])
+    calls = [spec["calls"][0]]
+    if chain_final is not None and chain_final.shape[0] >= spec["p"]:
+        calls.append(spec["calls"][1])
+    bad = 0
+    for c in calls:
+        bad += run_one_selcall(e, cs, where, "terms", "selterms", flags, spec["ent"], want, c, spec["p"], chain_final, cpu, mem, N, K, rc, rm, smp, smp_u, smp_s)
+    if tally:
+        picks["selterms"] = picks.get("selterms", 0) + len(calls)
+        if K > 8:
+            picks["selterms-wide"] = picks.get("selterms-wide", 0) + len(calls)
+        if late:
+            picks["selterms-late-full"] = picks.get("selterms-late-full", 0) + len(calls)
+    return bad
+
+
+def selterms_halves(cs, spec, masks, N, K, rc, rm, smp_u, att_u):
+    """the terms call through ksched_eval_begin / _end over spec's 1 to 5 row shards of its p pods: the entries as [T * K][p], a shard's
+    pointer at its first pod and sel_stride = p, so column (t, k) starts at (t * K + k) * sel_stride; with the uniform pick so that the
+    second half has bindings to hand back.  -> the number of failures"""
+    p, T = spec["p"], spec["T"]
+    draws = np.ascontiguousarray(smp_u[:p])
+    return shard_halves(None, cs, "selterms-", N, p, K, 0, L.SEL, L.SEL | L.SELOP_TAGGED | L.sel_terms(T) | L.PICK_UNIFORM, rc[:p], rm[:p],
+                        spec["ent"].reshape(T * K, p), None, draws, att_u, (masks[0], None, uniform_pick_blocks(masks[0], draws[:, 0], N)), n_sh=spec["shards"])
 
 
 def run_selop_whole(e, cs, where, spec, lab, sel, N, P, K, rc, rm):
@@ -630,14 +722,15 @@ def gathered_sequence(g, cs, tag, cpu, mem, lab, taints, N, P, K, nt, preds, fla
 
 
 def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc, rm, sel, tol, smp, d, want, ranked, tied,
-                    name="spread", restate=None, chain=None, after=None):
+                    name="spread", restate=None, chain=None, after=None, after_terms=False):
     """the multi-device sequence with the spread pick, twice: on freshly set replicas; then -- after ksched_apply_bindings_sharded_local of
     the gathered bindings over the same replicas, ragged cuts, no ksched_set_nodes -- on the columns that apply left on every replica: the
     oracle's mask and the restatement on the exact-integer apply of those bindings.  A replica whose columns the gathered commit left behind
     ranks its rows by old values.  Every replica's pick must run as "spread".  `ev`, cpu and mem are not touched.  -> the number of failures.
     name="pack", restate=pack_restated: the same for the pack pick (flags carry PICK_PACK).  chain=(spec, smp, smp_u, smp_s): after the
     sharded apply and the second sequence that combining chain runs on every replica, against the columns the apply left; behind it
-    after(e, where, ncpu, nmem) -> failures: the step's operator and tagged calls on that replica, on the same columns."""
+    after(e, where, ncpu, nmem) -> failures: the step's operator and tagged calls on that replica, on the same columns (after_terms: the
+    step's terms call is among them, tallied as 'selterms-on-replicas')."""
     import torch
     restate = restate or spread_restated
     tag, pick_flag = name + "-", {"spread": L.PICK_SPREAD, "pack": L.PICK_PACK}[name]
@@ -681,6 +774,8 @@ def spread_gathered(g, cs, cpu, mem, lab, taints, N, P, K, nt, preds, flags, rc,
         picks["combine-on-replicas"] = picks.get("combine-on-replicas", 0) + 1
         if after is not None:
             picks["selop-on-replicas"] = picks.get("selop-on-replicas", 0) + 1
+            if after_terms:
+                picks["selterms-on-replicas"] = picks.get("selterms-on-replicas", 0) + 1
     return bad + bad2
 
 
@@ -696,6 +791,7 @@ while time.time() < t_end:
     r3 = np.random.default_rng([cs, 0x5E4])  # every decision added after the sequence of `r2` was fixed: the spread legs
     r4 = np.random.default_rng([cs, 0xC0B])  # every decision added after the sequence of `r3` was fixed: the pack legs and the combining chains
     r5 = np.random.default_rng([cs, 0xE95])  # every decision added after the sequence of `r4` was fixed: the operator and the tagged selector calls
+    r6 = np.random.default_rng([cs, 0xE10])  # every decision added after the sequence of `r5` was fixed: the terms call
     wide = int(r2.choice([8192, 8193, 12_500])) if r2.random() < 0.1 else 0  # rows of more than 128 words: k_pick_uniform's two-pass form (8192: the longest one-pass row)
     N = int(r.choice([1, 2, 63, 64, 65, 300, 1023, 1024, 1025, 2500, 4097, 6000]))
     P = int(r.choice([1, 7, 64, 65, 500, 1500, 3000]))
@@ -885,6 +981,13 @@ while time.time() < t_end:
                 fails += selcall_halves(cs, selc, selm, N, K, rc, rm, sel, smp_u, att_u)
             if selc["whole"] is not None:
                 fails += run_selop_whole(ev, cs, f"step {step}", selc, lab, sel, N, P, K, rc, rm)
+            # the terms call on the same snapshot and labels (draw_selterms, run_selterms): bare, under a drawn combine with a drawn pick, and
+            # through the two halves over row shards
+            selt = draw_selterms(r6, lab, N, P, K)
+            if selt is not None:
+                seltm = selterms_masks(selt, lab, N)
+                fails += run_selterms(ev, cs, f"step {step}", selt, seltm, chain["final"], cpu, mem, N, P, K, rc, rm, smp, smp_u, smp_s)
+                fails += selterms_halves(cs, selt, seltm, N, K, rc, rm, smp_u, att_u)
         ev.set_kernel("auto")
         want3_u = (want[0], want[1], want_u)
         want3_s = (want[0], want[1], want_s)
@@ -903,7 +1006,9 @@ while time.time() < t_end:
             fails += spread_gathered(r4, cs, cpu, mem, lab, taints, N, P, K, nt, preds, fl_k, rc, rm, sel, tol, smp_k, d_k, (want[0], want[1], want_k), ranked_k, False,
                                      name="pack", restate=pack_restated, chain=(chain, smp, smp_u, smp_s),
                                      after=lambda e, where, ncpu, nmem: run_selcalls(e, cs, where, selc, selm, chain["final"], ncpu, nmem, N, P, K, rc, rm, sel,
-                                                                                     smp, smp_u, smp_s, tally=False))
+                                                                                     smp, smp_u, smp_s, tally=False) +
+                                     (run_selterms(e, cs, where, selt, seltm, chain["final"], ncpu, nmem, N, P, K, rc, rm, smp, smp_u, smp_s, tally=False)
+                                      if selt is not None else 0), after_terms=selt is not None)
         if r2.random() < 0.4:  # ksched_pick with the uniform pick: the oracle's mask, and that mask thinned by random words -- the restatement on either
             thin_u = want[0] & r2.integers(0, 1 << 63, want[0].shape, dtype=np.uint64)
             if not (np.array_equal(ev.pick(want[0], L.PICK_UNIFORM, samples=smp_u), want_u) and
