@@ -5,10 +5,7 @@
 //     valid bits AND ( OR over t of ( AND over k of seltag_pass(e[t][k][pod], v[k][node]) ) ),
 // an entry read as sel_tags.hpp reads it (tag << 29 | id, tags 6 and 7 pass nowhere, entry 0 passes), bits at or beyond n zero.
 //
-// Mapping: k_eval_seltag's (kernels_seltag.hpp), geometry included.  One wave owns kSelopCW consecutive 64-node word columns whose label
-// ids live in VGPRs; it walks pods 64 at a time; a pod's entries are wave-uniform and come in through the scalar cache; the tag is decoded
-// on the scalar side into the one compare form  word = ballot(v - lo < len) ^ neg  (no branch on the tag); the word of pod j is parked in
-// lane j by v_writelane, and after 64 pods every lane stores kSelopCW consecutive words of its pod row with plain vector stores.
+// k_eval_seltag's mapping, geometry included; the walk, the decode of an entry (sel_and_entry) and the launch are kernels_sel_walk.hpp's.
 //
 // What the OR changes.  Per pod the T term words are formed and ORed in scalar registers, THEN parked once and stored once: the walk's
 // fixed cost -- the writelanes, the row stores, the tile loop -- is paid once, not T times, and there is no combine pass over the mask.
@@ -36,36 +33,10 @@
 
 #include "../../include/ksched.h"
 #include "kernarg.hpp"
-#include "kernels_direct.hpp"  // ksched_writelane_u32
+#include "kernels_sel_walk.hpp"
 #include "sel_terms.hpp"
 
 namespace ksched {
-
-struct SeltermsArgs {
-    uint32_t n, p, W;
-    uint32_t pitch;                // words between consecutive pod rows of the mask (>= W)
-    uint32_t nkeys;                // all of the snapshot's keys (0: no key at all); k_eval_selterms: <= kSelopKeys
-    uint32_t terms;                // T >= 1
-    uint32_t pod_tiles_per_block;  // 64-pod tiles walked by one block
-    uint32_t key_passes;           // k_eval_selterms_wide: ceil(nkeys / kSelopKeys)
-};
-
-// m[c] &= [entry e against the label ids v[c]] for a constrained entry (e != 0): kernels_seltag.hpp's decode, seltag_form_bits' arithmetic
-// (sel_tags.hpp) on the scalar side, then a v_sub and one v_cmp per column.  The two v_readfirstlane keep the chain of words on the scalar
-// unit (kernels_seltag.hpp says what happens without them).
-__device__ __forceinline__ void selterms_and_entry(uint32_t e, const uint32_t (&v)[kSelopCW], uint64_t (&m)[kSelopCW]) {
-    const uint32_t tag = e >> KSCHED_SELTAG_SHIFT, id = e & KSCHED_SELTAG_ID_MASK;
-    const uint32_t t0 = tag & 1u, t1 = (tag >> 1) & 1u, t2 = tag >> 2;
-    const uint32_t neg32 = __builtin_amdgcn_readfirstlane(0u - (t0 & (t2 ^ 1u)));  // NE, ABSENT: all ones
-    const uint64_t neg = ((uint64_t)neg32 << 32) | neg32;
-    const uint32_t by_id = 0u - ((t1 ^ 1u) & ((t0 & t2) ^ 1u));  // EQ, NE, GT: the range starts at the id
-    const uint32_t lo = (id & by_id) + (t1 | t2);                // ... (+ 1 for GT); EXISTS, ABSENT, LT: at 1
-    const uint32_t len45 = ((id - (id != 0u ? 1u : 0u)) & (0u - t0)) | (~id & (t0 - 1u));  // LT: [1, id); GT: (id, 2^32)
-    const uint32_t len03 = 1u | (0u - t1);                                                 // EQ, NE: the id alone; EXISTS, ABSENT: [1, 2^32)
-    const uint32_t len = __builtin_amdgcn_readfirstlane(((len45 & (0u - t2)) | (len03 & (t2 - 1u))) & (0u - ((t1 & t2) ^ 1u)));  // tags 6, 7: empty
-#pragma unroll
-    for (uint32_t c = 0; c < kSelopCW; ++c) m[c] &= __ballot(v[c] - lo < len) ^ neg;  // (m starts as the valid-bits word: applied after the xor)
-}
 
 // One term's entries of one pod, keys [0, nk) of the columns that start at `col`, `p` entries apart; e[k] = 0 for k >= nk.  ALL loads are
 // issued before the first is used: a load per key under its own `k < nk` test is what the compiler turns into eight dependent
@@ -128,7 +99,7 @@ __global__ __launch_bounds__(64 * kSelopWaves) void k_eval_selterms(const uint32
                 selterms_load_entries(g_psel + (size_t)t * a.nkeys * a.p + pod, a.p, a.nkeys, e);
 #pragma unroll
                 for (uint32_t k = 0; k < kSelopKeys; ++k)
-                    if (e[k] != 0u) selterms_and_entry(e[k], nlab[k], m);  // wave-uniform branch: unconstrained keys cost no VALU work
+                    if (e[k] != 0u) sel_and_entry(e[k], nlab[k], m);  // wave-uniform branch: unconstrained keys cost no VALU work
                 uint64_t missing = 0;
 #pragma unroll
                 for (uint32_t c = 0; c < kSelopCW; ++c) {
@@ -137,19 +108,9 @@ __global__ __launch_bounds__(64 * kSelopWaves) void k_eval_selterms(const uint32
                 }
                 if (missing == 0) break;  // wave-uniform: every valid bit is set, no further term can add one
             }
-#pragma unroll
-            for (uint32_t c = 0; c < kSelopCW; ++c) {
-                flo[c] = ksched_writelane_u32((uint32_t)acc[c], j, flo[c]);
-                fhi[c] = ksched_writelane_u32((uint32_t)(acc[c] >> 32), j, fhi[c]);
-            }
+            sel_park(acc, j, flo, fhi);
         }
-
-        if (lane < jmax) {
-            const size_t row = (size_t)(p0 + lane) * a.pitch;
-#pragma unroll
-            for (uint32_t c = 0; c < kSelopCW; ++c)
-                if (w0 + c < a.W) out_feas[row + w0 + c] = ((uint64_t)fhi[c] << 32) | flo[c];
-        }
+        sel_store_rows(out_feas, a.pitch, a.W, w0, p0, lane, jmax, flo, fhi, 0u);
     }
 }
 
@@ -212,13 +173,9 @@ __global__ __launch_bounds__(64 * kSelopWaves) void k_eval_selterms_wide(const u
 #pragma unroll
                     for (uint32_t k = 0; k < kSelopKeys; ++k) {
                         const uint32_t e = (k < nk) ? col[(size_t)k * a.p] : 0u;
-                        if (e != 0u) selterms_and_entry(e, nlab[k], m);
+                        if (e != 0u) sel_and_entry(e, nlab[k], m);
                     }
-#pragma unroll
-                    for (uint32_t c = 0; c < kSelopCW; ++c) {
-                        plo[c] = ksched_writelane_u32((uint32_t)m[c], j, plo[c]);
-                        phi[c] = ksched_writelane_u32((uint32_t)(m[c] >> 32), j, phi[c]);
-                    }
+                    sel_park(m, j, plo, phi);
                 }
 #pragma unroll
                 for (uint32_t c = 0; c < kSelopCW; ++c) tlo[c] &= plo[c], thi[c] &= phi[c];
@@ -226,37 +183,13 @@ __global__ __launch_bounds__(64 * kSelopWaves) void k_eval_selterms_wide(const u
 #pragma unroll
             for (uint32_t c = 0; c < kSelopCW; ++c) flo[c] |= tlo[c], fhi[c] |= thi[c];
         }
-
-        if (lane < jmax) {
-            const size_t row = (size_t)(p0 + lane) * a.pitch;
-#pragma unroll
-            for (uint32_t c = 0; c < kSelopCW; ++c)
-                if (w0 + c < a.W) out_feas[row + w0 + c] = ((uint64_t)fhi[c] << 32) | flo[c];
-        }
+        sel_store_rows(out_feas, a.pitch, a.W, w0, p0, lane, jmax, flo, fhi, 0u);
     }
 }
 
-// The mask of a tagged call with `terms` >= 1 terms over [p] rows of W = ceil(n / 64) words, `pitch` words apart, enqueued on `s`: nlab =
-// the snapshot's label columns [nkeys][n], psel = the batch's tagged entries [terms][nkeys][p] (nullptr, or nkeys == 0: no pod constrains
-// anything -- the all-valid rows).  ONE launch; the geometry is sel_terms.hpp's; the one launch path (ksched_api.hip's launch_mask).
-inline hipError_t run_selterms(const uint32_t *nlab, const uint32_t *psel, uint64_t *out_feas, uint32_t p, uint32_t n, uint32_t W, uint32_t pitch, uint32_t nkeys,
-                               uint32_t terms, hipStream_t s) {
-    if (p == 0 || W == 0) return hipSuccess;
-    if (!out_feas || pitch < W || terms == 0 || terms > KSCHED_MAX_TERMS) return hipErrorInvalidValue;
-    if (!psel || !nlab) nkeys = 0;
-    const SeltermsLaunch l = plan_selterms_launch(p, W, nkeys, terms);
-    SeltermsArgs a{};
-    a.n = n;
-    a.p = p;
-    a.W = W;
-    a.pitch = pitch;
-    a.nkeys = nkeys;
-    a.terms = l.terms;
-    a.pod_tiles_per_block = l.pod_tiles_per_block;
-    a.key_passes = l.key_passes;
+inline void launch_selterms(const uint32_t *nlab, const uint32_t *psel, uint64_t *out_feas, const SeltermsLaunch &l, const SeltermsArgs &a, hipStream_t s) {
     if (l.wide) hipLaunchKernelGGL(k_eval_selterms_wide, dim3(l.gx, l.gy), dim3(l.block), 0, s, nlab, psel, out_feas, a);
     else hipLaunchKernelGGL(k_eval_selterms, dim3(l.gx, l.gy), dim3(l.block), 0, s, nlab, psel, out_feas, a);
-    return hipGetLastError();
 }
 
 }  // namespace ksched

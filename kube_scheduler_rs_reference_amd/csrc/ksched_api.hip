@@ -34,6 +34,7 @@
 #include "kernels_pick_pack.hpp"    // (k_pick_spread's body with the comparison turned round)
 #include "kernels_combine.hpp"      // (extension E6: the scratch mask folded into the caller's mask)
 #include "kernels_combine_soft.hpp" // (extension E7: ... row by row, unless that would leave the row empty)
+#include "kernels_sel_walk.hpp"     // (what the three selector kernels share, and their one launch path)
 #include "kernels_selop.hpp"        // (extension E8: the mask of an operator call -- Exists, Gt, Lt)
 #include "kernels_seltag.hpp"       // (extension E9: the mask of a tagged call -- the operator per pod and key)
 #include "kernels_selterms.hpp"     // (extension E10: ... with a term count -- the OR of several tagged rows per pod)
@@ -1182,15 +1183,11 @@ int launch_mask(ksched_ctx *c, const EvalRequest &r, const EvalPlan &plan) {
         o.round_order = c->opt_round_order;
         hipError_t e = run_fused(c->idx, r, feas, o);
         if (e != hipSuccess) return fail_hip(c, e, "run_fused");
-    } else if (plan.mask == MaskKernel::kSelOp) {  // (extension E8: the selector term alone, under the plan's operator, from the label columns)
-        if (hipError_t e = run_selop(plan.selop, c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, s); e != hipSuccess)
-            return fail_hip(c, e, "run_selop");
-    } else if (plan.mask == MaskKernel::kSelTag) {  // (extension E9: the selector term alone, the operator read out of every entry, from the label columns)
-        if (hipError_t e = run_seltag(c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, s); e != hipSuccess)
-            return fail_hip(c, e, "run_seltag");
-    } else if (plan.mask == MaskKernel::kSelTerms) {  // (extension E10: the OR over the plan's term count of such terms, entries [terms][nkeys][p])
-        if (hipError_t e = run_selterms(c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, plan.terms, s); e != hipSuccess)
-            return fail_hip(c, e, "run_selterms");
+    } else if (plan.mask == MaskKernel::kSelOp || plan.mask == MaskKernel::kSelTag || plan.mask == MaskKernel::kSelTerms) {
+        // (extensions E8, E9, E10: the selector term alone, from the label columns -- under the plan's operator, the operator read out of every
+        // entry, or the OR over the plan's term count of such terms, entries [terms][nkeys][p])
+        if (hipError_t e = run_selector_mask(plan.mask, plan.selop, plan.terms, c->nlab.ptr, r.sel(c->nkeys) ? r.psel : nullptr, feas, r.p, c->n, c->W, r.pitch, c->nkeys, s); e != hipSuccess)
+            return fail_hip(c, e, plan.mask == MaskKernel::kSelOp ? "run_selop" : plan.mask == MaskKernel::kSelTag ? "run_seltag" : "run_selterms");
     } else if (int rc = run_direct(c, r, feas)) {
         return rc;
     }

@@ -11,7 +11,7 @@
 // Host-only on purpose, like mask_combine.hpp and mask_combine_soft.hpp: no HIP include, no ksched_ctx, so that plain g++ compiles it and
 // tests/cpp/selop_plan_tests.cpp pins every rule at its boundary without a GPU.  check_eval_args (ksched_api.hip) asks check_selop_args for
 // every evaluation entry point; plan_eval (eval_plan.hpp) carries the operator from EvalFacts to EvalPlan; launch_mask launches k_eval_selop
-// (kernels_selop.hpp) with what plan_selop_launch says and takes no decision of its own.
+// (kernels_selop.hpp) through run_selector_mask (kernels_sel_walk.hpp) with what plan_selop_launch says and takes no decision of its own.
 #pragma once
 
 #include <cstdint>

@@ -10,8 +10,8 @@
 //
 // Host-only on purpose, like sel_ops.hpp: no HIP include, no ksched_ctx, so that plain g++ compiles it and tests/cpp/seltag_plan_tests.cpp
 // pins every rule at its boundary without a GPU.  check_eval_args (ksched_api.hip) asks check_seltag_args for every evaluation entry point;
-// plan_eval (eval_plan.hpp) carries `seltag` from EvalFacts to EvalPlan; launch_mask launches k_eval_seltag (kernels_seltag.hpp) with what
-// plan_seltag_launch says and takes no decision of its own.
+// plan_eval (eval_plan.hpp) carries `seltag` from EvalFacts to EvalPlan; launch_mask launches k_eval_seltag (kernels_seltag.hpp) through
+// run_selector_mask (kernels_sel_walk.hpp) with what plan_seltag_launch says and takes no decision of its own.
 #pragma once
 
 #include <cstdint>
@@ -72,7 +72,7 @@ constexpr bool seltag_pass(uint32_t e, uint32_t v) {
 //     GT      [id + 1, 2^32)      LT      [1, id)       (id 0 and 1: the empty range)
 //     tags 6 and 7: the empty range (len == 0 passes no v; neg is false for them).
 // `neg` is applied before the valid-bits word: a padding lane holds id 0 and PASSES a negated range.  The kernel computes the same three
-// numbers from the tag's three bits in integer arithmetic (kernels_seltag.hpp); tests/cpp/seltag_plan_tests.cpp pins both against
+// numbers from the tag's three bits in integer arithmetic (kernels_sel_walk.hpp: sel_and_entry); tests/cpp/seltag_plan_tests.cpp pins both against
 // seltag_pass.
 struct SeltagForm {
     uint32_t lo = 0, len = 0;

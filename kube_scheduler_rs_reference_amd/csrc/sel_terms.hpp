@@ -10,7 +10,8 @@
 // Host-only on purpose, like sel_tags.hpp: no HIP include, no ksched_ctx, so that plain g++ compiles it and
 // tests/cpp/selterms_plan_tests.cpp pins every rule at its boundary without a GPU.  check_eval_args (ksched_api.hip) asks
 // check_selterms_args for every evaluation entry point; plan_eval (eval_plan.hpp) carries `terms` from EvalFacts to EvalPlan; launch_mask
-// launches k_eval_selterms / k_eval_selterms_wide (kernels_selterms.hpp) with what plan_selterms_launch says and takes no decision of its own.
+// launches k_eval_selterms / k_eval_selterms_wide (kernels_selterms.hpp) through run_selector_mask (kernels_sel_walk.hpp) with what
+// plan_selterms_launch says and takes no decision of its own.
 #pragma once
 
 #include <cstdint>

@@ -9,35 +9,26 @@ with tests/combine_ref.py / tests/soft_ref.py and ksched_pick_device on top of i
  5. the host forms ksched_eval and ksched_eval_begin / _end give the device form's bits;
  6. label updates within the planned maxima and past them, another key count, and two streams around a label update;
  7. the refusals at every entry point, outputs untouched, and the edge sizes p == 0, n == 0, no snapshot.
-Every output goes into sentinel-filled buffers.  Shapes are the smallest at which the kernel takes each path."""
+Every output goes into sentinel-filled buffers.  Shapes are the smallest at which the kernel takes each path.  What the three selector
+files share -- the guarded evaluation, the bodies that are the same for every call -- is tests/selector_calls.py's."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, PICK_BESTFIT, PICK_PACK, PICK_SAMPLED,
-                                             PICK_SPREAD, PICK_UNIFORM, SEL, SEL_NEVER, SELOP_EXISTS, SELOP_GT, SELOP_LT, TAINT, WANT_FIT_MASK,
-                                             Evaluator, KschedError, _lib, pack_mask, synth)
-from tests import combine_ref, selop_ref, soft_ref
+from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM,
+                                             SEL, SEL_NEVER, SELOP_EXISTS, SELOP_GT, SELOP_LT, TAINT, WANT_FIT_MASK, Evaluator, _lib, pack_mask, synth)
+from tests import combine_ref, selector_calls, selop_ref
 from tests.pick_helpers import dev_of, fresh, mask_np, pod_tensors, to_dev
-from tests.uniform_ref import uniform_pick
+from tests.selector_calls import (COMBINES, CORES_KEY, GPU_KEY, PICKS, SENTINEL, ZONE_3, ZONE_KEY, SelectorCall, as_signed, ev, eval_into_view, indexed_cluster,  # noqa: F401 (ev: the fixture)
+                                  recipe_cluster, row_kinds)
 
 pytestmark = pytest.mark.gpu
 
 OPS = [SELOP_EXISTS, SELOP_GT, SELOP_LT]
 OP_IDS = ["exists", "gt", "lt"]
-SENTINEL = 0x5A5A5A5A5A5A5A5A
-GUARD_ROWS = 2
 IDS = np.array([0, 1, 2, 3, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFE], dtype=np.uint32)  # what a node carries: 0 = not the key
-
-
-@pytest.fixture
-def ev(evaluator):
-    evaluator.set_kernel("auto")
-    yield evaluator
-    evaluator.set_kernel("auto")
-    evaluator.set_option(_lib.OPT_PICK_FROM_MASK, 0)
-    evaluator.set_option(_lib.OPT_FUSED_PICK, 1)
+CALLS = {op: SelectorCall(SEL | op, "selop", lambda lab, sel, p=None, op=op: selop_ref.selop_mask(lab, sel, op, p=p)) for op in OPS}
 
 
 def test_the_flags_are_the_restatements():
@@ -63,10 +54,6 @@ def variant_bits(labels, entries, rule):
             e = entries[k][pods][:, None]
             ok[pods] &= np.where(e == SEL_NEVER, False, rule(e, labels[k][None, :]))
     return ok
-
-
-def as_signed(x):
-    return x.astype(np.uint32).astype(np.int32)
 
 
 def case(n, keys):
@@ -107,12 +94,6 @@ def case(n, keys):
             a.setflags(write=False)
         _CASES[(n, keys)] = dict(lab=lab, sel=sel, want=want, two=two)
     return _CASES[(n, keys)]
-
-
-def row_kinds(m, n):
-    """(rows with every node, rows with none, rows that are neither) of packed rows over n nodes"""
-    count = np.unpackbits(np.ascontiguousarray(m).view(np.uint8), axis=1).sum(axis=1)
-    return int((count == n).sum()), int((count == 0).sum()), int(((count > 0) & (count < n)).sum())
 
 
 _FACTS = {}
@@ -163,37 +144,6 @@ def check_matrix_facts():
         assert f["both_differ"] >= 1, f"{name}: no pod whose two keys together differ from each alone"
 
 
-def eval_into_view(ev, cols, flags, n, p, pitch, offset, old=None):
-    """One evaluation of the first p pods into a [p, W] view of rows `pitch` words apart that starts `offset` words into its buffer; behind the
-    view's rows lie GUARD_ROWS more.  Every word of the buffer is the sentinel (words [0, W) of the rows: `old`, where given).  Returns the
-    rows; the padding words, the guard rows and the words outside the view are checked here."""
-    import torch
-    W = (n + 63) // 64
-    rows = p + GUARD_ROWS
-    host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
-    body = host[offset:offset + rows * pitch].reshape(rows, pitch)
-    if old is not None:
-        body[:p, :W] = old[:p]
-    buf = torch.from_numpy(host.view(np.int64)).to(dev_of(ev))
-    view = buf[offset:offset + rows * pitch].view(rows, pitch)[:p, :W]
-    assert p == 1 or view.stride(0) == pitch
-    cpu, mem, sel = cols
-    ev.eval_device(cpu[:p], mem[:p], None if sel is None else sel[:, :p].contiguous(), None, None, flags, out_feasible=view)
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy().view(np.uint64)
-    got_body = got[offset:offset + rows * pitch].reshape(rows, pitch)
-    pad = got_body[:p, W:]
-    assert ((pad == SENTINEL) | (pad == 0)).all(), "a padding word is neither untouched nor zero"
-    assert (got_body[p:] == SENTINEL).all(), "wrote into the guard rows"
-    assert (got[:offset] == SENTINEL).all() and got[-1] == SENTINEL, "wrote outside the view"
-    return got_body[:p, :W].copy()
-
-
-def zeros_dev(ev, p):
-    import torch
-    return torch.zeros(p, dtype=torch.int64, device=dev_of(ev))
-
-
 @pytest.mark.parametrize("keys", KEYS)
 @pytest.mark.parametrize("n", NODES)
 def test_mask_parity(ev, n, keys):
@@ -205,13 +155,12 @@ def test_mask_parity(ev, n, keys):
         assert k["want"][op].shape == (P_MAX, W) and not (k["want"][op][:, -1] & ~np.uint64(valid_last)).any()
     ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), k["lab"])
     assert ev.W == W
-    cols = (zeros_dev(ev, P_MAX), zeros_dev(ev, P_MAX), to_dev(ev, k["sel"], np.int32))
     std = int(_lib.load().ksched_mask_pitch(n))
     assert std % 16 == 0 and std >= W
     for p in PODS:
         for pitch, offset in ((W, 0), (std, 0), (W, 1), (std, 1)):
             for op, name in zip(OPS, OP_IDS):
-                got = eval_into_view(ev, cols, SEL | op, n, p, pitch, offset)
+                got = eval_into_view(ev, k["sel"], SEL | op, n, p, pitch, offset)
                 want = k["want"][op][:p]
                 assert np.array_equal(got, want), f"{name}, p = {p}, pitch {pitch}, offset {offset}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ from selop_ref"
                 assert ev.last_kernel == "selop" and ev.last_pick == "none"
@@ -243,7 +192,6 @@ def test_a_block_that_walks_more_than_one_pod_tile(ev):
     sel[:, 3] = 0
     ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), lab)
     assert ev.W == W
-    cols = (zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, sel, np.int32))
     pitch = W + 3
     for op, name in zip(OPS, OP_IDS):
         want = selop_ref.selop_mask(lab, sel, op)
@@ -251,33 +199,16 @@ def test_a_block_that_walks_more_than_one_pod_tile(ev):
         assert row_kinds(want, n)[2] >= p // 4, f"{name}: rows that are neither full nor empty"
         # what a block that walked tile 0 twice would leave in the rows of tile 1, and one that skipped to tile 2 in those of tile 1
         assert (want[64:128] != want[0:64]).any(axis=1).sum() >= 32 and (want[64:66] != want[128:130]).any(), f"{name}: the tiles' rows differ"
-        got = eval_into_view(ev, cols, SEL | op, n, p, pitch, 1)
+        got = eval_into_view(ev, sel, SEL | op, n, p, pitch, 1)
         assert np.array_equal(got, want), f"{name}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ from selop_ref"
         assert ev.last_kernel == "selop" and ev.last_pick == "none"
 
 
 def test_no_selectors_and_no_keys_pass_every_node(ev):
-    n, p = 65, 3
-    lab = IDS[np.random.default_rng(0xE80).integers(0, IDS.size, size=(2, n))]
-    full = selop_ref.selop_mask(lab, None, SELOP_GT, p=p)
-    assert full.tolist() == [[0xFFFFFFFFFFFFFFFF, 1]] * p
-    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), lab)
-    for op in OPS:
-        got = eval_into_view(ev, (zeros_dev(ev, p), zeros_dev(ev, p), None), SEL | op, n, p, 2, 0)
-        assert np.array_equal(got, full) and ev.last_kernel == "selop"
-    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), None)
-    assert ev.n_keys == 0
-    for op in OPS:
-        got = eval_into_view(ev, (zeros_dev(ev, p), zeros_dev(ev, p), None), SEL | op, n, p, 16, 1)
-        assert np.array_equal(got, full) and ev.last_kernel == "selop"
+    selector_calls.no_selectors_and_no_keys_pass_every_node(ev, list(CALLS.values()), list(CALLS.values()), 0xE80, IDS)
 
 
 # ---- 2. both kinds of snapshot --------------------------------------------------------------------------------------------------------------
-def indexed_cluster():
-    c = synth.make_cluster(129, 1500, n_keys=8, n_taints=0, seed=0xE8001)
-    return c.avail_cpu, c.avail_mem, c.node_labels, np.ascontiguousarray(c.pod_sel)
-
-
 def unindexed_cluster():
     """three high-cardinality keys: no bitmap index (tests/test_gpu_summary.py's builder)"""
     rng = np.random.default_rng(0xE8002)
@@ -300,15 +231,14 @@ def test_the_same_bits_on_both_kinds_of_snapshot_under_every_kernel_option(ev, k
         assert row_kinds(want[op], n)[2] > p // 8, "most constrained rows are neither full nor empty"
     ev.set_nodes(cpu, mem, lab)
     assert (ev.index_checksum() != (0, 0)) == (kind == "indexed")
-    cols = (zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, sel, np.int32))
     for kernel in ("auto", "direct", "fused"):
         ev.set_kernel(kernel)  # (no effect on an operator call: the fused kernel forced on an unindexed snapshot is no refusal here)
         for op in OPS:
-            got = eval_into_view(ev, cols, SEL | op, n, p, (n + 63) // 64, 0)
+            got = eval_into_view(ev, sel, SEL | op, n, p, (n + 63) // 64, 0)
             assert np.array_equal(got, want[op]), f"{kind}, {kernel}, {selop_ref.NAMES[op]}"
             assert ev.last_kernel == "selop"
     ev.set_kernel("auto")
-    plain = eval_into_view(ev, cols, SEL, n, p, (n + 63) // 64, 0)
+    plain = eval_into_view(ev, sel, SEL, n, p, (n + 63) // 64, 0)
     assert ev.last_kernel in ("direct", "fused") and not np.array_equal(plain, want[SELOP_EXISTS])
 
 
@@ -316,11 +246,10 @@ def test_timing_brackets_the_operator_kernel(ev):
     cpu, mem, lab, sel = indexed_cluster()
     ev.set_nodes(cpu, mem, lab)
     p = sel.shape[1]
-    cols = (zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, sel, np.int32))
     ev.set_timing(True)
     try:
         ev.kernel_time_ms()  # (reading the samples resets them)
-        eval_into_view(ev, cols, SEL | SELOP_GT, lab.shape[1], p, ev.W, 0)
+        eval_into_view(ev, sel, SEL | SELOP_GT, lab.shape[1], p, ev.W, 0)
         ms, count = ev.kernel_time_ms()
         assert count == 1 and ms > 0, "one pair of stream events around the operator kernel"
     finally:
@@ -328,61 +257,18 @@ def test_timing_brackets_the_operator_kernel(ev):
 
 
 # ---- 3. combining ---------------------------------------------------------------------------------------------------------------------------
-COMBINES = [(COMBINE_AND, "and"), (COMBINE_OR, "or"), (COMBINE_ANDNOT, "andnot"), (COMBINE_AND | COMBINE_SOFT, "soft-and"), (COMBINE_ANDNOT | COMBINE_SOFT, "soft-andnot")]
-
-
-def combined(old, new, comb, n):
-    return soft_ref.soft_combine(old, new, comb, n) if comb & COMBINE_SOFT else combine_ref.combine(old, new, comb, n)
-
-
 @pytest.mark.parametrize("comb,comb_id", COMBINES, ids=[c[1] for c in COMBINES])
 @pytest.mark.parametrize("op", OPS, ids=OP_IDS)
 def test_every_operator_under_every_combine(ev, op, comb, comb_id):
-    n, keys, p = 1025, 9, 129
-    k = case(n, keys)
-    new = k["want"][op]
-    W = (n + 63) // 64
-    rng = np.random.default_rng([0xE83, op, comb])
-    old = rng.integers(0, 1 << 64, size=(p, W), dtype=np.uint64)
-    old[::5] &= rng.integers(0, 1 << 64, size=(len(old[::5]), W), dtype=np.uint64) & rng.integers(0, 1 << 64, size=(len(old[::5]), W), dtype=np.uint64)
-    old[:, -1] |= ~np.uint64(combine_ref.valid_bits_word(n))  # garbage at and beyond n
-    want = combined(old, new, comb, n)
-    assert not np.array_equal(want, new) and not np.array_equal(want, soft_ref.old_prime(old, n)), "the combine shows"
-    if comb & COMBINE_SOFT:
-        what = soft_ref.decisions(old, new, comb, n)
-        assert (what == soft_ref.NARROWED).any() and (what == soft_ref.DROPPED).any(), "rows that narrow and rows whose tier is dropped"
-        assert not np.array_equal(want, combine_ref.combine(old, new, comb & ~COMBINE_SOFT, n))
-    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), k["lab"])
-    cols = (zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, k["sel"], np.int32))
-    std = int(_lib.load().ksched_mask_pitch(n))
-    for pitch, offset in ((W, 0), (std, 0), (W, 1)):
-        got = eval_into_view(ev, cols, SEL | op | comb, n, p, pitch, offset, old=old)
-        assert np.array_equal(got, want), f"pitch {pitch}, offset {offset}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"
-        assert ev.last_kernel == "selop" and ev.last_pick == "none"
-
-
-GPU_KEY, CORES_KEY, ZONE_KEY, ZONE_3 = 0, 1, 2, 3
-
-
-def recipe_cluster():
-    """synth's capacities and requests under labels of the recipe's own: gpu present on three nodes in five, cores = 4 .. 64 interned as
-    id = cores + 1 (a tenth of the nodes carry none), zone 1 .. 3 (a tenth none)"""
-    P, N = 200, 300
-    c = synth.make_cluster(P, N, n_keys=8, n_taints=0, seed=0xE8C4A1)
-    c.req_mem[0] = 1 << 60  # pod 0 fits nowhere
-    rng = np.random.default_rng(0xE8C4)
-    lab = c.node_labels.copy()
-    lab[GPU_KEY] = np.where(rng.random(N) < 0.6, 1, 0)
-    lab[CORES_KEY] = np.where(rng.random(N) < 0.1, 0, np.array([4, 8, 16, 32, 64])[rng.integers(0, 5, N)] + 1)
-    lab[ZONE_KEY] = np.where(rng.random(N) < 0.1, 0, rng.integers(1, 4, N))
-    return c, lab.astype(np.uint32)
+    k = case(1025, 9)
+    selector_calls.the_call_under_every_combine(ev, CALLS[op], k["lab"], k["sel"], k["want"][op], comb, np.random.default_rng([0xE83, op, comb]))
 
 
 @pytest.mark.parametrize("pitched", [False, True], ids=["packed", "pitched"])
 def test_the_recipe_end_to_end(ev, pitched):
     """gpu Exists AND cores Gt 16 AND zone NotIn {z3} AND fit, then the spread pick: four calls on one mask, against the label columns"""
     import torch
-    c, lab = recipe_cluster()
+    c, lab = recipe_cluster(0xE8C4)
     P, N = c.P, c.N
     fits = (c.req_cpu[:, None] <= c.avail_cpu[None, :]) & (c.req_mem[:, None] <= c.avail_mem[None, :])
     gpu, cores, zone = lab[GPU_KEY], lab[CORES_KEY].astype(np.int64) - 1, lab[ZONE_KEY]
@@ -423,7 +309,6 @@ def test_the_recipe_end_to_end(ev, pitched):
 
 
 # ---- 4. picks -----------------------------------------------------------------------------------------------------------------------------------
-PICKS = [(PICK_SAMPLED, "from-mask"), (PICK_BESTFIT, "from-mask"), (PICK_UNIFORM, "uniform"), (PICK_SPREAD, "spread"), (PICK_PACK, "pack")]
 _PICK_CASE = {}
 
 
@@ -446,75 +331,18 @@ def pick_case():
 @pytest.mark.parametrize("op", OPS, ids=OP_IDS)
 @pytest.mark.parametrize("pick,last_pick", PICKS, ids=["sampled", "bestfit", "uniform", "spread", "pack"])
 def test_a_pick_in_an_operator_call_is_the_pick_from_the_resulting_mask(ev, pick, last_pick, op):
-    """plain (with and without out_feasible) and combining, under either setting of KSCHED_OPT_PICK_FROM_MASK and with the riding pick on
-    or off: the bindings of ksched_pick_device on the resulting mask with the pick flag alone"""
-    import torch
-    k = pick_case()
-    c = k["c"]
-    P, N = c.P, c.N
-    ev.set_nodes(c.avail_cpu, c.avail_mem, c.node_labels)
-    cpu, mem = to_dev(ev, c.req_cpu, np.int64), to_dev(ev, c.req_mem, np.int64)
-    sel = to_dev(ev, k["sel"], np.int32)
-    smp = to_dev(ev, c.samples if pick == PICK_SAMPLED else k["draws"], np.int32) if pick != PICK_BESTFIT else None
-    masks = {0: k["new"][op], COMBINE_AND: combine_ref.combine(k["old"], k["new"][op], COMBINE_AND, N)}
-    for comb, want in masks.items():
-        f, e, m = row_kinds(want, N)
-        assert e >= 1 and m > P // 4, "pods without a node, and many with some but not all"
-        alone = fresh(ev, P)
-        ev.pick_device(to_dev(ev, want, np.int64), pick, alone, req_mem_bytes=mem, samples=smp)
-        torch.cuda.synchronize()
-        alone = alone.cpu().numpy()
-        assert (alone >= 0).any() and ((alone >= 0) <= want.any(axis=1)).all()
-        if pick == PICK_UNIFORM:
-            assert np.array_equal(alone, uniform_pick(want, k["draws"][:, 0], N))
-        for from_mask, fused_pick in ((0, 1), (1, 1), (0, 0)):
-            ev.set_option(_lib.OPT_PICK_FROM_MASK, from_mask)
-            ev.set_option(_lib.OPT_FUSED_PICK, fused_pick)
-            for with_mask in ([True] if comb else [True, False]):
-                M = to_dev(ev, k["old"], np.int64) if with_mask else None
-                out = fresh(ev, P, 4)
-                ev.eval_device(cpu, mem, sel, None, smp, SEL | op | comb | pick, out_feasible=M, out_binding=out[:P])
-                assert ev.last_pick == last_pick and ev.last_kernel == "selop"
-                torch.cuda.synchronize()
-                if with_mask:
-                    assert np.array_equal(mask_np(M), want)
-                b = out.cpu().numpy()
-                assert np.array_equal(b[:P], alone), f"pods {np.nonzero(b[:P] != alone)[0][:5]} differ from ksched_pick_device on the mask"
-                assert (b[P:] == -7).all()
+    selector_calls.a_pick_in_the_call_is_the_pick_from_the_resulting_mask(ev, CALLS[op], pick_case(), pick_case()["new"][op], pick, last_pick)
 
 
 # ---- 5. the host forms --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("op", OPS, ids=OP_IDS)
 def test_the_host_forms_give_the_device_forms_bits(ev, op):
-    k = pick_case()
-    c = k["c"]
-    P, N = c.P, c.N
-    ev.set_nodes(c.avail_cpu, c.avail_mem, c.node_labels)
-    W = ev.W
-    want = k["new"][op]
-    picked = uniform_pick(want, k["draws"][:, 0], N)
-    r = ev.eval(c.req_cpu, c.req_mem, k["sel"], None, None, SEL | op)
-    assert np.array_equal(r.feasible, want) and r.binding is None and ev.last_kernel == "selop" and ev.last_pick == "none"
-    r = ev.eval(c.req_cpu, c.req_mem, k["sel"], None, k["draws"], SEL | op | PICK_UNIFORM)
-    assert np.array_equal(r.feasible, want) and np.array_equal(r.binding, picked) and ev.last_pick == "uniform"
-    r = ev.eval(c.req_cpu, c.req_mem, k["sel"], None, k["draws"], SEL | op | PICK_UNIFORM, want_mask=False)
-    assert r.feasible is None and np.array_equal(r.binding, picked)
-    # the two halves
-    lib, hp = ev._lib, lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    feas = np.full((P, W), SENTINEL, dtype=np.uint64)
-    part = np.full(P + 3, 555, dtype=np.int32)
-    dev_b, stream = C.c_void_p(), C.c_void_p()
-    rc = lib.ksched_eval_begin(ev._h, P, hp(c.req_cpu), hp(c.req_mem), hp(k["sel"]), P, None, hp(k["draws"]), 5, SEL | op | PICK_UNIFORM, hp(feas), None,
-                               P + 3, C.byref(dev_b), C.byref(stream))
-    assert rc == _lib.OK and dev_b.value
-    assert lib.ksched_eval_end(ev._h, dev_b, P + 3, hp(part)) == _lib.OK
-    assert np.array_equal(feas, want) and np.array_equal(part[:P], picked) and (part[P:] == -1).all()
-    assert ev.last_kernel == "selop"
+    selector_calls.the_host_forms_give_the_device_forms_bits(ev, CALLS[op], pick_case(), pick_case()["new"][op])
 
 
 # ---- 6. snapshot changes ------------------------------------------------------------------------------------------------------------------------
-def all_ops(ev, cols, n, p):
-    return {op: eval_into_view(ev, cols, SEL | op, n, p, (n + 63) // 64, 0) for op in OPS}
+def all_ops(ev, sel, n, p):
+    return {op: eval_into_view(ev, sel, SEL | op, n, p, (n + 63) // 64, 0) for op in OPS}
 
 
 def test_label_updates_another_key_count_and_a_fresh_evaluator(built):
@@ -526,8 +354,7 @@ def test_label_updates_another_key_count_and_a_fresh_evaluator(built):
     e = Evaluator(0)
     try:
         e.set_nodes(c.avail_cpu, c.avail_mem, lab)
-        cols = (zeros_dev(e, p), zeros_dev(e, p), to_dev(e, sel, np.int32))
-        for op, got in all_ops(e, cols, n, p).items():
+        for op, got in all_ops(e, sel, n, p).items():
             assert np.array_equal(got, selop_ref.selop_mask(lab, sel, op))
         # within the planned maxima: ids the keys already have, and nodes that lose a key
         idx = rng.choice(n, size=200, replace=False).astype(np.uint32)
@@ -536,7 +363,7 @@ def test_label_updates_another_key_count_and_a_fresh_evaluator(built):
         lab[:, idx] = rows
         assert all(not np.array_equal(before[op], selop_ref.selop_mask(lab, sel, op)) for op in OPS), "the update shows in every operator's mask"
         e.update_node_labels(idx, rows)
-        for op, got in all_ops(e, cols, n, p).items():
+        for op, got in all_ops(e, sel, n, p).items():
             assert np.array_equal(got, selop_ref.selop_mask(lab, sel, op)), f"{selop_ref.NAMES[op]} after an update within the planned maxima"
         # past them: ids above every planned maximum (the layout is planned again)
         idx = rng.choice(n, size=300, replace=False).astype(np.uint32)
@@ -544,7 +371,7 @@ def test_label_updates_another_key_count_and_a_fresh_evaluator(built):
         lab[:, idx] = rows
         assert (lab.max(axis=1) > c.node_labels.max(axis=1)).all()
         e.update_node_labels(idx, rows)
-        for op, got in all_ops(e, cols, n, p).items():
+        for op, got in all_ops(e, sel, n, p).items():
             assert np.array_equal(got, selop_ref.selop_mask(lab, sel, op)), f"{selop_ref.NAMES[op]} after a relabel past the planned maxima"
         # another key count: eleven keys (two passes) over other nodes
         k = case(1025, 9)
@@ -552,8 +379,7 @@ def test_label_updates_another_key_count_and_a_fresh_evaluator(built):
         sel2 = np.concatenate([k["sel"], k["sel"][:2]])
         e.set_nodes(np.zeros(1025, np.int64), np.zeros(1025, np.int64), lab2)
         assert e.n_keys == 11
-        cols2 = (zeros_dev(e, P_MAX), zeros_dev(e, P_MAX), to_dev(e, sel2, np.int32))
-        for op, got in all_ops(e, cols2, 1025, P_MAX).items():
+        for op, got in all_ops(e, sel2, 1025, P_MAX).items():
             want = selop_ref.selop_mask(lab2, sel2, op)
             assert np.array_equal(got, want) and not np.array_equal(want, k["want"][op]), f"{selop_ref.NAMES[op]} after ksched_set_nodes with eleven keys"
     finally:
@@ -562,43 +388,8 @@ def test_label_updates_another_key_count_and_a_fresh_evaluator(built):
 
 @pytest.mark.parametrize("op", OPS, ids=OP_IDS)
 def test_two_streams_around_a_label_update(ev, op):
-    """an operator call on stream A, a label update, an operator call on stream B, no host wait in between: each call sees the labels that
-    were current when it was enqueued"""
-    import torch
     c = synth.make_cluster(129, 1100, n_keys=8, n_taints=0, seed=0xE87)
-    lab = c.node_labels.copy()
-    sel = np.ascontiguousarray(c.pod_sel)
-    n, p = c.N, c.P
-    rng = np.random.default_rng([0xE87, op])
-    idx = rng.choice(n, size=400, replace=False).astype(np.uint32)
-    rows = rng.integers(0, lab.max(axis=1)[:, None] + 1, size=(8, idx.size)).astype(np.uint32)
-    lab_after = lab.copy()
-    lab_after[:, idx] = rows
-    want_a, want_b = selop_ref.selop_mask(lab, sel, op), selop_ref.selop_mask(lab_after, sel, op)
-    assert not np.array_equal(want_a, want_b)
-    ev.set_nodes(c.avail_cpu, c.avail_mem, lab)
-    cpu, mem, sel_t = zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, sel, np.int32)
-    a, b = torch.cuda.Stream(ev.device), torch.cuda.Stream(ev.device)
-    rounds = 3
-    masks_a = [ev.alloc_mask(p, pitched=True) for _ in range(rounds)]
-    masks_b = [ev.alloc_mask(p, pitched=False) for _ in range(rounds)]
-    for m in masks_a + masks_b:
-        m.fill_(0x5A)
-    torch.cuda.synchronize()
-    try:
-        for i in range(rounds):
-            ev.eval_device(cpu, mem, sel_t, None, None, SEL | op, out_feasible=masks_a[i], stream=a)
-            ev.update_node_labels(idx, rows)
-            ev.eval_device(cpu, mem, sel_t, None, None, SEL | op, out_feasible=masks_b[i], stream=b)
-            if i + 1 < rounds:
-                ev.update_node_labels(idx, np.ascontiguousarray(lab[:, idx]))  # back to the first labels for the next round
-        torch.cuda.synchronize()
-        for i in range(rounds):
-            assert np.array_equal(mask_np(masks_a[i]), want_a), f"round {i}, stream A: the labels before the update"
-            assert np.array_equal(mask_np(masks_b[i]), want_b), f"round {i}, stream B: the labels after it"
-    finally:
-        ev.forget_stream(a)
-        ev.forget_stream(b)
+    selector_calls.two_streams_around_a_label_update(ev, CALLS[op], c, np.ascontiguousarray(c.pod_sel), np.random.default_rng([0xE87, op]))
 
 
 # ---- 7. refusals and edge sizes -------------------------------------------------------------------------------------------------------------------
@@ -703,39 +494,4 @@ def test_refusals_leave_mask_and_bindings_untouched(ev, op):
 
 @pytest.mark.parametrize("op", OPS, ids=OP_IDS)
 def test_edge_sizes(built, op):
-    import torch
-    e = Evaluator(0)
-    try:
-        dev = torch.device("cuda", 0)
-        cpu = torch.zeros(5, dtype=torch.int64, device=dev)
-        sel = torch.ones((2, 5), dtype=torch.int32, device=dev)
-        smp = torch.zeros((5, 3), dtype=torch.int32, device=dev)
-        M = torch.full((5, 2), 0x5A, dtype=torch.int64, device=dev)
-        B = torch.full((5,), -7, dtype=torch.int32, device=dev)
-        vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        st = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
-        lib = e._lib
-        # before ksched_set_nodes
-        assert lib.ksched_eval_device(e._h, 5, vp(cpu), vp(cpu), vp(sel), None, None, 0, SEL | op, vp(M), None, None, st) == _lib.E_STATE
-        assert lib.ksched_eval_device_pitched(e._h, 5, vp(cpu), vp(cpu), vp(sel), None, vp(smp), 3, SEL | op | COMBINE_AND | PICK_UNIFORM, vp(M), None, vp(B), 2, st) == _lib.E_STATE
-        with pytest.raises(KschedError) as err:
-            e.eval(np.zeros(5, np.int64), np.zeros(5, np.int64), None, None, None, SEL | op)
-        assert err.value.code == _lib.E_STATE
-        # n == 0: the mask is left alone, every pod of a pick gets -1
-        e.set_nodes(np.zeros(0, np.int64), np.zeros(0, np.int64))
-        for comb in (0, COMBINE_AND):
-            B.fill_(-7)
-            assert lib.ksched_eval_device_pitched(e._h, 5, vp(cpu), vp(cpu), vp(sel), None, vp(smp), 3, SEL | op | comb | PICK_UNIFORM, vp(M), None, vp(B), 2, st) == _lib.OK
-            torch.cuda.synchronize()
-            assert (M == 0x5A).all() and (B == -1).all()
-        # p == 0: a no-op
-        e.set_nodes(np.zeros(70, np.int64), np.zeros(70, np.int64), np.ones((2, 70), np.uint32))
-        B.fill_(-7)
-        assert lib.ksched_eval_device_pitched(e._h, 0, vp(cpu), vp(cpu), vp(sel), None, vp(smp), 3, SEL | op | PICK_UNIFORM, vp(M), None, vp(B), 2, st) == _lib.OK
-        assert lib.ksched_eval_device_pitched(e._h, 0, None, None, None, None, None, 0, SEL | op, vp(M), None, None, 2, st) == _lib.OK
-        torch.cuda.synchronize()
-        assert (M == 0x5A).all() and (B == -7).all()
-        r = e.eval(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((2, 0), np.uint32), None, None, SEL | op)
-        assert r.feasible.shape == (0, 2)
-    finally:
-        e.close()
+    selector_calls.edge_sizes(CALLS[op])

@@ -12,30 +12,33 @@ top of it.
  4. the host forms ksched_eval and ksched_eval_begin / _end (sel_stride > p) give the device form's bits;
  5. a label update before the call, and two streams around a label update;
  6. the refusals at every entry point with outputs untouched, field 0 beside what is legal today, and the edge sizes.
-Every output goes into sentinel-filled buffers with guard rows.  Shapes are the smallest at which the kernels take each path."""
+Every output goes into sentinel-filled buffers with guard rows.  Shapes are the smallest at which the kernels take each path.  What the three selector
+files share -- the guarded evaluation, the bodies that are the same for every call -- is tests/selector_calls.py's."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, MAX_TERMS, PICK_BESTFIT, PICK_PACK, PICK_SAMPLED,
-                                             PICK_SPREAD, PICK_UNIFORM, SEL, SEL_NEVER, SEL_TERMS_MASK, SEL_TERMS_SHIFT, SELOP_EXISTS, SELOP_GT, SELOP_LT,
-                                             SELOP_TAGGED, TAINT, WANT_FIT_MASK, Evaluator, KschedError, _lib, node_affinity_rows, pack_mask, sel_terms, synth)
-from tests import combine_ref, selterms_ref, seltag_ref, soft_ref
+from kube_scheduler_rs_reference_amd import (COMBINE_AND, COMBINE_ANDNOT, COMBINE_OR, COMBINE_SOFT, FIT, MAX_TERMS, PICK_BESTFIT, PICK_SAMPLED, PICK_SPREAD, PICK_UNIFORM,
+                                             SEL, SEL_NEVER, SEL_TERMS_MASK, SEL_TERMS_SHIFT, SELOP_EXISTS, SELOP_GT, SELOP_LT, SELOP_TAGGED, TAINT, WANT_FIT_MASK,
+                                             Evaluator, _lib, node_affinity_rows, pack_mask, sel_terms, synth)
+from tests import combine_ref, selector_calls, selterms_ref, seltag_ref
 from tests.pick_helpers import dev_of, fresh, mask_np, oracle_mask, pod_tensors, to_dev
-from tests.uniform_ref import uniform_pick
+from tests.selector_calls import COMBINES, PICKS, SENTINEL, SelectorCall, ev, eval_into_view, row_kinds, zeros_dev  # noqa: F401 (ev: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 TG = SEL | SELOP_TAGGED
-SENTINEL = 0x5A5A5A5A5A5A5A5A
-GUARD_ROWS = 2
 EQ, NE, EX, AB, GT, LT = seltag_ref.TAGS
 E = seltag_ref.entry
 
 
 def F(t):
     return TG | sel_terms(t)
+
+
+def call(t):
+    return SelectorCall(F(t), "selterms", selterms_ref.selterms_mask, (t,))
 
 
 # the launch geometry (csrc/sel_ops.hpp, which csrc/sel_terms.hpp's plan takes over): a wave owns 4 word columns of 64 nodes, a block is 4
@@ -118,12 +121,6 @@ def case(n, keys, p=P_MAX):
     return _CASES[(n, keys, p)]
 
 
-def row_kinds(m, n):
-    """(rows with every node, rows with none, rows that are neither) of packed rows over n nodes"""
-    count = np.unpackbits(np.ascontiguousarray(m).view(np.uint8), axis=1).sum(axis=1)
-    return int((count == n).sum()), int((count == 0).sum()), int(((count > 0) & (count < n)).sum())
-
-
 _FACTS = {}
 
 
@@ -167,45 +164,6 @@ def check_matrix_facts():
         elif n >= 63:
             assert m >= 0.1, f"n = {n}, keys = {keys}, T = {T}: only {m:.0%} of the rows are neither empty nor full"
     assert set(range(8)) <= f["tags"], "every tag, 6 and 7 included, occurs in a row that is neither empty nor full"
-
-
-def zeros_dev(ev, p):
-    import torch
-    return torch.zeros(p, dtype=torch.int64, device=dev_of(ev))
-
-
-def eval_into_view(ev, sel, flags, n, p, pitch, offset, old=None):
-    """One evaluation of the first p pods of `sel` ([T][keys][P] numpy, or None) into a [p, W] view of rows `pitch` words apart that starts
-    `offset` words into its buffer; behind the view's rows lie GUARD_ROWS more.  Every word of the buffer is the sentinel (words [0, W) of
-    the rows: `old`, where given).  Returns the rows; the padding words, the guard rows and the words outside the view are checked here."""
-    import torch
-    W = (n + 63) // 64
-    rows = p + GUARD_ROWS
-    host = np.full(offset + rows * pitch + 1, SENTINEL, dtype=np.uint64)
-    body = host[offset:offset + rows * pitch].reshape(rows, pitch)
-    if old is not None:
-        body[:p, :W] = old[:p]
-    buf = torch.from_numpy(host.view(np.int64)).to(dev_of(ev))
-    view = buf[offset:offset + rows * pitch].view(rows, pitch)[:p, :W]
-    sel_t = None if sel is None else to_dev(ev, np.ascontiguousarray(sel[..., :p]), np.int32)
-    ev.eval_device(zeros_dev(ev, p), zeros_dev(ev, p), sel_t, None, None, flags, out_feasible=view)
-    torch.cuda.synchronize()
-    got = buf.cpu().numpy().view(np.uint64)
-    got_body = got[offset:offset + rows * pitch].reshape(rows, pitch)
-    pad = got_body[:p, W:]
-    assert ((pad == SENTINEL) | (pad == 0)).all(), "a padding word is neither untouched nor zero"
-    assert (got_body[p:] == SENTINEL).all(), "wrote into the guard rows"
-    assert (got[:offset] == SENTINEL).all() and got[-1] == SENTINEL, "wrote outside the view"
-    return got_body[:p, :W].copy()
-
-
-@pytest.fixture
-def ev(evaluator):
-    evaluator.set_kernel("auto")
-    yield evaluator
-    evaluator.set_kernel("auto")
-    evaluator.set_option(_lib.OPT_PICK_FROM_MASK, 0)
-    evaluator.set_option(_lib.OPT_FUSED_PICK, 1)
 
 
 def test_the_matrix_tells_the_kernels_from_wrong_ones():
@@ -257,18 +215,8 @@ def test_a_block_that_walks_more_than_one_pod_tile(ev, keys):
 
 
 def test_no_selectors_and_no_keys_pass_every_node(ev):
-    n, p = 65, 3
-    lab = IDS[np.random.default_rng(0xE100).integers(0, IDS.size, size=(2, n))]
-    full = selterms_ref.selterms_mask(lab, None, p=p)
-    assert full.tolist() == [[0xFFFFFFFFFFFFFFFF, 1]] * p
-    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), lab)
-    got = eval_into_view(ev, None, F(3), n, p, 2, 0)
-    assert np.array_equal(got, full) and ev.last_kernel == "selterms"
-    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), None)
-    assert ev.n_keys == 0
-    got = eval_into_view(ev, None, F(15), n, p, 16, 1)
-    assert np.array_equal(got, full) and ev.last_kernel == "selterms"
-    got = eval_into_view(ev, np.zeros((4, 0, p), np.uint32), F(4), n, p, 2, 0)
+    full = selector_calls.no_selectors_and_no_keys_pass_every_node(ev, [call(3)], [call(15)], 0xE100, IDS)
+    got = eval_into_view(ev, np.zeros((4, 0, 3), np.uint32), F(4), 65, 3, 2, 0)
     assert np.array_equal(got, full)
 
 
@@ -354,37 +302,12 @@ def test_timing_brackets_the_kernel(ev):
 
 
 # ---- 3. combining and picks ---------------------------------------------------------------------------------------------------------------------
-COMBINES = [(COMBINE_AND, "and"), (COMBINE_OR, "or"), (COMBINE_ANDNOT, "andnot"), (COMBINE_AND | COMBINE_SOFT, "soft-and"), (COMBINE_ANDNOT | COMBINE_SOFT, "soft-andnot")]
-
-
-def combined(old, new, comb, n):
-    return soft_ref.soft_combine(old, new, comb, n) if comb & COMBINE_SOFT else combine_ref.combine(old, new, comb, n)
-
-
 @pytest.mark.parametrize("comb,comb_id", COMBINES, ids=[c[1] for c in COMBINES])
 def test_the_call_under_every_combine(ev, comb, comb_id):
-    n, keys, p, T = 1025, PASS_KEYS + 1, 129, 3
-    k = case(n, keys)
-    new = k["want"][T]
-    W = (n + 63) // 64
-    rng = np.random.default_rng([0xE103, comb])
-    old = rng.integers(0, 1 << 64, size=(p, W), dtype=np.uint64)
-    old[::5] &= rng.integers(0, 1 << 64, size=(len(old[::5]), W), dtype=np.uint64) & rng.integers(0, 1 << 64, size=(len(old[::5]), W), dtype=np.uint64)
-    old[:, -1] |= ~np.uint64(combine_ref.valid_bits_word(n))  # garbage at and beyond n
-    want = combined(old, new, comb, n)
-    assert not np.array_equal(want, new) and not np.array_equal(want, soft_ref.old_prime(old, n)), "the combine shows"
-    if comb & COMBINE_SOFT:
-        what = soft_ref.decisions(old, new, comb, n)
-        assert (what == soft_ref.NARROWED).any() and (what == soft_ref.DROPPED).any(), "rows that narrow and rows whose tier is dropped"
-    ev.set_nodes(np.zeros(n, np.int64), np.zeros(n, np.int64), k["lab"])
-    std = int(_lib.load().ksched_mask_pitch(n))
-    for pitch, offset in ((W, 0), (std, 0), (W, 1)):
-        got = eval_into_view(ev, k["sel"][:T], F(T) | comb, n, p, pitch, offset, old=old)
-        assert np.array_equal(got, want), f"pitch {pitch}, offset {offset}: pods {np.nonzero((got != want).any(axis=1))[0][:5]} differ"
-        assert ev.last_kernel == "selterms" and ev.last_pick == "none"
+    k = case(1025, PASS_KEYS + 1)
+    selector_calls.the_call_under_every_combine(ev, call(3), k["lab"], k["sel"][:3], k["want"][3], comb, np.random.default_rng([0xE103, comb]))
 
 
-PICKS = [(PICK_SAMPLED, "from-mask"), (PICK_BESTFIT, "from-mask"), (PICK_UNIFORM, "uniform"), (PICK_SPREAD, "spread"), (PICK_PACK, "pack")]
 _PICK_CASE = {}
 
 
@@ -413,40 +336,8 @@ def pick_case():
 
 @pytest.mark.parametrize("pick,last_pick", PICKS, ids=["sampled", "bestfit", "uniform", "spread", "pack"])
 def test_a_pick_in_the_call_is_the_pick_from_the_resulting_mask(ev, pick, last_pick):
-    """plain (with and without out_feasible) and combining, under either setting of KSCHED_OPT_PICK_FROM_MASK: the bindings of
-    ksched_pick_device on the resulting mask with the pick flag alone"""
-    import torch
     k = pick_case()
-    c, T = k["c"], k["T"]
-    P, N = c.P, c.N
-    ev.set_nodes(c.avail_cpu, c.avail_mem, c.node_labels)
-    cpu, mem = to_dev(ev, c.req_cpu, np.int64), to_dev(ev, c.req_mem, np.int64)
-    sel = to_dev(ev, k["sel"], np.int32)
-    smp = to_dev(ev, c.samples if pick == PICK_SAMPLED else k["draws"], np.int32) if pick != PICK_BESTFIT else None
-    masks = {0: k["new"], COMBINE_AND: combine_ref.combine(k["old"], k["new"], COMBINE_AND, N)}
-    for comb, want in masks.items():
-        f, e, m = row_kinds(want, N)
-        assert e >= 1 and m > P // 4, "pods without a node, and many with some but not all"
-        alone = fresh(ev, P)
-        ev.pick_device(to_dev(ev, want, np.int64), pick, alone, req_mem_bytes=mem, samples=smp)
-        torch.cuda.synchronize()
-        alone = alone.cpu().numpy()
-        assert (alone >= 0).any() and ((alone >= 0) <= want.any(axis=1)).all()
-        if pick == PICK_UNIFORM:
-            assert np.array_equal(alone, uniform_pick(want, k["draws"][:, 0], N))
-        for from_mask in (0, 1):
-            ev.set_option(_lib.OPT_PICK_FROM_MASK, from_mask)
-            for with_mask in ([True] if comb else [True, False]):
-                M = to_dev(ev, k["old"], np.int64) if with_mask else None
-                out = fresh(ev, P, 4)
-                ev.eval_device(cpu, mem, sel, None, smp, F(T) | comb | pick, out_feasible=M, out_binding=out[:P])
-                assert ev.last_pick == last_pick and ev.last_kernel == "selterms"
-                torch.cuda.synchronize()
-                if with_mask:
-                    assert np.array_equal(mask_np(M), want)
-                b = out.cpu().numpy()
-                assert np.array_equal(b[:P], alone), f"pods {np.nonzero(b[:P] != alone)[0][:5]} differ from ksched_pick_device on the mask"
-                assert (b[P:] == -7).all()
+    selector_calls.a_pick_in_the_call_is_the_pick_from_the_resulting_mask(ev, call(k["T"]), k, k["new"], pick, last_pick, options=((0, 1), (1, 1)))
 
 
 @pytest.mark.parametrize("pitched", [False, True], ids=["packed", "pitched"])
@@ -501,41 +392,8 @@ def test_the_recipe_end_to_end(ev, pitched):
 
 # ---- 4. the host forms --------------------------------------------------------------------------------------------------------------------------
 def test_the_host_forms_give_the_device_forms_bits(ev):
-    import torch
     k = pick_case()
-    c, T = k["c"], k["T"]
-    P, N = c.P, c.N
-    ev.set_nodes(c.avail_cpu, c.avail_mem, c.node_labels)
-    W = ev.W
-    want = k["new"]
-    M = torch.full((P, W), 0x5A, dtype=torch.int64, device=dev_of(ev))
-    ev.eval_device(zeros_dev(ev, P), zeros_dev(ev, P), to_dev(ev, k["sel"], np.int32), None, None, F(T), out_feasible=M)
-    torch.cuda.synchronize()
-    assert np.array_equal(mask_np(M), want), "the device form"
-    picked = uniform_pick(want, k["draws"][:, 0], N)
-    r = ev.eval(c.req_cpu, c.req_mem, k["sel"], None, None, F(T))
-    assert np.array_equal(r.feasible, want) and r.binding is None and ev.last_kernel == "selterms" and ev.last_pick == "none"
-    r = ev.eval(c.req_cpu, c.req_mem, k["sel"].reshape(T * c.n_keys, P), None, k["draws"], F(T) | PICK_UNIFORM)
-    assert np.array_equal(r.feasible, want) and np.array_equal(r.binding, picked) and ev.last_pick == "uniform"
-    r = ev.eval(c.req_cpu, c.req_mem, k["sel"], None, k["draws"], F(T) | PICK_UNIFORM, want_mask=False)
-    assert r.feasible is None and np.array_equal(r.binding, picked)
-    # the two halves, over rows [lo, lo + p) of a wider batch: column (t, k) starts (t * n_keys + k) * sel_stride entries in
-    lo, p, stride = 37, 150, P
-    sub = want[lo:lo + p]
-    sub_picked = uniform_pick(sub, k["draws"][lo:lo + p, 0], N)
-    assert stride > p and row_kinds(sub, N)[2] > p // 4
-    lib, hp = ev._lib, lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    feas = np.full((p, W), SENTINEL, dtype=np.uint64)
-    part = np.full(p + 3, 555, dtype=np.int32)
-    dev_b, stream = C.c_void_p(), C.c_void_p()
-    flat = np.ascontiguousarray(k["sel"]).reshape(-1)
-    draws = np.ascontiguousarray(k["draws"][lo:lo + p])
-    rc = lib.ksched_eval_begin(ev._h, p, hp(c.req_cpu[lo:]), hp(c.req_mem[lo:]), hp(flat[lo:]), stride, None, hp(draws), 5, F(T) | PICK_UNIFORM, hp(feas), None,
-                               p + 3, C.byref(dev_b), C.byref(stream))
-    assert rc == _lib.OK and dev_b.value
-    assert lib.ksched_eval_end(ev._h, dev_b, p + 3, hp(part)) == _lib.OK
-    assert np.array_equal(feas, sub) and np.array_equal(part[:p], sub_picked) and (part[p:] == -1).all()
-    assert ev.last_kernel == "selterms"
+    selector_calls.the_host_forms_give_the_device_forms_bits(ev, call(k["T"]), k, k["new"], lo=37, p=150)
 
 
 # ---- 5. snapshot changes ------------------------------------------------------------------------------------------------------------------------
@@ -582,41 +440,8 @@ def test_a_label_update_before_the_call(built):
 
 
 def test_two_streams_around_a_label_update(ev):
-    """a call on stream A, a label update, a call on stream B, no host wait in between: each call sees the labels that were current when it
-    was enqueued"""
-    import torch
     c, sel, rng = snapshot_case(0xE107)
-    lab = c.node_labels.copy()
-    n, p, T = c.N, c.P, sel.shape[0]
-    idx = rng.choice(n, size=400, replace=False).astype(np.uint32)
-    rows = rng.integers(0, lab.max(axis=1)[:, None] + 1, size=(8, idx.size)).astype(np.uint32)
-    lab_after = lab.copy()
-    lab_after[:, idx] = rows
-    want_a, want_b = selterms_ref.selterms_mask(lab, sel), selterms_ref.selterms_mask(lab_after, sel)
-    assert not np.array_equal(want_a, want_b)
-    ev.set_nodes(c.avail_cpu, c.avail_mem, lab)
-    cpu, mem, sel_t = zeros_dev(ev, p), zeros_dev(ev, p), to_dev(ev, sel, np.int32)
-    a, b = torch.cuda.Stream(ev.device), torch.cuda.Stream(ev.device)
-    rounds = 3
-    masks_a = [ev.alloc_mask(p, pitched=True) for _ in range(rounds)]
-    masks_b = [ev.alloc_mask(p, pitched=False) for _ in range(rounds)]
-    for m in masks_a + masks_b:
-        m.fill_(0x5A)
-    torch.cuda.synchronize()
-    try:
-        for i in range(rounds):
-            ev.eval_device(cpu, mem, sel_t, None, None, F(T), out_feasible=masks_a[i], stream=a)
-            ev.update_node_labels(idx, rows)
-            ev.eval_device(cpu, mem, sel_t, None, None, F(T), out_feasible=masks_b[i], stream=b)
-            if i + 1 < rounds:
-                ev.update_node_labels(idx, np.ascontiguousarray(lab[:, idx]))  # back to the first labels for the next round
-        torch.cuda.synchronize()
-        for i in range(rounds):
-            assert np.array_equal(mask_np(masks_a[i]), want_a), f"round {i}, stream A: the labels before the update"
-            assert np.array_equal(mask_np(masks_b[i]), want_b), f"round {i}, stream B: the labels after it"
-    finally:
-        ev.forget_stream(a)
-        ev.forget_stream(b)
+    selector_calls.two_streams_around_a_label_update(ev, call(sel.shape[0]), c, sel, rng)
 
 
 # ---- 6. refusals and edge sizes -------------------------------------------------------------------------------------------------------------------
@@ -738,43 +563,8 @@ def sel_terms_zero():
 
 
 def test_edge_sizes(built):
-    import torch
-    e = Evaluator(0)
-    try:
-        dev = torch.device("cuda", 0)
-        cpu = torch.zeros(5, dtype=torch.int64, device=dev)
-        sel = torch.ones((3, 2, 5), dtype=torch.int32, device=dev)
-        smp = torch.zeros((5, 3), dtype=torch.int32, device=dev)
-        M = torch.full((5, 2), 0x5A, dtype=torch.int64, device=dev)
-        B = torch.full((5,), -7, dtype=torch.int32, device=dev)
-        vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        st = C.c_void_p(torch.cuda.current_stream(0).cuda_stream)
-        lib = e._lib
-        f = F(3)
-        # before ksched_set_nodes
-        assert lib.ksched_eval_device(e._h, 5, vp(cpu), vp(cpu), vp(sel), None, None, 0, f, vp(M), None, None, st) == _lib.E_STATE
-        assert lib.ksched_eval_device_pitched(e._h, 5, vp(cpu), vp(cpu), vp(sel), None, vp(smp), 3, f | COMBINE_OR | PICK_UNIFORM, vp(M), None, vp(B), 2, st) == _lib.E_STATE
-        with pytest.raises(KschedError) as err:
-            e.eval(np.zeros(5, np.int64), np.zeros(5, np.int64), None, None, None, f)
-        assert err.value.code == _lib.E_STATE
-        # n == 0: the mask is left alone, every pod of a pick gets -1
-        e.set_nodes(np.zeros(0, np.int64), np.zeros(0, np.int64))
-        for comb in (0, COMBINE_OR):
-            B.fill_(-7)
-            assert lib.ksched_eval_device_pitched(e._h, 5, vp(cpu), vp(cpu), vp(sel), None, vp(smp), 3, f | comb | PICK_UNIFORM, vp(M), None, vp(B), 2, st) == _lib.OK
-            torch.cuda.synchronize()
-            assert (M == 0x5A).all() and (B == -1).all()
-        # p == 0: a no-op
-        e.set_nodes(np.zeros(70, np.int64), np.zeros(70, np.int64), np.ones((2, 70), np.uint32))
-        B.fill_(-7)
-        assert lib.ksched_eval_device_pitched(e._h, 0, vp(cpu), vp(cpu), vp(sel), None, vp(smp), 3, f | PICK_UNIFORM, vp(M), None, vp(B), 2, st) == _lib.OK
-        assert lib.ksched_eval_device_pitched(e._h, 0, None, None, None, None, None, 0, f, vp(M), None, None, 2, st) == _lib.OK
-        torch.cuda.synchronize()
-        assert (M == 0x5A).all() and (B == -7).all()
-        r = e.eval(np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((3, 2, 0), np.uint32), None, None, f)
-        assert r.feasible.shape == (0, 2)
-        # and the smallest call that does something: one pod, three terms of EQ 1 on nodes that all carry id 1
-        r = e.eval(np.zeros(1, np.int64), np.zeros(1, np.int64), np.ones((3, 2, 1), np.uint32), None, None, f)
+    def smallest(e):
+        """the smallest call that does something: one pod, three terms of EQ 1 on nodes that all carry id 1"""
+        r = e.eval(np.zeros(1, np.int64), np.zeros(1, np.int64), np.ones((3, 2, 1), np.uint32), None, None, F(3))
         assert r.feasible.tolist() == [[0xFFFFFFFFFFFFFFFF, 0x3F]] and e.last_kernel == "selterms"
-    finally:
-        e.close()
+    selector_calls.edge_sizes(call(3), COMBINE_OR, smallest)
